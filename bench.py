@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the tiled-YOLO detect path on MI355X (driver contract: one JSON line on stdout from rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config s16k|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config s16k|c5] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+(--dump-outputs), the result line.  --full adds everything else the line has carried: hipEvents around every launch of the last
+timed step (forward_kernels, roofline, roofline_hbm), the dominant kernel timed alone, a second (warm) ingest, the same workload
+in the fp16x3 parity context (parity_mode) and the CPU oracle's rate (cpu_baseline).
+--dump-outputs DIR: rank 0 writes what the last timed step returned to its caller, DIR/catalog.npy (the final catalog records,
+[M, 8] float64, as TileEngine.merged_records returns them) and DIR/tile_stats.npy (float64: tiles, skipped tiles, per-tile
+detections, degenerate boxes, candidate-overflow tiles).  Inputs are seeded, so equal arguments give equal inputs.
 
 With N > 1 and no WORLD_SIZE in the environment this process only spawns the ranks (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`, one process per GPU over RCCL; it replaces
@@ -58,12 +66,17 @@ def parse_args(argv=None):
                     help="seeded:<scale>:<nc> = YOLOv8 (default: yolov8l nc=5, the headline), seeded11:<scale>:<nc> = YOLO11 (SURVEY 8 f3; "
                          "reported under its own metric name); random-init either way: no trained weights ship with the reference")
     ap.add_argument("--precision", default="fp16", help="context precision of the headline run: fp16 | fp16x3 | fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch profile and roofline figures, the dominant kernel alone, the warm ingest, "
+                         "the fp16x3 parity pass and the CPU baseline (each can be switched off by the --no-* options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's catalog and tile stats as DIR/catalog.npy and DIR/tile_stats.npy (float64)")
     ap.add_argument("--parity-steps", type=int, default=-1,
                     help="timed passes of the same workload in the fp16x3 parity context after the headline run (reported as "
-                         "`parity_mode`; default: 1 when the headline is fp16, else 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-launch hipEvents in the timed region")
-    ap.add_argument("--no-exclusive", action="store_true", help="skip the extra forward passes after the timed region that time the dominant kernel alone (roofline.achieved_exclusive)")
+                         "`parity_mode`; default: 1 with --full when the headline is fp16, else 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not record per-launch hipEvents in the timed region")
+    ap.add_argument("--no-exclusive", action="store_true", help="with --full: skip the extra forward passes after the timed region that time the dominant kernel alone (roofline.achieved_exclusive)")
     ap.add_argument("--dry-run", action="store_true",
                     help="ranks only rendezvous, partition the grid and run the (empty) all-gather on CPU tensors: exercises the "
                          "launch path on a box without GPUs (tests/test_bench_spawn.py)")
@@ -167,6 +180,24 @@ def catalog_digest(cat):
     import hashlib
     import numpy as np
     return hashlib.sha1(np.ascontiguousarray(np.asarray(cat, np.float64)).tobytes()).hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, cat, stats):
+    """--dump-outputs: the catalog records of the last timed step (float64, catalog order) and its tile stats.  A catalog above
+    the size limit is written as a fixed sample of its rows (seed 0, catalog order kept)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cat = np.ascontiguousarray(np.asarray(cat, np.float64).reshape(-1, 8))
+    max_rows = (DUMP_LIMIT_BYTES - 4096) // cat[:1].nbytes if len(cat) else 0
+    if len(cat) > max_rows:
+        log("bench: catalog of %d rows sampled to %d for --dump-outputs" % (len(cat), max_rows))
+        cat = cat[np.sort(np.random.default_rng(0).choice(len(cat), max_rows, replace=False))]
+    np.save(os.path.join(out_dir, "catalog.npy"), cat)
+    np.save(os.path.join(out_dir, "tile_stats.npy"),
+            np.array([stats[k] for k in ("tiles", "skipped", "per_tile_detections", "degenerate_boxes", "cand_overflow_tiles")], np.float64))
 
 
 def kernel_family(n):
@@ -353,14 +384,16 @@ def run_rank(args):
         return m, d, en, sr, 1000.0 * (time.time() - t_in)
 
     model, det, eng, src, ms_ingest = make_engine(args.precision, batch)
-    # the same ingest once more: the first one also pays for the allocations (pinned staging buffers, the device buffer of the
-    # band) that a process ingesting one mosaic after the other pays once
-    t_in = time.time()
-    src_w = MosaicSource(utils.read_fits_image(fits_path)[0], big_endian=True)
-    eng_w = TileEngine(det, src_w, grid, cfg, wl["imgsz"], 0.7, 0.5, 0.3, 0.8, rank, world, batch)
-    torch.cuda.synchronize()
-    ms_ingest_warm = 1000.0 * (time.time() - t_in)
-    del eng_w, src_w
+    ms_ingest_warm = None
+    if args.full:
+        # the same ingest once more: the first one also pays for the allocations (pinned staging buffers, the device buffer of the
+        # band) that a process ingesting one mosaic after the other pays once
+        t_in = time.time()
+        src_w = MosaicSource(utils.read_fits_image(fits_path)[0], big_endian=True)
+        eng_w = TileEngine(det, src_w, grid, cfg, wl["imgsz"], 0.7, 0.5, 0.3, 0.8, rank, world, batch)
+        torch.cuda.synchronize()
+        ms_ingest_warm = 1000.0 * (time.time() - t_in)
+        del eng_w, src_w
     if rank == 0:
         log("setup %.1f s: %d tiles, %d ranks, %d tiles on rank 0, ingest %.1f ms (%.1f MB on device)" % (
             time.time() - t_setup, len(grid), world, eng.n_my, ms_ingest, src.bytes_uploaded / 1e6))
@@ -399,16 +432,19 @@ def run_rank(args):
         tsplit[k] = 0.0
     if world > 1:
         dist.barrier()
+    profiled = args.full and not args.no_profile
     torch.cuda.synchronize()
     t0 = time.time()
     for k in range(args.steps):
-        if k == args.steps - 1 and not args.no_profile:
+        if k == args.steps - 1 and profiled:
             det.profile(1)               # hipEvents around EVERY launch of the last timed step (all batches, both lanes): ~3 % of that step
         cat, stats = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.time() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, cat, stats)
     per_rank = None
     if world > 1:
         cpu = dist.get_backend() != "nccl"
@@ -422,8 +458,8 @@ def run_rank(args):
         per_rank = [[float(v) for v in t.cpu()] for t in allr]
     # main lane (the full batches on the launch stream: 95 % of the tiles) and all launches incl. the small-batch lane, whose
     # kernels run on their own stream BESIDE the main lane's (their event times and the main lane's overlap)
-    prof = det.profile_summary(0) if not args.no_profile else None
-    prof_all = {p["kernel"]: p for p in det.profile_summary(-1) if p["launches"]} if not args.no_profile else None
+    prof = det.profile_summary(0) if profiled else None
+    prof_all = {p["kernel"]: p for p in det.profile_summary(-1) if p["launches"]} if profiled else None
     det.profile(False)
     # beside the in-situ figure: the same kernels timed with the GPU to themselves (one full batch through cy_forward on the
     # launch stream, no preprocessing / post-processing / second batch beside it), after the timed region
@@ -444,7 +480,7 @@ def run_rank(args):
     tsplit_main = dict(tsplit)                               # (the parity passes below go through the same step())
     # ---- the same workload in the parity context (fp16x3: the mode that meets the north star's parity bar), same timing protocol
     parity = None
-    psteps = args.parity_steps if args.parity_steps >= 0 else (1 if args.precision == "fp16" else 0)
+    psteps = args.parity_steps if args.parity_steps >= 0 else (1 if args.full and args.precision == "fp16" else 0)
     if psteps > 0:
         del eng
         pb = min(batch, 128)                                   # 4 bytes per activation value: 128 tiles keep every tensor below 4 GiB
@@ -536,8 +572,9 @@ def run_rank(args):
             # host-inclusive view (never `value`): FITS memory map -> H2D of this rank's regions -> on-device byte swap
             "ms_ingest": ms_in, "ingest_mb_rank0": src.bytes_uploaded / 1e6,
             "tiles_per_s_incl_ingest": ntiles / ((ms_step + ms_in) * 1e-3),
-            "ms_ingest_warm_rank0": ms_ingest_warm,     # second ingest of the same file in this process (buffers already allocated)
-            "tiles_per_s_incl_ingest_warm": ntiles / ((ms_step + ms_ingest_warm) * 1e-3) if world == 1 else None,
+            "ms_ingest_warm_rank0": ms_ingest_warm,     # --full: second ingest of the same file in this process (buffers already allocated)
+            "tiles_per_s_incl_ingest_warm": ntiles / ((ms_step + ms_ingest_warm) * 1e-3) if world == 1 and ms_ingest_warm is not None else None,
+            "full": args.full,
         }
         if parity:
             out["parity_mode"] = parity
@@ -615,7 +652,7 @@ def run_rank(args):
                                        "share_of_forward": p["ms"] / tot_ms if tot_ms else 0.0} for p in prof]
             out["profiled_forward_share_of_step"] = tot_ms / ms_step if ms_step > 0 else None   # > 1 is possible: the small-batch lane runs beside the main lane
             out["profiled_steps"] = 1
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if y11:
                 _g, wd = W.seeded11_folded(wparts[1], int(wparts[2]), int(wparts[3]) if len(wparts) > 3 else 11)
                 scale, names = wparts[1], model.names
@@ -639,6 +676,9 @@ def main():
     args = parse_args(argv)
     if args.gpus < 1:
         log("--gpus must be >= 1")
+        return 2
+    if args.steps < 1 and not args.dry_run:
+        log("--steps must be >= 1")
         return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args, argv)

@@ -43,3 +43,9 @@ def test_single_rank_dry_run():
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads(p.stdout.strip())
     assert out["n_gpus"] == 1 and out["tiles_per_rank"] == [1600]
+
+
+def test_steps_below_one_is_refused():
+    p = _run("--steps", "0")
+    assert p.returncode == 2 and "--steps" in p.stderr
+    assert not p.stdout.strip()

@@ -135,10 +135,11 @@ def test_analyzer_plot_and_preprocessed_fits(tmp_path, monkeypatch):
     assert reg[1] == "image" and len(reg) == 2 + len(an.bboxes_final)
 
 
-def test_analyzer_predict_three_channel_array():
+def test_analyzer_predict_three_channel_array(tmp_path, monkeypatch):
     """Analyzer.predict on a caller-supplied (H,W,3) array whose channels DIFFER (caesar_yolo/evaluation.py:146-154 takes a 3-D image as
     is): each plane through its channel's program on the device, the cube through the model call -- against the oracle pipeline on
     the same cube.  Also: a cube whose first rows are constant is rejected by the row check (:171-176)."""
+    monkeypatch.chdir(tmp_path)                                   # the default config saves out_<image_id>.json / .reg in the cwd
     from caesar_yolo_amd.model import YOLO
     from caesar_yolo_amd.evaluation import Analyzer
     from caesar_yolo_amd.config import CONFIG

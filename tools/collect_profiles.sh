@@ -1,15 +1,15 @@
 #!/bin/bash
 # Round profile collection on the GPU box (run through gpurun from the repo root).  Writes raw rocprofv3 output under
 # gpurun_out/<tag>_<name>_*; tools/summarize_profiles.py <tag> <name> turns it into the tracked files under profiles/.
-# usage: tools/collect_profiles.sh <tag> [final|c5|y11]      final = default `python bench.py` (S16k, yolov8l), c5 = --config c5,
+# usage: tools/collect_profiles.sh <tag> [final|c5|y11]      final = `python bench.py --full` (S16k, yolov8l), c5 = --config c5,
 #                                                             y11 = --weights seeded11:l:5 (YOLO11l on the S16k workload)
 set -e
 TAG=${1:-r04}
 NAME=${2:-final}
 case $NAME in
-  final) ARGS="" ;;
-  c5)    ARGS="--config c5" ;;
-  y11)   ARGS="--weights seeded11:l:5" ;;
+  final) ARGS="--full" ;;
+  c5)    ARGS="--full --config c5" ;;
+  y11)   ARGS="--full --weights seeded11:l:5" ;;
   *) echo "unknown profile set $NAME"; exit 2 ;;
 esac
 cd /tmp && export TMPDIR=/tmp

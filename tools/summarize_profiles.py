@@ -4,7 +4,7 @@ import csv, glob, json, os, sys, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 name = sys.argv[2] if len(sys.argv) > 2 else "final"
-CMD = {"final": "python bench.py", "c5": "python bench.py --config c5", "y11": "python bench.py --weights seeded11:l:5"}[name]
+CMD = {"final": "python bench.py --full", "c5": "python bench.py --full --config c5", "y11": "python bench.py --full --weights seeded11:l:5"}[name]
 raw, trk = tag + "_" + name, tag + "_" + name          # prefixes under gpurun_out/ and profiles/
 G = os.path.join(ROOT, "gpurun_out")
 P = os.path.join(ROOT, "profiles")

@@ -73,6 +73,39 @@ int fail(cy_ctx* c, int code, const std::string& m) { if (c) c->err = m; g_err =
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline size_t esize(Precision p) { return p == PREC_F16 ? 2 : 4; }      // bytes per activation value (fp16x3: two fp16 halves)
 inline Precision io_prec(Precision p) { return p == PREC_F16X3 ? PREC_F32 : p; }   // type of the network input buffer
+// depth-wise 3x3 filter [C][1][3][3] -> the [9][C] fp32 layout of dwconv3x3_kernel (weight loader, test entry cy_dwconv3x3)
+std::vector<float> dw_weights(const float* W, int C) {
+    std::vector<float> dw(9 * (size_t)C);
+    for (int ch = 0; ch < C; ++ch) for (int t = 0; t < 9; ++t) dw[(size_t)t * C + ch] = W[(size_t)ch * 9 + t];
+    return dw;
+}
+const char* const ATTN_TOO_LARGE = "attention map too large for this kernel (stride-32 map of the input must have <= 10240 pixels)";
+
+// Device scratch of one kernel-level test entry call, freed on every return path.  In the fp16x3 context the entries take fp32
+// [pix][ct] caller tensors and run the kernel on split copies [pix][2 ct] (high halves, then the low halves ct behind: the forward's
+// layout, channel offsets included); split() makes such a copy, the caller merges the written one back with launch_x3_merge.
+struct EntryScratch {
+    std::vector<void*> p;
+    ~EntryScratch() { for (void* q : p) hipFree(q); }
+    hipError_t alloc(size_t bytes, void** out) {
+        *out = nullptr;
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+    hipError_t split(const void* t, long npix, int ct, void** out, hipStream_t s) {
+        hipError_t e = alloc((size_t)npix * ct * 4, out);
+        return e == hipSuccess ? launch_x3_split(reinterpret_cast<const float*>(t), *out, npix, ct, s) : e;
+    }
+};
+// synchronise, then report the first error of the call (as cy_conv_bn_silu)
+int entry_done(cy_ctx* c, hipError_t e, hipStream_t s) {
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
+    return CY_OK;
+}
+inline bool ch8(int v) { return v >= 0 && v % 8 == 0; }     // channel offset / stride usable by the 8-channel vector accesses
 
 int py_round_half_even(double x) {
     double f = std::floor(x), d = x - f;
@@ -316,8 +349,7 @@ int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
         HIPCHK(c, hipMemcpy(dc.bias, bias.data(), 4 * cp, hipMemcpyHostToDevice));
         if (groups > 1) {   // depth-wise 3x3 (YOLO11): [9][C] fp32 for dwconv3x3_kernel
             if (groups != ci || co != ci || k != 3 || s != 1 || co % 8) return fail(c, CY_ERR_UNSUPPORTED, "only depth-wise 3x3 stride-1 grouped convs are supported: " + name);
-            std::vector<float> dw(9 * (size_t)co);
-            for (uint32_t ch = 0; ch < co; ++ch) for (int t = 0; t < 9; ++t) dw[(size_t)t * co + ch] = W[(size_t)ch * 9 + t];
+            const std::vector<float> dw = dw_weights(W, (int)co);
             HIPCHK(c, hipMalloc(&dc.dw_w, 4 * dw.size()));
             HIPCHK(c, hipMemcpy(dc.dw_w, dw.data(), 4 * dw.size(), hipMemcpyHostToDevice));
             continue;
@@ -778,7 +810,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             a.scale = 1.0f / sqrtf((float)a.kd);
             if (a.heads < 1 || ti.level != to.level) return fail(c, CY_ERR_STATE, "malformed attention op");
             hipError_t e = launch_attention(c->prec, a, s);
-            if (e == hipErrorInvalidValue) return fail(c, CY_ERR_UNSUPPORTED, "attention map too large for this kernel (stride-32 map of the input must have <= 10240 pixels)");
+            if (e == hipErrorInvalidValue) return fail(c, CY_ERR_UNSUPPORTED, ATTN_TOO_LARGE);
             HIPCHK(c, e);
             prof_done(CONV_NUM_VARIANTS + 3, 2.0 * Bn * a.heads * (double)a.N * a.N * (a.kd + a.hd));
         } else {
@@ -1059,6 +1091,107 @@ int cy_bottleneck64(cy_ctx* c, const void* d_in, int B, int H, int W, const floa
     if (e != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
     return CY_OK;
+}
+
+// ---- kernel-level test entries of the YOLO11 operators: one launch_dwconv / launch_attention / launch_pool5 with the argument
+// structs filled as the OPK_DWCONV / OPK_ATTN / OPK_POOL branches of the plan executor fill them
+int cy_dwconv3x3(cy_ctx* c, const void* d_in, int B, int H, int W, int C, int in_ct, int in_coff, const float* h_w, const float* h_b,
+                 int act, int blk, int gstride, int goff, const void* d_res, int res_ct, int res_coff, void* d_out, int out_ct,
+                 int out_coff, void* stream) {
+    if (!c || !d_in || !h_w || !h_b || !d_out) return fail(c, CY_ERR_ARG, "null argument");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8 || blk < 0) return fail(c, CY_ERR_ARG, "unsupported depth-wise geometry");
+    const int last = blk ? ((C - 1) / blk) * gstride + goff + (C - 1) % blk : C - 1;      // highest input channel read
+    if (!ch8(in_ct) || !ch8(in_coff) || !ch8(out_ct) || !ch8(out_coff) || !ch8(blk) || (blk && (!ch8(gstride) || !ch8(goff))) ||
+        in_coff + last >= in_ct || out_coff + C > out_ct || (d_res && (!ch8(res_ct) || !ch8(res_coff) || res_coff + C > res_ct)))
+        return fail(c, CY_ERR_ARG, "channel slice outside its tensor, or an offset / stride not a multiple of 8");
+    if (d_out == d_in || d_out == d_res) return fail(c, CY_ERR_ARG, "the output must not alias the input or the residual");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool x3 = c->prec == PREC_F16X3;
+    const int cm = x3 ? 2 : 1;
+    const long npix = (long)B * H * W;
+    const std::vector<float> dw = dw_weights(h_w, C);
+    EntryScratch sc;
+    void *wd = nullptr, *bd = nullptr, *in = const_cast<void*>(d_in), *res = const_cast<void*>(d_res), *out = d_out;
+    hipError_t e = sc.alloc(4 * dw.size(), &wd);
+    if (e == hipSuccess) e = sc.alloc(4 * (size_t)C, &bd);
+    if (e == hipSuccess) e = hipMemcpy(wd, dw.data(), 4 * dw.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(bd, h_b, 4 * (size_t)C, hipMemcpyHostToDevice);
+    if (e == hipSuccess && x3) e = sc.split(d_in, npix, in_ct, &in, st);
+    if (e == hipSuccess && x3 && d_res) e = sc.split(d_res, npix, res_ct, &res, st);
+    if (e == hipSuccess && x3) e = sc.split(d_out, npix, out_ct, &out, st);
+    if (e == hipSuccess) {
+        DwArgs a{};
+        a.in = in; a.in_ct = cm * in_ct; a.in_coff = in_coff; a.out = out; a.out_ct = cm * out_ct; a.out_coff = out_coff;
+        a.in_lo = in_ct; a.out_lo = out_ct;
+        if (d_res) { a.res = res; a.res_ct = cm * res_ct; a.res_coff = res_coff; a.res_lo = res_ct; }
+        a.w = reinterpret_cast<const float*>(wd); a.bias = reinterpret_cast<const float*>(bd);
+        a.B = B; a.H = H; a.W = W; a.C = C; a.act = act != 0;
+        a.blk = blk; a.gstride = gstride; a.goff = goff;
+        e = launch_dwconv(c->prec, a, st);
+    }
+    if (e == hipSuccess && x3) e = launch_x3_merge(out, reinterpret_cast<float*>(d_out), npix, out_ct, st);
+    return entry_done(c, e, st);
+}
+
+int cy_attention(cy_ctx* c, const void* d_qkv, int B, int N, int ct, int coff, int heads, int kd, int hd, void* d_out, int out_ct,
+                 int out_coff, void* stream) {
+    if (!c || !d_qkv || !d_out) return fail(c, CY_ERR_ARG, "null argument");
+    if (B < 1 || N < 1 || heads < 1 || kd < 1 || kd > 64 || hd < 1) return fail(c, CY_ERR_ARG, "unsupported attention geometry");
+    if (coff < 0 || coff + heads * (2 * kd + hd) > ct || out_coff < 0 || out_coff + heads * hd > out_ct)
+        return fail(c, CY_ERR_ARG, "channel slice outside its tensor");
+    if (d_out == d_qkv) return fail(c, CY_ERR_ARG, "the output must not alias the input");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool x3 = c->prec == PREC_F16X3;
+    const int cm = x3 ? 2 : 1;
+    const long npix = (long)B * N;
+    EntryScratch sc;
+    void *qkv = const_cast<void*>(d_qkv), *out = d_out;
+    hipError_t e = hipSuccess;
+    if (x3) e = sc.split(d_qkv, npix, ct, &qkv, st);
+    if (e == hipSuccess && x3) e = sc.split(d_out, npix, out_ct, &out, st);
+    if (e == hipSuccess) {
+        AttnArgs a{};
+        a.qkv = qkv; a.ct = cm * ct; a.coff = coff; a.out = out; a.out_ct = cm * out_ct; a.out_coff = out_coff;
+        a.lo = ct; a.out_lo = out_ct;
+        a.B = B; a.N = N; a.heads = heads; a.kd = kd; a.hd = hd;
+        a.scale = 1.0f / sqrtf((float)a.kd);
+        e = launch_attention(c->prec, a, st);
+        if (e == hipErrorInvalidValue) {
+            entry_done(c, hipSuccess, st);
+            return fail(c, CY_ERR_UNSUPPORTED, ATTN_TOO_LARGE);
+        }
+    }
+    if (e == hipSuccess && x3) e = launch_x3_merge(out, reinterpret_cast<float*>(d_out), npix, out_ct, st);
+    return entry_done(c, e, st);
+}
+
+int cy_maxpool5(cy_ctx* c, const void* d_src, int B, int H, int W, int C, int ct, int src_coff, void* d_dst, int dst_coff,
+                void* stream) {
+    if (!c || !d_src || !d_dst) return fail(c, CY_ERR_ARG, "null argument");
+    if (B < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail(c, CY_ERR_ARG, "unsupported pool geometry");
+    if (!ch8(ct) || !ch8(src_coff) || !ch8(dst_coff) || src_coff + C > ct || dst_coff + C > ct)
+        return fail(c, CY_ERR_ARG, "channel slice outside its tensor, or an offset / stride not a multiple of 8");
+    if (d_src == d_dst && src_coff < dst_coff + C && dst_coff < src_coff + C) return fail(c, CY_ERR_ARG, "overlapping source and destination slices");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool x3 = c->prec == PREC_F16X3;
+    const int cm = x3 ? 2 : 1;
+    const long npix = (long)B * H * W;
+    EntryScratch sc;
+    void *src = const_cast<void*>(d_src), *dst = d_dst;
+    hipError_t e = hipSuccess;
+    if (x3) e = sc.split(d_dst, npix, ct, &dst, st);
+    if (e == hipSuccess && x3) { if (d_src == d_dst) src = dst; else e = sc.split(d_src, npix, ct, &src, st); }   // SPPF: one buffer
+    if (e == hipSuccess) {
+        PoolArgs a{};
+        a.src = src; a.dst = dst; a.ct = cm * ct; a.src_coff = src_coff; a.dst_coff = dst_coff; a.lo = x3 ? ct : 0;
+        a.C = C; a.B = B; a.H = H; a.W = W;
+        e = launch_pool5(c->prec, a, st);
+    }
+    if (e == hipSuccess && x3) e = launch_x3_merge(dst, reinterpret_cast<float*>(d_dst), npix, ct, st);
+    return entry_done(c, e, st);
 }
 
 int cy_debug_stamps(unsigned long long* out8, int reset) {

@@ -316,6 +316,36 @@ class HipDetector(object):
                                            self._p(out), self._stream()))
         return out
 
+    # kernel-level test entries of the YOLO11 / SPPF operators: NHWC tensors [B,H,W,ct] of the context dtype, the op on channel
+    # slices of them (the forward's layout); the output tensor is written in place (channels outside its slice untouched)
+    def dwconv3x3(self, x, nch, w, b, out, in_coff=0, out_coff=0, act=True, res=None, res_coff=0, chmap=(0, 0, 0)):
+        """Depth-wise 3x3 (+SiLU)(+residual): out[..., out_coff:out_coff+nch] from x through chmap = (blk, gstride, goff)
+        (blk = 0: input channel in_coff + c); w [C,1,3,3], b [C]."""
+        B, H, Wd, in_ct = x.shape
+        w = np.ascontiguousarray(w, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        self._chk(self.lib.cy_dwconv3x3(self.ctx, self._p(x), B, H, Wd, int(nch), in_ct, int(in_coff),
+                                        w.ctypes.data_as(C.POINTER(C.c_float)), b.ctypes.data_as(C.POINTER(C.c_float)),
+                                        int(bool(act)), int(chmap[0]), int(chmap[1]), int(chmap[2]),
+                                        self._p(res) if res is not None else None, res.shape[-1] if res is not None else 0,
+                                        int(res_coff), self._p(out), out.shape[-1], int(out_coff), self._stream()))
+        return out
+
+    def attention(self, qkv, heads, kd, hd, out, coff=0, out_coff=0):
+        """C2PSA attention core: qkv [B,N,ct] with per-head [q kd | k kd | v hd] blocks from channel coff on -> out[..., out_coff:]."""
+        B, N, ct = qkv.shape
+        self._chk(self.lib.cy_attention(self.ctx, self._p(qkv), B, N, ct, int(coff), int(heads), int(kd), int(hd), self._p(out),
+                                        out.shape[-1], int(out_coff), self._stream()))
+        return out
+
+    def maxpool5(self, src, nch, dst, src_coff=0, dst_coff=0):
+        """MaxPool2d(5, 1, 2) of src[..., src_coff:src_coff+nch] into dst[..., dst_coff:]; dst may be src (SPPF, disjoint slices)."""
+        B, H, Wd, ct = src.shape
+        assert tuple(dst.shape) == tuple(src.shape)
+        self._chk(self.lib.cy_maxpool5(self.ctx, self._p(src), B, H, Wd, int(nch), ct, int(src_coff), self._p(dst), int(dst_coff),
+                                       self._stream()))
+        return dst
+
 
 class _Boxes(object):
     def __init__(self, det):

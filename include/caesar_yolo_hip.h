@@ -28,8 +28,8 @@ enum cy_status { CY_OK = 0, CY_ERR_ARG = -1, CY_ERR_HIP = -2, CY_ERR_IO = -3, CY
  * every product evaluated as hi*hi + lo*hi + hi*lo on the fp16 matrix cores with fp32 accumulation (3x the K of CY_F16).
  * Range: in CY_F16 and CY_F16X3 an activation is stored through an fp16 high half, so |activation| must stay below 65504 (beyond
  * that the value becomes inf; only CY_F32 has the fp32 range).  Weights have no such limit (scaled per output channel).
- * Buffers the caller hands to cy_forward / cy_preproc / cy_letterbox_pack / cy_conv_bn_silu are fp32 in the CY_F32 and CY_F16X3
- * contexts and fp16 in CY_F16. */
+ * Buffers the caller hands to cy_forward / cy_preproc / cy_letterbox_pack / cy_conv_bn_silu and the other kernel-level test
+ * entries are fp32 in the CY_F32 and CY_F16X3 contexts and fp16 in CY_F16. */
 enum cy_precision { CY_F16 = 0, CY_F32 = 1, CY_F16X3 = 2 };
 
 #define CY_MAX_DET 300        /* ultralytics max_det */
@@ -195,6 +195,25 @@ int cy_conv_bn_silu(cy_ctx* ctx, const void* d_in, int B, int Hi, int Wi, int Ci
  * h_w1, h_w2 [64][64][3][3], h_b1, h_b2 [64] fp32 */
 int cy_bottleneck64(cy_ctx* ctx, const void* d_in, int B, int H, int W, const float* h_w1, const float* h_b1,
                     const float* h_w2, const float* h_b2, int shortcut, void* d_out, void* stream);
+
+/* kernel-level test entries of the YOLO11 / SPPF operators: one launch of the kernel the forward runs for that op, on channel slices
+ * of caller NHWC tensors [pix][ct] in the context precision (fp32 in CY_F16X3: split into high / low halves, run, merged back, as
+ * the forward stores them).  Synchronous on `stream`.
+ * cy_dwconv3x3: out[., c] = act(sum_{3x3} in[., map(c)] * w + b[c]) (+ res[., c]), zero padding, stride 1; h_w [C][1][3][3],
+ *   h_b [C] fp32; map(c) = c (blk = 0) or (c / blk) * gstride + goff + c % blk (the C2PSA positional-encoding conv reading v
+ *   out of qkv).  C, every ct / coff and blk / gstride / goff are multiples of 8; d_res may be null.
+ * cy_attention: per head h, out[b][n][out_coff + h*hd + c] = sum_m softmax_m(q_n . k_m * kd^-0.5) v_m[c] over the per-head
+ *   [q kd | k kd | v hd] channel blocks of d_qkv [B][N][ct] starting at coff; kd <= 64.  N above 10240 (the per-query kernel's
+ *   LDS) -> CY_ERR_UNSUPPORTED, nothing launched.
+ * cy_maxpool5: MaxPool2d(5, 1, 2) with -inf padding, slice src_coff -> slice dst_coff of [B][H][W][ct] tensors; d_src and d_dst
+ *   may be the same buffer (SPPF) with disjoint slices.  C, ct and the offsets are multiples of 8. */
+int cy_dwconv3x3(cy_ctx* ctx, const void* d_in, int B, int H, int W, int C, int in_ct, int in_coff, const float* h_w,
+                 const float* h_b, int act, int blk, int gstride, int goff, const void* d_res, int res_ct, int res_coff,
+                 void* d_out, int out_ct, int out_coff, void* stream);
+int cy_attention(cy_ctx* ctx, const void* d_qkv, int B, int N, int ct, int coff, int heads, int kd, int hd, void* d_out,
+                 int out_ct, int out_coff, void* stream);
+int cy_maxpool5(cy_ctx* ctx, const void* d_src, int B, int H, int W, int C, int ct, int src_coff, void* d_dst, int dst_coff,
+                void* stream);
 
 /* ---- catalog records and cross-tile merge (host code, no GPU) --------------------------------- */
 /* Analyzer.make_json_results (caesar_yolo/evaluation.py:418-469: int() truncation, tile-local edge rule, tile origin)

@@ -15,20 +15,18 @@ TAPS = ["model.1", "model.2.cv2", "model.9.cv2", "model.10.cv2", "model.13.cv2",
         "model.23.cv3.0.0.0", "model.23.cv3.1.1.1"]
 
 
-@pytest.mark.parametrize("scale,prec,tol_raw,tol_tap", [("n", "fp32", 2e-4, 1e-4), ("n", "fp16", 6e-2, 3e-2), ("n", "fp16x3", 2e-4, 1e-4),
-                                                        ("l", "fp32", 2e-4, 1e-4), ("l", "fp16", 6e-2, 3e-2), ("l", "fp16x3", 2e-4, 1e-4)])
-def test_yolo11_forward_matches_oracle(tmp_path, scale, prec, tol_raw, tol_tap):
-    from caesar_yolo_amd import weights as W
+def _forward_vs_oracle(tmp_path, scale, prec, tol_raw, tol_tap, B, H, W):
+    from caesar_yolo_amd import weights as W_
     from caesar_yolo_amd.model import HipDetector
     from oracle import yolo11_ref as O
     nc = 3
     g, wd = seeded_folded(scale, nc)
     path = str(tmp_path / ("y11%s.cyw" % scale))
-    W.write_cyw2(path, g, [(cs, wd[cs.name][0], wd[cs.name][1]) for cs in g.convs], {0: "a", 1: "b", 2: "c"})
-    assert W.read_cyw_header(path) == (scale, {0: "a", 1: "b", 2: "c"}, nc, len(g.convs))
-    det = HipDetector(path, device=0, precision=prec, max_batch=2, max_imgsz=256)
+    W_.write_cyw2(path, g, [(cs, wd[cs.name][0], wd[cs.name][1]) for cs in g.convs], {0: "a", 1: "b", 2: "c"})
+    assert W_.read_cyw_header(path) == (scale, {0: "a", 1: "b", 2: "c"}, nc, len(g.convs))
+    det = HipDetector(path, device=0, precision=prec, max_batch=B, max_imgsz=max(256, H, W))
     rng = np.random.default_rng(5)
-    x = torch.from_numpy(rng.uniform(0, 1, (2, 3, 256, 192)).astype(np.float32))
+    x = torch.from_numpy(rng.uniform(0, 1, (B, 3, H, W)).astype(np.float32))
     if prec == "fp16":
         wd = {k: (v[0].astype(np.float16).astype(np.float32), v[1]) for k, v in wd.items()}
         x = x.half().float()
@@ -48,7 +46,26 @@ def test_yolo11_forward_matches_oracle(tmp_path, scale, prec, tol_raw, tol_tap):
         err = float((got - ref).abs().max())
         assert err <= tol_tap * sc, "%s: max abs err %.3e (scale %.2f)" % (name, err, sc)
     err = float((pred.cpu() - raw).abs().max())
-    assert err <= tol_raw * max(1.0, float(raw.abs().max())), "raw head output: max abs err %.3e" % err
+    sc = max(1.0, float(raw.abs().max()))
+    print("yolo11%s %s B%d %dx%d: raw head output max abs err %.3e (scale %.2f)" % (scale, prec, B, H, W, err, sc))
+    assert err <= tol_raw * sc, "raw head output: max abs err %.3e" % err
+    det.close()
+
+
+@pytest.mark.parametrize("scale,prec,tol_raw,tol_tap", [("n", "fp32", 2e-4, 1e-4), ("n", "fp16", 6e-2, 3e-2), ("n", "fp16x3", 2e-4, 1e-4),
+                                                        ("l", "fp32", 2e-4, 1e-4), ("l", "fp16", 6e-2, 3e-2), ("l", "fp16x3", 2e-4, 1e-4)])
+def test_yolo11_forward_matches_oracle(tmp_path, scale, prec, tol_raw, tol_tap):
+    _forward_vs_oracle(tmp_path, scale, prec, tol_raw, tol_tap, 2, 256, 192)
+
+
+# input sizes whose stride-32 maps reach the other attention code paths (the 256x192 cases above: 48 tokens)
+@pytest.mark.parametrize("prec", ["fp32", "fp16x3"])
+@pytest.mark.parametrize("H,W,scale,B", [(512, 512, "l", 2),        # 256 tokens: one query per thread of the fast kernel
+                                         (640, 640, "l", 1),        # 400 tokens: its two-query loop (the 640-px tile)
+                                         (640, 512, "n", 1),        # 320 tokens: ragged
+                                         (1024, 1024, "n", 1)])     # 1024 tokens: the per-query kernel
+def test_yolo11_forward_matches_oracle_attention_paths(tmp_path, prec, H, W, scale, B):
+    _forward_vs_oracle(tmp_path, scale, prec, 2e-4, 1e-4, B, H, W)
 
 
 def test_seeded_yolo11_weights_of_the_benchmark():
@@ -75,31 +92,40 @@ def test_seeded_yolo11_weights_of_the_benchmark():
     det.close()
 
 
-def test_yolo11_model_call_end_to_end(tmp_path):
-    """The reference-shaped model call (`YOLO(weights)(image, imgsz=, conf=, iou=)`, caesar_yolo/evaluation.py:181-193) with a
-    YOLO11 weight file: LetterBox -> network -> decode -> NMS -> scale_boxes on the GPU (f32 context) against the oracle
-    (oracle/yolo11_ref.Net11 + the shared decode/NMS of oracle/yolov8_ref.py)."""
+def _model_call_vs_oracle(tmp_path, prec, imgsz, hw, cls_bias):
     from caesar_yolo_amd import weights as W
     from caesar_yolo_amd.model import YOLO
     from oracle import yolo11_ref as O
     from oracle import yolov8_ref as Y
     nc, names = 3, {0: "a", 1: "b", 2: "c"}
-    g, wd = seeded_folded("n", nc, cls_bias=-1.5)
+    g, wd = seeded_folded("n", nc, cls_bias=cls_bias)
     path = str(tmp_path / "y11n.cyw")
     W.write_cyw2(path, g, [(cs, wd[cs.name][0], wd[cs.name][1]) for cs in g.convs], names)
-    model = YOLO(path, precision="fp32", max_batch=1, max_imgsz=256, device=0)
+    model = YOLO(path, precision=prec, max_batch=1, max_imgsz=imgsz, device=0)
     assert model.names == names and model.scale == "n"
     oracle = Y.OracleYOLO(None, names, net=O.Net11(wd, "n", nc))
     rng = np.random.default_rng(3)
-    img = rng.uniform(0, 255, (200, 230, 3))
-    got = model(img, imgsz=256, conf=0.3, iou=0.5)[0]
-    ref = oracle(img, imgsz=256, conf=0.3, iou=0.5)[0]
+    img = rng.uniform(0, 255, hw + (3,))
+    got = model(img, imgsz=imgsz, conf=0.3, iou=0.5)[0]
+    ref = oracle(img, imgsz=imgsz, conf=0.3, iou=0.5)[0]
     n = len(ref.boxes.conf)
     assert 3 <= n <= 300, n
     assert len(got.boxes.conf) == n
     np.testing.assert_array_equal(got.boxes.cls.cpu().numpy().astype(int), ref.boxes.cls.numpy().astype(int))
     np.testing.assert_allclose(got.boxes.conf.cpu().numpy(), ref.boxes.conf.numpy(), atol=1e-4)
-    np.testing.assert_allclose(got.boxes.xyxy.cpu().numpy(), ref.boxes.xyxy.numpy(), atol=256 * 1e-4)
+    np.testing.assert_allclose(got.boxes.xyxy.cpu().numpy(), ref.boxes.xyxy.numpy(), atol=imgsz * 1e-4)
+
+
+def test_yolo11_model_call_end_to_end(tmp_path):
+    """The reference-shaped model call (`YOLO(weights)(image, imgsz=, conf=, iou=)`, caesar_yolo/evaluation.py:181-193) with a
+    YOLO11 weight file: LetterBox -> network -> decode -> NMS -> scale_boxes on the GPU (f32 context) against the oracle
+    (oracle/yolo11_ref.Net11 + the shared decode/NMS of oracle/yolov8_ref.py)."""
+    _model_call_vs_oracle(tmp_path, "fp32", 256, (200, 230), -1.5)
+
+
+def test_yolo11_model_call_end_to_end_640(tmp_path):
+    """The same call at imgsz 640 in the fp16x3 context (400-token attention: the fast kernel's two-query loop)."""
+    _model_call_vs_oracle(tmp_path, "fp16x3", 640, (600, 520), -1.5)
 
 
 def test_yolo11_tile_path(tmp_path):

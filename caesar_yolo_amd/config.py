@@ -29,4 +29,5 @@ CONFIG = {
     # NEW: HIP tile pipeline
     'tile_batch': 64,                  # tiles per kernel launch sequence
     'precision': 'fp16x3',             # 'fp16x3' (default: parity context), 'fp32' (exact fp32, ~2.7x slower), 'fp16' (throughput, ~3x faster)
+    'augment': False,                  # test-time augmentation of every model call (ultralytics augment=True: 3 views, joint NMS)
 }

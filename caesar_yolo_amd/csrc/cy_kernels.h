@@ -221,4 +221,33 @@ hipError_t launch_preproc_planes(const PreArgs& a, hipStream_t s);    // statist
 hipError_t launch_letterbox_pack(const PreArgs& a, hipStream_t s);   // uses scratch/th/tw/new_*/H/W/top/left/out only
 hipError_t launch_mosaic_prepare(float* data, size_t n, int big_endian, hipStream_t s);
 
+// ---- test-time augmentation (ultralytics DetectionModel._predict_augment) ------------------------
+// Views of a letterboxed batch: bilinear resize (torch upsample_bilinear2d, align_corners=False) of the (optionally left-right
+// flipped) fp32 source to ch x cw, right / bottom padding with 0.447 up to Hp x Wp, NHWC4 in the context's input type.
+struct AugView {
+    void* out;                     // [B][Hp][Wp][4]
+    int ch, cw, Hp, Wp;            // content size (int(H * s), int(W * s)), padded size (multiple of 32)
+    int flip;                      // 1: x.flip(3) before the resize
+};
+struct AugPackArgs {
+    const float* src; int B, H, W;  // fp32 NHWC4 letterboxed batch (the values view 0 is made of)
+    AugView v[3]; int nview;        // one launch writes them all (blockIdx.z = view)
+    int out_prec;                   // PREC_F16: fp16 stores (rounded once, from fp32); else fp32
+};
+hipError_t launch_augment_pack(const AugPackArgs& a, hipStream_t s);
+
+// Decode of the three views' raw head outputs into ONE candidate list per tile (blockIdx.z = view): boxes de-scaled by the
+// view's scale s, x centre de-flipped with the original width, anchors outside [lo, hi) dropped (_clip_augmented), candidate
+// index = off + (anchor - lo) in the concatenated order.  Candidates feed nms_kernel unchanged.
+struct AugDecodeView {
+    const float* pred; int A; int lvl_h[3], lvl_w[3];
+    float s; int flip; int lo, hi, off;
+};
+struct AugDecodeArgs {
+    AugDecodeView v[3]; int nview;
+    int B, nc; float conf; float W0;      // W0: width of view 0 (the de-flip reference)
+    float* cand; int* cand_anchor; int* cand_count; int cap;
+};
+hipError_t launch_decode_augmented(const AugDecodeArgs& a, hipStream_t s);
+
 }  // namespace cy

@@ -1567,6 +1567,69 @@ hipError_t launch_letterbox_pack(const PreArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------- test-time augmentation views
+// ultralytics scale_img(x.flip(3) if flipped else x, s, gs=32): F.interpolate(bilinear, align_corners=False) to (int(H s), int(W s)),
+// then F.pad on the right / bottom with 0.447 up to multiples of 32.  One thread per output pixel (16-byte NHWC4 loads and stores,
+// neighbouring lanes on neighbouring pixels); the coordinates of the padding pixels are clamped into the content, so that the four
+// loads are unconditional, and the pad value is selected after them.  Resampling as torch's CPU upsample_bilinear2d: scale =
+// in / out in float, source index max(scale (d + 0.5) - 0.5, 0) -- evaluated as one fused multiply-add, which is what torch's
+// vectorised CPU build computes (against the unfused form the 0.67 view's indices drift by up to 1e-5 px) --, i0 = trunc,
+// i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, value = h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11) unfused.
+// A view of the source's own size (the fp16 context's view 0) is a copy, rounded to fp16 once at the store.
+template <typename T>
+__global__ __launch_bounds__(256) void augment_pack_kernel(const AugPackArgs a) {
+#pragma clang fp contract(off)
+    typedef T vec4 __attribute__((ext_vector_type(4)));
+    const int vz = blockIdx.z;
+    const AugView v = vz == 0 ? a.v[0] : (vz == 1 ? a.v[1] : a.v[2]);
+    const int b = blockIdx.y;
+    const int npx = v.Hp * v.Wp;
+    const bool ident = v.ch == a.H && v.cw == a.W && !v.flip;
+    const float sy = (float)a.H / (float)v.ch, sx = (float)a.W / (float)v.cw;
+    const float4* src = reinterpret_cast<const float4*>(a.src) + (size_t)b * a.H * a.W;
+    vec4* out = reinterpret_cast<vec4*>(v.out) + (size_t)b * npx;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += gridDim.x * 256) {
+        const int Y = i / v.Wp, X = i - Y * v.Wp;
+        const bool in = Y < v.ch && X < v.cw;
+        const int y = Y < v.ch ? Y : v.ch - 1, x = X < v.cw ? X : v.cw - 1;
+        float o0, o1, o2;
+        if (ident) {
+            const float4 q = src[(size_t)y * a.W + x];
+            o0 = q.x; o1 = q.y; o2 = q.z;
+        } else {
+            const float fy = fmaxf(__builtin_fmaf(sy, (float)y + 0.5f, -0.5f), 0.0f);
+            const float fx = fmaxf(__builtin_fmaf(sx, (float)x + 0.5f, -0.5f), 0.0f);
+            int y0 = (int)fy, x0 = (int)fx;
+            y0 = y0 < a.H - 1 ? y0 : a.H - 1; x0 = x0 < a.W - 1 ? x0 : a.W - 1;
+            const int y1 = y0 + (y0 < a.H - 1), x1 = x0 + (x0 < a.W - 1);
+            const float h1 = fy - (float)y0, h0 = 1.0f - h1, w1 = fx - (float)x0, w0 = 1.0f - w1;
+            const int c0 = v.flip ? a.W - 1 - x0 : x0, c1 = v.flip ? a.W - 1 - x1 : x1;    // column of the flipped source
+            const float4 v00 = src[(size_t)y0 * a.W + c0], v01 = src[(size_t)y0 * a.W + c1];
+            const float4 v10 = src[(size_t)y1 * a.W + c0], v11 = src[(size_t)y1 * a.W + c1];
+            o0 = h0 * (w0 * v00.x + w1 * v01.x) + h1 * (w0 * v10.x + w1 * v11.x);
+            o1 = h0 * (w0 * v00.y + w1 * v01.y) + h1 * (w0 * v10.y + w1 * v11.y);
+            o2 = h0 * (w0 * v00.z + w1 * v01.z) + h1 * (w0 * v10.z + w1 * v11.z);
+        }
+        if (!in) { o0 = 0.447f; o1 = 0.447f; o2 = 0.447f; }
+        const vec4 q = {(T)o0, (T)o1, (T)o2, (T)0.0f};
+        out[i] = q;
+    }
+}
+
+hipError_t launch_augment_pack(const AugPackArgs& a, hipStream_t s) {
+    if (a.nview < 1 || a.nview > 3 || a.B < 1 || a.H < 1 || a.W < 1) return hipErrorInvalidValue;
+    int npx = 0;
+    for (int k = 0; k < a.nview; ++k) {
+        const AugView& v = a.v[k];
+        if (!v.out || v.ch < 1 || v.cw < 1 || v.ch > a.H || v.cw > a.W || v.Hp < v.ch || v.Wp < v.cw) return hipErrorInvalidValue;
+        npx = v.Hp * v.Wp > npx ? v.Hp * v.Wp : npx;
+    }
+    int gx = (npx + 255) / 256; if (gx > 2048) gx = 2048;
+    if (a.out_prec == PREC_F16) hipLaunchKernelGGL(augment_pack_kernel<_Float16>, dim3(gx, a.B, a.nview), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(augment_pack_kernel<float>, dim3(gx, a.B, a.nview), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------- mosaic ingest
 __global__ __launch_bounds__(256) void mosaic_prepare_kernel(float* d, size_t n, int big_endian) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {

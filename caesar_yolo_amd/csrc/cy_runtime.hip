@@ -45,6 +45,15 @@ struct cy_ctx {
     } sb[3];                                            // [0], [1]: alternating sets of the batch pipeline; [2]: small batches (side forward stream)
     int slot = 0;                                       // buffer set used by the stage entry points
     StageBufs& S() { return sb[slot]; }
+    // test-time augmentation (cy_enable_augment): per buffer set the inputs / head outputs of views 1 and 2, the fp32 letterboxed
+    // source of the fp16 context (its view 0 is fp16), and candidate buffers sized for the concatenated anchors of the three views
+    struct AugBufs {
+        void* view[2] = {nullptr, nullptr}; float* pred[2] = {nullptr, nullptr}; float* src32 = nullptr;
+        float* cand = nullptr; int* cand_anchor = nullptr; uint64_t* keys = nullptr;
+    } ab[3];
+    bool aug = false;
+    int acap = 0, acap_pow2 = 0;
+    AugBufs& AB() { return ab[slot]; }
     size_t pre_scratch_elems = 0;
     int cap = 0, cap_pow2 = 0;
     hipStream_t s_pre = nullptr, s_post = nullptr;      // side streams of the pipelined cy_detect_tiles
@@ -140,6 +149,12 @@ void free_all(cy_ctx* c) {
         for (void* p : ptrs) if (p) hipFree(p);
         b = cy_ctx::StageBufs();
     }
+    for (auto& b : c->ab) {
+        void* ptrs[] = {b.view[0], b.view[1], b.pred[0], b.pred[1], b.src32, b.cand, b.cand_anchor, b.keys};
+        for (void* p : ptrs) if (p) hipFree(p);
+        b = cy_ctx::AugBufs();
+    }
+    c->aug = false; c->acap = 0; c->acap_pow2 = 0;
     if (c->counters) { hipFree(c->counters); c->counters = nullptr; }
     if (c->s_pre) { hipStreamDestroy(c->s_pre); c->s_pre = nullptr; }
     if (c->s_post) { hipStreamDestroy(c->s_post); c->s_post = nullptr; }
@@ -1255,9 +1270,18 @@ static int fill_pre_args(cy_ctx* c, const float* d_mosaic, int MH, int MW, const
     return CY_OK;
 }
 
+static int preproc_as(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw, int imgsz,
+                      const cy_preproc_cfg* cfg, void* d_netin, Precision out_prec, int* d_status, void* stream);
+
 int cy_preproc(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw, int imgsz,
                const cy_preproc_cfg* cfg, void* d_netin, int* d_status, void* stream) {
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    return preproc_as(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, d_netin, io_prec(c->prec), d_status, stream);
+}
+
+// cy_preproc with the type of the network-input canvas named (the augmented path of the fp16 context packs fp32)
+static int preproc_as(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw, int imgsz,
+                      const cy_preproc_cfg* cfg, void* d_netin, Precision out_prec, int* d_status, void* stream) {
     if (!d_mosaic || !h_tiles || !cfg || !d_netin || !d_status || B < 1 || B > c->cfg.max_batch)
         return fail(c, CY_ERR_ARG, "bad preproc arguments");
     cy_letterbox lb;
@@ -1267,7 +1291,7 @@ int cy_preproc(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_ti
     int rc = fill_pre_args(c, d_mosaic, MH, MW, h_tiles, B, th, tw, cfg, d_status, a);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    a.out = d_netin; a.out_prec = io_prec(c->prec); a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
+    a.out = d_netin; a.out_prec = out_prec; a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
     a.new_h = lb.new_h; a.new_w = lb.new_w;
     const bool resize = (lb.new_h != th) || (lb.new_w != tw);
     if (resize && (size_t)B * 3 * th * tw > c->pre_scratch_elems) return fail(c, CY_ERR_ARG, "resize scratch too small");
@@ -1463,6 +1487,214 @@ int cy_detect_counters(cy_ctx* c, long long* out4, int reset) {
     HIPCHK(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out4[i] = h[i];
     if (reset) HIPCHK(c, hipMemset(c->counters, 0, sizeof(h)));
+    return CY_OK;
+}
+
+// ---- test-time augmentation -------------------------------------------------------------------
+// ultralytics DetectionModel._predict_augment: scales (1, 0.83, 0.67), flips (none, left-right, none), gs = 32; sizes in double as
+// Python computes them (int(h * s) truncates, ceil(h * s / gs) * gs pads); _clip_augmented with g = 1 + 4 + 16 drops the stride-32
+// anchors of view 0 and the stride-8 anchors of view 2.
+static const double AUG_SCALE[3] = {1.0, 0.83, 0.67};
+static const int AUG_FLIP[3] = {0, 1, 0};
+
+int cy_augment_geometry(int H, int W, cy_augment_geom* o) {
+    if (!o || H < 32 || W < 32 || H % 32 || W % 32) return CY_ERR_ARG;
+    int off = 0;
+    for (int k = 0; k < 3; ++k) {
+        cy_augment_view& v = o->v[k];
+        const double s = AUG_SCALE[k];
+        v.scale = s; v.flip = AUG_FLIP[k];
+        v.ch = (int)(H * s); v.cw = (int)(W * s);
+        v.Hp = (int)std::ceil(H * s / 32.0) * 32; v.Wp = (int)std::ceil(W * s / 32.0) * 32;
+        v.A = cy_num_anchors(v.Hp, v.Wp);
+        const int g = v.A / 21;                                  // stride-32 cells (views are multiples of 32: A = 21 g)
+        v.lo = k == 2 ? g * 16 : 0;
+        v.hi = k == 0 ? v.A - g : v.A;
+        v.off = off;
+        off += v.hi - v.lo;
+    }
+    o->total = off;
+    return CY_OK;
+}
+
+int cy_enable_augment(cy_ctx* c) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (c->aug) return CY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const cy_config& g = c->cfg;
+    cy_augment_geom ag;
+    if (cy_augment_geometry(g.max_h, g.max_w, &ag)) return fail(c, CY_ERR_ARG, "bad context geometry");
+    const size_t es = esize(c->prec), Bm = g.max_batch;
+    // candidates per tile: as the plain path (cap = anchors of the largest input, at most ultralytics' max_nms), over the
+    // concatenation of the three views; an explicit max_cand is honoured
+    c->acap = g.max_cand > 0 ? g.max_cand : ag.total;
+    if (c->acap > 30000) c->acap = 30000;
+    c->acap = (c->acap + 63) / 64 * 64;
+    c->acap_pow2 = 1; while (c->acap_pow2 < c->acap) c->acap_pow2 <<= 1;
+    const int nc = c->plan.nc;
+    for (auto& b : c->ab) {
+        for (int k = 0; k < 2; ++k) {
+            const cy_augment_view& v = ag.v[k + 1];
+            HIPCHK(c, hipMalloc(&b.view[k], Bm * v.Hp * v.Wp * 4 * es));
+            HIPCHK(c, hipMalloc(&b.pred[k], Bm * v.A * (64 + nc) * sizeof(float)));
+        }
+        if (c->prec == PREC_F16) HIPCHK(c, hipMalloc(&b.src32, Bm * g.max_h * g.max_w * 4 * sizeof(float)));
+        HIPCHK(c, hipMalloc(&b.cand, Bm * c->acap * 6 * sizeof(float)));
+        HIPCHK(c, hipMalloc(&b.cand_anchor, Bm * c->acap * sizeof(int)));
+        HIPCHK(c, hipMalloc(&b.keys, Bm * c->acap_pow2 * sizeof(uint64_t)));
+    }
+    c->aug = true;
+    return CY_OK;
+}
+
+int cy_letterbox_pack_f32(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, float* d_out, void* stream) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (!d_planes || !d_out || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
+    cy_letterbox lb;
+    if (cy_letterbox_geometry(h0, w0, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad image/imgsz");
+    if (lb.H > c->cfg.max_h || lb.W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "letterboxed image exceeds max_h/max_w of the context");
+    PreArgs a{};
+    a.B = B; a.th = h0; a.tw = w0; a.scratch = const_cast<double*>(d_planes);
+    a.out = d_out; a.out_prec = PREC_F32; a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
+    a.new_h = lb.new_h; a.new_w = lb.new_w;
+    HIPCHK(c, launch_letterbox_pack(a, (hipStream_t)stream));
+    return CY_OK;
+}
+
+// the view kernel on (src, H, W) -> the views named (view 0 only in the fp16 context: its fp16 copy of src)
+static int augment_pack_on(cy_ctx* c, const float* d_src, int B, int H, int W, void* d_view0, void* d_view1, void* d_view2,
+                           hipStream_t s) {
+    cy_augment_geom ag;
+    if (cy_augment_geometry(H, W, &ag)) return fail(c, CY_ERR_ARG, "bad view-0 size (multiples of 32 required)");
+    AugPackArgs a{};
+    a.src = d_src; a.B = B; a.H = H; a.W = W; a.out_prec = io_prec(c->prec);
+    void* outs[3] = {d_view0, d_view1, d_view2};
+    for (int k = 0; k < 3; ++k) {
+        if (!outs[k]) continue;
+        const cy_augment_view& v = ag.v[k];
+        a.v[a.nview++] = AugView{outs[k], v.ch, v.cw, v.Hp, v.Wp, v.flip};
+    }
+    if (a.nview == 0) return CY_OK;
+    HIPCHK(c, launch_augment_pack(a, s));
+    return CY_OK;
+}
+
+int cy_augment_pack(cy_ctx* c, const float* d_src, int B, int H, int W, void* d_view0, void* d_view1, void* d_view2, void* stream) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (!c->aug) return fail(c, CY_ERR_STATE, "test-time augmentation not enabled on this context (cy_enable_augment)");
+    if (!d_src || !d_view1 || !d_view2 || B < 1 || B > c->cfg.max_batch || H > c->cfg.max_h || W > c->cfg.max_w)
+        return fail(c, CY_ERR_ARG, "bad arguments");
+    if (d_view0 && c->prec != PREC_F16) return fail(c, CY_ERR_ARG, "view 0 is the source itself outside the fp16 context");
+    return augment_pack_on(c, d_src, B, H, W, d_view0, d_view1, d_view2, (hipStream_t)stream);
+}
+
+// decode of the three views + NMS over the concatenation + scale_boxes, into the given outputs, on the context's buffer set
+static int decode_nms_aug_on(cy_ctx* c, const float* const* d_pred, int B, int H, int W, int h0, int w0, float conf, float iou,
+                             float* d_det, int* d_det_anchor, int* d_count, hipStream_t s) {
+    cy_augment_geom ag;
+    if (cy_augment_geometry(H, W, &ag)) return fail(c, CY_ERR_ARG, "bad view-0 size (multiples of 32 required)");
+    AugDecodeArgs d{};
+    d.nview = 3; d.B = B; d.nc = c->plan.nc; d.conf = conf; d.W0 = (float)W;
+    for (int k = 0; k < 3; ++k) {
+        const cy_augment_view& v = ag.v[k];
+        AugDecodeView& q = d.v[k];
+        q.pred = d_pred[k]; q.A = v.A; q.s = (float)v.scale; q.flip = v.flip; q.lo = v.lo; q.hi = v.hi; q.off = v.off;
+        for (int l = 0; l < 3; ++l) { q.lvl_h[l] = v.Hp >> (3 + l); q.lvl_w[l] = v.Wp >> (3 + l); }
+    }
+    d.cand = c->AB().cand; d.cand_anchor = c->AB().cand_anchor; d.cand_count = c->S().cand_count; d.cap = c->acap;
+    HIPCHK(c, hipMemsetAsync(c->S().cand_count, 0, B * sizeof(int), s));
+    HIPCHK(c, launch_decode_augmented(d, s));
+    NmsArgs n{};
+    n.cand = c->AB().cand; n.cand_anchor = c->AB().cand_anchor; n.cand_count = c->S().cand_count; n.cap = c->acap; n.B = B; n.iou = iou;
+    n.max_det = CY_MAX_DET;
+    const double gain = std::fmin((double)H / h0, (double)W / w0);         // scale_boxes against view 0, as cy_decode_nms
+    n.gain = (float)gain;
+    n.padw = py_round_half_even((W - w0 * gain) / 2 - 0.1); n.padh = py_round_half_even((H - h0 * gain) / 2 - 0.1);
+    n.w0 = w0; n.h0 = h0;
+    n.det = d_det; n.det_anchor = d_det_anchor; n.det_count = d_count; n.keys = c->AB().keys; n.mask = nullptr;
+    n.counters = c->counters;
+    HIPCHK(c, launch_nms(n, s));
+    return CY_OK;
+}
+
+int cy_decode_nms_augmented(cy_ctx* c, const float* d_pred0, const float* d_pred1, const float* d_pred2, int B, int H, int W,
+                            int h0, int w0, float conf, float iou, float* d_det, int* d_det_anchor, int* d_count, void* stream) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (!c->aug) return fail(c, CY_ERR_STATE, "test-time augmentation not enabled on this context (cy_enable_augment)");
+    if (!d_pred0 || !d_pred1 || !d_pred2 || !d_det || !d_det_anchor || !d_count || B < 1 || B > c->cfg.max_batch)
+        return fail(c, CY_ERR_ARG, "bad arguments");
+    if (H > c->cfg.max_h || W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "view 0 exceeds max_h/max_w of the context");
+    const float* preds[3] = {d_pred0, d_pred1, d_pred2};
+    return decode_nms_aug_on(c, preds, B, H, W, h0, w0, conf, iou, d_det, d_det_anchor, d_count, (hipStream_t)stream);
+}
+
+int cy_detect_tiles_augmented(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw,
+                              int imgsz, const cy_preproc_cfg* cfg, float conf, float iou, double soft, double hard, int augment,
+                              float* d_out, int* d_out_count, int* d_status, void* stream) {
+    if (!augment)
+        return cy_detect_tiles(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, conf, iou, soft, hard, d_out, d_out_count, d_status, stream);
+    // cy_detect_tiles' pipeline (streams, buffer sets, events, lanes: see there), with three views per batch: the view kernel runs
+    // on the preprocessing stream behind the letterbox pack, the three forwards back to back on the forward stream, and the
+    // augmented decode + NMS + IoU merge on the post-processing stream.  The view buffers belong to the buffer set, so the events
+    // that order a set's reuse order them too, and plain and augmented calls mix freely in one unflushed pipeline.
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (!c->aug) return fail(c, CY_ERR_STATE, "test-time augmentation not enabled on this context (cy_enable_augment)");
+    cy_letterbox lb;
+    if (cy_letterbox_geometry(th, tw, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad tile/imgsz");
+    if (lb.H > c->cfg.max_h || lb.W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "letterboxed tile exceeds max_h/max_w of the context");
+    cy_augment_geom ag;
+    if (cy_augment_geometry(lb.H, lb.W, &ag)) return fail(c, CY_ERR_ARG, "bad letterboxed size");
+    hipStream_t sm = (hipStream_t)stream;
+    const bool small = env_knob("CY_SMALL_LANE", 1) && c->prec != PREC_F32 && B < 64 && (long)B * 3 <= c->cfg.max_batch;
+    int rc = CY_OK;
+    if (small) { rc = ensure_small_lane(c); if (rc) return rc; }
+    const int sl = small ? 2 : (int)(c->batches & 1);
+    const bool reuse = small ? c->small_batches >= 1 : c->batches >= 2;
+    hipStream_t sf = small ? c->s_small : sm;
+    const int side_mode = env_knob("CY_SIDE_STREAMS", 2);
+    if (side_mode == 3) { rc = ensure_side_forward_stream(c); if (rc) return rc; }
+    hipStream_t spost = side_mode == 1 ? c->s_pre : (side_mode == 3 ? c->s_fwd2 : c->s_post);
+    c->slot = sl;
+    bool seen = false;
+    for (int i = 0; i < c->n_seen; ++i) seen = seen || c->seen_mosaic[i] == (const void*)d_mosaic;
+    if (c->batches + c->small_batches == 0 || c->mosaic_dirty || !seen) {
+        HIPCHK(c, hipEventRecord(c->ev_call, sm));
+        HIPCHK(c, hipStreamWaitEvent(c->s_pre, c->ev_call, 0));
+        if (c->mosaic_dirty || c->batches + c->small_batches == 0) c->n_seen = 0;
+        if (c->n_seen < 16) c->seen_mosaic[c->n_seen++] = d_mosaic;
+        c->mosaic_dirty = false;
+    }
+    if (reuse) HIPCHK(c, hipStreamWaitEvent(c->s_pre, c->ev_fwd[sl], 0));
+    // view 0 = the letterboxed batch; in the fp16 context it is packed in fp32 first, and the view kernel writes all three views
+    const bool f16 = c->prec == PREC_F16;
+    float* src32 = f16 ? c->AB().src32 : (float*)c->S().netin;
+    rc = preproc_as(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, src32, PREC_F32, d_status, c->s_pre);
+    if (!rc) rc = augment_pack_on(c, src32, B, lb.H, lb.W, f16 ? c->S().netin : nullptr, c->AB().view[0], c->AB().view[1], c->s_pre);
+    if (rc) { c->slot = 0; return rc; }
+    HIPCHK(c, hipEventRecord(c->ev_pre[sl], c->s_pre));
+    HIPCHK(c, hipStreamWaitEvent(sf, c->ev_pre[sl], 0));
+    if (reuse) HIPCHK(c, hipStreamWaitEvent(sf, c->ev_post[sl], 0));
+    const void* vin[3] = {c->S().netin, c->AB().view[0], c->AB().view[1]};
+    float* vpred[3] = {c->S().pred, c->AB().pred[0], c->AB().pred[1]};
+    for (int k = 0; k < 3 && !rc; ++k) {
+        const int Hk = ag.v[k].Hp, Wk = ag.v[k].Wp;
+        if (small) {
+            c->split_last = false;
+            rc = forward_on(c, vin[k], B, Hk, Wk, vpred[k], sf, c->ws3, c->ws3_bytes, true);
+        } else {
+            rc = forward_split(c, vin[k], B, Hk, Wk, vpred[k], sm);
+        }
+    }
+    if (rc) { c->slot = 0; return rc; }
+    HIPCHK(c, hipEventRecord(c->ev_fwd[sl], sf));
+    HIPCHK(c, hipStreamWaitEvent(spost, c->ev_fwd[sl], 0));
+    const float* cpred[3] = {vpred[0], vpred[1], vpred[2]};
+    rc = decode_nms_aug_on(c, cpred, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, spost);
+    if (!rc) rc = cy_iou_merge(c, c->S().det, c->S().det_count, B, conf, soft, hard, d_out, d_out_count, nullptr, spost);
+    if (rc) { c->slot = 0; return rc; }
+    HIPCHK(c, hipEventRecord(c->ev_post[sl], spost));
+    if (small) c->small_batches++; else c->batches++;
+    c->slot = 0;
     return CY_OK;
 }
 

@@ -76,6 +76,74 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ augmented decode
+// Test-time augmentation (ultralytics DetectionModel._predict_augment): the three views' head outputs decoded in one launch
+// (blockIdx.z = view) into one candidate list per tile.  Per view the Detect output (xywh in view pixels) is divided by the
+// view's scale s itself (not by the integer size ratio), the x centre of the flipped view is mirrored with the width of view 0,
+// and the anchors that _clip_augmented drops (stride 32 of view 0, stride 8 of the last view) are skipped.  The candidate's
+// index is its position in the concatenated prediction, so nms_kernel's (score, index) order is ultralytics' order over the
+// concatenation.  View 0 (s = 1, no flip) yields exactly the plain decode's candidates.
+__global__ __launch_bounds__(256) void decode_augmented_kernel(const AugDecodeArgs a) {
+    const int vz = blockIdx.z;
+    const AugDecodeView& v = vz == 0 ? a.v[0] : (vz == 1 ? a.v[1] : a.v[2]);
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < v.lo || i >= v.hi) return;
+    int lvl = 0, r = i;
+    const int n0 = v.lvl_h[0] * v.lvl_w[0], n1 = v.lvl_h[1] * v.lvl_w[1];
+    if (r >= n0) { r -= n0; lvl = 1; if (r >= n1) { r -= n1; lvl = 2; } }
+    const int gw = v.lvl_w[lvl];
+    const float ax = (float)(r % gw) + 0.5f, ay = (float)(r / gw) + 0.5f;
+    const float stride = (float)(8 << lvl);
+    const float* p = v.pred + ((size_t)b * v.A + i) * (64 + a.nc);
+    float best = -1.0f; int bj = 0;
+    for (int c = 0; c < a.nc; ++c) {
+        const float s = 1.0f / (1.0f + expf(-p[64 + c]));
+        if (s > best) { best = s; bj = c; }
+    }
+    if (!(best > a.conf)) return;
+    float d[4];
+#pragma unroll
+    for (int side = 0; side < 4; ++side) {
+        const float* q = p + side * 16;
+        float m = q[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) m = fmaxf(m, q[k]);
+        float e[16], s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { e[k] = expf(q[k] - m); s += e[k]; }
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc += (e[k] / s) * (float)k;
+        d[side] = acc;
+    }
+    const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
+    float cx = ((x1 + x2) / 2.0f) * stride, cy_ = ((y1 + y2) / 2.0f) * stride;
+    float w = (x2 - x1) * stride, h = (y2 - y1) * stride;
+    cx = cx / v.s; cy_ = cy_ / v.s; w = w / v.s; h = h / v.s;          // yi[:, :4] /= si
+    if (v.flip) cx = a.W0 - cx;                                        // yi[:, 0] = W - yi[:, 0]
+    const float hw = w / 2.0f, hh = h / 2.0f;
+    const int slot = atomicAdd(a.cand_count + b, 1);
+    if (slot >= a.cap) return;
+    float* o = a.cand + ((size_t)b * a.cap + slot) * 6;
+    o[0] = cx - hw; o[1] = cy_ - hh; o[2] = cx + hw; o[3] = cy_ + hh; o[4] = best; o[5] = (float)bj;
+    a.cand_anchor[(size_t)b * a.cap + slot] = v.off + (i - v.lo);
+}
+
+hipError_t launch_decode_augmented(const AugDecodeArgs& a, hipStream_t s) {
+    if (a.nview < 1 || a.nview > 3 || a.cap >= 65536) return hipErrorInvalidValue;
+    int amax = 0;
+    for (int k = 0; k < a.nview; ++k) {
+        const AugDecodeView& v = a.v[k];
+        if (v.lo < 0 || v.hi > v.A || v.lo > v.hi) return hipErrorInvalidValue;
+        if (v.off + (v.hi - v.lo) >= 65536) return hipErrorInvalidValue;      // key packing of nms_kernel: 16-bit index
+        amax = v.hi > amax ? v.hi : amax;
+    }
+    if (amax == 0) return hipSuccess;
+    hipLaunchKernelGGL(decode_augmented_kernel, dim3((amax + 255) / 256, a.B, a.nview), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ NMS
 // One 256-thread workgroup per tile.  (1) order candidates by (score desc, anchor asc) with a bitonic network on 64-bit
 // keys -- in LDS when they fit, else through L2; (2) wave 0 scans the ordered list 64 boxes at a time: every lane tests

@@ -27,6 +27,7 @@ class Analyzer(object):
         self.imgsize = config['img_size']
         self.device = config['devices'][0]
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
+        self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
         self.merge_overlap_iou_thr_hard = config['merge_overlap_iou_thr_hard']
         self.write_to_json = config.get('save_catalog', True)
@@ -69,7 +70,7 @@ class Analyzer(object):
             ny, nx = image.shape
             mosaic = det.mosaic_to_device(image)
             d, cnt, status = det.detect_tiles(mosaic, [(0, 0)], ny, nx, self.imgsize, cfg, self.score_thr, self.iou_thr,
-                                              self.merge_overlap_iou_thr_soft, self.merge_overlap_iou_thr_hard)
+                                              self.merge_overlap_iou_thr_soft, self.merge_overlap_iou_thr_hard, augment=self.augment)
             torch.cuda.synchronize(det.tdev)
         except L.CyError as e:
             logger.warning("Model prediction failed (err=%s)..." % str(e))
@@ -113,9 +114,14 @@ class Analyzer(object):
                     st = 2
             d = cnt = None
             if st == 0:
-                netin, lb = det.letterbox_pack(cube, self.imgsize)
-                pred = det.forward(netin)
-                dn, _, cn = det.decode_nms(pred, lb.H, lb.W, ny, nx, self.score_thr, self.iou_thr)
+                if self.augment:
+                    src, lb = det.letterbox_pack_f32(cube, self.imgsize)
+                    preds = [det.forward(v) for v in det.augment_pack(src)]
+                    dn, _, cn = det.decode_nms_augmented(preds, lb.H, lb.W, ny, nx, self.score_thr, self.iou_thr)
+                else:
+                    netin, lb = det.letterbox_pack(cube, self.imgsize)
+                    pred = det.forward(netin)
+                    dn, _, cn = det.decode_nms(pred, lb.H, lb.W, ny, nx, self.score_thr, self.iou_thr)
                 d, cnt, _ = det.iou_merge(dn, cn, self.score_thr, self.merge_overlap_iou_thr_soft, self.merge_overlap_iou_thr_hard)
                 torch.cuda.synchronize(det.tdev)
         except L.CyError as e:

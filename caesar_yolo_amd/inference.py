@@ -176,8 +176,9 @@ class TileEngine(object):
     shape-class segment of THIS rank's tiles is uploaded (the partition cuts the tile list into contiguous runs, so a
     rank's full-size tiles are a band of rows) and tile origins are rebased to it."""
 
-    def __init__(self, detector, mosaic_dev, grid, pre_cfg, imgsz, conf, iou, soft, hard, rank=0, world=1, batch=64):
+    def __init__(self, detector, mosaic_dev, grid, pre_cfg, imgsz, conf, iou, soft, hard, rank=0, world=1, batch=64, augment=False):
         self.det, self.mosaic, self.grid = detector, mosaic_dev, [tuple(int(v) for v in t) for t in grid]
+        self.augment = bool(augment)                           # test-time augmentation of every tile (cy_detect_tiles_augmented)
         self.pre_cfg, self.imgsz = pre_cfg, int(imgsz)
         self.conf, self.iou, self.soft, self.hard = float(conf), float(iou), float(soft), float(hard)
         self.rank, self.world, self.batch = rank, world, min(int(batch), detector.max_batch)
@@ -238,10 +239,11 @@ class TileEngine(object):
 
     def run_local(self):
         """Enqueue every batch of this rank's tiles (software-pipelined inside the library); results stay on device."""
+        kw = dict(augment=True) if self.augment else {}
         for th, tw, B, xy, row, img in self.plan:
             out = (self.det_all[row:row + B], self.cnt_all[row:row + B], self.st_all[row:row + B])
             self.det.detect_tiles(img, xy, th, tw, self.imgsz, self.pre_cfg, self.conf, self.iou,
-                                  self.soft, self.hard, out=out, flush=False)
+                                  self.soft, self.hard, out=out, flush=False, **kw)
         if hasattr(self.det, "flush"):
             self.det.flush()
         n = self.n_my
@@ -584,7 +586,7 @@ class SFinder(object):
             return -1
         conf, iou, soft, hard = self._thr()
         eng = TileEngine(det, mosaic, grid, self._pre_cfg(), c['img_size'], conf, iou, soft, hard, rank, world,
-                         c.get('tile_batch', 64))
+                         c.get('tile_batch', 64), augment=c.get('augment', False))
         # caesar_yolo/inference.py:1151-1160: the reference refuses a run in which a worker holds more than
         # max_ntasks_per_worker tiles (its default, 100, would refuse BASELINE configs 3-5 at any rank count up to 16).  The
         # batched engine has no such limit, so the guard applies only when the option was given explicitly (run.py passes

@@ -20,7 +20,8 @@ EXPORTS = [
     "cy_pred_elems", "cy_profile_enable", "cy_profile_summary", "cy_profile_summary_lane", "cy_profile_layers", "cy_mosaic_prepare", "cy_letterbox_pack", "cy_preproc", "cy_preproc_planes", "cy_preproc_params", "cy_forward", "cy_debug_read_conv",
     "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_bottleneck64", "cy_dwconv3x3",
     "cy_attention", "cy_maxpool5", "cy_make_tile_records",
-    "cy_merge_edge_sources",
+    "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
+    "cy_decode_nms_augmented", "cy_detect_tiles_augmented",
 ]
 
 
@@ -57,6 +58,15 @@ class cy_prof_entry(C.Structure):
 class cy_letterbox(C.Structure):
     _fields_ = [("new_h", C.c_int), ("new_w", C.c_int), ("top", C.c_int), ("left", C.c_int), ("H", C.c_int),
                 ("W", C.c_int)]
+
+
+class cy_augment_view(C.Structure):
+    _fields_ = [("scale", C.c_double), ("flip", C.c_int), ("ch", C.c_int), ("cw", C.c_int), ("Hp", C.c_int), ("Wp", C.c_int),
+                ("A", C.c_int), ("lo", C.c_int), ("hi", C.c_int), ("off", C.c_int)]
+
+
+class cy_augment_geom(C.Structure):
+    _fields_ = [("v", cy_augment_view * 3), ("total", C.c_int)]
 
 
 _lib = None
@@ -124,6 +134,15 @@ def load():
         "cy_maxpool5": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
         "cy_make_tile_records": (C.c_int, [fp, ip, C.c_int, ip, C.c_int, dp]),
         "cy_merge_edge_sources": (C.c_int, [dp, C.c_int, ip, C.c_int, dp]),
+        "cy_augment_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(cy_augment_geom)]),
+        "cy_enable_augment": (C.c_int, [vp]),
+        "cy_letterbox_pack_f32": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "cy_augment_pack": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "cy_decode_nms_augmented": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                              vp, vp, vp, vp]),
+        "cy_detect_tiles_augmented": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.POINTER(cy_preproc_cfg), C.c_float, C.c_float, C.c_double, C.c_double, C.c_int,
+                                                vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -154,3 +173,12 @@ def plan_convs(scale, nc):
         check(lib.cy_plan_conv_desc(scale.encode(), nc, i, C.byref(d)))
         out.append((d.name.decode(), d.cin, d.cout, d.k, d.s, d.act))
     return out
+
+
+def augment_geometry(H, W):
+    """Test-time augmentation views of an H x W letterboxed input (cy_augment_geometry): list of three dicts
+    (scale, flip, ch, cw, Hp, Wp, A, lo, hi, off) and the concatenated anchor count."""
+    g = cy_augment_geom()
+    check(load().cy_augment_geometry(int(H), int(W), C.byref(g)))
+    views = [{k: getattr(g.v[i], k) for k, _ in cy_augment_view._fields_} for i in range(3)]
+    return views, int(g.total)

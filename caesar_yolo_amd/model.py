@@ -3,7 +3,7 @@
 Mirrors the slice of `ultralytics.YOLO` that the reference touches:
   * construction with a weights path            scripts/run.py:347
   * `.names` (dict class id -> label)           caesar_yolo/evaluation.py:46-47, :265
-  * `model(image, device=, imgsz=, conf=, iou=, **ignored)` returning an iterable of results whose
+  * `model(image, device=, imgsz=, conf=, iou=, augment=, **ignored)` returning an iterable of results whose
     `.boxes.xyxy / .conf / .cls` support `.cpu().numpy()`      caesar_yolo/evaluation.py:181-193, :261-265
 plus the additive batched entry the tile scheduler uses (`detect_tiles`): B same-shape tiles cropped from an
 HBM-resident mosaic -> merged detections, everything on device.
@@ -274,9 +274,49 @@ class HipDetector(object):
         return {"degenerate_boxes": int(out[0]), "cand_overflow_tiles": int(out[1]), "median_bracket_hits": int(out[2]),
                 "median_bracket_misses": int(out[3])}
 
-    def detect_tiles(self, mosaic, tiles_xy, th, tw, imgsz, cfg, conf, iou, soft, hard, out=None, flush=True):
+    # ---- test-time augmentation (ultralytics `augment=True`): views 1 (0.83, flipped) and 2 (0.67) beside view 0
+    def enable_augment(self):
+        """Allocate the context's view buffers (cy_enable_augment; once, on the first augmented call)."""
+        if not getattr(self, "_aug", False):
+            self._chk(self.lib.cy_enable_augment(self.ctx))
+            self._aug = True
+
+    def letterbox_pack_f32(self, planes, imgsz):
+        """letterbox_pack into an fp32 canvas whatever the context precision (the views' source)."""
+        B, _, h0, w0 = planes.shape
+        lb = L.letterbox(h0, w0, imgsz)
+        out = torch.empty((B, lb.H, lb.W, 4), dtype=torch.float32, device=self.tdev)
+        self._chk(self.lib.cy_letterbox_pack_f32(self.ctx, self._p(planes), B, h0, w0, imgsz, self._p(out), self._stream()))
+        return out, lb
+
+    def augment_pack(self, src):
+        """View kernel: src fp32 [B,H,W,4] letterboxed -> [view 0, view 1, view 2] network inputs of the context dtype (view 0 is src
+        itself in the fp32 / fp16x3 contexts, its fp16 copy in the fp16 context)."""
+        self.enable_augment()
+        B, H, Wd, _ = src.shape
+        views, _ = L.augment_geometry(H, Wd)
+        outs = [torch.empty((B, v["Hp"], v["Wp"], 4), dtype=self.dtype, device=self.tdev) for v in views]
+        if self.precision != L.F16:
+            outs[0] = src
+        self._chk(self.lib.cy_augment_pack(self.ctx, self._p(src), B, H, Wd, self._p(outs[0]) if self.precision == L.F16 else None,
+                                           self._p(outs[1]), self._p(outs[2]), self._stream()))
+        return outs
+
+    def decode_nms_augmented(self, preds, H, Wd, h0, w0, conf, iou):
+        """preds: the three views' raw head outputs (forward()); H, Wd: view 0.  -> (det, concatenated index, count) as decode_nms."""
+        self.enable_augment()
+        B = preds[0].shape[0]
+        det = torch.zeros((B, L.CY_MAX_DET, 6), dtype=torch.float32, device=self.tdev)
+        anch = torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev)
+        cnt = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
+        self._chk(self.lib.cy_decode_nms_augmented(self.ctx, self._p(preds[0]), self._p(preds[1]), self._p(preds[2]), B, H, Wd, h0, w0,
+                                                   conf, iou, self._p(det), self._p(anch), self._p(cnt), self._stream()))
+        return det, anch, cnt
+
+    def detect_tiles(self, mosaic, tiles_xy, th, tw, imgsz, cfg, conf, iou, soft, hard, out=None, flush=True, augment=False):
         """Whole per-tile path for B same-shape tiles.  Returns (det [B,300,6], count [B], status [B]) on device.
-        With flush=False consecutive calls overlap (give each its own `out` buffers and call flush() before reading)."""
+        With flush=False consecutive calls overlap (give each its own `out` buffers and call flush() before reading).
+        augment=True: ultralytics' test-time augmentation (three views per tile, cy_detect_tiles_augmented)."""
         B = len(tiles_xy)
         if out is None:
             det = torch.empty((B, L.CY_MAX_DET, 6), dtype=torch.float32, device=self.tdev)
@@ -285,9 +325,15 @@ class HipDetector(object):
         else:
             det, cnt, status = out
         t = (C.c_int * (2 * B))(*[int(v) for xy in tiles_xy for v in xy])
-        self._chk(self.lib.cy_detect_tiles(self.ctx, self._p(mosaic), mosaic.shape[0], mosaic.shape[1], t, B, th, tw,
-                                           imgsz, C.byref(cfg), conf, iou, soft, hard, self._p(det), self._p(cnt),
-                                           self._p(status), self._stream()))
+        if augment:
+            self.enable_augment()
+            self._chk(self.lib.cy_detect_tiles_augmented(self.ctx, self._p(mosaic), mosaic.shape[0], mosaic.shape[1], t, B, th, tw,
+                                                         imgsz, C.byref(cfg), conf, iou, soft, hard, 1, self._p(det), self._p(cnt),
+                                                         self._p(status), self._stream()))
+        else:
+            self._chk(self.lib.cy_detect_tiles(self.ctx, self._p(mosaic), mosaic.shape[0], mosaic.shape[1], t, B, th, tw,
+                                               imgsz, C.byref(cfg), conf, iou, soft, hard, self._p(det), self._p(cnt),
+                                               self._p(status), self._stream()))
         if flush:
             self.flush()
         return det, cnt, status
@@ -430,12 +476,20 @@ class YOLO(object):
             self._det = HipDetector(self._wpath, device=dev, **self._kw)
         return self._det
 
-    def __call__(self, image, device=None, imgsz=640, conf=0.25, iou=0.7, **ignored):
+    def __call__(self, image, device=None, imgsz=640, conf=0.25, iou=0.7, augment=False, **ignored):
+        """augment=True: ultralytics' test-time augmentation -- the letterboxed image, its 0.83-scale left-right flip and its
+        0.67-scale view through the network, one NMS over the three predictions (DetectionModel._predict_augment)."""
         det = self.engine(device)
         img = np.asarray(image, dtype=np.float64)
         if img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("expected an (H,W,3) image")
         planes = torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1))[None]).to(det.tdev)
+        if augment:
+            src, lb = det.letterbox_pack_f32(planes, int(imgsz))
+            preds = [det.forward(v) for v in det.augment_pack(src)]
+            d, _, cnt = det.decode_nms_augmented(preds, lb.H, lb.W, img.shape[0], img.shape[1], float(conf), float(iou))
+            n = int(cnt[0].item())
+            return [Results(d[0, :n])]
         netin, lb = det.letterbox_pack(planes, int(imgsz))
         pred = det.forward(netin)
         d, _, cnt = det.decode_nms(pred, lb.H, lb.W, img.shape[0], img.shape[1], float(conf), float(iou))
@@ -443,7 +497,7 @@ class YOLO(object):
         return [Results(d[0, :n])]
 
     def predict_tiles(self, device_mosaic, tile_coords, pre_cfg, device=None, imgsz=640, conf=0.25, iou=0.7,
-                      merge_overlap_iou_thr_soft=0.3, merge_overlap_iou_thr_hard=0.8, **ignored):
+                      merge_overlap_iou_thr_soft=0.3, merge_overlap_iou_thr_hard=0.8, augment=False, **ignored):
         """Batched entry of the tile queue (SURVEY §8b "additive" entry; no counterpart in ultralytics).
 
         device_mosaic : [ny,nx] fp32 tensor on the GPU (HipDetector.mosaic_to_device)
@@ -451,7 +505,8 @@ class YOLO(object):
         pre_cfg       : cy_preproc_cfg (DataPreprocessor.program())
         Runs TileTask.find_sources' per-tile chain (caesar_yolo/inference.py:173-275: crop, preprocessing, model call,
         process_detections) for the whole batch; returns one Results per tile (boxes in TILE pixel coordinates), or None
-        where the reference would skip the tile (pipeline gave None / constant rows)."""
+        where the reference would skip the tile (pipeline gave None / constant rows).  augment=True: test-time augmentation
+        of every tile's model call (see __call__)."""
         det = self.engine(device)
         tc = np.asarray(tile_coords, dtype=np.int64).reshape(-1, 4)
         if len(tc) == 0:
@@ -461,6 +516,6 @@ class YOLO(object):
             raise ValueError("predict_tiles needs tiles of one shape per call (group ragged edge tiles separately)")
         d, cnt, status = det.detect_tiles(device_mosaic, [(int(r[0]), int(r[2])) for r in tc], int(th[0]), int(tw[0]),
                                           int(imgsz), pre_cfg, float(conf), float(iou),
-                                          float(merge_overlap_iou_thr_soft), float(merge_overlap_iou_thr_hard))
+                                          float(merge_overlap_iou_thr_soft), float(merge_overlap_iou_thr_hard), augment=bool(augment))
         cnt, status = cnt.cpu().numpy(), status.cpu().numpy()
         return [Results(d[b, :int(cnt[b])]) if status[b] == 0 else None for b in range(len(tc))]

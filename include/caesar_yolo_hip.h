@@ -215,6 +215,42 @@ int cy_attention(cy_ctx* ctx, const void* d_qkv, int B, int N, int ct, int coff,
 int cy_maxpool5(cy_ctx* ctx, const void* d_src, int B, int H, int W, int C, int ct, int src_coff, void* d_dst, int dst_coff,
                 void* stream);
 
+/* ---- test-time augmentation (ultralytics `model(img, augment=True)`, DetectionModel._predict_augment) ----------------------
+ * Three views of the letterboxed batch: (scale 1, no flip), (0.83, left-right flip), (0.67, no flip); a scaled view is the
+ * bilinear resize (align_corners=False) of the flipped / plain batch to (int(H s), int(W s)), padded right and bottom with 0.447
+ * up to multiples of 32.  Each view's Detect output is divided by s, the flipped view's x centre mirrored with W, the stride-32
+ * anchors of view 0 and the stride-8 anchors of view 2 dropped, and the three concatenated before the unchanged NMS and
+ * scale_boxes.  Kept-box indices (d_det_anchor) are positions in that concatenation. */
+typedef struct cy_augment_view {
+    double scale; int flip;   /* 1, 0.83, 0.67; 1 = left-right flip */
+    int ch, cw;               /* resized content (int(H * scale), int(W * scale)) */
+    int Hp, Wp;               /* padded network input (ceil(H * scale / 32) * 32, ...) */
+    int A;                    /* anchors of the view's head output */
+    int lo, hi;               /* anchors kept: [lo, hi) */
+    int off;                  /* position of anchor lo in the concatenation */
+} cy_augment_view;
+typedef struct cy_augment_geom { cy_augment_view v[3]; int total; } cy_augment_geom;
+/* host-only: the views of an H x W letterboxed input (multiples of 32) */
+int cy_augment_geometry(int H, int W, cy_augment_geom* out);
+/* allocates, once, the per-buffer-set view inputs, view head outputs and the larger candidate buffers (capacity: the
+ * concatenated anchor count of a max_h x max_w input, at most 30000, or max_cand when given).  The calls below fail with
+ * CY_ERR_STATE on a context without it. */
+int cy_enable_augment(cy_ctx* ctx);
+/* cy_letterbox_pack into an fp32 canvas whatever the context precision (the source of the views in the fp16 context) */
+int cy_letterbox_pack_f32(cy_ctx* ctx, const double* d_planes, int B, int h0, int w0, int imgsz, float* d_out, void* stream);
+/* view kernel (kernel-level test entry): d_src fp32 [B][H][W][4] letterboxed -> d_view1 / d_view2 [B][Hp][Wp][4] in the context's
+ * input type; d_view0 (fp16 context only, may be NULL) receives the fp16 copy of d_src.  One launch. */
+int cy_augment_pack(cy_ctx* ctx, const float* d_src, int B, int H, int W, void* d_view0, void* d_view1, void* d_view2, void* stream);
+/* the views' raw head outputs (as cy_forward writes them) -> decode + NMS over the concatenation + scale_boxes; H, W = view 0 */
+int cy_decode_nms_augmented(cy_ctx* ctx, const float* d_pred0, const float* d_pred1, const float* d_pred2, int B, int H, int W,
+                            int h0, int w0, float conf, float iou, float* d_det, int* d_det_anchor, int* d_count, void* stream);
+/* cy_detect_tiles with augment != 0: the same per-tile path, pipelining and ordering contract, on the three views (their forwards
+ * back to back on the forward stream); augment = 0 is cy_detect_tiles itself.  Plain and augmented calls may alternate in one
+ * unflushed pipeline (cy_detect_flush covers both). */
+int cy_detect_tiles_augmented(cy_ctx* ctx, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw,
+                              int imgsz, const cy_preproc_cfg* cfg, float conf, float iou, double thr_soft, double thr_hard,
+                              int augment, float* d_out, int* d_out_count, int* d_status, void* stream);
+
 /* ---- catalog records and cross-tile merge (host code, no GPU) --------------------------------- */
 /* Analyzer.make_json_results (caesar_yolo/evaluation.py:418-469: int() truncation, tile-local edge rule, tile origin)
  * followed by SFinder.find_sources_at_edge (caesar_yolo/inference.py:663-726).

@@ -10,7 +10,9 @@ Differences that come with the MI355X engine:
   multi-GPU  = one process per GPU: `python -m torch.distributed.run --nproc-per-node N scripts/run.py ...`
              (replaces `mpirun -np N`, test/run_inference_parallel.sh:47-52);
   --precision fp16x3|fp32|fp16 (default fp16x3 = the fast parity context: fp16 high + low halves, fp32 accumulate; fp32 = exact fp32
-  FMA chains, 2.7x slower; fp16 = throughput mode, 3x faster, ~2 % of detections differ), --tile_batch N  are new.
+  FMA chains, 2.7x slower; fp16 = throughput mode, 3x faster, ~2 % of detections differ), --tile_batch N  are new;
+  --augment  (new) test-time augmentation of every model call, ultralytics' augment=True: the tile, its 0.83-scale left-right
+             flip and its 0.67-scale view through the network, one NMS over the three (about 2.2x the network work per tile).
 """
 import argparse
 import logging
@@ -81,6 +83,8 @@ def parse_args(argv=None):
                         'fp32: exact fp32 FMA chains (the reference\'s own arithmetic), ~2.7x slower than fp16x3.  fp16: throughput mode, fp16 '
                         'operands / fp32 accumulate, ~3x the fp16x3 rate; 2-4 %% of the detections differ from the fp32 run (DESIGN.md section 2)')
     p.add_argument('--tile_batch', type=int, default=64)
+    p.add_argument('--augment', dest='augment', action='store_true',
+                   help='test-time augmentation (ultralytics augment=True): three views per tile, one joint NMS')
     return p.parse_args(argv)
 
 
@@ -159,7 +163,7 @@ def main(argv=None):
               'save_plot': args.save_plots,
               'save_tile_catalog': args.save_tile_catalog, 'save_tile_region': args.save_tile_region,
               'save_tile_img': args.save_tile_img,
-              'precision': args.precision})
+              'precision': args.precision, 'augment': args.augment})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,
                  max_imgsz=max(args.imgsize, 32))
     sfinder = SFinder(model, C)

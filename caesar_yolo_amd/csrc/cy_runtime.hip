@@ -82,6 +82,8 @@ int fail(cy_ctx* c, int code, const std::string& m) { if (c) c->err = m; g_err =
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline size_t esize(Precision p) { return p == PREC_F16 ? 2 : 4; }      // bytes per activation value (fp16x3: two fp16 halves)
 inline Precision io_prec(Precision p) { return p == PREC_F16X3 ? PREC_F32 : p; }   // type of the network input buffer
+// candidate capacity per tile: n (<= CY_MAX_CAND) rounded up to 64, kept within the 16-bit slot field of the NMS sort key
+inline int cand_capacity(int n) { const int r = (n + 63) / 64 * 64; return r > CY_MAX_CAND ? CY_MAX_CAND : r; }
 // depth-wise 3x3 filter [C][1][3][3] -> the [9][C] fp32 layout of dwconv3x3_kernel (weight loader, test entry cy_dwconv3x3)
 std::vector<float> dw_weights(const float* W, int C) {
     std::vector<float> dw(9 * (size_t)C);
@@ -454,12 +456,11 @@ int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
     c->ws_bytes = act;
     HIPCHK(c, hipMalloc(&c->ws, c->ws_bytes));
     const int A = cy_num_anchors(g.max_h, g.max_w);
-    // candidates per tile: ultralytics keeps at most max_nms = 30000 by score; with cap >= the anchor count of the largest
-    // letterboxed tile an overflow cannot happen (8400 anchors at 640x640).  A smaller explicit max_cand is honoured, and a
-    // tile that overflows it is counted (cy_detect_counters) -- its surplus candidates are dropped in arrival order.
-    c->cap = g.max_cand > 0 ? g.max_cand : A;
-    if (c->cap > 30000) c->cap = 30000;
-    c->cap = (c->cap + 63) / 64 * 64;
+    // candidates per tile: cap >= the anchor count of the largest letterboxed tile, so an overflow cannot happen; nms_kernel
+    // sorts them all and keeps ultralytics' top max_nms = 30000 by score.  An explicit max_cand is honoured, and a tile that
+    // overflows it is counted (cy_detect_counters) -- its surplus candidates are dropped in arrival order.  cy_create has
+    // checked both against CY_MAX_CAND (the 16-bit fields of the NMS sort key).
+    c->cap = cand_capacity(g.max_cand > 0 ? g.max_cand : A);
     c->cap_pow2 = 1; while (c->cap_pow2 < c->cap) c->cap_pow2 <<= 1;
     const size_t Bm = g.max_batch;
     c->pre_scratch_elems = Bm * 3 * (size_t)g.max_h * g.max_w;
@@ -521,6 +522,14 @@ int cy_create(int device, const cy_config* cfg, cy_ctx** out) {
     if (cfg->max_batch < 1 || cfg->max_h < 32 || cfg->max_w < 32 || cfg->max_h % 32 || cfg->max_w % 32)
         return fail(nullptr, CY_ERR_ARG, "max_batch >= 1 and max_h/max_w multiples of 32 required");
     if (cfg->precision != CY_F16 && cfg->precision != CY_F32 && cfg->precision != CY_F16X3) return fail(nullptr, CY_ERR_ARG, "bad precision");
+    const int A = cy_num_anchors(cfg->max_h, cfg->max_w);
+    if (A > CY_MAX_CAND)
+        return fail(nullptr, CY_ERR_ARG, "max_h x max_w = " + std::to_string(cfg->max_h) + " x " + std::to_string(cfg->max_w) + ": " +
+                                             std::to_string(A) + " anchors, more than CY_MAX_CAND = " + std::to_string(CY_MAX_CAND) +
+                                             " (16-bit anchor field of the NMS sort key)");
+    if (cfg->max_cand > CY_MAX_CAND)
+        return fail(nullptr, CY_ERR_ARG, "max_cand " + std::to_string(cfg->max_cand) + " exceeds CY_MAX_CAND = " + std::to_string(CY_MAX_CAND) +
+                                             " (16-bit slot field of the NMS sort key)");
     int n = 0;
     const hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || device < 0 || device >= n)
@@ -1331,6 +1340,7 @@ int cy_decode_nms(cy_ctx* c, const float* d_pred, int B, int H, int W, int h0, i
                   float* d_det, int* d_det_anchor, int* d_count, void* stream) {
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
     if (!d_pred || !d_det || !d_det_anchor || !d_count || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
+    if (H > c->cfg.max_h || W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "input exceeds max_h/max_w of the context");
     hipStream_t s = (hipStream_t)stream;
     DecodeArgs d{};
     d.pred = d_pred; d.B = B; d.A = cy_num_anchors(H, W); d.nc = c->plan.nc; d.conf = conf;
@@ -1525,11 +1535,13 @@ int cy_enable_augment(cy_ctx* c) {
     cy_augment_geom ag;
     if (cy_augment_geometry(g.max_h, g.max_w, &ag)) return fail(c, CY_ERR_ARG, "bad context geometry");
     const size_t es = esize(c->prec), Bm = g.max_batch;
-    // candidates per tile: as the plain path (cap = anchors of the largest input, at most ultralytics' max_nms), over the
+    // candidates per tile: as the plain path (cap = anchors of the largest input; NMS keeps the top max_nms by score), over the
     // concatenation of the three views; an explicit max_cand is honoured
-    c->acap = g.max_cand > 0 ? g.max_cand : ag.total;
-    if (c->acap > 30000) c->acap = 30000;
-    c->acap = (c->acap + 63) / 64 * 64;
+    if (ag.total > CY_MAX_CAND)
+        return fail(c, CY_ERR_ARG, "test-time augmentation of a " + std::to_string(g.max_h) + " x " + std::to_string(g.max_w) +
+                                   " context: " + std::to_string(ag.total) + " concatenated anchors, more than CY_MAX_CAND = " +
+                                   std::to_string(CY_MAX_CAND) + " (16-bit index of the NMS sort key)");
+    c->acap = cand_capacity(g.max_cand > 0 ? g.max_cand : ag.total);
     c->acap_pow2 = 1; while (c->acap_pow2 < c->acap) c->acap_pow2 <<= 1;
     const int nc = c->plan.nc;
     for (auto& b : c->ab) {

@@ -233,20 +233,38 @@ class HipDetector(object):
         d = tuple(dims)
         return buf[:int(np.prod(d))].reshape(d)
 
-    def decode_nms(self, pred, H, Wd, h0, w0, conf, iou):
+    def _det_out(self, B, out):
+        """(det [B,300,6] fp32, index [B,300] int32, count [B] int32): the caller's tensors (out) or zero-filled new ones."""
+        if out is not None:
+            det, anch, cnt = out
+            assert det.shape == (B, L.CY_MAX_DET, 6) and anch.shape == (B, L.CY_MAX_DET) and cnt.shape == (B,)
+            assert det.dtype == torch.float32 and anch.dtype == torch.int32 and cnt.dtype == torch.int32
+            assert det.is_contiguous() and anch.is_contiguous() and cnt.is_contiguous()
+            return det, anch, cnt
+        return (torch.zeros((B, L.CY_MAX_DET, 6), dtype=torch.float32, device=self.tdev),
+                torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev),
+                torch.zeros((B,), dtype=torch.int32, device=self.tdev))
+
+    def decode_nms(self, pred, H, Wd, h0, w0, conf, iou, out=None):
+        """pred [B, A, 64+nc] fp32 raw head output -> (det, anchor index, count); out: optional (det, index, count) to write."""
         B = pred.shape[0]
-        det = torch.zeros((B, L.CY_MAX_DET, 6), dtype=torch.float32, device=self.tdev)
-        anch = torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev)
-        cnt = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
+        det, anch, cnt = self._det_out(B, out)
         self._chk(self.lib.cy_decode_nms(self.ctx, self._p(pred), B, H, Wd, h0, w0, conf, iou, self._p(det),
                                          self._p(anch), self._p(cnt), self._stream()))
         return det, anch, cnt
 
-    def iou_merge(self, det, cnt, score_thr, soft, hard):
+    def iou_merge(self, det, cnt, score_thr, soft, hard, out=None):
+        """-> (merged det, count, source row); out: optional (det, count, source row) tensors to write."""
         B = det.shape[0]
-        out = torch.zeros_like(det)
-        ocnt = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
-        osrc = torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev)
+        if out is not None:
+            out, ocnt, osrc = out
+            assert out.shape == det.shape and ocnt.shape == (B,) and osrc.shape == (B, L.CY_MAX_DET)
+            assert out.dtype == torch.float32 and ocnt.dtype == torch.int32 and osrc.dtype == torch.int32
+            assert out.is_contiguous() and ocnt.is_contiguous() and osrc.is_contiguous()
+        else:
+            out = torch.zeros_like(det)
+            ocnt = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
+            osrc = torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev)
         self._chk(self.lib.cy_iou_merge(self.ctx, self._p(det), self._p(cnt), B, score_thr, soft, hard, self._p(out),
                                         self._p(ocnt), self._p(osrc), self._stream()))
         return out, ocnt, osrc
@@ -302,13 +320,11 @@ class HipDetector(object):
                                            self._p(outs[1]), self._p(outs[2]), self._stream()))
         return outs
 
-    def decode_nms_augmented(self, preds, H, Wd, h0, w0, conf, iou):
+    def decode_nms_augmented(self, preds, H, Wd, h0, w0, conf, iou, out=None):
         """preds: the three views' raw head outputs (forward()); H, Wd: view 0.  -> (det, concatenated index, count) as decode_nms."""
         self.enable_augment()
         B = preds[0].shape[0]
-        det = torch.zeros((B, L.CY_MAX_DET, 6), dtype=torch.float32, device=self.tdev)
-        anch = torch.zeros((B, L.CY_MAX_DET), dtype=torch.int32, device=self.tdev)
-        cnt = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
+        det, anch, cnt = self._det_out(B, out)
         self._chk(self.lib.cy_decode_nms_augmented(self.ctx, self._p(preds[0]), self._p(preds[1]), self._p(preds[2]), B, H, Wd, h0, w0,
                                                    conf, iou, self._p(det), self._p(anch), self._p(cnt), self._stream()))
         return det, anch, cnt

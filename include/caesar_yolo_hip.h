@@ -35,14 +35,16 @@ enum cy_precision { CY_F16 = 0, CY_F32 = 1, CY_F16X3 = 2 };
 #define CY_MAX_DET 300        /* ultralytics max_det */
 #define CY_DET_STRIDE 6       /* x1,y1,x2,y2,score,class */
 #define CY_MAX_STAGES 8
+#define CY_MAX_CAND 65535     /* candidates per tile and anchors per input: the 16-bit slot and anchor fields of the NMS sort key */
 
 typedef struct cy_config {
     int precision;            /* cy_precision */
     int max_batch;            /* tiles per launch the workspace is sized for */
     int max_h, max_w;         /* largest letterboxed network input (multiple of 32) */
-    int max_cand;             /* candidate capacity per tile before NMS (<= 30000 = ultralytics max_nms); 0 -> the anchor
-                                 count of a max_h x max_w input (no overflow possible); a tile that overflows a smaller
-                                 explicit capacity is counted in cy_detect_counters */
+    int max_cand;             /* candidate capacity per tile before NMS (<= CY_MAX_CAND); 0 -> the anchor count of a
+                                 max_h x max_w input (no overflow possible: NMS then keeps the top max_nms = 30000 by score,
+                                 as ultralytics); a tile that overflows an explicit capacity is counted in cy_detect_counters.
+                                 cy_create refuses max_h x max_w with more than CY_MAX_CAND anchors (from 1792 x 1792) */
 } cy_config;
 
 /* Preprocessing program: the CLI-fixed stage order of scripts/run.py:272-302, one op list per output channel.
@@ -178,8 +180,9 @@ int cy_compact_records_ctx(cy_ctx* ctx, const float* d_gathered, long long n_row
 /* events the reference would not survive silently, accumulated over cy_decode_nms / cy_iou_merge / cy_detect_tiles calls:
  * out4[0] degenerate boxes (x1 >= x2 or y1 >= y2) dropped before the IoU merge -- the reference aborts on them inside
  * get_iou's assert (caesar_yolo/utils.py:78-81); out4[1] tiles with more candidates than the
- * context's capacity (ultralytics keeps the top max_nms = 30000 by score; here the surplus is dropped in arrival order, so
- * a non-zero count means "raise max_cand"); out4[2], out4[3]: performance diagnostics of the sigma-clip statistics (median
+ * context's explicit max_cand (the default capacity, the anchor count, cannot overflow; NMS keeps the top max_nms = 30000
+ * by score as ultralytics does, but the surplus over max_cand is dropped in arrival order, so a non-zero count means "raise
+ * max_cand"); out4[2], out4[3]: performance diagnostics of the sigma-clip statistics (median
  * selections served by the one-pass bracket / fallen back to the three-pass radix select).  Synchronises the device.
  * reset != 0 clears them. */
 int cy_detect_counters(cy_ctx* ctx, long long* out4, int reset);
@@ -233,8 +236,8 @@ typedef struct cy_augment_geom { cy_augment_view v[3]; int total; } cy_augment_g
 /* host-only: the views of an H x W letterboxed input (multiples of 32) */
 int cy_augment_geometry(int H, int W, cy_augment_geom* out);
 /* allocates, once, the per-buffer-set view inputs, view head outputs and the larger candidate buffers (capacity: the
- * concatenated anchor count of a max_h x max_w input, at most 30000, or max_cand when given).  The calls below fail with
- * CY_ERR_STATE on a context without it. */
+ * concatenated anchor count of a max_h x max_w input, or max_cand when given).  Fails with CY_ERR_ARG when that anchor
+ * count exceeds CY_MAX_CAND (from 1376 x 1376).  The calls below fail with CY_ERR_STATE on a context without it. */
 int cy_enable_augment(cy_ctx* ctx);
 /* cy_letterbox_pack into an fp32 canvas whatever the context precision (the source of the views in the fp16 context) */
 int cy_letterbox_pack_f32(cy_ctx* ctx, const double* d_planes, int B, int h0, int w0, int imgsz, float* d_out, void* stream);

@@ -47,20 +47,27 @@ def predict_augment_raw(net, x, scales=SCALES, flips=FLIPS):
     """-> (concatenated decoded prediction [B, 4+nc, A'], raw head outputs of the views [B, 64+nc, A_k]).  With the three standard
     views the stride-32 anchors of view 0 and the stride-8 anchors of view 2 are dropped (_clip_augmented); a single view is
     the plain prediction."""
-    W = x.shape[-1]
-    ys, raws = [], []
-    for xi, s, f in zip(views(x, scales, flips), scales, flips):
-        raw = net.forward(xi)
-        yi = Y.decode(raw, net.level_shapes, net.nc)
+    raws, shapes = [], []
+    for xi in views(x, scales, flips):
+        raws.append(net.forward(xi))
+        shapes.append(net.level_shapes)
+    return decode_views(raws, shapes, net.nc, x.shape[-1], scales, flips), raws
+
+
+def decode_views(raws, level_shapes, nc, W, scales=SCALES, flips=FLIPS):
+    """The views' raw head outputs [B, 64+nc, A_k] (level shapes of each view) -> the concatenated decoded prediction; W: width of
+    view 0 (the mirror of the flipped view)."""
+    ys = []
+    for raw, shp, s, f in zip(raws, level_shapes, scales, flips):
+        yi = Y.decode(raw, shp, nc)
         yi[:, :4] /= s                                    # divided by s itself, not by the integer size ratio
         if f == 3:
             yi[:, 0] = W - yi[:, 0]
         ys.append(yi)
-        raws.append(raw)
     if len(ys) == 3:
         rng = clip_ranges([y.shape[-1] for y in ys])
         ys = [y[..., lo:hi] for y, (lo, hi) in zip(ys, rng)]
-    return torch.cat(ys, -1), raws
+    return torch.cat(ys, -1)
 
 
 @torch.no_grad()

@@ -79,7 +79,10 @@ def test_augmented_calls_need_the_context_enabled():
 @pytest.mark.parametrize("name,imgsz,conf,iou", [("big512", 512, 0.5, 0.5), ("rag", 256, 0.25, 0.7), ("galaxy", 640, 0.7, 0.5),
                                                  # conf ~ 0 at 640: ~15000 candidates (> 8192: the global-memory sort of nms_kernel)
                                                  ("galaxy", 640, 0.001, 0.7),
-                                                 ("big512", 1024, 0.6, 0.5)])
+                                                 ("big512", 1024, 0.6, 0.5),
+                                                 # conf ~ 0 at 1024: more than max_nms = 30000 candidates over the three views (the
+                                                 # default capacity holds them all; NMS keeps the top 30000 by score)
+                                                 ("big512", 1024, 0.001, 0.7)])
 def test_decode_nms_augmented_on_oracle_logits(name, imgsz, conf, iou):
     """cy_decode_nms_augmented on the oracle's raw head outputs of the three views: kept concatenated-index list identical (order
     included), boxes and scores within 1e-4 relative, classes equal."""

@@ -87,7 +87,8 @@ def test_analyzer_predict_contract(tmp_path, monkeypatch):
 
 def test_counters_report_candidate_overflow_and_degenerate_boxes():
     """A context with a deliberately small candidate capacity counts the tiles that overflow it (cy_detect_counters); the
-    default capacity (= anchor count) cannot overflow even at conf 0."""
+    default capacity (= anchor count) does not overflow even at conf 0, also where a tile has more than max_nms = 30000
+    candidates (1280 px: 33600 anchors), which NMS itself cuts to the top 30000 by score."""
     from caesar_yolo_amd.model import HipDetector
     from caesar_yolo_amd import preprocessing as PP
     g = np.load(os.path.join(ROOT, "tests/golden/preproc.npz"))
@@ -105,6 +106,26 @@ def test_counters_report_candidate_overflow_and_degenerate_boxes():
     d, cnt, st = full.detect_tiles(mosaic, [(0, 0)], 192, 192, 192, cfg, 0.0, IOU, SOFT, HARD)
     assert full.counters()["cand_overflow_tiles"] == 0 and int(cnt[0]) > 0
     full.close()
+    import postproc_cases as P
+    big = HipDetector(seeded_weights()[0], device=0, precision="fp16", max_batch=1, max_imgsz=1280)
+    r = P.Raw(1, 1280, 1280, 5)                                   # every anchor a candidate at conf 0
+    d, _, cnt = big.decode_nms(P.device_layout(r.raw).cuda(), 1280, 1280, 1280, 1280, 0.0, IOU)
+    assert big.counters()["cand_overflow_tiles"] == 0 and int(cnt[0]) == 300
+    big.close()
+
+
+def test_augmented_context_beyond_the_sort_key_is_refused():
+    """cy_enable_augment refuses a context whose three views have more than CY_MAX_CAND = 65535 concatenated anchors (1376 px:
+    68401), naming the limit; 1344 px (65210) is accepted."""
+    from caesar_yolo_amd.model import HipDetector
+    from caesar_yolo_amd import lib as L
+    det = HipDetector(seeded_weights("n", 5)[0], device=0, precision="fp32", max_batch=1, max_imgsz=1376)
+    with pytest.raises(L.CyError, match="65535"):
+        det.enable_augment()
+    det.close()
+    det = HipDetector(seeded_weights("n", 5)[0], device=0, precision="fp32", max_batch=1, max_imgsz=1344)
+    det.enable_augment()
+    det.close()
 
 
 def test_analyzer_plot_and_preprocessed_fits(tmp_path, monkeypatch):

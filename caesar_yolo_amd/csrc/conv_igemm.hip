@@ -832,7 +832,7 @@ __global__ __launch_bounds__(512) void head1x1_pair_kernel(const ConvArgs a, con
 // L2->LDS traffic per flop drops ~3x (TH=16: 185 KB per 37.7 MFLOP = 204 flop/B).  Zero padding of the halo and of
 // ragged image edges comes from the buffer range check, as in the generic kernel.
 
-template <int WM, int RING, int PB = 2>
+template <int WM, int RING>
 __global__ __launch_bounds__(WM * 128) void conv3x3_halo_kernel(const ConvArgs a) {
     constexpr int TH = 4 * WM, TW = 16, NT = WM * 128, NW = NT / 64, BN = 128;
     constexpr int PR = (TH + 2) * (TW + 2);                 // halo rows (one row = one pixel, 64 channels = 128 B)
@@ -843,7 +843,7 @@ __global__ __launch_bounds__(WM * 128) void conv3x3_halo_kernel(const ConvArgs a
     constexpr int DIST = RING - 1;                           // weight slabs in flight: tap t+DIST is fetched while tap t computes
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const Pbuf = smem;
-    char* const Wbuf = smem + PB * P_BYTES;              // [halo 0 (| halo 1) | weight ring]
+    char* const Wbuf = smem + 2 * P_BYTES;               // [halo 0 | halo 1 | weight ring]
     typedef __attribute__((address_space(3))) void lds_void;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -944,17 +944,10 @@ __global__ __launch_bounds__(WM * 128) void conv3x3_halo_kernel(const ConvArgs a
     unsigned long long acc_dma = 0, acc_cmp = 0, acc_wait = 0, acc_bar = 0;
     const unsigned long long t_begin = stamps ? stamp_now() : 0;
     for (int ch = 0; ch < chunks; ++ch) {
-        const char* P = Pbuf + (PB == 2 ? (ch & 1) : 0) * P_BYTES;
-        if (PB == 1 && ch > 0) {
-            // single halo buffer: every wave is past the last tap's barrier, so the buffer is free; fetch the next
-            // 64-channel halo now and wait for it (once per nine taps) -- the LDS saved buys a third weight slot
-            dma_patch(0, ch);
-            CY_WAIT_VM(0);
-            __builtin_amdgcn_s_barrier();
-        }
+        const char* P = Pbuf + (ch & 1) * P_BYTES;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap, ++it) {
-            const bool pre_p = PB == 2 && tap == 0 && ch + 1 < chunks, pre_w = it + DIST < total;
+            const bool pre_p = tap == 0 && ch + 1 < chunks, pre_w = it + DIST < total;
             unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
             if (stamps) { __builtin_amdgcn_sched_barrier(0); t0 = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
             if (pre_p) dma_patch((ch + 1) & 1, ch + 1);
@@ -1697,14 +1690,13 @@ static hipError_t launch_halo2(const ConvArgs& a, hipStream_t s) {
 // per wave and stage, 32 MFMAs per wave between barriers.
 // DUAL = true: maps at most 16 pixels wide (the stride-32 level of a 512-px tile): the 32 patch columns are the 16 columns of
 // TWO consecutive images, each with its own left/right halo column (patch rows of 36 instead of 34 pixels).
-template <bool TAIL, int WN, bool DUAL = false, int TPS = 2, bool SPLIT = false, int SCHED = 0>
+template <bool TAIL, int WN, bool DUAL = false, int TPS = 2, bool SPLIT = false>
 __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
-    // SCHED = 1 (round 4 experiment, CY_WIDE_SCHED=1): the eight fragment reads of a half-step are spread between the 16 MFMAs of the
-    // previous one (sched_group_barrier: one ds_read_b128 per two MFMAs) instead of where the compiler sinks them
+    // TAIL and TPS are single-valued; they keep their places because the profile summaries read WN, DUAL and SPLIT by position
+    static_assert(TAIL && TPS == 2, "the last 16 MFMAs of a stage run behind its barrier; two taps per stage");
     // SPLIT (fp16x3 context): three passes over the input channels -- halo slabs of [x_lo | x_hi | x_hi] against the weight
     // slabs [w_hi | w_lo | w_hi] of the packed copy, i.e. the same stage loop over 3x the slab pairs; scaled / split epilogue
-    // TPS = taps per stage (between two barriers): 2, or 3 (WN = 2 only: six stages of 96 MFMAs per slab pair, 152 KiB of LDS)
-    static_assert(TPS == 2 || (TPS == 3 && WN == 2), "three taps per stage: 128-channel variant only");
+    // TPS = taps per stage (between two barriers)
     constexpr int NST = 18 / TPS;
     constexpr int TH = 16, TW = 32, NW = 8, BN = 64 * WN, PWID = DUAL ? 36 : TW + 2, HALF = DUAL ? 18 : 16;
     constexpr int RPW = TH / (NW / WN), MIW = 2 * RPW, WPS = WN == 2 ? TPS : 1;   // image rows / pixel fragments per wave; weight pieces per wave and stage
@@ -1816,8 +1808,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
     auto stage_compute = [&](int st) {                       // taps u = TPS*st .. of the current slab pair
         const int u0 = TPS * st, u1 = u0 + 1, t0 = u0 % 9, t1 = u1 % 9;
         const int p0 = (u0 / 9) * P_BYTES, p1 = (u1 / 9) * P_BYTES, w0 = (st % 3) * W_BYTES, w1 = w0 + SLAB;
-        if constexpr (TPS == 3) {                             // six half-steps, fragments double-buffered one half-step ahead
-            const int u2 = u0 + 2, t2 = u2 % 9, p2 = (u2 / 9) * P_BYTES, w2 = w1 + SLAB;
+        if constexpr (WN == 2) {
             load_w(wb[0], w0);
             load_x(xa[0], p0, t0 / 3, t0 % 3, 0);
             load_x(xa[1], p0, t0 / 3, t0 % 3, 1);
@@ -1829,43 +1820,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             load_x(xa[1], p1, t1 / 3, t1 % 3, 1);
             mma(wb[1], xa[0], 0);
-            __builtin_amdgcn_sched_barrier(0);
-            load_w(wb[0], w2);
-            load_x(xa[0], p2, t2 / 3, t2 % 3, 0);
-            mma(wb[1], xa[1], 1);
-            __builtin_amdgcn_sched_barrier(0);
-            load_x(xa[1], p2, t2 / 3, t2 % 3, 1);
-            mma(wb[0], xa[0], 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (!TAIL) mma(wb[0], xa[1], 1);
-        } else if constexpr (WN == 2) {
-            load_w(wb[0], w0);
-            load_x(xa[0], p0, t0 / 3, t0 % 3, 0);
-            load_x(xa[1], p0, t0 / 3, t0 % 3, 1);
-            mma(wb[0], xa[0], 0);
-            if constexpr (SCHED != 0 && TAIL) {              // region = [tail MFMAs of the previous stage, 12 reads, 16 MFMAs]
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); }
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            load_w(wb[1], w1);
-            load_x(xa[0], p1, t1 / 3, t1 % 3, 0);
-            mma(wb[0], xa[1], 1);
-            if constexpr (SCHED != 0) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            load_x(xa[1], p1, t1 / 3, t1 % 3, 1);
-            mma(wb[1], xa[0], 0);
-            if constexpr (SCHED != 0) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (!TAIL) mma(wb[1], xa[1], 1);                 // TAIL: the last 16 MFMAs are issued behind the stage barrier
+            __builtin_amdgcn_sched_barrier(0);              // the last 16 MFMAs are issued behind the stage barrier
         } else {                                             // one half-step (4 fragments = this wave's 64 pixels) per tap
             load_w(wb[0], w0);
             load_x(xa[0], p0, t0 / 3, t0 % 3, 0);
@@ -1873,7 +1828,6 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
             load_x(xa[1], p1, t1 / 3, t1 % 3, 0);
             mma(wb[0], xa[0], 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (!TAIL) mma(wb[1], xa[1], 0);
         }
     };
 
@@ -1928,29 +1882,19 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
             else if (more) dma_stage((st + 2) % 3, 2 * cp + 2, TPS * (st + 2 - NST));
             // halo: odd slab of this pair (first read in stage NST/2, rounded up) and even slab of the next pair (its buffer
             // is free once the stage holding tap 8 is done)
-            constexpr int ST_EVEN = TPS == 2 ? 5 : 3;
             if (st == 0) dma_patch(1, 2 * cp + 1);
-            if (st == ST_EVEN && more) dma_patch(0, 2 * cp + 2);
+            if (st == 5 && more) dma_patch(0, 2 * cp + 2);
             stage_compute(st);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // the weights of stage g+1 (requested first thing in stage g-1) must have landed; younger requests may fly on
-            if constexpr (TPS == 2) {
-                if (st == 0 || st == 1) { CY_WAIT_VM(WPS + PROUNDS); }
-                else if (st == 5 || st == 6) { if (more) { CY_WAIT_VM(WPS + PROUNDS); } else { CY_WAIT_VM(WPS); } }
-                else if (has_w) { CY_WAIT_VM(WPS); }
-                else { CY_WAIT_VM(0); }
-            } else {
-                // a halo patch requested in stage 0 / 3 is first read in stage 3 / (next pair's) 0: it may stay in flight for two stages
-                if (st == 0 || st == 1) { CY_WAIT_VM(WPS + PROUNDS); }
-                else if (st == 3) { if (more) { CY_WAIT_VM(WPS + PROUNDS); } else { CY_WAIT_VM(WPS); } }
-                else if (st == 4) { if (more) { CY_WAIT_VM(WPS + PROUNDS); } else { CY_WAIT_VM(0); } }
-                else if (has_w) { CY_WAIT_VM(WPS); }
-                else { CY_WAIT_VM(0); }
-            }
+            if (st == 0 || st == 1) { CY_WAIT_VM(WPS + PROUNDS); }
+            else if (st == 5 || st == 6) { if (more) { CY_WAIT_VM(WPS + PROUNDS); } else { CY_WAIT_VM(WPS); } }
+            else if (has_w) { CY_WAIT_VM(WPS); }
+            else { CY_WAIT_VM(0); }
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (TAIL) mma(wb[TPS == 3 ? 0 : 1], xa[1], WN == 2 ? 1 : 0);    // operands are in registers: overlaps the next stage's DMA issue / first reads
+            mma(wb[1], xa[1], WN == 2 ? 1 : 0);    // operands are in registers: overlaps the next stage's DMA issue / first reads
         }
     }
 
@@ -2090,259 +2034,18 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
     }
 }
 
-template <int WN, bool DUAL = false, int TPS = 2, bool SPLIT = false, int SCHED = 0>
+template <int WN, bool DUAL = false, bool SPLIT = false>
 static hipError_t launch_wide(const ConvArgs& a, hipStream_t s) {
     constexpr int PR = 18 * (DUAL ? 36 : 34), NPC = (PR + 15) / 16, PROUNDS = (NPC + 7) / 8, BN = 64 * WN;
-    const size_t lds = 2 * PROUNDS * 8 * 1024 + 3 * TPS * BN * 64 + 1024;       // halo x2, weight ring, bias
+    const size_t lds = 2 * PROUNDS * 8 * 1024 + 3 * 2 * BN * 64 + 1024;       // halo x2, weight ring, bias
     static bool attr_set = false;
     if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wide_kernel<false, WN, DUAL, TPS, SPLIT, SCHED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wide_kernel<true, WN, DUAL, TPS, SPLIT, SCHED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wide_kernel<true, WN, DUAL, 2, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
     const int bx = DUAL ? (a.B + 1) / 2 : a.B * ((a.Wi + 31) / 32);
     const int blocks = bx * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + BN - 1) / BN);
-    static const int tail = getenv("CY_WIDE_TAIL") ? atoi(getenv("CY_WIDE_TAIL")) : 1;
-    if (tail) hipLaunchKernelGGL((conv3x3_wide_kernel<true, WN, DUAL, TPS, SPLIT, SCHED>), dim3(blocks), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv3x3_wide_kernel<false, WN, DUAL, TPS, SPLIT, SCHED>), dim3(blocks), dim3(512), lds, s, a);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ 3x3 s1, 512 px x 128 ch, 32x32x16 MFMA
-// Round 4 A/B experiment (CY_WIDE_MFMA=32): conv3x3_wide_kernel<true, 2> with its K loop on v_mfma_f32_32x32x16_f16 instead of
-// v_mfma_f32_16x16x32_f16 -- the same workgroup (16 x 32 px x 128 ch), wave tile (128 px x 64 ch = 4 x 2 blocks of 32 x 32, 128
-// accumulator registers), stage stream (halo x2, 3-slot weight ring, two taps per barrier, counted vmcnt, tail MFMAs behind the
-// barrier) and the same packed weights; half as many MFMA instructions, each holding the SIMD's vector issue for 8 of its 32 cycles
-// instead of 8 of 16.  A lane's fragment is (row lane & 31, 8 channels of K-step s at chunk 2 s + (lane >> 5)), so the 16 lanes of a
-// ds_read_b128 group read ONE chunk of 16 rows: the swizzle has to spread a row's chunk over all four 16-byte slots,
-// chunk' = chunk ^ f with f = (rx >> 2) & 3 of the halo column rx (not of the linear row index: a tap then shifts the lane's row by a
-// compile-time constant and only kw changes f -> six lane bases for the pixels, two for the weights), f = (row >> 4) & 3 for the
-// weight rows.  Weight rows are read through the permutation that makes a lane's 16 accumulator registers of a block 16 contiguous
-// output channels on the 16x16-ordered packed copy: MFMA row m of block ni <- packed row 16 (m >> 3) + 8 ni + 4 ((m >> 2) & 1) + (m & 3).
-// SCHED = 1: the fragment reads of the next K-step are spread between the MFMAs of the current one (one ds_read_b128 per 32-cycle
-// MFMA, sched_group_barrier) instead of wherever the compiler sinks them (in front of the last MFMA of the group, latency exposed).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int SCHED>
-__global__ __launch_bounds__(512) void conv3x3_wide32_kernel(const ConvArgs a) {
-    constexpr int NST = 9, TH = 16, TW = 32, NW = 8, BN = 128, PWID = TW + 2, RPW = 4;
-    constexpr int PR = (TH + 2) * PWID, NPC = (PR + 15) / 16, PROUNDS = (NPC + NW - 1) / NW;
-    constexpr int P_BYTES = PROUNDS * NW * 1024, SLAB = BN * 64, W_BYTES = 2 * SLAB, RING = 3, WPS = 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* const Pbuf = smem;
-    char* const Wbuf = smem + 2 * P_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int H = a.Hi, W = a.Wi;
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int cpad = pad128(a.Cout);
-    const int ntn = (pad64(a.Cout) + BN - 1) / BN;
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
-    const int nt = id % ntn;
-    int rest = id / ntn;
-    const int tx = rest % tiles_x; rest /= tiles_x;
-    const int ty = rest % tiles_y;
-    const int b = rest / tiles_y;
-    const int y0 = ty * TH, x0 = tx * TW, n0 = nt * BN;
-    const int pairs = a.Cin / 64;
-
-    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.in0), 0, a.in0_bytes, 0x00020000);
-    const auto rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wgt32), 0, a.wgt32_bytes, 0x00020000);
-    unsigned poff[PROUNDS];
-#pragma unroll
-    for (int j = 0; j < PROUNDS; ++j) {
-        const int r = (j * NW + wave) * 16 + (lane >> 2);
-        const int ry = r / PWID, rx = r - ry * PWID;
-        const int y = y0 + ry - 1, x = x0 + rx - 1;
-        const int q = (lane & 3) ^ ((rx >> 2) & 3);
-        const bool ok = r < PR && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-        poff[j] = ok ? (unsigned)(((b * H + y) * W + x) * a.in0_ct + a.in0_coff + q * 8) * 2u : CY_OOB;
-    }
-    unsigned woff;
-    {
-        const int row = wave * 16 + (lane >> 2);
-        woff = (unsigned)((n0 + row) * 64 + ((lane & 3) ^ ((row >> 4) & 3)) * 16);
-    }
-    auto dma_patch = [&](int buf, int slab) {
-#pragma unroll
-        for (int j = 0; j < PROUNDS; ++j)
-            dma_piece(rs0, (lds_ptr_t*)(Pbuf + buf * P_BYTES + (j * NW + wave) * 1024), poff[j], (unsigned)slab * 64u);
-    };
-    auto dma_stage = [&](int ring, int slab0, int u0) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int u = u0 + t, sl = slab0 + u / 9, tap = u % 9;
-            dma_piece(rsw, (lds_ptr_t*)(Wbuf + ring * W_BYTES + t * SLAB + wave * 1024), woff, (sl * 9 + tap) * cpad * 64);
-        }
-    };
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[ni][mi][j] = 0.f;
-    const int lr = lane & 31, lh = lane >> 5;
-    unsigned pbx[6], wlx[2];
-    const int rw0 = wm * RPW * PWID;
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-            pbx[kw * 2 + s] = (unsigned)((rw0 + kw + lr) * 64 + (((2 * s + lh) ^ (((kw + lr) >> 2) & 3)) << 4));
-    {
-        const int p0 = 16 * (lr >> 3) + 4 * ((lr >> 2) & 1) + (lr & 3);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) wlx[s] = (unsigned)(2 * P_BYTES + (wn * 64 + p0) * 64 + (((2 * s + lh) ^ (lr >> 3)) << 4));
-    }
-    f16x8 wa[2][2], xb[2][4];
-    auto load_k = [&](int bi, int pbuf_off, int wbuf_off, int kh, int kw, int s) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) wa[bi][ni] = *reinterpret_cast<const f16x8*>(smem + wlx[s] + (wbuf_off + ni * 512));
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) xb[bi][mi] = *reinterpret_cast<const f16x8*>(smem + pbx[kw * 2 + s] + (pbuf_off + (mi + kh) * PWID * 64));
-    };
-    auto mma = [&](int bi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa[bi][ni], xb[bi][mi], acc[ni][mi], 0, 0, 0);
-    };
-    auto stage_compute = [&](int st) {
-        const int u0 = 2 * st, u1 = u0 + 1, t0 = u0 % 9, t1 = u1 % 9;
-        const int p0 = (u0 / 9) * P_BYTES, p1 = (u1 / 9) * P_BYTES, w0 = (st % 3) * W_BYTES, w1 = w0 + SLAB;
-        load_k(0, p0, w0, t0 / 3, t0 % 3, 0);
-        load_k(1, p0, w0, t0 / 3, t0 % 3, 1);
-        mma(0);
-        if constexpr (SCHED != 0) {                          // region = [tail MFMAs of the previous stage, 12 reads, 8 MFMAs]
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        load_k(0, p1, w1, t1 / 3, t1 % 3, 0);
-        mma(1);
-        if constexpr (SCHED != 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        load_k(1, p1, w1, t1 / 3, t1 % 3, 1);
-        mma(0);
-        if constexpr (SCHED != 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);                  // the last 8 MFMAs of the stage are issued behind the stage barrier
-    };
-
-    float* const bias_lds = reinterpret_cast<float*>(smem + 2 * P_BYTES + RING * W_BYTES);
-    if (wave == 0) {
-        const auto rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, (unsigned)pad64(a.Cout) * 4u, 0x00020000);
-        dma_piece(rsb, (lds_ptr_t*)bias_lds, lane * 16 < BN * 4 ? (unsigned)(n0 * 4 + lane * 16) : CY_OOB, 0);
-    }
-    dma_patch(0, 0);
-    dma_stage(0, 0, 0);
-    dma_stage(1, 0, 2);
-    CY_WAIT_VM(WPS);
-    __builtin_amdgcn_s_barrier();
-#pragma unroll 1
-    for (int cp = 0; cp < pairs; ++cp) {
-        const bool more = cp + 1 < pairs;
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-            const bool has_w = st + 2 < NST || more;
-            if (st + 2 < NST) dma_stage((st + 2) % 3, 2 * cp, 2 * (st + 2));
-            else if (more) dma_stage((st + 2) % 3, 2 * cp + 2, 2 * (st + 2 - NST));
-            if (st == 0) dma_patch(1, 2 * cp + 1);
-            if (st == 5 && more) dma_patch(0, 2 * cp + 2);
-            stage_compute(st);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (st == 0 || st == 1) { CY_WAIT_VM(WPS + PROUNDS); }
-            else if (st == 5 || st == 6) { if (more) { CY_WAIT_VM(WPS + PROUNDS); } else { CY_WAIT_VM(WPS); } }
-            else if (has_w) { CY_WAIT_VM(WPS); }
-            else { CY_WAIT_VM(0); }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            mma(1);
-        }
-    }
-
-    // epilogue: lane (lr, lh) holds, per block (ni, mi), channels n0 + wn*64 + ni*32 + lh*16 + 0..15 of pixel (y0 + wm*4 + mi, x0 + lr)
-    const int x = x0 + lr;
-    const auto rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.res ? a.res : a.in0), 0,
-                                                       a.res ? (unsigned)((long)a.B * H * W * a.res_ct * 2) : 0u, 0x00020000);
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-        const int cl = wn * 64 + ni * 32 + lh * 16, cbase = n0 + cl;
-        const bool vec = cbase + 16 <= a.Cout, res_vec = a.res != nullptr && vec;
-        f16x8 rv[4][2];
-        if (res_vec) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                const int y = y0 + wm * RPW + mi;
-                const bool ok = y < H && x < W;
-                const unsigned ro = ok ? (unsigned)((((b * H + y) * W + x) * a.res_ct + a.res_coff + cbase) * 2) : CY_OOB;
-                rv[mi][0] = __builtin_bit_cast(f16x8, load_b128(rsr, ro, 0));
-                rv[mi][1] = __builtin_bit_cast(f16x8, load_b128(rsr, ro, 16));
-            }
-        }
-        float bv[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(bias_lds + cl + j * 4);
-            bv[j * 4] = t[0]; bv[j * 4 + 1] = t[1]; bv[j * 4 + 2] = t[2]; bv[j * 4 + 3] = t[3];
-        }
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            const int y = y0 + wm * RPW + mi;
-            if (y >= H || x >= W) continue;
-            const long pix = ((long)b * H + y) * W + x;
-            const f32x16& c = acc[ni][mi];
-            float v[16];
-            bias_act16(f32x4{c[0], c[1], c[2], c[3]}, f32x4{c[4], c[5], c[6], c[7]}, f32x4{c[8], c[9], c[10], c[11]},
-                       f32x4{c[12], c[13], c[14], c[15]}, bv, a.act != 0, v);
-            if (vec) {
-                f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-                if (res_vec) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { v[j] += (float)rv[mi][0][j]; v[8 + j] += (float)rv[mi][1][j]; }
-                }
-                f16x8 o0, o1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { o0[j] = (f16)v[j]; o1[j] = (f16)v[8 + j]; }
-                *reinterpret_cast<f16x8*>(dst) = o0;
-                *reinterpret_cast<f16x8*>(dst + 8) = o1;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int ch = cbase + j;
-                    if (ch >= a.Cout) continue;
-                    float t = v[j];
-                    if (a.res) t += (float)(reinterpret_cast<const f16*>(a.res)[pix * a.res_ct + a.res_coff + ch]);
-                    reinterpret_cast<f16*>(a.out)[pix * a.out_ct + a.out_coff + ch] = (f16)t;
-                }
-            }
-        }
-    }
-}
-
-template <int SCHED>
-static hipError_t launch_wide32(const ConvArgs& a, hipStream_t s) {
-    constexpr int PR = 18 * 34, NPC = (PR + 15) / 16, PROUNDS = (NPC + 7) / 8;
-    const size_t lds = 2 * PROUNDS * 8 * 1024 + 3 * 2 * 128 * 64 + 1024;        // halo x2, weight ring, bias
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wide32_kernel<SCHED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    const int blocks = a.B * ((a.Wi + 31) / 32) * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
-    hipLaunchKernelGGL(conv3x3_wide32_kernel<SCHED>, dim3(blocks), dim3(512), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_wide_kernel<true, WN, DUAL, 2, SPLIT>), dim3(blocks), dim3(512), lds, s, a);
     return hipGetLastError();
 }
 
@@ -3171,18 +2874,18 @@ static hipError_t launch_direct(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int WM, int RING, int PB = 2>
+template <int WM, int RING>
 static hipError_t launch_halo(const ConvArgs& a, hipStream_t s) {
     constexpr int TH = 4 * WM, NT = WM * 128;
     constexpr int PR = (TH + 2) * 18, NWI = (PR + 7) / 8, NW = NT / 64, PROUNDS = (NWI + NW - 1) / NW;
-    const size_t lds = PB * PROUNDS * NW * 1024 + RING * 128 * 128;
+    const size_t lds = 2 * PROUNDS * NW * 1024 + RING * 128 * 128;
     static bool attr_set = false;
     if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<WM, RING, PB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<WM, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
     const int blocks = a.B * ((a.Hi + TH - 1) / TH) * ((a.Wi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
-    hipLaunchKernelGGL((conv3x3_halo_kernel<WM, RING, PB>), dim3(blocks), dim3(NT), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<WM, RING>), dim3(blocks), dim3(NT), lds, s, a);
     return hipGetLastError();
 }
 
@@ -3262,7 +2965,6 @@ hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, h
 static const char* const kVariantNames[CONV_NUM_VARIANTS] = {
     "conv_igemm_kernel<2,2,4> generic 128x128", "conv_igemm_kernel<4,1,2> generic 128x64",
     "conv3x3_halo2_kernel 3x3 s1 16x16px x128ch (halo<2,2> for odd slab counts)", "conv3x3_pp_kernel<2> 3x3 s1 16x16px x64ch",
-    "conv3x3_pp_kernel<4> 3x3 s1 16x16px x128ch", "conv3x3_halo_kernel<4,*> 3x3 s1 16x16px x128ch",
     "conv3x3_c64_kernel<64|32> 3x3 s1 persistent, Cin 64 or 32", "conv_igemm_kernel<4,2,4,3> generic 256x128, 3-slab ring",
     "conv3x3_wide_kernel 3x3 s1 16x32px x128ch, K slabs of 32",
     "conv1x1_direct_kernel<4,2> 1x1 256px x256ch, pixels to regs", "conv1x1_direct_kernel<2,2> 1x1 256px x128ch, pixels to regs",
@@ -3270,8 +2972,6 @@ static const char* const kVariantNames[CONV_NUM_VARIANTS] = {
     "conv3x3_widep_kernel<strip> 3x3 s1 512 flattened px x128ch, persistent",
     "head1x1_kernel detect-head output 1x1, weights stationary in LDS, fp32 rows"};
 const char* conv_variant_name(int v) { return v >= 0 && v < CONV_NUM_VARIANTS ? kVariantNames[v] : "?"; }
-
-static bool s2_direct() { static const int v = getenv("CY_S2_DIRECT") ? atoi(getenv("CY_S2_DIRECT")) : 1; return v != 0; }
 
 // Batch-invariant kernel selection (default; CY_BATCH_INVARIANT=0 turns it off): every batch-size threshold below (and the
 // stem fusion) is evaluated as if the batch held >= 256 tiles, so a layer always runs the SAME kernel and a tile's fp16
@@ -3317,33 +3017,26 @@ int conv_variant(Precision p, const ConvArgs& a) {
         return CONV_C64_PERSIST;                             // 32-channel variant of the persistent kernel
     if (p == PREC_F16 && a.k == 3 && a.s == 1 && a.c1 == 0 && !a.up0 && !a.out_f32 && a.Cin % 64 == 0 &&
         a.out_bs == a.Ho * a.Wo && a.out_ro == 0) {
-        static const int force = getenv("CY_HALO_WM") ? atoi(getenv("CY_HALO_WM")) : 0;     // tuning override
-        static const int wide64 = getenv("CY_WIDE64") ? atoi(getenv("CY_WIDE64")) : 1;
         // 64-channel variant of the wide kernel for the box-head convs with deep inputs, when it fills the chip
-        if (narrow && wide64 && a.wgt32 && a.Cin >= 128 && a.Wi % 32 == 0 && force == 0 &&
-            Bv * ((a.Hi + 15) / 16) * (a.Wi / 32) >= 256)
-            return CONV_WIDE_64;
+        if (narrow && a.wgt32 && a.Cin >= 128 && a.Wi % 32 == 0 && Bv * ((a.Hi + 15) / 16) * (a.Wi / 32) >= 256) return CONV_WIDE_64;
         // 64 output channels on maps of a few pixels with deep inputs (the box head of 128- / 256-px inputs): the strip form with half
         // of its channel tile empty still beats the 16 x 16-pixel patches of the 64-channel kernels there (68 -> ~250 TFLOP/s on 4 x 4 maps)
-        if (narrow && force == 0 && a.wgt32 && a.Cin >= 128 && env_knob("CY_STRIP", 1) && strip_small(a) && strip_fits(a)) return CONV_STRIP_128;
-        if (narrow && a.Cin == 64 && force != 8) return force == 9 ? CONV_GENERIC_64 : CONV_C64_PERSIST;
-        if (narrow) return force == 9 ? CONV_GENERIC_64 : CONV_PP_64;
-        if (force == 5) return CONV_PP_128;
-        if (force == 4 || force == 43) return CONV_HALO16_128;
-        static const int wide = getenv("CY_WIDE") ? atoi(getenv("CY_WIDE")) : 1;
+        if (narrow && a.wgt32 && a.Cin >= 128 && env_knob("CY_STRIP", 1) && strip_small(a) && strip_fits(a)) return CONV_STRIP_128;
+        if (narrow && a.Cin == 64) return CONV_C64_PERSIST;
+        if (narrow) return CONV_PP_64;
         // strip form of the wide kernel (maps flattened to one dimension) where 16 x 32-pixel patches would leave > 4 % more of the MFMA
         // lanes idle: 80 / 40 / 20-px maps of 640-px inputs, 52 x 64 / 26 x 32 maps of the ragged 416 x 512 tiles.  CY_STRIP: 0 off,
         // 2 regardless of the launch size (tests); read per call.
         const int strip = env_knob("CY_STRIP", 1);
-        if (wide && strip && a.wgt32 && strip_fits(a) && strip_cover(a.Hi, a.Wi) + 0.04 < wide2d_cover(a.Hi, a.Wi) &&
+        if (strip && a.wgt32 && strip_fits(a) && strip_cover(a.Hi, a.Wi) + 0.04 < wide2d_cover(a.Hi, a.Wi) &&
             (strip > 1 || strip_small(a) || Bv * (long)(a.Hi + 1) * (a.Wi + 1) / 512 * ((pad64(a.Cout) + 127) / 128) >= 200))      // (about one strip per CU; tiny maps: every alternative idles more)
             return CONV_STRIP_128;
         const int wpad = (a.Wi + 31) / 32 * 32;
-        if (wide && a.wgt32 && (wpad - a.Wi) * 8 <= a.Wi) return CONV_WIDE_128;     // <= 12.5 % of the patch columns idle
+        if (a.wgt32 && (wpad - a.Wi) * 8 <= a.Wi) return CONV_WIDE_128;     // <= 12.5 % of the patch columns idle
         const int dual = getenv("CY_WIDE_DUAL") ? atoi(getenv("CY_WIDE_DUAL")) : 1;      // read per call: 2 forces it (tests)
         // two 16-px-wide images side by side: +8 % over the two-tap halo kernel once it still fills the chip (half as many
         // workgroups), slower below that
-        if (wide && dual && a.wgt32 && a.Wi <= 16 && a.Wi >= 14 &&
+        if (dual && a.wgt32 && a.Wi <= 16 && a.Wi >= 14 &&
             ((Bv + 1) / 2) * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + 127) / 128) >= (dual > 1 ? 1 : 224))
             return CONV_WIDE_DUAL;
         return CONV_HALO8_128;
@@ -3353,18 +3046,16 @@ int conv_variant(Precision p, const ConvArgs& a) {
     // 1x1: pixels-direct kernel once there is at least one 256-pixel tile per CU (below that the 128x128 tiles of the generic
     // kernel fill the chip better).  CY_DIRECT_MIN_BLOCKS is read per call so that the parity tests can force the path.
     if (p == PREC_F16 && !a.out_f32 && a.Cin % 64 == 0 &&
-        ((a.k == 1 && a.s == 1 && (a.c1 == 0 || a.c0 % 64 == 0)) || (a.k == 3 && a.s == 2 && a.c1 == 0 && !a.up0 && (a.Cin >= 128 || pad64(a.Cout) < 256) && s2_direct()))) {
+        ((a.k == 1 && a.s == 1 && (a.c1 == 0 || a.c0 % 64 == 0)) || (a.k == 3 && a.s == 2 && a.c1 == 0 && !a.up0 && (a.Cin >= 128 || pad64(a.Cout) < 256)))) {
         const char* e = getenv("CY_DIRECT_MIN_BLOCKS");
         const long min_blocks = e ? atol(e) : 256;
-        static const int bn_force = getenv("CY_DIRECT_BN") ? atoi(getenv("CY_DIRECT_BN")) : 0;      // tuning knob
-        const int bn = bn_force == 128 && a.k == 1 ? 128 : (pad64(a.Cout) >= 256 ? 256 : 128);
+        const int bn = pad64(a.Cout) >= 256 ? 256 : 128;
         const long blocks = ((Bv * a.Ho * a.Wo + 255) / 256) * ((pad64(a.Cout) + bn - 1) / bn);
         if (min_blocks >= 0 && blocks >= min_blocks) return bn == 256 ? CONV_DIRECT_256 : CONV_DIRECT_128;
     }
     // 1x1 and strided convs with enough 256-pixel tiles to fill the chip: deeper-pipelined 256x128 tile
-    static const int big = getenv("CY_BIG") ? atoi(getenv("CY_BIG")) : 1;
     const long M = Bv * a.Ho * a.Wo;
-    if (p == PREC_F16 && big && (M / 256) * ((pad64(a.Cout) + 127) / 128) >= big * 256) return CONV_GENERIC_BIG;
+    if (p == PREC_F16 && (M / 256) * ((pad64(a.Cout) + 127) / 128) >= 256) return CONV_GENERIC_BIG;
     return CONV_GENERIC_128;
 }
 
@@ -3374,10 +3065,10 @@ hipError_t launch_conv(Precision p, const ConvArgs& a, hipStream_t s) {
         switch (conv_variant_x3(a)) {
             case CONV_WIDE_128:      // persistent form (bit-identical) with CY_X3_PERSIST=1: measured before it became a default
                 if (env_knob("CY_X3_PERSIST", 0) && a.Cout % 16 == 0) return launch_widep(a, s);
-                return launch_wide<2, false, 2, true>(a, s);
+                return launch_wide<2, false, true>(a, s);
             case CONV_STRIP_128: return launch_strip(a, s);
-            case CONV_WIDE_64: return launch_wide<1, false, 2, true>(a, s);
-            case CONV_WIDE_DUAL: return launch_wide<2, true, 2, true>(a, s);
+            case CONV_WIDE_64: return launch_wide<1, false, true>(a, s);
+            case CONV_WIDE_DUAL: return launch_wide<2, true, true>(a, s);
             case CONV_DIRECT_256: return a.k == 3 ? launch_direct<4, 2, 3, true, true>(a, s) : launch_direct<4, 2, 3, false, true>(a, s);
             case CONV_DIRECT_128: return a.k == 3 ? launch_direct<2, 4, 2, true, true>(a, s) : launch_direct<2, 2, 2, false, true>(a, s);
             case CONV_HEAD_1X1: return launch_head<true>(a, s);
@@ -3388,54 +3079,42 @@ hipError_t launch_conv(Precision p, const ConvArgs& a, hipStream_t s) {
     switch (conv_variant(p, a)) {
         case CONV_C64_PERSIST: return a.Cin == 32 ? launch_c64<32>(a, s) : launch_c64<64>(a, s);
         case CONV_PP_64: return launch_pp<2>(a, s);
-        case CONV_PP_128: { ConvArgs b2 = a; b2.dbg = dev_knob("CY_DBG", 0); return launch_pp<4>(b2, s); }
-        case CONV_HALO16_128: return (getenv("CY_HALO_WM") && atoi(getenv("CY_HALO_WM")) == 43) ? launch_halo<4, 3>(a, s) : launch_halo<4, 2>(a, s);
         case CONV_HALO8_128: {
             ConvArgs b2 = a; b2.dbg = dev_knob("CY_DBG", 0);
-            static const int v = getenv("CY_HALO_V") ? atoi(getenv("CY_HALO_V")) : 2;      // 2: two taps per barrier (default)
-            if (v == 2 && (a.Cin / 64) % 2 == 0) return launch_halo2(b2, s);
-            return v == 1 ? launch_halo<2, 3, 1>(b2, s) : launch_halo<2, 2>(b2, s);
+            if ((a.Cin / 64) % 2 == 0) return launch_halo2(b2, s);      // two taps per barrier: walks the 64-channel slabs in pairs
+            return launch_halo<2, 2>(b2, s);
         }
         case CONV_GENERIC_BIG: return launch_t<f16, 4, 2, 4, 3>(a, s);
         case CONV_WIDE_128: {
-            static const int tps = getenv("CY_WIDE_TPS") ? atoi(getenv("CY_WIDE_TPS")) : 2;
             ConvArgs b2 = a; b2.dbg = dev_knob("CY_DBG", 0);
             // persistent form (same arithmetic in the same order: bit-identical outputs) when every CU gets at least two patches
             // and the output tile has whole 16-channel groups; CY_WIDE_PERSIST: 0 off, 2 regardless of the launch size (tests)
-            // round-4 A/B: the K loop on 32x32x16 MFMAs (32: compiler-placed fragment reads, 33: one read per MFMA gap)
-            if (const int mf = env_knob("CY_WIDE_MFMA", 16); mf >= 32) return mf == 33 ? launch_wide32<1>(b2, s) : launch_wide32<0>(b2, s);
             const int wp = env_knob("CY_WIDE_PERSIST", 1);
             const long patches = (long)a.B * ((a.Wi + 31) / 32) * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
             // Measured per layer at batch 256: 18-stage layers (Cin 128: model.4 / model.15 bottlenecks) -4..-6 %, 36-stage ones
             // -1.7..+1.5 %: taken for up to two slab pairs.
-            if (wp && tps == 2 && a.Cout % 16 == 0 && (wp > 1 || (patches >= 512 && a.Cin <= 128))) return launch_widep(b2, s);
-            if (tps == 2 && env_knob("CY_WIDE_SCHED", 0)) return launch_wide<2, false, 2, false, 1>(b2, s);      // round-4 experiment: reads interleaved with the MFMAs
-            return tps == 3 ? launch_wide<2, false, 3>(b2, s) : launch_wide<2>(b2, s);
+            if (wp && a.Cout % 16 == 0 && (wp > 1 || (patches >= 512 && a.Cin <= 128))) return launch_widep(b2, s);
+            return launch_wide<2>(b2, s);
         }
         case CONV_STRIP_128: return launch_strip(a, s);
         case CONV_WIDE_64: return launch_wide<1>(a, s);
         case CONV_WIDE_DUAL: return launch_wide<2, true>(a, s);
         case CONV_DIRECT_256: {
             ConvArgs a2 = a; a2.dbg = dev_knob("CY_DBG", 0);
-            // tuning knob, off: 128 px x 256 ch tiles with two workgroups per CU for Cin <= CY_D256_V.  Measured at batch 256: 2-12 %
-            // SLOWER on every 256-channel 1x1 layer but model.4.cv1 (-4 %): twice the weight pieces per MFMA cost more than the overlap buys
-            static const int v256 = getenv("CY_D256_V") ? atoi(getenv("CY_D256_V")) : 0;
-            if (a.k != 3 && v256 > 0 && a.Cin <= v256) return launch_direct<4, 1, 2, false>(a, s);
-            // (a 4-slot ring for this tile: 256 VGPRs with spills, 3-10 % slower)
-            // weight requests on 4 waves (one per SIMD) or on all 8 (CY_DIRECT_NDW forces one; same bits either way).  Measured per layer
-            // at batch 256: four requesting waves are 2-5 % faster on the strided 3x3 layers (model.5, model.7) and 1-6 % slower on the 1x1s
-            static const int ndw = env_knob("CY_DIRECT_NDW", 0);
+            // (tried, not kept: 128 px x 256 ch tiles with two workgroups per CU, 2-12 % slower on every 256-channel 1x1 layer but
+            // model.4.cv1 (-4 %): twice the weight pieces per MFMA cost more than the overlap buys; a 4-slot ring for this tile:
+            // 256 VGPRs with spills, 3-10 % slower)
+            // weight requests on 4 waves (one per SIMD) for the strided 3x3 layers, on all 8 for the 1x1s (same bits either way).  Measured
+            // per layer at batch 256: four requesting waves are 2-5 % faster on model.5 / model.7 and 1-6 % slower on the 1x1s
             // back-to-back pair (the runtime sets wgt2 when this layer's only reader is a 256 -> <= 256 1x1 and the tile holds all channels)
             if (a.wgt2 && pad64(a.Cout) == 256 && a.c1 == 0 && !a.res && !a.out_f32)
                 return a.k == 3 ? launch_direct<4, 2, 3, true, false, 4, true>(a2, s) : launch_direct<4, 2, 3, false, false, 8, true>(a2, s);
-            if (a.k == 3) return ndw == 8 ? launch_direct<4, 2, 3, true>(a2, s) : launch_direct<4, 2, 3, true, false, 4>(a2, s);
-            return ndw == 4 ? launch_direct<4, 2, 3, false, false, 4>(a2, s) : launch_direct<4, 2, 3, false>(a2, s);
+            return a.k == 3 ? launch_direct<4, 2, 3, true, false, 4>(a2, s) : launch_direct<4, 2, 3, false>(a2, s);
         }
         case CONV_DIRECT_128:     // strided 3x3 (model.1): 64 px per wave, so every weight fragment feeds four MFMAs (-8 % vs 32 px)
             // 1x1 with a 128-channel tile = the HBM-bound layers (model.2.cv1/cv2): two workgroups per CU (126 VGPRs, one chunk
             // ahead) overlap each other's prologue/epilogue: -12 % against one workgroup with a 4-chunk ring
-            if (a.k != 3 && !(getenv("CY_D128_V") && atoi(getenv("CY_D128_V")) == 0)) return launch_direct<2, 2, 2, false>(a, s);
-            return a.k == 3 ? launch_direct<2, 4, 2, true>(a, s) : launch_direct<2, 2, 4, false>(a, s);
+            return a.k == 3 ? launch_direct<2, 4, 2, true>(a, s) : launch_direct<2, 2, 2, false>(a, s);
         case CONV_HEAD_1X1: return launch_head<false>(a, s);
         case CONV_GENERIC_64: return p == PREC_F16 ? launch_t<f16, 4, 1, 2>(a, s) : launch_t<float, 4, 1, 2>(a, s);
         default: return p == PREC_F16 ? launch_t<f16, 2, 2, 4>(a, s) : launch_t<float, 2, 2, 4>(a, s);

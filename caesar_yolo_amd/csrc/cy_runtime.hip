@@ -483,14 +483,13 @@ int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
     HIPCHK(c, hipMalloc(&c->counters, 4 * sizeof(int)));
     HIPCHK(c, hipMemset(c->counters, 0, 4 * sizeof(int)));
     // side streams at the LOWEST priority: preprocessing and decode/NMS/merge fill the gaps of the conv stack on the caller's
-    // stream instead of competing with it for CUs (CY_SIDE_PRIO=0 restores default-priority streams).  Round 4: confining them to a
+    // stream instead of competing with it for CUs.  Round 4: confining them to a
     // subset of the CUs instead (hipExtStreamCreateWithCUMask, 64 / 32 / 16 CUs spread over the XCDs) costs 10-12 % of the S16k rate
     // (8950 -> 8000 / 8000 / 7910 tiles/s): the pass then waits for its side kernels.
     int prio_lo = 0, prio_hi = 0;
     hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);          // lo = numerically greatest = lowest priority
-    const bool low = !(getenv("CY_SIDE_PRIO") && atoi(getenv("CY_SIDE_PRIO")) == 0);
-    HIPCHK(c, hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, low ? prio_lo : 0));
-    HIPCHK(c, hipStreamCreateWithPriority(&c->s_post, hipStreamNonBlocking, low ? prio_lo : 0));
+    HIPCHK(c, hipStreamCreateWithPriority(&c->s_pre, hipStreamNonBlocking, prio_lo));
+    HIPCHK(c, hipStreamCreateWithPriority(&c->s_post, hipStreamNonBlocking, prio_lo));
     hipEvent_t* evs[] = {&c->ev_call, &c->ev_pre[0], &c->ev_pre[1], &c->ev_pre[2], &c->ev_fwd[0], &c->ev_fwd[1], &c->ev_fwd[2], &c->ev_post[0], &c->ev_post[1], &c->ev_post[2]};
     for (hipEvent_t* e : evs) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     c->loaded = true;
@@ -714,28 +713,6 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         c->prof.push_back({ev_prev, e, kind, flops, cur_conv, (c->ws3 && ws == c->ws3) ? 1 : 0});
         ev_prev = e;
     };
-    // Optional (CY_SUB=n): run the full-resolution head of the graph (stem .. model.2, levels 1-2; tensors of 134-537 MB
-    // at batch 64) in sub-batches so that producer and consumer could meet in the 256 MiB Infinity Cache; only the
-    // stage output and the network input are addressed per sub-batch.  Measured on MI355X: 1-6 % SLOWER at n = 4/8/16
-    // (the extra launches cost more than the cache buys), so it is off by default and kept as a tuning knob.
-    static const int sub_env = getenv("CY_SUB") ? atoi(getenv("CY_SUB")) : 0;   // measured: no gain on MI355X (profiles/), off by default
-    size_t n_head = 0;
-    while (n_head < p.ops.size()) {
-        const Op& o = p.ops[n_head];
-        const int lo = o.out >= 0 ? p.tensors[o.out].level : 9;
-        if (lo > 2 || o.in1 >= 0) break;
-        ++n_head;
-    }
-    std::vector<char> crosses(p.tensors.size(), 0);      // written in the head, read after it
-    for (size_t i = n_head; i < p.ops.size(); ++i) {
-        const Op& o = p.ops[i];
-        if (o.in0 >= 0) crosses[o.in0] = 1;
-        if (o.in1 >= 0) crosses[o.in1] = 1;
-        if (o.res >= 0) crosses[o.res] = 1;
-    }
-    crosses[0] = 1;
-    const int sub = (sub_env > 0 && sub_env < B && n_head > 0) ? sub_env : B;
-
     // model.0 + model.1 in one kernel (fp16 context) when the stem's only reader is a 3x3 s2 64->128 SiLU conv and the launch
     // fills the chip.  CY_STEM_FUSE: 0 = off, 2 = regardless of size (parity tests); read per call.
     const int fuse_env = getenv("CY_STEM_FUSE") ? atoi(getenv("CY_STEM_FUSE")) : 1;
@@ -757,26 +734,21 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     struct HeadPend { ConvArgs a; double flops; int conv; bool on; };
     HeadPend pend[3] = {};                                    // deferred box-branch output convolutions, per stride level
     const int bneck_env = env_knob("CY_BNECK_FUSE", 0);       // off by default (slower than two launches so far, see bneck64.hip); read per call: the parity tests run both forms
-    auto run_op = [&](const Op& o, const Op* next, int b0, int Bn, bool* fused) -> int {
-        auto tp = [&](int t) -> char* {                    // tensor base for images [b0, b0+Bn)
-            char* base = tptr(t);
-            if (b0 && crosses[t]) base += (size_t)b0 * (H >> p.tensors[t].level) * (W >> p.tensors[t].level) * p.tensors[t].C * es;
-            return base;
-        };
+    auto run_op = [&](const Op& o, const Op* next, bool* fused) -> int {
         cur_conv = o.conv;
         if (bneck_env && c->prec == PREC_F16 && o.kind == OPK_CONV && next && c->dconv[o.conv].bneck &&
             bneck_pair(p, (size_t)(&o - p.ops.data()))) {
             const Op& n = *next;
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[n.out];
             BneckArgs a{};
-            a.in = tp(o.in0); a.in_ct = ti.C; a.in_coff = o.in0_coff;
-            a.B = Bn; a.H = H >> ti.level; a.W = W >> ti.level;
-            a.in_bytes = (uint32_t)((size_t)Bn * a.H * a.W * ti.C * es);
-            a.out = tp(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
+            a.in = tptr(o.in0); a.in_ct = ti.C; a.in_coff = o.in0_coff;
+            a.B = B; a.H = H >> ti.level; a.W = W >> ti.level;
+            a.in_bytes = (uint32_t)((size_t)B * a.H * a.W * ti.C * es);
+            a.out = tptr(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
             a.wfrag = c->dconv[o.conv].bneck; a.bias1 = c->dconv[o.conv].bias; a.bias2 = c->dconv[n.conv].bias;
             a.shortcut = n.res >= 0;
             HIPCHK(c, launch_bneck64(a, s));
-            prof_done(CONV_NUM_VARIANTS + 4, 2.0 * (2.0 * Bn * a.H * a.W * 64.0 * 64.0 * 9.0));
+            prof_done(CONV_NUM_VARIANTS + 4, 2.0 * (2.0 * B * a.H * a.W * 64.0 * 64.0 * 9.0));
             *fused = true; c->bneck_fused_last = true;
             return CY_OK;
         }
@@ -784,15 +756,15 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             const Op& n = *next;
             const Tensor& ti = p.tensors[o.in0]; const Tensor& t1 = p.tensors[o.out]; const Tensor& to = p.tensors[n.out];
             StemDownArgs a{};
-            a.B = Bn; a.Hi = H >> ti.level; a.Wi = W >> ti.level; a.H1 = H >> t1.level; a.W1 = W >> t1.level;
+            a.B = B; a.Hi = H >> ti.level; a.Wi = W >> ti.level; a.H1 = H >> t1.level; a.W1 = W >> t1.level;
             a.Ho = a.H1 / 2; a.Wo = a.W1 / 2;
-            a.in = tp(o.in0); a.in_bytes = (uint32_t)((size_t)Bn * a.Hi * a.Wi * ti.C * es);
+            a.in = tptr(o.in0); a.in_bytes = (uint32_t)((size_t)B * a.Hi * a.Wi * ti.C * es);
             a.wpk2 = reinterpret_cast<const char*>(c->dconv[o.conv].w) + 64 * 32 * 2; a.bias0 = c->dconv[o.conv].bias;
             a.wgt32 = c->dconv[n.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[n.conv].w32bytes; a.bias1 = c->dconv[n.conv].bias;
-            a.out = tp(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
+            a.out = tptr(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
             if (ti.C == 4 && (fuse_env > 1 || batch_invariant() || stem_down_blocks(a) >= 256)) {
                 HIPCHK(c, launch_stem_down(a, s));
-                prof_done(CONV_NUM_VARIANTS, 2.0 * Bn * a.H1 * a.W1 * 64 * 27.0 + 2.0 * Bn * a.Ho * a.Wo * 128.0 * 64 * 9);
+                prof_done(CONV_NUM_VARIANTS, 2.0 * B * a.H1 * a.W1 * 64 * 27.0 + 2.0 * B * a.Ho * a.Wo * 128.0 * 64 * 9);
                 *fused = true; c->stem_fused_last = true;
                 return CY_OK;
             }
@@ -800,73 +772,73 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         if (o.kind == OPK_STEM) {
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[o.out];
             StemArgs a{};
-            a.in = tp(o.in0); a.out = tp(o.out); a.w = c->dconv[o.conv].stem_w; a.bias = c->dconv[o.conv].bias; a.wpk = c->dconv[o.conv].w;
-            a.B = Bn; a.Hi = H >> ti.level; a.Wi = W >> ti.level; a.Ho = H >> to.level; a.Wo = W >> to.level;
+            a.in = tptr(o.in0); a.out = tptr(o.out); a.w = c->dconv[o.conv].stem_w; a.bias = c->dconv[o.conv].bias; a.wpk = c->dconv[o.conv].w;
+            a.B = B; a.Hi = H >> ti.level; a.Wi = W >> ti.level; a.Ho = H >> to.level; a.Wo = W >> to.level;
             a.Cout = p.convs[o.conv].cout; a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_lo = x3 ? to.C : 0;
             HIPCHK(c, launch_stem(c->prec, a, s));
-            prof_done(CONV_NUM_VARIANTS, 2.0 * Bn * a.Ho * a.Wo * a.Cout * 27.0);
+            prof_done(CONV_NUM_VARIANTS, 2.0 * B * a.Ho * a.Wo * a.Cout * 27.0);
         } else if (o.kind == OPK_POOL) {
             const Tensor& t = p.tensors[o.in0];
             PoolArgs a{};
-            a.src = tp(o.in0); a.dst = tp(o.out); a.ct = cm * t.C; a.src_coff = o.in0_coff; a.dst_coff = o.out_coff; a.lo = x3 ? t.C : 0;
-            a.C = o.c0; a.B = Bn; a.H = H >> t.level; a.W = W >> t.level;
+            a.src = tptr(o.in0); a.dst = tptr(o.out); a.ct = cm * t.C; a.src_coff = o.in0_coff; a.dst_coff = o.out_coff; a.lo = x3 ? t.C : 0;
+            a.C = o.c0; a.B = B; a.H = H >> t.level; a.W = W >> t.level;
             HIPCHK(c, launch_pool5(c->prec, a, s));
             prof_done(CONV_NUM_VARIANTS + 1, 0.0);
         } else if (o.kind == OPK_DWCONV) {
             const ConvDesc& d = p.convs[o.conv];
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[o.out];
             DwArgs a{};
-            a.in = tp(o.in0); a.in_ct = cm * ti.C; a.in_coff = o.in0_coff; a.out = tp(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff;
+            a.in = tptr(o.in0); a.in_ct = cm * ti.C; a.in_coff = o.in0_coff; a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff;
             a.in_lo = ti.C; a.out_lo = to.C;
-            if (o.res >= 0) { a.res = tp(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
+            if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
             a.w = c->dconv[o.conv].dw_w; a.bias = c->dconv[o.conv].bias;
-            a.B = Bn; a.H = H >> ti.level; a.W = W >> ti.level; a.C = d.cout; a.act = d.act;
+            a.B = B; a.H = H >> ti.level; a.W = W >> ti.level; a.C = d.cout; a.act = d.act;
             a.blk = o.p0; a.gstride = o.p1; a.goff = o.p2;
             if (!a.w || ti.level != to.level) return fail(c, CY_ERR_STATE, "malformed depth-wise op");
             HIPCHK(c, launch_dwconv(c->prec, a, s));
-            prof_done(CONV_NUM_VARIANTS + 2, 2.0 * Bn * a.H * a.W * (double)a.C * 9.0);
+            prof_done(CONV_NUM_VARIANTS + 2, 2.0 * B * a.H * a.W * (double)a.C * 9.0);
         } else if (o.kind == OPK_ATTN) {
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[o.out];
             AttnArgs a{};
-            a.qkv = tp(o.in0); a.ct = cm * ti.C; a.coff = o.in0_coff; a.out = tp(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff;
+            a.qkv = tptr(o.in0); a.ct = cm * ti.C; a.coff = o.in0_coff; a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff;
             a.lo = ti.C; a.out_lo = to.C;
-            a.B = Bn; a.N = (H >> ti.level) * (W >> ti.level); a.heads = o.p0; a.kd = o.p1; a.hd = o.p2;
+            a.B = B; a.N = (H >> ti.level) * (W >> ti.level); a.heads = o.p0; a.kd = o.p1; a.hd = o.p2;
             a.scale = 1.0f / sqrtf((float)a.kd);
             if (a.heads < 1 || ti.level != to.level) return fail(c, CY_ERR_STATE, "malformed attention op");
             hipError_t e = launch_attention(c->prec, a, s);
             if (e == hipErrorInvalidValue) return fail(c, CY_ERR_UNSUPPORTED, ATTN_TOO_LARGE);
             HIPCHK(c, e);
-            prof_done(CONV_NUM_VARIANTS + 3, 2.0 * Bn * a.heads * (double)a.N * a.N * (a.kd + a.hd));
+            prof_done(CONV_NUM_VARIANTS + 3, 2.0 * B * a.heads * (double)a.N * a.N * (a.kd + a.hd));
         } else {
             const ConvDesc& d = p.convs[o.conv];
             ConvArgs a{};
             const Tensor& t0 = p.tensors[o.in0];
-            auto span = [&](int t) -> uint32_t {           // bytes addressable from tp(t) for Bn images
+            auto span = [&](int t) -> uint32_t {           // bytes addressable from tptr(t) for B images
                 const Tensor& tt = p.tensors[t];
-                return (uint32_t)((size_t)Bn * (H >> tt.level) * (W >> tt.level) * tt.C * es);
+                return (uint32_t)((size_t)B * (H >> tt.level) * (W >> tt.level) * tt.C * es);
             };
-            a.in0 = tp(o.in0); a.in0_ct = cm * t0.C; a.in0_coff = o.in0_coff; a.c0 = o.c0; a.up0 = o.up0;
+            a.in0 = tptr(o.in0); a.in0_ct = cm * t0.C; a.in0_coff = o.in0_coff; a.c0 = o.c0; a.up0 = o.up0;
             a.in0_bytes = span(o.in0);
             a.split = x3 ? c->dconv[o.conv].passes : 0; a.in0_lo = t0.C; a.oscale = c->dconv[o.conv].oscale;
             int lev_in = o.up0 ? t0.level - 1 : t0.level;
             if (o.in1 >= 0) {
                 const Tensor& t1 = p.tensors[o.in1];
-                a.in1 = tp(o.in1); a.in1_ct = cm * t1.C; a.in1_coff = o.in1_coff; a.c1 = o.c1; a.in1_bytes = span(o.in1); a.in1_lo = t1.C;
+                a.in1 = tptr(o.in1); a.in1_ct = cm * t1.C; a.in1_coff = o.in1_coff; a.c1 = o.c1; a.in1_bytes = span(o.in1); a.in1_lo = t1.C;
                 lev_in = t1.level;
             }
             a.wgt = c->dconv[o.conv].w; a.wgt_bytes = (uint32_t)c->dconv[o.conv].wbytes; a.bias = c->dconv[o.conv].bias;
             a.wgt32 = c->dconv[o.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[o.conv].w32bytes;
-            a.B = Bn; a.Hi = H >> lev_in; a.Wi = W >> lev_in; a.k = d.k; a.s = d.s; a.act = d.act;
+            a.B = B; a.Hi = H >> lev_in; a.Wi = W >> lev_in; a.k = d.k; a.s = d.s; a.act = d.act;
             a.Ho = d.s == 2 ? a.Hi / 2 : a.Hi; a.Wo = d.s == 2 ? a.Wi / 2 : a.Wi;
             a.Cin = d.cin; a.Cout = d.cout;
             if (o.out >= 0) {
                 const Tensor& to = p.tensors[o.out];
-                a.out = tp(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_bs = a.Ho * a.Wo; a.out_ro = 0; a.out_f32 = 0; a.out_lo = to.C;
+                a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_bs = a.Ho * a.Wo; a.out_ro = 0; a.out_f32 = 0; a.out_lo = to.C;
             } else {
                 a.out = d_pred; a.out_ct = 64 + p.nc; a.out_coff = o.pred_coff; a.out_bs = A; a.out_ro = a_off[o.pred_level]; a.out_f32 = 1;
             }
-            if (o.res >= 0) { a.res = tp(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
-            double flops = 2.0 * Bn * a.Ho * a.Wo * (double)a.Cout * a.Cin * a.k * a.k;
+            if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
+            double flops = 2.0 * B * a.Ho * a.Wo * (double)a.Cout * a.Cin * a.k * a.k;
             if (pw_env && c->prec == PREC_F16 && next && next->conv >= 0 && c->dconv[next->conv].w2f && conv_variant(c->prec, a) == CONV_DIRECT_256 &&
                 pw_pair(p, (size_t)(&o - p.ops.data()))) {
                 const Op& n = *next;
@@ -874,8 +846,8 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
                 const Tensor& to2 = p.tensors[n.out];
                 a.wgt2 = c->dconv[n.conv].w2f; a.wgt2_bytes = (uint32_t)c->dconv[n.conv].w2fbytes; a.bias2 = c->dconv[n.conv].bias;
                 a.act2 = d2.act; a.cout2 = d2.cout;
-                a.out2 = tp(n.out); a.out2_ct = to2.C; a.out2_coff = n.out_coff;
-                flops += 2.0 * Bn * a.Ho * a.Wo * (double)d2.cout * d2.cin;
+                a.out2 = tptr(n.out); a.out2_ct = to2.C; a.out2_coff = n.out_coff;
+                flops += 2.0 * B * a.Ho * a.Wo * (double)d2.cout * d2.cin;
                 *fused = true; c->pw_fused_conv = o.conv;
             }
             // the two output convolutions of a detect-head level (box branch at column 0, class branch at column 64 of the same
@@ -902,20 +874,12 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         }
         return CY_OK;
     };
-    auto run_range = [&](size_t lo, size_t hi, int b0, int Bn) -> int {
-        for (size_t i = lo; i < hi; ++i) {
-            bool fused = false;
-            const int r = run_op(p.ops[i], i + 1 < hi ? &p.ops[i + 1] : nullptr, b0, Bn, &fused);
-            if (r) return r;
-            if (fused) ++i;                                  // the next op ran inside this one's kernel
-        }
-        return CY_OK;
-    };
-    for (int b0 = 0; b0 < B; b0 += sub) {
-        const int Bn = B - b0 < sub ? B - b0 : sub;
-        rc = run_range(0, n_head, b0, Bn); if (rc) return rc;
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        bool fused = false;
+        rc = run_op(p.ops[i], i + 1 < p.ops.size() ? &p.ops[i + 1] : nullptr, &fused);
+        if (rc) return rc;
+        if (fused) ++i;                                      // the next op ran inside this one's kernel
     }
-    rc = run_range(n_head, p.ops.size(), 0, B); if (rc) return rc;
     for (HeadPend& h : pend)                                  // a box branch whose class branch never came (no such plan today)
         if (h.on) { h.on = false; cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); }
     return CY_OK;

@@ -30,4 +30,6 @@ CONFIG = {
     'tile_batch': 64,                  # tiles per kernel launch sequence
     'precision': 'fp16x3',             # 'fp16x3' (default: parity context), 'fp32' (exact fp32, ~2.7x slower), 'fp16' (throughput, ~3x faster)
     'augment': False,                  # test-time augmentation of every model call (ultralytics augment=True: 3 views, joint NMS)
+    'measure_sources': False,          # NEW: flux, peak, centroid, local background and sky position of every catalog source
+    'measure_ring': 8,                 # width in pixels of the background ring around a source's box
 }

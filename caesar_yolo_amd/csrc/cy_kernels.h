@@ -250,4 +250,15 @@ struct AugDecodeArgs {
 };
 hipError_t launch_decode_augmented(const AugDecodeArgs& a, hipStream_t s);
 
+// ---- catalog source measurement (cy_measure.hip) ---------------------------------------------------
+constexpr int MEAS_FIELDS = 12;    // CY_MEAS_FIELDS
+struct MeasureArgs {
+    const float* img; int MH, MW;   // resident image as cy_mosaic_prepare leaves it (blank = 0); MH * MW < 2^31
+    const int* win;                 // [n][8] inclusive pixel windows {bx0, bx1, by0, by1 | gx0, gx1, gy0, gy1}: box, box grown by the ring;
+                                    // both inside the image, the grown one containing the box; bx1 < bx0 or by1 < by0 = empty
+    int n;
+    double* out;                    // [n][MEAS_FIELDS]
+};
+hipError_t launch_measure(const MeasureArgs& a, hipStream_t s);
+
 }  // namespace cy

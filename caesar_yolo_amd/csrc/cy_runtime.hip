@@ -3,6 +3,7 @@
 #include "../../include/caesar_yolo_hip.h"
 #include "cy_kernels.h"
 #include "cy_plan.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -63,6 +64,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
+    double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1461,6 +1463,70 @@ int cy_detect_counters(cy_ctx* c, long long* out4, int reset) {
     HIPCHK(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; ++i) out4[i] = h[i];
     if (reset) HIPCHK(c, hipMemset(c->counters, 0, sizeof(h)));
+    return CY_OK;
+}
+
+// ---- catalog source measurement ---------------------------------------------------------------
+static_assert(CY_MEAS_FIELDS == MEAS_FIELDS, "header and kernel disagree on the measurement row");
+// Inclusive integer window [max(0, ceil(lo)), min(N - 1, floor(hi))] of a float64 box side; empty (first > last) when the side
+// misses the image or holds no pixel centre.  A NaN edge makes it empty.
+static void window_1d(double lo, double hi, int N, int* first, int* last) {
+    *first = 0; *last = -1;
+    if (std::isnan(lo) || std::isnan(hi)) return;
+    const double c = std::ceil(lo), f = std::floor(hi);
+    if (c > (double)(N - 1) || f < 0.0) return;
+    *first = c > 0.0 ? (int)c : 0;
+    *last = f < (double)(N - 1) ? (int)f : N - 1;
+}
+
+int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (n < 0 || ring < 0 || MH <= 0 || MW <= 0) return fail(c, CY_ERR_ARG, "n >= 0, ring >= 0 and MH, MW > 0 required");
+    if (n == 0) return CY_OK;
+    if (!d_img || !h_boxes || !h_out) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
+    std::vector<int> win((size_t)n * 8);
+    const long long rg = ring;
+    for (int i = 0; i < n; ++i) {
+        int* w = &win[(size_t)i * 8];
+        const double* b = h_boxes + (size_t)i * 4;
+        window_1d(b[0], b[2], MW, &w[0], &w[1]);
+        window_1d(b[1], b[3], MH, &w[2], &w[3]);
+        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }        // empty in one axis = empty
+        // the ring's outer window: the box window grown by `ring`, clipped to the image (an empty box window has no ring)
+        w[4] = (int)std::max(0LL, w[0] - rg); w[5] = (int)std::min((long long)MW - 1, w[1] + rg);
+        w[6] = (int)std::max(0LL, w[2] - rg); w[7] = (int)std::min((long long)MH - 1, w[3] + rg);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    void *d_win = nullptr, *d_out = nullptr;
+    HIPCHK(c, sc.alloc(win.size() * sizeof(int), &d_win));
+    HIPCHK(c, sc.alloc((size_t)n * CY_MEAS_FIELDS * sizeof(double), &d_out));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) {
+        MeasureArgs a{};
+        a.img = d_img; a.MH = MH; a.MW = MW; a.win = reinterpret_cast<const int*>(d_win); a.n = n; a.out = reinterpret_cast<double*>(d_out);
+        e = launch_measure(a, st);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, (size_t)n * CY_MEAS_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st);
+    const int rc = entry_done(c, e, st);
+    float ms = -1.0f;
+    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    c->measure_ms = ms;
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
+}
+
+int cy_measure_kernel_ms(const cy_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return CY_ERR_ARG;
+    *out_ms = c->measure_ms;
     return CY_OK;
 }
 

@@ -28,6 +28,10 @@ class Analyzer(object):
         self.device = config['devices'][0]
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
+        # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
+        self.measure = bool(config.get('measure_sources', False))
+        self.measure_ring = int(config.get('measure_ring', 8))
+        self.beam_area, self.wcs, self.wcs_origin = 0, None, (0, 0)
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
         self.merge_overlap_iou_thr_hard = config['merge_overlap_iou_thr_hard']
         self.write_to_json = config.get('save_catalog', True)
@@ -76,7 +80,7 @@ class Analyzer(object):
             logger.warning("Model prediction failed (err=%s)..." % str(e))
             return -1
         return self._finish(det, d, cnt, int(status[0]), nx, ny, xmin, ymin,
-                            lambda: det.preproc_planes(mosaic, [(0, 0)], ny, nx, cfg)[0][0])
+                            lambda: det.preproc_planes(mosaic, [(0, 0)], ny, nx, cfg)[0][0], frame=mosaic)
 
     def _predict_cube(self, image, image_id, xmin, ymin):
         """An (H,W,3) array whose channels differ (the reference takes it as is, caesar_yolo/evaluation.py:146-154, and every CLI
@@ -129,7 +133,7 @@ class Analyzer(object):
             return -1
         return self._finish(det, d, cnt, st, nx, ny, xmin, ymin, lambda: cube[0])
 
-    def _finish(self, det, d, cnt, st, nx, ny, xmin, ymin, planes_fn):
+    def _finish(self, det, d, cnt, st, nx, ny, xmin, ymin, planes_fn, frame=None):
         if st == 1:
             logger.warning("Input image is None, no prediction made.")
             return -1
@@ -145,6 +149,17 @@ class Analyzer(object):
         self.labels_final = [self.class_names[c] for c in self.class_ids_final]
         self.results = {"image_id": self.image_id,
                         "objs": objs_from_detections(dd, self.class_names, nx, ny, xmin, ymin, self.obj_name_tag)}
+        if self.measure:
+            if frame is None:
+                logger.warning("Source measurement needs a 2-D frame: skipped for a 3-channel input image.")
+            else:
+                from . import measure
+                try:
+                    measure.measure_and_annotate(det, frame, self.results["objs"], self.measure_ring, self.beam_area, self.wcs,
+                                                 box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
+                except L.CyError as e:
+                    logger.warning("Source measurement failed (err=%s)..." % str(e))
+                    return -1
         if self.draw:                                             # caesar_yolo/evaluation.py:203-210
             self.draw_results(self.outfile or ('out_' + str(self.image_id) + '.png'))
         if self.write_to_json:

@@ -32,7 +32,7 @@ logger = logging.getLogger("caesar_yolo_amd")
 
 def wcs_of_header(header):
     """The `WCS(header)` of caesar_yolo/inference.py:473 (and utils.py:234-238, where a failure is logged and the WCS dropped):
-    caesar_yolo_amd.wcs restates the celestial part of the standard; nothing on the detect path reads it."""
+    caesar_yolo_amd.wcs restates the celestial part of the standard; --measure_sources reads it for ra / dec (measure.py)."""
     from .wcs import WCS
     try:
         return WCS(header)
@@ -523,6 +523,9 @@ class SFinder(object):
         analyzer = Analyzer(self.model, self.config)
         analyzer.device = self._device()
         analyzer.outfile_json = self.outfile_json
+        # --measure_sources: what the Analyzer needs beside the pixels (the crop's origin places its pixels in the frame of the WCS)
+        analyzer.beam_area, analyzer.wcs = self.beamArea, self.wcs
+        analyzer.wcs_origin = (rng[0], rng[2]) if not all(v in (0, -1) for v in rng) else (0, 0)
         if analyzer.predict(image=data, image_id=self.image_id, header=self.header) < 0:
             logger.error("Failed to run model prediction on image %s!" % path)
             return -1
@@ -567,6 +570,16 @@ class SFinder(object):
                     tid = grid_id[(x + ox, y + oy, th, tw)]
                     utils.write_fits_image('timg_' + str(self.image_id) + '_tid' + str(tid) + '.fits', ch0[b], bitpix=-64)
 
+    def _measure(self, det, mosaic, src):
+        """--measure_sources: the final merged catalog measured on the whole image (a region already resident is reused, otherwise
+        rank 0 uploads what it lacks), one kernel launch; adds the keys of measure.KEYS to every source."""
+        from . import measure
+        t0 = time.time()
+        img, ox, oy = mosaic.region(det, 0, self.nx, 0, self.ny)
+        measure.measure_and_annotate(det, img, src, int(self.config.get('measure_ring', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
+        self.stats["measure_ms"] = 1e3 * (time.time() - t0)
+        self.stats["measure_kernel_ms"] = det.measure_kernel_ms() if src else 0.0
+
     # ---- tiled (reference :578-658)
     def run_parallel(self):
         import torch.distributed as dist
@@ -601,6 +614,8 @@ class SFinder(object):
         if rank == 0:
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
+            if c.get('measure_sources', False):
+                self._measure(det, mosaic, src)
             self.sources = {"sources": src}
             if self.write_to_json:
                 out = self.outfile_json or ('catalog_' + str(self.image_id) + '.json')

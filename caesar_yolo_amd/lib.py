@@ -10,6 +10,8 @@ LIB_PATH = os.path.join(_HERE, "libcaesar_yolo_hip.so")
 
 CY_MAX_DET = 300
 CY_MAX_STAGES = 8
+CY_MEAS_FIELDS = 12
+MEAS_NAMES = ("npix", "nring", "bkg", "rms", "peak", "x_peak", "y_peak", "sum", "sw", "swx", "swy", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
 F16, F32, F16X3 = 0, 1, 2
 PRECISIONS = {"fp16": F16, "f16": F16, "half": F16, "fp32": F32, "f32": F32, "float": F32, "fp16x3": F16X3, "f16x3": F16X3, "split": F16X3}
@@ -21,7 +23,7 @@ EXPORTS = [
     "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_bottleneck64", "cy_dwconv3x3",
     "cy_attention", "cy_maxpool5", "cy_make_tile_records",
     "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
-    "cy_decode_nms_augmented", "cy_detect_tiles_augmented",
+    "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
 ]
 
 
@@ -143,6 +145,8 @@ def load():
         "cy_detect_tiles_augmented": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.POINTER(cy_preproc_cfg), C.c_float, C.c_float, C.c_double, C.c_double, C.c_int,
                                                 vp, vp, vp, vp]),
+        "cy_measure_sources": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_int, dp, vp]),
+        "cy_measure_kernel_ms": (C.c_int, [vp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -292,6 +292,26 @@ class HipDetector(object):
         return {"degenerate_boxes": int(out[0]), "cand_overflow_tiles": int(out[1]), "median_bracket_hits": int(out[2]),
                 "median_bracket_misses": int(out[3])}
 
+    # ---- catalog source measurement (an addition to the reference's catalog)
+    def measure_sources(self, img_dev, boxes, ring=8):
+        """img_dev: device fp32 image [MH, MW] as mosaic_to_device leaves it; boxes: [n, 4] float64 {x1, y1, x2, y2} in its 0-based
+        pixels (they may leave the image).  -> numpy float64 [n, CY_MEAS_FIELDS] (lib.MEAS_NAMES), cy_measure_sources."""
+        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        n = boxes.shape[0]
+        out = np.zeros((n, L.CY_MEAS_FIELDS), np.float64)
+        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
+            raise L.CyError("measure_sources: a contiguous 2-D float32 image on %s is required" % (self.tdev,))
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_measure_sources(self.ctx, self._p(img_dev), int(img_dev.shape[0]), int(img_dev.shape[1]),
+                                              boxes.ctypes.data_as(dp), n, int(ring), out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def measure_kernel_ms(self):
+        """Kernel time of the last measure_sources call in ms (hipEvents around the launch); -1 before the first."""
+        ms = C.c_double(-1.0)
+        self._chk(self.lib.cy_measure_kernel_ms(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
     # ---- test-time augmentation (ultralytics `augment=True`): views 1 (0.83, flipped) and 2 (0.67) beside view 0
     def enable_augment(self):
         """Allocate the context's view buffers (cy_enable_augment; once, on the first augmented call)."""

@@ -4,7 +4,7 @@ caesar_yolo/inference.py:473 (`SFinder.wcs`) and caesar_yolo/utils.py:236 / :411
 here (Greisen & Calabretta 2002, Calabretta & Greisen 2002: linear transform, TAN / SIN / ARC / STG zenithal, CAR / SFL / MER
 cylindrical projections, spherical rotation with LONPOLE / LATPOLE defaults, CROTA2 / CDi_j / PCi_j conventions); everything
 else (distortions, -TAB, spectral axes) is out of scope and raises.  Pinned against astropy 4.3.1 by tests/golden/wcs.json
-(oracle/gen_golden.py: gen_wcs; tests/test_wcs_cpu.py).  No output of the detect path uses it -- as in the reference."""
+(oracle/gen_golden.py: gen_wcs; tests/test_wcs_cpu.py).  The detect path itself does not use it, as in the reference; --measure_sources reads it for the ra / dec of a source (measure.py)."""
 import math
 import numpy as np
 

@@ -254,6 +254,31 @@ int cy_detect_tiles_augmented(cy_ctx* ctx, const float* d_mosaic, int MH, int MW
                               int imgsz, const cy_preproc_cfg* cfg, float conf, float iou, double thr_soft, double thr_hard,
                               int augment, float* d_out, int* d_out_count, int* d_status, void* stream);
 
+/* ---- catalog source measurement (an addition: the reference's catalog stops at boxes) ----------------------------------
+ * Flux, peak, centroid moments and the local background of n catalog boxes on the resident image d_img [MH][MW] (fp32 as
+ * cy_mosaic_prepare leaves it: blank pixels are 0; a pixel is VALID when it is != 0 and finite).  h_boxes: n x {x1, y1, x2, y2}
+ * float64 in 0-based pixels of d_img (a pixel's centre at its index); they may lie partly or wholly outside the image.
+ *   box window  ix in [max(0, ceil(x1)), min(MW - 1, floor(x2))], iy likewise with MH; it may be empty
+ *   ring        the box window grown by `ring` pixels on each side, clipped to the image, minus the box window (an empty box
+ *               window has no ring)
+ * h_out row, CY_MEAS_FIELDS float64:
+ *   [0] npix, [1] nring  valid pixels of the box window / of the ring
+ *   [2] bkg   exact median of the ring's valid pixels (even count: (a + b) / 2), [3] rms = 1.4826 * exact median of |v - bkg|;
+ *             both 0 when nring == 0
+ *   [4] peak  largest valid pixel of the box window, [5] x_peak, [6] y_peak its first occurrence in row-major order
+ *   [7] sum   of (v - bkg) over the valid pixels of the box window
+ *   [8] sw, [9] swx, [10] swy   sums of w, w * ix, w * iy with w = v - bkg where that is > 0, else 0
+ *   [11] reserved (0)
+ *   npix == 0: peak = sum = sw = swx = swy = 0, x_peak = y_peak = -1.
+ * Counts, medians and the peak do not depend on summation order; the sums are float64 with a fixed association (two calls give
+ * the same bits).  One launch (one workgroup per box) and one copy to h_out; synchronous on `stream`.  n == 0: CY_OK, nothing
+ * launched.  ring < 0, MH / MW <= 0, a null pointer, or an image of 2^31 pixels or more: CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_MEAS_FIELDS 12   /* npix nring bkg rms peak x_peak y_peak sum sw swx swy reserved */
+int cy_measure_sources(cy_ctx* ctx, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring,
+                       double* h_out /* [n][CY_MEAS_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_measure_sources call took (hipEvents around the launch); -1 before the first call */
+int cy_measure_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- catalog records and cross-tile merge (host code, no GPU) --------------------------------- */
 /* Analyzer.make_json_results (caesar_yolo/evaluation.py:418-469: int() truncation, tile-local edge rule, tile origin)
  * followed by SFinder.find_sources_at_edge (caesar_yolo/inference.py:663-726).

@@ -12,7 +12,10 @@ Differences that come with the MI355X engine:
   --precision fp16x3|fp32|fp16 (default fp16x3 = the fast parity context: fp16 high + low halves, fp32 accumulate; fp32 = exact fp32
   FMA chains, 2.7x slower; fp16 = throughput mode, 3x faster, ~2 % of detections differ), --tile_batch N  are new;
   --augment  (new) test-time augmentation of every model call, ultralytics' augment=True: the tile, its 0.83-scale left-right
-             flip and its 0.67-scale view through the network, one NMS over the three (about 2.2x the network work per tile).
+             flip and its 0.67-scale view through the network, one NMS over the three (about 2.2x the network work per tile);
+  --measure_sources  (new) every source of the final catalog (serial: out_<id>.json, tiled: catalog_<id>.json) also carries
+             npix, bkg, rms, peak, snr, x_peak, y_peak, x0, y0, flux_sum, flux, ra, dec, measured on the device-resident image
+             (cy_measure_sources; definitions in DESIGN.md); --measure_ring N (default 8) is the width of the background ring.
 """
 import argparse
 import logging
@@ -85,6 +88,10 @@ def parse_args(argv=None):
     p.add_argument('--tile_batch', type=int, default=64)
     p.add_argument('--augment', dest='augment', action='store_true',
                    help='test-time augmentation (ultralytics augment=True): three views per tile, one joint NMS')
+    p.add_argument('--measure_sources', dest='measure_sources', action='store_true',
+                   help='measure every catalog source on the GPU: background, rms, peak, centroid, flux and sky position')
+    p.add_argument('--measure_ring', dest='measure_ring', type=int, default=8,
+                   help='width in pixels of the background ring around a source box (with --measure_sources)')
     return p.parse_args(argv)
 
 
@@ -100,6 +107,9 @@ def validate_args(args):
         return -1
     if not args.weights.startswith("seeded:") and not os.path.isfile(args.weights):
         logger.error("Given weight file %s not existing or not a file!" % args.weights)
+        return -1
+    if args.measure_ring < 0:
+        logger.error("--measure_ring must be >= 0!")
         return -1
     if args.split_img_in_tiles and (args.xmin >= 0 or args.xmax >= 0 or args.ymin >= 0 or args.ymax >= 0):
         # serial runs crop like the reference (inference.py:499-505); the tiled run of the reference derives its grid from
@@ -163,7 +173,8 @@ def main(argv=None):
               'save_plot': args.save_plots,
               'save_tile_catalog': args.save_tile_catalog, 'save_tile_region': args.save_tile_region,
               'save_tile_img': args.save_tile_img,
-              'precision': args.precision, 'augment': args.augment})
+              'precision': args.precision, 'augment': args.augment,
+              'measure_sources': args.measure_sources, 'measure_ring': args.measure_ring})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,
                  max_imgsz=max(args.imgsize, 32))
     sfinder = SFinder(model, C)

@@ -1,0 +1,92 @@
+"""Cost of --measure_sources (developer tool): the S16k tiled run of scripts/run.py (README recipe: seeded:l:5, zscale + minmax,
+512-px tiles at step 0.8) in ONE process, switch off and on alternating, `--runs` timed runs each after a warm-up.
+
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--host-ref]
+
+Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
+also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
+(hipEvents around the launch, cy_measure_kernel_ms) and the number of sources.  --host-ref times tests/measure_ref.py (numpy
+float64) on the same boxes.  --off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
+JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import numpy as np
+import __graft_entry__ as ge
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=16384)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--ring", type=int, default=8)
+    ap.add_argument("--off-only", action="store_true")
+    ap.add_argument("--host-ref", action="store_true")
+    args = ap.parse_args()
+    ge.build()
+    import run
+    from caesar_yolo_amd import synth, utils, inference
+    seen = []
+    orig = inference.SFinder.run_parallel
+
+    def timed(self):
+        rc = orig(self)
+        seen.append({"run_ms": 1e3 * self.runtime, "sources": len(self.sources["sources"]),
+                     "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms")})
+        return rc
+    inference.SFinder.run_parallel = timed
+    res = {"size": args.size, "runs": args.runs, "ring": args.ring}
+    with tempfile.TemporaryDirectory() as d:
+        img = synth.make_mosaic(args.size, seed=20260104)
+        path = os.path.join(d, "s16k.fits")
+        utils.write_fits_image(path, img, synth.FITS_CARDS + [("CTYPE1", "RA---SIN"), ("CTYPE2", "DEC--SIN"), ("CRVAL1", 254.5),
+                                                              ("CRVAL2", -41.25), ("CRPIX1", args.size / 2.0), ("CRPIX2", args.size / 2.0)])
+        base = ["--image=" + path, "--weights=seeded:l:5", "--preprocessing", "--zscale_stretch", "--normalize_minmax", "--norm_max=255",
+                "--imgsize=512", "--split_img_in_tiles", "--tile_xsize=512", "--tile_ysize=512", "--tile_xstep=0.8", "--tile_ystep=0.8",
+                "--devices=0"]
+        on = ["--measure_sources", "--measure_ring=%d" % args.ring]
+        cwd = os.getcwd()
+        os.chdir(d)
+        try:
+            variants = [("off", base)] + ([] if args.off_only else [("on", base + on)])
+            for name, argv in variants:                    # warm-up of each variant
+                assert run.main(argv) == 0
+            seen.clear()
+            got = {name: [] for name, _ in variants}
+            for _ in range(args.runs):                     # alternating
+                for name, argv in variants:
+                    assert run.main(argv) == 0
+                    got[name].append(seen.pop())
+            for name, rows in got.items():
+                res[name] = {"run_ms": [round(r["run_ms"], 1) for r in rows], "run_ms_median": statistics.median(r["run_ms"] for r in rows),
+                             "sources": rows[0]["sources"]}
+                if name == "on":
+                    res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
+                    res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
+                    res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
+                    res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
+            if "on" in got:
+                res["added_ms"] = res["on"]["run_ms_median"] - res["off"]["run_ms_median"]
+            if args.host_ref and "on" in got:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import measure_ref
+                from caesar_yolo_amd import measure
+                src = json.load(open(os.path.join(d, "catalog_s16k.json")))["sources"]
+                host = np.where(np.isfinite(img), img, np.float32(0)).astype(np.float32)
+                t0 = time.time()
+                measure_ref.measure(host, measure.boxes_of(src), args.ring)
+                res["host_ref_ms"] = 1e3 * (time.time() - t0)
+        finally:
+            os.chdir(cwd)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

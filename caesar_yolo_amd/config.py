@@ -32,4 +32,8 @@ CONFIG = {
     'augment': False,                  # test-time augmentation of every model call (ultralytics augment=True: 3 views, joint NMS)
     'measure_sources': False,          # NEW: flux, peak, centroid, local background and sky position of every catalog source
     'measure_ring': 8,                 # width in pixels of the background ring around a source's box
+    'measure_islands': False,          # NEW: seed / merge-threshold islands of every source's box: pixel count, flux, centroid, shape
+    'island_seed_sigma': 5.0,          # a pixel at or above bkg + island_seed_sigma * rms seeds an island ...
+    'island_merge_sigma': 2.5,         # ... which grows over connected pixels at or above bkg + island_merge_sigma * rms
+    'island_conn': 8,                  # 8 or 4 neighbours
 }

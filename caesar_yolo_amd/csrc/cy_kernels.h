@@ -261,4 +261,21 @@ struct MeasureArgs {
 };
 hipError_t launch_measure(const MeasureArgs& a, hipStream_t s);
 
+// ---- source islands (cy_islands.hip) ---------------------------------------------------------------
+constexpr int ISL_FIELDS = 20;                 // CY_ISL_FIELDS
+constexpr int ISL_LDS_MAX = 4096;              // largest window (pixels) whose labels live in LDS: 16 KiB of labels per workgroup
+constexpr long long ISL_MAX_AREA = 1LL << 24;  // largest supported window; a larger one gets status 1
+constexpr long long ISL_OFF_LDS = -1, ISL_OFF_TOO_LARGE = -2;
+struct IslandArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    const int* win;                 // [n][4] inclusive box windows {bx0, bx1, by0, by1} inside the image; bx1 < bx0 or by1 < by0 = empty
+    const double* thr;              // [n][3] {seed_thr, merge_thr, bkg}
+    const long long* off;           // [n][2] {first label of the source in ws | ISL_OFF_LDS | ISL_OFF_TOO_LARGE, first mask byte in mask}
+    int n, conn;                    // conn: 4 or 8
+    unsigned* ws;                   // labels of the windows above ISL_LDS_MAX pixels, one u32 per pixel (null when there is none)
+    unsigned char* mask;            // zeroed by the caller; null: no mask wanted
+    double* out;                    // [n][ISL_FIELDS]
+};
+hipError_t launch_islands(const IslandArgs& a, hipStream_t s);
+
 }  // namespace cy

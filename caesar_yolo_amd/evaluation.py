@@ -29,7 +29,8 @@ class Analyzer(object):
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
-        self.measure = bool(config.get('measure_sources', False))
+        self.islands = bool(config.get('measure_islands', False))       # NEW: --measure_islands, the second step (implies the first)
+        self.measure = bool(config.get('measure_sources', False)) or self.islands
         self.measure_ring = int(config.get('measure_ring', 8))
         self.beam_area, self.wcs, self.wcs_origin = 0, None, (0, 0)
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
@@ -157,6 +158,11 @@ class Analyzer(object):
                 try:
                     measure.measure_and_annotate(det, frame, self.results["objs"], self.measure_ring, self.beam_area, self.wcs,
                                                  box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
+                    if self.islands:
+                        c = self.config
+                        measure.islands_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
+                                                     c.get('island_merge_sigma', 2.5), int(c.get('island_conn', 8)), self.beam_area,
+                                                     self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
                 except L.CyError as e:
                     logger.warning("Source measurement failed (err=%s)..." % str(e))
                     return -1

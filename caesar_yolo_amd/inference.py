@@ -579,6 +579,13 @@ class SFinder(object):
         measure.measure_and_annotate(det, img, src, int(self.config.get('measure_ring', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
         self.stats["measure_ms"] = 1e3 * (time.time() - t0)
         self.stats["measure_kernel_ms"] = det.measure_kernel_ms() if src else 0.0
+        if self.config.get('measure_islands', False):         # --measure_islands: the second step, on the same resident image
+            t1 = time.time()
+            c = self.config
+            measure.islands_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5),
+                                         int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
+            self.stats["islands_ms"] = 1e3 * (time.time() - t1)
+            self.stats["islands_kernel_ms"] = det.islands_kernel_ms() if src else 0.0
 
     # ---- tiled (reference :578-658)
     def run_parallel(self):
@@ -614,7 +621,7 @@ class SFinder(object):
         if rank == 0:
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
-            if c.get('measure_sources', False):
+            if c.get('measure_sources', False) or c.get('measure_islands', False):
                 self._measure(det, mosaic, src)
             self.sources = {"sources": src}
             if self.write_to_json:

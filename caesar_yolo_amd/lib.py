@@ -12,6 +12,9 @@ CY_MAX_DET = 300
 CY_MAX_STAGES = 8
 CY_MEAS_FIELDS = 12
 MEAS_NAMES = ("npix", "nring", "bkg", "rms", "peak", "x_peak", "y_peak", "sum", "sw", "swx", "swy", "reserved")
+CY_ISL_FIELDS = 20
+ISL_NAMES = ("status", "nseed", "nislands", "npix", "npix_main", "nborder", "xmin", "xmax", "ymin", "ymax", "S", "Sx", "Sy", "Sxx", "Syy",
+             "Sxy", "S_main", "reserved0", "reserved1", "reserved2")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
 F16, F32, F16X3 = 0, 1, 2
 PRECISIONS = {"fp16": F16, "f16": F16, "half": F16, "fp32": F32, "f32": F32, "float": F32, "fp16x3": F16X3, "f16x3": F16X3, "split": F16X3}
@@ -24,6 +27,7 @@ EXPORTS = [
     "cy_attention", "cy_maxpool5", "cy_make_tile_records",
     "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
+    "cy_measure_islands", "cy_islands_kernel_ms",
 ]
 
 
@@ -147,6 +151,8 @@ def load():
                                                 vp, vp, vp, vp]),
         "cy_measure_sources": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_int, dp, vp]),
         "cy_measure_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_measure_islands": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, dp, vp, C.POINTER(C.c_longlong), vp]),
+        "cy_islands_kernel_ms": (C.c_int, [vp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -6,10 +6,18 @@ finite) in the box window and in the background ring, the ring's median and 1.48
 valid pixel of the box and where it first occurs, the sum of (v - bkg) and the moments of the weights max(v - bkg, 0).  All positions
 are 0-based pixel indices of the measured image with a pixel's centre at its index.
 
+--measure_islands adds a second step: `cy_measure_islands` (HipDetector.measure_islands) on the same boxes with thresholds formed
+from the first step's bkg and rms, raw rows lib.ISL_NAMES, keys ISLAND_KEYS (annotate_islands).
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
+import math
+
 import numpy as np
 
 KEYS = ("npix", "bkg", "rms", "peak", "snr", "x_peak", "y_peak", "x0", "y0", "flux_sum", "flux", "ra", "dec")
+ISLAND_KEYS = ("island_count", "island_npix", "island_npix_main", "island_border", "island_x1", "island_x2", "island_y1", "island_y2",
+               "island_flux_sum", "island_flux", "island_flux_main", "x_isl", "y_isl", "ra_isl", "dec_isl", "major", "minor", "pa")
+FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
 
 def boxes_of(sources):
@@ -68,3 +76,99 @@ def measure_and_annotate(det, img_dev, sources, ring, beam_area, wcs, box_origin
         raw[:, 9] += bx * raw[:, 8]
         raw[:, 10] += by * raw[:, 8]
     return annotate(sources, raw, beam_area, wcs, wcs_origin)
+
+
+def box_window(box, MH, MW):
+    """(wx0, wy0, h, w) of the box window of cy_measure_sources / cy_measure_islands: ix in [max(0, ceil(x1)), min(MW - 1,
+    floor(x2))], iy likewise with MH; (0, 0, 0, 0) when it is empty (a NaN edge makes it empty)."""
+    x1, y1, x2, y2 = (float(v) for v in box)
+    if any(math.isnan(v) for v in (x1, y1, x2, y2)) or x1 > MW - 1 or y1 > MH - 1 or x2 < 0 or y2 < 0:
+        return 0, 0, 0, 0
+    # clipped before the conversion to int: an infinite edge is an ordinary edge beyond the image, as in the library
+    fx, fy = math.ceil(x1) if x1 > 0 else 0, math.ceil(y1) if y1 > 0 else 0
+    lx, ly = math.floor(x2) if x2 < MW - 1 else MW - 1, math.floor(y2) if y2 < MH - 1 else MH - 1
+    if lx < fx or ly < fy:
+        return 0, 0, 0, 0
+    return fx, fy, ly - fy + 1, lx - fx + 1
+
+
+def island_shape(S, Sx, Sy, Sxx, Syy, Sxy):
+    """(major, minor, pa) from the moments of the weights about the window's first pixel: central second moments cxx = Sxx / S -
+    (Sx / S)^2 etc., their eigenvalues l1 >= l2 (a negative one, from rounding, counts as 0), major / minor = FWHM * sqrt(l) in
+    pixels, pa = angle of the major axis from +x towards +y in degrees, in (-90, 90], 0 when l1 == l2."""
+    mx, my = Sx / S, Sy / S
+    cxx, cyy, cxy = Sxx / S - mx * mx, Syy / S - my * my, Sxy / S - mx * my
+    half, d = (cxx + cyy) / 2.0, math.hypot((cxx - cyy) / 2.0, cxy)
+    l1, l2 = max(half + d, 0.0), max(half - d, 0.0)
+    pa = 0.0
+    if l1 != l2:
+        pa = 0.5 * math.degrees(math.atan2(2.0 * cxy + 0.0, cxx - cyy))
+        if pa <= -90.0:
+            pa += 180.0
+    return FWHM * math.sqrt(l1), FWHM * math.sqrt(l2), pa
+
+
+def annotate_islands(sources, raw, win0, beam_area, wcs, origin=(0, 0)):
+    """Adds ISLAND_KEYS to every source dict (in place; returns the list).  raw: [n, CY_ISL_FIELDS] rows of cy_measure_islands on
+    the boxes of `sources`; win0: [n, 2] first column / row (wx0, wy0) of every box window (box_window), in the frame the catalog's
+    positions are wanted in, as is the bounding box in raw.
+      island_count, island_npix, island_npix_main   nislands, npix, npix_main;  island_border  nborder > 0
+      island_x1 / x2 / y1 / y2   bounding box of the island set (pixel indices)
+      island_flux_sum  S;  island_flux, island_flux_main = S / beam_area, S_main / beam_area when beam_area > 0, else None
+      x_isl, y_isl  wx0 + Sx / S, wy0 + Sy / S;  ra_isl, dec_isl  wcs.wcs_pix2world(x_isl + ox, y_isl + oy, 0), None without a WCS
+      major, minor, pa   island_shape()
+    No seed: the three counts are 0, island_border False and every other key None.  status == 1 (window above the supported
+    maximum): every key None.  S == 0: position and shape keys None."""
+    if not sources:
+        return sources
+    raw = np.asarray(raw, np.float64).reshape(len(sources), -1)
+    win0 = np.asarray(win0, np.float64).reshape(len(sources), 2)
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for s, r, (wx0, wy0) in zip(sources, raw, win0):
+        for k in ISLAND_KEYS:
+            s[k] = None
+        if r[0] != 0.0:
+            continue
+        s["island_count"], s["island_npix"], s["island_npix_main"], s["island_border"] = int(r[2]), int(r[3]), int(r[4]), bool(r[5] > 0)
+        if r[1] == 0.0:
+            continue
+        s["island_x1"], s["island_x2"], s["island_y1"], s["island_y2"] = (int(v) for v in r[6:10])
+        S, Sx, Sy, Sxx, Syy, Sxy, Sm = (float(v) for v in r[10:17])
+        s["island_flux_sum"] = S
+        if ba > 0.0:
+            s["island_flux"], s["island_flux_main"] = S / ba, Sm / ba
+        if S == 0.0:
+            continue
+        s["x_isl"], s["y_isl"] = float(wx0) + Sx / S, float(wy0) + Sy / S
+        s["major"], s["minor"], s["pa"] = island_shape(S, Sx, Sy, Sxx, Syy, Sxy)
+        if wcs is not None:
+            a, d = wcs.wcs_pix2world(s["x_isl"] + ox, s["y_isl"] + oy, 0)
+            s["ra_isl"], s["dec_isl"] = float(a), float(d)
+    return sources
+
+
+def island_thresholds(sources, k_seed, k_merge):
+    """[n, 3] float64 {seed_thr, merge_thr, bkg} from the bkg and rms the first step (annotate) left on the sources."""
+    bkg = np.array([s["bkg"] for s in sources], np.float64)
+    rms = np.array([s["rms"] for s in sources], np.float64)
+    return np.stack([bkg + float(k_seed) * rms, bkg + float(k_merge) * rms, bkg], 1)
+
+
+def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0)):
+    """The island step, after measure_and_annotate on the same sources and image: thresholds bkg + k * rms in numpy float64, one
+    cy_measure_islands call, then annotate_islands().  box_origin / wcs_origin as in measure_and_annotate: positions come back in
+    catalog coordinates."""
+    if not sources:
+        return sources
+    bx, by = float(box_origin[0]), float(box_origin[1])
+    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
+    raw = det.measure_islands(img_dev, boxes, island_thresholds(sources, k_seed, k_merge), conn=conn)
+    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
+    if bx or by:
+        raw = raw.copy()
+        has = raw[:, 3] > 0
+        raw[has, 6:8] += bx
+        raw[has, 8:10] += by
+    return annotate_islands(sources, raw, win0, beam_area, wcs, wcs_origin)

@@ -312,6 +312,42 @@ class HipDetector(object):
         self._chk(self.lib.cy_measure_kernel_ms(self.ctx, C.byref(ms)))
         return float(ms.value)
 
+    # ---- source islands (the second measurement step)
+    def measure_islands(self, img_dev, boxes, thr, conn=8, return_masks=False):
+        """Seed / merge-threshold islands of the box windows (cy_measure_islands).  img_dev, boxes: as measure_sources; thr: [n, 3]
+        float64 {seed_thr, merge_thr, bkg} per source.  -> numpy float64 [n, CY_ISL_FIELDS] (lib.ISL_NAMES); with return_masks
+        also a list of n uint8 arrays shaped like the box windows (0 outside the island set, 1 in it, 2 in the main island; an
+        empty window gives an array of shape (0, 0))."""
+        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        thr = np.ascontiguousarray(np.asarray(thr, np.float64).reshape(-1, 3))
+        n = boxes.shape[0]
+        if thr.shape[0] != n:
+            raise L.CyError("measure_islands: %d boxes but %d threshold rows" % (n, thr.shape[0]))
+        out = np.zeros((n, L.CY_ISL_FIELDS), np.float64)
+        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
+            raise L.CyError("measure_islands: a contiguous 2-D float32 image on %s is required" % (self.tdev,))
+        MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+        dp = C.POINTER(C.c_double)
+        mask = off = shapes = None
+        if return_masks:
+            from .measure import box_window
+            shapes = [box_window(b, MH, MW)[2:] for b in boxes]
+            off = np.zeros(n + 1, np.int64)
+            np.cumsum([h * w for h, w in shapes], out=off[1:])
+            mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+        self._chk(self.lib.cy_measure_islands(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), thr.ctypes.data_as(dp), n, int(conn),
+                                              out.ctypes.data_as(dp), C.c_void_p(mask.ctypes.data) if return_masks else None,
+                                              off.ctypes.data_as(C.POINTER(C.c_longlong)) if return_masks else None, self._stream()))
+        if not return_masks:
+            return out
+        return out, [mask[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(n)]
+
+    def islands_kernel_ms(self):
+        """Kernel time of the last measure_islands call in ms (hipEvents around the launch); -1 before the first."""
+        ms = C.c_double(-1.0)
+        self._chk(self.lib.cy_islands_kernel_ms(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
     # ---- test-time augmentation (ultralytics `augment=True`): views 1 (0.83, flipped) and 2 (0.67) beside view 0
     def enable_augment(self):
         """Allocate the context's view buffers (cy_enable_augment; once, on the first augmented call)."""

@@ -279,6 +279,37 @@ int cy_measure_sources(cy_ctx* ctx, const float* d_img, int MH, int MW, const do
 /* milliseconds the kernel of the last cy_measure_sources call took (hipEvents around the launch); -1 before the first call */
 int cy_measure_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- source islands (an addition, the second measurement step) -------------------------------------------------------------
+ * Seed / merge-threshold connected components of the box windows of n catalog boxes.  Image, validity of a pixel, pixel-centre
+ * convention and box window are those of cy_measure_sources.  h_thr: n x {seed_thr, merge_thr, bkg} float64.
+ *   candidate   valid pixel of the box window with (double)v >= merge_thr; seed: a candidate with (double)v >= seed_thr.  A NaN
+ *               threshold leaves the source without candidates (or seeds)
+ *   component   maximal set of candidates connected through `conn` = 8 or 4 neighbours inside the box window
+ *   island set  union of the components that hold a seed; main island: the component of the window's peak pixel (largest valid
+ *               pixel, first in row-major order), which is a seed whenever there is one
+ * h_out row, CY_ISL_FIELDS float64, with dx = ix - wx0, dy = iy - wy0 (wx0, wy0: first column / row of the box window) and
+ * w = (double)v - bkg:
+ *   [0] status   0 measured; 1 the window has more than 2^24 pixels: nothing measured, every other field as for an empty window
+ *   [1] nseed, [2] nislands, [3] npix (island set), [4] npix_main, [5] nborder (island-set pixels on the window's outer rows / columns)
+ *   [6] xmin, [7] xmax, [8] ymin, [9] ymax   bounding box of the island set in image pixels; -1 when npix == 0
+ *   [10] S = sum w, [11] Sx = sum w * dx, [12] Sy = sum w * dy, [13] Sxx = sum w * (dx * dx), [14] Syy = sum w * (dy * dy),
+ *   [15] Sxy = sum w * (dx * dy), [16] S_main = sum w over the main island, [17..19] reserved (0)
+ *   Empty window or no seed: counts and sums 0, bounding box -1, status 0.
+ * h_mask (may be NULL): one byte per pixel of every box window, windows concatenated in source order, row-major inside a window:
+ * 0 not in the island set, 1 in it, 2 in the main island.  h_mask_off: n + 1 offsets, [0] = 0 and [i + 1] - [i] = pixels of window
+ * i; required with h_mask and checked against the windows.
+ * Counts, bounding box and mask do not depend on any order; the sums are float64 with a fixed association (two calls give the same
+ * bytes).  One launch (one workgroup per source, labels in LDS for windows of up to 4096 pixels, else in a workspace allocated
+ * for the call) and the copies to h_out / h_mask; synchronous on `stream`.  n == 0: CY_OK, nothing launched.  conn not 4 or 8,
+ * MH / MW <= 0, a null pointer, an image of 2^31 pixels or more, seed_thr < merge_thr, or h_mask_off that disagrees with the
+ * windows: CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_ISL_FIELDS 20
+int cy_measure_islands(cy_ctx* ctx, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_thr /* n x {seed, merge, bkg} */,
+                       int n, int conn, double* h_out /* [n][CY_ISL_FIELDS] */, unsigned char* h_mask /* may be NULL */,
+                       const long long* h_mask_off /* n + 1 offsets, required with h_mask */, void* stream);
+/* milliseconds the kernel of the last cy_measure_islands call took (hipEvents around the launch); -1 before the first call */
+int cy_islands_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- catalog records and cross-tile merge (host code, no GPU) --------------------------------- */
 /* Analyzer.make_json_results (caesar_yolo/evaluation.py:418-469: int() truncation, tile-local edge rule, tile origin)
  * followed by SFinder.find_sources_at_edge (caesar_yolo/inference.py:663-726).

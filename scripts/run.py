@@ -16,6 +16,11 @@ Differences that come with the MI355X engine:
   --measure_sources  (new) every source of the final catalog (serial: out_<id>.json, tiled: catalog_<id>.json) also carries
              npix, bkg, rms, peak, snr, x_peak, y_peak, x0, y0, flux_sum, flux, ra, dec, measured on the device-resident image
              (cy_measure_sources; definitions in DESIGN.md); --measure_ring N (default 8) is the width of the background ring.
+  --measure_islands  (new; implies --measure_sources) every source also carries the islands of its box: pixels at or above
+             bkg + --island_merge_sigma * rms (default 2.5) connected (--island_conn 8 or 4) to a pixel at or above
+             bkg + --island_seed_sigma * rms (default 5): island_count, island_npix, island_npix_main, island_border,
+             island_x1 / x2 / y1 / y2, island_flux_sum, island_flux, island_flux_main, x_isl, y_isl, ra_isl, dec_isl, major, minor, pa
+             (cy_measure_islands; DESIGN.md "Source islands").
 """
 import argparse
 import logging
@@ -92,6 +97,15 @@ def parse_args(argv=None):
                    help='measure every catalog source on the GPU: background, rms, peak, centroid, flux and sky position')
     p.add_argument('--measure_ring', dest='measure_ring', type=int, default=8,
                    help='width in pixels of the background ring around a source box (with --measure_sources)')
+    p.add_argument('--measure_islands', dest='measure_islands', action='store_true',
+                   help='extract the seed / merge-threshold islands of every source box on the GPU: pixel count, flux, centroid, shape '
+                        '(implies --measure_sources)')
+    p.add_argument('--island_seed_sigma', dest='island_seed_sigma', type=float, default=5.0,
+                   help='an island needs a pixel at or above bkg + this many rms (with --measure_islands)')
+    p.add_argument('--island_merge_sigma', dest='island_merge_sigma', type=float, default=2.5,
+                   help='an island grows over connected pixels at or above bkg + this many rms (with --measure_islands)')
+    p.add_argument('--island_conn', dest='island_conn', type=int, choices=[4, 8], default=8,
+                   help='neighbours that connect the pixels of an island (with --measure_islands)')
     return p.parse_args(argv)
 
 
@@ -110,6 +124,9 @@ def validate_args(args):
         return -1
     if args.measure_ring < 0:
         logger.error("--measure_ring must be >= 0!")
+        return -1
+    if args.measure_islands and not args.island_seed_sigma >= args.island_merge_sigma:
+        logger.error("--island_seed_sigma must not be below --island_merge_sigma!")
         return -1
     if args.split_img_in_tiles and (args.xmin >= 0 or args.xmax >= 0 or args.ymin >= 0 or args.ymax >= 0):
         # serial runs crop like the reference (inference.py:499-505); the tiled run of the reference derives its grid from
@@ -174,7 +191,9 @@ def main(argv=None):
               'save_tile_catalog': args.save_tile_catalog, 'save_tile_region': args.save_tile_region,
               'save_tile_img': args.save_tile_img,
               'precision': args.precision, 'augment': args.augment,
-              'measure_sources': args.measure_sources, 'measure_ring': args.measure_ring})
+              'measure_sources': args.measure_sources or args.measure_islands, 'measure_ring': args.measure_ring,
+              'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
+              'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,
                  max_imgsz=max(args.imgsize, 32))
     sfinder = SFinder(model, C)

@@ -1,12 +1,15 @@
-"""Cost of --measure_sources (developer tool): the S16k tiled run of scripts/run.py (README recipe: seeded:l:5, zscale + minmax,
-512-px tiles at step 0.8) in ONE process, switch off and on alternating, `--runs` timed runs each after a warm-up.
+"""Cost of --measure_sources and --measure_islands (developer tool): the S16k tiled run of scripts/run.py (README recipe:
+seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
+alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
 (hipEvents around the launch, cy_measure_kernel_ms) and the number of sources.  --host-ref times tests/measure_ref.py (numpy
-float64) on the same boxes.  --off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
+float64) on the same boxes.  With --measure_islands the same three numbers for the island step (islands_ms, islands_kernel_ms), the
+histogram of the box-window areas of the catalog and the share of sources whose window is labelled in LDS (up to 4096 pixels); --host-ref
+then also times tests/island_ref.py.  --off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
 JSON line."""
 import argparse
 import json
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--ring", type=int, default=8)
     ap.add_argument("--off-only", action="store_true")
+    ap.add_argument("--no-islands", action="store_true")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -39,7 +43,8 @@ def main():
     def timed(self):
         rc = orig(self)
         seen.append({"run_ms": 1e3 * self.runtime, "sources": len(self.sources["sources"]),
-                     "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms")})
+                     "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms"),
+                     "islands_ms": self.stats.get("islands_ms"), "islands_kernel_ms": self.stats.get("islands_kernel_ms")})
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -56,6 +61,8 @@ def main():
         os.chdir(d)
         try:
             variants = [("off", base)] + ([] if args.off_only else [("on", base + on)])
+            if not (args.off_only or args.no_islands):
+                variants.append(("islands", base + on + ["--measure_islands"]))
             for name, argv in variants:                    # warm-up of each variant
                 assert run.main(argv) == 0
             seen.clear()
@@ -67,13 +74,27 @@ def main():
             for name, rows in got.items():
                 res[name] = {"run_ms": [round(r["run_ms"], 1) for r in rows], "run_ms_median": statistics.median(r["run_ms"] for r in rows),
                              "sources": rows[0]["sources"]}
-                if name == "on":
+                if name == "islands":
+                    for k in ("islands_ms", "islands_kernel_ms"):
+                        res[name][k] = [round(r[k], 3) for r in rows]
+                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
+                if name in ("on", "islands"):
                     res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
                     res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
                     res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
                     res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
             if "on" in got:
                 res["added_ms"] = res["on"]["run_ms_median"] - res["off"]["run_ms_median"]
+            if "islands" in got:                            # read before the next variant overwrites the catalog: it was the last to run
+                from caesar_yolo_amd import measure
+                res["islands_added_ms"] = res["islands"]["run_ms_median"] - res["off"]["run_ms_median"]
+                src = json.load(open(os.path.join(d, "catalog_s16k.json")))["sources"]
+                area = np.array([np.prod(measure.box_window(b, args.size, args.size)[2:]) for b in measure.boxes_of(src)])
+                edges = [0, 1, 256, 1024, 4097, 16384, 65536, 262144, 1 << 24, 1 << 62]
+                res["window_area_histogram"] = {"[%d, %d)" % (a, b): int(((area >= a) & (area < b)).sum()) for a, b in zip(edges, edges[1:])}
+                res["window_area_max"] = int(area.max()) if area.size else 0
+                res["lds_share"] = float((area <= 4096).mean()) if area.size else 0.0
+                res["with_island"] = int(sum(bool(s["island_count"]) for s in src))
             if args.host_ref and "on" in got:
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import measure_ref
@@ -83,6 +104,11 @@ def main():
                 t0 = time.time()
                 measure_ref.measure(host, measure.boxes_of(src), args.ring)
                 res["host_ref_ms"] = 1e3 * (time.time() - t0)
+                if "islands" in got:
+                    import island_ref
+                    t0 = time.time()
+                    island_ref.islands(host, measure.boxes_of(src), measure.island_thresholds(src, 5.0, 2.5), 8)
+                    res["host_island_ref_ms"] = 1e3 * (time.time() - t0)
         finally:
             os.chdir(cwd)
     print(json.dumps(res))

@@ -36,4 +36,10 @@ CONFIG = {
     'island_seed_sigma': 5.0,          # a pixel at or above bkg + island_seed_sigma * rms seeds an island ...
     'island_merge_sigma': 2.5,         # ... which grows over connected pixels at or above bkg + island_merge_sigma * rms
     'island_conn': 8,                  # 8 or 4 neighbours
+    'bkg_map': False,                  # NEW: global background / noise mesh; bkg_map, rms_map, snr_map per source, island thresholds from it
+    'bkg_cell': 128,                   # side of a mesh cell in pixels (4 .. 4096)
+    'bkg_clip_sigma': 3.0,             # a clip keeps the pixels within this many rms of the cell median ...
+    'bkg_clip_iters': 3,               # ... and is applied this many times (0 .. 32)
+    'bkg_min_pix': 64,                 # a cell with fewer surviving pixels is filled from the nearest cell that has them
+    'save_bkg_maps': False,            # write the per-pixel maps as FITS images beside the catalog
 }

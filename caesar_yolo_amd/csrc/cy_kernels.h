@@ -278,4 +278,22 @@ struct IslandArgs {
 };
 hipError_t launch_islands(const IslandArgs& a, hipStream_t s);
 
+// ---- background and noise mesh (cy_background.hip) -------------------------------------------------
+constexpr int BKG_FIELDS = 8;                  // CY_BKG_FIELDS
+constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;
+constexpr int BKG_LDS_MAX = 128 * 128;         // largest cell (pixels) that is copied into LDS: 64 KiB per workgroup
+struct BackgroundArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    int cell, ncy, ncx;             // ncx = ceil(MW / cell), ncy = ceil(MH / cell)
+    double k; int niter;            // clip width (> 0) and number of clips (0 .. BKG_NITER_MAX)
+    double* out;                    // [ncy][ncx][BKG_FIELDS]
+};
+hipError_t launch_background(const BackgroundArgs& a, hipStream_t s);
+struct BackgroundExpandArgs {
+    const double* mesh;             // [ncy][ncx][2] {bkg, rms}, filled
+    int ncy, ncx, cell, MH, MW;
+    float *bkg, *rms;               // [MH][MW] each; either may be null
+};
+hipError_t launch_background_expand(const BackgroundExpandArgs& a, hipStream_t s);
+
 }  // namespace cy

@@ -66,6 +66,7 @@ struct cy_ctx {
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
     double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
     double islands_ms = -1.0;                           // ... of the last cy_measure_islands call (cy_islands_kernel_ms)
+    double background_ms = -1.0;                        // ... of the last cy_measure_background call (cy_background_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1601,6 +1602,71 @@ int cy_islands_kernel_ms(const cy_ctx* c, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
     *out_ms = c->islands_ms;
     return CY_OK;
+}
+
+// ---- background and noise mesh ----------------------------------------------------------------
+static_assert(CY_BKG_FIELDS == BKG_FIELDS, "header and kernel disagree on the background row");
+
+int cy_measure_background(cy_ctx* c, const float* d_img, int MH, int MW, int cell, double k, int niter, double* h_out, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (MH <= 0 || MW <= 0 || cell < BKG_CELL_MIN || cell > BKG_CELL_MAX || !(k > 0.0) || niter < 0 || niter > BKG_NITER_MAX)
+        return fail(c, CY_ERR_ARG, "MH, MW > 0, 4 <= cell <= 4096, k > 0 and 0 <= niter <= 32 required");
+    if (!d_img || !h_out) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per cell)");
+    const int ncx = (MW + cell - 1) / cell, ncy = (MH + cell - 1) / cell;
+    const size_t bytes = (size_t)ncy * ncx * CY_BKG_FIELDS * sizeof(double);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    void* d_out = nullptr;
+    HIPCHK(c, sc.alloc(bytes, &d_out));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) {
+        BackgroundArgs a{};
+        a.img = d_img; a.MH = MH; a.MW = MW; a.cell = cell; a.ncy = ncy; a.ncx = ncx; a.k = k; a.niter = niter;
+        a.out = reinterpret_cast<double*>(d_out);
+        e = launch_background(a, st);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, bytes, hipMemcpyDeviceToHost, st);
+    const int rc = entry_done(c, e, st);
+    float ms = -1.0f;
+    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    c->background_ms = ms;
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
+}
+
+int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return CY_ERR_ARG;
+    *out_ms = c->background_ms;
+    return CY_OK;
+}
+
+int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (MH <= 0 || MW <= 0 || cell < BKG_CELL_MIN || cell > BKG_CELL_MAX) return fail(c, CY_ERR_ARG, "MH, MW > 0 and 4 <= cell <= 4096 required");
+    if (!h_mesh || (!d_bkg && !d_rms)) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more");
+    if (ncx != (MW + cell - 1) / cell || ncy != (MH + cell - 1) / cell) return fail(c, CY_ERR_ARG, "mesh shape disagrees with MH, MW and cell");
+    const size_t bytes = (size_t)ncy * ncx * 2 * sizeof(double);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    void* d_mesh = nullptr;
+    HIPCHK(c, sc.alloc(bytes, &d_mesh));
+    hipError_t e = hipMemcpyAsync(d_mesh, h_mesh, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        BackgroundExpandArgs a{};
+        a.mesh = reinterpret_cast<const double*>(d_mesh); a.ncy = ncy; a.ncx = ncx; a.cell = cell; a.MH = MH; a.MW = MW;
+        a.bkg = d_bkg; a.rms = d_rms;
+        e = launch_background_expand(a, st);
+    }
+    return entry_done(c, e, st);
 }
 
 // ---- test-time augmentation -------------------------------------------------------------------

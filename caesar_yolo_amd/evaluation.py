@@ -30,7 +30,8 @@ class Analyzer(object):
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
         self.islands = bool(config.get('measure_islands', False))       # NEW: --measure_islands, the second step (implies the first)
-        self.measure = bool(config.get('measure_sources', False)) or self.islands
+        self.bkg_map = bool(config.get('bkg_map', False)) or bool(config.get('save_bkg_maps', False))      # NEW: --bkg_map, between the two
+        self.measure = bool(config.get('measure_sources', False)) or self.islands or self.bkg_map
         self.measure_ring = int(config.get('measure_ring', 8))
         self.beam_area, self.wcs, self.wcs_origin = 0, None, (0, 0)
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
@@ -158,11 +159,20 @@ class Analyzer(object):
                 try:
                     measure.measure_and_annotate(det, frame, self.results["objs"], self.measure_ring, self.beam_area, self.wcs,
                                                  box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
+                    c = self.config
+                    if self.bkg_map:
+                        cell, k, niter, min_pix = measure.background_config(c)
+                        mesh, ndef = measure.background_and_annotate(det, frame, self.results["objs"], cell, k, niter, min_pix,
+                                                                     box_origin=(xmin, ymin))
+                        if ndef == 0:
+                            logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % min_pix)
+                        if c.get('save_bkg_maps', False):
+                            measure.save_background_maps(det, mesh, cell, frame.shape,
+                                                         self.outfile_json or ('out_' + str(self.image_id) + '.json'))
                     if self.islands:
-                        c = self.config
                         measure.islands_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
                                                      c.get('island_merge_sigma', 2.5), int(c.get('island_conn', 8)), self.beam_area,
-                                                     self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
+                                                     self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin, use_map=self.bkg_map)
                 except L.CyError as e:
                     logger.warning("Source measurement failed (err=%s)..." % str(e))
                     return -1

@@ -579,11 +579,22 @@ class SFinder(object):
         measure.measure_and_annotate(det, img, src, int(self.config.get('measure_ring', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
         self.stats["measure_ms"] = 1e3 * (time.time() - t0)
         self.stats["measure_kernel_ms"] = det.measure_kernel_ms() if src else 0.0
-        if self.config.get('measure_islands', False):         # --measure_islands: the second step, on the same resident image
+        c = self.config
+        use_map = bool(c.get('bkg_map', False)) or bool(c.get('save_bkg_maps', False))
+        if use_map:                                           # --bkg_map: the global mesh, between the two steps, same resident image
             t1 = time.time()
-            c = self.config
+            cell, k, niter, min_pix = measure.background_config(c)
+            mesh, ndef = measure.background_and_annotate(det, img, src, cell, k, niter, min_pix, box_origin=(ox, oy))
+            if ndef == 0:
+                logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % min_pix)
+            self.stats["background_ms"] = 1e3 * (time.time() - t1)
+            self.stats["background_kernel_ms"] = det.background_kernel_ms()
+            if c.get('save_bkg_maps', False):
+                measure.save_background_maps(det, mesh, cell, img.shape, self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
+        if c.get('measure_islands', False):                   # --measure_islands: the second step, on the same resident image
+            t1 = time.time()
             measure.islands_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5),
-                                         int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
+                                         int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy), use_map=use_map)
             self.stats["islands_ms"] = 1e3 * (time.time() - t1)
             self.stats["islands_kernel_ms"] = det.islands_kernel_ms() if src else 0.0
 
@@ -621,7 +632,7 @@ class SFinder(object):
         if rank == 0:
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
-            if c.get('measure_sources', False) or c.get('measure_islands', False):
+            if c.get('measure_sources', False) or c.get('measure_islands', False) or c.get('bkg_map', False) or c.get('save_bkg_maps', False):
                 self._measure(det, mosaic, src)
             self.sources = {"sources": src}
             if self.write_to_json:

@@ -9,6 +9,11 @@ are 0-based pixel indices of the measured image with a pixel's centre at its ind
 --measure_islands adds a second step: `cy_measure_islands` (HipDetector.measure_islands) on the same boxes with thresholds formed
 from the first step's bkg and rms, raw rows lib.ISL_NAMES, keys ISLAND_KEYS (annotate_islands).
 
+--bkg_map adds a global background and noise mesh between the two: `cy_measure_background` (HipDetector.measure_background) gives
+the clipped median and MAD of every cell (raw rows lib.BKG_NAMES), fill_mesh() fills the cells without data, sample_mesh()
+interpolates bilinearly between the cell centres, keys BKG_KEYS (annotate_background); the island step then takes its thresholds
+from bkg_map / rms_map.
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
 import math
 
@@ -17,6 +22,7 @@ import numpy as np
 KEYS = ("npix", "bkg", "rms", "peak", "snr", "x_peak", "y_peak", "x0", "y0", "flux_sum", "flux", "ra", "dec")
 ISLAND_KEYS = ("island_count", "island_npix", "island_npix_main", "island_border", "island_x1", "island_x2", "island_y1", "island_y2",
                "island_flux_sum", "island_flux", "island_flux_main", "x_isl", "y_isl", "ra_isl", "dec_isl", "major", "minor", "pa")
+BKG_KEYS = ("bkg_map", "rms_map", "snr_map")
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
 
@@ -148,22 +154,24 @@ def annotate_islands(sources, raw, win0, beam_area, wcs, origin=(0, 0)):
     return sources
 
 
-def island_thresholds(sources, k_seed, k_merge):
-    """[n, 3] float64 {seed_thr, merge_thr, bkg} from the bkg and rms the first step (annotate) left on the sources."""
-    bkg = np.array([s["bkg"] for s in sources], np.float64)
-    rms = np.array([s["rms"] for s in sources], np.float64)
+def island_thresholds(sources, k_seed, k_merge, use_map=False):
+    """[n, 3] float64 {seed_thr, merge_thr, bkg} from the bkg and rms the first step (annotate) left on the sources; use_map: from
+    the bkg_map and rms_map of the background mesh (annotate_background) instead."""
+    kb, kr = ("bkg_map", "rms_map") if use_map else ("bkg", "rms")
+    bkg = np.array([s[kb] for s in sources], np.float64)
+    rms = np.array([s[kr] for s in sources], np.float64)
     return np.stack([bkg + float(k_seed) * rms, bkg + float(k_merge) * rms, bkg], 1)
 
 
-def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0)):
+def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0), use_map=False):
     """The island step, after measure_and_annotate on the same sources and image: thresholds bkg + k * rms in numpy float64, one
     cy_measure_islands call, then annotate_islands().  box_origin / wcs_origin as in measure_and_annotate: positions come back in
-    catalog coordinates."""
+    catalog coordinates.  use_map: thresholds (and the bkg of the sums) from bkg_map / rms_map, after background_and_annotate."""
     if not sources:
         return sources
     bx, by = float(box_origin[0]), float(box_origin[1])
     boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    raw = det.measure_islands(img_dev, boxes, island_thresholds(sources, k_seed, k_merge), conn=conn)
+    raw = det.measure_islands(img_dev, boxes, island_thresholds(sources, k_seed, k_merge, use_map), conn=conn)
     MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
     win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
     if bx or by:
@@ -172,3 +180,98 @@ def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area
         raw[has, 6:8] += bx
         raw[has, 8:10] += by
     return annotate_islands(sources, raw, win0, beam_area, wcs, wcs_origin)
+
+
+# ---- background and noise mesh (--bkg_map)
+def fill_mesh(raw, min_pix=64):
+    """raw: [ncy, ncx, CY_BKG_FIELDS] rows of cy_measure_background.  -> (mesh [ncy, ncx, 2] float64 {bkg, rms}, number of defined
+    cells).  A cell is defined when n >= min_pix; an undefined cell takes bkg and rms of the defined cell with the smallest squared
+    index distance dcy^2 + dcx^2, ties to the smallest row-major index.  No defined cell: the mesh is 0 and the count 0."""
+    raw = np.asarray(raw, np.float64)
+    ncy, ncx = raw.shape[:2]
+    mesh = np.zeros((ncy, ncx, 2), np.float64)
+    ok = raw[:, :, 1] >= float(min_pix)
+    dy, dx = np.nonzero(ok)                                  # row-major order: the first minimum is the smallest index
+    if dy.size == 0:
+        return mesh, 0
+    mesh[ok] = raw[:, :, 2:4][ok]
+    uy, ux = np.nonzero(~ok)
+    for i in range(0, uy.size, 256):
+        d = (uy[i:i + 256, None] - dy[None, :]) ** 2 + (ux[i:i + 256, None] - dx[None, :]) ** 2
+        j = np.argmin(d, 1)
+        mesh[uy[i:i + 256], ux[i:i + 256]] = mesh[dy[j], dx[j]]
+    return mesh, int(dy.size)
+
+
+def _mesh_coord(p, cell, nc):
+    p = np.asarray(p, np.float64)
+    if nc == 1:
+        return np.zeros(p.shape, np.int64), np.zeros(p.shape, np.float64)
+    t = (p - (cell - 1) / 2.0) / float(cell)
+    t = np.where(t < 0.0, 0.0, t)
+    t = np.where(t > float(nc - 1), float(nc - 1), t)
+    i0 = np.minimum(np.floor(t).astype(np.int64), nc - 2)
+    return i0, t - i0
+
+
+def sample_mesh(mesh, cell, x, y):
+    """Bilinear interpolation of mesh [ncy, ncx] (or [ncy, ncx, C]: every plane) between the cell centres cx * cell + (cell - 1) / 2
+    at the pixel positions x, y (scalars or arrays of one shape); constant outside the outermost centres.  float64, the
+    expression and association of background_expand_kernel: (m00 (1 - fx) + m01 fx) (1 - fy) + (m10 (1 - fx) + m11 fx) fy."""
+    mesh = np.asarray(mesh, np.float64)
+    cell = int(cell)
+    ncy, ncx = mesh.shape[:2]
+    x0, fx = _mesh_coord(x, cell, ncx)
+    y0, fy = _mesh_coord(y, cell, ncy)
+    x1, y1 = np.minimum(x0 + 1, ncx - 1), np.minimum(y0 + 1, ncy - 1)
+    if mesh.ndim == 3:
+        fx, fy = fx[..., None], fy[..., None]
+    gx, gy = 1.0 - fx, 1.0 - fy
+    return (mesh[y0, x0] * gx + mesh[y0, x1] * fx) * gy + (mesh[y1, x0] * gx + mesh[y1, x1] * fx) * fy
+
+
+def annotate_background(sources, mesh, cell, origin=(0, 0)):
+    """Adds BKG_KEYS to every source dict (in place; returns the list), after annotate(): bkg_map, rms_map = sample_mesh at
+    (x_peak, y_peak), at the centre of the box when npix == 0; snr_map = (peak - bkg_map) / rms_map, 0 when rms_map == 0.
+    origin: catalog coordinates of pixel [0, 0] of the image the mesh was measured on."""
+    if not sources:
+        return sources
+    ox, oy = float(origin[0]), float(origin[1])
+    x = np.array([float(s["x_peak"]) if s["npix"] > 0 else (float(s["x1"]) + float(s["x2"])) / 2.0 for s in sources], np.float64) - ox
+    y = np.array([float(s["y_peak"]) if s["npix"] > 0 else (float(s["y1"]) + float(s["y2"])) / 2.0 for s in sources], np.float64) - oy
+    v = sample_mesh(np.asarray(mesh, np.float64)[:, :, :2], cell, x, y)
+    for s, (b, r) in zip(sources, v):
+        b, r = float(b), float(r)
+        s["bkg_map"], s["rms_map"] = b, r
+        s["snr_map"] = (float(s["peak"]) - b) / r if r != 0.0 else 0.0
+    return sources
+
+
+def background_and_annotate(det, img_dev, sources, cell=128, k=3.0, niter=3, min_pix=64, box_origin=(0, 0)):
+    """The background step, after measure_and_annotate on the same sources and image: one cy_measure_background call, fill_mesh(),
+    annotate_background().  -> (filled mesh [ncy, ncx, 2], number of defined cells); box_origin as in measure_and_annotate."""
+    raw = det.measure_background(img_dev, cell=cell, k=k, niter=niter)
+    mesh, ndef = fill_mesh(raw, min_pix)
+    annotate_background(sources, mesh, cell, box_origin)
+    return mesh, ndef
+
+
+def save_background_maps(det, mesh, cell, shape, catalog_path):
+    """--save_bkg_maps: the mesh expanded on the GPU (HipDetector.expand_background) and written as fp32 FITS images
+    bkg_<name>.fits / rms_<name>.fits beside the catalog file, <name> = the catalog's file name without its extension.
+    -> the two paths."""
+    import os
+    from . import utils
+    d, name = os.path.split(catalog_path)
+    name = os.path.splitext(name)[0]
+    paths = []
+    for tag, m in zip(("bkg_", "rms_"), det.expand_background(mesh, cell, shape)):
+        paths.append(os.path.join(d, tag + name + ".fits"))
+        utils.write_fits_image(paths[-1], m.cpu().numpy())
+    return tuple(paths)
+
+
+def background_config(config):
+    """(cell, k, niter, min_pix) of --bkg_map from a config dictionary."""
+    return (int(config.get('bkg_cell', 128)), float(config.get('bkg_clip_sigma', 3.0)), int(config.get('bkg_clip_iters', 3)),
+            int(config.get('bkg_min_pix', 64)))

@@ -348,6 +348,45 @@ class HipDetector(object):
         self._chk(self.lib.cy_islands_kernel_ms(self.ctx, C.byref(ms)))
         return float(ms.value)
 
+    # ---- background and noise mesh (the global noise map of the measurement steps)
+    def _image_2d(self, img_dev, what):
+        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
+            raise L.CyError("%s: a contiguous 2-D float32 image on %s is required" % (what, self.tdev))
+        return int(img_dev.shape[0]), int(img_dev.shape[1])
+
+    def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
+        """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.
+        -> numpy float64 [ncy, ncx, CY_BKG_FIELDS] (lib.BKG_NAMES), ncy = ceil(MH / cell), ncx = ceil(MW / cell)."""
+        MH, MW = self._image_2d(img_dev, "measure_background")
+        cell = int(cell)
+        if cell < 1:
+            raise L.CyError("measure_background: cell must be in [4, 4096]")
+        out = np.zeros((-(-MH // cell), -(-MW // cell), L.CY_BKG_FIELDS), np.float64)
+        self._chk(self.lib.cy_measure_background(self.ctx, self._p(img_dev), MH, MW, cell, float(k), int(niter),
+                                                 out.ctypes.data_as(C.POINTER(C.c_double)), self._stream()))
+        return out
+
+    def background_kernel_ms(self):
+        """Kernel time of the last measure_background call in ms (hipEvents around the launch); -1 before the first."""
+        ms = C.c_double(-1.0)
+        self._chk(self.lib.cy_background_kernel_ms(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
+    def expand_background(self, mesh, cell, shape, want=("bkg", "rms")):
+        """mesh: filled [ncy, ncx, 2] float64 {bkg, rms} (measure.fill_mesh); shape = (MH, MW).  -> (bkg, rms) device fp32 maps
+        [MH, MW], bilinear between the cell centres (cy_expand_background; measure.sample_mesh at every pixel, rounded to fp32);
+        a map not named in `want` is None."""
+        mesh = np.ascontiguousarray(np.asarray(mesh, np.float64))
+        if mesh.ndim != 3 or mesh.shape[2] != 2:
+            raise L.CyError("expand_background: a [ncy, ncx, 2] mesh is required")
+        MH, MW = int(shape[0]), int(shape[1])
+        if MH <= 0 or MW <= 0 or not want:
+            raise L.CyError("expand_background: a non-empty image shape and at least one map are required")
+        maps = [torch.empty((MH, MW), dtype=torch.float32, device=self.tdev) if n in want else None for n in ("bkg", "rms")]
+        self._chk(self.lib.cy_expand_background(self.ctx, mesh.ctypes.data_as(C.POINTER(C.c_double)), int(mesh.shape[0]), int(mesh.shape[1]),
+                                                int(cell), MH, MW, *[self._p(m) if m is not None else None for m in maps], self._stream()))
+        return tuple(maps)
+
     # ---- test-time augmentation (ultralytics `augment=True`): views 1 (0.83, flipped) and 2 (0.67) beside view 0
     def enable_augment(self):
         """Allocate the context's view buffers (cy_enable_augment; once, on the first augmented call)."""

@@ -310,6 +310,40 @@ int cy_measure_islands(cy_ctx* ctx, const float* d_img, int MH, int MW, const do
 /* milliseconds the kernel of the last cy_measure_islands call took (hipEvents around the launch); -1 before the first call */
 int cy_islands_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
+ * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
+ * and pixel-centre convention are those of cy_measure_sources.
+ *   mesh   ncx = ceil(MW / cell), ncy = ceil(MH / cell); cell (cy, cx) covers ix in [cx * cell, min(MW, (cx + 1) * cell) - 1], iy
+ *          likewise: the last row / column of cells may be partial
+ *   med(V) exact median of a set of pixels as float64 (even count: (a + b) / 2), sig(V) = 1.4826 * exact median of |v - med(V)|
+ *   clip   V_0 = the cell's valid pixels; lo = med(V_j) - k * sig(V_j), hi = med(V_j) + k * sig(V_j), V_{j+1} = the v of V_j with
+ *          lo <= (double)v <= hi; so V_j = V_0 inside [L_j, H_j], L_j = max(L_{j-1}, lo_{j-1}), H_j = min(H_{j-1}, hi_{j-1}).
+ *          An empty V_j is not clipped again (its median and sig count as 0)
+ * h_out row, CY_BKG_FIELDS float64, rows in cell order [ncy][ncx]:
+ *   [0] n0 = |V_0|, [1] n = |V_niter|, [2] bkg = med(V_niter), [3] rms = sig(V_niter)
+ *   [4] L, [5] H   the final interval; -inf, +inf when niter == 0 or n0 == 0
+ *   [6] rounds     clips that removed at least one pixel, [7] reserved (0)
+ *   n == 0: bkg = rms = 0.
+ * Every field is a count, a selection or one rounded operation on selections: none depends on the order in which pixels are
+ * visited (two calls give the same bytes).  One launch (one workgroup per cell; a cell of up to 128 x 128 pixels is held in LDS,
+ * a larger one is re-read from the image) and one copy to h_out; synchronous on `stream`.  cell outside [4, 4096], k not > 0 (or
+ * NaN), niter outside [0, 32], MH / MW <= 0, a null pointer, or an image of 2^31 pixels or more: CY_ERR_ARG.  Needs no loaded
+ * weights. */
+#define CY_BKG_FIELDS 8   /* n0 n bkg rms L H rounds reserved */
+int cy_measure_background(cy_ctx* ctx, const float* d_img, int MH, int MW, int cell, double k, int niter,
+                          double* h_out /* [ncy][ncx][CY_BKG_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_measure_background call took (hipEvents around the launch); -1 before the first call */
+int cy_background_kernel_ms(const cy_ctx* ctx, double* out_ms);
+/* A filled mesh h_mesh [ncy][ncx] x {bkg, rms} float64 (host) expanded to per-pixel fp32 maps [MH][MW] in the caller's device
+ * buffers d_bkg / d_rms (either may be NULL, not both).  The centre of cell cx is cx * cell + (cell - 1) / 2.0, also for a
+ * partial edge cell.  At pixel ix: t = (ix - (cell - 1) / 2.0) / cell clamped to [0, ncx - 1], i0 = min(floor(t), ncx - 2),
+ * fx = t - i0 (i0 = 0, fx = 0 when ncx == 1); iy likewise; value = (m00 * (1 - fx) + m01 * fx) * (1 - fy) + (m10 * (1 - fx) +
+ * m11 * fx) * fy in float64, every operation rounded on its own, then rounded to fp32: constant outside the outermost centres.
+ * One upload, one launch; synchronous on `stream`.  cell outside [4, 4096], MH / MW <= 0, a null mesh or two null outputs, an
+ * image of 2^31 pixels or more, or ncy / ncx that are not ceil(MH / cell) / ceil(MW / cell): CY_ERR_ARG.  Needs no loaded weights. */
+int cy_expand_background(cy_ctx* ctx, const double* h_mesh /* [ncy][ncx][2], filled */, int ncy, int ncx, int cell, int MH, int MW,
+                         float* d_bkg, float* d_rms, void* stream);
+
 /* ---- catalog records and cross-tile merge (host code, no GPU) --------------------------------- */
 /* Analyzer.make_json_results (caesar_yolo/evaluation.py:418-469: int() truncation, tile-local edge rule, tile origin)
  * followed by SFinder.find_sources_at_edge (caesar_yolo/inference.py:663-726).

@@ -21,6 +21,12 @@ Differences that come with the MI355X engine:
              bkg + --island_seed_sigma * rms (default 5): island_count, island_npix, island_npix_main, island_border,
              island_x1 / x2 / y1 / y2, island_flux_sum, island_flux, island_flux_main, x_isl, y_isl, ra_isl, dec_isl, major, minor, pa
              (cy_measure_islands; DESIGN.md "Source islands").
+  --bkg_map  (new; implies --measure_sources) a global background and noise mesh: clipped median and MAD (--bkg_clip_sigma, default
+             3; --bkg_clip_iters, default 3) of every --bkg_cell x --bkg_cell cell (default 128), cells with fewer than --bkg_min_pix
+             (default 64) surviving pixels filled from the nearest one, bilinear between the cell centres; every source also
+             carries bkg_map, rms_map, snr_map, and with --measure_islands the island thresholds come from them.  --save_bkg_maps
+             (implies --bkg_map) writes the per-pixel maps as bkg_<catalog name>.fits / rms_<catalog name>.fits beside the catalog
+             (cy_measure_background, cy_expand_background; DESIGN.md "Background mesh").
 """
 import argparse
 import logging
@@ -106,6 +112,18 @@ def parse_args(argv=None):
                    help='an island grows over connected pixels at or above bkg + this many rms (with --measure_islands)')
     p.add_argument('--island_conn', dest='island_conn', type=int, choices=[4, 8], default=8,
                    help='neighbours that connect the pixels of an island (with --measure_islands)')
+    p.add_argument('--bkg_map', dest='bkg_map', action='store_true',
+                   help='estimate a global background / noise mesh on the GPU and add bkg_map, rms_map, snr_map to every source; the island '
+                        'thresholds of --measure_islands then come from it (implies --measure_sources)')
+    p.add_argument('--bkg_cell', dest='bkg_cell', type=int, default=128, help='side of a mesh cell in pixels, 4 .. 4096 (with --bkg_map)')
+    p.add_argument('--bkg_clip_sigma', dest='bkg_clip_sigma', type=float, default=3.0,
+                   help='a clip keeps the pixels within this many rms of the cell median (with --bkg_map)')
+    p.add_argument('--bkg_clip_iters', dest='bkg_clip_iters', type=int, default=3, help='number of clips, 0 .. 32 (with --bkg_map)')
+    p.add_argument('--bkg_min_pix', dest='bkg_min_pix', type=int, default=64,
+                   help='a cell with fewer surviving pixels takes the values of the nearest cell that has them (with --bkg_map)')
+    p.add_argument('--save_bkg_maps', dest='save_bkg_maps', action='store_true',
+                   help='write the per-pixel background and noise maps as bkg_<catalog>.fits / rms_<catalog>.fits beside the catalog '
+                        '(implies --bkg_map)')
     return p.parse_args(argv)
 
 
@@ -127,6 +145,18 @@ def validate_args(args):
         return -1
     if args.measure_islands and not args.island_seed_sigma >= args.island_merge_sigma:
         logger.error("--island_seed_sigma must not be below --island_merge_sigma!")
+        return -1
+    if not 4 <= args.bkg_cell <= 4096:
+        logger.error("--bkg_cell must be in [4, 4096]!")
+        return -1
+    if not args.bkg_clip_sigma > 0:
+        logger.error("--bkg_clip_sigma must be > 0!")
+        return -1
+    if not 0 <= args.bkg_clip_iters <= 32:
+        logger.error("--bkg_clip_iters must be in [0, 32]!")
+        return -1
+    if args.bkg_min_pix < 1:
+        logger.error("--bkg_min_pix must be >= 1!")
         return -1
     if args.split_img_in_tiles and (args.xmin >= 0 or args.xmax >= 0 or args.ymin >= 0 or args.ymax >= 0):
         # serial runs crop like the reference (inference.py:499-505); the tiled run of the reference derives its grid from
@@ -191,9 +221,12 @@ def main(argv=None):
               'save_tile_catalog': args.save_tile_catalog, 'save_tile_region': args.save_tile_region,
               'save_tile_img': args.save_tile_img,
               'precision': args.precision, 'augment': args.augment,
-              'measure_sources': args.measure_sources or args.measure_islands, 'measure_ring': args.measure_ring,
+              'measure_sources': args.measure_sources or args.measure_islands or args.bkg_map or args.save_bkg_maps,
+              'measure_ring': args.measure_ring,
               'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
-              'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn})
+              'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
+              'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
+              'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,
                  max_imgsz=max(args.imgsize, 32))
     sfinder = SFinder(model, C)

@@ -1,15 +1,18 @@
-"""Cost of --measure_sources and --measure_islands (developer tool): the S16k tiled run of scripts/run.py (README recipe:
+"""Cost of --measure_sources, --measure_islands and --bkg_map (developer tool): the S16k tiled run of scripts/run.py (README recipe:
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
 (hipEvents around the launch, cy_measure_kernel_ms) and the number of sources.  --host-ref times tests/measure_ref.py (numpy
 float64) on the same boxes.  With --measure_islands the same three numbers for the island step (islands_ms, islands_kernel_ms), the
 histogram of the box-window areas of the catalog and the share of sources whose window is labelled in LDS (up to 4096 pixels); --host-ref
-then also times tests/island_ref.py.  --off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
+then also times tests/island_ref.py.  Unless --no-bkg is given there is a fourth variant, --bkg_map (background_ms, background_kernel_ms), and after the runs
+the kernels alone on the same image: cy_measure_background at cell 64 / 128 / 256 (k 3, 3 clips) and cy_expand_background of the
+cell-128 mesh to both maps, `--runs` calls each after a warm-up; --host-ref then also times tests/bkg_ref.py at cell 128.
+--off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
 JSON line."""
 import argparse
 import json
@@ -25,6 +28,42 @@ import numpy as np
 import __graft_entry__ as ge
 
 
+def background_kernels(img, runs, host_ref):
+    """The two background kernels alone on `img`: medians of `runs` calls after a warm-up."""
+    import torch
+    from caesar_yolo_amd import measure
+    from caesar_yolo_amd.model import YOLO
+    det = YOLO("seeded:l:5", precision="fp16x3", max_batch=1, max_imgsz=64).engine(0)
+    dev = det.mosaic_to_device(img)
+    out = {}
+    for cell in (64, 128, 256):
+        ms = []
+        for i in range(runs + 1):
+            raw = det.measure_background(dev, cell=cell, k=3.0, niter=3)
+            ms.append(det.background_kernel_ms())
+        out["background_kernel_ms_cell%d" % cell] = [round(v, 3) for v in ms[1:]]
+        out["background_kernel_ms_cell%d_median" % cell] = statistics.median(ms[1:])
+        if cell == 128:
+            mesh, out["defined_cells"] = measure.fill_mesh(raw, 64)
+    ms = []
+    for i in range(runs + 1):                              # wall time of the call: upload of the mesh, kernel, synchronisation
+        torch.cuda.synchronize()
+        t0 = time.time()
+        maps = det.expand_background(mesh, 128, img.shape)
+        ms.append(1e3 * (time.time() - t0))
+        del maps
+    out["expand_call_ms"] = [round(v, 3) for v in ms[1:]]
+    out["expand_call_ms_median"] = statistics.median(ms[1:])
+    if host_ref:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import bkg_ref
+        host = np.where(np.isfinite(img), img, np.float32(0)).astype(np.float32)
+        t0 = time.time()
+        bkg_ref.background(host, 128, 3.0, 3)
+        out["host_bkg_ref_ms"] = 1e3 * (time.time() - t0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=16384)
@@ -32,6 +71,7 @@ def main():
     ap.add_argument("--ring", type=int, default=8)
     ap.add_argument("--off-only", action="store_true")
     ap.add_argument("--no-islands", action="store_true")
+    ap.add_argument("--no-bkg", action="store_true")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -44,7 +84,8 @@ def main():
         rc = orig(self)
         seen.append({"run_ms": 1e3 * self.runtime, "sources": len(self.sources["sources"]),
                      "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms"),
-                     "islands_ms": self.stats.get("islands_ms"), "islands_kernel_ms": self.stats.get("islands_kernel_ms")})
+                     "islands_ms": self.stats.get("islands_ms"), "islands_kernel_ms": self.stats.get("islands_kernel_ms"),
+                     "background_ms": self.stats.get("background_ms"), "background_kernel_ms": self.stats.get("background_kernel_ms")})
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -61,7 +102,9 @@ def main():
         os.chdir(d)
         try:
             variants = [("off", base)] + ([] if args.off_only else [("on", base + on)])
-            if not (args.off_only or args.no_islands):
+            if not (args.off_only or args.no_bkg):
+                variants.append(("bkg", base + on + ["--bkg_map"]))
+            if not (args.off_only or args.no_islands):         # the last one: its catalog is read below
                 variants.append(("islands", base + on + ["--measure_islands"]))
             for name, argv in variants:                    # warm-up of each variant
                 assert run.main(argv) == 0
@@ -78,13 +121,20 @@ def main():
                     for k in ("islands_ms", "islands_kernel_ms"):
                         res[name][k] = [round(r[k], 3) for r in rows]
                         res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                if name in ("on", "islands"):
+                if name == "bkg":
+                    for k in ("background_ms", "background_kernel_ms"):
+                        res[name][k] = [round(r[k], 3) for r in rows]
+                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
+                if name in ("on", "islands", "bkg"):
                     res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
                     res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
                     res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
                     res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
             if "on" in got:
                 res["added_ms"] = res["on"]["run_ms_median"] - res["off"]["run_ms_median"]
+            if "bkg" in got:
+                res["bkg_added_ms"] = res["bkg"]["run_ms_median"] - res["off"]["run_ms_median"]
+                res.update(background_kernels(img, args.runs, args.host_ref))
             if "islands" in got:                            # read before the next variant overwrites the catalog: it was the last to run
                 from caesar_yolo_amd import measure
                 res["islands_added_ms"] = res["islands"]["run_ms_median"] - res["off"]["run_ms_median"]

@@ -800,7 +800,13 @@ __device__ __forceinline__ ClipStats sigma_clip_run(Smem& s, const TileView& tv,
         set_moments<RAW>(s, tv, upto, cs, K, radix_trip && c != -1, br, &n, &mean, &sd, &below, &ncand);
         pre_acc(0, ts);
         if (c >= 1 && n == nprev) break;      // the clip removed nothing: converged, (mean, sd, med) describe this very set
-        if (n == 0) { mean = sd = med = NAN; break; }
+        if (n == 0) {
+            // a clip that removes every member: the reference then makes one more iteration over the empty set, whose bounds are NaN
+            // (a CLIP stage clamps nothing) -- unless that clip was the fifth, whose bounds stand
+            mean = sd = med = NAN;
+            if (c >= 1 && c < 5) r.lo = r.hi = NAN;
+            break;
+        }
         if (br.on && ncand > 0) density = (double)ncand / (br.vh - br.vl);          // measured (also when the bracket overflowed or missed)
         if (c != -1) {
             const unsigned long long kA = (n - 1) / 2, kB = n / 2;
@@ -1182,7 +1188,7 @@ __global__ __launch_bounds__(NT) void pre_stats_kernel(const PreArgs a) {
             hits += r.hits; misses += r.misses;
             if (op == OP_BKG) { o0 = r.mean; if (r.n == 0) status = 1; }
             else if (op == OP_SHIFT) { o0 = r.mean + p0 * r.std; o1 = r.mean; o2 = r.std; if (r.n == 0) status = 1; }
-            else { o0 = r.lo; o1 = r.hi; if (r.n == 0 && isnan(r.lo)) status = 1; }
+            else { o0 = r.lo; o1 = r.hi; }      // (an empty set gives NaN bounds and clamps nothing: SigmaClipper never returns None)
         } else if (op == OP_ZSCALE) {
             zscale_run(s, tv, k, p0, &o0, &o1);
         } else if (op == OP_HISTEQ) {

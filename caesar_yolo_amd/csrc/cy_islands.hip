@@ -19,54 +19,20 @@
 // Workspace labels are read and written with agent-scope atomics (they go to L2, never to a stale line of the vector cache).
 // Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
 // fixed association, so two runs give the same bits.  The atomics are integer minima / ors on labels only.
-#include "cy_kernels.h"
-#include <cfloat>
-#include <climits>
+#include "cy_label.h"                   // Lab, Win, label_window: sweeps 1-4, shared with cy_deblend.hip
 
 #pragma clang fp contract(off)          // w * (dx * dx) is rounded before it is added, as the float64 definition does
 
 namespace cy {
 namespace {
 
-constexpr int INT = 256, INW = INT / 64;
-constexpr unsigned NOLAB = 0xFFFFFFFFu, SEEDED = 0x80000000u, ROOT = 0x7FFFFFFFu;
-static_assert(ISL_MAX_AREA < (long long)SEEDED, "bit 31 of a label is the seed flag");
-
 struct ISmem {
     unsigned lab[ISL_LDS_MAX];
+    LabRed lr;
     double red[7][INW];
     unsigned cnt[5][INW];
     int box[4][INW];
-    float pv[INW]; unsigned pi[INW];
 };
-
-__device__ __forceinline__ bool valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
-
-// label accesses: LDS (workgroup scope) or this workgroup's slice of the global workspace (agent scope: served by L2)
-template <bool LDS> struct Lab {
-    static constexpr int SC = LDS ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_AGENT;
-    unsigned* p;
-    __device__ __forceinline__ unsigned ld(unsigned i) const { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, SC); }
-    __device__ __forceinline__ void st(unsigned i, unsigned v) const { __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, SC); }
-    __device__ __forceinline__ unsigned amin(unsigned i, unsigned v) const { return __hip_atomic_fetch_min(p + i, v, __ATOMIC_RELAXED, SC); }
-    __device__ __forceinline__ void aor(unsigned i, unsigned v) const { __hip_atomic_fetch_or(p + i, v, __ATOMIC_RELAXED, SC); }
-    __device__ __forceinline__ unsigned root(unsigned a, unsigned A) const {        // labels only decrease along the walk
-        for (unsigned k = 0; k < A; ++k) { const unsigned q = ld(a); if (q == a) break; a = q; }
-        return a;
-    }
-    __device__ __forceinline__ void unite(unsigned a, unsigned b, unsigned A) const {
-        for (unsigned k = 0; k < A; ++k) {
-            a = root(a, A); b = root(b, A);
-            if (a == b) return;
-            if (a < b) { const unsigned t = a; a = b; b = t; }
-            const unsigned old = amin(a, b);            // a was a root when read: hang it under b
-            if (old == a) return;
-            a = old;                                    // somebody re-hung a under `old` first: old and b still have to meet
-        }
-    }
-};
-
-struct Win { int x0, y0; unsigned W, H, A; };
 
 template <bool LDS>
 __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const Win wn, const double seed, const double merge,
@@ -76,71 +42,13 @@ __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const W
     const float* __restrict__ img = a.img + (size_t)wn.y0 * MW + (size_t)wn.x0;
     const unsigned W = wn.W, A = wn.A;
 
-    // ---- 1 init
-    unsigned nseed = 0;
-    float pv = -INFINITY; unsigned pi = NOLAB;
-    for (unsigned base = 0; base < A; base += INT) {          // uniform trip count: every lane takes part in the ballots
-        const unsigned i = base + tid, dy = i / W, dx = i - dy * W;
-        const float v = i < A ? img[(size_t)dy * MW + dx] : 0.0f;
-        const bool ok = valid_px(v), cand = ok && (double)v >= merge;
-        if (ok && v > pv) { pv = v; pi = i; }                  // increasing index per lane: the first stays
-        nseed += cand && (double)v >= seed;
-        const unsigned long long m = __ballot(cand);
-        const bool joins = cand && lane > 0 && dx > 0 && ((m >> (lane - 1)) & 1ull);
-        const unsigned long long starts = __ballot(cand && !joins);
-        if (i < A) L.st(i, cand ? i - lane + (63u - (unsigned)__clzll((long long)(starts & (~0ull >> (63 - lane))))) : NOLAB);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nseed += __shfl_down(nseed, o);
-        const float v2 = __shfl_down(pv, o); const unsigned p2 = __shfl_down(pi, o);
-        if (v2 > pv || (v2 == pv && p2 < pi)) { pv = v2; pi = p2; }
-    }
-    if (lane == 0) { s.cnt[0][w] = nseed; s.pv[w] = pv; s.pi[w] = pi; }
-    __syncthreads();                                          // also: the labels of sweep 1 are in place
-    nseed = s.cnt[0][0]; pv = s.pv[0]; pi = s.pi[0];
-#pragma unroll
-    for (int j = 1; j < INW; ++j) {
-        nseed += s.cnt[0][j];
-        if (s.pv[j] > pv || (s.pv[j] == pv && s.pi[j] < pi)) { pv = s.pv[j]; pi = s.pi[j]; }
-    }
+    // ---- 1-4 init, link, flatten, seeds (cy_label.h)
+    float pv; unsigned pi;
+    const unsigned nseed = label_window<LDS>(s.lr, L, img, MW, a.conn == 8, wn, seed, merge, pv, pi);
     if (nseed == 0) {                                         // uniform (from LDS): no island; the mask bytes are 0 already
         if (tid < ISL_FIELDS) out[tid] = (tid >= 6 && tid <= 9) ? -1.0 : 0.0;
         return;
     }
-
-    // ---- 2 link
-    const bool c8 = a.conn == 8;
-    for (unsigned i = tid; i < A; i += INT) {
-        if (L.ld(i) == NOLAB) continue;
-        const unsigned dy = i / W, dx = i - dy * W;
-        const bool left = dx > 0 && L.ld(i - 1) != NOLAB;
-        if (left && (i & 63u) == 0) L.unite(i, i - 1, A);      // the run continues across the 64-pixel boundary of sweep 1
-        if (dy == 0) continue;
-        const unsigned u = i - W;
-        const bool up = L.ld(u) != NOLAB, ul = dx > 0 && L.ld(u - 1) != NOLAB;
-        if (up) {
-            if (!(left && ul)) L.unite(i, u, A);               // left && ul: the left neighbour is linked to ul, which is in up's run
-        } else if (c8) {
-            if (ul && !left) L.unite(i, u - 1, A);             // left: ul is the left neighbour's `up`
-            if (dx + 1 < W && L.ld(u + 1) != NOLAB) L.unite(i, u + 1, A);
-        }
-    }
-    __syncthreads();
-
-    // ---- 3 flatten
-    for (unsigned i = tid; i < A; i += INT)
-        if (L.ld(i) != NOLAB) L.st(i, L.root(i, A));
-    __syncthreads();
-
-    // ---- 4 seeds
-    for (unsigned i = tid; i < A; i += INT) {
-        const unsigned l = L.ld(i);
-        if (l == NOLAB) continue;
-        const unsigned dy = i / W, dx = i - dy * W;
-        if ((double)img[(size_t)dy * MW + dx] >= seed && !(L.ld(l & ROOT) & SEEDED)) L.aor(l & ROOT, SEEDED);
-    }
-    __syncthreads();
 
     // ---- 5 sums (the peak pixel is a seed, so its component is in the island set)
     const unsigned mainroot = L.ld(pi) & ROOT;

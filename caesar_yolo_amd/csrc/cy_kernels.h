@@ -278,8 +278,25 @@ struct IslandArgs {
 };
 hipError_t launch_islands(const IslandArgs& a, hipStream_t s);
 
+// ---- source components (cy_deblend.hip) ------------------------------------------------------------
+constexpr int DBL_FIELDS = 8, DBL_COMP_FIELDS = 12, DBL_MAX_COMP = 16;    // CY_DBL_FIELDS, CY_DBL_COMP_FIELDS, CY_DBL_MAX_COMP
+constexpr int DBL_RADIUS_MAX = 8;
+struct DeblendArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    const int* win;                 // [n][4] as IslandArgs
+    const double* thr;              // [n][4] {seed_thr, merge_thr, bkg, peak_thr}
+    const long long* off;           // [n][2] as IslandArgs
+    int n, conn, radius;            // conn: 4 or 8; radius: 1 .. DBL_RADIUS_MAX
+    unsigned* ws;                   // labels of the windows above ISL_LDS_MAX pixels, one u32 per pixel (null when there is none) ...
+    unsigned* ws_up;                // ... and their `up` words, a second slice of the same size with the same offsets
+    unsigned char* mask;            // zeroed by the caller; null: no mask wanted
+    double* out;                    // [n][DBL_FIELDS]
+    double* comp;                   // [n][DBL_MAX_COMP][DBL_COMP_FIELDS], zeroed by the caller
+};
+hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
-constexpr int BKG_FIELDS = 8;                  // CY_BKG_FIELDS
+constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;
 constexpr int BKG_LDS_MAX = 128 * 128;         // largest cell (pixels) that is copied into LDS: 64 KiB per workgroup
 struct BackgroundArgs {

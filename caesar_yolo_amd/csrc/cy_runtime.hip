@@ -65,6 +65,7 @@ struct cy_ctx {
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
     double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
+    double deblend_ms = -1.0;                           // ... of the last cy_deblend_islands call (cy_deblend_kernel_ms)
     double islands_ms = -1.0;                           // ... of the last cy_measure_islands call (cy_islands_kernel_ms)
     double background_ms = -1.0;                        // ... of the last cy_measure_background call (cy_background_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
@@ -1601,6 +1602,86 @@ int cy_measure_islands(cy_ctx* c, const float* d_img, int MH, int MW, const doub
 int cy_islands_kernel_ms(const cy_ctx* c, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
     *out_ms = c->islands_ms;
+    return CY_OK;
+}
+
+// ---- source components ------------------------------------------------------------------------
+static_assert(CY_DBL_FIELDS == DBL_FIELDS && CY_DBL_COMP_FIELDS == DBL_COMP_FIELDS && CY_DBL_MAX_COMP == DBL_MAX_COMP,
+              "header and kernel disagree on the component rows");
+
+int cy_deblend_islands(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_thr, int n, int conn, int radius,
+                       double* h_out, double* h_comp, unsigned char* h_mask, const long long* h_mask_off, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (n < 0 || (conn != 4 && conn != 8) || radius < 1 || radius > DBL_RADIUS_MAX || MH <= 0 || MW <= 0)
+        return fail(c, CY_ERR_ARG, "n >= 0, conn 4 or 8, 1 <= radius <= 8 and MH, MW > 0 required");
+    if (n == 0) return CY_OK;
+    if (!d_img || !h_boxes || !h_thr || !h_out || !h_comp || (h_mask && !h_mask_off)) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
+    std::vector<int> win((size_t)n * 4);
+    std::vector<long long> off((size_t)n * 2);
+    long long nws = 0, nmask = 0;
+    for (int i = 0; i < n; ++i) {
+        if (h_thr[(size_t)i * 4] < h_thr[(size_t)i * 4 + 1]) return fail(c, CY_ERR_ARG, "seed_thr below merge_thr");
+        int* w = &win[(size_t)i * 4];
+        const double* b = h_boxes + (size_t)i * 4;
+        window_1d(b[0], b[2], MW, &w[0], &w[1]);
+        window_1d(b[1], b[3], MH, &w[2], &w[3]);
+        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
+        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
+        if (h_mask && (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area))
+            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
+        off[(size_t)i * 2] = area > ISL_MAX_AREA ? ISL_OFF_TOO_LARGE : area > ISL_LDS_MAX ? nws : ISL_OFF_LDS;
+        off[(size_t)i * 2 + 1] = nmask;
+        if (area > ISL_LDS_MAX && area <= ISL_MAX_AREA) nws += area;
+        nmask += area;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    const size_t out_bytes = (size_t)n * CY_DBL_FIELDS * sizeof(double), comp_bytes = (size_t)n * CY_DBL_MAX_COMP * CY_DBL_COMP_FIELDS * sizeof(double);
+    void *d_win = nullptr, *d_off = nullptr, *d_thr = nullptr, *d_out = nullptr, *d_comp = nullptr, *d_ws = nullptr, *d_mask = nullptr;
+    HIPCHK(c, sc.alloc(win.size() * sizeof(int), &d_win));
+    HIPCHK(c, sc.alloc(off.size() * sizeof(long long), &d_off));
+    HIPCHK(c, sc.alloc((size_t)n * 4 * sizeof(double), &d_thr));
+    HIPCHK(c, sc.alloc(out_bytes, &d_out));
+    HIPCHK(c, sc.alloc(comp_bytes, &d_comp));
+    if (nws) HIPCHK(c, sc.alloc((size_t)nws * 2 * sizeof(unsigned), &d_ws));       // labels, then `up` words; every word is written before it is read
+    const bool masks = h_mask && nmask > 0;
+    if (masks) HIPCHK(c, sc.alloc((size_t)nmask, &d_mask));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_thr, h_thr, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_comp, 0, comp_bytes, st);                  // the kernel writes the rows below ncomp only
+    if (e == hipSuccess && masks) e = hipMemsetAsync(d_mask, 0, (size_t)nmask, st);      // the kernel writes the non-zero bytes only
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) {
+        DeblendArgs a{};
+        a.img = d_img; a.MH = MH; a.MW = MW; a.win = reinterpret_cast<const int*>(d_win); a.thr = reinterpret_cast<const double*>(d_thr);
+        a.off = reinterpret_cast<const long long*>(d_off); a.n = n; a.conn = conn; a.radius = radius;
+        a.ws = reinterpret_cast<unsigned*>(d_ws); a.ws_up = d_ws ? a.ws + nws : nullptr;
+        a.mask = masks ? reinterpret_cast<unsigned char*>(d_mask) : nullptr;
+        a.out = reinterpret_cast<double*>(d_out); a.comp = reinterpret_cast<double*>(d_comp);
+        e = launch_deblend(a, st);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_comp, d_comp, comp_bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && masks) e = hipMemcpyAsync(h_mask, d_mask, (size_t)nmask, hipMemcpyDeviceToHost, st);
+    const int rc = entry_done(c, e, st);
+    float ms = -1.0f;
+    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    c->deblend_ms = ms;
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    return rc;
+}
+
+int cy_deblend_kernel_ms(const cy_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return CY_ERR_ARG;
+    *out_ms = c->deblend_ms;
     return CY_OK;
 }
 

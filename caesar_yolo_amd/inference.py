@@ -597,6 +597,13 @@ class SFinder(object):
                                          int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy), use_map=use_map)
             self.stats["islands_ms"] = 1e3 * (time.time() - t1)
             self.stats["islands_kernel_ms"] = det.islands_kernel_ms() if src else 0.0
+        if c.get('deblend_islands', False):                   # --deblend_islands: the components, right after the island step
+            t1 = time.time()
+            k_peak, radius = measure.deblend_config(c)
+            measure.deblend_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5), k_peak,
+                                         int(c.get('island_conn', 8)), radius, self.beamArea, self.wcs, box_origin=(ox, oy), use_map=use_map)
+            self.stats["deblend_ms"] = 1e3 * (time.time() - t1)
+            self.stats["deblend_kernel_ms"] = det.deblend_kernel_ms() if src else 0.0
 
     # ---- tiled (reference :578-658)
     def run_parallel(self):
@@ -632,7 +639,8 @@ class SFinder(object):
         if rank == 0:
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
-            if c.get('measure_sources', False) or c.get('measure_islands', False) or c.get('bkg_map', False) or c.get('save_bkg_maps', False):
+            if (c.get('measure_sources', False) or c.get('measure_islands', False) or c.get('bkg_map', False) or c.get('save_bkg_maps', False)
+                    or c.get('deblend_islands', False)):
                 self._measure(det, mosaic, src)
             self.sources = {"sources": src}
             if self.write_to_json:

@@ -14,6 +14,10 @@ the clipped median and MAD of every cell (raw rows lib.BKG_NAMES), fill_mesh() f
 interpolates bilinearly between the cell centres, keys BKG_KEYS (annotate_background); the island step then takes its thresholds
 from bkg_map / rms_map.
 
+--deblend_islands adds a fourth step: `cy_deblend_islands` (HipDetector.deblend_islands) splits the island set of every box into
+components by local peaks and steepest-ascent basins, raw rows lib.DBL_NAMES / lib.DBL_COMP_NAMES, keys COMPONENT_KEYS
+(annotate_components).
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
 import math
 
@@ -23,6 +27,8 @@ KEYS = ("npix", "bkg", "rms", "peak", "snr", "x_peak", "y_peak", "x0", "y0", "fl
 ISLAND_KEYS = ("island_count", "island_npix", "island_npix_main", "island_border", "island_x1", "island_x2", "island_y1", "island_y2",
                "island_flux_sum", "island_flux", "island_flux_main", "x_isl", "y_isl", "ra_isl", "dec_isl", "major", "minor", "pa")
 BKG_KEYS = ("bkg_map", "rms_map", "snr_map")
+COMPONENT_KEYS = ("npeaks", "ncomponents", "components_truncated", "components_unassigned_npix", "components")
+COMPONENT_ITEM_KEYS = ("x", "y", "ra", "dec", "peak", "x_peak", "y_peak", "npix", "flux_sum", "flux", "major", "minor", "pa", "main", "nsummits")
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
 
@@ -180,6 +186,88 @@ def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area
         raw[has, 6:8] += bx
         raw[has, 8:10] += by
     return annotate_islands(sources, raw, win0, beam_area, wcs, wcs_origin)
+
+
+# ---- source components (--deblend_islands)
+def deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map=False):
+    """[n, 4] float64 {seed_thr, merge_thr, bkg, peak_thr}: island_thresholds() plus bkg + k_peak * rms."""
+    t = island_thresholds(sources, k_seed, k_merge, use_map)
+    kb, kr = ("bkg_map", "rms_map") if use_map else ("bkg", "rms")
+    bkg = np.array([s[kb] for s in sources], np.float64)
+    rms = np.array([s[kr] for s in sources], np.float64)
+    return np.concatenate([t.reshape(-1, 3), (bkg + float(k_peak) * rms).reshape(-1, 1)], 1)
+
+
+def annotate_components(sources, raw, comp, win0, beam_area, wcs, origin=(0, 0)):
+    """Adds COMPONENT_KEYS to every source dict (in place; returns the list).  raw: [n, CY_DBL_FIELDS] rows and comp:
+    [n, CY_DBL_MAX_COMP, CY_DBL_COMP_FIELDS] component rows of cy_deblend_islands on the boxes of `sources`; win0: [n, 2] first
+    column / row (wx0, wy0) of every box window (box_window), in the frame the catalog's positions are wanted in, as are the peak
+    positions in comp.
+      npeaks, ncomponents   npeaks, ncomp;  components_truncated  status == 2 (more than CY_DBL_MAX_COMP peaks)
+      components_unassigned_npix   npix_unassigned
+      components   a list of ncomp dicts in component order (COMPONENT_ITEM_KEYS): x, y = wx0 + Sx / S, wy0 + Sy / S;  ra, dec =
+                   wcs.wcs_pix2world(x + ox, y + oy, 0), None without a WCS;  peak, x_peak, y_peak;  npix;  flux_sum = S;  flux =
+                   S / beam_area when beam_area > 0, else None;  major, minor, pa  island_shape();  main (bool);  nsummits
+    No seed: the counts are 0 and components is an empty list.  status == 1 (window above the supported maximum): every key
+    None.  S == 0: position and shape keys of that component None."""
+    if not sources:
+        return sources
+    n = len(sources)
+    raw = np.asarray(raw, np.float64).reshape(n, -1)
+    comp = np.asarray(comp, np.float64).reshape(n, -1, 12)                # CY_DBL_COMP_FIELDS
+    win0 = np.asarray(win0, np.float64).reshape(n, 2)
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for s, r, cr, (wx0, wy0) in zip(sources, raw, comp, win0):
+        for k in COMPONENT_KEYS:
+            s[k] = None
+        if r[0] == 1.0:
+            continue
+        s["npeaks"], s["ncomponents"], s["components_truncated"], s["components_unassigned_npix"] = int(r[2]), int(r[3]), bool(r[0] == 2.0), int(r[5])
+        items = []
+        for c in cr[:int(r[3])]:
+            S, Sx, Sy, Sxx, Syy, Sxy = (float(v) for v in c[4:10])
+            d = dict.fromkeys(COMPONENT_ITEM_KEYS)
+            d["peak"], d["x_peak"], d["y_peak"], d["npix"] = float(c[1]), int(c[2]), int(c[3]), int(c[0])
+            d["flux_sum"], d["main"], d["nsummits"] = S, bool(c[10] != 0.0), int(c[11])
+            if ba > 0.0:
+                d["flux"] = S / ba
+            if S != 0.0:
+                d["x"], d["y"] = float(wx0) + Sx / S, float(wy0) + Sy / S
+                d["major"], d["minor"], d["pa"] = island_shape(S, Sx, Sy, Sxx, Syy, Sxy)
+                if wcs is not None:
+                    a, dd = wcs.wcs_pix2world(d["x"] + ox, d["y"] + oy, 0)
+                    d["ra"], d["dec"] = float(a), float(dd)
+            items.append(d)
+        s["components"] = items
+    return sources
+
+
+def deblend_and_annotate(det, img_dev, sources, k_seed, k_merge, k_peak, conn, radius, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
+                         use_map=False):
+    """The component step, after islands_and_annotate on the same sources and image: thresholds in numpy float64, one
+    cy_deblend_islands call, then annotate_components().  box_origin / wcs_origin / use_map as in islands_and_annotate: positions
+    come back in catalog coordinates."""
+    if not sources:
+        return sources
+    bx, by = float(box_origin[0]), float(box_origin[1])
+    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
+    raw, comp = det.deblend_islands(img_dev, boxes, deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map), conn=conn, radius=radius)
+    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
+    if bx or by:
+        comp = comp.copy()
+        ncomp = raw[:, 3].astype(np.int64)
+        has = np.arange(comp.shape[1])[None, :] < ncomp[:, None]
+        comp[:, :, 2][has] += bx
+        comp[:, :, 3][has] += by
+    return annotate_components(sources, raw, comp, win0, beam_area, wcs, wcs_origin)
+
+
+def deblend_config(config):
+    """(k_peak, radius) of --deblend_islands from a config dictionary; the peak threshold defaults to the island seed threshold."""
+    k = config.get('deblend_peak_sigma')
+    return (float(config.get('island_seed_sigma', 5.0)) if k is None else float(k)), int(config.get('deblend_radius', 2))
 
 
 # ---- background and noise mesh (--bkg_map)

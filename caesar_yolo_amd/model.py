@@ -348,6 +348,43 @@ class HipDetector(object):
         self._chk(self.lib.cy_islands_kernel_ms(self.ctx, C.byref(ms)))
         return float(ms.value)
 
+    # ---- source components (the fourth measurement step)
+    def deblend_islands(self, img_dev, boxes, thr4, conn=8, radius=2, return_masks=False):
+        """Components of the island set of every box window by local peaks and steepest-ascent basins (cy_deblend_islands).
+        img_dev, boxes: as measure_sources; thr4: [n, 4] float64 {seed_thr, merge_thr, bkg, peak_thr} per source.  -> (rows numpy
+        float64 [n, CY_DBL_FIELDS] (lib.DBL_NAMES), component rows [n, CY_DBL_MAX_COMP, CY_DBL_COMP_FIELDS] (lib.DBL_COMP_NAMES));
+        with return_masks also a list of n uint8 arrays shaped like the box windows (0 outside the island set, k + 1 component k,
+        255 unassigned; an empty window gives an array of shape (0, 0))."""
+        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        thr4 = np.ascontiguousarray(np.asarray(thr4, np.float64).reshape(-1, 4))
+        n = boxes.shape[0]
+        if thr4.shape[0] != n:
+            raise L.CyError("deblend_islands: %d boxes but %d threshold rows" % (n, thr4.shape[0]))
+        out = np.zeros((n, L.CY_DBL_FIELDS), np.float64)
+        comp = np.zeros((n, L.CY_DBL_MAX_COMP, L.CY_DBL_COMP_FIELDS), np.float64)
+        MH, MW = self._image_2d(img_dev, "deblend_islands")
+        dp = C.POINTER(C.c_double)
+        mask = off = shapes = None
+        if return_masks:
+            from .measure import box_window
+            shapes = [box_window(b, MH, MW)[2:] for b in boxes]
+            off = np.zeros(n + 1, np.int64)
+            np.cumsum([h * w for h, w in shapes], out=off[1:])
+            mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+        self._chk(self.lib.cy_deblend_islands(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), thr4.ctypes.data_as(dp), n, int(conn),
+                                              int(radius), out.ctypes.data_as(dp), comp.ctypes.data_as(dp),
+                                              C.c_void_p(mask.ctypes.data) if return_masks else None,
+                                              off.ctypes.data_as(C.POINTER(C.c_longlong)) if return_masks else None, self._stream()))
+        if not return_masks:
+            return out, comp
+        return out, comp, [mask[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(n)]
+
+    def deblend_kernel_ms(self):
+        """Kernel time of the last deblend_islands call in ms (hipEvents around the launch); -1 before the first."""
+        ms = C.c_double(-1.0)
+        self._chk(self.lib.cy_deblend_kernel_ms(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def _image_2d(self, img_dev, what):
         if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:

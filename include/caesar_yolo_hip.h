@@ -310,6 +310,51 @@ int cy_measure_islands(cy_ctx* ctx, const float* d_img, int MH, int MW, const do
 /* milliseconds the kernel of the last cy_measure_islands call took (hipEvents around the launch); -1 before the first call */
 int cy_islands_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- source components (an addition, the fourth measurement step) -----------------------------------------------------------
+ * The island set of every box split into components by local peaks and steepest-ascent basins.  Image, valid pixel, pixel-centre
+ * convention, box window, candidate, seed, component of candidates (`conn` = 8 or 4), island set and main island are exactly those
+ * of cy_measure_islands.  h_thr: n x {seed_thr, merge_thr, bkg, peak_thr} float64.  Inside one box window, pixel index
+ * i = dy * W + dx:
+ *   rank      pixel p outranks q when v(p) > v(q), or when v(p) == v(q) and i(p) < i(q): a total order on valid pixels
+ *   up(p)     for an island-set pixel: the highest-ranked of p and its `conn` neighbours that are candidates inside the window
+ *             (those neighbours are in p's component by construction)
+ *   summit    a pixel with up(p) == p.  Following up from any island-set pixel reaches a summit (rank rises strictly on the way)
+ *   basin     of a summit: the pixels that end at it
+ *   peak      a summit s that outranks every island-set pixel of its own component with |dx| <= radius and |dy| <= radius
+ *             (radius in [1, 8]) and either has (double)v(s) >= peak_thr or is the top-ranked pixel of its component: every island
+ *             has at least one peak whatever peak_thr is, and a NaN peak_thr leaves exactly those
+ *   order     peaks are ordered by rank over the whole window; npeaks is their number.  The first CY_DBL_MAX_COMP are KEPT and
+ *             become components 0 .. ncomp - 1; the rest are demoted to ordinary summits and status becomes 2
+ *   assign    the basin of a kept peak belongs to that peak's component.  The basin of any other summit s belongs to the kept peak
+ *             t of the same island that minimises the integer squared distance (dx_s - dx_t)^2 + (dy_s - dy_t)^2, ties to the
+ *             lower component index.  An island with no kept peak (only with status 2) leaves its pixels UNASSIGNED.  Basins are
+ *             never split
+ * h_out row, CY_DBL_FIELDS float64:
+ *   [0] status   0 measured; 1 the window has more than 2^24 pixels: nothing measured; 2 measured, more than CY_DBL_MAX_COMP peaks
+ *   [1] nsummits, [2] npeaks, [3] ncomp, [4] npix (island set: field [3] of cy_measure_islands for the same arguments),
+ *   [5] npix_unassigned, [6..7] reserved (0).  Empty window or no seed: all 0.
+ * h_comp row of component k (rows at and beyond ncomp are 0), CY_DBL_COMP_FIELDS float64, with dx, dy relative to the window's first
+ * pixel and w = (double)v - bkg, the expressions and roundings of cy_measure_islands:
+ *   [0] npix, [1] peak = v of the kept peak, [2] x_peak, [3] y_peak its position in image pixels
+ *   [4] S, [5] Sx, [6] Sy, [7] Sxx, [8] Syy, [9] Sxy
+ *   [10] main   1 when the component lies in the main island, [11] nsummits   basins merged into it
+ * h_mask (may be NULL), h_mask_off: laid out as for cy_measure_islands; byte 0 not in the island set, k + 1 component k,
+ * 255 unassigned.
+ * Counts, peaks, positions and mask do not depend on any order; the sums are float64 with a fixed association (two calls give
+ * the same bytes).  One launch (one workgroup per source; two u32 per pixel in LDS for windows of up to 4096 pixels, else in a
+ * workspace allocated for the call) and one copy per output; synchronous on `stream`.  n == 0: CY_OK, nothing read or launched.
+ * Argument errors as for cy_measure_islands, and radius outside [1, 8]: CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_DBL_MAX_COMP 16
+#define CY_DBL_FIELDS 8        /* status nsummits npeaks ncomp npix npix_unassigned reserved reserved */
+#define CY_DBL_COMP_FIELDS 12  /* npix peak x_peak y_peak S Sx Sy Sxx Syy Sxy main nsummits */
+int cy_deblend_islands(cy_ctx* ctx, const float* d_img, int MH, int MW, const double* h_boxes,
+                       const double* h_thr /* n x {seed, merge, bkg, peak} */, int n, int conn, int radius,
+                       double* h_out /* [n][CY_DBL_FIELDS] */, double* h_comp /* [n][CY_DBL_MAX_COMP][CY_DBL_COMP_FIELDS] */,
+                       unsigned char* h_mask /* may be NULL */, const long long* h_mask_off /* n + 1 offsets, required with h_mask */,
+                       void* stream);
+/* milliseconds the kernel of the last cy_deblend_islands call took (hipEvents around the launch); -1 before the first call */
+int cy_deblend_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

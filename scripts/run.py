@@ -27,6 +27,12 @@ Differences that come with the MI355X engine:
              carries bkg_map, rms_map, snr_map, and with --measure_islands the island thresholds come from them.  --save_bkg_maps
              (implies --bkg_map) writes the per-pixel maps as bkg_<catalog name>.fits / rms_<catalog name>.fits beside the catalog
              (cy_measure_background, cy_expand_background; DESIGN.md "Background mesh").
+  --deblend_islands  (new; implies --measure_islands) the island set of every box split into components: local peaks (no
+             higher island pixel within --deblend_radius pixels, default 2, 1..8; at or above bkg + --deblend_peak_sigma * rms,
+             default = --island_seed_sigma, or the highest pixel of their island) and their steepest-ascent basins, at most 16 per
+             box.  Every source also carries npeaks, ncomponents, components_truncated, components_unassigned_npix and components,
+             a list of {x, y, ra, dec, peak, x_peak, y_peak, npix, flux_sum, flux, major, minor, pa, main, nsummits}
+             (cy_deblend_islands; DESIGN.md "Source components").
 """
 import argparse
 import logging
@@ -124,7 +130,19 @@ def parse_args(argv=None):
     p.add_argument('--save_bkg_maps', dest='save_bkg_maps', action='store_true',
                    help='write the per-pixel background and noise maps as bkg_<catalog>.fits / rms_<catalog>.fits beside the catalog '
                         '(implies --bkg_map)')
-    return p.parse_args(argv)
+    p.add_argument('--deblend_islands', dest='deblend_islands', action='store_true',
+                   help='split the islands of every source box into components by local peaks and steepest-ascent basins on the GPU '
+                        '(implies --measure_islands)')
+    p.add_argument('--deblend_peak_sigma', dest='deblend_peak_sigma', type=float, default=None,
+                   help='a local peak becomes a component at or above bkg + this many rms (default: --island_seed_sigma; with --deblend_islands)')
+    p.add_argument('--deblend_radius', dest='deblend_radius', type=int, choices=list(range(1, 9)), default=2,
+                   help='a peak is the highest island pixel within this many pixels in x and y (with --deblend_islands)')
+    args = p.parse_args(argv)
+    if args.deblend_islands:
+        args.measure_islands = True
+    if args.deblend_peak_sigma is None:
+        args.deblend_peak_sigma = args.island_seed_sigma
+    return args
 
 
 def validate_args(args):
@@ -225,6 +243,7 @@ def main(argv=None):
               'measure_ring': args.measure_ring,
               'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
               'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
+              'deblend_islands': args.deblend_islands, 'deblend_peak_sigma': args.deblend_peak_sigma, 'deblend_radius': args.deblend_radius,
               'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
               'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,

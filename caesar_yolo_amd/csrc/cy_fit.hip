@@ -1,0 +1,273 @@
+// Component fits (cy_fit_components): one elliptical Gaussian per deblended component, unweighted Levenberg-Marquardt in float64
+// (definitions: include/caesar_yolo_hip.h, DESIGN.md "Component fits").
+//   model    m = A exp(-(a u^2 + 2 b u v + c v^2) / 2), u = dx - x0, v = dy - y0; p = (A, x0, y0, a, b, c), x0 / y0 relative to the
+//            window's first pixel in here (the runtime converts from and to image pixels)
+//   sweep    F = sum r^2, g = J^T r, H = J^T J (upper triangle) at one p over the job's pixels: FIT_NSUM = 28 float64 sums
+//   step     thread 0: 6 x 6 Cholesky of H + lambda diag(H), d, `small`, admissibility of p + d; everyone: sweep at the trial;
+//            thread 0: accept / reject, lambda, convergence.  Decisions reach the other threads through two LDS words
+// One workgroup of 256 threads owns one job of the job table from start to finish; no workgroup reads what another one wrote.
+// The job's pixels arrive as a list of window indices i = dy * W + dx in increasing order, built by the runtime from the mask: the
+// kernel never searches a window.  A list entry whose pixel is not valid (0 or non-finite) keeps its list position and contributes
+// nothing.  A job of at most FIT_LDS_MAX list entries keeps {value, index} of every entry in LDS (8 bytes per pixel, 32 KiB; with
+// the reduction scratch 34 KiB per workgroup: the 160 KiB of a CU would hold four); a larger one re-reads list and
+// image, which L2 serves from the second sweep on.
+// Registers: 28 float64 accumulators are 56 VGPRs per lane; with the six Jacobian entries, exp's temporaries and thread 0's 6 x 6
+// factor the build reports 180 VGPRs and no spill (the 96 bytes of scratch hold the job record, read once).  Of the 512 registers
+// per lane of a SIMD that leaves two waves per SIMD, so two workgroups (68 KiB of LDS) are resident per CU.  Holding the kernel
+// to 128 VGPRs for four waves spills 25 registers and was not kept.
+// Every loop has a bound fixed before it starts:
+//   iteration   it = 1 .. max_iter (<= FIT_MAX_ITER = 256); every lambda escalation is one iteration, so there is no inner loop
+//   sweeps      over the npos list entries of the job, npos <= 2^24; at most max_iter + 1 sweeps per job
+//   reductions  6 shuffle steps and FIT_T / 64 = 4 waves;  Cholesky and the two triangular solves: 6 x 6, fully unrolled
+// Sums: float64 per lane over increasing list position (entry q belongs to thread q mod 256), __shfl_down tree per wave, the
+// four waves added in order by thread 0: fixed association, so two runs give the same bits.  No atomics.
+#include "cy_kernels.h"
+#include <cfloat>
+
+#pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
+
+namespace cy {
+namespace {
+
+constexpr int FIT_T = 256, FIT_W = FIT_T / 64;
+constexpr unsigned FIT_BAD = 0xFFFFFFFFu;
+constexpr int ACT_NONE = 0, ACT_SWEEP = 1, ACT_STOP = 2;
+
+struct FSmem {
+    float val[FIT_LDS_MAX];
+    unsigned idx[FIT_LDS_MAX];
+    double red[FIT_NSUM][FIT_W];
+    double tot[FIT_NSUM];               // sums of the last sweep
+    double cur[FIT_NSUM];               // sums at the accepted p
+    double p[6], pt[6];                 // accepted and trial parameters
+    unsigned cnt[FIT_W];
+    volatile int act, stop;
+};
+
+__device__ __forceinline__ bool fit_valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
+__device__ __forceinline__ bool fin(double v) { return fabs(v) <= DBL_MAX; }
+__device__ __forceinline__ bool admissible(const double* p) {
+    return fin(p[0]) && fin(p[1]) && fin(p[2]) && fin(p[3]) && fin(p[4]) && fin(p[5]) && p[0] > 0.0 && p[3] > 0.0 && p[5] > 0.0 &&
+           p[3] * p[5] - p[4] * p[4] > 0.0;
+}
+__host__ __device__ constexpr int hidx(int i, int j) { return 7 + i * 6 - i * (i - 1) / 2 + (j - i); }   // H(i, j), i <= j, in the 28 sums
+static_assert(hidx(0, 0) == 7 && hidx(5, 5) == FIT_NSUM - 1, "F, g (6), H upper triangle row-major (21)");
+
+// F, g, H at pp (LDS, uniform) over the job's list; the totals land in s.tot (valid for thread 0 after the barrier inside)
+template <bool LDS>
+__device__ __forceinline__ void sweep(FSmem& s, const double* pp, const unsigned* __restrict__ list, const unsigned npos,
+                                      const float* __restrict__ img, const size_t MW, const unsigned W, const unsigned A, const double bkg) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const double pA = pp[0], x0 = pp[1], y0 = pp[2], a = pp[3], b = pp[4], c = pp[5];
+    double acc[FIT_NSUM];
+#pragma unroll
+    for (int k = 0; k < FIT_NSUM; ++k) acc[k] = 0.0;
+    for (unsigned q = tid; q < npos; q += FIT_T) {
+        unsigned i; float fv;
+        if (LDS) { i = s.idx[q]; fv = s.val[q]; }
+        else {
+            i = list[q]; fv = 0.0f;
+            if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
+            if (i >= A || !fit_valid_px(fv)) i = FIT_BAD;
+        }
+        if (i == FIT_BAD) continue;
+        const unsigned dy = i / W, dx = i - dy * W;
+        const double y = (double)fv - bkg, u = (double)dx - x0, v = (double)dy - y0;
+        const double e = exp(-0.5 * ((a * u) * u + ((2.0 * b) * u) * v + (c * v) * v));
+        const double m = pA * e, r = y - m;
+        double J[6];
+        J[0] = e; J[1] = m * (a * u + b * v); J[2] = m * (b * u + c * v);
+        J[3] = ((-0.5 * m) * u) * u; J[4] = ((-m) * u) * v; J[5] = ((-0.5 * m) * v) * v;
+        acc[0] += r * r;
+#pragma unroll
+        for (int ii = 0; ii < 6; ++ii) {
+            acc[1 + ii] += J[ii] * r;
+#pragma unroll
+            for (int jj = ii; jj < 6; ++jj) acc[hidx(ii, jj)] += J[ii] * J[jj];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < FIT_NSUM; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
+        if (lane == 0) s.red[k][w] = acc[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < FIT_NSUM; ++k) {
+            double t = acc[k];
+#pragma unroll
+            for (int j = 1; j < FIT_W; ++j) t += s.red[k][j];
+            s.tot[k] = t;
+        }
+    }
+}
+
+// thread 0: d of (H + lam diag(H)) d = g by Cholesky (row by row, every inner sum subtracted term by term in increasing k); false
+// on a pivot that is not positive and finite
+__device__ __forceinline__ bool lm_solve(const double* cur, const double lam, double* d) {
+    double L[6][6], z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const double hjj = cur[hidx(j, j)];
+        double t = hjj + lam * hjj;
+#pragma unroll
+        for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k];
+        if (!(t > 0.0) || !fin(t)) return false;
+        L[j][j] = sqrt(t);
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double q = cur[hidx(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) q -= L[i][k] * L[j][k];
+            L[i][j] = q / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double q = cur[1 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) q -= L[i][k] * z[k];
+        z[i] = q / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double q = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) q -= L[k][i] * d[k];
+        d[i] = q / L[i][i];
+    }
+    return true;
+}
+
+template <bool LDS>
+__device__ void fit(FSmem& s, const FitJob& j, const FitArgs& a, double* __restrict__ out) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const size_t MW = (size_t)a.MW;
+    const float* __restrict__ img = a.img + (size_t)j.y0 * MW + (size_t)j.x0;
+    const unsigned* __restrict__ list = a.list + j.list_off;
+    const unsigned W = j.W, A = j.A, npos = j.npos;
+    const double bkg = j.bkg;
+
+    // ---- valid pixels of the list (and, in LDS, their values)
+    unsigned np = 0;
+    for (unsigned q = tid; q < npos; q += FIT_T) {
+        unsigned i = list[q]; float fv = 0.0f;
+        if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
+        if (i >= A || !fit_valid_px(fv)) i = FIT_BAD;
+        if (LDS) { s.idx[q] = i; s.val[q] = fv; }
+        np += i != FIT_BAD;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) np += __shfl_down(np, o);
+    if (lane == 0) s.cnt[w] = np;
+    if (tid < 6) { s.p[tid] = j.p0[tid]; s.pt[tid] = j.p0[tid]; }
+    if (tid == 0) { s.act = ACT_NONE; s.stop = 0; }
+    __syncthreads();
+    np = s.cnt[0];
+#pragma unroll
+    for (int k = 1; k < FIT_W; ++k) np += s.cnt[k];
+
+    const int early = !admissible(j.p0) ? 4 : np < (unsigned)FIT_MIN_PIX ? 3 : 0;     // uniform
+    if (early) {
+        if (tid < FIT_FIELDS) out[tid] = tid == 0 ? (double)early : tid == 2 ? (double)np : tid >= 5 && tid < 11 ? s.p[tid - 5] : 0.0;
+        return;
+    }
+
+    // ---- sums at the start
+    sweep<LDS>(s, s.pt, list, npos, img, MW, W, A, bkg);
+    double lam = 1e-3;
+    int status = 2, niter = a.max_iter;
+    bool small = false;
+    if (tid == 0)
+        for (int k = 0; k < FIT_NSUM; ++k) s.cur[k] = s.tot[k];
+
+    for (int it = 1; it <= a.max_iter; ++it) {
+        if (tid == 0) {
+            double d[6];
+            int act = ACT_NONE;
+            small = false;
+            if (lm_solve(s.cur, lam, d)) {
+                small = true;
+                double pn[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    small = small && fabs(d[k]) <= 1e-10 * (fabs(s.p[k]) + 1e-6);
+                    pn[k] = s.p[k] + d[k];
+                }
+                if (admissible(pn)) {
+                    act = ACT_SWEEP;
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) s.pt[k] = pn[k];
+                }
+            }
+            if (act == ACT_NONE) {                            // rejected without a sweep
+                if (small) { status = 0; niter = it; act = ACT_STOP; }
+                else {
+                    lam *= 10.0;
+                    if (lam > 1e12) { status = 2; niter = it; act = ACT_STOP; }
+                }
+            }
+            s.act = act;
+        }
+        __syncthreads();
+        const int act = s.act;                                // uniform (from LDS)
+        if (act == ACT_STOP) break;
+        if (act == ACT_SWEEP) {
+            sweep<LDS>(s, s.pt, list, npos, img, MW, W, A, bkg);
+            if (tid == 0) {
+                const double F = s.cur[0], Fn = s.tot[0];
+                if (Fn < F) {
+                    const bool conv = small || F - Fn <= 1e-14 * F;
+                    for (int k = 0; k < FIT_NSUM; ++k) s.cur[k] = s.tot[k];
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) s.p[k] = s.pt[k];
+                    lam = fmax(lam / 10.0, 1e-12);
+                    if (conv) { status = 0; niter = it; s.stop = 1; }
+                } else if (small) { status = 0; niter = it; s.stop = 1; }
+                else {
+                    lam *= 10.0;
+                    if (lam > 1e12) { status = 2; niter = it; s.stop = 1; }
+                }
+            }
+        }
+        __syncthreads();
+        if (s.stop) break;                                    // uniform (from LDS)
+    }
+    if (tid == 0) {
+        out[0] = (double)status; out[1] = (double)niter; out[2] = (double)np; out[3] = s.cur[0]; out[4] = lam;
+        for (int k = 0; k < 6; ++k) out[5 + k] = s.p[k];
+        for (int k = 0; k < 21; ++k) out[11 + k] = s.cur[7 + k];
+    }
+}
+
+__global__ __launch_bounds__(FIT_T) void fit_kernel(const FitArgs a) {
+    __shared__ FSmem s;
+    const FitJob j = a.jobs[blockIdx.x];
+    const int tid = threadIdx.x;
+    // the runtime's jobs are inside the image, their rows inside the output and their lists inside the list buffer; checked again
+    // so that no index can leave a buffer whatever arrives here.  cy_fit_components cannot produce such a job; should it ever
+    // happen, nothing is fitted and, where the row itself is inside the output, it is NaN throughout
+    const bool rowok = j.row >= 0 && j.row < a.nrows;
+    const bool ok = rowok && j.x0 >= 0 && j.y0 >= 0 && j.W >= 1 && j.A >= j.W && j.A % j.W == 0 && (long long)j.A <= FIT_MAX_AREA &&
+                    (long long)j.x0 + j.W <= a.MW && (long long)j.y0 + j.A / j.W <= a.MH && j.list_off >= 0 && j.npos <= j.A &&
+                    j.list_off + (long long)j.npos <= a.nlist;
+    if (!ok) {
+        if (rowok && tid < FIT_FIELDS) a.out[(size_t)j.row * FIT_FIELDS + tid] = __longlong_as_double(0x7FF8000000000000LL);
+        return;
+    }
+    double* out = a.out + (size_t)j.row * FIT_FIELDS;
+    if (j.npos <= (unsigned)FIT_LDS_MAX) fit<true>(s, j, a, out);
+    else fit<false>(s, j, a, out);
+}
+
+}  // namespace
+
+hipError_t launch_fit(const FitArgs& a, hipStream_t s) {
+    if (a.njobs < 1 || a.MH < 1 || a.MW < 1 || a.max_iter < 1 || a.max_iter > FIT_MAX_ITER) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fit_kernel, dim3(a.njobs), dim3(FIT_T), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace cy

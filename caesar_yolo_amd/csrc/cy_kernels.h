@@ -295,6 +295,30 @@ struct DeblendArgs {
 };
 hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s);
 
+// ---- component fits (cy_fit.hip) -------------------------------------------------------------------
+constexpr int FIT_FIELDS = 32;                 // CY_FIT_FIELDS
+constexpr int FIT_NSUM = 28;                   // F, g (6), H upper triangle (21)
+constexpr int FIT_LDS_MAX = 4096;              // largest job (list entries) whose values and indices live in LDS: 32 KiB per workgroup
+constexpr int FIT_MIN_PIX = 7, FIT_MAX_ITER = 256;
+constexpr long long FIT_MAX_AREA = 1LL << 24;  // largest supported window; the components of a larger one get status 1 from the runtime
+struct FitJob {
+    long long list_off;             // first list entry of the job in FitArgs::list
+    unsigned npos;                  // list entries: window pixels whose mask byte is the job's component + 1, valid or not
+    int x0, y0;                     // first column / row of the box window, inside the image
+    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
+    int row;                        // output row: source * DBL_MAX_COMP + component
+    double bkg;
+    double p0[6];                   // start {A, x0, y0, a, b, c}, x0 / y0 relative to the window's first pixel
+};
+struct FitArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    const FitJob* jobs; int njobs;
+    const unsigned* list; long long nlist;      // window indices dy * W + dx, increasing inside a job
+    int max_iter;                   // 1 .. FIT_MAX_ITER
+    double* out; int nrows;         // [nrows][FIT_FIELDS], zeroed by the caller; the kernel writes the jobs' rows
+};
+hipError_t launch_fit(const FitArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

@@ -65,6 +65,7 @@ struct cy_ctx {
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
     double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
+    double fit_ms = -1.0;                               // ... of the last cy_fit_components call that launched (cy_fit_kernel_ms)
     double deblend_ms = -1.0;                           // ... of the last cy_deblend_islands call (cy_deblend_kernel_ms)
     double islands_ms = -1.0;                           // ... of the last cy_measure_islands call (cy_islands_kernel_ms)
     double background_ms = -1.0;                        // ... of the last cy_measure_background call (cy_background_kernel_ms)
@@ -1682,6 +1683,123 @@ int cy_deblend_islands(cy_ctx* c, const float* d_img, int MH, int MW, const doub
 int cy_deblend_kernel_ms(const cy_ctx* c, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
     *out_ms = c->deblend_ms;
+    return CY_OK;
+}
+
+// ---- component fits ---------------------------------------------------------------------------
+static_assert(CY_FIT_FIELDS == FIT_FIELDS, "header and kernel disagree on the fit row");
+
+int cy_fit_components(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_bkg, const int* h_ncomp,
+                      const double* h_start, int n, int max_iter, const unsigned char* h_mask, const long long* h_mask_off, double* h_fit,
+                      void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (n < 0 || max_iter < 1 || max_iter > FIT_MAX_ITER || MH <= 0 || MW <= 0)
+        return fail(c, CY_ERR_ARG, "n >= 0, 1 <= max_iter <= 256 and MH, MW > 0 required");
+    if (n == 0) return CY_OK;
+    if (!d_img || !h_boxes || !h_bkg || !h_ncomp || !h_start || !h_mask || !h_mask_off || !h_fit) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
+    // one pass over the mask bytes: the job table and, per job, the window indices of its pixels in increasing order
+    std::vector<FitJob> jobs;
+    std::vector<unsigned> list;
+    std::vector<unsigned> per[DBL_MAX_COMP];
+    std::vector<int> wx0((size_t)n), wy0((size_t)n);
+    std::vector<char> large((size_t)n, 0);
+    long long nmask = 0;
+    for (int i = 0; i < n; ++i) {
+        const int nc = h_ncomp[i];
+        if (nc < 0 || nc > DBL_MAX_COMP) return fail(c, CY_ERR_ARG, "h_ncomp outside 0 .. CY_DBL_MAX_COMP");
+        int w[4];
+        const double* b = h_boxes + (size_t)i * 4;
+        window_1d(b[0], b[2], MW, &w[0], &w[1]);
+        window_1d(b[1], b[3], MH, &w[2], &w[3]);
+        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
+        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
+        if (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area)
+            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
+        wx0[i] = w[0]; wy0[i] = w[2];
+        const unsigned char* m = h_mask + nmask;
+        nmask += area;
+        const bool collect = area <= FIT_MAX_AREA;            // a larger window is only checked: its rows get status 1
+        for (int k = 0; k < nc; ++k) per[k].clear();
+        for (long long q = 0; q < area; ++q) {
+            if (m[q] > DBL_MAX_COMP && m[q] != 255) return fail(c, CY_ERR_ARG, "mask byte in 17 .. 254");
+            const int k = (int)m[q] - 1;
+            if (collect && k >= 0 && k < nc) per[k].push_back((unsigned)q);
+        }
+        if (!collect) { large[i] = 1; continue; }
+        for (int k = 0; k < nc; ++k) {
+            FitJob j{};
+            j.list_off = (long long)list.size(); j.npos = (unsigned)per[k].size();
+            j.x0 = w[0]; j.y0 = w[2]; j.W = (unsigned)(w[1] - w[0] + 1); j.A = (unsigned)area;
+            j.row = i * DBL_MAX_COMP + k; j.bkg = h_bkg[i];
+            const double* p = h_start + ((size_t)i * DBL_MAX_COMP + k) * 6;
+            for (int t = 0; t < 6; ++t) j.p0[t] = p[t];
+            j.p0[1] = p[1] - (double)w[0]; j.p0[2] = p[2] - (double)w[2];
+            if (area == 0) { j.x0 = j.y0 = 0; j.W = 1; j.A = 1; }       // an empty window has no pixel: a job without a list entry
+            list.insert(list.end(), per[k].begin(), per[k].end());
+            jobs.push_back(j);
+        }
+    }
+    const size_t fit_bytes = (size_t)n * DBL_MAX_COMP * CY_FIT_FIELDS * sizeof(double);
+    std::memset(h_fit, 0, fit_bytes);
+    for (int i = 0; i < n; ++i)
+        if (large[i])
+            for (int k = 0; k < h_ncomp[i]; ++k) h_fit[((size_t)i * DBL_MAX_COMP + k) * CY_FIT_FIELDS] = 1.0;
+    if (jobs.empty()) return CY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    void *d_jobs = nullptr, *d_list = nullptr, *d_out = nullptr;
+    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(unsigned);
+    HIPCHK(c, sc.alloc(jobs.size() * sizeof(FitJob), &d_jobs));
+    HIPCHK(c, sc.alloc(list_bytes, &d_list));
+    HIPCHK(c, sc.alloc(fit_bytes, &d_out));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(FitJob), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, fit_bytes, st);                    // the kernel writes the jobs' rows only
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) {
+        FitArgs a{};
+        a.img = d_img; a.MH = MH; a.MW = MW; a.jobs = reinterpret_cast<const FitJob*>(d_jobs); a.njobs = (int)jobs.size();
+        a.list = reinterpret_cast<const unsigned*>(d_list); a.nlist = (long long)list.size(); a.max_iter = max_iter;
+        a.out = reinterpret_cast<double*>(d_out); a.nrows = n * DBL_MAX_COMP;
+        e = launch_fit(a, st);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    std::vector<double> got;
+    if (e == hipSuccess) {
+        got.resize((size_t)n * DBL_MAX_COMP * CY_FIT_FIELDS);
+        e = hipMemcpyAsync(got.data(), d_out, fit_bytes, hipMemcpyDeviceToHost, st);
+    }
+    const int rc = entry_done(c, e, st);
+    float ms = -1.0f;
+    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    c->fit_ms = ms;
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (rc != CY_OK) return rc;
+    // the jobs' rows: centres back in image pixels; a job that was not fitted (status 3, 4) reports its start exactly as given
+    for (const FitJob& j : jobs) {
+        const double* g = &got[(size_t)j.row * CY_FIT_FIELDS];
+        double* o = h_fit + (size_t)j.row * CY_FIT_FIELDS;
+        for (int t = 0; t < CY_FIT_FIELDS; ++t) o[t] = g[t];
+        const int src = j.row / DBL_MAX_COMP;
+        if (g[0] == 3.0 || g[0] == 4.0) {
+            const double* p = h_start + (size_t)j.row * 6;
+            for (int t = 0; t < 6; ++t) o[5 + t] = p[t];
+        } else {
+            o[6] = g[6] + (double)wx0[src]; o[7] = g[7] + (double)wy0[src];
+        }
+    }
+    return CY_OK;
+}
+
+int cy_fit_kernel_ms(const cy_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return CY_ERR_ARG;
+    *out_ms = c->fit_ms;
     return CY_OK;
 }
 

@@ -29,7 +29,8 @@ class Analyzer(object):
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
-        self.deblend = bool(config.get('deblend_islands', False))       # NEW: --deblend_islands, the components (implies the islands)
+        self.fit = bool(config.get('fit_components', False))            # NEW: --fit_components, one Gaussian per component (implies the components)
+        self.deblend = bool(config.get('deblend_islands', False)) or self.fit       # NEW: --deblend_islands, the components (implies the islands)
         self.islands = bool(config.get('measure_islands', False)) or self.deblend       # NEW: --measure_islands, the second step (implies the first)
         self.bkg_map = bool(config.get('bkg_map', False)) or bool(config.get('save_bkg_maps', False))      # NEW: --bkg_map, between the two
         self.measure = bool(config.get('measure_sources', False)) or self.islands or self.bkg_map
@@ -176,10 +177,14 @@ class Analyzer(object):
                                                      self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin, use_map=self.bkg_map)
                     if self.deblend:
                         k_peak, radius = measure.deblend_config(c)
-                        measure.deblend_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
-                                                     c.get('island_merge_sigma', 2.5), k_peak, int(c.get('island_conn', 8)), radius,
-                                                     self.beam_area, self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
-                                                     use_map=self.bkg_map)
+                        kept = measure.deblend_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
+                                                            c.get('island_merge_sigma', 2.5), k_peak, int(c.get('island_conn', 8)), radius,
+                                                            self.beam_area, self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
+                                                            use_map=self.bkg_map, return_raw=self.fit)
+                        if self.fit:
+                            measure.fit_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], self.beam_area, self.wcs,
+                                                     box_origin=(xmin, ymin), wcs_origin=self.wcs_origin, use_map=self.bkg_map,
+                                                     max_iter=int(c.get('fit_max_iter', 64)))
                 except L.CyError as e:
                     logger.warning("Source measurement failed (err=%s)..." % str(e))
                     return -1

@@ -18,6 +18,10 @@ from bkg_map / rms_map.
 components by local peaks and steepest-ascent basins, raw rows lib.DBL_NAMES / lib.DBL_COMP_NAMES, keys COMPONENT_KEYS
 (annotate_components).
 
+--fit_components adds a fifth step: `cy_fit_components` (HipDetector.fit_components) fits one elliptical Gaussian to every component
+by Levenberg-Marquardt from the start values fit_start() forms out of the component rows, raw rows lib.FIT_NAMES, keys FIT_KEYS on
+every component dict (annotate_fits).
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
 import math
 
@@ -29,6 +33,9 @@ ISLAND_KEYS = ("island_count", "island_npix", "island_npix_main", "island_border
 BKG_KEYS = ("bkg_map", "rms_map", "snr_map")
 COMPONENT_KEYS = ("npeaks", "ncomponents", "components_truncated", "components_unassigned_npix", "components")
 COMPONENT_ITEM_KEYS = ("x", "y", "ra", "dec", "peak", "x_peak", "y_peak", "npix", "flux_sum", "flux", "major", "minor", "pa", "main", "nsummits")
+FIT_KEYS = ("fit_status", "fit_niter", "fit_npix", "fit_chi2", "fit_peak", "fit_x", "fit_y", "fit_ra", "fit_dec", "fit_major", "fit_minor",
+            "fit_pa", "fit_flux", "fit_peak_err", "fit_x_err", "fit_y_err", "fit_flux_err")
+FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
 
@@ -244,24 +251,194 @@ def annotate_components(sources, raw, comp, win0, beam_area, wcs, origin=(0, 0))
 
 
 def deblend_and_annotate(det, img_dev, sources, k_seed, k_merge, k_peak, conn, radius, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
-                         use_map=False):
+                         use_map=False, return_raw=False):
     """The component step, after islands_and_annotate on the same sources and image: thresholds in numpy float64, one
     cy_deblend_islands call, then annotate_components().  box_origin / wcs_origin / use_map as in islands_and_annotate: positions
-    come back in catalog coordinates."""
+    come back in catalog coordinates.  return_raw: -> (sources, raw rows, component rows, masks) as HipDetector.deblend_islands
+    returns them with return_masks, in the pixel frame of img_dev: what fit_and_annotate() takes, so that the kernel runs once."""
     if not sources:
-        return sources
+        return (sources, np.zeros((0, 8)), np.zeros((0, 16, 12)), []) if return_raw else sources
     bx, by = float(box_origin[0]), float(box_origin[1])
     boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    raw, comp = det.deblend_islands(img_dev, boxes, deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map), conn=conn, radius=radius)
+    thr4 = deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map)
+    if return_raw:
+        raw, comp, masks = det.deblend_islands(img_dev, boxes, thr4, conn=conn, radius=radius, return_masks=True)
+        keep = (sources, raw, comp, masks)
+    else:
+        raw, comp = det.deblend_islands(img_dev, boxes, thr4, conn=conn, radius=radius)
     MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
     win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
+    annotate_components(sources, raw, _shift_comp(raw, comp, bx, by), win0, beam_area, wcs, wcs_origin)
+    return keep if return_raw else sources
+
+
+def _shift_comp(raw, comp, bx, by):
+    """Component rows with the peak positions of the rows below ncomp moved by (bx, by); a copy when anything moves."""
+    if not (bx or by):
+        return comp
+    comp = comp.copy()
+    has = np.arange(comp.shape[1])[None, :] < raw[:, 3].astype(np.int64)[:, None]
+    comp[:, :, 2][has] += bx
+    comp[:, :, 3][has] += by
+    return comp
+
+
+# ---- component fits (--fit_components)
+def fit_start(comp_rows, bkg, win0):
+    """Start values {A, x0, y0, a, b, c} of the fit from component rows (lib.DBL_COMP_NAMES): comp_rows [..., 12], bkg [...] and
+    win0 [..., 2] (first column / row of the box window) broadcast against the leading axes; x0, y0 in the frame of win0 and of the
+    rows' peak positions.  -> float64 [..., 6].
+      A        peak - bkg
+      centre   the moment centroid win0 + (Sx / S, Sy / S)
+      a, b, c  the inverse of the central-moment covariance (cxx = Sxx / S - (Sx / S)^2 ...) with its eigenvalues floored at
+               FIT_SIGMA2_MIN = 0.25 px^2 (the eigenvectors stay)
+      S <= 0, or a moment, the centroid or the covariance not finite: the peak position and a circular sigma of 1 px (a = c = 1,
+      b = 0)."""
+    r = np.asarray(comp_rows, np.float64)
+    lead = r.shape[:-1]
+    bkg = np.broadcast_to(np.asarray(bkg, np.float64).reshape(np.shape(bkg) + (1,) * (len(lead) - np.ndim(bkg))), lead)
+    w0 = np.asarray(win0, np.float64)
+    w0 = np.broadcast_to(w0.reshape(w0.shape[:-1] + (1,) * (len(lead) - (w0.ndim - 1)) + (2,)), lead + (2,))
+    S, Sx, Sy, Sxx, Syy, Sxy = (r[..., k] for k in range(4, 10))
+    with np.errstate(all="ignore"):
+        mx, my = Sx / S, Sy / S
+        cxx, cyy, cxy = Sxx / S - mx * mx, Syy / S - my * my, Sxy / S - mx * my
+        half, d = (cxx + cyy) / 2.0, np.hypot((cxx - cyy) / 2.0, cxy)
+        l1, l2 = np.maximum(half + d, FIT_SIGMA2_MIN), np.maximum(half - d, FIT_SIGMA2_MIN)
+        th = 0.5 * np.arctan2(2.0 * cxy, cxx - cyy)
+        cs, sn = np.cos(th), np.sin(th)
+        vxx, vyy, vxy = l1 * cs * cs + l2 * sn * sn, l1 * sn * sn + l2 * cs * cs, (l1 - l2) * sn * cs
+        det = l1 * l2
+        a, b, c = vyy / det, -vxy / det, vxx / det
+        good = (S > 0.0) & np.isfinite(S) & np.isfinite(mx) & np.isfinite(my) & np.isfinite(a) & np.isfinite(b) & np.isfinite(c)
+    out = np.empty(lead + (6,), np.float64)
+    out[..., 0] = r[..., 1] - bkg
+    out[..., 1] = np.where(good, w0[..., 0] + mx, r[..., 2])
+    out[..., 2] = np.where(good, w0[..., 1] + my, r[..., 3])
+    out[..., 3] = np.where(good, a, 1.0)
+    out[..., 4] = np.where(good, b, 0.0)
+    out[..., 5] = np.where(good, c, 1.0)
+    return out
+
+
+def gaussian_shape(a, b, c):
+    """(major, minor, pa) of a fitted Gaussian with inverse covariance [[a, b], [b, c]]: FWHM * sqrt of the eigenvalues of the
+    covariance, in pixels; pa as island_shape(): angle of the major axis from +x towards +y in degrees, in (-90, 90], 0 for a
+    circle."""
+    det = a * c - b * b
+    cxx, cyy, cxy = c / det, a / det, -b / det
+    half, d = (cxx + cyy) / 2.0, math.hypot((cxx - cyy) / 2.0, cxy)
+    l1, l2 = max(half + d, 0.0), max(half - d, 0.0)
+    pa = 0.0
+    if l1 != l2:
+        pa = 0.5 * math.degrees(math.atan2(2.0 * cxy + 0.0, cxx - cyy))
+        if pa <= -90.0:
+            pa += 180.0
+    return FWHM * math.sqrt(l1), FWHM * math.sqrt(l2), pa
+
+
+def fit_flux(p, beam_area):
+    """Integrated flux of the model p = (A, x0, y0, a, b, c): 2 pi A / sqrt(a c - b^2) pixel-sums, over the beam area."""
+    return 2.0 * math.pi * p[0] / math.sqrt(p[3] * p[5] - p[4] * p[4]) / beam_area
+
+
+def fit_flux_grad(p, beam_area):
+    """Gradient of fit_flux() with respect to the six parameters (the centre does not enter)."""
+    f, D = fit_flux(p, beam_area), p[3] * p[5] - p[4] * p[4]
+    return np.array([f / p[0], 0.0, 0.0, -0.5 * f * p[5] / D, f * p[4] / D, -0.5 * f * p[3] / D], np.float64)
+
+
+def fit_covariance(row, rms):
+    """rms^2 * inv(H) from a fit row (lib.FIT_NAMES), the covariance of the six parameters for uncorrelated noise of that rms; None
+    when H is singular or not finite."""
+    H = np.zeros((6, 6), np.float64)
+    H[np.triu_indices(6)] = np.asarray(row, np.float64)[11:32]
+    H = H + np.triu(H, 1).T
+    if not np.isfinite(H).all():
+        return None
+    try:
+        cov = np.linalg.inv(H) * (float(rms) * float(rms))
+    except np.linalg.LinAlgError:
+        return None
+    return cov if np.isfinite(cov).all() and (np.diag(cov) >= 0.0).all() else None
+
+
+def annotate_fits(sources, fit, beam_area, wcs, origin=(0, 0), use_map=False):
+    """Adds FIT_KEYS to every component dict of every source (in place; returns the list), after annotate_components().  fit:
+    [n, CY_DBL_MAX_COMP, CY_FIT_FIELDS] rows of cy_fit_components with x0, y0 in the frame the catalog's positions are wanted in.
+      fit_status, fit_niter, fit_npix   as in the row
+      fit_chi2   F / rms^2 with the source's rms (rms_map with use_map); None when that is missing or 0
+      fit_peak = A, fit_x, fit_y; fit_ra, fit_dec  wcs.wcs_pix2world(fit_x + ox, fit_y + oy, 0), None without a WCS
+      fit_major, fit_minor, fit_pa   gaussian_shape(a, b, c)
+      fit_flux   fit_flux(): 2 pi A / sqrt(a c - b^2) / beam_area, None without a beam
+      fit_peak_err, fit_x_err, fit_y_err   square roots of the diagonal of fit_covariance() = rms^2 inv(H); fit_flux_err =
+                 sqrt(g^T cov g) with g = fit_flux_grad(): first-order propagation.  None without rms or with a singular H
+    With status 1, 3 or 4 every key but fit_status, fit_niter and fit_npix is None.  A source whose components are None (window above
+    the supported maximum) is left alone."""
+    if not sources:
+        return sources
+    fit = np.asarray(fit, np.float64).reshape(len(sources), -1, 32)       # CY_FIT_FIELDS
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for s, fr in zip(sources, fit):
+        rms = s.get("rms_map" if use_map else "rms")
+        rms = float(rms) if rms else 0.0
+        for d, r in zip(s.get("components") or [], fr):
+            for k in FIT_KEYS:
+                d[k] = None
+            st = int(r[0])
+            d["fit_status"], d["fit_niter"], d["fit_npix"] = st, int(r[1]), int(r[2])
+            if st not in (0, 2):
+                continue
+            p = [float(v) for v in r[5:11]]
+            d["fit_chi2"] = float(r[3]) / (rms * rms) if rms > 0.0 else None
+            d["fit_peak"], d["fit_x"], d["fit_y"] = p[0], p[1], p[2]
+            d["fit_major"], d["fit_minor"], d["fit_pa"] = gaussian_shape(p[3], p[4], p[5])
+            if wcs is not None:
+                a, dd = wcs.wcs_pix2world(p[1] + ox, p[2] + oy, 0)
+                d["fit_ra"], d["fit_dec"] = float(a), float(dd)
+            if ba > 0.0:
+                d["fit_flux"] = fit_flux(p, ba)
+            cov = fit_covariance(r, rms) if rms > 0.0 else None
+            if cov is not None:
+                d["fit_peak_err"], d["fit_x_err"], d["fit_y_err"] = (math.sqrt(cov[k, k]) for k in range(3))
+                if ba > 0.0:
+                    g = fit_flux_grad(p, ba)
+                    d["fit_flux_err"] = math.sqrt(max(float(g @ cov @ g), 0.0))
+    return sources
+
+
+def fit_and_annotate(det, img_dev, sources, raw, comp, masks, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0), use_map=False,
+                     max_iter=64):
+    """The fit step, after deblend_and_annotate(..., return_raw=True) on the same sources and image, whose raw rows, component rows
+    and masks it takes (pixel frame of img_dev): fit_start(), one cy_fit_components call, then annotate_fits().  The background of
+    a source is the one its thresholds were formed with (bkg, or bkg_map with use_map).  -> the fit rows, centres in catalog
+    coordinates."""
+    n = len(sources)
+    if not n:
+        return np.zeros((0, 16, 32), np.float64)
+    bx, by = float(box_origin[0]), float(box_origin[1])
+    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
+    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2)
+    bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
+    raw = np.asarray(raw, np.float64).reshape(n, -1)
+    ncomp = np.where(raw[:, 0] == 1.0, 0, raw[:, 3]).astype(np.int32)
+    start = fit_start(np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
+    fit = det.fit_components(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
     if bx or by:
-        comp = comp.copy()
-        ncomp = raw[:, 3].astype(np.int64)
-        has = np.arange(comp.shape[1])[None, :] < ncomp[:, None]
-        comp[:, :, 2][has] += bx
-        comp[:, :, 3][has] += by
-    return annotate_components(sources, raw, comp, win0, beam_area, wcs, wcs_origin)
+        has = (np.arange(fit.shape[1])[None, :] < ncomp[:, None]) & (fit[:, :, 0] != 1.0)
+        fit[:, :, 6][has] += bx
+        fit[:, :, 7][has] += by
+    annotate_fits(sources, fit, beam_area, wcs, wcs_origin, use_map)
+    return fit
+
+
+def fit_iterations(fit):
+    """(jobs, mean niter, largest niter) over the fitted rows (status 0 or 2) of cy_fit_components; (0, 0.0, 0) without one."""
+    fit = np.asarray(fit, np.float64).reshape(-1, 32)
+    it = fit[(fit[:, 1] > 0) & ((fit[:, 0] == 0.0) | (fit[:, 0] == 2.0)), 1]
+    return (int(it.size), float(it.mean()), int(it.max())) if it.size else (0, 0.0, 0)
 
 
 def deblend_config(config):

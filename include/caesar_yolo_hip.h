@@ -355,6 +355,49 @@ int cy_deblend_islands(cy_ctx* ctx, const float* d_img, int MH, int MW, const do
 /* milliseconds the kernel of the last cy_deblend_islands call took (hipEvents around the launch); -1 before the first call */
 int cy_deblend_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- component fits (an addition, the fifth measurement step) ---------------------------------------------------------------
+ * One elliptical Gaussian fitted to every component of cy_deblend_islands, unweighted Levenberg-Marquardt in float64.  Image, valid
+ * pixel, pixel-centre convention and box window are those of cy_measure_islands; h_mask / h_mask_off are laid out as
+ * cy_deblend_islands writes them (both required here).  h_bkg: one background per source; h_ncomp: its number of components.
+ *   job      one per (source, component k) with k < ncomp.  Its LIST is the window pixels whose mask byte is k + 1, in increasing
+ *            window index i = dy * W + dx; its pixel set is the valid pixels of the list, npix their number.  A pixel that is not
+ *            valid keeps its list position and contributes nothing.  Bytes 0, 255 and bytes above ncomp belong to no job
+ *   data     y_i = (double)v_i - bkg at (dx, dy) relative to the window's first pixel
+ *   model    m = A * exp(-0.5 * q), q = (a*u)*u + ((2*b)*u)*v + (c*v)*v, u = dx - x0, v = dy - y0; p = (A, x0, y0, a, b, c) with
+ *            (a, b, c) the inverse covariance.  The fit runs on x0, y0 relative to the window (start - wx0, result + wx0)
+ *   admissible   all six finite, A > 0, a > 0, c > 0, a * c - b * b > 0
+ *   sweep    r = y - m; J = (e, m*(a*u + b*v), m*(b*u + c*v), ((-0.5*m)*u)*u, ((-m)*u)*v, ((-0.5*m)*v)*v) with e = exp(-0.5 * q);
+ *            F = sum r*r, g_i = sum J_i*r, H_ij = sum J_i*J_j (i <= j): 28 float64 sums at one p, every product rounded on its own
+ *   solve    Cholesky of M = H + lambda * diag(H) (M_jj = H_jj + lambda * H_jj), row by row, inner sums subtracted term by term in
+ *            increasing index; L z = g, L^T d = z.  A pivot that is not positive and finite is a rejection without a trial
+ *   iterate  lambda = 1e-3, sweep at the start; for it = 1 .. max_iter: solve; small = all |d_j| <= 1e-10 * (|p_j| + 1e-6); when
+ *            p + d is admissible, sweep there (F'): F' < F accepts (lambda = max(lambda / 10, 1e-12)) and the job has converged when
+ *            small holds or F - F' <= 1e-14 * F.  A rejected trial (not admissible, or not F' < F) with small true has converged at
+ *            the old p.  Any other rejection: lambda *= 10, and lambda > 1e12 stops with status 2.  niter = the `it` of the stop
+ * h_fit row of job (source, k), CY_FIT_FIELDS float64 (rows at and beyond ncomp are 0):
+ *   [0] status   0 converged; 1 the window has more than 2^24 pixels: nothing done, every other field 0; 2 max_iter or the lambda
+ *                limit reached, the last accepted p reported; 3 npix < 7: start reported as given, niter = 0; 4 start not admissible:
+ *                reported as given, niter = 0 (4 is tested before 3).  With 3 and 4, F, lambda and H are 0
+ *   [1] niter, [2] npix, [3] F, [4] lambda, [5..10] A x0 y0 a b c (x0, y0 in image pixels), [11..31] H upper triangle row-major,
+ *   F and H at the reported p
+ * The runtime builds the job table and the lists in one pass over the mask bytes and uploads them; one launch (one workgroup of 256
+ * threads per job; a job of up to 4096 list entries keeps values and indices in LDS, a larger one re-reads them) and one copy back;
+ * synchronous on `stream`.  The sums are float64 with a fixed association, entry q of the list on thread q mod 256 (two calls give
+ * the same bytes).  n == 0, or no job at all: CY_OK, nothing launched.  A null pointer, MH / MW <= 0, an image of 2^31 pixels or
+ * more, max_iter outside [1, 256], an h_ncomp entry outside [0, 16], h_mask_off that disagrees with the windows, or a mask byte
+ * in 17 .. 254: CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_FIT_FIELDS 32
+/* status niter npix F lambda A x0 y0 a b c, then H upper triangle row-major (21);
+   x0, y0 in image pixels */
+int cy_fit_components(cy_ctx* ctx, const float* d_img, int MH, int MW,
+                      const double* h_boxes, const double* h_bkg /* n */, const int* h_ncomp /* n */,
+                      const double* h_start /* [n][CY_DBL_MAX_COMP][6], x0 y0 in image pixels */,
+                      int n, int max_iter,
+                      const unsigned char* h_mask, const long long* h_mask_off /* n + 1 */,
+                      double* h_fit /* [n][CY_DBL_MAX_COMP][CY_FIT_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_fit_components call that launched one took (hipEvents around the launch); -1 before it */
+int cy_fit_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

@@ -33,6 +33,10 @@ Differences that come with the MI355X engine:
              box.  Every source also carries npeaks, ncomponents, components_truncated, components_unassigned_npix and components,
              a list of {x, y, ra, dec, peak, x_peak, y_peak, npix, flux_sum, flux, major, minor, pa, main, nsummits}
              (cy_deblend_islands; DESIGN.md "Source components").
+  --fit_components  (new; implies --deblend_islands) one elliptical Gaussian fitted to every component by Levenberg-Marquardt on
+             the pixels of its basin, at most --fit_max_iter iterations (default 64, 1..256).  Every component also carries
+             fit_status, fit_niter, fit_npix, fit_chi2, fit_peak, fit_x, fit_y, fit_ra, fit_dec, fit_major, fit_minor, fit_pa,
+             fit_flux and fit_peak_err, fit_x_err, fit_y_err, fit_flux_err (cy_fit_components; DESIGN.md "Component fits").
 """
 import argparse
 import logging
@@ -137,7 +141,13 @@ def parse_args(argv=None):
                    help='a local peak becomes a component at or above bkg + this many rms (default: --island_seed_sigma; with --deblend_islands)')
     p.add_argument('--deblend_radius', dest='deblend_radius', type=int, choices=list(range(1, 9)), default=2,
                    help='a peak is the highest island pixel within this many pixels in x and y (with --deblend_islands)')
+    p.add_argument('--fit_components', dest='fit_components', action='store_true',
+                   help='fit one elliptical Gaussian to every component on the GPU (implies --deblend_islands)')
+    p.add_argument('--fit_max_iter', dest='fit_max_iter', type=int, choices=list(range(1, 257)), default=64, metavar='N',
+                   help='Levenberg-Marquardt iterations per component at most, 1..256 (with --fit_components)')
     args = p.parse_args(argv)
+    if args.fit_components:
+        args.deblend_islands = True
     if args.deblend_islands:
         args.measure_islands = True
     if args.deblend_peak_sigma is None:
@@ -244,6 +254,7 @@ def main(argv=None):
               'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
               'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
               'deblend_islands': args.deblend_islands, 'deblend_peak_sigma': args.deblend_peak_sigma, 'deblend_radius': args.deblend_radius,
+              'fit_components': args.fit_components, 'fit_max_iter': args.fit_max_iter,
               'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
               'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,

@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -12,6 +12,8 @@ histogram of the box-window areas of the catalog and the share of sources whose 
 then also times tests/island_ref.py.  Unless --no-bkg is given there is a fourth variant, --bkg_map (background_ms, background_kernel_ms), and after the runs
 the kernels alone on the same image: cy_measure_background at cell 64 / 128 / 256 (k 3, 3 clips) and cy_expand_background of the
 cell-128 mesh to both maps, `--runs` calls each after a warm-up; --host-ref then also times tests/bkg_ref.py at cell 128.
+Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
+their mean and largest niter beside the deblend_ms and deblend_kernel_ms of the same runs).
 Unless --no-deblend is given there is a variant --deblend_islands (deblend_ms, deblend_kernel_ms beside the islands_ms and
 islands_kernel_ms of the same run: both steps on the same boxes).
 --off-only serves a tree without the switch (the comparison against an earlier commit).  Prints one
@@ -75,6 +77,7 @@ def main():
     ap.add_argument("--no-islands", action="store_true")
     ap.add_argument("--no-bkg", action="store_true")
     ap.add_argument("--no-deblend", action="store_true")
+    ap.add_argument("--no-fit", action="store_true")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -89,7 +92,9 @@ def main():
                      "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms"),
                      "islands_ms": self.stats.get("islands_ms"), "islands_kernel_ms": self.stats.get("islands_kernel_ms"),
                      "background_ms": self.stats.get("background_ms"), "background_kernel_ms": self.stats.get("background_kernel_ms"),
-                     "deblend_ms": self.stats.get("deblend_ms"), "deblend_kernel_ms": self.stats.get("deblend_kernel_ms")})
+                     "deblend_ms": self.stats.get("deblend_ms"), "deblend_kernel_ms": self.stats.get("deblend_kernel_ms"),
+                     "fit_ms": self.stats.get("fit_ms"), "fit_kernel_ms": self.stats.get("fit_kernel_ms"), "fit_jobs": self.stats.get("fit_jobs"),
+                     "fit_niter_mean": self.stats.get("fit_niter_mean"), "fit_niter_max": self.stats.get("fit_niter_max")})
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -110,6 +115,8 @@ def main():
                 variants.append(("bkg", base + on + ["--bkg_map"]))
             if not (args.off_only or args.no_deblend):         # --deblend_islands implies the island step: both steps on the same boxes
                 variants.append(("deblend", base + on + ["--deblend_islands"]))
+            if not (args.off_only or args.no_deblend or args.no_fit):       # --fit_components implies the component step
+                variants.append(("fit", base + on + ["--fit_components"]))
             if not (args.off_only or args.no_islands):         # the last one: its catalog is read below
                 variants.append(("islands", base + on + ["--measure_islands"]))
             for name, argv in variants:                    # warm-up of each variant
@@ -135,13 +142,20 @@ def main():
                     for k in ("background_ms", "background_kernel_ms"):
                         res[name][k] = [round(r[k], 3) for r in rows]
                         res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                if name in ("on", "islands", "bkg", "deblend"):
+                if name == "fit":
+                    for k in ("deblend_ms", "deblend_kernel_ms", "fit_ms", "fit_kernel_ms"):
+                        res[name][k] = [round(r[k], 3) for r in rows]
+                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
+                    res[name].update({k: rows[0][k] for k in ("fit_jobs", "fit_niter_mean", "fit_niter_max")})
+                if name in ("on", "islands", "bkg", "deblend", "fit"):
                     res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
                     res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
                     res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
                     res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
             if "on" in got:
                 res["added_ms"] = res["on"]["run_ms_median"] - res["off"]["run_ms_median"]
+            if "fit" in got:
+                res["fit_added_ms"] = res["fit"]["run_ms_median"] - res["off"]["run_ms_median"]
             if "deblend" in got:
                 res["deblend_added_ms"] = res["deblend"]["run_ms_median"] - res["off"]["run_ms_median"]
             if "bkg" in got:

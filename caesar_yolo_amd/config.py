@@ -40,6 +40,7 @@ CONFIG = {
     'deblend_peak_sigma': None,        # a local peak at or above bkg + this many rms becomes a component; None: island_seed_sigma
     'deblend_radius': 2,               # a peak is the highest island pixel within this many pixels in x and y (1 .. 8)
     'fit_components': False,           # NEW: one elliptical Gaussian fitted to every component (implies deblend_islands)
+    'fit_blends': False,               # NEW: groups of touching components fitted jointly (implies fit_components)
     'fit_max_iter': 64,                # Levenberg-Marquardt iterations per component at most (1 .. 256)
     'bkg_map': False,                  # NEW: global background / noise mesh; bkg_map, rms_map, snr_map per source, island thresholds from it
     'bkg_cell': 128,                   # side of a mesh cell in pixels (4 .. 4096)

@@ -319,6 +319,31 @@ struct FitArgs {
 };
 hipError_t launch_fit(const FitArgs& a, hipStream_t s);
 
+// ---- joint fits of blends (cy_blend.hip) -----------------------------------------------------------
+constexpr int BLEND_FIELDS = 36;               // CY_BLEND_FIELDS
+constexpr int BLEND_MAX_MEMBERS = 4;           // CY_BLEND_MAX_MEMBERS
+constexpr int BLEND_CHUNK = 128;               // list entries whose residual and Jacobian rows are in LDS at a time
+constexpr int BLEND_NSUM_MAX = 325;            // F, g (24), H upper triangle (300) at four members
+struct BlendJob {
+    long long list_off;             // first list entry of the job in BlendArgs::list
+    unsigned npos;                  // list entries: window pixels whose mask byte belongs to a member, valid or not
+    int x0, y0;                     // first column / row of the box window, inside the image
+    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
+    int row0;                       // output row of the source's component 0: source * DBL_MAX_COMP
+    int M;                          // members, 2 .. BLEND_MAX_MEMBERS
+    int comp[BLEND_MAX_MEMBERS];    // their component indices, increasing; comp[0] is the group's id
+    double bkg;
+    double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the window's first pixel
+};
+struct BlendArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    const BlendJob* jobs; int njobs;
+    const unsigned* list; long long nlist;      // window indices dy * W + dx, increasing inside a job
+    int max_iter;                   // 1 .. FIT_MAX_ITER
+    double* out; int nrows;         // [nrows][BLEND_FIELDS], zeroed by the caller; the kernel writes the rows of the jobs' members
+};
+hipError_t launch_blend(const BlendArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

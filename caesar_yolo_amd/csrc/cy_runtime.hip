@@ -65,6 +65,7 @@ struct cy_ctx {
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
     double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
+    double blend_ms = -1.0;                             // ... of the last cy_fit_blends call that launched (cy_blend_kernel_ms)
     double fit_ms = -1.0;                               // ... of the last cy_fit_components call that launched (cy_fit_kernel_ms)
     double deblend_ms = -1.0;                           // ... of the last cy_deblend_islands call (cy_deblend_kernel_ms)
     double islands_ms = -1.0;                           // ... of the last cy_measure_islands call (cy_islands_kernel_ms)
@@ -1800,6 +1801,175 @@ int cy_fit_components(cy_ctx* c, const float* d_img, int MH, int MW, const doubl
 int cy_fit_kernel_ms(const cy_ctx* c, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
     *out_ms = c->fit_ms;
+    return CY_OK;
+}
+
+// ---- joint fits of blends ---------------------------------------------------------------------
+static_assert(CY_BLEND_FIELDS == BLEND_FIELDS && CY_BLEND_MAX_MEMBERS == BLEND_MAX_MEMBERS, "header and kernel disagree on the blend row");
+
+int cy_fit_blends(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_bkg, const int* h_ncomp,
+                  const double* h_start, int n, int max_iter, const unsigned char* h_mask, const long long* h_mask_off, double* h_out,
+                  void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (n < 0 || max_iter < 1 || max_iter > FIT_MAX_ITER || MH <= 0 || MW <= 0)
+        return fail(c, CY_ERR_ARG, "n >= 0, 1 <= max_iter <= 256 and MH, MW > 0 required");
+    if (n == 0) return CY_OK;
+    if (!d_img || !h_boxes || !h_bkg || !h_ncomp || !h_start || !h_mask || !h_mask_off || !h_out) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
+    // one pass over the mask bytes: the member pixels in increasing window index, the 16 x 16 adjacency bits and, from them, the
+    // groups by union-find; then the job table and every job's list, dealt out from the collected pixels in the same order
+    struct Px { unsigned q; int k; };
+    std::vector<BlendJob> jobs;
+    std::vector<unsigned> list;
+    std::vector<Px> px;
+    std::vector<unsigned> per[DBL_MAX_COMP];
+    std::vector<int> wx0((size_t)n), wy0((size_t)n);
+    std::vector<double> rows((size_t)n * DBL_MAX_COMP * CY_BLEND_FIELDS, 0.0);      // what the host itself decides: status 1, 5, 6
+    long long nmask = 0;
+    for (int i = 0; i < n; ++i) {
+        const int nc = h_ncomp[i];
+        if (nc < 0 || nc > DBL_MAX_COMP) return fail(c, CY_ERR_ARG, "h_ncomp outside 0 .. CY_DBL_MAX_COMP");
+        int w[4];
+        const double* b = h_boxes + (size_t)i * 4;
+        window_1d(b[0], b[2], MW, &w[0], &w[1]);
+        window_1d(b[1], b[3], MH, &w[2], &w[3]);
+        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
+        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
+        if (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area)
+            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
+        wx0[i] = w[0]; wy0[i] = w[2];
+        const unsigned char* m = h_mask + nmask;
+        nmask += area;
+        const bool collect = area <= FIT_MAX_AREA;            // a larger window is only checked: its rows get status 1
+        const long long W = w[1] - w[0] + 1;
+        unsigned adj[DBL_MAX_COMP] = {};
+        px.clear();
+        long long x = 0;                                      // column of q
+        for (long long q = 0; q < area; ++q, ++x) {
+            if (x == W) x = 0;
+            if (m[q] > DBL_MAX_COMP && m[q] != 255) return fail(c, CY_ERR_ARG, "mask byte in 17 .. 254");
+            const int k = (int)m[q] - 1;
+            if (!collect || k < 0 || k >= nc) continue;
+            px.push_back(Px{(unsigned)q, k});
+            // the four neighbours already passed (left, and the three of the row above); the other four see this pixel from theirs
+            const long long nb[4] = {x > 0 ? q - 1 : -1, q >= W && x > 0 ? q - W - 1 : -1, q >= W ? q - W : -1, q >= W && x + 1 < W ? q - W + 1 : -1};
+            for (int t = 0; t < 4; ++t) {
+                if (nb[t] < 0) continue;
+                const int l = (int)m[nb[t]] - 1;
+                if (l >= 0 && l < nc && l != k) { adj[k] |= 1u << l; adj[l] |= 1u << k; }
+            }
+        }
+        double* srow = &rows[(size_t)i * DBL_MAX_COMP * CY_BLEND_FIELDS];
+        if (!collect) {
+            for (int k = 0; k < nc; ++k) srow[(size_t)k * CY_BLEND_FIELDS] = 1.0;
+            continue;
+        }
+        int root[DBL_MAX_COMP];
+        for (int k = 0; k < nc; ++k) root[k] = k;
+        auto find = [&](int k) { while (root[k] != k) k = root[k] = root[root[k]]; return k; };
+        for (int k = 0; k < nc; ++k)
+            for (int l = k + 1; l < nc; ++l)
+                if (adj[k] >> l & 1u) {
+                    const int a = find(k), bb = find(l);
+                    if (a != bb) root[std::max(a, bb)] = std::min(a, bb);       // the root of a group is its lowest member
+                }
+        int slot[DBL_MAX_COMP], size[DBL_MAX_COMP] = {}, job_of[DBL_MAX_COMP];
+        for (int k = 0; k < nc; ++k) { root[k] = find(k); slot[k] = size[root[k]]++; job_of[k] = -1; }
+        const size_t first_job = jobs.size();
+        for (int k = 0; k < nc; ++k) {
+            const int g = root[k], M = size[g];
+            double* o = srow + (size_t)k * CY_BLEND_FIELDS;
+            o[5] = (double)g; o[6] = (double)M; o[7] = (double)slot[k];
+            if (M == 1) { o[0] = 6.0; continue; }
+            const double* p = h_start + ((size_t)i * DBL_MAX_COMP + k) * 6;
+            if (M > BLEND_MAX_MEMBERS) {
+                o[0] = 5.0;
+                for (int t = 0; t < 6; ++t) o[8 + t] = p[t];
+                continue;
+            }
+            if (k == g) {
+                BlendJob j{};
+                j.x0 = w[0]; j.y0 = w[2]; j.W = (unsigned)W; j.A = (unsigned)area;
+                j.row0 = i * DBL_MAX_COMP; j.M = M; j.bkg = h_bkg[i];
+                job_of[g] = (int)(jobs.size() - first_job);
+                jobs.push_back(j);
+            }
+            BlendJob& j = jobs[first_job + job_of[g]];
+            j.comp[slot[k]] = k;
+            double* q0 = j.p0 + 6 * slot[k];
+            for (int t = 0; t < 6; ++t) q0[t] = p[t];
+            q0[1] = p[1] - (double)w[0]; q0[2] = p[2] - (double)w[2];
+        }
+        const size_t njob = jobs.size() - first_job;
+        for (size_t t = 0; t < njob; ++t) per[t].clear();
+        for (const Px& e : px)
+            if (job_of[root[e.k]] >= 0) per[job_of[root[e.k]]].push_back(e.q);
+        for (size_t t = 0; t < njob; ++t) {
+            BlendJob& j = jobs[first_job + t];
+            j.list_off = (long long)list.size(); j.npos = (unsigned)per[t].size();
+            list.insert(list.end(), per[t].begin(), per[t].end());
+        }
+    }
+    const size_t out_bytes = rows.size() * sizeof(double);
+    std::memcpy(h_out, rows.data(), out_bytes);
+    if (jobs.empty()) return CY_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    EntryScratch sc;
+    void *d_jobs = nullptr, *d_list = nullptr, *d_out = nullptr;
+    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(unsigned);
+    HIPCHK(c, sc.alloc(jobs.size() * sizeof(BlendJob), &d_jobs));
+    HIPCHK(c, sc.alloc(list_bytes, &d_list));
+    HIPCHK(c, sc.alloc(out_bytes, &d_out));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(c, hipEventCreate(&e0));
+    hipError_t e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(BlendJob), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, out_bytes, st);                    // the kernel writes the members' rows only
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    if (e == hipSuccess) {
+        BlendArgs a{};
+        a.img = d_img; a.MH = MH; a.MW = MW; a.jobs = reinterpret_cast<const BlendJob*>(d_jobs); a.njobs = (int)jobs.size();
+        a.list = reinterpret_cast<const unsigned*>(d_list); a.nlist = (long long)list.size(); a.max_iter = max_iter;
+        a.out = reinterpret_cast<double*>(d_out); a.nrows = n * DBL_MAX_COMP;
+        e = launch_blend(a, st);
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    std::vector<double> got;
+    if (e == hipSuccess) {
+        got.resize(rows.size());
+        e = hipMemcpyAsync(got.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st);
+    }
+    const int rc = entry_done(c, e, st);
+    float ms = -1.0f;
+    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+    c->blend_ms = ms;
+    hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (rc != CY_OK) return rc;
+    // the members' rows: centres back in image pixels; a job that was not fitted (status 3, 4) reports its starts exactly as given
+    for (const BlendJob& j : jobs) {
+        const int src = j.row0 / DBL_MAX_COMP;
+        for (int t = 0; t < j.M; ++t) {
+            const size_t row = (size_t)j.row0 + j.comp[t];
+            const double* g = &got[row * CY_BLEND_FIELDS];
+            double* o = h_out + row * CY_BLEND_FIELDS;
+            for (int f = 0; f < CY_BLEND_FIELDS; ++f) o[f] = g[f];
+            if (g[0] == 3.0 || g[0] == 4.0) {
+                const double* p = h_start + row * 6;
+                for (int f = 0; f < 6; ++f) o[8 + f] = p[f];
+            } else {
+                o[9] = g[9] + (double)wx0[src]; o[10] = g[10] + (double)wy0[src];
+            }
+        }
+    }
+    return CY_OK;
+}
+
+int cy_blend_kernel_ms(const cy_ctx* c, double* out_ms) {
+    if (!c || !out_ms) return CY_ERR_ARG;
+    *out_ms = c->blend_ms;
     return CY_OK;
 }
 

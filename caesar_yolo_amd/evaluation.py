@@ -29,7 +29,8 @@ class Analyzer(object):
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
-        self.fit = bool(config.get('fit_components', False))            # NEW: --fit_components, one Gaussian per component (implies the components)
+        self.blends = bool(config.get('fit_blends', False))             # NEW: --fit_blends, touching components fitted jointly (implies the fits)
+        self.fit = bool(config.get('fit_components', False)) or self.blends            # NEW: --fit_components, one Gaussian per component (implies the components)
         self.deblend = bool(config.get('deblend_islands', False)) or self.fit       # NEW: --deblend_islands, the components (implies the islands)
         self.islands = bool(config.get('measure_islands', False)) or self.deblend       # NEW: --measure_islands, the second step (implies the first)
         self.bkg_map = bool(config.get('bkg_map', False)) or bool(config.get('save_bkg_maps', False))      # NEW: --bkg_map, between the two
@@ -182,9 +183,14 @@ class Analyzer(object):
                                                             self.beam_area, self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
                                                             use_map=self.bkg_map, return_raw=self.fit)
                         if self.fit:
-                            measure.fit_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], self.beam_area, self.wcs,
-                                                     box_origin=(xmin, ymin), wcs_origin=self.wcs_origin, use_map=self.bkg_map,
-                                                     max_iter=int(c.get('fit_max_iter', 64)))
+                            _, rows = measure.fit_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], self.beam_area,
+                                                               self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
+                                                               use_map=self.bkg_map, max_iter=int(c.get('fit_max_iter', 64)),
+                                                               return_pixel_rows=True)
+                            if self.blends:
+                                measure.blends_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], rows, self.beam_area,
+                                                            self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
+                                                            use_map=self.bkg_map, max_iter=int(c.get('fit_max_iter', 64)))
                 except L.CyError as e:
                     logger.warning("Source measurement failed (err=%s)..." % str(e))
                     return -1

@@ -21,6 +21,10 @@ DBL_COMP_NAMES = ("npix", "peak", "x_peak", "y_peak", "S", "Sx", "Sy", "Sxx", "S
 CY_FIT_FIELDS = 32
 FIT_NAMES = ("status", "niter", "npix", "F", "lambda", "A", "x0", "y0", "a", "b", "c") + tuple(
     "H%d%d" % (i, j) for i in range(6) for j in range(i, 6))
+CY_BLEND_FIELDS = 36
+CY_BLEND_MAX_MEMBERS = 4
+BLEND_NAMES = ("status", "niter", "npix", "F", "lambda", "group", "nmembers", "slot", "A", "x0", "y0", "a", "b", "c", "cov_ok") + tuple(
+    "C%d%d" % (i, j) for i in range(6) for j in range(i, 6))
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -36,7 +40,7 @@ EXPORTS = [
     "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
     "cy_measure_islands", "cy_islands_kernel_ms", "cy_measure_background", "cy_background_kernel_ms", "cy_expand_background",
-    "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms",
+    "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
 ]
 
 
@@ -166,6 +170,8 @@ def load():
         "cy_deblend_kernel_ms": (C.c_int, [vp, dp]),
         "cy_fit_components": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
         "cy_fit_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_fit_blends": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
+        "cy_blend_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

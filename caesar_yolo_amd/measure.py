@@ -22,6 +22,10 @@ components by local peaks and steepest-ascent basins, raw rows lib.DBL_NAMES / l
 by Levenberg-Marquardt from the start values fit_start() forms out of the component rows, raw rows lib.FIT_NAMES, keys FIT_KEYS on
 every component dict (annotate_fits).
 
+--fit_blends adds a sixth step: `cy_fit_blends` (HipDetector.fit_blends) fits the sum of the Gaussians of every group of touching
+components (blend_groups) jointly to the union of their basins, from the single fits as starts (blend_start), raw rows
+lib.BLEND_NAMES, keys BLEND_KEYS on every component dict (annotate_blends).
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
 import math
 
@@ -35,6 +39,9 @@ COMPONENT_KEYS = ("npeaks", "ncomponents", "components_truncated", "components_u
 COMPONENT_ITEM_KEYS = ("x", "y", "ra", "dec", "peak", "x_peak", "y_peak", "npix", "flux_sum", "flux", "major", "minor", "pa", "main", "nsummits")
 FIT_KEYS = ("fit_status", "fit_niter", "fit_npix", "fit_chi2", "fit_peak", "fit_x", "fit_y", "fit_ra", "fit_dec", "fit_major", "fit_minor",
             "fit_pa", "fit_flux", "fit_peak_err", "fit_x_err", "fit_y_err", "fit_flux_err")
+BLEND_KEYS = ("blend_group", "blend_size", "blend_status", "blend_niter", "blend_npix", "blend_chi2", "blend_peak", "blend_x", "blend_y",
+              "blend_ra", "blend_dec", "blend_major", "blend_minor", "blend_pa", "blend_flux", "blend_peak_err", "blend_x_err", "blend_y_err",
+              "blend_flux_err")
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
@@ -409,14 +416,15 @@ def annotate_fits(sources, fit, beam_area, wcs, origin=(0, 0), use_map=False):
 
 
 def fit_and_annotate(det, img_dev, sources, raw, comp, masks, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0), use_map=False,
-                     max_iter=64):
+                     max_iter=64, return_pixel_rows=False):
     """The fit step, after deblend_and_annotate(..., return_raw=True) on the same sources and image, whose raw rows, component rows
     and masks it takes (pixel frame of img_dev): fit_start(), one cy_fit_components call, then annotate_fits().  The background of
     a source is the one its thresholds were formed with (bkg, or bkg_map with use_map).  -> the fit rows, centres in catalog
-    coordinates."""
+    coordinates; with return_pixel_rows -> (those rows, the rows as the library gave them, in the pixel frame of img_dev: what
+    blends_and_annotate() takes)."""
     n = len(sources)
     if not n:
-        return np.zeros((0, 16, 32), np.float64)
+        return (np.zeros((0, 16, 32), np.float64),) * 2 if return_pixel_rows else np.zeros((0, 16, 32), np.float64)
     bx, by = float(box_origin[0]), float(box_origin[1])
     boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
     MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -426,12 +434,13 @@ def fit_and_annotate(det, img_dev, sources, raw, comp, masks, beam_area, wcs, bo
     ncomp = np.where(raw[:, 0] == 1.0, 0, raw[:, 3]).astype(np.int32)
     start = fit_start(np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
     fit = det.fit_components(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
+    pixel_rows = fit.copy() if return_pixel_rows else None
     if bx or by:
         has = (np.arange(fit.shape[1])[None, :] < ncomp[:, None]) & (fit[:, :, 0] != 1.0)
         fit[:, :, 6][has] += bx
         fit[:, :, 7][has] += by
     annotate_fits(sources, fit, beam_area, wcs, wcs_origin, use_map)
-    return fit
+    return (fit, pixel_rows) if return_pixel_rows else fit
 
 
 def fit_iterations(fit):
@@ -439,6 +448,137 @@ def fit_iterations(fit):
     fit = np.asarray(fit, np.float64).reshape(-1, 32)
     it = fit[(fit[:, 1] > 0) & ((fit[:, 0] == 0.0) | (fit[:, 0] == 2.0)), 1]
     return (int(it.size), float(it.mean()), int(it.max())) if it.size else (0, 0.0, 0)
+
+
+# ---- joint fits of blends (--fit_blends)
+def blend_groups(mask, h, w, ncomp):
+    """The grouping of cy_fit_blends on one mask (h x w bytes as cy_deblend_islands writes them): components k and l (< ncomp) are
+    adjacent when a pixel with byte k + 1 has a pixel with byte l + 1 among its 8 neighbours inside the window; a group is a
+    connected set of that graph.  -> int64 [ncomp, 3] {group id (lowest member), members M, slot (position among the members in
+    increasing index)}."""
+    ncomp = int(ncomp)
+    m = np.asarray(mask, np.uint8).reshape(int(h), int(w)).astype(np.int64)
+    adj = np.eye(ncomp, dtype=bool)
+    if ncomp and m.size:
+        for a, b in ((m[:, :-1], m[:, 1:]), (m[:-1, :], m[1:, :]), (m[:-1, :-1], m[1:, 1:]), (m[:-1, 1:], m[1:, :-1])):
+            ok = (a >= 1) & (a <= ncomp) & (b >= 1) & (b <= ncomp) & (a != b)
+            adj[a[ok] - 1, b[ok] - 1] = True
+            adj[b[ok] - 1, a[ok] - 1] = True
+    group = np.arange(ncomp)
+    for _ in range(ncomp):                                   # lowest index reachable: ncomp rounds reach every member of a chain
+        for k in range(ncomp):
+            group[k] = group[adj[k]].min()
+    out = np.zeros((ncomp, 3), np.int64)
+    for k in range(ncomp):
+        members = np.nonzero(group == group[k])[0]
+        out[k] = [group[k], members.size, int(np.searchsorted(members, k))]
+    return out
+
+
+def blend_start(fit_rows, comp_rows, bkg, win0):
+    """One start {A, x0, y0, a, b, c} per component for cy_fit_blends: the parameters of its cy_fit_components row (fit_rows
+    [..., 32]) when that row's status is 0 or 2, else fit_start(comp_rows, bkg, win0).  Both in the same pixel frame.
+    -> float64 [..., 6]."""
+    fit_rows = np.asarray(fit_rows, np.float64)
+    out = fit_start(comp_rows, bkg, win0)
+    use = ((fit_rows[..., 0] == 0.0) | (fit_rows[..., 0] == 2.0)) & (fit_rows[..., 1] > 0.0)     # niter 0: a row beyond ncomp
+    out[use] = fit_rows[..., 5:11][use]
+    return out
+
+
+def blend_covariance(row, rms):
+    """rms^2 times the member's 6 x 6 block of inv(H) from a blend row (lib.BLEND_NAMES); None when cov_ok is 0 or it is not finite."""
+    row = np.asarray(row, np.float64)
+    if row[14] == 0.0:
+        return None
+    C = np.zeros((6, 6), np.float64)
+    C[np.triu_indices(6)] = row[15:36]
+    C = (C + np.triu(C, 1).T) * (float(rms) * float(rms))
+    return C if np.isfinite(C).all() and (np.diag(C) >= 0.0).all() else None
+
+
+def annotate_blends(sources, rows, beam_area, wcs, origin=(0, 0), use_map=False):
+    """Adds BLEND_KEYS to every component dict of every source (in place; returns the list), after annotate_fits().  rows:
+    [n, CY_DBL_MAX_COMP, CY_BLEND_FIELDS] rows of cy_fit_blends with x0, y0 in the frame the catalog's positions are wanted in.
+      blend_group, blend_size, blend_status, blend_niter, blend_npix   group, nmembers, status, niter, npix of the row
+      blend_chi2   F / rms^2 of the job with the source's rms (rms_map with use_map); None when that is missing or 0
+      blend_peak = A, blend_x, blend_y; blend_ra, blend_dec; blend_major, blend_minor, blend_pa (gaussian_shape); blend_flux
+      (fit_flux): as their fit_ namesakes, from the member's parameters of the joint fit
+      blend_peak_err, blend_x_err, blend_y_err, blend_flux_err   from rms^2 times the member's block of C (blend_covariance),
+                 the flux by fit_flux_grad(); None without rms or with cov_ok == 0
+    Status 6 (the component is alone): blend_chi2 and the value and error keys repeat the component's fit_ values, so that one set
+    of columns describes every component.  Status 1, 3, 4 or 5: they are None.  A source whose components are None is left alone."""
+    if not sources:
+        return sources
+    rows = np.asarray(rows, np.float64).reshape(len(sources), -1, 36)     # CY_BLEND_FIELDS
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for s, br in zip(sources, rows):
+        rms = s.get("rms_map" if use_map else "rms")
+        rms = float(rms) if rms else 0.0
+        for d, r in zip(s.get("components") or [], br):
+            for k in BLEND_KEYS:
+                d[k] = None
+            st = int(r[0])
+            d["blend_group"], d["blend_size"], d["blend_status"], d["blend_niter"], d["blend_npix"] = int(r[5]), int(r[6]), st, int(r[1]), int(r[2])
+            if st == 6:
+                for k in BLEND_KEYS[5:]:
+                    d[k] = d.get("fit_" + k[6:])
+                continue
+            if st not in (0, 2):
+                continue
+            p = [float(v) for v in r[8:14]]
+            d["blend_chi2"] = float(r[3]) / (rms * rms) if rms > 0.0 else None
+            d["blend_peak"], d["blend_x"], d["blend_y"] = p[0], p[1], p[2]
+            d["blend_major"], d["blend_minor"], d["blend_pa"] = gaussian_shape(p[3], p[4], p[5])
+            if wcs is not None:
+                a, dd = wcs.wcs_pix2world(p[1] + ox, p[2] + oy, 0)
+                d["blend_ra"], d["blend_dec"] = float(a), float(dd)
+            if ba > 0.0:
+                d["blend_flux"] = fit_flux(p, ba)
+            cov = blend_covariance(r, rms) if rms > 0.0 else None
+            if cov is not None:
+                d["blend_peak_err"], d["blend_x_err"], d["blend_y_err"] = (math.sqrt(cov[k, k]) for k in range(3))
+                if ba > 0.0:
+                    g = fit_flux_grad(p, ba)
+                    d["blend_flux_err"] = math.sqrt(max(float(g @ cov @ g), 0.0))
+    return sources
+
+
+def blends_and_annotate(det, img_dev, sources, raw, comp, masks, fit_rows, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
+                        use_map=False, max_iter=64):
+    """The joint-fit step, after fit_and_annotate(..., return_pixel_rows=True) on the same sources, image, raw rows, component
+    rows and masks, whose fit rows in the pixel frame of img_dev it takes: blend_start(), one cy_fit_blends call, then
+    annotate_blends().  -> the blend rows, centres in catalog coordinates."""
+    n = len(sources)
+    if not n:
+        return np.zeros((0, 16, 36), np.float64)
+    bx, by = float(box_origin[0]), float(box_origin[1])
+    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
+    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2)
+    bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
+    raw = np.asarray(raw, np.float64).reshape(n, -1)
+    ncomp = np.where(raw[:, 0] == 1.0, 0, raw[:, 3]).astype(np.int32)
+    fit_rows = np.asarray(fit_rows, np.float64).reshape(n, -1, 32)
+    start = blend_start(fit_rows, np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
+    rows = det.fit_blends(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
+    if bx or by:
+        has = (np.arange(rows.shape[1])[None, :] < ncomp[:, None]) & np.isin(rows[:, :, 0], (0.0, 2.0, 3.0, 4.0, 5.0))
+        rows[:, :, 9][has] += bx
+        rows[:, :, 10][has] += by
+    annotate_blends(sources, rows, beam_area, wcs, wcs_origin, use_map)
+    return rows
+
+
+def blend_stats(rows):
+    """(jobs, mean niter, largest niter, groups above CY_BLEND_MAX_MEMBERS) over the rows of cy_fit_blends: a fitted job (status 0
+    or 2) is counted once, on its slot-0 row, as is a group above the limit (status 5); (0, 0.0, 0, 0) without any."""
+    rows = np.asarray(rows, np.float64).reshape(-1, 36)
+    first = rows[:, 7] == 0.0
+    it = rows[first & (rows[:, 1] > 0) & ((rows[:, 0] == 0.0) | (rows[:, 0] == 2.0)), 1]
+    over = int((first & (rows[:, 0] == 5.0)).sum())
+    return (int(it.size), float(it.mean()), int(it.max()), over) if it.size else (0, 0.0, 0, over)
 
 
 def deblend_config(config):

@@ -429,6 +429,48 @@ class HipDetector(object):
         self._chk(self.lib.cy_fit_kernel_ms(self.ctx, C.byref(ms)))
         return float(ms.value)
 
+    # ---- joint fits of blends (the sixth measurement step)
+    def fit_blends(self, img_dev, boxes, bkg, ncomp, start, masks, max_iter=64):
+        """The sum of the Gaussians of every group of touching components fitted jointly by Levenberg-Marquardt (cy_fit_blends).
+        Arguments as fit_components; start: one start per component, for instance measure.blend_start().  -> numpy float64
+        [n, CY_DBL_MAX_COMP, CY_BLEND_FIELDS] (lib.BLEND_NAMES); rows at and beyond ncomp are 0."""
+        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        n = boxes.shape[0]
+        bkg = np.ascontiguousarray(np.asarray(bkg, np.float64).reshape(-1))
+        ncomp = np.ascontiguousarray(np.asarray(ncomp).reshape(-1).astype(np.int32))
+        start = np.ascontiguousarray(np.asarray(start, np.float64).reshape(-1, L.CY_DBL_MAX_COMP, 6))
+        if bkg.shape[0] != n or ncomp.shape[0] != n or start.shape[0] != n or len(masks) != n:
+            raise L.CyError("fit_blends: %d boxes but %d bkg, %d ncomp, %d start rows and %d masks" % (
+                n, bkg.shape[0], ncomp.shape[0], start.shape[0], len(masks)))
+        if not 1 <= int(max_iter) <= 256:
+            raise L.CyError("fit_blends: max_iter must be in [1, 256]")
+        MH, MW = self._image_2d(img_dev, "fit_blends")
+        out = np.zeros((n, L.CY_DBL_MAX_COMP, L.CY_BLEND_FIELDS), np.float64)
+        if n == 0:
+            return out
+        from .measure import box_window
+        off = np.zeros(n + 1, np.int64)
+        for i, (b, m) in enumerate(zip(boxes, masks)):
+            h, w = box_window(b, MH, MW)[2:]
+            if np.asarray(m).size != h * w:
+                raise L.CyError("fit_blends: mask %d has %d bytes but the box window %d x %d" % (i, np.asarray(m).size, h, w))
+            off[i + 1] = off[i] + h * w
+        mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+        if off[-1]:
+            mask[:off[-1]] = np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in masks])
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_fit_blends(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), bkg.ctypes.data_as(dp),
+                                         ncomp.ctypes.data_as(C.POINTER(C.c_int)), start.ctypes.data_as(dp), n, int(max_iter),
+                                         C.c_void_p(mask.ctypes.data), off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                         out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def blend_kernel_ms(self):
+        """Kernel time of the last fit_blends call that launched a kernel, in ms (hipEvents around the launch); -1 before it."""
+        ms = C.c_double(-1.0)
+        self._chk(self.lib.cy_blend_kernel_ms(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def _image_2d(self, img_dev, what):
         if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:

@@ -398,6 +398,60 @@ int cy_fit_components(cy_ctx* ctx, const float* d_img, int MH, int MW,
 /* milliseconds the kernel of the last cy_fit_components call that launched one took (hipEvents around the launch); -1 before it */
 int cy_fit_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- joint fits of blends (an addition, the sixth measurement step) ---------------------------------------------------------
+ * The sum of the Gaussians of every group of touching components fitted to the union of their basins, unweighted Levenberg-
+ * Marquardt in float64.  Image, valid pixel, pixel-centre convention, box window, h_mask / h_mask_off, h_bkg, h_ncomp, the data
+ * y = (double)v - bkg, the single-Gaussian model, its Jacobian expressions and roundings (every product rounded on its own) and
+ * "admissible" are exactly those of cy_fit_components.
+ *   adjacent   components k and l (both < ncomp) of one source are adjacent when some window pixel with mask byte k + 1 has a pixel
+ *              with byte l + 1 among its 8 neighbours inside the window: always 8, whatever `conn` the islands were built with.
+ *              Bytes 0, 255 and bytes above ncomp link nothing
+ *   group      a connected set of the adjacency graph; its id is its lowest member index, its M members are taken in increasing
+ *              index and the slot of a member is its position in that order
+ *   job        one per group with 2 <= M <= CY_BLEND_MAX_MEMBERS.  Its LIST is the window pixels whose byte belongs to a member, in
+ *              increasing window index i = dy * W + dx; its pixel set is the valid pixels of the list, npix their number.  A list
+ *              entry that is not valid keeps its position and contributes nothing
+ *   model      m = (..(m_0 + m_1) + ..) + m_{M-1}, m_s = A_s * exp(-0.5 * q_s) of member s in slot order;
+ *              p = (p_0, .., p_{M-1}), P = 6 M parameters, member by member, each (A, x0, y0, a, b, c); admissible when every
+ *              member is
+ *   sweep      r = y - m; per entry the vector w = (r, J_0, .., J_{P-1}), J the members' six Jacobian entries one after the other.
+ *              F = sum w_0 w_0, g_i = sum w_0 w_{1+i}, H_ij = sum w_{1+i} w_{1+j} (i <= j): the upper triangle of w^T w row-major,
+ *              1 + P + P (P + 1) / 2 float64 sums (325 at M = 4).  ASSOCIATION: every sum is one plain sequential sum, started
+ *              at 0 and taken over the list in increasing list position, every product rounded before it is added
+ *   solve, iterate   as cy_fit_components on P parameters: Cholesky of H + lambda * diag(H) row by row, inner sums subtracted term
+ *              by term in increasing index; lambda = 1e-3, accept: max(lambda / 10, 1e-12), reject: lambda *= 10 and status 2
+ *              above 1e12; small = all P of |d_j| <= 1e-10 * (|p_j| + 1e-6); converged when small or F - F' <= 1e-14 * F;
+ *              max_iter in [1, 256]
+ *   covariance at the reported p of a status 0 or 2 job, C = inv(H): H = L L^T by the same Cholesky with lambda = 0; X = inv(L)
+ *              column by column, X_cc = 1 / L_cc, X_ic = (0 - L_ic X_cc - .. - L_i,i-1 X_i-1,c) / L_ii (terms in increasing
+ *              index); C_ij = X_ji X_jj + .. + X_P-1,i X_P-1,j (i <= j, increasing index, from 0).  A pivot that is not positive
+ *              and finite: cov_ok = 0 and the C fields are 0.  Only every member's own 6 x 6 diagonal block of C is reported
+ * h_out row of (source, component k), CY_BLEND_FIELDS float64 (rows at and beyond ncomp are 0):
+ *   [0] status   0 converged; 1 the window has more than 2^24 pixels: nothing done, every other field 0; 2 max_iter or the lambda
+ *                limit reached, the last accepted p reported; 3 npix < 6 M + 1: starts reported as given, niter = 0; 4 some member's
+ *                start is not admissible (tested before 3): starts reported as given, niter = 0; 5 the group has more than
+ *                CY_BLEND_MAX_MEMBERS members: nothing fitted, start reported as given, niter = npix = 0; 6 the component is alone
+ *                in its group: no job, group = k, nmembers = 1, every other field 0.  With 3, 4 and 5, F, lambda, cov_ok and C are 0
+ *   [1] niter, [2] npix, [3] F, [4] lambda   the job's, the same on every member's row
+ *   [5] group, [6] nmembers, [7] slot, [8..13] A x0 y0 a b c of the member (x0, y0 in image pixels; the fit runs relative to the
+ *   window), [14] cov_ok, [15..35] the upper triangle of the member's block of C, row-major
+ * The runtime finds the adjacency bits, the groups (union-find), the job table and the lists in one pass over the mask bytes; one
+ * launch (one workgroup of 256 threads per job, thread t adding sums t and t + 256 over the whole list; a job of up to 4096 list
+ * entries keeps values and indices in LDS, a larger one re-reads them) and one copy back; synchronous on `stream`.  Two calls
+ * give the same bytes.  n == 0, or no job at all: CY_OK, nothing launched.  Argument errors are exactly those of
+ * cy_fit_components.  Needs no loaded weights. */
+#define CY_BLEND_FIELDS 36
+#define CY_BLEND_MAX_MEMBERS 4
+/* status niter npix F lambda group nmembers slot A x0 y0 a b c cov_ok, then the member's block of C, upper triangle row-major (21) */
+int cy_fit_blends(cy_ctx* ctx, const float* d_img, int MH, int MW,
+                  const double* h_boxes, const double* h_bkg /* n */, const int* h_ncomp /* n */,
+                  const double* h_start /* [n][CY_DBL_MAX_COMP][6], x0 y0 in image pixels */,
+                  int n, int max_iter,
+                  const unsigned char* h_mask, const long long* h_mask_off /* n + 1 */,
+                  double* h_out /* [n][CY_DBL_MAX_COMP][CY_BLEND_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_fit_blends call that launched one took (hipEvents around the launch); -1 before it */
+int cy_blend_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

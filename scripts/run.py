@@ -37,6 +37,10 @@ Differences that come with the MI355X engine:
              the pixels of its basin, at most --fit_max_iter iterations (default 64, 1..256).  Every component also carries
              fit_status, fit_niter, fit_npix, fit_chi2, fit_peak, fit_x, fit_y, fit_ra, fit_dec, fit_major, fit_minor, fit_pa,
              fit_flux and fit_peak_err, fit_x_err, fit_y_err, fit_flux_err (cy_fit_components; DESIGN.md "Component fits").
+  --fit_blends  (new; implies --fit_components) every group of two to four touching components fitted jointly, the sum of their
+             Gaussians on the union of their basins, from the single fits as starts and with --fit_max_iter.  Every component
+             also carries blend_group, blend_size, blend_status and the blend_ namesakes of the fit_ keys (cy_fit_blends;
+             DESIGN.md "Joint fits of blends").
 """
 import argparse
 import logging
@@ -145,7 +149,11 @@ def parse_args(argv=None):
                    help='fit one elliptical Gaussian to every component on the GPU (implies --deblend_islands)')
     p.add_argument('--fit_max_iter', dest='fit_max_iter', type=int, choices=list(range(1, 257)), default=64, metavar='N',
                    help='Levenberg-Marquardt iterations per component at most, 1..256 (with --fit_components)')
+    p.add_argument('--fit_blends', dest='fit_blends', action='store_true',
+                   help='fit every group of touching components jointly on the GPU (implies --fit_components; reuses --fit_max_iter)')
     args = p.parse_args(argv)
+    if args.fit_blends:
+        args.fit_components = True
     if args.fit_components:
         args.deblend_islands = True
     if args.deblend_islands:
@@ -254,7 +262,7 @@ def main(argv=None):
               'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
               'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
               'deblend_islands': args.deblend_islands, 'deblend_peak_sigma': args.deblend_peak_sigma, 'deblend_radius': args.deblend_radius,
-              'fit_components': args.fit_components, 'fit_max_iter': args.fit_max_iter,
+              'fit_components': args.fit_components, 'fit_max_iter': args.fit_max_iter, 'fit_blends': args.fit_blends,
               'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
               'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,

@@ -941,6 +941,23 @@ int cy_profile_layers(cy_ctx* c, cy_prof_entry* out, int cap) {
     return n;
 }
 
+int cy_profile_layer_variant(cy_ctx* c, const char* conv_name, char* out, int cap) {
+    if (!c || !c->loaded || !conv_name || !out || cap < 1) return fail(c, CY_ERR_ARG, "bad arguments");
+    static const char* const extra[5] = {"stem_kernel", "pool5_kernel", "dwconv3x3_kernel", "attention_kernel", "bneck64_kernel"};
+    out[0] = 0;
+    const int n = (int)c->plan.convs.size();
+    for (int i = 0; i < n; ++i) {
+        if (c->plan.convs[i].name != conv_name) continue;
+        for (const auto& r : c->prof)                          // the last launch timed for this convolution
+            if (r.conv == i) {
+                const char* nm = r.kind < CONV_NUM_VARIANTS ? conv_variant_name(r.kind) : extra[r.kind - CONV_NUM_VARIANTS];
+                strncpy(out, nm, (size_t)cap - 1); out[cap - 1] = 0;
+            }
+        return CY_OK;
+    }
+    return fail(c, CY_ERR_ARG, std::string("no such conv: ") + conv_name);
+}
+
 int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t cap, int* dims4) {
     if (!c || !c->loaded || !conv_name || !h_out) return fail(c, CY_ERR_ARG, "bad arguments");
     if (c->lastB == 0) return fail(c, CY_ERR_STATE, "no forward has run");
@@ -949,6 +966,12 @@ int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t ca
     for (const Op& o : p.ops) {
         if (o.conv < 0 || p.convs[o.conv].name != conv_name) continue;      // pool and attention ops carry no convolution
         if (o.out < 0) return fail(c, CY_ERR_UNSUPPORTED, "head outputs are read from d_pred");
+        // the bottlenecks of one C2f share the buffer of their cv1 outputs: all but the last one's are gone after the pass
+        for (const Op* q = &o + 1; q < p.ops.data() + p.ops.size(); ++q) {
+            const int qc = q->conv >= 0 ? p.convs[q->conv].cout : q->c0;
+            if (q->out == o.out && q->out_coff < o.out_coff + p.convs[o.conv].cout && o.out_coff < q->out_coff + qc)
+                return fail(c, CY_ERR_STATE, "this layer's output was not materialised beyond its reader: a later layer of the same block reuses its buffer");
+        }
         if (c->bneck_fused_last && c->dconv[o.conv].bneck && env_knob("CY_BNECK_FUSE", 0))
             return fail(c, CY_ERR_STATE, "this bottleneck ran fused: its cv1 output was not materialised; unset CY_BNECK_FUSE");
         if (o.conv == c->pw_fused_conv && c->pw_fused_conv >= 0 && env_knob("CY_FUSE_PW", 1))

@@ -225,6 +225,13 @@ class HipDetector(object):
         n = self._chk(self.lib.cy_profile_layers(self.ctx, ent, 256))
         return [dict(name=ent[i].kernel.decode(), ms=ent[i].ms, flops=ent[i].flops, launches=ent[i].launches) for i in range(n)]
 
+    def layer_variant(self, name):
+        """Kernel variant of the last timed launch of the named convolution (profile(1) before the forward); '' when the layer
+        ran inside a neighbouring layer's kernel."""
+        buf = C.create_string_buffer(96)
+        self._chk(self.lib.cy_profile_layer_variant(self.ctx, name.encode(), buf, 96))
+        return buf.value.decode()
+
     def read_conv(self, name, shape_hint_elems):
         buf = np.zeros(shape_hint_elems, np.float32)
         dims = (C.c_int * 4)()

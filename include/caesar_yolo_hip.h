@@ -125,6 +125,9 @@ int cy_profile_summary(cy_ctx* ctx, cy_prof_entry* out, int cap);
  * a split batch), 1 = the small-batch lane, -1 = all */
 int cy_profile_summary_lane(cy_ctx* ctx, cy_prof_entry* out, int cap, int lane);
 int cy_profile_layers(cy_ctx* ctx, cy_prof_entry* out, int cap);    /* the same, one entry per convolution (graph order) */
+/* name of the kernel variant that the last timed launch of one named convolution ran (profiling enabled); an empty string when the
+ * convolution had no launch of its own (it ran inside the kernel of a neighbouring layer, or no forward was timed) */
+int cy_profile_layer_variant(cy_ctx* ctx, const char* conv_name, char* out, int cap);
 /* copy the output of one named convolution of the last cy_forward to host as fp32 [B][C][Ho][Wo] (test hook) */
 int cy_debug_read_conv(cy_ctx* ctx, const char* conv_name, float* h_out, size_t cap_elems, int* dims4);
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "cy_measure_jobs.h"
 
 namespace cy {
 
@@ -263,9 +264,7 @@ hipError_t launch_measure(const MeasureArgs& a, hipStream_t s);
 
 // ---- source islands (cy_islands.hip) ---------------------------------------------------------------
 constexpr int ISL_FIELDS = 20;                 // CY_ISL_FIELDS
-constexpr int ISL_LDS_MAX = 4096;              // largest window (pixels) whose labels live in LDS: 16 KiB of labels per workgroup
-constexpr long long ISL_MAX_AREA = 1LL << 24;  // largest supported window; a larger one gets status 1
-constexpr long long ISL_OFF_LDS = -1, ISL_OFF_TOO_LARGE = -2;
+// ISL_LDS_MAX, ISL_MAX_AREA, ISL_OFF_LDS, ISL_OFF_TOO_LARGE: cy_measure_jobs.h
 struct IslandArgs {
     const float* img; int MH, MW;   // as MeasureArgs
     const int* win;                 // [n][4] inclusive box windows {bx0, bx1, by0, by1} inside the image; bx1 < bx0 or by1 < by0 = empty
@@ -279,7 +278,7 @@ struct IslandArgs {
 hipError_t launch_islands(const IslandArgs& a, hipStream_t s);
 
 // ---- source components (cy_deblend.hip) ------------------------------------------------------------
-constexpr int DBL_FIELDS = 8, DBL_COMP_FIELDS = 12, DBL_MAX_COMP = 16;    // CY_DBL_FIELDS, CY_DBL_COMP_FIELDS, CY_DBL_MAX_COMP
+constexpr int DBL_FIELDS = 8, DBL_COMP_FIELDS = 12;    // CY_DBL_FIELDS, CY_DBL_COMP_FIELDS; DBL_MAX_COMP: cy_measure_jobs.h
 constexpr int DBL_RADIUS_MAX = 8;
 struct DeblendArgs {
     const float* img; int MH, MW;   // as MeasureArgs
@@ -296,20 +295,10 @@ struct DeblendArgs {
 hipError_t launch_deblend(const DeblendArgs& a, hipStream_t s);
 
 // ---- component fits (cy_fit.hip) -------------------------------------------------------------------
-constexpr int FIT_FIELDS = 32;                 // CY_FIT_FIELDS
+// FIT_FIELDS, FIT_MAX_AREA and struct FitJob: cy_measure_jobs.h
 constexpr int FIT_NSUM = 28;                   // F, g (6), H upper triangle (21)
 constexpr int FIT_LDS_MAX = 4096;              // largest job (list entries) whose values and indices live in LDS: 32 KiB per workgroup
 constexpr int FIT_MIN_PIX = 7, FIT_MAX_ITER = 256;
-constexpr long long FIT_MAX_AREA = 1LL << 24;  // largest supported window; the components of a larger one get status 1 from the runtime
-struct FitJob {
-    long long list_off;             // first list entry of the job in FitArgs::list
-    unsigned npos;                  // list entries: window pixels whose mask byte is the job's component + 1, valid or not
-    int x0, y0;                     // first column / row of the box window, inside the image
-    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
-    int row;                        // output row: source * DBL_MAX_COMP + component
-    double bkg;
-    double p0[6];                   // start {A, x0, y0, a, b, c}, x0 / y0 relative to the window's first pixel
-};
 struct FitArgs {
     const float* img; int MH, MW;   // as MeasureArgs
     const FitJob* jobs; int njobs;
@@ -320,21 +309,9 @@ struct FitArgs {
 hipError_t launch_fit(const FitArgs& a, hipStream_t s);
 
 // ---- joint fits of blends (cy_blend.hip) -----------------------------------------------------------
-constexpr int BLEND_FIELDS = 36;               // CY_BLEND_FIELDS
-constexpr int BLEND_MAX_MEMBERS = 4;           // CY_BLEND_MAX_MEMBERS
+// BLEND_FIELDS, BLEND_MAX_MEMBERS and struct BlendJob: cy_measure_jobs.h
 constexpr int BLEND_CHUNK = 128;               // list entries whose residual and Jacobian rows are in LDS at a time
 constexpr int BLEND_NSUM_MAX = 325;            // F, g (24), H upper triangle (300) at four members
-struct BlendJob {
-    long long list_off;             // first list entry of the job in BlendArgs::list
-    unsigned npos;                  // list entries: window pixels whose mask byte belongs to a member, valid or not
-    int x0, y0;                     // first column / row of the box window, inside the image
-    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
-    int row0;                       // output row of the source's component 0: source * DBL_MAX_COMP
-    int M;                          // members, 2 .. BLEND_MAX_MEMBERS
-    int comp[BLEND_MAX_MEMBERS];    // their component indices, increasing; comp[0] is the group's id
-    double bkg;
-    double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the window's first pixel
-};
 struct BlendArgs {
     const float* img; int MH, MW;   // as MeasureArgs
     const BlendJob* jobs; int njobs;

@@ -1,0 +1,38 @@
+// Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip) and the
+// host-side planner that fills them (cy_measure_plan.cpp).  No HIP include: the planner also builds as plain C++.
+#pragma once
+
+namespace cy {
+
+constexpr int ISL_LDS_MAX = 4096;              // largest window (pixels) whose labels live in LDS: 16 KiB of labels per workgroup
+constexpr long long ISL_MAX_AREA = 1LL << 24;  // largest supported window; a larger one gets status 1
+constexpr long long ISL_OFF_LDS = -1, ISL_OFF_TOO_LARGE = -2;
+constexpr int DBL_MAX_COMP = 16;               // CY_DBL_MAX_COMP
+constexpr int FIT_FIELDS = 32;                 // CY_FIT_FIELDS
+constexpr long long FIT_MAX_AREA = 1LL << 24;  // largest supported window; the components of a larger one get status 1 from the runtime
+constexpr int BLEND_FIELDS = 36;               // CY_BLEND_FIELDS
+constexpr int BLEND_MAX_MEMBERS = 4;           // CY_BLEND_MAX_MEMBERS
+
+struct FitJob {
+    long long list_off;             // first list entry of the job in FitArgs::list
+    unsigned npos;                  // list entries: window pixels whose mask byte is the job's component + 1, valid or not
+    int x0, y0;                     // first column / row of the box window, inside the image
+    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
+    int row;                        // output row: source * DBL_MAX_COMP + component
+    double bkg;
+    double p0[6];                   // start {A, x0, y0, a, b, c}, x0 / y0 relative to the window's first pixel
+};
+
+struct BlendJob {
+    long long list_off;             // first list entry of the job in BlendArgs::list
+    unsigned npos;                  // list entries: window pixels whose mask byte belongs to a member, valid or not
+    int x0, y0;                     // first column / row of the box window, inside the image
+    unsigned W, A;                  // width and pixel count of the window; A <= FIT_MAX_AREA
+    int row0;                       // output row of the source's component 0: source * DBL_MAX_COMP
+    int M;                          // members, 2 .. BLEND_MAX_MEMBERS
+    int comp[BLEND_MAX_MEMBERS];    // their component indices, increasing; comp[0] is the group's id
+    double bkg;
+    double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the window's first pixel
+};
+
+}  // namespace cy

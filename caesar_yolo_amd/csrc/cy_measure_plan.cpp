@@ -1,0 +1,217 @@
+// Host-side planning of the measurement entries (see cy_measure_plan.h).
+#include "cy_measure_plan.h"
+#include <algorithm>
+#include <cmath>
+
+namespace cy {
+
+namespace {
+const char* const MASK_OFF_MSG = "h_mask_off disagrees with the areas of the box windows";
+
+// Inclusive integer window [max(0, ceil(lo)), min(N - 1, floor(hi))] of a float64 box side; empty (first > last) when the side
+// misses the image or holds no pixel centre.  A NaN edge makes it empty.
+void window_1d(double lo, double hi, int N, int* first, int* last) {
+    *first = 0; *last = -1;
+    if (std::isnan(lo) || std::isnan(hi)) return;
+    const double c = std::ceil(lo), f = std::floor(hi);
+    if (c > (double)(N - 1) || f < 0.0) return;
+    *first = c > 0.0 ? (int)c : 0;
+    *last = f < (double)(N - 1) ? (int)f : N - 1;
+}
+
+// One source of the mask walk: its window, its bytes and whether its pixels are collected (a window above FIT_MAX_AREA is only checked)
+struct MaskSource { int i, nc; BoxWindow w; long long W; const unsigned char* m; bool collect; };
+
+// The pass over the mask bytes that the fit and the blend planner share.  Per source, in this order: ncomp in range, the window,
+// its claimed offsets, then every byte (17 .. 254 is no component, no 255).  pixel(s, q, x, k) gets every collected pixel of a
+// component k < ncomp in increasing window index q (x: its column); done(s) closes the source.
+template <class Pixel, class Done>
+const char* walk_masks(const FitInputs& in, std::vector<int>& win0, Pixel&& pixel, Done&& done) {
+    win0.assign((size_t)in.n * 2, 0);
+    long long nmask = 0;
+    for (int i = 0; i < in.n; ++i) {
+        MaskSource s;
+        s.i = i; s.nc = in.ncomp[i];
+        if (s.nc < 0 || s.nc > DBL_MAX_COMP) return "h_ncomp outside 0 .. CY_DBL_MAX_COMP";
+        s.w = box_window(in.boxes + (size_t)i * 4, in.MH, in.MW);
+        if (in.mask_off[i] != nmask || in.mask_off[i + 1] != nmask + s.w.area) return MASK_OFF_MSG;
+        win0[(size_t)i * 2] = s.w.x0; win0[(size_t)i * 2 + 1] = s.w.y0;
+        s.m = in.mask + nmask;
+        nmask += s.w.area;
+        s.collect = s.w.area <= FIT_MAX_AREA;
+        s.W = (long long)s.w.x1 - s.w.x0 + 1;
+        long long x = 0;
+        for (long long q = 0; q < s.w.area; ++q, ++x) {
+            if (x == s.W) x = 0;
+            if (s.m[q] > DBL_MAX_COMP && s.m[q] != 255) return "mask byte in 17 .. 254";
+            const int k = (int)s.m[q] - 1;
+            if (s.collect && k >= 0 && k < s.nc) pixel(s, q, x, k);
+        }
+        done(s);
+    }
+    return nullptr;
+}
+
+// start of component k of source i with the centre relative to the window's first pixel
+void relative_start(const FitInputs& in, const MaskSource& s, int k, double* p0) {
+    const double* p = in.start + ((size_t)s.i * DBL_MAX_COMP + k) * 6;
+    for (int t = 0; t < 6; ++t) p0[t] = p[t];
+    p0[1] = p[1] - (double)s.w.x0; p0[2] = p[2] - (double)s.w.y0;
+}
+}  // namespace
+
+BoxWindow box_window(const double* b, int MH, int MW) {
+    BoxWindow w;
+    window_1d(b[0], b[2], MW, &w.x0, &w.x1);
+    window_1d(b[1], b[3], MH, &w.y0, &w.y1);
+    if (w.x1 < w.x0 || w.y1 < w.y0) { w.x0 = w.y0 = 0; w.x1 = w.y1 = -1; }        // empty in one axis = empty
+    w.area = w.x1 < w.x0 ? 0 : (long long)(w.x1 - w.x0 + 1) * (w.y1 - w.y0 + 1);
+    return w;
+}
+
+std::vector<int> ring_windows(const double* boxes, int n, int ring, int MH, int MW) {
+    std::vector<int> win((size_t)n * 8);
+    const long long rg = ring;
+    for (int i = 0; i < n; ++i) {
+        const BoxWindow b = box_window(boxes + (size_t)i * 4, MH, MW);
+        int* w = &win[(size_t)i * 8];
+        w[0] = b.x0; w[1] = b.x1; w[2] = b.y0; w[3] = b.y1;
+        // the ring's outer window: the box window grown by `ring`, clipped to the image (an empty box window has no ring)
+        w[4] = (int)std::max(0LL, w[0] - rg); w[5] = (int)std::min((long long)MW - 1, w[1] + rg);
+        w[6] = (int)std::max(0LL, w[2] - rg); w[7] = (int)std::min((long long)MH - 1, w[3] + rg);
+    }
+    return win;
+}
+
+const char* plan_islands(const double* boxes, const double* thr, int thr_stride, const long long* mask_off, int n, int MH, int MW, IslandTable& t) {
+    t.win.assign((size_t)n * 4, 0);
+    t.off.assign((size_t)n * 2, 0);
+    t.nws = t.nmask = 0;
+    for (int i = 0; i < n; ++i) {
+        if (thr[(size_t)i * thr_stride] < thr[(size_t)i * thr_stride + 1]) return "seed_thr below merge_thr";
+        const BoxWindow b = box_window(boxes + (size_t)i * 4, MH, MW);
+        int* w = &t.win[(size_t)i * 4];
+        w[0] = b.x0; w[1] = b.x1; w[2] = b.y0; w[3] = b.y1;
+        if (mask_off && (mask_off[i] != t.nmask || mask_off[i + 1] != t.nmask + b.area)) return MASK_OFF_MSG;
+        t.off[(size_t)i * 2] = b.area > ISL_MAX_AREA ? ISL_OFF_TOO_LARGE : b.area > ISL_LDS_MAX ? t.nws : ISL_OFF_LDS;
+        t.off[(size_t)i * 2 + 1] = t.nmask;
+        if (b.area > ISL_LDS_MAX && b.area <= ISL_MAX_AREA) t.nws += b.area;
+        t.nmask += b.area;
+    }
+    return nullptr;
+}
+
+const char* plan_fit(const FitInputs& in, FitPlan& p) {
+    p.jobs.clear(); p.list.clear();
+    p.large.assign((size_t)in.n, 0);
+    std::vector<unsigned> per[DBL_MAX_COMP];                  // the pixels of the current source, by component
+    return walk_masks(in, p.win0,
+        [&](const MaskSource&, long long q, long long, int k) { per[k].push_back((unsigned)q); },
+        [&](const MaskSource& s) {
+            if (!s.collect) { p.large[s.i] = 1; return; }
+            for (int k = 0; k < s.nc; ++k) {
+                FitJob j{};
+                j.list_off = (long long)p.list.size(); j.npos = (unsigned)per[k].size();
+                j.x0 = s.w.x0; j.y0 = s.w.y0; j.W = (unsigned)s.W; j.A = (unsigned)s.w.area;
+                j.row = s.i * DBL_MAX_COMP + k; j.bkg = in.bkg[s.i];
+                relative_start(in, s, k, j.p0);
+                if (s.w.area == 0) { j.x0 = j.y0 = 0; j.W = 1; j.A = 1; }       // an empty window has no pixel: a job without a list entry
+                p.list.insert(p.list.end(), per[k].begin(), per[k].end());
+                p.jobs.push_back(j);
+                per[k].clear();
+            }
+        });
+}
+
+const char* plan_blend(const FitInputs& in, BlendPlan& p) {
+    // per source: the member pixels in increasing window index and the 16 x 16 adjacency bits; from them the groups by union-find,
+    // then the source's jobs and every job's list, dealt out from the collected pixels in the same order
+    struct Px { unsigned q; int k; };
+    p.jobs.clear(); p.list.clear();
+    p.rows.assign((size_t)in.n * DBL_MAX_COMP * BLEND_FIELDS, 0.0);
+    std::vector<Px> px;
+    std::vector<unsigned> per[DBL_MAX_COMP / 2];              // a source has at most DBL_MAX_COMP / 2 jobs (two members each)
+    unsigned adj[DBL_MAX_COMP] = {};
+    return walk_masks(in, p.win0,
+        [&](const MaskSource& s, long long q, long long x, int k) {
+            px.push_back(Px{(unsigned)q, k});
+            // the four neighbours already passed (left, and the three of the row above); the other four see this pixel from theirs
+            const long long W = s.W;
+            const long long nb[4] = {x > 0 ? q - 1 : -1, q >= W && x > 0 ? q - W - 1 : -1, q >= W ? q - W : -1, q >= W && x + 1 < W ? q - W + 1 : -1};
+            for (int t = 0; t < 4; ++t) {
+                if (nb[t] < 0) continue;
+                const int l = (int)s.m[nb[t]] - 1;
+                if (l >= 0 && l < s.nc && l != k) { adj[k] |= 1u << l; adj[l] |= 1u << k; }
+            }
+        },
+        [&](const MaskSource& s) {
+            const int nc = s.nc;
+            double* srow = &p.rows[(size_t)s.i * DBL_MAX_COMP * BLEND_FIELDS];
+            if (!s.collect) {
+                for (int k = 0; k < nc; ++k) srow[(size_t)k * BLEND_FIELDS] = 1.0;
+                return;
+            }
+            int root[DBL_MAX_COMP];
+            for (int k = 0; k < nc; ++k) root[k] = k;
+            auto find = [&](int k) { while (root[k] != k) k = root[k] = root[root[k]]; return k; };
+            for (int k = 0; k < nc; ++k)
+                for (int l = k + 1; l < nc; ++l)
+                    if (adj[k] >> l & 1u) {
+                        const int a = find(k), b = find(l);
+                        if (a != b) root[std::max(a, b)] = std::min(a, b);       // the root of a group is its lowest member
+                    }
+            int slot[DBL_MAX_COMP], size[DBL_MAX_COMP] = {}, job_of[DBL_MAX_COMP];
+            for (int k = 0; k < nc; ++k) { root[k] = find(k); slot[k] = size[root[k]]++; job_of[k] = -1; }
+            const size_t first_job = p.jobs.size();
+            for (int k = 0; k < nc; ++k) {
+                const int g = root[k], M = size[g];
+                double* o = srow + (size_t)k * BLEND_FIELDS;
+                o[5] = (double)g; o[6] = (double)M; o[7] = (double)slot[k];
+                if (M == 1) { o[0] = 6.0; continue; }
+                if (M > BLEND_MAX_MEMBERS) {
+                    o[0] = 5.0;
+                    const double* st = in.start + ((size_t)s.i * DBL_MAX_COMP + k) * 6;
+                    for (int t = 0; t < 6; ++t) o[8 + t] = st[t];
+                    continue;
+                }
+                if (k == g) {
+                    BlendJob j{};
+                    j.x0 = s.w.x0; j.y0 = s.w.y0; j.W = (unsigned)s.W; j.A = (unsigned)s.w.area;
+                    j.row0 = s.i * DBL_MAX_COMP; j.M = M; j.bkg = in.bkg[s.i];
+                    job_of[g] = (int)(p.jobs.size() - first_job);
+                    p.jobs.push_back(j);
+                }
+                BlendJob& j = p.jobs[first_job + job_of[g]];
+                j.comp[slot[k]] = k;
+                relative_start(in, s, k, j.p0 + 6 * slot[k]);
+            }
+            const size_t njob = p.jobs.size() - first_job;
+            for (const Px& e : px)
+                if (job_of[root[e.k]] >= 0) per[job_of[root[e.k]]].push_back(e.q);
+            for (size_t t = 0; t < njob; ++t) {
+                BlendJob& j = p.jobs[first_job + t];
+                j.list_off = (long long)p.list.size(); j.npos = (unsigned)per[t].size();
+                p.list.insert(p.list.end(), per[t].begin(), per[t].end());
+                per[t].clear();
+            }
+            px.clear();
+            std::fill(adj, adj + DBL_MAX_COMP, 0u);
+        });
+}
+
+void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
+    for (int r = 0; r < nrows; ++r) {
+        const size_t row = (size_t)rows[r];
+        const double* g = got + row * width;
+        double* o = out + row * width;
+        for (int f = 0; f < width; ++f) o[f] = g[f];
+        if (g[0] == 3.0 || g[0] == 4.0) {
+            for (int f = 0; f < 6; ++f) o[par + f] = start[row * 6 + f];
+        } else {
+            const int* w0 = win0 + row / DBL_MAX_COMP * 2;
+            o[par + 1] = g[par + 1] + (double)w0[0]; o[par + 2] = g[par + 2] + (double)w0[1];
+        }
+    }
+}
+
+}  // namespace cy

@@ -1,0 +1,52 @@
+// Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
+// cy_fit_blends): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
+// it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
+#pragma once
+#include "cy_measure_jobs.h"
+#include <vector>
+
+namespace cy {
+
+// Inclusive pixel window of a float64 box {x1, y1, x2, y2}: columns [max(0, ceil(x1)), min(MW - 1, floor(x2))], rows likewise with MH.
+// A side that misses the image or holds no pixel centre, or a NaN edge, makes the whole window empty: {0, -1, 0, -1}, area 0.
+struct BoxWindow { int x0, x1, y0, y1; long long area; };
+BoxWindow box_window(const double* box, int MH, int MW);
+
+// win[n][8] of MeasureArgs: the box window, then the box window grown by `ring` and clipped to the image
+std::vector<int> ring_windows(const double* boxes, int n, int ring, int MH, int MW);
+
+// win[n][4] and off[n][2] of IslandArgs / DeblendArgs.  nws: pixels of the windows labelled in the workspace (above ISL_LDS_MAX, up
+// to ISL_MAX_AREA); nmask: pixels of all windows.  thr: rows of thr_stride doubles {seed_thr, merge_thr, ..}; mask_off: [n + 1]
+// byte offsets the caller claims for the windows, checked against their areas, or null.
+struct IslandTable { std::vector<int> win; std::vector<long long> off; long long nws = 0, nmask = 0; };
+const char* plan_islands(const double* boxes, const double* thr, int thr_stride, const long long* mask_off, int n, int MH, int MW, IslandTable& t);
+
+// Inputs of cy_fit_components / cy_fit_blends: per source a box, a background, ncomp components with a start of six parameters
+// each ([n][DBL_MAX_COMP][6]) and the bytes of its window in mask, from mask_off[i] to mask_off[i + 1] (byte k + 1: component k).
+struct FitInputs {
+    int MH, MW, n;
+    const double* boxes; const double* bkg; const int* ncomp; const double* start;
+    const unsigned char* mask; const long long* mask_off;
+};
+struct FitPlan {
+    std::vector<FitJob> jobs;           // one per component of every window up to FIT_MAX_AREA pixels
+    std::vector<unsigned> list;         // the jobs' window indices, job after job, increasing inside a job
+    std::vector<int> win0;              // [n][2] first column and row of the windows
+    std::vector<char> large;            // [n] 1: window above FIT_MAX_AREA, no job; its components report status 1
+};
+const char* plan_fit(const FitInputs& in, FitPlan& p);
+struct BlendPlan {
+    std::vector<BlendJob> jobs;         // one per group of 2 .. BLEND_MAX_MEMBERS touching components
+    std::vector<unsigned> list;         // the jobs' window indices (pixels of any member), job after job, increasing inside a job
+    std::vector<int> win0;              // [n][2] as FitPlan
+    std::vector<double> rows;           // [n][DBL_MAX_COMP][BLEND_FIELDS] what the host decides: {group, members, slot} in fields 5 .. 7 of
+                                        // every component; status 1 (large window), 6 (alone), 5 with the start in fields 8 .. 13 (group above the limit)
+};
+const char* plan_blend(const FitInputs& in, BlendPlan& p);
+
+// Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
+// centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.
+void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out);
+
+}  // namespace cy

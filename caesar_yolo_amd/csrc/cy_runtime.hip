@@ -2,6 +2,7 @@
 // enqueue the gfx950 kernels.  One context per GPU / per process (one process per GPU under torch.distributed).
 #include "../../include/caesar_yolo_hip.h"
 #include "cy_kernels.h"
+#include "cy_measure_plan.h"
 #include "cy_plan.h"
 #include <algorithm>
 #include <cmath>
@@ -19,6 +20,9 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  int passes = 3;                // fp16x3 context: passes over K -- 3, or 2 when the filter is fp16-exact up to a per-channel scale (then oscale = that scale)
                  float* dw_w = nullptr;         // dw_w: depth-wise 3x3 weights [9][C] fp32 (YOLO11)
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
+
+// the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_COUNT };
 
 struct cy_ctx {
     int device = 0;
@@ -64,12 +68,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double measure_ms = -1.0;                           // kernel time of the last cy_measure_sources call (cy_measure_kernel_ms)
-    double blend_ms = -1.0;                             // ... of the last cy_fit_blends call that launched (cy_blend_kernel_ms)
-    double fit_ms = -1.0;                               // ... of the last cy_fit_components call that launched (cy_fit_kernel_ms)
-    double deblend_ms = -1.0;                           // ... of the last cy_deblend_islands call (cy_deblend_kernel_ms)
-    double islands_ms = -1.0;                           // ... of the last cy_measure_islands call (cy_islands_kernel_ms)
-    double background_ms = -1.0;                        // ... of the last cy_measure_background call (cy_background_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -123,6 +122,60 @@ int entry_done(cy_ctx* c, hipError_t e, hipStream_t s) {
     if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
     return CY_OK;
 }
+const char* const IMAGE_TOO_LARGE = "image of 2^31 pixels or more (32-bit pixel counts per window)";
+
+// One kernel launch of a measurement entry between two events on the caller's stream.  The entry names its device buffers in
+// the order it wants them allocated (upload / zeros / scratch) and its copies back (download), then calls run(): copies and memsets
+// are queued before the first event and the copies back after the second, so that the events enclose the kernel alone; run()
+// synchronises, stores the elapsed time as the step's kernel time (-1 when anything queued failed) and reports the call's first error.
+// A failure before anything is queued (device, allocation, first event) is reported with the failing call's name in front, without
+// a synchronise, and leaves the stored time as it was.
+struct TimedLaunch {
+    struct Copy { void* dst; const void* src; size_t bytes; };      // src null: zero dst
+    cy_ctx* c; hipStream_t st; hipError_t e;
+    const char* early = nullptr;                                     // the call that failed before anything was queued
+    EntryScratch sc;
+    std::vector<Copy> before, after;
+    TimedLaunch(cy_ctx* c_, void* stream) : c(c_), st((hipStream_t)stream), e(hipSetDevice(c_->device)) {
+        if (e != hipSuccess) early = "hipSetDevice(c->device)";
+    }
+    template <class T> T* scratch(size_t count) {
+        void* d = nullptr;
+        if (e == hipSuccess && (e = sc.alloc(std::max<size_t>(count, 1) * sizeof(T), &d)) != hipSuccess) early = "sc.alloc(bytes, &d)";      // an empty table still gets a buffer
+        return reinterpret_cast<T*>(d);
+    }
+    template <class T> T* upload(const T* src, size_t count) {
+        T* d = scratch<T>(count);
+        if (count) before.push_back(Copy{d, src, count * sizeof(T)});
+        return d;
+    }
+    template <class T> T* zeros(size_t count) {
+        T* d = scratch<T>(count);
+        before.push_back(Copy{d, nullptr, count * sizeof(T)});
+        return d;
+    }
+    template <class T> void download(T* host, const T* dev, size_t count) { after.push_back(Copy{host, dev, count * sizeof(T)}); }
+    template <class Launch> int run(MeasureStep step, Launch&& launch) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (e == hipSuccess && (e = hipEventCreate(&e0)) != hipSuccess) early = "hipEventCreate(&e0)";
+        if (early) return fail(c, CY_ERR_HIP, std::string(early) + ": " + hipGetErrorString(e));
+        e = hipEventCreate(&e1);
+        for (const Copy& q : before)
+            if (e == hipSuccess) e = q.src ? hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyHostToDevice, st) : hipMemsetAsync(q.dst, 0, q.bytes, st);
+        if (e == hipSuccess) e = hipEventRecord(e0, st);
+        if (e == hipSuccess) e = launch(st);
+        if (e == hipSuccess) e = hipEventRecord(e1, st);
+        for (const Copy& q : after)
+            if (e == hipSuccess) e = hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, st);
+        const int rc = entry_done(c, e, st);
+        float ms = -1.0f;
+        if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
+        c->step_ms[step] = ms;
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return rc;
+    }
+};
 inline bool ch8(int v) { return v >= 0 && v % 8 == 0; }     // channel offset / stride usable by the 8-channel vector accesses
 
 int py_round_half_even(double x) {
@@ -1494,72 +1547,31 @@ int cy_detect_counters(cy_ctx* c, long long* out4, int reset) {
     return CY_OK;
 }
 
-// ---- catalog source measurement ---------------------------------------------------------------
+// ---- measurement entries ----------------------------------------------------------------------
+// Each one: argument checks, the host-side plan (cy_measure_plan.cpp), the kernel's arguments, one TimedLaunch.
 static_assert(CY_MEAS_FIELDS == MEAS_FIELDS, "header and kernel disagree on the measurement row");
-// Inclusive integer window [max(0, ceil(lo)), min(N - 1, floor(hi))] of a float64 box side; empty (first > last) when the side
-// misses the image or holds no pixel centre.  A NaN edge makes it empty.
-static void window_1d(double lo, double hi, int N, int* first, int* last) {
-    *first = 0; *last = -1;
-    if (std::isnan(lo) || std::isnan(hi)) return;
-    const double c = std::ceil(lo), f = std::floor(hi);
-    if (c > (double)(N - 1) || f < 0.0) return;
-    *first = c > 0.0 ? (int)c : 0;
-    *last = f < (double)(N - 1) ? (int)f : N - 1;
-}
+static_assert(CY_ISL_FIELDS == ISL_FIELDS, "header and kernel disagree on the island row");
+static_assert(CY_DBL_FIELDS == DBL_FIELDS && CY_DBL_COMP_FIELDS == DBL_COMP_FIELDS && CY_DBL_MAX_COMP == DBL_MAX_COMP,
+              "header and kernel disagree on the component rows");
+static_assert(CY_FIT_FIELDS == FIT_FIELDS, "header and kernel disagree on the fit row");
+static_assert(CY_BLEND_FIELDS == BLEND_FIELDS && CY_BLEND_MAX_MEMBERS == BLEND_MAX_MEMBERS, "header and kernel disagree on the blend row");
+static_assert(CY_BKG_FIELDS == BKG_FIELDS, "header and kernel disagree on the background row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
     if (n < 0 || ring < 0 || MH <= 0 || MW <= 0) return fail(c, CY_ERR_ARG, "n >= 0, ring >= 0 and MH, MW > 0 required");
     if (n == 0) return CY_OK;
     if (!d_img || !h_boxes || !h_out) return fail(c, CY_ERR_ARG, "null argument");
-    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
-    std::vector<int> win((size_t)n * 8);
-    const long long rg = ring;
-    for (int i = 0; i < n; ++i) {
-        int* w = &win[(size_t)i * 8];
-        const double* b = h_boxes + (size_t)i * 4;
-        window_1d(b[0], b[2], MW, &w[0], &w[1]);
-        window_1d(b[1], b[3], MH, &w[2], &w[3]);
-        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }        // empty in one axis = empty
-        // the ring's outer window: the box window grown by `ring`, clipped to the image (an empty box window has no ring)
-        w[4] = (int)std::max(0LL, w[0] - rg); w[5] = (int)std::min((long long)MW - 1, w[1] + rg);
-        w[6] = (int)std::max(0LL, w[2] - rg); w[7] = (int)std::min((long long)MH - 1, w[3] + rg);
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    void *d_win = nullptr, *d_out = nullptr;
-    HIPCHK(c, sc.alloc(win.size() * sizeof(int), &d_win));
-    HIPCHK(c, sc.alloc((size_t)n * CY_MEAS_FIELDS * sizeof(double), &d_out));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        MeasureArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.win = reinterpret_cast<const int*>(d_win); a.n = n; a.out = reinterpret_cast<double*>(d_out);
-        e = launch_measure(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, (size_t)n * CY_MEAS_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st);
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->measure_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, IMAGE_TOO_LARGE);
+    const std::vector<int> win = ring_windows(h_boxes, n, ring, MH, MW);
+    TimedLaunch t(c, stream);
+    MeasureArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.n = n;
+    a.win = t.upload(win.data(), win.size());
+    a.out = t.scratch<double>((size_t)n * CY_MEAS_FIELDS);
+    t.download(h_out, a.out, (size_t)n * CY_MEAS_FIELDS);
+    return t.run(STEP_SOURCES, [&](hipStream_t s) { return launch_measure(a, s); });
 }
-
-int cy_measure_kernel_ms(const cy_ctx* c, double* out_ms) {
-    if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->measure_ms;
-    return CY_OK;
-}
-
-// ---- source islands ---------------------------------------------------------------------------
-static_assert(CY_ISL_FIELDS == ISL_FIELDS, "header and kernel disagree on the island row");
 
 int cy_measure_islands(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_thr, int n, int conn,
                        double* h_out, unsigned char* h_mask, const long long* h_mask_off, void* stream) {
@@ -1567,72 +1579,23 @@ int cy_measure_islands(cy_ctx* c, const float* d_img, int MH, int MW, const doub
     if (n < 0 || (conn != 4 && conn != 8) || MH <= 0 || MW <= 0) return fail(c, CY_ERR_ARG, "n >= 0, conn 4 or 8 and MH, MW > 0 required");
     if (n == 0) return CY_OK;
     if (!d_img || !h_boxes || !h_thr || !h_out || (h_mask && !h_mask_off)) return fail(c, CY_ERR_ARG, "null argument");
-    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
-    std::vector<int> win((size_t)n * 4);
-    std::vector<long long> off((size_t)n * 2);
-    long long nws = 0, nmask = 0;
-    for (int i = 0; i < n; ++i) {
-        if (h_thr[(size_t)i * 3] < h_thr[(size_t)i * 3 + 1]) return fail(c, CY_ERR_ARG, "seed_thr below merge_thr");
-        int* w = &win[(size_t)i * 4];
-        const double* b = h_boxes + (size_t)i * 4;
-        window_1d(b[0], b[2], MW, &w[0], &w[1]);
-        window_1d(b[1], b[3], MH, &w[2], &w[3]);
-        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
-        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
-        if (h_mask && (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area))
-            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
-        off[(size_t)i * 2] = area > ISL_MAX_AREA ? ISL_OFF_TOO_LARGE : area > ISL_LDS_MAX ? nws : ISL_OFF_LDS;
-        off[(size_t)i * 2 + 1] = nmask;
-        if (area > ISL_LDS_MAX && area <= ISL_MAX_AREA) nws += area;
-        nmask += area;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    void *d_win = nullptr, *d_off = nullptr, *d_thr = nullptr, *d_out = nullptr, *d_ws = nullptr, *d_mask = nullptr;
-    HIPCHK(c, sc.alloc(win.size() * sizeof(int), &d_win));
-    HIPCHK(c, sc.alloc(off.size() * sizeof(long long), &d_off));
-    HIPCHK(c, sc.alloc((size_t)n * 3 * sizeof(double), &d_thr));
-    HIPCHK(c, sc.alloc((size_t)n * CY_ISL_FIELDS * sizeof(double), &d_out));
-    if (nws) HIPCHK(c, sc.alloc((size_t)nws * sizeof(unsigned), &d_ws));           // every label is written before it is read: no memset
-    const bool masks = h_mask && nmask > 0;
-    if (masks) HIPCHK(c, sc.alloc((size_t)nmask, &d_mask));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_thr, h_thr, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && masks) e = hipMemsetAsync(d_mask, 0, (size_t)nmask, st);      // the kernel writes the non-zero bytes only
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        IslandArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.win = reinterpret_cast<const int*>(d_win); a.thr = reinterpret_cast<const double*>(d_thr);
-        a.off = reinterpret_cast<const long long*>(d_off); a.n = n; a.conn = conn; a.ws = reinterpret_cast<unsigned*>(d_ws);
-        a.mask = masks ? reinterpret_cast<unsigned char*>(d_mask) : nullptr; a.out = reinterpret_cast<double*>(d_out);
-        e = launch_islands(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, (size_t)n * CY_ISL_FIELDS * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && masks) e = hipMemcpyAsync(h_mask, d_mask, (size_t)nmask, hipMemcpyDeviceToHost, st);
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->islands_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, IMAGE_TOO_LARGE);
+    IslandTable tab;
+    if (const char* msg = plan_islands(h_boxes, h_thr, 3, h_mask ? h_mask_off : nullptr, n, MH, MW, tab)) return fail(c, CY_ERR_ARG, msg);
+    const bool masks = h_mask && tab.nmask > 0;
+    TimedLaunch t(c, stream);
+    IslandArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.n = n; a.conn = conn;
+    a.win = t.upload(tab.win.data(), tab.win.size());
+    a.off = t.upload(tab.off.data(), tab.off.size());
+    a.thr = t.upload(h_thr, (size_t)n * 3);
+    a.out = t.scratch<double>((size_t)n * CY_ISL_FIELDS);
+    a.ws = tab.nws ? t.scratch<unsigned>((size_t)tab.nws) : nullptr;           // every label is written before it is read: no memset
+    a.mask = masks ? t.zeros<unsigned char>((size_t)tab.nmask) : nullptr;      // the kernel writes the non-zero bytes only
+    t.download(h_out, a.out, (size_t)n * CY_ISL_FIELDS);
+    if (masks) t.download(h_mask, a.mask, (size_t)tab.nmask);
+    return t.run(STEP_ISLANDS, [&](hipStream_t s) { return launch_islands(a, s); });
 }
-
-int cy_islands_kernel_ms(const cy_ctx* c, double* out_ms) {
-    if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->islands_ms;
-    return CY_OK;
-}
-
-// ---- source components ------------------------------------------------------------------------
-static_assert(CY_DBL_FIELDS == DBL_FIELDS && CY_DBL_COMP_FIELDS == DBL_COMP_FIELDS && CY_DBL_MAX_COMP == DBL_MAX_COMP,
-              "header and kernel disagree on the component rows");
 
 int cy_deblend_islands(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_thr, int n, int conn, int radius,
                        double* h_out, double* h_comp, unsigned char* h_mask, const long long* h_mask_off, void* stream) {
@@ -1641,363 +1604,95 @@ int cy_deblend_islands(cy_ctx* c, const float* d_img, int MH, int MW, const doub
         return fail(c, CY_ERR_ARG, "n >= 0, conn 4 or 8, 1 <= radius <= 8 and MH, MW > 0 required");
     if (n == 0) return CY_OK;
     if (!d_img || !h_boxes || !h_thr || !h_out || !h_comp || (h_mask && !h_mask_off)) return fail(c, CY_ERR_ARG, "null argument");
-    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
-    std::vector<int> win((size_t)n * 4);
-    std::vector<long long> off((size_t)n * 2);
-    long long nws = 0, nmask = 0;
-    for (int i = 0; i < n; ++i) {
-        if (h_thr[(size_t)i * 4] < h_thr[(size_t)i * 4 + 1]) return fail(c, CY_ERR_ARG, "seed_thr below merge_thr");
-        int* w = &win[(size_t)i * 4];
-        const double* b = h_boxes + (size_t)i * 4;
-        window_1d(b[0], b[2], MW, &w[0], &w[1]);
-        window_1d(b[1], b[3], MH, &w[2], &w[3]);
-        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
-        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
-        if (h_mask && (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area))
-            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
-        off[(size_t)i * 2] = area > ISL_MAX_AREA ? ISL_OFF_TOO_LARGE : area > ISL_LDS_MAX ? nws : ISL_OFF_LDS;
-        off[(size_t)i * 2 + 1] = nmask;
-        if (area > ISL_LDS_MAX && area <= ISL_MAX_AREA) nws += area;
-        nmask += area;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    const size_t out_bytes = (size_t)n * CY_DBL_FIELDS * sizeof(double), comp_bytes = (size_t)n * CY_DBL_MAX_COMP * CY_DBL_COMP_FIELDS * sizeof(double);
-    void *d_win = nullptr, *d_off = nullptr, *d_thr = nullptr, *d_out = nullptr, *d_comp = nullptr, *d_ws = nullptr, *d_mask = nullptr;
-    HIPCHK(c, sc.alloc(win.size() * sizeof(int), &d_win));
-    HIPCHK(c, sc.alloc(off.size() * sizeof(long long), &d_off));
-    HIPCHK(c, sc.alloc((size_t)n * 4 * sizeof(double), &d_thr));
-    HIPCHK(c, sc.alloc(out_bytes, &d_out));
-    HIPCHK(c, sc.alloc(comp_bytes, &d_comp));
-    if (nws) HIPCHK(c, sc.alloc((size_t)nws * 2 * sizeof(unsigned), &d_ws));       // labels, then `up` words; every word is written before it is read
-    const bool masks = h_mask && nmask > 0;
-    if (masks) HIPCHK(c, sc.alloc((size_t)nmask, &d_mask));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_win, win.data(), win.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_thr, h_thr, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_comp, 0, comp_bytes, st);                  // the kernel writes the rows below ncomp only
-    if (e == hipSuccess && masks) e = hipMemsetAsync(d_mask, 0, (size_t)nmask, st);      // the kernel writes the non-zero bytes only
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        DeblendArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.win = reinterpret_cast<const int*>(d_win); a.thr = reinterpret_cast<const double*>(d_thr);
-        a.off = reinterpret_cast<const long long*>(d_off); a.n = n; a.conn = conn; a.radius = radius;
-        a.ws = reinterpret_cast<unsigned*>(d_ws); a.ws_up = d_ws ? a.ws + nws : nullptr;
-        a.mask = masks ? reinterpret_cast<unsigned char*>(d_mask) : nullptr;
-        a.out = reinterpret_cast<double*>(d_out); a.comp = reinterpret_cast<double*>(d_comp);
-        e = launch_deblend(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_comp, d_comp, comp_bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && masks) e = hipMemcpyAsync(h_mask, d_mask, (size_t)nmask, hipMemcpyDeviceToHost, st);
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->deblend_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, IMAGE_TOO_LARGE);
+    IslandTable tab;
+    if (const char* msg = plan_islands(h_boxes, h_thr, 4, h_mask ? h_mask_off : nullptr, n, MH, MW, tab)) return fail(c, CY_ERR_ARG, msg);
+    const bool masks = h_mask && tab.nmask > 0;
+    const size_t ncomp = (size_t)n * CY_DBL_MAX_COMP * CY_DBL_COMP_FIELDS;
+    TimedLaunch t(c, stream);
+    DeblendArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.n = n; a.conn = conn; a.radius = radius;
+    a.win = t.upload(tab.win.data(), tab.win.size());
+    a.off = t.upload(tab.off.data(), tab.off.size());
+    a.thr = t.upload(h_thr, (size_t)n * 4);
+    a.out = t.scratch<double>((size_t)n * CY_DBL_FIELDS);
+    a.comp = t.zeros<double>(ncomp);                                           // the kernel writes the rows below ncomp only
+    a.ws = tab.nws ? t.scratch<unsigned>((size_t)tab.nws * 2) : nullptr;       // labels, then `up` words; every word is written before it is read
+    a.ws_up = a.ws ? a.ws + tab.nws : nullptr;
+    a.mask = masks ? t.zeros<unsigned char>((size_t)tab.nmask) : nullptr;      // the kernel writes the non-zero bytes only
+    t.download(h_out, a.out, (size_t)n * CY_DBL_FIELDS);
+    t.download(h_comp, a.comp, ncomp);
+    if (masks) t.download(h_mask, a.mask, (size_t)tab.nmask);
+    return t.run(STEP_DEBLEND, [&](hipStream_t s) { return launch_deblend(a, s); });
 }
 
-int cy_deblend_kernel_ms(const cy_ctx* c, double* out_ms) {
-    if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->deblend_ms;
-    return CY_OK;
+// the argument checks cy_fit_components and cy_fit_blends share: the call's result, or FIT_GO_ON when there is something to plan
+constexpr int FIT_GO_ON = 1;
+static int fit_arguments(cy_ctx* c, const void* d_img, const FitInputs& in, int max_iter, const void* h_out) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (in.n < 0 || max_iter < 1 || max_iter > FIT_MAX_ITER || in.MH <= 0 || in.MW <= 0)
+        return fail(c, CY_ERR_ARG, "n >= 0, 1 <= max_iter <= 256 and MH, MW > 0 required");
+    if (in.n == 0) return CY_OK;
+    if (!d_img || !in.boxes || !in.bkg || !in.ncomp || !in.start || !in.mask || !in.mask_off || !h_out) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)in.MH * in.MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, IMAGE_TOO_LARGE);
+    return FIT_GO_ON;
 }
-
-// ---- component fits ---------------------------------------------------------------------------
-static_assert(CY_FIT_FIELDS == FIT_FIELDS, "header and kernel disagree on the fit row");
 
 int cy_fit_components(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_bkg, const int* h_ncomp,
                       const double* h_start, int n, int max_iter, const unsigned char* h_mask, const long long* h_mask_off, double* h_fit,
                       void* stream) {
-    if (!c) return fail(c, CY_ERR_ARG, "null argument");
-    if (n < 0 || max_iter < 1 || max_iter > FIT_MAX_ITER || MH <= 0 || MW <= 0)
-        return fail(c, CY_ERR_ARG, "n >= 0, 1 <= max_iter <= 256 and MH, MW > 0 required");
-    if (n == 0) return CY_OK;
-    if (!d_img || !h_boxes || !h_bkg || !h_ncomp || !h_start || !h_mask || !h_mask_off || !h_fit) return fail(c, CY_ERR_ARG, "null argument");
-    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
-    // one pass over the mask bytes: the job table and, per job, the window indices of its pixels in increasing order
-    std::vector<FitJob> jobs;
-    std::vector<unsigned> list;
-    std::vector<unsigned> per[DBL_MAX_COMP];
-    std::vector<int> wx0((size_t)n), wy0((size_t)n);
-    std::vector<char> large((size_t)n, 0);
-    long long nmask = 0;
-    for (int i = 0; i < n; ++i) {
-        const int nc = h_ncomp[i];
-        if (nc < 0 || nc > DBL_MAX_COMP) return fail(c, CY_ERR_ARG, "h_ncomp outside 0 .. CY_DBL_MAX_COMP");
-        int w[4];
-        const double* b = h_boxes + (size_t)i * 4;
-        window_1d(b[0], b[2], MW, &w[0], &w[1]);
-        window_1d(b[1], b[3], MH, &w[2], &w[3]);
-        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
-        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
-        if (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area)
-            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
-        wx0[i] = w[0]; wy0[i] = w[2];
-        const unsigned char* m = h_mask + nmask;
-        nmask += area;
-        const bool collect = area <= FIT_MAX_AREA;            // a larger window is only checked: its rows get status 1
-        for (int k = 0; k < nc; ++k) per[k].clear();
-        for (long long q = 0; q < area; ++q) {
-            if (m[q] > DBL_MAX_COMP && m[q] != 255) return fail(c, CY_ERR_ARG, "mask byte in 17 .. 254");
-            const int k = (int)m[q] - 1;
-            if (collect && k >= 0 && k < nc) per[k].push_back((unsigned)q);
-        }
-        if (!collect) { large[i] = 1; continue; }
-        for (int k = 0; k < nc; ++k) {
-            FitJob j{};
-            j.list_off = (long long)list.size(); j.npos = (unsigned)per[k].size();
-            j.x0 = w[0]; j.y0 = w[2]; j.W = (unsigned)(w[1] - w[0] + 1); j.A = (unsigned)area;
-            j.row = i * DBL_MAX_COMP + k; j.bkg = h_bkg[i];
-            const double* p = h_start + ((size_t)i * DBL_MAX_COMP + k) * 6;
-            for (int t = 0; t < 6; ++t) j.p0[t] = p[t];
-            j.p0[1] = p[1] - (double)w[0]; j.p0[2] = p[2] - (double)w[2];
-            if (area == 0) { j.x0 = j.y0 = 0; j.W = 1; j.A = 1; }       // an empty window has no pixel: a job without a list entry
-            list.insert(list.end(), per[k].begin(), per[k].end());
-            jobs.push_back(j);
-        }
-    }
-    const size_t fit_bytes = (size_t)n * DBL_MAX_COMP * CY_FIT_FIELDS * sizeof(double);
-    std::memset(h_fit, 0, fit_bytes);
+    const FitInputs in{MH, MW, n, h_boxes, h_bkg, h_ncomp, h_start, h_mask, h_mask_off};
+    int rc = fit_arguments(c, d_img, in, max_iter, h_fit);
+    if (rc != FIT_GO_ON) return rc;
+    FitPlan p;
+    if (const char* msg = plan_fit(in, p)) return fail(c, CY_ERR_ARG, msg);
+    const size_t nrows = (size_t)n * DBL_MAX_COMP;
+    std::memset(h_fit, 0, nrows * CY_FIT_FIELDS * sizeof(double));
     for (int i = 0; i < n; ++i)
-        if (large[i])
+        if (p.large[i])
             for (int k = 0; k < h_ncomp[i]; ++k) h_fit[((size_t)i * DBL_MAX_COMP + k) * CY_FIT_FIELDS] = 1.0;
-    if (jobs.empty()) return CY_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    void *d_jobs = nullptr, *d_list = nullptr, *d_out = nullptr;
-    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(unsigned);
-    HIPCHK(c, sc.alloc(jobs.size() * sizeof(FitJob), &d_jobs));
-    HIPCHK(c, sc.alloc(list_bytes, &d_list));
-    HIPCHK(c, sc.alloc(fit_bytes, &d_out));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(FitJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, fit_bytes, st);                    // the kernel writes the jobs' rows only
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        FitArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.jobs = reinterpret_cast<const FitJob*>(d_jobs); a.njobs = (int)jobs.size();
-        a.list = reinterpret_cast<const unsigned*>(d_list); a.nlist = (long long)list.size(); a.max_iter = max_iter;
-        a.out = reinterpret_cast<double*>(d_out); a.nrows = n * DBL_MAX_COMP;
-        e = launch_fit(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    std::vector<double> got;
-    if (e == hipSuccess) {
-        got.resize((size_t)n * DBL_MAX_COMP * CY_FIT_FIELDS);
-        e = hipMemcpyAsync(got.data(), d_out, fit_bytes, hipMemcpyDeviceToHost, st);
-    }
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->fit_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
+    if (p.jobs.empty()) return CY_OK;
+    std::vector<double> got(nrows * CY_FIT_FIELDS);
+    TimedLaunch t(c, stream);
+    FitArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.njobs = (int)p.jobs.size(); a.nlist = (long long)p.list.size(); a.max_iter = max_iter;
+    a.jobs = t.upload(p.jobs.data(), p.jobs.size());
+    a.list = t.upload(p.list.data(), p.list.size());
+    a.out = t.zeros<double>(got.size()); a.nrows = (int)nrows;                 // the kernel writes the jobs' rows only
+    t.download(got.data(), a.out, got.size());
+    rc = t.run(STEP_FIT, [&](hipStream_t s) { return launch_fit(a, s); });
     if (rc != CY_OK) return rc;
-    // the jobs' rows: centres back in image pixels; a job that was not fitted (status 3, 4) reports its start exactly as given
-    for (const FitJob& j : jobs) {
-        const double* g = &got[(size_t)j.row * CY_FIT_FIELDS];
-        double* o = h_fit + (size_t)j.row * CY_FIT_FIELDS;
-        for (int t = 0; t < CY_FIT_FIELDS; ++t) o[t] = g[t];
-        const int src = j.row / DBL_MAX_COMP;
-        if (g[0] == 3.0 || g[0] == 4.0) {
-            const double* p = h_start + (size_t)j.row * 6;
-            for (int t = 0; t < 6; ++t) o[5 + t] = p[t];
-        } else {
-            o[6] = g[6] + (double)wx0[src]; o[7] = g[7] + (double)wy0[src];
-        }
-    }
+    for (const FitJob& j : p.jobs) write_back(got.data(), h_start, p.win0.data(), CY_FIT_FIELDS, 5, &j.row, 1, h_fit);
     return CY_OK;
 }
-
-int cy_fit_kernel_ms(const cy_ctx* c, double* out_ms) {
-    if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->fit_ms;
-    return CY_OK;
-}
-
-// ---- joint fits of blends ---------------------------------------------------------------------
-static_assert(CY_BLEND_FIELDS == BLEND_FIELDS && CY_BLEND_MAX_MEMBERS == BLEND_MAX_MEMBERS, "header and kernel disagree on the blend row");
 
 int cy_fit_blends(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, const double* h_bkg, const int* h_ncomp,
                   const double* h_start, int n, int max_iter, const unsigned char* h_mask, const long long* h_mask_off, double* h_out,
                   void* stream) {
-    if (!c) return fail(c, CY_ERR_ARG, "null argument");
-    if (n < 0 || max_iter < 1 || max_iter > FIT_MAX_ITER || MH <= 0 || MW <= 0)
-        return fail(c, CY_ERR_ARG, "n >= 0, 1 <= max_iter <= 256 and MH, MW > 0 required");
-    if (n == 0) return CY_OK;
-    if (!d_img || !h_boxes || !h_bkg || !h_ncomp || !h_start || !h_mask || !h_mask_off || !h_out) return fail(c, CY_ERR_ARG, "null argument");
-    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per window)");
-    // one pass over the mask bytes: the member pixels in increasing window index, the 16 x 16 adjacency bits and, from them, the
-    // groups by union-find; then the job table and every job's list, dealt out from the collected pixels in the same order
-    struct Px { unsigned q; int k; };
-    std::vector<BlendJob> jobs;
-    std::vector<unsigned> list;
-    std::vector<Px> px;
-    std::vector<unsigned> per[DBL_MAX_COMP];
-    std::vector<int> wx0((size_t)n), wy0((size_t)n);
-    std::vector<double> rows((size_t)n * DBL_MAX_COMP * CY_BLEND_FIELDS, 0.0);      // what the host itself decides: status 1, 5, 6
-    long long nmask = 0;
-    for (int i = 0; i < n; ++i) {
-        const int nc = h_ncomp[i];
-        if (nc < 0 || nc > DBL_MAX_COMP) return fail(c, CY_ERR_ARG, "h_ncomp outside 0 .. CY_DBL_MAX_COMP");
-        int w[4];
-        const double* b = h_boxes + (size_t)i * 4;
-        window_1d(b[0], b[2], MW, &w[0], &w[1]);
-        window_1d(b[1], b[3], MH, &w[2], &w[3]);
-        if (w[1] < w[0] || w[3] < w[2]) { w[0] = w[2] = 0; w[1] = w[3] = -1; }
-        const long long area = w[1] < w[0] ? 0 : (long long)(w[1] - w[0] + 1) * (w[3] - w[2] + 1);
-        if (h_mask_off[i] != nmask || h_mask_off[i + 1] != nmask + area)
-            return fail(c, CY_ERR_ARG, "h_mask_off disagrees with the areas of the box windows");
-        wx0[i] = w[0]; wy0[i] = w[2];
-        const unsigned char* m = h_mask + nmask;
-        nmask += area;
-        const bool collect = area <= FIT_MAX_AREA;            // a larger window is only checked: its rows get status 1
-        const long long W = w[1] - w[0] + 1;
-        unsigned adj[DBL_MAX_COMP] = {};
-        px.clear();
-        long long x = 0;                                      // column of q
-        for (long long q = 0; q < area; ++q, ++x) {
-            if (x == W) x = 0;
-            if (m[q] > DBL_MAX_COMP && m[q] != 255) return fail(c, CY_ERR_ARG, "mask byte in 17 .. 254");
-            const int k = (int)m[q] - 1;
-            if (!collect || k < 0 || k >= nc) continue;
-            px.push_back(Px{(unsigned)q, k});
-            // the four neighbours already passed (left, and the three of the row above); the other four see this pixel from theirs
-            const long long nb[4] = {x > 0 ? q - 1 : -1, q >= W && x > 0 ? q - W - 1 : -1, q >= W ? q - W : -1, q >= W && x + 1 < W ? q - W + 1 : -1};
-            for (int t = 0; t < 4; ++t) {
-                if (nb[t] < 0) continue;
-                const int l = (int)m[nb[t]] - 1;
-                if (l >= 0 && l < nc && l != k) { adj[k] |= 1u << l; adj[l] |= 1u << k; }
-            }
-        }
-        double* srow = &rows[(size_t)i * DBL_MAX_COMP * CY_BLEND_FIELDS];
-        if (!collect) {
-            for (int k = 0; k < nc; ++k) srow[(size_t)k * CY_BLEND_FIELDS] = 1.0;
-            continue;
-        }
-        int root[DBL_MAX_COMP];
-        for (int k = 0; k < nc; ++k) root[k] = k;
-        auto find = [&](int k) { while (root[k] != k) k = root[k] = root[root[k]]; return k; };
-        for (int k = 0; k < nc; ++k)
-            for (int l = k + 1; l < nc; ++l)
-                if (adj[k] >> l & 1u) {
-                    const int a = find(k), bb = find(l);
-                    if (a != bb) root[std::max(a, bb)] = std::min(a, bb);       // the root of a group is its lowest member
-                }
-        int slot[DBL_MAX_COMP], size[DBL_MAX_COMP] = {}, job_of[DBL_MAX_COMP];
-        for (int k = 0; k < nc; ++k) { root[k] = find(k); slot[k] = size[root[k]]++; job_of[k] = -1; }
-        const size_t first_job = jobs.size();
-        for (int k = 0; k < nc; ++k) {
-            const int g = root[k], M = size[g];
-            double* o = srow + (size_t)k * CY_BLEND_FIELDS;
-            o[5] = (double)g; o[6] = (double)M; o[7] = (double)slot[k];
-            if (M == 1) { o[0] = 6.0; continue; }
-            const double* p = h_start + ((size_t)i * DBL_MAX_COMP + k) * 6;
-            if (M > BLEND_MAX_MEMBERS) {
-                o[0] = 5.0;
-                for (int t = 0; t < 6; ++t) o[8 + t] = p[t];
-                continue;
-            }
-            if (k == g) {
-                BlendJob j{};
-                j.x0 = w[0]; j.y0 = w[2]; j.W = (unsigned)W; j.A = (unsigned)area;
-                j.row0 = i * DBL_MAX_COMP; j.M = M; j.bkg = h_bkg[i];
-                job_of[g] = (int)(jobs.size() - first_job);
-                jobs.push_back(j);
-            }
-            BlendJob& j = jobs[first_job + job_of[g]];
-            j.comp[slot[k]] = k;
-            double* q0 = j.p0 + 6 * slot[k];
-            for (int t = 0; t < 6; ++t) q0[t] = p[t];
-            q0[1] = p[1] - (double)w[0]; q0[2] = p[2] - (double)w[2];
-        }
-        const size_t njob = jobs.size() - first_job;
-        for (size_t t = 0; t < njob; ++t) per[t].clear();
-        for (const Px& e : px)
-            if (job_of[root[e.k]] >= 0) per[job_of[root[e.k]]].push_back(e.q);
-        for (size_t t = 0; t < njob; ++t) {
-            BlendJob& j = jobs[first_job + t];
-            j.list_off = (long long)list.size(); j.npos = (unsigned)per[t].size();
-            list.insert(list.end(), per[t].begin(), per[t].end());
-        }
-    }
-    const size_t out_bytes = rows.size() * sizeof(double);
-    std::memcpy(h_out, rows.data(), out_bytes);
-    if (jobs.empty()) return CY_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    void *d_jobs = nullptr, *d_list = nullptr, *d_out = nullptr;
-    const size_t list_bytes = std::max<size_t>(list.size(), 1) * sizeof(unsigned);
-    HIPCHK(c, sc.alloc(jobs.size() * sizeof(BlendJob), &d_jobs));
-    HIPCHK(c, sc.alloc(list_bytes, &d_list));
-    HIPCHK(c, sc.alloc(out_bytes, &d_out));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(BlendJob), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !list.empty()) e = hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(unsigned), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, out_bytes, st);                    // the kernel writes the members' rows only
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        BlendArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.jobs = reinterpret_cast<const BlendJob*>(d_jobs); a.njobs = (int)jobs.size();
-        a.list = reinterpret_cast<const unsigned*>(d_list); a.nlist = (long long)list.size(); a.max_iter = max_iter;
-        a.out = reinterpret_cast<double*>(d_out); a.nrows = n * DBL_MAX_COMP;
-        e = launch_blend(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    std::vector<double> got;
-    if (e == hipSuccess) {
-        got.resize(rows.size());
-        e = hipMemcpyAsync(got.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st);
-    }
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->blend_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
+    const FitInputs in{MH, MW, n, h_boxes, h_bkg, h_ncomp, h_start, h_mask, h_mask_off};
+    int rc = fit_arguments(c, d_img, in, max_iter, h_out);
+    if (rc != FIT_GO_ON) return rc;
+    BlendPlan p;
+    if (const char* msg = plan_blend(in, p)) return fail(c, CY_ERR_ARG, msg);
+    std::memcpy(h_out, p.rows.data(), p.rows.size() * sizeof(double));
+    if (p.jobs.empty()) return CY_OK;
+    std::vector<double> got(p.rows.size());
+    TimedLaunch t(c, stream);
+    BlendArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.njobs = (int)p.jobs.size(); a.nlist = (long long)p.list.size(); a.max_iter = max_iter;
+    a.jobs = t.upload(p.jobs.data(), p.jobs.size());
+    a.list = t.upload(p.list.data(), p.list.size());
+    a.out = t.zeros<double>(got.size()); a.nrows = n * DBL_MAX_COMP;           // the kernel writes the members' rows only
+    t.download(got.data(), a.out, got.size());
+    rc = t.run(STEP_BLEND, [&](hipStream_t s) { return launch_blend(a, s); });
     if (rc != CY_OK) return rc;
-    // the members' rows: centres back in image pixels; a job that was not fitted (status 3, 4) reports its starts exactly as given
-    for (const BlendJob& j : jobs) {
-        const int src = j.row0 / DBL_MAX_COMP;
-        for (int t = 0; t < j.M; ++t) {
-            const size_t row = (size_t)j.row0 + j.comp[t];
-            const double* g = &got[row * CY_BLEND_FIELDS];
-            double* o = h_out + row * CY_BLEND_FIELDS;
-            for (int f = 0; f < CY_BLEND_FIELDS; ++f) o[f] = g[f];
-            if (g[0] == 3.0 || g[0] == 4.0) {
-                const double* p = h_start + row * 6;
-                for (int f = 0; f < 6; ++f) o[8 + f] = p[f];
-            } else {
-                o[9] = g[9] + (double)wx0[src]; o[10] = g[10] + (double)wy0[src];
-            }
-        }
+    for (const BlendJob& j : p.jobs) {
+        int rows[BLEND_MAX_MEMBERS];
+        for (int m = 0; m < j.M; ++m) rows[m] = j.row0 + j.comp[m];
+        write_back(got.data(), h_start, p.win0.data(), CY_BLEND_FIELDS, 8, rows, j.M, h_out);
     }
     return CY_OK;
 }
-
-int cy_blend_kernel_ms(const cy_ctx* c, double* out_ms) {
-    if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->blend_ms;
-    return CY_OK;
-}
-
-// ---- background and noise mesh ----------------------------------------------------------------
-static_assert(CY_BKG_FIELDS == BKG_FIELDS, "header and kernel disagree on the background row");
 
 int cy_measure_background(cy_ctx* c, const float* d_img, int MH, int MW, int cell, double k, int niter, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -2005,39 +1700,27 @@ int cy_measure_background(cy_ctx* c, const float* d_img, int MH, int MW, int cel
         return fail(c, CY_ERR_ARG, "MH, MW > 0, 4 <= cell <= 4096, k > 0 and 0 <= niter <= 32 required");
     if (!d_img || !h_out) return fail(c, CY_ERR_ARG, "null argument");
     if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more (32-bit pixel counts per cell)");
-    const int ncx = (MW + cell - 1) / cell, ncy = (MH + cell - 1) / cell;
-    const size_t bytes = (size_t)ncy * ncx * CY_BKG_FIELDS * sizeof(double);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
-    void* d_out = nullptr;
-    HIPCHK(c, sc.alloc(bytes, &d_out));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    if (e == hipSuccess) {
-        BackgroundArgs a{};
-        a.img = d_img; a.MH = MH; a.MW = MW; a.cell = cell; a.ncy = ncy; a.ncx = ncx; a.k = k; a.niter = niter;
-        a.out = reinterpret_cast<double*>(d_out);
-        e = launch_background(a, st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, bytes, hipMemcpyDeviceToHost, st);
-    const int rc = entry_done(c, e, st);
-    float ms = -1.0f;
-    if (rc == CY_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = -1.0f;
-    c->background_ms = ms;
-    hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    return rc;
+    TimedLaunch t(c, stream);
+    BackgroundArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.cell = cell; a.ncy = (MH + cell - 1) / cell; a.ncx = (MW + cell - 1) / cell; a.k = k; a.niter = niter;
+    const size_t nout = (size_t)a.ncy * a.ncx * CY_BKG_FIELDS;
+    a.out = t.scratch<double>(nout);
+    t.download(h_out, a.out, nout);
+    return t.run(STEP_BACKGROUND, [&](hipStream_t s) { return launch_background(a, s); });
 }
 
-int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) {
+// kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
+static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
-    *out_ms = c->background_ms;
+    *out_ms = c->step_ms[step];
     return CY_OK;
 }
+int cy_measure_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_SOURCES, out_ms); }
+int cy_islands_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_ISLANDS, out_ms); }
+int cy_deblend_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_DEBLEND, out_ms); }
+int cy_fit_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_FIT, out_ms); }
+int cy_blend_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_BLEND, out_ms); }
+int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_BACKGROUND, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

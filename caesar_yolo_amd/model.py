@@ -299,25 +299,57 @@ class HipDetector(object):
         return {"degenerate_boxes": int(out[0]), "cand_overflow_tiles": int(out[1]), "median_bracket_hits": int(out[2]),
                 "median_bracket_misses": int(out[3])}
 
-    # ---- catalog source measurement (an addition to the reference's catalog)
+    # ---- measurement steps (an addition to the reference's catalog): helpers shared by the methods below
+    def _image_2d(self, img_dev, what):
+        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
+            raise L.CyError("%s: a contiguous 2-D float32 image on %s is required" % (what, self.tdev))
+        return int(img_dev.shape[0]), int(img_dev.shape[1])
+
+    @staticmethod
+    def _boxes4(boxes):
+        return np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+
+    @staticmethod
+    def _mask_layout(boxes, MH, MW):
+        """-> (shapes [(h, w)] of the box windows, off int64 [n + 1]: first byte of every window in one buffer of all of them)."""
+        from .measure import box_window
+        shapes = [box_window(b, MH, MW)[2:] for b in boxes]
+        off = np.zeros(len(shapes) + 1, np.int64)
+        np.cumsum([h * w for h, w in shapes], out=off[1:])
+        return shapes, off
+
+    def _pack_masks(self, what, boxes, masks, MH, MW):
+        """The window masks of the boxes in one buffer -> (mask uint8 of at least one byte, off as _mask_layout)."""
+        shapes, off = self._mask_layout(boxes, MH, MW)
+        for i, ((h, w), m) in enumerate(zip(shapes, masks)):
+            if np.asarray(m).size != h * w:
+                raise L.CyError("%s: mask %d has %d bytes but the box window %d x %d" % (what, i, np.asarray(m).size, h, w))
+        mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+        if off[-1]:
+            mask[:off[-1]] = np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in masks])
+        return mask, off
+
+    def _kernel_ms(self, fn):
+        ms = C.c_double(-1.0)
+        self._chk(fn(self.ctx, C.byref(ms)))
+        return float(ms.value)
+
+    # ---- catalog source measurement
     def measure_sources(self, img_dev, boxes, ring=8):
         """img_dev: device fp32 image [MH, MW] as mosaic_to_device leaves it; boxes: [n, 4] float64 {x1, y1, x2, y2} in its 0-based
         pixels (they may leave the image).  -> numpy float64 [n, CY_MEAS_FIELDS] (lib.MEAS_NAMES), cy_measure_sources."""
-        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        boxes = self._boxes4(boxes)
         n = boxes.shape[0]
         out = np.zeros((n, L.CY_MEAS_FIELDS), np.float64)
-        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
-            raise L.CyError("measure_sources: a contiguous 2-D float32 image on %s is required" % (self.tdev,))
+        MH, MW = self._image_2d(img_dev, "measure_sources")
         dp = C.POINTER(C.c_double)
-        self._chk(self.lib.cy_measure_sources(self.ctx, self._p(img_dev), int(img_dev.shape[0]), int(img_dev.shape[1]),
-                                              boxes.ctypes.data_as(dp), n, int(ring), out.ctypes.data_as(dp), self._stream()))
+        self._chk(self.lib.cy_measure_sources(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), n, int(ring),
+                                              out.ctypes.data_as(dp), self._stream()))
         return out
 
     def measure_kernel_ms(self):
         """Kernel time of the last measure_sources call in ms (hipEvents around the launch); -1 before the first."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_measure_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_measure_kernel_ms)
 
     # ---- source islands (the second measurement step)
     def measure_islands(self, img_dev, boxes, thr, conn=8, return_masks=False):
@@ -325,35 +357,33 @@ class HipDetector(object):
         float64 {seed_thr, merge_thr, bkg} per source.  -> numpy float64 [n, CY_ISL_FIELDS] (lib.ISL_NAMES); with return_masks
         also a list of n uint8 arrays shaped like the box windows (0 outside the island set, 1 in it, 2 in the main island; an
         empty window gives an array of shape (0, 0))."""
-        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        boxes = self._boxes4(boxes)
         thr = np.ascontiguousarray(np.asarray(thr, np.float64).reshape(-1, 3))
         n = boxes.shape[0]
         if thr.shape[0] != n:
             raise L.CyError("measure_islands: %d boxes but %d threshold rows" % (n, thr.shape[0]))
         out = np.zeros((n, L.CY_ISL_FIELDS), np.float64)
-        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
-            raise L.CyError("measure_islands: a contiguous 2-D float32 image on %s is required" % (self.tdev,))
-        MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+        MH, MW = self._image_2d(img_dev, "measure_islands")
+        masks = self._island_call(self.lib.cy_measure_islands, img_dev, MH, MW, boxes, thr, (int(conn),), (out,), return_masks)
+        return (out, masks) if return_masks else out
+
+    def _island_call(self, entry, img_dev, MH, MW, boxes, thr, params, outs, return_masks):
+        """cy_measure_islands / cy_deblend_islands: (.., boxes, thr, n, *params, *outs, mask, mask offsets, stream).  -> the window
+        masks, or None when they are not wanted."""
         dp = C.POINTER(C.c_double)
-        mask = off = shapes = None
+        mask = off = None
         if return_masks:
-            from .measure import box_window
-            shapes = [box_window(b, MH, MW)[2:] for b in boxes]
-            off = np.zeros(n + 1, np.int64)
-            np.cumsum([h * w for h, w in shapes], out=off[1:])
+            shapes, off = self._mask_layout(boxes, MH, MW)
             mask = np.zeros(max(int(off[-1]), 1), np.uint8)
-        self._chk(self.lib.cy_measure_islands(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), thr.ctypes.data_as(dp), n, int(conn),
-                                              out.ctypes.data_as(dp), C.c_void_p(mask.ctypes.data) if return_masks else None,
-                                              off.ctypes.data_as(C.POINTER(C.c_longlong)) if return_masks else None, self._stream()))
-        if not return_masks:
-            return out
-        return out, [mask[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(n)]
+        self._chk(entry(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), thr.ctypes.data_as(dp), boxes.shape[0], *params,
+                        *[o.ctypes.data_as(dp) for o in outs], C.c_void_p(mask.ctypes.data) if return_masks else None,
+                        off.ctypes.data_as(C.POINTER(C.c_longlong)) if return_masks else None, self._stream()))
+        if return_masks:
+            return [mask[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(boxes.shape[0])]
 
     def islands_kernel_ms(self):
         """Kernel time of the last measure_islands call in ms (hipEvents around the launch); -1 before the first."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_islands_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_islands_kernel_ms)
 
     # ---- source components (the fourth measurement step)
     def deblend_islands(self, img_dev, boxes, thr4, conn=8, radius=2, return_masks=False):
@@ -362,7 +392,7 @@ class HipDetector(object):
         float64 [n, CY_DBL_FIELDS] (lib.DBL_NAMES), component rows [n, CY_DBL_MAX_COMP, CY_DBL_COMP_FIELDS] (lib.DBL_COMP_NAMES));
         with return_masks also a list of n uint8 arrays shaped like the box windows (0 outside the island set, k + 1 component k,
         255 unassigned; an empty window gives an array of shape (0, 0))."""
-        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
+        boxes = self._boxes4(boxes)
         thr4 = np.ascontiguousarray(np.asarray(thr4, np.float64).reshape(-1, 4))
         n = boxes.shape[0]
         if thr4.shape[0] != n:
@@ -370,120 +400,60 @@ class HipDetector(object):
         out = np.zeros((n, L.CY_DBL_FIELDS), np.float64)
         comp = np.zeros((n, L.CY_DBL_MAX_COMP, L.CY_DBL_COMP_FIELDS), np.float64)
         MH, MW = self._image_2d(img_dev, "deblend_islands")
-        dp = C.POINTER(C.c_double)
-        mask = off = shapes = None
-        if return_masks:
-            from .measure import box_window
-            shapes = [box_window(b, MH, MW)[2:] for b in boxes]
-            off = np.zeros(n + 1, np.int64)
-            np.cumsum([h * w for h, w in shapes], out=off[1:])
-            mask = np.zeros(max(int(off[-1]), 1), np.uint8)
-        self._chk(self.lib.cy_deblend_islands(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), thr4.ctypes.data_as(dp), n, int(conn),
-                                              int(radius), out.ctypes.data_as(dp), comp.ctypes.data_as(dp),
-                                              C.c_void_p(mask.ctypes.data) if return_masks else None,
-                                              off.ctypes.data_as(C.POINTER(C.c_longlong)) if return_masks else None, self._stream()))
-        if not return_masks:
-            return out, comp
-        return out, comp, [mask[off[i]:off[i + 1]].reshape(shapes[i]) for i in range(n)]
+        masks = self._island_call(self.lib.cy_deblend_islands, img_dev, MH, MW, boxes, thr4, (int(conn), int(radius)), (out, comp), return_masks)
+        return (out, comp, masks) if return_masks else (out, comp)
 
     def deblend_kernel_ms(self):
         """Kernel time of the last deblend_islands call in ms (hipEvents around the launch); -1 before the first."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_deblend_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_deblend_kernel_ms)
 
-    # ---- component fits (the fifth measurement step)
+    # ---- component fits (the fifth measurement step) and joint fits of blends (the sixth)
+    def _fit_call(self, what, entry, fields, img_dev, boxes, bkg, ncomp, start, masks, max_iter):
+        """cy_fit_components / cy_fit_blends, which take the same arguments.  -> numpy float64 [n, CY_DBL_MAX_COMP, fields]."""
+        boxes = self._boxes4(boxes)
+        n = boxes.shape[0]
+        bkg = np.ascontiguousarray(np.asarray(bkg, np.float64).reshape(-1))
+        ncomp = np.ascontiguousarray(np.asarray(ncomp).reshape(-1).astype(np.int32))
+        start = np.ascontiguousarray(np.asarray(start, np.float64).reshape(-1, L.CY_DBL_MAX_COMP, 6))
+        if bkg.shape[0] != n or ncomp.shape[0] != n or start.shape[0] != n or len(masks) != n:
+            raise L.CyError("%s: %d boxes but %d bkg, %d ncomp, %d start rows and %d masks" % (
+                what, n, bkg.shape[0], ncomp.shape[0], start.shape[0], len(masks)))
+        if not 1 <= int(max_iter) <= 256:
+            raise L.CyError("%s: max_iter must be in [1, 256]" % what)
+        MH, MW = self._image_2d(img_dev, what)
+        out = np.zeros((n, L.CY_DBL_MAX_COMP, fields), np.float64)
+        if n == 0:
+            return out
+        mask, off = self._pack_masks(what, boxes, masks, MH, MW)
+        dp = C.POINTER(C.c_double)
+        self._chk(entry(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), bkg.ctypes.data_as(dp),
+                        ncomp.ctypes.data_as(C.POINTER(C.c_int)), start.ctypes.data_as(dp), n, int(max_iter),
+                        C.c_void_p(mask.ctypes.data), off.ctypes.data_as(C.POINTER(C.c_longlong)), out.ctypes.data_as(dp), self._stream()))
+        return out
+
     def fit_components(self, img_dev, boxes, bkg, ncomp, start, masks, max_iter=64):
         """One elliptical Gaussian per component by Levenberg-Marquardt (cy_fit_components).  img_dev, boxes: as measure_sources;
         bkg: [n] float64; ncomp: [n] components per source (0 .. CY_DBL_MAX_COMP); start: [n, CY_DBL_MAX_COMP, 6] float64
         {A, x0, y0, a, b, c} with x0, y0 in image pixels (measure.fit_start); masks: the n uint8 arrays deblend_islands returns
         with return_masks (shaped like the box windows: byte k + 1 = component k).  -> numpy float64
         [n, CY_DBL_MAX_COMP, CY_FIT_FIELDS] (lib.FIT_NAMES); rows at and beyond ncomp are 0."""
-        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
-        n = boxes.shape[0]
-        bkg = np.ascontiguousarray(np.asarray(bkg, np.float64).reshape(-1))
-        ncomp = np.ascontiguousarray(np.asarray(ncomp).reshape(-1).astype(np.int32))
-        start = np.ascontiguousarray(np.asarray(start, np.float64).reshape(-1, L.CY_DBL_MAX_COMP, 6))
-        if bkg.shape[0] != n or ncomp.shape[0] != n or start.shape[0] != n or len(masks) != n:
-            raise L.CyError("fit_components: %d boxes but %d bkg, %d ncomp, %d start rows and %d masks" % (
-                n, bkg.shape[0], ncomp.shape[0], start.shape[0], len(masks)))
-        if not 1 <= int(max_iter) <= 256:
-            raise L.CyError("fit_components: max_iter must be in [1, 256]")
-        MH, MW = self._image_2d(img_dev, "fit_components")
-        out = np.zeros((n, L.CY_DBL_MAX_COMP, L.CY_FIT_FIELDS), np.float64)
-        if n == 0:
-            return out
-        from .measure import box_window
-        off = np.zeros(n + 1, np.int64)
-        for i, (b, m) in enumerate(zip(boxes, masks)):
-            h, w = box_window(b, MH, MW)[2:]
-            if np.asarray(m).size != h * w:
-                raise L.CyError("fit_components: mask %d has %d bytes but the box window %d x %d" % (i, np.asarray(m).size, h, w))
-            off[i + 1] = off[i] + h * w
-        mask = np.zeros(max(int(off[-1]), 1), np.uint8)
-        if off[-1]:
-            mask[:off[-1]] = np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in masks])
-        dp = C.POINTER(C.c_double)
-        self._chk(self.lib.cy_fit_components(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), bkg.ctypes.data_as(dp),
-                                             ncomp.ctypes.data_as(C.POINTER(C.c_int)), start.ctypes.data_as(dp), n, int(max_iter),
-                                             C.c_void_p(mask.ctypes.data), off.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                             out.ctypes.data_as(dp), self._stream()))
-        return out
+        return self._fit_call("fit_components", self.lib.cy_fit_components, L.CY_FIT_FIELDS, img_dev, boxes, bkg, ncomp, start, masks, max_iter)
 
     def fit_kernel_ms(self):
         """Kernel time of the last fit_components call that launched a kernel, in ms (hipEvents around the launch); -1 before it."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_fit_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_fit_kernel_ms)
 
-    # ---- joint fits of blends (the sixth measurement step)
     def fit_blends(self, img_dev, boxes, bkg, ncomp, start, masks, max_iter=64):
         """The sum of the Gaussians of every group of touching components fitted jointly by Levenberg-Marquardt (cy_fit_blends).
         Arguments as fit_components; start: one start per component, for instance measure.blend_start().  -> numpy float64
         [n, CY_DBL_MAX_COMP, CY_BLEND_FIELDS] (lib.BLEND_NAMES); rows at and beyond ncomp are 0."""
-        boxes = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 4))
-        n = boxes.shape[0]
-        bkg = np.ascontiguousarray(np.asarray(bkg, np.float64).reshape(-1))
-        ncomp = np.ascontiguousarray(np.asarray(ncomp).reshape(-1).astype(np.int32))
-        start = np.ascontiguousarray(np.asarray(start, np.float64).reshape(-1, L.CY_DBL_MAX_COMP, 6))
-        if bkg.shape[0] != n or ncomp.shape[0] != n or start.shape[0] != n or len(masks) != n:
-            raise L.CyError("fit_blends: %d boxes but %d bkg, %d ncomp, %d start rows and %d masks" % (
-                n, bkg.shape[0], ncomp.shape[0], start.shape[0], len(masks)))
-        if not 1 <= int(max_iter) <= 256:
-            raise L.CyError("fit_blends: max_iter must be in [1, 256]")
-        MH, MW = self._image_2d(img_dev, "fit_blends")
-        out = np.zeros((n, L.CY_DBL_MAX_COMP, L.CY_BLEND_FIELDS), np.float64)
-        if n == 0:
-            return out
-        from .measure import box_window
-        off = np.zeros(n + 1, np.int64)
-        for i, (b, m) in enumerate(zip(boxes, masks)):
-            h, w = box_window(b, MH, MW)[2:]
-            if np.asarray(m).size != h * w:
-                raise L.CyError("fit_blends: mask %d has %d bytes but the box window %d x %d" % (i, np.asarray(m).size, h, w))
-            off[i + 1] = off[i] + h * w
-        mask = np.zeros(max(int(off[-1]), 1), np.uint8)
-        if off[-1]:
-            mask[:off[-1]] = np.concatenate([np.asarray(m, np.uint8).reshape(-1) for m in masks])
-        dp = C.POINTER(C.c_double)
-        self._chk(self.lib.cy_fit_blends(self.ctx, self._p(img_dev), MH, MW, boxes.ctypes.data_as(dp), bkg.ctypes.data_as(dp),
-                                         ncomp.ctypes.data_as(C.POINTER(C.c_int)), start.ctypes.data_as(dp), n, int(max_iter),
-                                         C.c_void_p(mask.ctypes.data), off.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                         out.ctypes.data_as(dp), self._stream()))
-        return out
+        return self._fit_call("fit_blends", self.lib.cy_fit_blends, L.CY_BLEND_FIELDS, img_dev, boxes, bkg, ncomp, start, masks, max_iter)
 
     def blend_kernel_ms(self):
         """Kernel time of the last fit_blends call that launched a kernel, in ms (hipEvents around the launch); -1 before it."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_blend_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_blend_kernel_ms)
 
     # ---- background and noise mesh (the global noise map of the measurement steps)
-    def _image_2d(self, img_dev, what):
-        if img_dev.dim() != 2 or img_dev.dtype != torch.float32 or not img_dev.is_contiguous() or img_dev.device != self.tdev:
-            raise L.CyError("%s: a contiguous 2-D float32 image on %s is required" % (what, self.tdev))
-        return int(img_dev.shape[0]), int(img_dev.shape[1])
-
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.
         -> numpy float64 [ncy, ncx, CY_BKG_FIELDS] (lib.BKG_NAMES), ncy = ceil(MH / cell), ncx = ceil(MW / cell)."""
@@ -498,9 +468,7 @@ class HipDetector(object):
 
     def background_kernel_ms(self):
         """Kernel time of the last measure_background call in ms (hipEvents around the launch); -1 before the first."""
-        ms = C.c_double(-1.0)
-        self._chk(self.lib.cy_background_kernel_ms(self.ctx, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms(self.lib.cy_background_kernel_ms)
 
     def expand_background(self, mesh, cell, shape, want=("bkg", "rms")):
         """mesh: filled [ncy, ncx, 2] float64 {bkg, rms} (measure.fill_mesh); shape = (MH, MW).  -> (bkg, rms) device fp32 maps

@@ -42,6 +42,9 @@ CONFIG = {
     'fit_components': False,           # NEW: one elliptical Gaussian fitted to every component (implies deblend_islands)
     'fit_blends': False,               # NEW: groups of touching components fitted jointly (implies fit_components)
     'fit_max_iter': 64,                # Levenberg-Marquardt iterations per component at most (1 .. 256)
+    'residual_map': False,             # NEW: model map of the fitted components, residual map and per-source residuals (implies fit_components)
+    'residual_nsigma': 5.0,            # a component is rendered within this many marginal sigmas of its centre (1 .. 8)
+    'save_residual_maps': False,       # write the model and residual maps as FITS images beside the catalog (implies residual_map)
     'bkg_map': False,                  # NEW: global background / noise mesh; bkg_map, rms_map, snr_map per source, island thresholds from it
     'bkg_cell': 128,                   # side of a mesh cell in pixels (4 .. 4096)
     'bkg_clip_sigma': 3.0,             # a clip keeps the pixels within this many rms of the cell median ...

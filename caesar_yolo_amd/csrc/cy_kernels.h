@@ -321,6 +321,31 @@ struct BlendArgs {
 };
 hipError_t launch_blend(const BlendArgs& a, hipStream_t s);
 
+// ---- model and residual maps (cy_residual.hip) -----------------------------------------------------
+// RND_FIELDS, RND_HALF_MAX, RND_TILE, RES_FIELDS: cy_measure_jobs.h
+constexpr int RND_CHUNK = 64;                  // components of a tile that are in LDS at a time: 4 KiB per workgroup
+struct RenderArgs {
+    const float* img; int MH, MW;   // as MeasureArgs
+    const double* comp;             // [m][6] {A, x0, y0, a, b, c}, x0 / y0 in image pixels
+    const int* rect;                // [m][4] inclusive support rectangles {sx0, sx1, sy0, sy1} inside the image (read for listed components only)
+    const int* tile_off;            // [ntx * nty + 1] first list entry of every RND_TILE x RND_TILE tile, tiles row-major
+    const int* tile_list;           // per tile the rendered components whose rectangle meets it, in increasing index
+    int ntx, nty;                   // ceil(MW / RND_TILE), ceil(MH / RND_TILE)
+    const float* bkg;               // [MH][MW] or null (0)
+    float *model, *resid;           // [MH][MW] each; either may be null, not both
+};
+hipError_t launch_render(const RenderArgs& a, hipStream_t s);
+struct ResidualArgs {
+    const float* img; const float* model; int MH, MW;   // image as MeasureArgs, model map of the same shape
+    const int* win;                 // [n][4] as IslandArgs
+    const long long* off;           // [n][2] {ISL_OFF_TOO_LARGE for a window above ISL_MAX_AREA, first mask byte in mask}
+    const double* bkg;              // [n]
+    const unsigned char* mask;      // the windows' bytes, non-zero: in the island set
+    int n;
+    double* out;                    // [n][RES_FIELDS]
+};
+hipError_t launch_residual_stats(const ResidualArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

@@ -12,6 +12,12 @@ constexpr int FIT_FIELDS = 32;                 // CY_FIT_FIELDS
 constexpr long long FIT_MAX_AREA = 1LL << 24;  // largest supported window; the components of a larger one get status 1 from the runtime
 constexpr int BLEND_FIELDS = 36;               // CY_BLEND_FIELDS
 constexpr int BLEND_MAX_MEMBERS = 4;           // CY_BLEND_MAX_MEMBERS
+constexpr int RND_FIELDS = 8;                  // CY_RND_FIELDS
+constexpr int RND_HALF_MAX = 256;              // CY_RND_HALF_MAX: largest half-width of a support rectangle
+constexpr int RND_TILE = 32;                   // side of an image tile of the render kernel: one workgroup each
+constexpr int RND_MAX_COMP = 1 << 20;          // most components of one cy_render_gaussians call
+constexpr long long RND_MAX_LIST = 1LL << 27;  // most entries of its tile table
+constexpr int RES_FIELDS = 12;                 // CY_RES_FIELDS
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list

@@ -199,6 +199,71 @@ const char* plan_blend(const FitInputs& in, BlendPlan& p) {
         });
 }
 
+const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p) {
+#pragma clang fp contract(off)          // a*c - b*b: both products are rounded before the subtraction, whatever the build's default
+    p.rows.clear(); p.rect.clear(); p.tile_off.clear(); p.tile_list.clear();
+    p.ntx = (MW + RND_TILE - 1) / RND_TILE; p.nty = (MH + RND_TILE - 1) / RND_TILE;
+    if (m < 0 || m > RND_MAX_COMP) return "m outside 0 .. 2^20";
+    p.rows.assign((size_t)m * RND_FIELDS, 0.0);
+    p.rect.assign((size_t)m * 4, 0);
+    const size_t ntiles = (size_t)p.ntx * p.nty;
+    p.tile_off.assign(ntiles + 1, 0);
+    // one side of a rectangle: [max(0, floor(c0) - h), min(N - 1, floor(c0) + 1 + h)], compared in double; false when it misses
+    auto side = [](double c0, double h, int N, int* lo, int* hi) {
+        const double f = std::floor(c0), l = f - h, u = (f + 1.0) + h;
+        if (u < 0.0 || l > (double)(N - 1)) return false;
+        *lo = l > 0.0 ? (int)l : 0;
+        *hi = u < (double)(N - 1) ? (int)u : N - 1;
+        return true;
+    };
+    long long total = 0;
+    for (int k = 0; k < m; ++k) {
+        const double* q = comp + (size_t)k * 6;
+        double* row = &p.rows[(size_t)k * RND_FIELDS];
+        int* r = &p.rect[(size_t)k * 4];
+        r[0] = r[2] = 0; r[1] = r[3] = -1;
+        row[1] = row[2] = row[3] = row[4] = -1.0;
+        bool fin = true;
+        for (int t = 0; t < 6; ++t) fin = fin && std::isfinite(q[t]);
+        const double a = q[3], b = q[4], c = q[5];
+        const double ac = a * c, bb = b * b;
+        const double det = ac - bb;
+        if (!(fin && q[0] > 0.0 && a > 0.0 && c > 0.0 && det > 0.0)) { row[0] = 1.0; continue; }
+        double hx = std::ceil(nsigma * std::sqrt(c / det)), hy = std::ceil(nsigma * std::sqrt(a / det));
+        bool capped = false;
+        if (!(hx <= (double)RND_HALF_MAX)) { hx = (double)RND_HALF_MAX; capped = true; }      // a half-width that is not finite is above the cap
+        if (!(hy <= (double)RND_HALF_MAX)) { hy = (double)RND_HALF_MAX; capped = true; }
+        if (!side(q[1], hx, MW, &r[0], &r[1]) || !side(q[2], hy, MH, &r[2], &r[3])) {
+            r[0] = r[2] = 0; r[1] = r[3] = -1;
+            row[0] = 3.0;
+            continue;
+        }
+        row[0] = capped ? 2.0 : 0.0;
+        for (int t = 0; t < 4; ++t) row[1 + t] = (double)r[t];
+        const int tx0 = r[0] / RND_TILE, tx1 = r[1] / RND_TILE, ty0 = r[2] / RND_TILE, ty1 = r[3] / RND_TILE;
+        row[5] = (double)((long long)(tx1 - tx0 + 1) * (ty1 - ty0 + 1));
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) ++p.tile_off[(size_t)ty * p.ntx + tx + 1];
+        total += (long long)row[5];
+        if (total > RND_MAX_LIST) return "tile table above 2^27 entries";
+    }
+    for (size_t t = 0; t < ntiles; ++t) p.tile_off[t + 1] += p.tile_off[t];
+    p.tile_list.assign((size_t)total, 0);
+    std::vector<int> next(p.tile_off.begin(), p.tile_off.end() - 1);
+    for (int k = 0; k < m; ++k) {                             // increasing k: every tile's list comes out in increasing index
+        const int* r = &p.rect[(size_t)k * 4];
+        if (r[1] < r[0]) continue;
+        for (int ty = r[2] / RND_TILE; ty <= r[3] / RND_TILE; ++ty)
+            for (int tx = r[0] / RND_TILE; tx <= r[1] / RND_TILE; ++tx) p.tile_list[(size_t)next[(size_t)ty * p.ntx + tx]++] = k;
+    }
+    return nullptr;
+}
+
+const char* plan_residuals(const double* boxes, const long long* mask_off, int n, int MH, int MW, IslandTable& t) {
+    static const double no_thr[2] = {0.0, 0.0};               // plan_islands' windows and offsets; there is no threshold to check
+    return plan_islands(boxes, no_thr, 0, mask_off, n, MH, MW, t);
+}
+
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
     for (int r = 0; r < nrows; ++r) {
         const size_t row = (size_t)rows[r];

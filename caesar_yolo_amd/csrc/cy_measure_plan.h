@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -44,6 +44,25 @@ struct BlendPlan {
                                         // every component; status 1 (large window), 6 (alone), 5 with the start in fields 8 .. 13 (group above the limit)
 };
 const char* plan_blend(const FitInputs& in, BlendPlan& p);
+
+// cy_render_gaussians.  comp: [m][6] {A, x0, y0, a, b, c} with x0, y0 in image pixels.  Per component the status and the support
+// rectangle (float64, every operation rounded on its own: det = a*c - b*b, hx = min(ceil(nsigma * sqrt(c / det)), RND_HALF_MAX),
+// hy likewise with a; columns [max(0, floor(x0) - hx), min(MW - 1, floor(x0) + 1 + hx)], rows likewise with MH), and a CSR table over
+// the RND_TILE x RND_TILE tiles of the image (row-major): per tile the rendered components whose rectangle meets it, in increasing
+// index.  Returns the message of a size limit: m outside [0, RND_MAX_COMP], or a table above RND_MAX_LIST entries.
+struct RenderPlan {
+    std::vector<double> rows;           // [m][RND_FIELDS] {status, sx0, sx1, sy0, sy1, ntiles, 0, 0}: status 0 rendered, 1 not admissible,
+                                        // 2 rendered with a capped half-width, 3 the rectangle misses the image; rectangle -1 when skipped
+    std::vector<int> rect;              // [m][4] the rectangles as integers ({0, -1, 0, -1} when skipped)
+    std::vector<int> tile_off;          // [ntx * nty + 1]
+    std::vector<int> tile_list;
+    int ntx = 0, nty = 0;
+};
+const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p);
+
+// cy_measure_residuals: the box windows and checked mask offsets, as plan_islands gives them (off[i][0] is ISL_OFF_TOO_LARGE for a
+// window above ISL_MAX_AREA pixels, off[i][1] the window's first mask byte)
+const char* plan_residuals(const double* boxes, const long long* mask_off, int n, int MH, int MW, IslandTable& t);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

@@ -22,7 +22,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_COUNT };
 
 struct cy_ctx {
     int device = 0;
@@ -68,7 +68,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1556,6 +1556,8 @@ static_assert(CY_DBL_FIELDS == DBL_FIELDS && CY_DBL_COMP_FIELDS == DBL_COMP_FIEL
 static_assert(CY_FIT_FIELDS == FIT_FIELDS, "header and kernel disagree on the fit row");
 static_assert(CY_BLEND_FIELDS == BLEND_FIELDS && CY_BLEND_MAX_MEMBERS == BLEND_MAX_MEMBERS, "header and kernel disagree on the blend row");
 static_assert(CY_BKG_FIELDS == BKG_FIELDS, "header and kernel disagree on the background row");
+static_assert(CY_RND_FIELDS == RND_FIELDS && CY_RND_HALF_MAX == RND_HALF_MAX, "header and planner disagree on the render row");
+static_assert(CY_RES_FIELDS == RES_FIELDS, "header and kernel disagree on the residual row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1709,6 +1711,47 @@ int cy_measure_background(cy_ctx* c, const float* d_img, int MH, int MW, int cel
     return t.run(STEP_BACKGROUND, [&](hipStream_t s) { return launch_background(a, s); });
 }
 
+int cy_render_gaussians(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_comp, int m, double nsigma, const float* d_bkg,
+                        float* d_model, float* d_resid, double* h_rows, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (MH <= 0 || MW <= 0 || !(nsigma >= 1.0 && nsigma <= 8.0)) return fail(c, CY_ERR_ARG, "MH, MW > 0 and 1 <= nsigma <= 8 required");
+    if (!d_img || (!d_model && !d_resid) || (m > 0 && (!h_comp || !h_rows))) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more");
+    RenderPlan p;
+    if (const char* msg = plan_render(h_comp, m, nsigma, MH, MW, p)) return fail(c, CY_ERR_ARG, msg);
+    TimedLaunch t(c, stream);
+    RenderArgs a{};
+    a.img = d_img; a.MH = MH; a.MW = MW; a.ntx = p.ntx; a.nty = p.nty; a.bkg = d_bkg; a.model = d_model; a.resid = d_resid;
+    a.comp = t.upload(h_comp, (size_t)m * 6);
+    a.rect = t.upload(p.rect.data(), p.rect.size());
+    a.tile_off = t.upload(p.tile_off.data(), p.tile_off.size());
+    a.tile_list = t.upload(p.tile_list.data(), p.tile_list.size());
+    const int rc = t.run(STEP_RENDER, [&](hipStream_t s) { return launch_render(a, s); });
+    if (rc == CY_OK && m > 0) std::memcpy(h_rows, p.rows.data(), p.rows.size() * sizeof(double));      // rows only beside maps that were written
+    return rc;
+}
+
+int cy_measure_residuals(cy_ctx* c, const float* d_img, const float* d_model, int MH, int MW, const double* h_boxes, const double* h_bkg,
+                         int n, const unsigned char* h_mask, const long long* h_mask_off, double* h_out, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (n < 0 || MH <= 0 || MW <= 0) return fail(c, CY_ERR_ARG, "n >= 0 and MH, MW > 0 required");
+    if (n == 0) return CY_OK;
+    if (!d_img || !d_model || !h_boxes || !h_bkg || !h_mask || !h_mask_off || !h_out) return fail(c, CY_ERR_ARG, "null argument");
+    if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, IMAGE_TOO_LARGE);
+    IslandTable tab;
+    if (const char* msg = plan_residuals(h_boxes, h_mask_off, n, MH, MW, tab)) return fail(c, CY_ERR_ARG, msg);
+    TimedLaunch t(c, stream);
+    ResidualArgs a{};
+    a.img = d_img; a.model = d_model; a.MH = MH; a.MW = MW; a.n = n;
+    a.win = t.upload(tab.win.data(), tab.win.size());
+    a.off = t.upload(tab.off.data(), tab.off.size());
+    a.bkg = t.upload(h_bkg, (size_t)n);
+    a.mask = t.upload(h_mask, (size_t)tab.nmask);
+    a.out = t.scratch<double>((size_t)n * CY_RES_FIELDS);
+    t.download(h_out, a.out, (size_t)n * CY_RES_FIELDS);
+    return t.run(STEP_RESIDUAL, [&](hipStream_t s) { return launch_residual_stats(a, s); });
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1721,6 +1764,8 @@ int cy_deblend_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_m
 int cy_fit_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_FIT, out_ms); }
 int cy_blend_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_BLEND, out_ms); }
 int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_BACKGROUND, out_ms); }
+int cy_render_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RENDER, out_ms); }
+int cy_residual_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RESIDUAL, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

@@ -30,7 +30,8 @@ class Analyzer(object):
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
         # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
         self.blends = bool(config.get('fit_blends', False))             # NEW: --fit_blends, touching components fitted jointly (implies the fits)
-        self.fit = bool(config.get('fit_components', False)) or self.blends            # NEW: --fit_components, one Gaussian per component (implies the components)
+        self.residual = bool(config.get('residual_map', False)) or bool(config.get('save_residual_maps', False))    # NEW: --residual_map, model and residual maps (implies the fits)
+        self.fit = bool(config.get('fit_components', False)) or self.blends or self.residual            # NEW: --fit_components, one Gaussian per component (implies the components)
         self.deblend = bool(config.get('deblend_islands', False)) or self.fit       # NEW: --deblend_islands, the components (implies the islands)
         self.islands = bool(config.get('measure_islands', False)) or self.deblend       # NEW: --measure_islands, the second step (implies the first)
         self.bkg_map = bool(config.get('bkg_map', False)) or bool(config.get('save_bkg_maps', False))      # NEW: --bkg_map, between the two
@@ -187,10 +188,19 @@ class Analyzer(object):
                                                                self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
                                                                use_map=self.bkg_map, max_iter=int(c.get('fit_max_iter', 64)),
                                                                return_pixel_rows=True)
+                            brows = None
                             if self.blends:
-                                measure.blends_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], rows, self.beam_area,
-                                                            self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
-                                                            use_map=self.bkg_map, max_iter=int(c.get('fit_max_iter', 64)))
+                                _, brows = measure.blends_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], rows,
+                                                                       self.beam_area, self.wcs, box_origin=(xmin, ymin),
+                                                                       wcs_origin=self.wcs_origin, use_map=self.bkg_map,
+                                                                       max_iter=int(c.get('fit_max_iter', 64)), return_pixel_rows=True)
+                            if self.residual:
+                                bkg_dev = det.expand_background(mesh, cell, frame.shape, want=("bkg",))[0] if self.bkg_map else None
+                                model, resid, _ = measure.residuals_and_annotate(det, frame, self.results["objs"], kept[3], rows, brows,
+                                                                                 float(c.get('residual_nsigma', 5.0)), bkg_dev, self.beam_area,
+                                                                                 box_origin=(xmin, ymin), use_map=self.bkg_map)
+                                if c.get('save_residual_maps', False):
+                                    measure.save_residual_maps(model, resid, self.outfile_json or ('out_' + str(self.image_id) + '.json'))
                 except L.CyError as e:
                     logger.warning("Source measurement failed (err=%s)..." % str(e))
                     return -1

@@ -591,17 +591,18 @@ class SFinder(object):
             self.stats["background_kernel_ms"] = det.background_kernel_ms()
             if c.get('save_bkg_maps', False):
                 measure.save_background_maps(det, mesh, cell, img.shape, self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
-        if c.get('measure_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False):     # --measure_islands: the second step, on the same resident image
+        residual = bool(c.get('residual_map', False)) or bool(c.get('save_residual_maps', False))      # --residual_map: implies the fits
+        if c.get('measure_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False) or residual:     # --measure_islands: the second step, on the same resident image
             t1 = time.time()
             measure.islands_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5),
                                          int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy), use_map=use_map)
             self.stats["islands_ms"] = 1e3 * (time.time() - t1)
             self.stats["islands_kernel_ms"] = det.islands_kernel_ms() if src else 0.0
-        if c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False):     # --deblend_islands: the components, right after the island step
+        if c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False) or residual:     # --deblend_islands: the components, right after the island step
             t1 = time.time()
             k_peak, radius = measure.deblend_config(c)
             blends = bool(c.get('fit_blends', False))         # --fit_blends: the joint fits, right after the single fits they start from
-            fit = bool(c.get('fit_components', False)) or blends      # --fit_components: the raw rows and masks are kept for the fit step
+            fit = bool(c.get('fit_components', False)) or blends or residual      # --fit_components: the raw rows and masks are kept for the fit step
             kept = measure.deblend_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5), k_peak,
                                                 int(c.get('island_conn', 8)), radius, self.beamArea, self.wcs, box_origin=(ox, oy),
                                                 use_map=use_map, return_raw=fit)
@@ -615,14 +616,29 @@ class SFinder(object):
                 self.stats["fit_ms"] = 1e3 * (time.time() - t1)
                 self.stats["fit_kernel_ms"] = max(det.fit_kernel_ms(), 0.0) if src else 0.0
                 self.stats["fit_jobs"], self.stats["fit_niter_mean"], self.stats["fit_niter_max"] = measure.fit_iterations(rows)
+                blend_pixel_rows = None
                 if blends:
                     t1 = time.time()
-                    brows = measure.blends_and_annotate(det, img, src, kept[1], kept[2], kept[3], pixel_rows, self.beamArea, self.wcs,
-                                                        box_origin=(ox, oy), use_map=use_map, max_iter=int(c.get('fit_max_iter', 64)))
+                    brows, blend_pixel_rows = measure.blends_and_annotate(det, img, src, kept[1], kept[2], kept[3], pixel_rows, self.beamArea,
+                                                                          self.wcs, box_origin=(ox, oy), use_map=use_map,
+                                                                          max_iter=int(c.get('fit_max_iter', 64)), return_pixel_rows=True)
                     self.stats["blend_ms"] = 1e3 * (time.time() - t1)
                     self.stats["blend_kernel_ms"] = max(det.blend_kernel_ms(), 0.0) if src else 0.0
                     (self.stats["blend_jobs"], self.stats["blend_niter_mean"], self.stats["blend_niter_max"],
                      self.stats["blend_over_limit"]) = measure.blend_stats(brows)
+                if residual:                                  # --residual_map: the fitted components back on the sky, the last step
+                    t1 = time.time()
+                    bkg_dev = det.expand_background(mesh, cell, img.shape, want=("bkg",))[0] if use_map else None
+                    model, resid, rs = measure.residuals_and_annotate(det, img, src, kept[3], pixel_rows, blend_pixel_rows,
+                                                                      float(c.get('residual_nsigma', 5.0)), bkg_dev, self.beamArea,
+                                                                      box_origin=(ox, oy), use_map=use_map)
+                    self.stats["residual_ms"] = 1e3 * (time.time() - t1)
+                    self.stats["render_kernel_ms"] = det.render_kernel_ms()
+                    self.stats["residual_kernel_ms"] = det.residual_kernel_ms() if src else 0.0
+                    self.stats["residual_rendered"], self.stats["residual_duplicates"], self.stats["residual_capped"] = (
+                        rs["rendered"], rs["duplicates"], rs["capped"])
+                    if c.get('save_residual_maps', False):
+                        measure.save_residual_maps(model, resid, self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
 
     # ---- tiled (reference :578-658)
     def run_parallel(self):
@@ -659,7 +675,8 @@ class SFinder(object):
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
             if (c.get('measure_sources', False) or c.get('measure_islands', False) or c.get('bkg_map', False) or c.get('save_bkg_maps', False)
-                    or c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False)):
+                    or c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False)
+                    or c.get('residual_map', False) or c.get('save_residual_maps', False)):
                 self._measure(det, mosaic, src)
             self.sources = {"sources": src}
             if self.write_to_json:

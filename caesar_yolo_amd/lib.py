@@ -25,6 +25,11 @@ CY_BLEND_FIELDS = 36
 CY_BLEND_MAX_MEMBERS = 4
 BLEND_NAMES = ("status", "niter", "npix", "F", "lambda", "group", "nmembers", "slot", "A", "x0", "y0", "a", "b", "c", "cov_ok") + tuple(
     "C%d%d" % (i, j) for i in range(6) for j in range(i, 6))
+CY_RND_FIELDS, CY_RND_HALF_MAX = 8, 256
+RND_NAMES = ("status", "sx0", "sx1", "sy0", "sy1", "ntiles", "reserved0", "reserved1")
+CY_RES_FIELDS = 12
+RES_NAMES = ("status", "npix_win", "npix_isl", "sum_win", "sumsq_win", "sum_isl", "sumsq_isl", "maxabs_isl", "x_max", "y_max", "model_isl",
+             "reserved")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -41,6 +46,7 @@ EXPORTS = [
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
     "cy_measure_islands", "cy_islands_kernel_ms", "cy_measure_background", "cy_background_kernel_ms", "cy_expand_background",
     "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
+    "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms",
 ]
 
 
@@ -173,6 +179,10 @@ def load():
         "cy_fit_kernel_ms": (C.c_int, [vp, dp]),
         "cy_fit_blends": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, dp, ip, dp, C.c_int, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
         "cy_blend_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_render_gaussians": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, vp, vp, vp, dp, vp]),
+        "cy_render_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_measure_residuals": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
+        "cy_residual_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

@@ -26,6 +26,12 @@ every component dict (annotate_fits).
 components (blend_groups) jointly to the union of their basins, from the single fits as starts (blend_start), raw rows
 lib.BLEND_NAMES, keys BLEND_KEYS on every component dict (annotate_blends).
 
+--residual_map adds a seventh step: `cy_render_gaussians` (HipDetector.render_gaussians) renders the sum of the fitted components
+(render_selection: the joint fit where there is one, else the single fit, every peak pixel once) over the whole image into a model
+map and forms the residual map; `cy_measure_residuals` (HipDetector.measure_residuals) measures the residual inside every source's
+box and island set, raw rows lib.RND_NAMES / lib.RES_NAMES, keys RESIDUAL_KEYS on every source and RENDER_ITEM_KEYS on every
+component dict (annotate_residuals).
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
 import math
 
@@ -42,6 +48,8 @@ FIT_KEYS = ("fit_status", "fit_niter", "fit_npix", "fit_chi2", "fit_peak", "fit_
 BLEND_KEYS = ("blend_group", "blend_size", "blend_status", "blend_niter", "blend_npix", "blend_chi2", "blend_peak", "blend_x", "blend_y",
               "blend_ra", "blend_dec", "blend_major", "blend_minor", "blend_pa", "blend_flux", "blend_peak_err", "blend_x_err", "blend_y_err",
               "blend_flux_err")
+RESIDUAL_KEYS = ("res_npix", "res_mean", "res_rms", "res_rms_box", "res_max", "res_x_max", "res_y_max", "res_flux", "res_model_flux", "res_ratio")
+RENDER_ITEM_KEYS = ("rendered", "render_status")
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
@@ -546,13 +554,14 @@ def annotate_blends(sources, rows, beam_area, wcs, origin=(0, 0), use_map=False)
 
 
 def blends_and_annotate(det, img_dev, sources, raw, comp, masks, fit_rows, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
-                        use_map=False, max_iter=64):
+                        use_map=False, max_iter=64, return_pixel_rows=False):
     """The joint-fit step, after fit_and_annotate(..., return_pixel_rows=True) on the same sources, image, raw rows, component
     rows and masks, whose fit rows in the pixel frame of img_dev it takes: blend_start(), one cy_fit_blends call, then
-    annotate_blends().  -> the blend rows, centres in catalog coordinates."""
+    annotate_blends().  -> the blend rows, centres in catalog coordinates; with return_pixel_rows -> (those rows, the rows as the
+    library gave them, in the pixel frame of img_dev: what residuals_and_annotate() takes)."""
     n = len(sources)
     if not n:
-        return np.zeros((0, 16, 36), np.float64)
+        return (np.zeros((0, 16, 36), np.float64),) * 2 if return_pixel_rows else np.zeros((0, 16, 36), np.float64)
     bx, by = float(box_origin[0]), float(box_origin[1])
     boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
     MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -563,12 +572,13 @@ def blends_and_annotate(det, img_dev, sources, raw, comp, masks, fit_rows, beam_
     fit_rows = np.asarray(fit_rows, np.float64).reshape(n, -1, 32)
     start = blend_start(fit_rows, np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
     rows = det.fit_blends(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
+    pixel_rows = rows.copy() if return_pixel_rows else None
     if bx or by:
         has = (np.arange(rows.shape[1])[None, :] < ncomp[:, None]) & np.isin(rows[:, :, 0], (0.0, 2.0, 3.0, 4.0, 5.0))
         rows[:, :, 9][has] += bx
         rows[:, :, 10][has] += by
     annotate_blends(sources, rows, beam_area, wcs, wcs_origin, use_map)
-    return rows
+    return (rows, pixel_rows) if return_pixel_rows else rows
 
 
 def blend_stats(rows):
@@ -579,6 +589,117 @@ def blend_stats(rows):
     it = rows[first & (rows[:, 1] > 0) & ((rows[:, 0] == 0.0) | (rows[:, 0] == 2.0)), 1]
     over = int((first & (rows[:, 0] == 5.0)).sum())
     return (int(it.size), float(it.mean()), int(it.max()), over) if it.size else (0, 0.0, 0, over)
+
+
+# ---- model and residual maps (--residual_map)
+def _fitted_params(fit_row, blend_row):
+    """The six parameters a component is rendered with: those of its blend row when that row's status is 0 or 2, else those of its
+    fit row when that row's status is 0 or 2, else None."""
+    if blend_row is not None and blend_row[0] in (0.0, 2.0):
+        return blend_row[8:14]
+    if fit_row[0] in (0.0, 2.0):
+        return fit_row[5:11]
+    return None
+
+
+def render_selection(sources, fit_rows, blend_rows=None):
+    """The components cy_render_gaussians is given, after annotate_components() on `sources`.  fit_rows [n, 16, CY_FIT_FIELDS] /
+    blend_rows [n, 16, CY_BLEND_FIELDS] (or None): the rows of cy_fit_components / cy_fit_blends with their centres in the pixel frame
+    of the image that is rendered.  Per component of every source, in source order, then component order:
+      parameters   the blend row's when its status is 0 or 2, else the fit row's when its status is 0 or 2, else it is not rendered
+      duplicates   overlapping boxes share islands, so the same peak can be a component of two sources; a component whose kept peak
+                   pixel (x_peak, y_peak) was already taken by an earlier rendered component is not rendered: the model counts a
+                   peak once
+    -> (comp float64 [m, 6] {A, x0, y0, a, b, c}, index int64 [m, 2] {source, component}, the number of duplicates left out)."""
+    n = len(sources)
+    fit_rows = np.asarray(fit_rows, np.float64).reshape(n, 16, 32)        # CY_DBL_MAX_COMP, CY_FIT_FIELDS
+    blend_rows = None if blend_rows is None else np.asarray(blend_rows, np.float64).reshape(n, 16, 36)     # CY_BLEND_FIELDS
+    comp, index, taken, ndup = [], [], set(), 0
+    for i, s in enumerate(sources):
+        for k, d in enumerate(s.get("components") or []):
+            p = _fitted_params(fit_rows[i, k], None if blend_rows is None else blend_rows[i, k])
+            peak = (int(d["x_peak"]), int(d["y_peak"]))
+            if p is None:
+                continue
+            if peak in taken:
+                ndup += 1
+                continue
+            taken.add(peak)
+            comp.append(p)
+            index.append((i, k))
+    return np.array(comp, np.float64).reshape(-1, 6), np.array(index, np.int64).reshape(-1, 2), ndup
+
+
+def annotate_residuals(sources, raw, index, render_rows, beam_area, origin=(0, 0), use_map=False):
+    """Adds RESIDUAL_KEYS to every source dict and RENDER_ITEM_KEYS to every component dict (in place; returns the list).  raw:
+    [n, CY_RES_FIELDS] rows of cy_measure_residuals; index, render_rows: what render_selection() and cy_render_gaussians returned.
+      rendered, render_status   whether the component is part of the model, and the status of its render row (0, 2: rendered; 1, 3:
+                   skipped by the library); None for a component that was not selected
+      res_npix     valid pixels of the island set; res_mean = sum_isl / npix_isl, res_rms = sqrt(sumsq_isl / npix_isl)
+      res_rms_box  sqrt(sumsq_win / npix_win), None when the window has no valid pixel
+      res_max      largest |residual| of the island set, res_x_max, res_y_max its position (+ origin)
+      res_flux     sum_isl / beam_area, res_model_flux = model_isl / beam_area; None without a beam
+      res_ratio    res_rms / rms (rms_map with use_map); None when that is missing or 0
+    Status 1 (window above the supported maximum) or npix_isl == 0: every value but res_npix (0) is None."""
+    if not sources:
+        return sources
+    raw = np.asarray(raw, np.float64).reshape(len(sources), -1)
+    ox, oy = int(origin[0]), int(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    status = {(int(i), int(k)): int(r[0]) for (i, k), r in zip(np.asarray(index).reshape(-1, 2), np.asarray(render_rows).reshape(-1, 8))}     # CY_RND_FIELDS
+    for i, (s, r) in enumerate(zip(sources, raw)):
+        for k, d in enumerate(s.get("components") or []):
+            st = status.get((i, k))
+            d["rendered"], d["render_status"] = st in (0, 2), st
+        for key in RESIDUAL_KEYS:
+            s[key] = None
+        n_isl = int(r[2]) if r[0] == 0.0 else 0
+        s["res_npix"] = n_isl
+        if n_isl == 0:
+            continue
+        rms = s.get("rms_map" if use_map else "rms")
+        rms = float(rms) if rms else 0.0
+        s["res_mean"], s["res_rms"] = float(r[5]) / n_isl, math.sqrt(float(r[6]) / n_isl)
+        s["res_rms_box"] = math.sqrt(float(r[4]) / float(r[1])) if r[1] > 0 else None
+        s["res_max"], s["res_x_max"], s["res_y_max"] = float(r[7]), int(r[8]) + ox, int(r[9]) + oy
+        if ba > 0.0:
+            s["res_flux"], s["res_model_flux"] = float(r[5]) / ba, float(r[10]) / ba
+        s["res_ratio"] = s["res_rms"] / rms if rms > 0.0 else None
+    return sources
+
+
+def residuals_and_annotate(det, img_dev, sources, masks, fit_rows, blend_rows=None, nsigma=5.0, bkg_dev=None, beam_area=0, box_origin=(0, 0),
+                           use_map=False):
+    """The residual step, after fit_and_annotate(..., return_pixel_rows=True) (and blends_and_annotate) on the same sources and
+    image: render_selection() on their rows in the pixel frame of img_dev (return_pixel_rows), one cy_render_gaussians call over the
+    whole image (bkg_dev: the expanded background map, or None: the residual keeps the background), one cy_measure_residuals
+    call on the boxes with the masks of deblend_and_annotate and the background the fits used, then annotate_residuals().
+    -> (model, resid device maps, {"rendered", "duplicates", "capped"})."""
+    n = len(sources)
+    bx, by = float(box_origin[0]), float(box_origin[1])
+    comp, index, ndup = render_selection(sources, fit_rows, blend_rows) if n else (np.zeros((0, 6)), np.zeros((0, 2), np.int64), 0)
+    rows, model, resid = det.render_gaussians(img_dev, comp, nsigma, bkg_dev)
+    if n:
+        boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
+        bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
+        raw = det.measure_residuals(img_dev, model, boxes, bkg, masks)
+        annotate_residuals(sources, raw, index, rows, beam_area, box_origin, use_map)
+    stats = {"rendered": int(np.isin(rows[:, 0], (0.0, 2.0)).sum()), "duplicates": ndup, "capped": int((rows[:, 0] == 2.0).sum())}
+    return model, resid, stats
+
+
+def save_residual_maps(model, resid, catalog_path):
+    """--save_residual_maps: the two device maps written as fp32 FITS images model_<name>.fits / resid_<name>.fits beside the
+    catalog file, <name> = the catalog's file name without its extension.  -> the two paths."""
+    import os
+    from . import utils
+    d, name = os.path.split(catalog_path)
+    name = os.path.splitext(name)[0]
+    paths = []
+    for tag, m in zip(("model_", "resid_"), (model, resid)):
+        paths.append(os.path.join(d, tag + name + ".fits"))
+        utils.write_fits_image(paths[-1], m.cpu().numpy())
+    return tuple(paths)
 
 
 def deblend_config(config):

@@ -453,6 +453,57 @@ class HipDetector(object):
         """Kernel time of the last fit_blends call that launched a kernel, in ms (hipEvents around the launch); -1 before it."""
         return self._kernel_ms(self.lib.cy_blend_kernel_ms)
 
+    # ---- model and residual maps (the seventh measurement step)
+    def render_gaussians(self, img_dev, comp, nsigma=5.0, bkg_dev=None, want=("model", "resid")):
+        """The sum of the Gaussians comp [m, 6] float64 {A, x0, y0, a, b, c} (x0, y0 in image pixels) over the whole image, each
+        inside its support rectangle of nsigma marginal sigmas (cy_render_gaussians).  img_dev: as measure_sources; bkg_dev: a
+        device fp32 map of its shape, or None (0).  -> (rows numpy float64 [m, CY_RND_FIELDS] (lib.RND_NAMES), model, resid): the two
+        device fp32 maps [MH, MW]; one not named in `want` is None."""
+        MH, MW = self._image_2d(img_dev, "render_gaussians")
+        comp = np.ascontiguousarray(np.asarray(comp, np.float64).reshape(-1, 6))
+        m = comp.shape[0]
+        if bkg_dev is not None and (bkg_dev.shape != img_dev.shape or self._image_2d(bkg_dev, "render_gaussians (bkg_dev)") != (MH, MW)):
+            raise L.CyError("render_gaussians: bkg_dev must have the shape of the image")
+        rows = np.zeros((m, L.CY_RND_FIELDS), np.float64)
+        maps = [torch.empty((MH, MW), dtype=torch.float32, device=self.tdev) if n in want else None for n in ("model", "resid")]
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_render_gaussians(self.ctx, self._p(img_dev), MH, MW, comp.ctypes.data_as(dp) if m else None, m, float(nsigma),
+                                               self._p(bkg_dev) if bkg_dev is not None else None,
+                                               *[self._p(t) if t is not None else None for t in maps],
+                                               rows.ctypes.data_as(dp) if m else None, self._stream()))
+        return rows, maps[0], maps[1]
+
+    def render_kernel_ms(self):
+        """Kernel time of the last render_gaussians call in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_render_kernel_ms)
+
+    def measure_residuals(self, img_dev, model_dev, boxes, bkg, masks):
+        """The residual ((v - bkg) - model) of every box window and of its island set (cy_measure_residuals).  img_dev, boxes: as
+        measure_sources; model_dev: the model map render_gaussians returns; bkg: [n] float64; masks: the n uint8 arrays
+        deblend_islands returns with return_masks (non-zero: in the island set).  -> numpy float64 [n, CY_RES_FIELDS]
+        (lib.RES_NAMES)."""
+        boxes = self._boxes4(boxes)
+        n = boxes.shape[0]
+        bkg = np.ascontiguousarray(np.asarray(bkg, np.float64).reshape(-1))
+        if bkg.shape[0] != n or len(masks) != n:
+            raise L.CyError("measure_residuals: %d boxes but %d bkg and %d masks" % (n, bkg.shape[0], len(masks)))
+        MH, MW = self._image_2d(img_dev, "measure_residuals")
+        if self._image_2d(model_dev, "measure_residuals (model_dev)") != (MH, MW):
+            raise L.CyError("measure_residuals: model_dev must have the shape of the image")
+        out = np.zeros((n, L.CY_RES_FIELDS), np.float64)
+        if n == 0:
+            return out
+        mask, off = self._pack_masks("measure_residuals", boxes, masks, MH, MW)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_measure_residuals(self.ctx, self._p(img_dev), self._p(model_dev), MH, MW, boxes.ctypes.data_as(dp),
+                                                bkg.ctypes.data_as(dp), n, C.c_void_p(mask.ctypes.data),
+                                                off.ctypes.data_as(C.POINTER(C.c_longlong)), out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def residual_kernel_ms(self):
+        """Kernel time of the last measure_residuals call in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_residual_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

@@ -455,6 +455,68 @@ int cy_fit_blends(cy_ctx* ctx, const float* d_img, int MH, int MW,
 /* milliseconds the kernel of the last cy_fit_blends call that launched one took (hipEvents around the launch); -1 before it */
 int cy_blend_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- model and residual maps (an addition, the seventh measurement step) ---------------------------------------------------
+ * The sum of m elliptical Gaussians rendered over the whole resident image d_img [MH][MW], and the image minus background minus
+ * that model.  Image, valid pixel and pixel-centre convention are those of cy_measure_sources; the single-Gaussian model, its
+ * expression for q (every product rounded on its own) and "admissible" are exactly those of cy_fit_components.  h_comp: m x
+ * {A, x0, y0, a, b, c} float64 with x0, y0 in image pixels.
+ *   term       of component k at pixel (ix, iy): A * exp(-0.5 * q), q = (a*u)*u + ((2*b)*u)*v + (c*v)*v, u = (double)ix - x0,
+ *              v = (double)iy - y0
+ *   support    component k contributes to the pixels of its support rectangle and to no others.  The rectangle is decided on the
+ *              host in float64, every operation rounded on its own: det = a*c - b*b, hx = min(ceil(nsigma * sqrt(c / det)),
+ *              CY_RND_HALF_MAX), hy = min(ceil(nsigma * sqrt(a / det)), CY_RND_HALF_MAX), a half-width that is not finite counting
+ *              as above the cap; columns [max(0, floor(x0) - hx), min(MW - 1, floor(x0) + 1 + hx)], rows likewise with y0, hy and
+ *              MH, compared in double before any conversion to int (a centre at 1e300 is a rectangle that misses the image)
+ *   model      model(ix, iy) = one plain sequential float64 sum, started at 0, of the terms of the contributing components in
+ *              increasing k
+ * h_rows row of component k, CY_RND_FIELDS float64:
+ *   [0] status   0 rendered; 1 not admissible, skipped; 2 rendered with a capped half-width (either one); 3 the rectangle misses
+ *                the image, skipped
+ *   [1] sx0, [2] sx1, [3] sy0, [4] sy1   the rectangle, inclusive, in image pixels; -1 when skipped
+ *   [5] ntiles   32 x 32 tiles of the image (tile (ty, tx) covers ix in [32 tx, 32 tx + 31], iy likewise) the rectangle touches; 0
+ *                when skipped.  [6..7] reserved (0)
+ * d_model (may be NULL): (float)model at every pixel of the image, 0 where nothing contributes.  d_resid (may be NULL, not both):
+ * (float)(((double)v - bkg) - model) on valid pixels, 0 on the others; bkg = (double)d_bkg[p], or 0 when d_bkg is NULL.  m == 0 is
+ * legal: the model is 0 everywhere and the residual is v - bkg.
+ * The runtime builds, per 32 x 32 tile, the list of rendered components whose rectangle meets it, in increasing index, and uploads
+ * it; one launch (one workgroup of 256 threads per tile, the tile's components staged through LDS 64 at a time; no atomics) writes
+ * both maps in one pass; synchronous on `stream`.  A pixel's value does not depend on the tiling: two calls give the same bytes.
+ * nsigma outside [1, 8] or NaN, MH / MW <= 0, a null image, both outputs null, an image of 2^31 pixels or more, m outside
+ * [0, 2^20], a null h_comp / h_rows with m > 0, or a tile table above 2^27 entries: CY_ERR_ARG.  h_rows is written only when the
+ * call returns CY_OK.  Needs no loaded weights. */
+#define CY_RND_FIELDS 8       /* status sx0 sx1 sy0 sy1 ntiles reserved reserved */
+#define CY_RND_HALF_MAX 256
+int cy_render_gaussians(cy_ctx* ctx, const float* d_img, int MH, int MW,
+                        const double* h_comp /* [m][6] A x0 y0 a b c, x0 y0 in image pixels */, int m, double nsigma,
+                        const float* d_bkg /* [MH][MW] or NULL */, float* d_model /* or NULL */, float* d_resid /* or NULL, not both */,
+                        double* h_rows /* [m][CY_RND_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_render_gaussians call took (hipEvents around the launch); -1 before the first call */
+int cy_render_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
+/* The residual of n catalog boxes against a model map d_model [MH][MW] (as cy_render_gaussians writes it).  Box window as
+ * cy_measure_sources; h_mask / h_mask_off laid out as cy_deblend_islands writes them (both required; h_mask_off is checked
+ * against the windows as in cy_fit_components); the island set of a window is the pixels whose mask byte is non-zero.  h_bkg:
+ * one background per source.  On a valid pixel p: r = ((double)v - bkg_i) - (double)d_model[p]; other pixels contribute nothing.
+ * h_out row, CY_RES_FIELDS float64:
+ *   [0] status   0 measured; 1 the window has more than 2^24 pixels: nothing measured, every other field as for an empty window
+ *   [1] npix_win, [2] npix_isl   valid pixels of the window / of its island set
+ *   [3] sum_win = sum r, [4] sumsq_win = sum r * r over the window; [5] sum_isl, [6] sumsq_isl over the island set
+ *   [7] maxabs_isl   largest |r| of the island set, [8] x_max, [9] y_max its first occurrence in row-major order, in image pixels;
+ *                    0, -1, -1 when npix_isl == 0
+ *   [10] model_isl = sum of (double)d_model[p] over the island set, [11] reserved (0)
+ *   Empty window: counts and sums 0, position -1, status 0.
+ * Counts, the maximum and its position do not depend on any order; the five sums are float64 with a fixed association, that of
+ * cy_measure_islands: window pixel i = dy * W + dx on thread i mod 256, sequential per thread, a shuffle tree per wave of 64, the
+ * four waves in order (two calls give the same bytes).  One launch (one workgroup per source) and one copy to h_out; synchronous
+ * on `stream`.  n == 0: CY_OK, nothing launched.  n < 0, MH / MW <= 0, a null pointer, an image of 2^31 pixels or more, or
+ * h_mask_off that disagrees with the windows: CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_RES_FIELDS 12      /* status npix_win npix_isl sum_win sumsq_win sum_isl sumsq_isl maxabs_isl x_max y_max model_isl reserved */
+int cy_measure_residuals(cy_ctx* ctx, const float* d_img, const float* d_model, int MH, int MW, const double* h_boxes,
+                         const double* h_bkg /* n */, int n, const unsigned char* h_mask, const long long* h_mask_off /* n + 1 */,
+                         double* h_out /* [n][CY_RES_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_measure_residuals call took (hipEvents around the launch); -1 before the first call */
+int cy_residual_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

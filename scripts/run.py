@@ -41,6 +41,13 @@ Differences that come with the MI355X engine:
              Gaussians on the union of their basins, from the single fits as starts and with --fit_max_iter.  Every component
              also carries blend_group, blend_size, blend_status and the blend_ namesakes of the fit_ keys (cy_fit_blends;
              DESIGN.md "Joint fits of blends").
+  --residual_map  (new; implies --fit_components) the sum of the fitted components (the joint fit where --fit_blends gave one, every
+             peak pixel once) rendered over the whole image, each inside --residual_nsigma (default 5, 1..8) marginal sigmas, and
+             the residual image - background - model measured in every source's box and island set.  Every source also carries
+             res_npix, res_mean, res_rms, res_rms_box, res_max, res_x_max, res_y_max, res_flux, res_model_flux, res_ratio, every
+             component rendered and render_status; with --bkg_map the residual is background-subtracted.  --save_residual_maps
+             (implies --residual_map) writes model_<catalog name>.fits / resid_<catalog name>.fits beside the catalog
+             (cy_render_gaussians, cy_measure_residuals; DESIGN.md "Model and residual maps").
 """
 import argparse
 import logging
@@ -151,7 +158,19 @@ def parse_args(argv=None):
                    help='Levenberg-Marquardt iterations per component at most, 1..256 (with --fit_components)')
     p.add_argument('--fit_blends', dest='fit_blends', action='store_true',
                    help='fit every group of touching components jointly on the GPU (implies --fit_components; reuses --fit_max_iter)')
+    p.add_argument('--residual_map', dest='residual_map', action='store_true',
+                   help='render the fitted components into a model map on the GPU and measure the residual of every source '
+                        '(implies --fit_components; uses the joint fits with --fit_blends)')
+    p.add_argument('--residual_nsigma', dest='residual_nsigma', type=float, default=5.0,
+                   help='a component is rendered within this many marginal sigmas of its centre, 1..8 (with --residual_map)')
+    p.add_argument('--save_residual_maps', dest='save_residual_maps', action='store_true',
+                   help='write the model and residual maps as model_<catalog name>.fits / resid_<catalog name>.fits beside the catalog '
+                        '(implies --residual_map)')
     args = p.parse_args(argv)
+    if args.save_residual_maps:
+        args.residual_map = True
+    if args.residual_map:
+        args.fit_components = True
     if args.fit_blends:
         args.fit_components = True
     if args.fit_components:
@@ -263,6 +282,7 @@ def main(argv=None):
               'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
               'deblend_islands': args.deblend_islands, 'deblend_peak_sigma': args.deblend_peak_sigma, 'deblend_radius': args.deblend_radius,
               'fit_components': args.fit_components, 'fit_max_iter': args.fit_max_iter, 'fit_blends': args.fit_blends,
+              'residual_map': args.residual_map, 'residual_nsigma': args.residual_nsigma, 'save_residual_maps': args.save_residual_maps,
               'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
               'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,

@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -12,6 +12,8 @@ histogram of the box-window areas of the catalog and the share of sources whose 
 then also times tests/island_ref.py.  Unless --no-bkg is given there is a fourth variant, --bkg_map (background_ms, background_kernel_ms), and after the runs
 the kernels alone on the same image: cy_measure_background at cell 64 / 128 / 256 (k 3, 3 clips) and cy_expand_background of the
 cell-128 mesh to both maps, `--runs` calls each after a warm-up; --host-ref then also times tests/bkg_ref.py at cell 128.
+Unless --no-residual (or --no-blend) is given there is a variant `residual`, --fit_blends --residual_map (residual_ms, render_kernel_ms,
+residual_kernel_ms, the numbers of rendered, duplicated and capped components beside the blend_ms of the same runs).
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
 their mean and largest niter beside the deblend_ms and deblend_kernel_ms of the same runs).
@@ -80,6 +82,7 @@ def main():
     ap.add_argument("--no-deblend", action="store_true")
     ap.add_argument("--no-fit", action="store_true")
     ap.add_argument("--no-blend", action="store_true")
+    ap.add_argument("--no-residual", action="store_true")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -99,7 +102,10 @@ def main():
                      "fit_niter_mean": self.stats.get("fit_niter_mean"), "fit_niter_max": self.stats.get("fit_niter_max"),
                      "blend_ms": self.stats.get("blend_ms"), "blend_kernel_ms": self.stats.get("blend_kernel_ms"),
                      "blend_jobs": self.stats.get("blend_jobs"), "blend_niter_mean": self.stats.get("blend_niter_mean"),
-                     "blend_niter_max": self.stats.get("blend_niter_max"), "blend_over_limit": self.stats.get("blend_over_limit")})
+                     "blend_niter_max": self.stats.get("blend_niter_max"), "blend_over_limit": self.stats.get("blend_over_limit"),
+                     "residual_ms": self.stats.get("residual_ms"), "render_kernel_ms": self.stats.get("render_kernel_ms"),
+                     "residual_kernel_ms": self.stats.get("residual_kernel_ms"), "residual_rendered": self.stats.get("residual_rendered"),
+                     "residual_duplicates": self.stats.get("residual_duplicates"), "residual_capped": self.stats.get("residual_capped")})
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -124,6 +130,8 @@ def main():
                 variants.append(("fit", base + on + ["--fit_components"]))
                 if not args.no_blend:                         # --fit_blends implies the fit step
                     variants.append(("blend", base + on + ["--fit_blends"]))
+                    if not args.no_residual:                  # --residual_map on top of the joint fits
+                        variants.append(("residual", base + on + ["--fit_blends", "--residual_map"]))
             if not (args.off_only or args.no_islands):         # the last one: its catalog is read below
                 variants.append(("islands", base + on + ["--measure_islands"]))
             for name, argv in variants:                    # warm-up of each variant
@@ -159,7 +167,12 @@ def main():
                         res[name][k] = [round(r[k], 3) for r in rows]
                         res[name][k + "_median"] = statistics.median(r[k] for r in rows)
                     res[name].update({k: rows[0][k] for k in ("blend_jobs", "blend_niter_mean", "blend_niter_max", "blend_over_limit")})
-                if name in ("on", "islands", "bkg", "deblend", "fit", "blend"):
+                if name == "residual":
+                    for k in ("blend_ms", "residual_ms", "render_kernel_ms", "residual_kernel_ms"):
+                        res[name][k] = [round(r[k], 3) for r in rows]
+                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
+                    res[name].update({k: rows[0][k] for k in ("residual_rendered", "residual_duplicates", "residual_capped")})
+                if name in ("on", "islands", "bkg", "deblend", "fit", "blend", "residual"):
                     res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
                     res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
                     res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
@@ -170,6 +183,8 @@ def main():
                 res["fit_added_ms"] = res["fit"]["run_ms_median"] - res["off"]["run_ms_median"]
             if "blend" in got:
                 res["blend_added_ms"] = res["blend"]["run_ms_median"] - res["off"]["run_ms_median"]
+            if "residual" in got:
+                res["residual_added_ms"] = res["residual"]["run_ms_median"] - res["off"]["run_ms_median"]
             if "deblend" in got:
                 res["deblend_added_ms"] = res["deblend"]["run_ms_median"] - res["off"]["run_ms_median"]
             if "bkg" in got:

@@ -11,37 +11,26 @@
 //         pass reads them from there;
 //   L2    a larger cell (up to 4096 x 4096) is re-read from the image in every pass, 64-bit pixel offsets, four loads in flight
 //         per lane.
-// Medians are radix selections as in ring_median of cy_measure.hip: 8 bits per pass over order-preserving 64-bit keys, 256-bin
-// histograms in LDS (pixels: fkey of the float in the high word, 4 passes; deviations: the bit pattern of the non-negative
-// float64, 8 passes), an extra pass for the upper middle element of an even count when it is a different value.
+// Medians are the exact radix selections of cy_select.h, the ones of measure_kernel: the cell hands them its valid pixels inside
+// [L, H].  n == stop_at ends a selection after its counting pass: a clip that removed nothing needs no new median.
 // Every loop is bounded before it starts: niter <= 32 clips, 4 or 8 passes, cell pixels / 512 steps per pass.  A clip that removes
 // nothing ends the loop (the fixed point: the next clip would form the same lo and hi).  Counts, selections and single rounded
 // operations only: nothing depends on the order in which pixels are visited.  The LDS atomics are integer counts.
 // background_expand_kernel: the filled mesh [ncy][ncx][2] float64 sampled bilinearly at every pixel centre (the expression of
 // measure.sample_mesh, float64, each operation rounded on its own), stored as fp32; consecutive lanes write consecutive ix.
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_px.h"                      // valid_px
+#include "cy_select.h"                  // SelSmem, select_median
 
 #pragma clang fp contract(off)          // m * (1 - f) is rounded before it is added, as the float64 definition does
 
 namespace cy {
 namespace {
 
-constexpr int BNT = 512, BNW = BNT / 64, BUNROLL = 4;
+constexpr int BNT = 512, BUNROLL = 4;
 
 struct BSmem {
-    unsigned hist[256];
-    unsigned wsum[4];
-    unsigned sel[4];                     // digit, rank inside the bin, elements below the bin, elements in the bin
-    unsigned long long umin[BNW];
+    SelSmem<BNT> sel;
 };
-
-__device__ __forceinline__ bool valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
-__device__ __forceinline__ unsigned fkey32(float f) {                   // order-preserving float -> u32 (fkey of cy_preproc.hip)
-    const unsigned b = __float_as_uint(f);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey32_inv(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k); }
 
 struct Cell {
     const float* img;                   // first pixel of the cell in the image (L2 form)
@@ -50,15 +39,6 @@ struct Cell {
     unsigned cw, n;                     // width and pixel count of the cell
     double L, H;                        // current interval
 };
-
-template <int MODE> __device__ __forceinline__ unsigned long long cell_key(float v, double med) {
-    if constexpr (MODE == 0) return (unsigned long long)fkey32(v) << 32;
-    else return (unsigned long long)__double_as_longlong(fabs((double)v - med));      // d >= 0: orders like its bit pattern
-}
-template <int MODE> __device__ __forceinline__ double key_value(unsigned long long k) {
-    if constexpr (MODE == 0) return (double)fkey32_inv((unsigned)(k >> 32));
-    else return __longlong_as_double((long long)k);
-}
 
 // f(v) for every valid pixel of the cell inside [L, H]; an out-of-range slot reads as 0 = blank
 template <bool LDS, typename F>
@@ -77,59 +57,6 @@ __device__ __forceinline__ void cell_for_each(const Cell& c, F f) {
             if (valid_px(v[u]) && d >= c.L && d <= c.H) f(v[u]);
         }
     }
-}
-
-// Exact median of the keys of the cell's valid pixels inside [L, H]; n = their count (0: returns 0).  n == stop_at: returns 0
-// after the counting pass (the caller keeps the median it has).  Every thread gets the same result.
-template <int MODE, bool LDS>
-__device__ double cell_median(BSmem& s, const Cell& c, double med, unsigned stop_at, unsigned& n) {
-    constexpr int NP = MODE == 0 ? 4 : 8;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned long long prefix = 0;
-    unsigned k = 0, below = 0, eq = 0;
-    n = 0;
-    for (int p = 0; p < NP; ++p) {
-        const int shift = 56 - 8 * p;
-        if (tid < 256) s.hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long want = p ? prefix >> (shift + 8) : 0;
-        cell_for_each<LDS>(c, [&](float v) {
-            const unsigned long long key = cell_key<MODE>(v, med);
-            if (p == 0 || (key >> (shift + 8)) == want) atomicAdd(&s.hist[(unsigned)(key >> shift) & 255u], 1u);
-        });
-        __syncthreads();
-        const unsigned h = tid < 256 ? s.hist[tid] : 0u;
-        unsigned incl = h;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-        if (tid < 256 && lane == 63) s.wsum[w] = incl;
-        __syncthreads();
-        unsigned off = 0, total = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const unsigned t = s.wsum[j]; if (j < w) off += t; total += t; }
-        if (p == 0) {
-            n = total;
-            if (n == 0 || n == stop_at) return 0.0;         // uniform: `total` came from LDS
-            k = (n - 1) / 2;
-        }
-        const unsigned excl = off + incl - h;
-        if (tid < 256 && k >= excl && k < excl + h) { s.sel[0] = (unsigned)tid; s.sel[1] = k - excl; s.sel[2] = excl; s.sel[3] = h; }
-        __syncthreads();
-        prefix |= (unsigned long long)s.sel[0] << shift;
-        k = s.sel[1]; below += s.sel[2]; eq = s.sel[3];
-    }
-    const double a = key_value<MODE>(prefix);
-    if ((n & 1u) || below + eq > n / 2) return a;           // odd count, or the upper middle element has the same value
-    unsigned long long m = ~0ull;                           // smallest key above `prefix`
-    cell_for_each<LDS>(c, [&](float v) { const unsigned long long key = cell_key<MODE>(v, med); if (key > prefix && key < m) m = key; });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_down(m, o); m = t < m ? t : m; }
-    if (lane == 0) s.umin[w] = m;
-    __syncthreads();
-    m = s.umin[0];
-#pragma unroll
-    for (int j = 1; j < BNW; ++j) m = s.umin[j] < m ? s.umin[j] : m;
-    return (a + key_value<MODE>(m)) / 2.0;
 }
 
 template <bool LDS>
@@ -156,16 +83,17 @@ __global__ __launch_bounds__(BNT) void background_kernel(const BackgroundArgs a)
     }
 
     unsigned n0 = 0, n = 0, n2 = 0, rounds = 0;
-    double med = cell_median<0, LDS>(s, c, 0.0, 0xFFFFFFFFu, n0), sig = 0.0;
+    const auto cell = [&](auto f) { cell_for_each<LDS>(c, f); };       // c.L and c.H as they are at the call
+    double med = select_median<0, BNT>(s.sel, cell, 0.0, 0xFFFFFFFFu, n0), sig = 0.0;
     n = n0;
-    if (n) sig = 1.4826 * cell_median<1, LDS>(s, c, med, 0xFFFFFFFFu, n2);
+    if (n) sig = 1.4826 * select_median<1, BNT>(s.sel, cell, med, 0xFFFFFFFFu, n2);
     for (int j = 0; j < a.niter && n; ++j) {                // n, and with it every branch below, is the same in every thread
         const double d = a.k * sig, lo = med - d, hi = med + d;
         c.L = fmax(c.L, lo); c.H = fmin(c.H, hi);
-        const double m2 = cell_median<0, LDS>(s, c, 0.0, n, n2);
+        const double m2 = select_median<0, BNT>(s.sel, cell, 0.0, n, n2);
         if (n2 == n) break;                                 // nothing removed: the fixed point
         ++rounds; n = n2; med = m2; sig = 0.0;
-        if (n) sig = 1.4826 * cell_median<1, LDS>(s, c, med, 0xFFFFFFFFu, n2);
+        if (n) sig = 1.4826 * select_median<1, BNT>(s.sel, cell, med, 0xFFFFFFFFu, n2);
     }
     if (tid == 0) {
         out[0] = (double)n0; out[1] = (double)n; out[2] = med; out[3] = sig;

@@ -6,7 +6,8 @@
 //   sweep    per list entry the vector w = (r, J_0 .. J_{P-1}), P + 1 numbers; the sums are the upper triangle of w^T w in row-major
 //            order: F = w_0 w_0, g_i = w_0 w_{1+i}, H_ij = w_{1+i} w_{1+j}: NS = (P + 1)(P + 2) / 2 <= 325 float64 sums
 //   step     thread 0: P x P Cholesky of H + lambda diag(H) in LDS, d, `small`, admissibility of p + d; everyone: sweep at the trial;
-//            thread 0: accept / reject, lambda, convergence, and at the end inv(H).  Decisions reach the others through two LDS words
+//            thread 0: accept / reject, lambda, convergence (lm_iterate of cy_lm.h, which states the rule and owns the loop), and
+//            at the end inv(H)
 // One workgroup of 256 threads owns one job of the job table from start to finish; no workgroup reads what another one wrote.  The
 // job's pixels arrive as a list of window indices in increasing order, built by the runtime from the mask: the kernel never searches
 // a window.  A list entry whose pixel is not valid (0 or non-finite) keeps its list position and contributes nothing (its w is 0).
@@ -22,8 +23,7 @@
 //   sweeps      at most max_iter + 1 per job; chunks ceil(npos / 128), npos <= 2^24; per chunk <= 128 entries, M <= 4 members each
 //   pair        the (row, column) of a sum index: at most P + 1 = 25 steps, once per job
 //   thread 0    Cholesky, the two triangular solves, the inverse of L and the members' blocks of inv(H): nested loops over P <= 24
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_lm.h"                      // gauss_terms, stage_list, lm_iterate
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
 
@@ -32,8 +32,6 @@ namespace {
 
 constexpr int BL_T = 256;
 constexpr int BL_PMAX = 6 * BLEND_MAX_MEMBERS, BL_WMAX = BL_PMAX + 1;       // 24 parameters, 25 numbers per list entry
-constexpr unsigned BL_BAD = 0xFFFFFFFFu;
-constexpr int ACT_NONE = 0, ACT_SWEEP = 1, ACT_STOP = 2;
 static_assert(BLEND_NSUM_MAX == BL_WMAX * (BL_WMAX + 1) / 2 && BLEND_NSUM_MAX <= 2 * BL_T, "two sums per thread cover every sum");
 static_assert(BL_PMAX * BL_PMAX <= BLEND_CHUNK * BL_WMAX, "the inverse of L reuses the chunk rows");
 
@@ -46,15 +44,9 @@ struct BSmem {
     double L[BL_PMAX][BL_PMAX];         // thread 0's Cholesky factor
     double p[BL_PMAX], pt[BL_PMAX], z[BL_PMAX], d[BL_PMAX];
     unsigned cnt[BL_T / 64];
-    int act, stop;
+    LmCtl ctl;
 };
 
-__device__ __forceinline__ bool bl_valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
-__device__ __forceinline__ bool fin(double v) { return fabs(v) <= DBL_MAX; }
-__device__ __forceinline__ bool admissible(const double* p) {
-    return fin(p[0]) && fin(p[1]) && fin(p[2]) && fin(p[3]) && fin(p[4]) && fin(p[5]) && p[0] > 0.0 && p[3] > 0.0 && p[5] > 0.0 &&
-           p[3] * p[5] - p[4] * p[4] > 0.0;
-}
 __device__ __forceinline__ bool admissible_all(const double* p, const int M) {
     bool ok = true;
     for (int s = 0; s < M; ++s) ok = ok && admissible(p + 6 * s);
@@ -87,13 +79,9 @@ __device__ __forceinline__ void sweep(BSmem& s, const double* pp, const int M, c
             const unsigned q = base + tid;
             unsigned i; float fv;
             if (LDS) { i = s.idx[q]; fv = s.val[q]; }
-            else {
-                i = list[q]; fv = 0.0f;
-                if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
-                if (i >= A || !bl_valid_px(fv)) i = BL_BAD;
-            }
+            else i = list_pixel(list, q, img, MW, W, A, fv);
             double* w = s.ch[tid];
-            if (i == BL_BAD) {
+            if (i == LM_BAD) {
                 for (int k = 0; k <= 6 * M; ++k) w[k] = 0.0;
             } else {
                 const unsigned dy = i / W, dx = i - dy * W;
@@ -101,13 +89,7 @@ __device__ __forceinline__ void sweep(BSmem& s, const double* pp, const int M, c
                 double mt = 0.0;
                 for (int t = 0; t < M; ++t) {
                     const double* p = pp + 6 * t;
-                    const double pA = p[0], a = p[3], b = p[4], c = p[5];
-                    const double u = (double)dx - p[1], v = (double)dy - p[2];
-                    const double e = exp(-0.5 * ((a * u) * u + ((2.0 * b) * u) * v + (c * v) * v));
-                    const double m = pA * e;
-                    double* J = w + 1 + 6 * t;
-                    J[0] = e; J[1] = m * (a * u + b * v); J[2] = m * (b * u + c * v);
-                    J[3] = ((-0.5 * m) * u) * u; J[4] = ((-m) * u) * v; J[5] = ((-0.5 * m) * v) * v;
+                    const double m = gauss_terms(p[0], p[1], p[2], p[3], p[4], p[5], (double)dx, (double)dy, w + 1 + 6 * t);
                     mt = t == 0 ? m : mt + m;
                 }
                 w[0] = y - mt;
@@ -179,7 +161,7 @@ __device__ __forceinline__ void early_rows(const BlendJob& j, const BlendArgs& a
 
 template <bool LDS>
 __device__ void fit(BSmem& s, const BlendJob& j, const BlendArgs& a) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t MW = (size_t)a.MW;
     const float* __restrict__ img = a.img + (size_t)j.y0 * MW + (size_t)j.x0;
     const unsigned* __restrict__ list = a.list + j.list_off;
@@ -187,24 +169,9 @@ __device__ void fit(BSmem& s, const BlendJob& j, const BlendArgs& a) {
     const int M = j.M, P = 6 * M, nsum = (P + 1) * (P + 2) / 2;
     const double bkg = j.bkg;
 
-    // ---- valid pixels of the list (and, in LDS, their values)
-    unsigned np = 0;
-    for (unsigned q = tid; q < npos; q += BL_T) {
-        unsigned i = list[q]; float fv = 0.0f;
-        if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
-        if (i >= A || !bl_valid_px(fv)) i = BL_BAD;
-        if (LDS) { s.idx[q] = i; s.val[q] = fv; }
-        np += i != BL_BAD;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) np += __shfl_down(np, o);
-    if (lane == 0) s.cnt[wv] = np;
     if (tid < P) { s.p[tid] = j.p0[tid]; s.pt[tid] = j.p0[tid]; }
-    if (tid == 0) { s.act = ACT_NONE; s.stop = 0; }
-    __syncthreads();
-    np = s.cnt[0];
-#pragma unroll
-    for (int k = 1; k < BL_T / 64; ++k) np += s.cnt[k];
+    if (tid == 0) { s.ctl.act = ACT_NONE; s.ctl.stop = 0; }
+    const unsigned np = stage_list<BL_T, LDS>(s.val, s.idx, s.cnt, list, npos, img, MW, W, A);       // the barrier is inside
 
     const int early = !admissible_all(j.p0, M) ? 4 : np < (unsigned)(P + 1) ? 3 : 0;     // uniform
     if (early) { early_rows(j, a, early, np); return; }
@@ -217,54 +184,20 @@ __device__ void fit(BSmem& s, const BlendJob& j, const BlendArgs& a) {
     sweep<LDS>(s, s.pt, M, list, npos, img, MW, W, A, bkg, a1, b1, a2, b2, nsum);
     for (int k = tid; k < nsum; k += BL_T) s.cur[k] = s.tot[k];
     __syncthreads();
-    double lam = 1e-3;
-    int status = 2, niter = a.max_iter;
-    bool small = false;
-
-    for (int it = 1; it <= a.max_iter; ++it) {
-        if (tid == 0) {
-            int act = ACT_NONE;
-            small = false;
-            if (lm_solve(s, P, lam)) {
-                small = true;
-                for (int k = 0; k < P; ++k) {
-                    small = small && fabs(s.d[k]) <= 1e-10 * (fabs(s.p[k]) + 1e-6);
-                    s.pt[k] = s.p[k] + s.d[k];
-                }
-                if (admissible_all(s.pt, M)) act = ACT_SWEEP;
-            }
-            if (act == ACT_NONE) {                            // rejected without a sweep
-                if (small) { status = 0; niter = it; act = ACT_STOP; }
-                else {
-                    lam *= 10.0;
-                    if (lam > 1e12) { status = 2; niter = it; act = ACT_STOP; }
-                }
-            }
-            s.act = act;
-        }
-        __syncthreads();
-        const int act = s.act;                                // uniform (from LDS)
-        if (act == ACT_STOP) break;
-        if (act == ACT_SWEEP) {
-            sweep<LDS>(s, s.pt, M, list, npos, img, MW, W, A, bkg, a1, b1, a2, b2, nsum);
-            if (tid == 0) {
-                const double F = s.cur[0], Fn = s.tot[0];
-                if (Fn < F) {
-                    const bool conv = small || F - Fn <= 1e-14 * F;
-                    for (int k = 0; k < nsum; ++k) s.cur[k] = s.tot[k];
-                    for (int k = 0; k < P; ++k) s.p[k] = s.pt[k];
-                    lam = fmax(lam / 10.0, 1e-12);
-                    if (conv) { status = 0; niter = it; s.stop = 1; }
-                } else if (small) { status = 0; niter = it; s.stop = 1; }
-                else {
-                    lam *= 10.0;
-                    if (lam > 1e12) { status = 2; niter = it; s.stop = 1; }
-                }
-            }
-        }
-        __syncthreads();
-        if (s.stop) break;                                    // uniform (from LDS)
-    }
+    double lam;
+    int status, niter;
+    lm_iterate(s.ctl, a.max_iter, lam, status, niter,
+               [&](const double lam, bool& small) {
+                   if (!lm_solve(s, P, lam)) return false;
+                   small = lm_trial(P, s.p, s.d, s.pt);
+                   return admissible_all(s.pt, M);
+               },
+               [&] { sweep<LDS>(s, s.pt, M, list, npos, img, MW, W, A, bkg, a1, b1, a2, b2, nsum); },
+               [&] { return s.cur[0]; }, [&] { return s.tot[0]; },
+               [&] {
+                   for (int k = 0; k < nsum; ++k) s.cur[k] = s.tot[k];
+                   for (int k = 0; k < P; ++k) s.p[k] = s.pt[k];
+               });
     if (tid != 0) return;
     // ---- thread 0: C = inv(H) at the reported p through H = L L^T, X = inv(L) column by column, C_ij = sum_k>=j X_ki X_kj
     double* X = &s.ch[0][0];

@@ -314,13 +314,10 @@ __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const Debl
 __global__ __launch_bounds__(INT) void deblend_kernel(const DeblendArgs a) {
     __shared__ DSmem s;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int* wn = a.win + (size_t)b * 4;
-    // the host's windows are already inside the image; clamped again so that no index can leave it whatever arrives here (a
-    // clamp only shrinks a window, so the label and mask slices the host sized still hold it)
-    const int bx0 = max(wn[0], 0), bx1 = min(wn[1], a.MW - 1), by0 = max(wn[2], 0), by1 = min(wn[3], a.MH - 1);
+    Win w;
+    const long long area = window_of(a.win + (size_t)b * 4, a.MW, a.MH, w);       // held inside the image (cy_px.h)
     double* out = a.out + (size_t)b * DBL_FIELDS;
     const long long wo = a.off[(size_t)b * 2], mo = a.off[(size_t)b * 2 + 1];
-    const long long area = bx1 < bx0 || by1 < by0 ? 0 : (long long)(bx1 - bx0 + 1) * (by1 - by0 + 1);
     const bool lds = wo < 0;
     if (area == 0 || area > ISL_MAX_AREA || wo == ISL_OFF_TOO_LARGE) {
         // empty window: nothing to measure.  Above the supported maximum: status 1, nothing measured
@@ -333,8 +330,6 @@ __global__ __launch_bounds__(INT) void deblend_kernel(const DeblendArgs a) {
         if (tid < DBL_FIELDS) out[tid] = __longlong_as_double(0x7FF8000000000000LL);
         return;
     }
-    Win w;
-    w.x0 = bx0; w.y0 = by0; w.W = (unsigned)(bx1 - bx0 + 1); w.H = (unsigned)(by1 - by0 + 1); w.A = (unsigned)area;
     const double* t = a.thr + (size_t)b * 4;
     unsigned char* mask = a.mask ? a.mask + mo : nullptr;
     double* comp = a.comp + (size_t)b * DBL_MAX_COMP * DBL_COMP_FIELDS;

@@ -4,7 +4,8 @@
 //            window's first pixel in here (the runtime converts from and to image pixels)
 //   sweep    F = sum r^2, g = J^T r, H = J^T J (upper triangle) at one p over the job's pixels: FIT_NSUM = 28 float64 sums
 //   step     thread 0: 6 x 6 Cholesky of H + lambda diag(H), d, `small`, admissibility of p + d; everyone: sweep at the trial;
-//            thread 0: accept / reject, lambda, convergence.  Decisions reach the other threads through two LDS words
+//            thread 0: accept / reject, lambda, convergence: lm_iterate of cy_lm.h, which states the rule and owns the loop
+// The Gaussian and its Jacobian (gauss_terms) and the staging of the list (list_pixel, stage_list) are in cy_lm.h as well.
 // One workgroup of 256 threads owns one job of the job table from start to finish; no workgroup reads what another one wrote.
 // The job's pixels arrive as a list of window indices i = dy * W + dx in increasing order, built by the runtime from the mask: the
 // kernel never searches a window.  A list entry whose pixel is not valid (0 or non-finite) keeps its list position and contributes
@@ -21,8 +22,7 @@
 //   reductions  6 shuffle steps and FIT_T / 64 = 4 waves;  Cholesky and the two triangular solves: 6 x 6, fully unrolled
 // Sums: float64 per lane over increasing list position (entry q belongs to thread q mod 256), __shfl_down tree per wave, the
 // four waves added in order by thread 0: fixed association, so two runs give the same bits.  No atomics.
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_lm.h"                      // gauss_terms, stage_list, lm_iterate
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
 
@@ -30,8 +30,6 @@ namespace cy {
 namespace {
 
 constexpr int FIT_T = 256, FIT_W = FIT_T / 64;
-constexpr unsigned FIT_BAD = 0xFFFFFFFFu;
-constexpr int ACT_NONE = 0, ACT_SWEEP = 1, ACT_STOP = 2;
 
 struct FSmem {
     float val[FIT_LDS_MAX];
@@ -41,15 +39,9 @@ struct FSmem {
     double cur[FIT_NSUM];               // sums at the accepted p
     double p[6], pt[6];                 // accepted and trial parameters
     unsigned cnt[FIT_W];
-    volatile int act, stop;
+    LmCtl ctl;
 };
 
-__device__ __forceinline__ bool fit_valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
-__device__ __forceinline__ bool fin(double v) { return fabs(v) <= DBL_MAX; }
-__device__ __forceinline__ bool admissible(const double* p) {
-    return fin(p[0]) && fin(p[1]) && fin(p[2]) && fin(p[3]) && fin(p[4]) && fin(p[5]) && p[0] > 0.0 && p[3] > 0.0 && p[5] > 0.0 &&
-           p[3] * p[5] - p[4] * p[4] > 0.0;
-}
 __host__ __device__ constexpr int hidx(int i, int j) { return 7 + i * 6 - i * (i - 1) / 2 + (j - i); }   // H(i, j), i <= j, in the 28 sums
 static_assert(hidx(0, 0) == 7 && hidx(5, 5) == FIT_NSUM - 1, "F, g (6), H upper triangle row-major (21)");
 
@@ -65,19 +57,11 @@ __device__ __forceinline__ void sweep(FSmem& s, const double* pp, const unsigned
     for (unsigned q = tid; q < npos; q += FIT_T) {
         unsigned i; float fv;
         if (LDS) { i = s.idx[q]; fv = s.val[q]; }
-        else {
-            i = list[q]; fv = 0.0f;
-            if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
-            if (i >= A || !fit_valid_px(fv)) i = FIT_BAD;
-        }
-        if (i == FIT_BAD) continue;
+        else i = list_pixel(list, q, img, MW, W, A, fv);
+        if (i == LM_BAD) continue;
         const unsigned dy = i / W, dx = i - dy * W;
-        const double y = (double)fv - bkg, u = (double)dx - x0, v = (double)dy - y0;
-        const double e = exp(-0.5 * ((a * u) * u + ((2.0 * b) * u) * v + (c * v) * v));
-        const double m = pA * e, r = y - m;
         double J[6];
-        J[0] = e; J[1] = m * (a * u + b * v); J[2] = m * (b * u + c * v);
-        J[3] = ((-0.5 * m) * u) * u; J[4] = ((-m) * u) * v; J[5] = ((-0.5 * m) * v) * v;
+        const double y = (double)fv - bkg, r = y - gauss_terms(pA, x0, y0, a, b, c, (double)dx, (double)dy, J);
         acc[0] += r * r;
 #pragma unroll
         for (int ii = 0; ii < 6; ++ii) {
@@ -143,31 +127,16 @@ __device__ __forceinline__ bool lm_solve(const double* cur, const double lam, do
 
 template <bool LDS>
 __device__ void fit(FSmem& s, const FitJob& j, const FitArgs& a, double* __restrict__ out) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t MW = (size_t)a.MW;
     const float* __restrict__ img = a.img + (size_t)j.y0 * MW + (size_t)j.x0;
     const unsigned* __restrict__ list = a.list + j.list_off;
     const unsigned W = j.W, A = j.A, npos = j.npos;
     const double bkg = j.bkg;
 
-    // ---- valid pixels of the list (and, in LDS, their values)
-    unsigned np = 0;
-    for (unsigned q = tid; q < npos; q += FIT_T) {
-        unsigned i = list[q]; float fv = 0.0f;
-        if (i < A) { const unsigned yy = i / W; fv = img[(size_t)yy * MW + (i - yy * W)]; }
-        if (i >= A || !fit_valid_px(fv)) i = FIT_BAD;
-        if (LDS) { s.idx[q] = i; s.val[q] = fv; }
-        np += i != FIT_BAD;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) np += __shfl_down(np, o);
-    if (lane == 0) s.cnt[w] = np;
     if (tid < 6) { s.p[tid] = j.p0[tid]; s.pt[tid] = j.p0[tid]; }
-    if (tid == 0) { s.act = ACT_NONE; s.stop = 0; }
-    __syncthreads();
-    np = s.cnt[0];
-#pragma unroll
-    for (int k = 1; k < FIT_W; ++k) np += s.cnt[k];
+    if (tid == 0) { s.ctl.act = ACT_NONE; s.ctl.stop = 0; }
+    const unsigned np = stage_list<FIT_T, LDS>(s.val, s.idx, s.cnt, list, npos, img, MW, W, A);      // the barrier is inside
 
     const int early = !admissible(j.p0) ? 4 : np < (unsigned)FIT_MIN_PIX ? 3 : 0;     // uniform
     if (early) {
@@ -177,64 +146,27 @@ __device__ void fit(FSmem& s, const FitJob& j, const FitArgs& a, double* __restr
 
     // ---- sums at the start
     sweep<LDS>(s, s.pt, list, npos, img, MW, W, A, bkg);
-    double lam = 1e-3;
-    int status = 2, niter = a.max_iter;
-    bool small = false;
     if (tid == 0)
         for (int k = 0; k < FIT_NSUM; ++k) s.cur[k] = s.tot[k];
-
-    for (int it = 1; it <= a.max_iter; ++it) {
-        if (tid == 0) {
-            double d[6];
-            int act = ACT_NONE;
-            small = false;
-            if (lm_solve(s.cur, lam, d)) {
-                small = true;
-                double pn[6];
+    double lam;
+    int status, niter;
+    lm_iterate(s.ctl, a.max_iter, lam, status, niter,
+               [&](const double lam, bool& small) {
+                   double d[6], pn[6];
+                   if (!lm_solve(s.cur, lam, d)) return false;
+                   small = lm_trial(6, s.p, d, pn);
+                   if (!admissible(pn)) return false;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    small = small && fabs(d[k]) <= 1e-10 * (fabs(s.p[k]) + 1e-6);
-                    pn[k] = s.p[k] + d[k];
-                }
-                if (admissible(pn)) {
-                    act = ACT_SWEEP;
+                   for (int k = 0; k < 6; ++k) s.pt[k] = pn[k];
+                   return true;
+               },
+               [&] { sweep<LDS>(s, s.pt, list, npos, img, MW, W, A, bkg); },
+               [&] { return s.cur[0]; }, [&] { return s.tot[0]; },
+               [&] {
+                   for (int k = 0; k < FIT_NSUM; ++k) s.cur[k] = s.tot[k];
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) s.pt[k] = pn[k];
-                }
-            }
-            if (act == ACT_NONE) {                            // rejected without a sweep
-                if (small) { status = 0; niter = it; act = ACT_STOP; }
-                else {
-                    lam *= 10.0;
-                    if (lam > 1e12) { status = 2; niter = it; act = ACT_STOP; }
-                }
-            }
-            s.act = act;
-        }
-        __syncthreads();
-        const int act = s.act;                                // uniform (from LDS)
-        if (act == ACT_STOP) break;
-        if (act == ACT_SWEEP) {
-            sweep<LDS>(s, s.pt, list, npos, img, MW, W, A, bkg);
-            if (tid == 0) {
-                const double F = s.cur[0], Fn = s.tot[0];
-                if (Fn < F) {
-                    const bool conv = small || F - Fn <= 1e-14 * F;
-                    for (int k = 0; k < FIT_NSUM; ++k) s.cur[k] = s.tot[k];
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) s.p[k] = s.pt[k];
-                    lam = fmax(lam / 10.0, 1e-12);
-                    if (conv) { status = 0; niter = it; s.stop = 1; }
-                } else if (small) { status = 0; niter = it; s.stop = 1; }
-                else {
-                    lam *= 10.0;
-                    if (lam > 1e12) { status = 2; niter = it; s.stop = 1; }
-                }
-            }
-        }
-        __syncthreads();
-        if (s.stop) break;                                    // uniform (from LDS)
-    }
+                   for (int k = 0; k < 6; ++k) s.p[k] = s.pt[k];
+               });
     if (tid == 0) {
         out[0] = (double)status; out[1] = (double)niter; out[2] = (double)np; out[3] = s.cur[0]; out[4] = lam;
         for (int k = 0; k < 6; ++k) out[5 + k] = s.p[k];

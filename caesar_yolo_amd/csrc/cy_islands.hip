@@ -19,7 +19,7 @@
 // Workspace labels are read and written with agent-scope atomics (they go to L2, never to a stale line of the vector cache).
 // Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
 // fixed association, so two runs give the same bits.  The atomics are integer minima / ors on labels only.
-#include "cy_label.h"                   // Lab, Win, label_window: sweeps 1-4, shared with cy_deblend.hip
+#include "cy_label.h"                   // Lab, label_window: sweeps 1-4, shared with cy_deblend.hip; Win, window_of (cy_px.h)
 
 #pragma clang fp contract(off)          // w * (dx * dx) is rounded before it is added, as the float64 definition does
 
@@ -100,13 +100,10 @@ __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const W
 __global__ __launch_bounds__(INT) void islands_kernel(const IslandArgs a) {
     __shared__ ISmem s;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int* wn = a.win + (size_t)b * 4;
-    // the host's windows are already inside the image; clamped again so that no index can leave it whatever arrives here (a
-    // clamp only shrinks a window, so the label and mask slices the host sized still hold it)
-    const int bx0 = max(wn[0], 0), bx1 = min(wn[1], a.MW - 1), by0 = max(wn[2], 0), by1 = min(wn[3], a.MH - 1);
+    Win w;
+    const long long area = window_of(a.win + (size_t)b * 4, a.MW, a.MH, w);       // held inside the image (cy_px.h)
     double* out = a.out + (size_t)b * ISL_FIELDS;
     const long long wo = a.off[(size_t)b * 2], mo = a.off[(size_t)b * 2 + 1];
-    const long long area = bx1 < bx0 || by1 < by0 ? 0 : (long long)(bx1 - bx0 + 1) * (by1 - by0 + 1);
     const bool lds = wo < 0;
     if (area == 0 || area > ISL_MAX_AREA || wo == ISL_OFF_TOO_LARGE) {
         // empty window: nothing to measure.  Above the supported maximum: status 1, nothing measured
@@ -120,8 +117,6 @@ __global__ __launch_bounds__(INT) void islands_kernel(const IslandArgs a) {
         if (tid < ISL_FIELDS) out[tid] = __longlong_as_double(0x7FF8000000000000LL);
         return;
     }
-    Win w;
-    w.x0 = bx0; w.y0 = by0; w.W = (unsigned)(bx1 - bx0 + 1); w.H = (unsigned)(by1 - by0 + 1); w.A = (unsigned)area;
     const double seed = a.thr[(size_t)b * 3], merge = a.thr[(size_t)b * 3 + 1], bkg = a.thr[(size_t)b * 3 + 2];
     unsigned char* mask = a.mask ? a.mask + mo : nullptr;
     if (lds) islands<true>(s, Lab<true>{s.lab}, a, w, seed, merge, bkg, mask, out);

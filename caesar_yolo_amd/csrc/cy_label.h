@@ -8,8 +8,7 @@
 // decreasing labels (at most A steps), and unite() lowers the larger of its two roots with every retry (at most A retries).
 // Workspace labels are read and written with agent-scope atomics (they go to L2, never to a stale line of the vector cache).
 #pragma once
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_px.h"                      // valid_px, Win, window_of
 #include <climits>
 
 namespace cy {
@@ -23,8 +22,6 @@ struct LabRed {                         // reduction scratch of label_window
     unsigned cnt[INW];
     float pv[INW]; unsigned pi[INW];
 };
-
-__device__ __forceinline__ bool valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
 
 // label accesses: LDS (workgroup scope) or this workgroup's slice of the global workspace (agent scope: served by L2)
 template <bool LDS> struct Lab {
@@ -49,8 +46,6 @@ template <bool LDS> struct Lab {
         }
     }
 };
-
-struct Win { int x0, y0; unsigned W, H, A; };
 
 // Sweeps 1-4.  img: first pixel of the window, MW: row pitch of the image.  -> the number of seeds; pv / pi: the window's peak
 // pixel (largest valid pixel, first in row-major order; pi == NOLAB when there is no valid pixel).  No seed: returns 0 right

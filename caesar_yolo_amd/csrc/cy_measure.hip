@@ -6,15 +6,12 @@
 // One workgroup of 256 threads per source; the integer windows are solved on the host (launch_measure's caller) from the float64
 // boxes.  Neither the box window nor the ring is assumed to fit LDS: every pass re-reads its pixels (a ring of a catalog source
 // is a few KiB and stays in the vector cache / L2), 64-bit pixel offsets throughout (the 32k mosaic is one 4 GiB allocation).
-// Medians are radix selections, 8 bits per pass over order-preserving 64-bit keys, 256-bin histograms in LDS:
-//   pixels      fkey(v) in the high word                    -> 4 passes
-//   deviations  bit pattern of the non-negative float64 d   -> 8 passes
-// The selection finds the element of rank (n - 1) / 2 and how many elements are <= it; for an even n the upper middle element is
-// the same value when that count exceeds n / 2, else the smallest larger key (one more pass).
+// Medians are the exact radix selections of cy_select.h (pixels: 4 passes, deviations: 8 passes, one more for the upper middle
+// element of an even count when it is a different value); the ring hands its valid pixels to them.
 // Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
 // fixed association, so two runs give the same bits.  Nothing here is atomic outside LDS, and the LDS atomics are integer counts.
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_px.h"                      // valid_px
+#include "cy_select.h"                  // SelSmem, select_median
 #include <climits>
 
 #pragma clang fp contract(off)          // w * ix is rounded before it is added, as the float64 definition does
@@ -25,21 +22,11 @@ namespace {
 constexpr int MNT = 256, MNW = MNT / 64, MUNROLL = 4;
 
 struct MSmem {
-    unsigned hist[256];
-    unsigned wsum[MNW];
-    unsigned sel[4];                     // digit, rank inside the bin, elements below the bin, elements in the bin
-    unsigned long long umin[MNW];
+    SelSmem<MNT> sel;
     double red[4][MNW];
     unsigned cnt[MNW];
     float pv[MNW]; long long pp[MNW];
 };
-
-__device__ __forceinline__ bool valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
-__device__ __forceinline__ unsigned fkey32(float f) {                   // order-preserving float -> u32 (fkey of cy_preproc.hip)
-    const unsigned b = __float_as_uint(f);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey32_inv(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // The ring = grown window minus box window, as four rectangles walked one after the other with consecutive lanes on consecutive
 // ix: top and bottom bands over the grown width, then the left and right flanks beside the box rows.
@@ -55,76 +42,16 @@ __device__ __forceinline__ float ring_value(const float* __restrict__ img, size_
     else { const unsigned j = i - r.nT - r.nB - r.nL; iy = r.by0 + (int)(j / r.rw); ix = r.bx1 + 1 + (int)(j % r.rw); }
     return img[(size_t)iy * MW + (size_t)ix];
 }
-template <int MODE> __device__ __forceinline__ unsigned long long ring_key(float v, double bkg) {
-    if constexpr (MODE == 0) return (unsigned long long)fkey32(v) << 32;
-    else return (unsigned long long)__double_as_longlong(fabs((double)v - bkg));      // d >= 0: orders like its bit pattern
-}
-template <int MODE> __device__ __forceinline__ double key_value(unsigned long long k) {
-    if constexpr (MODE == 0) return (double)fkey32_inv((unsigned)(k >> 32));
-    else return __longlong_as_double((long long)k);
-}
-
-// f(key) for every valid pixel of the ring; MUNROLL independent loads in flight per lane (an out-of-range slot reads as 0 = blank)
-template <int MODE, typename F>
-__device__ __forceinline__ void ring_for_each(const float* __restrict__ img, size_t MW, const Ring& r, double bkg, F f) {
+// f(v) for every valid pixel of the ring; MUNROLL independent loads in flight per lane (an out-of-range slot reads as 0 = blank)
+template <typename F>
+__device__ __forceinline__ void ring_for_each(const float* __restrict__ img, size_t MW, const Ring& r, F f) {
     for (unsigned i0 = threadIdx.x; i0 < r.n; i0 += MUNROLL * MNT) {
         float v[MUNROLL];
 #pragma unroll
         for (int u = 0; u < MUNROLL; ++u) { const unsigned i = i0 + u * MNT; v[u] = i < r.n ? ring_value(img, MW, r, i) : 0.0f; }
 #pragma unroll
-        for (int u = 0; u < MUNROLL; ++u) if (valid_px(v[u])) f(ring_key<MODE>(v[u], bkg));
+        for (int u = 0; u < MUNROLL; ++u) if (valid_px(v[u])) f(v[u]);
     }
-}
-
-// Exact median of the keys of the ring's valid pixels; n = their count (0: returns 0).  Every thread gets the result.
-template <int MODE>
-__device__ double ring_median(MSmem& s, const float* __restrict__ img, size_t MW, const Ring& r, double bkg, unsigned& n) {
-    constexpr int NP = MODE == 0 ? 4 : 8;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    unsigned long long prefix = 0;
-    unsigned k = 0, below = 0, eq = 0;
-    n = 0;
-    for (int p = 0; p < NP; ++p) {
-        const int shift = 56 - 8 * p;
-        s.hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long want = p ? prefix >> (shift + 8) : 0;
-        ring_for_each<MODE>(img, MW, r, bkg, [&](unsigned long long key) {
-            if (p == 0 || (key >> (shift + 8)) == want) atomicAdd(&s.hist[(unsigned)(key >> shift) & 255u], 1u);
-        });
-        __syncthreads();
-        const unsigned h = s.hist[tid];
-        unsigned incl = h;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-        if (lane == 63) s.wsum[w] = incl;
-        __syncthreads();
-        unsigned off = 0, total = 0;
-#pragma unroll
-        for (int j = 0; j < MNW; ++j) { const unsigned t = s.wsum[j]; if (j < w) off += t; total += t; }
-        if (p == 0) {
-            n = total;
-            if (n == 0) return 0.0;                         // uniform: `total` came from LDS
-            k = (n - 1) / 2;
-        }
-        const unsigned excl = off + incl - h;
-        if (k >= excl && k < excl + h) { s.sel[0] = (unsigned)tid; s.sel[1] = k - excl; s.sel[2] = excl; s.sel[3] = h; }
-        __syncthreads();
-        prefix |= (unsigned long long)s.sel[0] << shift;
-        k = s.sel[1]; below += s.sel[2]; eq = s.sel[3];
-    }
-    const double a = key_value<MODE>(prefix);
-    if ((n & 1u) || below + eq > n / 2) return a;           // odd count, or the upper middle element has the same value
-    unsigned long long m = ~0ull;                           // smallest key above `prefix`
-    ring_for_each<MODE>(img, MW, r, bkg, [&](unsigned long long key) { if (key > prefix && key < m) m = key; });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_down(m, o); m = t < m ? t : m; }
-    if (lane == 0) s.umin[w] = m;
-    __syncthreads();
-    m = s.umin[0];
-#pragma unroll
-    for (int j = 1; j < MNW; ++j) m = s.umin[j] < m ? s.umin[j] : m;
-    return (a + key_value<MODE>(m)) / 2.0;
 }
 
 __global__ __launch_bounds__(MNT) void measure_kernel(const MeasureArgs a) {
@@ -148,8 +75,9 @@ __global__ __launch_bounds__(MNT) void measure_kernel(const MeasureArgs a) {
     r.n = r.nT + r.nB + r.nL + r.rw * bh;
 
     unsigned nring = 0, n2 = 0;
-    double bkg = ring_median<0>(s, a.img, MW, r, 0.0, nring), rms = 0.0;
-    if (nring) rms = 1.4826 * ring_median<1>(s, a.img, MW, r, bkg, n2);
+    const auto ring = [&](auto f) { ring_for_each(a.img, MW, r, f); };
+    double bkg = select_median<0, MNT>(s.sel, ring, 0.0, 0xFFFFFFFFu, nring), rms = 0.0;
+    if (nring) rms = 1.4826 * select_median<1, MNT>(s.sel, ring, bkg, 0xFFFFFFFFu, n2);
 
     // ---- box window: counts, peak, moments
     double sum = 0.0, sw = 0.0, swx = 0.0, swy = 0.0;

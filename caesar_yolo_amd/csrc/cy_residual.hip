@@ -22,8 +22,7 @@
 //   chunks      over the tile's list entries, tile_off[t] .. tile_off[t + 1] (the whole table holds at most 2^27), 64 at a time
 //   components  at most 64 per chunk, four pixels each
 //   statistics  over the A <= 2^24 pixels of the window, 256 at a time; 6 shuffle steps and 4 waves
-#include "cy_kernels.h"
-#include <cfloat>
+#include "cy_px.h"                      // valid_px, Win, window_of
 #include <cstdint>
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
@@ -35,8 +34,6 @@ constexpr int RND_T = 256, RND_GRID_MAX = 1 << 20;
 constexpr int RES_T = 256, RES_W = RES_T / 64;
 static_assert(RND_T == (RND_TILE / 4) * RND_TILE, "one thread per four pixels of a tile row");
 static_assert(RND_CHUNK <= RND_T, "thread j loads entry j of a chunk");
-
-__device__ __forceinline__ bool res_valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
 
 struct RSmem {
     double par[RND_CHUNK][6];
@@ -89,7 +86,7 @@ __device__ __forceinline__ void render_tile(RSmem& s, const RenderArgs& a, const
             const float px[4] = {pv.x, pv.y, pv.z, pv.w}, bk[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                if (res_valid_px(px[t])) ro[t] = (float)(((double)px[t] - (a.bkg ? (double)bk[t] : 0.0)) - acc[t]);
+                if (valid_px(px[t])) ro[t] = (float)(((double)px[t] - (a.bkg ? (double)bk[t] : 0.0)) - acc[t]);
             *reinterpret_cast<float4*>(a.resid + p) = make_float4(ro[0], ro[1], ro[2], ro[3]);
         }
         if (a.model) *reinterpret_cast<float4*>(a.model + p) = make_float4(mo[0], mo[1], mo[2], mo[3]);
@@ -100,7 +97,7 @@ __device__ __forceinline__ void render_tile(RSmem& s, const RenderArgs& a, const
             if (a.resid) {
                 const float px = a.img[p + t];
                 const double bk = a.bkg ? (double)a.bkg[p + t] : 0.0;
-                a.resid[p + t] = res_valid_px(px) ? (float)(((double)px - bk) - acc[t]) : 0.0f;
+                a.resid[p + t] = valid_px(px) ? (float)(((double)px - bk) - acc[t]) : 0.0f;
             }
             if (a.model) a.model[p + t] = mo[t];
         }
@@ -124,18 +121,16 @@ struct StSmem {
 __global__ __launch_bounds__(RES_T) void residual_stats_kernel(const ResidualArgs a) {
     __shared__ StSmem s;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int* wn = a.win + (size_t)b * 4;
-    // the host's windows are already inside the image; clamped again so that no index can leave it whatever arrives here (a clamp
-    // only shrinks a window, so the mask slice the host checked still holds it)
-    const int bx0 = max(wn[0], 0), bx1 = min(wn[1], a.MW - 1), by0 = max(wn[2], 0), by1 = min(wn[3], a.MH - 1);
+    Win wn;
+    const long long area = window_of(a.win + (size_t)b * 4, a.MW, a.MH, wn);      // held inside the image (cy_px.h)
     double* out = a.out + (size_t)b * RES_FIELDS;
-    const long long area = bx1 < bx0 || by1 < by0 ? 0 : (long long)(bx1 - bx0 + 1) * (by1 - by0 + 1);
     const bool large = area > ISL_MAX_AREA || a.off[(size_t)b * 2] == ISL_OFF_TOO_LARGE;
     if (area == 0 || large) {                                 // empty: nothing to measure.  Above the supported maximum: status 1
         if (tid < RES_FIELDS) out[tid] = tid == 0 ? (large && area ? 1.0 : 0.0) : (tid == 8 || tid == 9) ? -1.0 : 0.0;
         return;
     }
-    const unsigned W = (unsigned)(bx1 - bx0 + 1), A = (unsigned)area;
+    const int bx0 = wn.x0, by0 = wn.y0;
+    const unsigned W = wn.W, A = wn.A;
     const size_t MW = (size_t)a.MW, org = (size_t)by0 * MW + (size_t)bx0;
     const unsigned char* __restrict__ mask = a.mask + a.off[(size_t)b * 2 + 1];
     const double bkg = a.bkg[b];
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(RES_T) void residual_stats_kernel(const ResidualArg
         const unsigned dy = i / W, dx = i - dy * W;
         const size_t p = org + (size_t)dy * MW + dx;
         const float px = a.img[p];
-        if (!res_valid_px(px)) continue;
+        if (!valid_px(px)) continue;
         const double md = (double)a.model[p], r = ((double)px - bkg) - md, rr = r * r;
         ++nw; Sw += r; Qw += rr;
         if (mask[i]) {

@@ -35,27 +35,18 @@
 // SIMD) the register-resident weights leave no room for the accumulators + read ring without spills.  Next idea: cv1 and cv2
 // on different waves of a SIMD (producer / consumer on a double-buffered T, 4 x 32-pixel patches so that it fits in LDS).
 #include "cy_kernels.h"
+#include "cy_conv_dev.h"
 #include <cstring>
 
 namespace cy {
 
-typedef _Float16 f16;
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-constexpr unsigned OOB = 0xFFFFFF00u;
 constexpr int OH = 8, OW = 32;                    // output patch
 constexpr int TH = OH + 2, TP = 36;               // T: 10 rows, pitch 36 (34 used): 2 * pitch = 0 mod 8 keeps the swizzle phase of a row pair
 constexpr int YH = OH + 4, YP = 36;               // Y: 12 x 36
 constexpr int YPIECES = 56, YBYTES = YPIECES * 1024;          // 448 rows of 128 B (432 used; the tail is zero-filled and read by masked lanes)
 constexpr int TBYTES = TH * TP * 128;
 constexpr int LDS_BYTES = 2 * YBYTES + TBYTES;    // 160768 <= 163840
-
-__device__ __forceinline__ float silu_fast(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
-}
 }  // namespace
 
 template <int NWAVE>
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(NWAVE * 64) void bneck64_kernel(const BneckArgs a) 
             const int y = y0 + ry, x = x0 + rx;
             const int q = (lane & 7) ^ (r & 7);
             const bool ok = ry < YH && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            const unsigned off = ok ? (unsigned)(((b * H + y) * W + x) * a.in_ct + a.in_coff + q * 8) * 2u : OOB;
+            const unsigned off = ok ? (unsigned)(((b * H + y) * W + x) * a.in_ct + a.in_coff + q * 8) * 2u : CY_OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lds_void*)(Yl + buf * YBYTES + pc * 1024), 16, off, 0, 0, 0);
         }
     };
@@ -252,12 +243,6 @@ __global__ __launch_bounds__(NWAVE * 64) void bneck64_kernel(const BneckArgs a) 
 }
 
 hipError_t launch_bneck64(const BneckArgs& a, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(bneck64_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(bneck64_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_set = true;
-    }
     const int npatch = a.B * ((a.H + OH - 1) / OH) * ((a.W + OW - 1) / OW);
     int cus = 256;
     { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
@@ -265,9 +250,10 @@ hipError_t launch_bneck64(const BneckArgs& a, hipStream_t s) {
     BneckArgs b2 = a;
     b2.dbg = dev_knob("CY_BK_DBG", 0);          // ablation bits of diagnostic builds: 1 no stores, 2 no halo DMA after the first, 4 no cv1, 8 no cv2
     static const int nwave = env_knob("CY_BNECK_WAVES", 4);
-    if (nwave == 8) hipLaunchKernelGGL(bneck64_kernel<8>, dim3(grid), dim3(512), LDS_BYTES, s, b2);
-    else hipLaunchKernelGGL(bneck64_kernel<4>, dim3(grid), dim3(256), LDS_BYTES, s, b2);
-    return hipGetLastError();
+    lds_cap<bneck64_kernel<4>>(LDS_BYTES);                          // both before the first launch of either
+    lds_cap<bneck64_kernel<8>>(LDS_BYTES);
+    if (nwave == 8) return launch_lds<bneck64_kernel<8>>(dim3(grid), dim3(512), LDS_BYTES, LDS_BYTES, s, b2);
+    return launch_lds<bneck64_kernel<4>>(dim3(grid), dim3(256), LDS_BYTES, LDS_BYTES, s, b2);
 }
 
 // W1, W2: [64][64][3][3] fp32 (folded Conv+BN) -> dst[conv][block nb][k-step ks][lane] x 8 halves:

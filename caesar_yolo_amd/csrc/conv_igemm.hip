@@ -17,23 +17,18 @@
 // writes 0).  The LDS image is double-buffered and XOR-swizzled through the SOURCE address so that ds_read_b128
 // fragment reads are conflict-free (slot = chunk ^ (row & 7): conflict-free for any 16 consecutive rows, whatever the first row -- the 3x3 taps of the
 // halo kernels read at arbitrary row offsets; a 256-byte bank row holds two 128-byte tile rows).
+//
+// This file holds the implicit-GEMM kernels, their launchers and the dispatch (conv_variant, launch_conv) and nothing else: the
+// device prelude and the shared epilogue steps are in cy_conv_dev.h, the stem kernels in conv_stem.hip, weight packing in
+// conv_weights.hip, the SPPF pool with the other non-GEMM layer operators in cy_extra.hip.
 #include "cy_kernels.h"
+#include "cy_conv_dev.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 namespace cy {
-
-typedef _Float16 f16;
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-#define CY_OOB 0xFFFFFF00u
-#define CY_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 
 // developer diagnostics: per-segment s_memtime sums of the 3x3 kernels' stage loop, summed over waves.  Compiled in only
 // with -DCY_STAMPS_ENABLED=1 (then enabled at run time by CY_DBG bit 6); a stamped build is for SHARES, not for timing.
@@ -54,114 +49,10 @@ __device__ __forceinline__ unsigned long long stamp_real() {       // constant 1
     return t;
 }
 
-__device__ __forceinline__ float silu_exact(float x) { return x / (1.0f + expf(-x)); }
-// fp16 context: x * sigmoid(x) with the hardware exp2/rcp (1 ulp each; the result is rounded to fp16 anyway):
-// 5 VALU instructions per element instead of the ~50 of an IEEE-exact division
-__device__ __forceinline__ float silu_fast(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f));
-}
-// The epilogue of the fp16 kernels for the 16 values a lane holds of one pixel (four accumulators of four channels): bias +
-// SiLU with two values per VALU instruction where the ISA has a packed fp32 form (add, mul; exp2 and rcp stay scalar), and
-// the activation switch as ONE uniform branch (written per value it becomes a v_cndmask per value behind an unconditional SiLU).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void bias_act16(const f32x4& a0, const f32x4& a1, const f32x4& a2, const f32x4& a3, const float (&bv)[16],
-                                           bool act, float (&v)[16]) {
-    const f32x4 acc[4] = {a0, a1, a2, a3};
-    if (act) {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 t = f32x2{acc[ni][2 * h], acc[ni][2 * h + 1]} + f32x2{bv[ni * 4 + 2 * h], bv[ni * 4 + 2 * h + 1]};
-                f32x2 e = t * f32x2{-1.44269504088896341f, -1.44269504088896341f};
-                e = f32x2{__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])} + f32x2{1.0f, 1.0f};
-                t = t * f32x2{__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-                v[ni * 4 + 2 * h] = t[0]; v[ni * 4 + 2 * h + 1] = t[1];
-            }
-    } else {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[ni * 4 + j] = acc[ni][j] + bv[ni * 4 + j];
-    }
-}
-
-// fp16x3 context: the same epilogue with the accumulator first multiplied by the power of two that undoes the weight scale of its
-// output channel, and the result stored as two fp16 halves hi = fp16(v), lo = fp16(v - hi) (lo_off halves behind hi)
-__device__ __forceinline__ void scale_bias_act16(const f32x4& a0, const f32x4& a1, const f32x4& a2, const f32x4& a3, const float (&bv)[16],
-                                                 const float (&sc)[16], bool act, float (&v)[16]) {
-    const f32x4 acc[4] = {a0, a1, a2, a3};
-    if (act) {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 t = f32x2{acc[ni][2 * h], acc[ni][2 * h + 1]} * f32x2{sc[ni * 4 + 2 * h], sc[ni * 4 + 2 * h + 1]} +
-                          f32x2{bv[ni * 4 + 2 * h], bv[ni * 4 + 2 * h + 1]};
-                f32x2 e = t * f32x2{-1.44269504088896341f, -1.44269504088896341f};
-                e = f32x2{__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])} + f32x2{1.0f, 1.0f};
-                t = t * f32x2{__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-                v[ni * 4 + 2 * h] = t[0]; v[ni * 4 + 2 * h + 1] = t[1];
-            }
-    } else {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[ni * 4 + j] = acc[ni][j] * sc[ni * 4 + j] + bv[ni * 4 + j];
-    }
-}
-__device__ __forceinline__ void store_split16(f16* dst, int lo_off, const float (&v)[16]) {
-    f16x8 h0, h1, l0, l1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        h0[j] = (f16)v[j]; h1[j] = (f16)v[8 + j];
-        l0[j] = (f16)(v[j] - (float)h0[j]); l1[j] = (f16)(v[8 + j] - (float)h1[j]);
-    }
-    *reinterpret_cast<f16x8*>(dst) = h0;
-    *reinterpret_cast<f16x8*>(dst + 8) = h1;
-    *reinterpret_cast<f16x8*>(dst + lo_off) = l0;
-    *reinterpret_cast<f16x8*>(dst + lo_off + 8) = l1;
-}
-__device__ __forceinline__ void store_split1(f16* dst, int lo_off, float v) {
-    const f16 h = (f16)v;
-    dst[0] = h; dst[lo_off] = (f16)(v - (float)h);
-}
-// virtual K chunk of the fp16x3 passes [x_lo | x_hi | x_hi] (against weights [w_hi | w_lo | w_hi]) -> physical chunk; lo = 1 in the
-// first pass.  The two small cross terms come FIRST: the fp32 accumulator of the MFMA rounds at every step by an amount relative
-// to its current magnitude, so they are summed while it is still ~2^-11 of the final value (their rounding is then negligible)
-// and the x_hi * w_hi chain runs last, exactly as long as in the fp16 context.
-__device__ __forceinline__ int x3_chunk(int v, int per_pass, int& lo) {
-    lo = v < per_pass;
-    if (v >= 2 * per_pass) return v - 2 * per_pass;
-    if (v >= per_pass) return v - per_pass;
-    return v;
-}
-
-template <typename T> struct Elem;
-template <> struct Elem<f16> { static constexpr int BKE = 64, EPC = 8, ES = 2; };
-template <> struct Elem<float> { static constexpr int BKE = 32, EPC = 4, ES = 4; };
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    // blocks b and b+8 share an XCD (round-robin dispatch): give each XCD a contiguous run of tiles so that
-    // neighbouring tiles (same activation rows, different channel blocks) hit one L2.  Bijective for any nwg.
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 // NSTAGE = 2: the slab for step s+1 is requested while step s computes and drained at the barrier (two workgroups of
 // four waves per CU hide each other's drains).  NSTAGE = 3 (the 256x128 tile, eight waves, one workgroup per CU): slabs
 // are requested TWO steps ahead and the wait before a barrier is a counted vmcnt that leaves the newest request in
 // flight, so an L2 round trip (about one step's worth of MFMA time for K-slabs of 64) is off the critical path.
-// Non-template wrappers: inside a template kernel a buffer builtin whose soffset is not a constant makes this clang drop
-// the kernel's host-side instantiation without a diagnostic; called through these, the builtin is never value-dependent.
-typedef __attribute__((address_space(3))) void lds_ptr_t;
-__device__ __forceinline__ void dma_piece(__amdgpu_buffer_rsrc_t rs, lds_ptr_t* dst, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff, soff, 0, 0);     // soffset is NOT range-checked (voffset is)
-}
-__device__ __forceinline__ u32x4 load_b128(__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
-}
-
 template <typename T, int WM, int WN, int MI, int NSTAGE = 2, bool SPLIT = false>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void conv_igemm_kernel(const ConvArgs a) {
     static_assert(!SPLIT || sizeof(T) == 2, "fp16x3: fp16 operands");
@@ -368,25 +259,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void conv_ige
         if constexpr (SPLIT) {
             scale_bias_act16(acc[0][mi], acc[1][mi], acc[2][mi], acc[3][mi], bv, sc, a.act != 0, v);
             if (!a.out_f32) {
-                f16* dst = reinterpret_cast<f16*>(a.out) + opix * a.out_ct + a.out_coff + cbase;
-                const f16* rp = a.res ? reinterpret_cast<const f16*>(a.res) + (long)m * a.res_ct + a.res_coff + cbase : nullptr;
-                if (cbase + 16 <= a.Cout) {
-                    if (rp) {
-                        const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
-                        const f16x8 q0v = *reinterpret_cast<const f16x8*>(rp + a.res_lo), q1v = *reinterpret_cast<const f16x8*>(rp + a.res_lo + 8);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { v[j] += (float)r0v[j] + (float)q0v[j]; v[8 + j] += (float)r1v[j] + (float)q1v[j]; }
-                    }
-                    store_split16(dst, a.out_lo, v);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if (cbase + j >= a.Cout) continue;
-                        float x = v[j];
-                        if (rp) x += (float)rp[j] + (float)rp[a.res_lo + j];
-                        store_split1(dst + j, a.out_lo, x);
-                    }
-                }
+                store_px_split(reinterpret_cast<f16*>(a.out), opix * a.out_ct + a.out_coff + cbase, a.out_lo, reinterpret_cast<const f16*>(a.res),
+                               (long)m * a.res_ct + a.res_coff + cbase, a.res_lo, cbase, a.Cout, v, LoadRes{});
                 continue;
             }
         } else {
@@ -399,35 +273,29 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4 ? 2 : 1)) void conv_ige
                 v[ni * 4 + j] = x;
             }
         }
+        if constexpr (sizeof(T) == 2) {
+            if (!a.out_f32) {
+                store_px(reinterpret_cast<f16*>(a.out), opix * a.out_ct + a.out_coff + cbase, reinterpret_cast<const f16*>(a.res),
+                         (long)m * a.res_ct + a.res_coff + cbase, cbase, a.Cout, v, LoadRes{});
+                continue;
+            }
+        }
+        // what is left: the fp32 context, and fp32 prediction rows (out_f32) from fp16 operands
         const bool full = (cbase + 16 <= a.Cout) && !a.out_f32;
         if (full) {
             T* dst = reinterpret_cast<T*>(a.out) + opix * a.out_ct + a.out_coff + cbase;
             if (a.res) {
                 const T* rp = reinterpret_cast<const T*>(a.res) + (long)m * a.res_ct + a.res_coff + cbase;
-                if constexpr (sizeof(T) == 2) {
-                    const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { v[j] += (float)r0v[j]; v[8 + j] += (float)r1v[j]; }
-                } else {
+                for (int j4 = 0; j4 < 4; ++j4) {
+                    const f32x4 rv = *reinterpret_cast<const f32x4*>(rp + 4 * j4);
 #pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) {
-                        const f32x4 rv = *reinterpret_cast<const f32x4*>(rp + 4 * j4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[4 * j4 + j] += rv[j];
-                    }
+                    for (int j = 0; j < 4; ++j) v[4 * j4 + j] += rv[j];
                 }
             }
-            if constexpr (sizeof(T) == 2) {
-                f16x8 o0, o1;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { o0[j] = (f16)v[j]; o1[j] = (f16)v[8 + j]; }
-                *reinterpret_cast<f16x8*>(dst) = o0;
-                *reinterpret_cast<f16x8*>(dst + 8) = o1;
-            } else {
-#pragma unroll
-                for (int j4 = 0; j4 < 4; ++j4)
-                    *reinterpret_cast<f32x4*>(dst + 4 * j4) = f32x4{v[4 * j4], v[4 * j4 + 1], v[4 * j4 + 2], v[4 * j4 + 3]};
-            }
+            for (int j4 = 0; j4 < 4; ++j4)
+                *reinterpret_cast<f32x4*>(dst + 4 * j4) = f32x4{v[4 * j4], v[4 * j4 + 1], v[4 * j4 + 2], v[4 * j4 + 3]};
         } else if (a.out_f32 && !a.res && cbase + 16 <= a.Cout) {
             // fp32 head output (box logits): rows of the prediction buffer are 64+nc floats, so only dword-aligned; four
             // 16-byte stores per lane through a 4-byte-aligned vector type instead of sixteen scattered dword stores
@@ -559,43 +427,9 @@ __global__ __launch_bounds__(256) void head1x1_kernel(const ConvArgs a, const in
                 // narrow 1x1 layers inside the network (YOLO11 C3k branches, small YOLOv8 scales): fp16 (or high / low halves) into a
                 // channel slice, optional residual -- the generic kernel's epilogue, value for value
                 if (m >= M) continue;
-                f16* dst = reinterpret_cast<f16*>(a.out) + (long)m * a.out_ct + a.out_coff + cbase;
-                const f16* rp = a.res ? reinterpret_cast<const f16*>(a.res) + (long)m * a.res_ct + a.res_coff + cbase : nullptr;
-                if (cbase + 16 <= a.Cout) {
-                    if (rp) {
-                        const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
-                        if constexpr (SPLIT) {
-                            const f16x8 q0v = *reinterpret_cast<const f16x8*>(rp + a.res_lo), q1v = *reinterpret_cast<const f16x8*>(rp + a.res_lo + 8);
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { o[j] += (float)r0v[j] + (float)q0v[j]; o[8 + j] += (float)r1v[j] + (float)q1v[j]; }
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) { o[j] += (float)r0v[j]; o[8 + j] += (float)r1v[j]; }
-                        }
-                    }
-                    if constexpr (SPLIT) {
-                        store_split16(dst, a.out_lo, o);
-                    } else {
-                        f16x8 o0, o1;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { o0[j] = (f16)o[j]; o1[j] = (f16)o[8 + j]; }
-                        *reinterpret_cast<f16x8*>(dst) = o0;
-                        *reinterpret_cast<f16x8*>(dst + 8) = o1;
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if (cbase + j >= a.Cout) continue;
-                        float xo = o[j];
-                        if constexpr (SPLIT) {
-                            if (rp) xo += (float)rp[j] + (float)rp[a.res_lo + j];
-                            store_split1(dst + j, a.out_lo, xo);
-                        } else {
-                            if (rp) xo += (float)rp[j];
-                            dst[j] = (f16)xo;
-                        }
-                    }
-                }
+                const long oidx = (long)m * a.out_ct + a.out_coff + cbase, ridx = (long)m * a.res_ct + a.res_coff + cbase;
+                if constexpr (SPLIT) store_px_split(reinterpret_cast<f16*>(a.out), oidx, a.out_lo, reinterpret_cast<const f16*>(a.res), ridx, a.res_lo, cbase, a.Cout, o, LoadRes{});
+                else store_px(reinterpret_cast<f16*>(a.out), oidx, reinterpret_cast<const f16*>(a.res), ridx, cbase, a.Cout, o, LoadRes{});
                 continue;
             }
             if (tstore) {
@@ -988,29 +822,8 @@ __global__ __launch_bounds__(WM * 128) void conv3x3_halo_kernel(const ConvArgs a
         const long pix = ((long)b * H + y) * W + x;
         float v[16];
         bias_act16(acc[0][mi], acc[1][mi], acc[2][mi], acc[3][mi], bv, a.act != 0, v);
-        if (cbase + 16 <= a.Cout) {
-            f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-            if (a.res) {
-                const f16* rp = reinterpret_cast<const f16*>(a.res) + pix * a.res_ct + a.res_coff + cbase;
-                const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { v[j] += (float)r0v[j]; v[8 + j] += (float)r1v[j]; }
-            }
-            f16x8 o0, o1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v[j]; o1[j] = (f16)v[8 + j]; }
-            *reinterpret_cast<f16x8*>(dst) = o0;
-            *reinterpret_cast<f16x8*>(dst + 8) = o1;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int c = cbase + j;
-                if (c >= a.Cout) continue;
-                float t = v[j];
-                if (a.res) t += (float)(reinterpret_cast<const f16*>(a.res)[pix * a.res_ct + a.res_coff + c]);
-                reinterpret_cast<f16*>(a.out)[pix * a.out_ct + a.out_coff + c] = (f16)t;
-            }
-        }
+        store_px(reinterpret_cast<f16*>(a.out), pix * a.out_ct + a.out_coff + cbase, reinterpret_cast<const f16*>(a.res),
+                 pix * a.res_ct + a.res_coff + cbase, cbase, a.Cout, v, LoadRes{});
     }
 }
 
@@ -1183,34 +996,8 @@ __global__ __launch_bounds__(512) void conv3x3_pp_kernel(const ConvArgs a) {
                 if (a.act) t = silu_fast(t);
                 v[ni * 4 + j] = t;
             }
-        if (cbase + NI * 4 <= a.Cout) {
-            f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-            if (a.res) {
-                const f16* rp = reinterpret_cast<const f16*>(a.res) + pix * a.res_ct + a.res_coff + cbase;
-#pragma unroll
-                for (int h8 = 0; h8 < NI / 2; ++h8) {
-                    const f16x8 rv = *reinterpret_cast<const f16x8*>(rp + 8 * h8);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[8 * h8 + j] += (float)rv[j];
-                }
-            }
-#pragma unroll
-            for (int h8 = 0; h8 < NI / 2; ++h8) {
-                f16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (f16)v[8 * h8 + j];
-                *reinterpret_cast<f16x8*>(dst + 8 * h8) = o;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NI * 4; ++j) {
-                const int c = cbase + j;
-                if (c >= a.Cout) continue;
-                float t = v[j];
-                if (a.res) t += (float)(reinterpret_cast<const f16*>(a.res)[pix * a.res_ct + a.res_coff + c]);
-                reinterpret_cast<f16*>(a.out)[pix * a.out_ct + a.out_coff + c] = (f16)t;
-            }
-        }
+        store_px(reinterpret_cast<f16*>(a.out), pix * a.out_ct + a.out_coff + cbase, reinterpret_cast<const f16*>(a.res),
+                 pix * a.res_ct + a.res_coff + cbase, cbase, a.Cout, v, LoadRes{});
     }
 }
 
@@ -1218,14 +1005,8 @@ template <int NI>
 static hipError_t launch_pp(const ConvArgs& a, hipStream_t s) {
     constexpr int BN = 2 * NI * 16, PR = 18 * 18, NWI = (PR + 7) / 8;
     const size_t lds = 2 * (NWI + 1) * 1024 + 4 * BN * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_pp_kernel<NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int blocks = a.B * ((a.Hi + 15) / 16) * ((a.Wi + 15) / 16) * ((pad64(a.Cout) + BN - 1) / BN);
-    hipLaunchKernelGGL((conv3x3_pp_kernel<NI>), dim3(blocks), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3x3_pp_kernel<NI>>(dim3(blocks), dim3(512), lds, lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 s1, Cin = 64: persistent
@@ -1464,21 +1245,16 @@ template <int KC>
 static hipError_t launch_c64(const ConvArgs& a, hipStream_t s) {
     constexpr int RPP = 1024 / (KC * 2), NWI = (18 * 18 + RPP - 1) / RPP;
     const size_t lds = 9 * 64 * KC * 2 + 2 * (NWI + 1) * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<KC, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<KC, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<KC, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<KC, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    lds_cap<conv3x3_c64_kernel<KC, true, false>>(lds);        // all four before the first launch of any
+    lds_cap<conv3x3_c64_kernel<KC, true, true>>(lds);
+    lds_cap<conv3x3_c64_kernel<KC, false, false>>(lds);
+    lds_cap<conv3x3_c64_kernel<KC, false, true>>(lds);
     const int npatch = a.B * ((a.Hi + 15) / 16) * ((a.Wi + 15) / 16);
-    const int grid = npatch < 256 ? npatch : 256;                                  // one persistent workgroup per CU
-    if (a.act && a.res) hipLaunchKernelGGL((conv3x3_c64_kernel<KC, true, true>), dim3(grid), dim3(512), lds, s, a);
-    else if (a.act) hipLaunchKernelGGL((conv3x3_c64_kernel<KC, true, false>), dim3(grid), dim3(512), lds, s, a);
-    else if (a.res) hipLaunchKernelGGL((conv3x3_c64_kernel<KC, false, true>), dim3(grid), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv3x3_c64_kernel<KC, false, false>), dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError();
+    const dim3 grid(npatch < 256 ? npatch : 256), block(512);                      // one persistent workgroup per CU
+    if (a.act && a.res) return launch_lds<conv3x3_c64_kernel<KC, true, true>>(grid, block, lds, lds, s, a);
+    if (a.act) return launch_lds<conv3x3_c64_kernel<KC, true, false>>(grid, block, lds, lds, s, a);
+    if (a.res) return launch_lds<conv3x3_c64_kernel<KC, false, true>>(grid, block, lds, lds, s, a);
+    return launch_lds<conv3x3_c64_kernel<KC, false, false>>(grid, block, lds, lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 s1, two taps per barrier
@@ -1636,43 +1412,16 @@ __global__ __launch_bounds__(512) void conv3x3_halo2_kernel(const ConvArgs a) {
         const long pix = ((long)b * H + y) * W + x;
         float v[16];
         bias_act16(acc[0][mi], acc[1][mi], acc[2][mi], acc[3][mi], bv, a.act != 0, v);
-        if (cbase + 16 <= a.Cout) {
-            f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-            if (a.res) {
-                const f16* rp = reinterpret_cast<const f16*>(a.res) + pix * a.res_ct + a.res_coff + cbase;
-                const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { v[j] += (float)r0v[j]; v[8 + j] += (float)r1v[j]; }
-            }
-            f16x8 o0, o1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v[j]; o1[j] = (f16)v[8 + j]; }
-            *reinterpret_cast<f16x8*>(dst) = o0;
-            *reinterpret_cast<f16x8*>(dst + 8) = o1;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int c = cbase + j;
-                if (c >= a.Cout) continue;
-                float t = v[j];
-                if (a.res) t += (float)(reinterpret_cast<const f16*>(a.res)[pix * a.res_ct + a.res_coff + c]);
-                reinterpret_cast<f16*>(a.out)[pix * a.out_ct + a.out_coff + c] = (f16)t;
-            }
-        }
+        store_px(reinterpret_cast<f16*>(a.out), pix * a.out_ct + a.out_coff + cbase, reinterpret_cast<const f16*>(a.res),
+                 pix * a.res_ct + a.res_coff + cbase, cbase, a.Cout, v, LoadRes{});
     }
 }
 
 static hipError_t launch_halo2(const ConvArgs& a, hipStream_t s) {
     constexpr int NWI = (18 * 18 + 7) / 8, PROUNDS = (NWI + 7) / 8;
     const size_t lds = 2 * PROUNDS * 8 * 1024 + 2 * 2 * 128 * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int blocks = a.B * ((a.Hi + 15) / 16) * ((a.Wi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
-    hipLaunchKernelGGL(conv3x3_halo2_kernel, dim3(blocks), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3x3_halo2_kernel>(dim3(blocks), dim3(512), lds, lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 s1, 512 px x 128 ch
@@ -1904,11 +1653,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
         // fp16x3 epilogue: acc * oscale + bias, SiLU, residual = its high + low halves (requested two pixel fragments at a
         // time: the accumulators leave no room for more), result stored as high / low halves
         float bv[16], sc[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(bias_lds + wn * 64 + fq * 16 + j * 4);
-            bv[j * 4] = t[0]; bv[j * 4 + 1] = t[1]; bv[j * 4 + 2] = t[2]; bv[j * 4 + 3] = t[3];
-        }
+        load16(bias_lds + wn * 64 + fq * 16, bv);
 #pragma unroll
         for (int j = 0; j < 16; ++j) sc[j] = a.oscale[cbase + j];
         const bool vec = cbase + 16 <= a.Cout;
@@ -1941,28 +1686,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
                 const long pix = ((long)bb * H + y) * W + x;
                 float v[16];
                 scale_bias_act16(acc[0][mi], acc[1][mi], acc[2][mi], acc[3][mi], bv, sc, a.act != 0, v);
-                f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-                if (vec) {
-                    if (res_vec) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            v[j] += (float)rv[m][0][j] + (float)rv[m][2][j];
-                            v[8 + j] += (float)rv[m][1][j] + (float)rv[m][3][j];
-                        }
-                    }
-                    store_split16(dst, a.out_lo, v);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if (cbase + j >= a.Cout) continue;
-                        float t = v[j];
-                        if (a.res) {
-                            const f16* rp = reinterpret_cast<const f16*>(a.res) + pix * a.res_ct + a.res_coff + cbase + j;
-                            t += (float)rp[0] + (float)rp[a.res_lo];
-                        }
-                        store_split1(dst + j, a.out_lo, t);
-                    }
-                }
+                store_px_split(reinterpret_cast<f16*>(a.out), pix * a.out_ct + a.out_coff + cbase, a.out_lo, reinterpret_cast<const f16*>(a.res),
+                               pix * a.res_ct + a.res_coff + cbase, a.res_lo, cbase, a.Cout, v, rv[m]);
             }
         }
     } else {
@@ -1984,11 +1709,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
         }
     }
     float bv[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(bias_lds + wn * 64 + fq * 16 + j * 4);
-        bv[j * 4] = t[0]; bv[j * 4 + 1] = t[1]; bv[j * 4 + 2] = t[2]; bv[j * 4 + 3] = t[3];
-    }
+    load16(bias_lds + wn * 64 + fq * 16, bv);
 #pragma unroll
     for (int mi = 0; mi < MIW; ++mi) {
         const int y = y0 + wm * RPW + (mi >> 1), x = DUAL ? fr : x0 + (mi & 1) * 16 + fr;
@@ -1997,27 +1718,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(const ConvArgs a) {
         const long pix = ((long)bb * H + y) * W + x;
         float v[16];
         bias_act16(acc[0][mi], acc[1][mi], acc[2][mi], acc[3][mi], bv, a.act != 0, v);
-        if (cbase + 16 <= a.Cout) {
-            f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-            if (res_vec) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { v[j] += (float)rv[mi][0][j]; v[8 + j] += (float)rv[mi][1][j]; }
-            }
-            f16x8 o0, o1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v[j]; o1[j] = (f16)v[8 + j]; }
-            *reinterpret_cast<f16x8*>(dst) = o0;
-            *reinterpret_cast<f16x8*>(dst + 8) = o1;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int c = cbase + j;
-                if (c >= a.Cout) continue;
-                float t = v[j];
-                if (a.res) t += (float)(reinterpret_cast<const f16*>(a.res)[pix * a.res_ct + a.res_coff + c]);
-                reinterpret_cast<f16*>(a.out)[pix * a.out_ct + a.out_coff + c] = (f16)t;
-            }
-        }
+        store_px(reinterpret_cast<f16*>(a.out), pix * a.out_ct + a.out_coff + cbase, reinterpret_cast<const f16*>(a.res),
+                 pix * a.res_ct + a.res_coff + cbase, cbase, a.Cout, v, rv[mi]);
     }
     }
     // diagnostic builds: one record per workgroup (wave 0, plain stores; units of 10 ns): [0] entry -> loop (address setup, prologue
@@ -2038,15 +1740,9 @@ template <int WN, bool DUAL = false, bool SPLIT = false>
 static hipError_t launch_wide(const ConvArgs& a, hipStream_t s) {
     constexpr int PR = 18 * (DUAL ? 36 : 34), NPC = (PR + 15) / 16, PROUNDS = (NPC + 7) / 8, BN = 64 * WN;
     const size_t lds = 2 * PROUNDS * 8 * 1024 + 3 * 2 * BN * 64 + 1024;       // halo x2, weight ring, bias
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wide_kernel<true, WN, DUAL, 2, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int bx = DUAL ? (a.B + 1) / 2 : a.B * ((a.Wi + 31) / 32);
     const int blocks = bx * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + BN - 1) / BN);
-    hipLaunchKernelGGL((conv3x3_wide_kernel<true, WN, DUAL, 2, SPLIT>), dim3(blocks), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3x3_wide_kernel<true, WN, DUAL, 2, SPLIT>>(dim3(blocks), dim3(512), lds, lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------ 3x3 s1, 512 px x 128 ch, persistent
@@ -2443,17 +2139,12 @@ template <int STRIP, bool SPLIT = false>
 static hipError_t launch_widep_t(const ConvArgs& a, hipStream_t s, int total, const StripGeo& sg) {
     constexpr int PR = 18 * 34, NPC = (PR + 15) / 16, PROUNDS = STRIP ? STRIP : (NPC + 3) / 4;
     const size_t lds = 2 * PROUNDS * 4 * 1024 + 3 * 2 * 128 * 64 + 4096;        // halo x2, weight ring, bias (+ oscale) x2
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_widep_kernel<SPLIT, false, STRIP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_widep_kernel<SPLIT, true, STRIP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    lds_cap<conv3x3_widep_kernel<SPLIT, false, STRIP>>(lds);       // both before the first launch of either
+    lds_cap<conv3x3_widep_kernel<SPLIT, true, STRIP>>(lds);
     static const int ncu = [] { int dev = 0, n = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
     const int grid = total < ncu ? total : ncu;
-    if (a.res) hipLaunchKernelGGL((conv3x3_widep_kernel<SPLIT, true, STRIP>), dim3(grid), dim3(512), lds, s, a, total, sg);
-    else hipLaunchKernelGGL((conv3x3_widep_kernel<SPLIT, false, STRIP>), dim3(grid), dim3(512), lds, s, a, total, sg);
-    return hipGetLastError();
+    if (a.res) return launch_lds<conv3x3_widep_kernel<SPLIT, true, STRIP>>(dim3(grid), dim3(512), lds, lds, s, a, total, sg);
+    return launch_lds<conv3x3_widep_kernel<SPLIT, false, STRIP>>(dim3(grid), dim3(512), lds, lds, s, a, total, sg);
 }
 
 static hipError_t launch_widep(const ConvArgs& a, hipStream_t s) {
@@ -2863,15 +2554,9 @@ template <int NB, int MI, int RING, bool K3, bool SPLIT = false, int NDW = 8, bo
 static hipError_t launch_direct(const ConvArgs& a, hipStream_t s) {
     constexpr int BN = 64 * NB, BM = 8 * MI * 16;
     const size_t lds = (FUSE2 ? 4 : RING) * BN * 128 + 2048;             // weight ring (four slots for the second layer of a fused pair), bias (x2)
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_direct_kernel<NB, MI, RING, K3, SPLIT, NDW, FUSE2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int M = a.B * a.Ho * a.Wo;
     const int blocks = ((M + BM - 1) / BM) * ((pad64(a.Cout) + BN - 1) / BN);
-    hipLaunchKernelGGL((conv1x1_direct_kernel<NB, MI, RING, K3, SPLIT, NDW, FUSE2>), dim3(blocks), dim3(512), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv1x1_direct_kernel<NB, MI, RING, K3, SPLIT, NDW, FUSE2>>(dim3(blocks), dim3(512), lds, lds, s, a);
 }
 
 template <int WM, int RING>
@@ -2879,14 +2564,8 @@ static hipError_t launch_halo(const ConvArgs& a, hipStream_t s) {
     constexpr int TH = 4 * WM, NT = WM * 128;
     constexpr int PR = (TH + 2) * 18, NWI = (PR + 7) / 8, NW = NT / 64, PROUNDS = (NWI + NW - 1) / NW;
     const size_t lds = 2 * PROUNDS * NW * 1024 + RING * 128 * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<WM, RING>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const int blocks = a.B * ((a.Hi + TH - 1) / TH) * ((a.Wi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
-    hipLaunchKernelGGL((conv3x3_halo_kernel<WM, RING>), dim3(blocks), dim3(NT), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv3x3_halo_kernel<WM, RING>>(dim3(blocks), dim3(NT), lds, lds, s, a);
 }
 
 template <typename T, int WM, int WN, int MI, int NSTAGE = 2, bool SPLIT = false>
@@ -2895,14 +2574,7 @@ static hipError_t launch_t(const ConvArgs& a, hipStream_t s) {
     const int M = a.B * a.Ho * a.Wo;
     const int ntm = (M + BM - 1) / BM, ntn = (pad64(a.Cout) + BN - 1) / BN;
     const size_t lds = NSTAGE * (BM + BN) * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<T, WM, WN, MI, NSTAGE, SPLIT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, MI, NSTAGE, SPLIT>), dim3(ntm * ntn), dim3(WM * WN * 64), lds, s, a);
-    return hipGetLastError();
+    return launch_lds<conv_igemm_kernel<T, WM, WN, MI, NSTAGE, SPLIT>>(dim3(ntm * ntn), dim3(WM * WN * 64), lds, lds, s, a);
 }
 
 // head1x1_kernel: which layers it takes, and its launch -- the detect head's output 1x1s (fp32 prediction rows, no activation) and, since
@@ -2920,15 +2592,9 @@ template <bool SPLIT>
 static hipError_t launch_head(const ConvArgs& a, hipStream_t s) {
     const int nrows = head_rows(a);
     const size_t lds = (size_t)(SPLIT ? a.split : 1) * (a.Cin / 64) * nrows * 128 + (a.Cout == 64 && a.out_f32 ? 4 * 32 * 68 * 4 : 0);     // weights + store transpose
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(head1x1_kernel<SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 4 * 32 * 68 * 4);
-        attr_set = true;
-    }
     const long M = (long)a.B * a.Ho * a.Wo;
     const long wgs = (M + 127) / 128;                             // one 32-pixel group per wave at least
-    hipLaunchKernelGGL((head1x1_kernel<SPLIT>), dim3((unsigned)(wgs < 512 ? wgs : 512)), dim3(256), lds, s, a, nrows);      // persistent: two 4-wave workgroups per CU
-    return hipGetLastError();
+    return launch_lds<head1x1_kernel<SPLIT>>(dim3((unsigned)(wgs < 512 ? wgs : 512)), dim3(256), lds, 65536 + 4 * 32 * 68 * 4, s, a, nrows);      // persistent: two 4-wave workgroups per CU
 }
 
 // the two output convolutions of a stride level as one launch (head1x1_pair_kernel): a = box branch (64 channels at column 0),
@@ -2947,18 +2613,13 @@ bool head_pair_ok(Precision p, const ConvArgs& a, const ConvArgs& b) {
 }
 hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, hipStream_t s) {
     const size_t lds = head_pair_lds(p, a, b);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(head1x1_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(head1x1_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        attr_set = true;
-    }
+    lds_cap<head1x1_pair_kernel<false>>(128 * 1024);              // both before the first launch of either
+    lds_cap<head1x1_pair_kernel<true>>(128 * 1024);
     const long M = (long)a.B * a.Ho * a.Wo;
     const long wgs = (M + 255) / 256;                             // one 32-pixel group per wave at least
     const unsigned grid = (unsigned)(wgs < 256 ? wgs : 256);           // persistent: one 8-wave workgroup per CU is what the register file holds
-    if (p == PREC_F16X3) hipLaunchKernelGGL((head1x1_pair_kernel<true>), dim3(grid), dim3(512), lds, s, a, b, head_rows(b), head_pair_pitch(a.out_ct));
-    else hipLaunchKernelGGL((head1x1_pair_kernel<false>), dim3(grid), dim3(512), lds, s, a, b, head_rows(b), head_pair_pitch(a.out_ct));
-    return hipGetLastError();
+    if (p == PREC_F16X3) return launch_lds<head1x1_pair_kernel<true>>(dim3(grid), dim3(512), lds, 128 * 1024, s, a, b, head_rows(b), head_pair_pitch(a.out_ct));
+    return launch_lds<head1x1_pair_kernel<false>>(dim3(grid), dim3(512), lds, 128 * 1024, s, a, b, head_rows(b), head_pair_pitch(a.out_ct));
 }
 
 // Kernel variants (also the keys of the profiling summary)
@@ -3138,854 +2799,6 @@ void debug_read_stamps(unsigned long long* out8, bool reset) {
         if (reset) { memset(rec, 0, sizeof(rec)); hipMemcpyToSymbol(HIP_SYMBOL(g_wg_stamps), rec, sizeof(rec)); }
     }
     if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)); }
-}
-
-// ------------------------------------------------------------------------------------------------ weights
-// Packed layout ("slab-major"): [K chunk of 128 B][tap][row in Cout_pad128][128 B] (zero rows past Cout, so no kernel
-// needs a range check on weight rows).  The unit every kernel stages -- the
-// rows n0..n0+BN of one (chunk, tap) -- is ONE contiguous run of BN*128 bytes, so a DMA wave-instruction (8 rows) reads
-// 1 KiB of consecutive cache lines instead of 8 lines a whole filter row (k*k*Cin elements) apart.  K is zero-padded to
-// a whole chunk; rows are permuted per 64 so that a lane of the MFMA result holds 16 contiguous output channels.
-size_t packed_weight_bytes(Precision p, int cout, int cin, int k, int chunk_bytes) {
-    const int epb = chunk_bytes / (p == PREC_F16 ? 2 : 4);
-    return (size_t)((cin + epb - 1) / epb) * k * k * pad128(cout) * chunk_bytes;
-}
-
-void pack_weights(Precision p, const float* W, int cout, int cin, int k, void* dst, int chunk_bytes) {
-    const int taps = k * k, cp = pad128(cout), epb = chunk_bytes / (p == PREC_F16 ? 2 : 4), chunks = (cin + epb - 1) / epb;
-    memset(dst, 0, packed_weight_bytes(p, cout, cin, k, chunk_bytes));
-    for (int row = 0; row < cp; ++row) {
-        const int blk = row >> 6, ni = (row >> 4) & 3, rr = row & 15;
-        const int n = blk * 64 + (rr >> 2) * 16 + ni * 4 + (rr & 3);      // channel held by packed row `row`
-        if (n >= cout) continue;
-        for (int t = 0; t < taps; ++t)
-            for (int c = 0; c < cin; ++c) {
-                const float v = W[((size_t)n * cin + c) * taps + t];
-                const size_t o = (((size_t)(c / epb) * taps + t) * cp + row) * epb + (c % epb);
-                if (p == PREC_F16) reinterpret_cast<f16*>(dst)[o] = (f16)v;
-                else reinterpret_cast<float*>(dst)[o] = v;
-            }
-    }
-    (void)chunks;
-}
-
-// second layer of a back-to-back pair: 1x1 weights with the input channels in the accumulator order of the first layer's kernel
-void pack_weights_fused2(const float* W2, int cout2, int cin2, void* dst) {
-    std::vector<float> perm((size_t)cout2 * cin2);
-    for (int n = 0; n < cout2; ++n)
-        for (int p = 0; p < cin2; ++p) {
-            const int c = p >> 6, kk = (p >> 5) & 1, q = (p >> 3) & 3, j = p & 7;
-            perm[(size_t)n * cin2 + p] = W2[(size_t)n * cin2 + 64 * c + 16 * q + 8 * kk + j];
-        }
-    pack_weights(PREC_F16, perm.data(), cout2, cin2, 1, dst);
-}
-
-// fp16x3 context.  Per output channel n the filter is scaled by 2^e(n) so that its largest weight lies in [2^13, 2^14): the low
-// halves w_lo = fp16(w' - fp16(w')) of all but vanishing weights are then normal fp16 numbers (unscaled they would sit in the
-// subnormal range and carry ~3e-6 relative error); oscale[n] = 2^-e(n) multiplies the accumulator in the epilogue (exact).
-// K holds three passes over the (chunk-padded) input channels: w_hi, w_lo, w_hi -- against x_lo, x_hi, x_hi (see x3_chunk).
-// TWO passes (round 4) when every weight of the layer is an fp16 value times its channel's scale, exactly: W[n] = fl32(w16[n] * scale[n])
-// with w16 representable in fp16 -- what an ultralytics checkpoint is (its tensors are stored in fp16; Conv + BatchNorm are folded in
-// fp32 at load time, so the folded filter of channel n is the fp16 filter times gamma / sqrt(var + eps)).  The layer is then
-// scale[n] * sum_k (x_lo + x_hi) * w16: K holds [w16 | w16] against [x_lo | x_hi], oscale[n] = scale[n], and the weights carry no
-// rounding at all.  x3_passes() decides from the numbers themselves (scale = null: all ones).
-int x3_passes(const float* W, int cout, int cin, int k, const float* scale) {
-    const size_t per = (size_t)cin * k * k;
-    for (int n = 0; n < cout; ++n) {
-        const float sc = scale ? scale[n] : 1.0f;
-        if (!(sc != 0.0f) || !std::isfinite(sc)) return 3;
-        for (size_t i = 0; i < per; ++i) {
-            const float w = W[(size_t)n * per + i];
-            const f16 h = (f16)(w / sc);
-            if (!((float)h * sc == w)) return 3;
-        }
-    }
-    return 2;
-}
-
-size_t packed_weight_bytes_x3(int cout, int cin, int k, int chunk_bytes, int passes) {
-    const int epb = chunk_bytes / 2;
-    return packed_weight_bytes(PREC_F16, cout, passes * ((cin + epb - 1) / epb * epb), k, chunk_bytes);
-}
-
-void pack_weights_x3(const float* W, int cout, int cin, int k, void* dst, float* oscale, int chunk_bytes, int passes, const float* scale) {
-    const int taps = k * k, epb = chunk_bytes / 2, cinp = (cin + epb - 1) / epb * epb, cp = pad128(cout);
-    memset(dst, 0, packed_weight_bytes_x3(cout, cin, k, chunk_bytes, passes));
-    for (int i = 0; i < cp; ++i) oscale[i] = 1.0f;
-    f16* o = reinterpret_cast<f16*>(dst);
-    for (int row = 0; row < cp; ++row) {
-        const int blk = row >> 6, ni = (row >> 4) & 3, rr = row & 15;
-        const int n = blk * 64 + (rr >> 2) * 16 + ni * 4 + (rr & 3);      // channel held by packed row `row`
-        if (n >= cout) continue;
-        if (passes == 2) {                                   // exact fp16 filter, the channel's scale in the epilogue
-            const float sc = scale ? scale[n] : 1.0f;
-            oscale[n] = sc;
-            for (int t = 0; t < taps; ++t)
-                for (int c = 0; c < cin; ++c) {
-                    const f16 h = (f16)(W[((size_t)n * cin + c) * taps + t] / sc);
-                    for (int pass = 0; pass < 2; ++pass) {
-                        const int cv = pass * cinp + c;
-                        o[(((size_t)(cv / epb) * taps + t) * cp + row) * epb + (cv % epb)] = h;
-                    }
-                }
-            continue;
-        }
-        float m = 0.0f;
-        for (size_t i = 0; i < (size_t)cin * taps; ++i) m = fmaxf(m, fabsf(W[(size_t)n * cin * taps + i]));
-        int e = 0;
-        if (m > 0.0f && std::isfinite(m)) { int ex; frexpf(m, &ex); e = 14 - ex; }       // m = f * 2^ex, f in [0.5, 1): m * 2^e in [2^13, 2^14)
-        if (e > 60) e = 60;
-        if (e < -60) e = -60;
-        const float up = ldexpf(1.0f, e);
-        oscale[n] = ldexpf(1.0f, -e);
-        for (int t = 0; t < taps; ++t)
-            for (int c = 0; c < cin; ++c) {
-                const float v = W[((size_t)n * cin + c) * taps + t] * up;
-                const f16 hi = (f16)v, lo = (f16)(v - (float)hi);
-                for (int pass = 0; pass < 3; ++pass) {
-                    const int cv = pass * cinp + c;
-                    o[(((size_t)(cv / epb) * taps + t) * cp + row) * epb + (cv % epb)] = pass == 1 ? lo : hi;
-                }
-            }
-    }
-}
-
-// fp32 NHWC <-> high / low halves (kernel-level test entry and debug reads of the fp16x3 context)
-__global__ __launch_bounds__(256) void x3_split_kernel(const float* __restrict__ in, f16* __restrict__ out, long n, int C) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long pix = i / C; const int c = (int)(i - pix * C);
-        store_split1(out + pix * 2 * C + c, C, in[i]);
-    }
-}
-__global__ __launch_bounds__(256) void x3_merge_kernel(const f16* __restrict__ in, float* __restrict__ out, long n, int C) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const long pix = i / C; const int c = (int)(i - pix * C);
-        out[i] = (float)in[pix * 2 * C + c] + (float)in[pix * 2 * C + C + c];
-    }
-}
-hipError_t launch_x3_split(const float* in, void* out, long npix, int C, hipStream_t s) {
-    const long n = npix * C;
-    hipLaunchKernelGGL(x3_split_kernel, dim3((unsigned)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535)), dim3(256), 0, s, in, reinterpret_cast<f16*>(out), n, C);
-    return hipGetLastError();
-}
-hipError_t launch_x3_merge(const void* in, float* out, long npix, int C, hipStream_t s) {
-    const long n = npix * C;
-    hipLaunchKernelGGL(x3_merge_kernel, dim3((unsigned)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535)), dim3(256), 0, s, reinterpret_cast<const f16*>(in), out, n, C);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ stem
-// Layer 0: Conv(3, C, 3, 2) on the NHWC4 network input.  K = 27 is too small for the matrix cores to matter; the
-// layer is bound by its 64-channel output write.  One thread = one output pixel x 16 output channels.
-template <typename T, bool SPLIT = false>      // SPLIT (fp16x3 context): T = float input, output as fp16 high / low halves
-__global__ __launch_bounds__(256) void stem_kernel(const StemArgs a) {
-    __shared__ float w[27 * 64];
-    __shared__ float bs[64];
-    const int co_blocks = a.Cout / 16;
-    for (int i = threadIdx.x; i < 27 * a.Cout; i += 256) w[i] = a.w[i];
-    for (int i = threadIdx.x; i < a.Cout; i += 256) bs[i] = a.bias[i];
-    __syncthreads();
-    const long total = (long)a.B * a.Ho * a.Wo * co_blocks;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int cb = (int)(idx % co_blocks);
-        const long pix = idx / co_blocks;
-        const int wo = (int)(pix % a.Wo);
-        const int ho = (int)((pix / a.Wo) % a.Ho);
-        const int b = (int)(pix / ((long)a.Wo * a.Ho));
-        float x[27];
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int hi = ho * 2 - 1 + kh, wi = wo * 2 - 1 + kw;
-                const bool ok = (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi;
-                typedef T vec4 __attribute__((ext_vector_type(4)));
-                vec4 pv = {(T)0, (T)0, (T)0, (T)0};
-                if (ok) pv = *reinterpret_cast<const vec4*>(reinterpret_cast<const T*>(a.in) +
-                                                            (((long)b * a.Hi + hi) * a.Wi + wi) * 4);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) x[(kh * 3 + kw) * 3 + c] = (float)pv[c];
-            }
-        float acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 27; ++t)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = fmaf(x[t], w[t * a.Cout + cb * 16 + j], acc[j]);
-        if constexpr (SPLIT) {
-            float v16[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v16[j] = silu_fast(acc[j] + bs[cb * 16 + j]);
-            store_split16(reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cb * 16, a.out_lo, v16);
-            continue;
-        }
-        T* dst = reinterpret_cast<T*>(a.out) + pix * a.out_ct + a.out_coff + cb * 16;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float v = acc[j] + bs[cb * 16 + j];
-            dst[j] = (T)((sizeof(T) == 2) ? silu_fast(v) : silu_exact(v));
-        }
-    }
-}
-
-// The same layer with FOUR horizontally adjacent output pixels per thread (maps whose width is a multiple of 4): the form above reads
-// every weight from LDS for a single FMA and is bound by that (16-byte LDS reads for 4 lanes' worth of FMAs: 20 TFLOP/s of fp32 in the
-// fp16x3 context, 4.9 % of its forward pass); here a weight read feeds four pixels, and the four pixels' 3 x 9 input columns are loaded
-// once (27 loads instead of 36).  Per output value the FMA chain is the one above (taps ascending, fmaf), so results are bit-identical
-// (tests/test_gpu_forward.py::test_stem_four_pixel_form_is_bit_identical).  CY_STEM_QUAD=0: the form above.
-template <typename T, bool SPLIT = false>
-__global__ __launch_bounds__(256) void stem_quad_kernel(const StemArgs a) {
-    __shared__ __attribute__((aligned(16))) float w[27 * 64];
-    __shared__ float bs[64];
-    const int co_blocks = a.Cout / 16, wq = a.Wo >> 2;
-    for (int i = threadIdx.x; i < 27 * a.Cout; i += 256) w[i] = a.w[i];
-    for (int i = threadIdx.x; i < a.Cout; i += 256) bs[i] = a.bias[i];
-    __syncthreads();
-    const long total = (long)a.B * a.Ho * wq * co_blocks;
-    typedef T vec4 __attribute__((ext_vector_type(4)));
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int cb = (int)(idx % co_blocks);
-        const long q = idx / co_blocks;
-        const int wo0 = (int)(q % wq) * 4;
-        const int ho = (int)((q / wq) % a.Ho);
-        const int b = (int)(q / ((long)wq * a.Ho));
-        float acc[4][16];
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[p][j] = 0.0f;
-#pragma unroll 1
-        for (int kh = 0; kh < 3; ++kh) {
-            const int hi = ho * 2 - 1 + kh;
-            const bool row_ok = (unsigned)hi < (unsigned)a.Hi;
-            const int hic = hi < 0 ? 0 : (hi >= a.Hi ? a.Hi - 1 : hi);
-            vec4 r[9];
-#pragma unroll
-            for (int ci = 0; ci < 9; ++ci) {
-                const int wi = wo0 * 2 - 1 + ci;
-                // loaded at clamped coordinates and zeroed by a select (a conditional load is a branch with a full wait behind it)
-                const int wic = wi < 0 ? 0 : (wi >= a.Wi ? a.Wi - 1 : wi);
-                const vec4 t = *reinterpret_cast<const vec4*>(reinterpret_cast<const T*>(a.in) + (((long)b * a.Hi + hic) * a.Wi + wic) * 4);
-                r[ci] = (row_ok && (unsigned)wi < (unsigned)a.Wi) ? t : vec4{(T)0, (T)0, (T)0, (T)0};
-            }
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    asm volatile("" ::: "memory");           // weights of one tap at a time (hoisted, all 432 of them would live in registers)
-                    const float* wr = w + ((kh * 3 + kw) * 3 + c) * a.Cout + cb * 16;
-                    float wv[16];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) {
-                        const f32x4 t4 = *reinterpret_cast<const f32x4*>(wr + 4 * j4);
-                        wv[4 * j4] = t4[0]; wv[4 * j4 + 1] = t4[1]; wv[4 * j4 + 2] = t4[2]; wv[4 * j4 + 3] = t4[3];
-                    }
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float xv = (float)r[2 * p + kw][c];
-#pragma unroll
-                        for (int j = 0; j < 16; ++j) acc[p][j] = fmaf(xv, wv[j], acc[p][j]);
-                    }
-                }
-        }
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const long pix = ((long)b * a.Ho + ho) * a.Wo + wo0 + p;
-            if constexpr (SPLIT) {
-                float v16[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j) v16[j] = silu_fast(acc[p][j] + bs[cb * 16 + j]);
-                store_split16(reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cb * 16, a.out_lo, v16);
-            } else {
-                T* dst = reinterpret_cast<T*>(a.out) + pix * a.out_ct + a.out_coff + cb * 16;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float v = acc[p][j] + bs[cb * 16 + j];
-                    dst[j] = (T)((sizeof(T) == 2) ? silu_fast(v) : silu_exact(v));
-                }
-            }
-        }
-    }
-}
-
-// fp16 context: the stem as a K=32 (27 padded) MFMA GEMM.  A wave turns 16 output pixels x 64 channels per step:
-// the 64x32 weight panel lives in registers for the whole kernel (A operand), each lane gathers the 8 im2col values of
-// its (pixel, k-chunk) from the NHWC4 image with the halo zeroed, and stores 16 contiguous channels of its pixel.
-// Bound by the 64-channel output write (8 MB per 512x512 tile), not by arithmetic.
-__global__ __launch_bounds__(256) void stem_mfma_kernel(const StemArgs a, const f16* __restrict__ wpk) {
-    const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
-    f16x8 wb[4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) wb[ni] = *reinterpret_cast<const f16x8*>(wpk + (ni * 16 + fr) * 32 + fq * 8);
-    float bv[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) bv[j] = a.bias[fq * 16 + j];
-    // k = 8*fq + j  ->  tap = k/3 (kh = tap/3, kw = tap%3), channel = k%3; k >= 27 is zero padding
-    int dh[8], dw[8], dc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = 8 * fq + j, tap = k / 3;
-        dh[j] = tap / 3 - 1; dw[j] = tap % 3 - 1; dc[j] = k < 27 ? k % 3 : -1;
-    }
-    const long ngroups = ((long)a.B * a.Ho * a.Wo + 15) / 16;
-    const long npix = (long)a.B * a.Ho * a.Wo;
-    const int wave_id = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = gridDim.x * 4;
-    const f16* in = reinterpret_cast<const f16*>(a.in);
-    const bool rows16 = (a.Wo & 15) == 0;                   // a group of 16 pixels never straddles an image row: the
-    const int gw = a.Wo >> 4;                               // (b, ho, wo) split is wave-uniform -> scalar divisions
-    for (int g = wave_id; g < (int)ngroups; g += nwaves) {
-        const long pix = (long)g * 16 + fr;
-        const bool pv = pix < npix;
-        int wo, ho, b;
-        if (rows16) {
-            const int row = g / gw;                          // = b*Ho + ho (uniform)
-            wo = (g - row * gw) * 16 + fr;
-            b = row / a.Ho;
-            ho = row - b * a.Ho;
-        } else {
-            wo = (int)(pix % a.Wo); ho = (int)((pix / a.Wo) % a.Ho); b = (int)(pix / ((long)a.Wo * a.Ho));
-        }
-        f16x8 xa;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int hi = 2 * ho + dh[j], wi = 2 * wo + dw[j];
-            const bool ok = pv && dc[j] >= 0 && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi;
-            xa[j] = ok ? in[(((long)b * a.Hi + hi) * a.Wi + wi) * 4 + dc[j]] : (f16)0.0f;
-        }
-        f32x4 acc[4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[ni], xa, acc[ni], 0, 0, 0);
-        }
-        if (pv) {
-            f16x8 o0, o1;
-            float v16[16];
-            bias_act16(acc[0], acc[1], acc[2], acc[3], bv, true, v16);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v16[j]; o1[j] = (f16)v16[8 + j]; }
-            f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + fq * 16;
-            *reinterpret_cast<f16x8*>(dst) = o0;
-            *reinterpret_cast<f16x8*>(dst + 8) = o1;
-        }
-    }
-}
-
-hipError_t launch_stem(Precision p, const StemArgs& a, hipStream_t s) {
-    if (a.Cout > 64 || a.Cout % 16) return hipErrorInvalidValue;
-    if (p == PREC_F16 && a.Cout == 64 && a.wpk) {
-        const long ngroups = ((long)a.B * a.Ho * a.Wo + 15) / 16;
-        const int grid = (int)((ngroups + 3) / 4 < 4096 ? (ngroups + 3) / 4 : 4096);
-        hipLaunchKernelGGL(stem_mfma_kernel, dim3(grid), dim3(256), 0, s, a, reinterpret_cast<const f16*>(a.wpk));
-        return hipGetLastError();
-    }
-    if (p != PREC_F16 && a.Wo % 4 == 0 && env_knob("CY_STEM_QUAD", 1)) {      // four pixels per thread (bit-identical; read per call: tests)
-        const long total4 = (long)a.B * a.Ho * (a.Wo / 4) * (a.Cout / 16);
-        const int grid4 = (int)((total4 + 255) / 256 < 16384 ? (total4 + 255) / 256 : 16384);
-        if (p == PREC_F16X3) hipLaunchKernelGGL((stem_quad_kernel<float, true>), dim3(grid4), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(stem_quad_kernel<float>, dim3(grid4), dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    const long total = (long)a.B * a.Ho * a.Wo * (a.Cout / 16);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (p == PREC_F16) hipLaunchKernelGGL(stem_kernel<f16>, dim3(grid), dim3(256), 0, s, a);
-    else if (p == PREC_F16X3) hipLaunchKernelGGL((stem_kernel<float, true>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(stem_kernel<float>, dim3(grid), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// packed stem weights for stem_mfma_kernel: [64 rows, permuted like pack_weights][32] fp16, k = (kh*3+kw)*3 + c
-void pack_stem_weights(const float* W, int cout, void* dst) {
-    f16* o = reinterpret_cast<f16*>(dst);
-    for (int row = 0; row < 64; ++row) {
-        const int ni = (row >> 4) & 3, rr = row & 15;
-        const int n = (rr >> 2) * 16 + ni * 4 + (rr & 3);
-        for (int k = 0; k < 32; ++k) {
-            float v = 0.0f;
-            if (n < cout && k < 27) { const int tap = k / 3, c = k % 3; v = W[((size_t)n * 3 + c) * 9 + tap]; }
-            o[row * 32 + k] = (f16)v;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ stem + first down conv
-// model.0 (3x3 s2, 3 -> 64) and model.1 (3x3 s2, 64 -> 128) fused.  As separate layers they are the two slowest launches
-// of the forward pass and both HBM-bound: the 64-channel half-resolution map is 8.4 MB per 512x512 tile, written once and
-// read back ~1.6 times (the nine taps of a stride-2 conv come back long after each other: the L2 does not hold them).
-// Here a workgroup owns 8 x 32 output pixels of model.1 x all 128 channels:
-//   phase 1: the 17 x 65 stem pixels under them are computed on the matrix cores (K = 9 taps x 4 NHWC channels = 36,
-//            padded to 64: a lane's k-chunk is two whole input pixels = two 8-byte loads) and written, bias + SiLU applied,
-//            to LDS as fp16 [row][64 ch] (138 KiB).  Stem pixels outside the map are model.1's zero padding: zeros.
-//            Rows are split by column parity (even columns first), so the 16 pixels of a stride-2 fragment are 16
-//            CONSECUTIVE LDS rows and the usual chunk ^ (row & 7) swizzle keeps ds_read_b128 conflict-free.
-//   phase 2: 9 taps x 2 K-halves; a wave owns 64 px x 64 ch, reads its pixel fragments from LDS and its weight fragments
-//            straight from global memory (the 147 KB panel is L2-resident; no LDS left for it), one step ahead.
-// HBM traffic: input (0.5 MB/tile x 1.08 halo) + output (4.2 MB/tile) instead of + 8.4 MB written + >= 8.4 MB read.
-// Measured at batch 256 (CY_SD_DBG phase switches): 1.38 ms against 1.03 + 1.13 ms for the two layers; phase 1 0.70 ms (one
-// exposed gather latency + 144 SiLU per lane per tile), phase 2 0.39 ms, epilogue + stores 0.38 ms.  An 8 x 16-pixel variant
-// with two workgroups per CU (72 KiB, 114 VGPRs) was no faster: its 8-MFMA steps are too short to cover the weight fetch.
-constexpr int SD_TH = 8, SD_TW = 32, SD_PH = 2 * SD_TH + 1, SD_PW = 2 * SD_TW + 1, SD_EVEN = SD_TW + 1;
-constexpr int SD_ROWS = SD_PH * SD_PW, SD_FRAGS = (SD_ROWS + 15) / 16, SD_LDS = SD_FRAGS * 16 * 128;
-
-__device__ __forceinline__ u32x2 load_b64(__amdgpu_buffer_rsrc_t rs, unsigned voff) {
-    return __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
-}
-
-__global__ __launch_bounds__(512) void stem_down_kernel(const StemDownArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 1, wm = wave >> 1;
-    const int tiles_x = (a.Wo + SD_TW - 1) / SD_TW, tiles_y = (a.Ho + SD_TH - 1) / SD_TH;
-    int id = xcd_remap(blockIdx.x, gridDim.x);
-    const int tx = id % tiles_x; id /= tiles_x;
-    const int ty = id % tiles_y;
-    const int b = id / tiles_y;
-    const int oy0 = ty * SD_TH, ox0 = tx * SD_TW;
-    const int sy0 = 2 * oy0 - 1, sx0 = 2 * ox0 - 1;          // stem-map coordinates of LDS pixel (0, 0)
-    const auto rsi = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.in), 0, a.in_bytes, 0x00020000);
-    const auto rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wgt32), 0, a.wgt32_bytes, 0x00020000);
-
-    // weight fragments of step (tap, h): rows wn*64 + ni*16 + fr of chunk h, bytes fq*16.. ; cpad = 128 rows of 64 B
-    constexpr int SD_RING = 4;                                // ring: fragments are requested three steps ahead (a ring of 8 measured
-    f16x8 wa[SD_RING][4];                                     // 6 % slower: its 28 loads per lane up front delay phase 1's gathers)
-    const unsigned wl = (unsigned)((wn * 64 + fr) * 64 + fq * 16);
-    auto load_wa = [&](f16x8* dst, int step) {
-        const int h = step & 1, tap = step >> 1;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) dst[ni] = __builtin_bit_cast(f16x8, load_b128(rsw, wl + ni * 1024, (h * 9 + tap) * 8192));
-    };
-#pragma unroll
-    for (int st = 0; st < SD_RING - 1; ++st) load_wa(wa[st], st);      // in flight during phase 1
-
-    if (!(a.dbg & 1)) {   // ---- phase 1: stem pixels -> LDS
-        const f16* wp = reinterpret_cast<const f16*>(a.wpk2);
-        f16x8 sw0[4], sw1[4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            sw0[ni] = *reinterpret_cast<const f16x8*>(wp + (ni * 16 + fr) * 64 + fq * 8);
-            sw1[ni] = *reinterpret_cast<const f16x8*>(wp + (ni * 16 + fr) * 64 + 32 + fq * 8);
-        }
-        float bv[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) bv[j] = a.bias0[fq * 16 + j];
-        const int t0 = 2 * fq, t1 = 2 * fq + 1;              // the two taps of this lane's k-chunk; tap 8 rides in the second MFMA (fq = 0)
-        const int dh0 = t0 / 3 - 1, dw0 = t0 % 3 - 1, dh1 = t1 / 3 - 1, dw1 = t1 % 3 - 1;
-        const int d0 = (dh0 * a.Wi + dw0) * 8, d1 = (dh1 * a.Wi + dw1) * 8, d2 = (a.Wi + 1) * 8;
-        constexpr int NG = (SD_FRAGS + 7) / 8;
-        u32x2 q0[NG], q1[NG], q2[NG];
-        unsigned inmask = 0;
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-            const int g = gi * 8 + wave, p = g * 16 + fr;
-            const int sy = p / SD_PW, q = p - sy * SD_PW;
-            const int sx = q < SD_EVEN ? 2 * q : 2 * (q - SD_EVEN) + 1;
-            const int Y = sy0 + sy, X = sx0 + sx;
-            const bool inmap = p < SD_ROWS && (unsigned)Y < (unsigned)a.H1 && (unsigned)X < (unsigned)a.W1;
-            inmask |= inmap ? (1u << gi) : 0u;
-            // input pixel (2Y + dh, 2X + dw): with Hi = 2*H1 and Wi = 2*W1 only the -1 row / column can fall outside
-            const int hc = 2 * Y, wc = 2 * X;
-            const int base = ((b * a.Hi + hc) * a.Wi + wc) * 8;
-            const bool ok0 = inmap && ((hc + dh0) | (wc + dw0)) >= 0, ok1 = inmap && ((hc + dh1) | (wc + dw1)) >= 0;
-            q0[gi] = load_b64(rsi, ok0 ? (unsigned)(base + d0) : CY_OOB);
-            q1[gi] = load_b64(rsi, ok1 ? (unsigned)(base + d1) : CY_OOB);
-            q2[gi] = load_b64(rsi, (inmap && fq == 0) ? (unsigned)(base + d2) : CY_OOB);
-        }
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-            const int g = gi * 8 + wave;
-            if (g >= SD_FRAGS) break;                         // wave-uniform
-            const int p = g * 16 + fr;
-            const bool inmap = (inmask >> gi) & 1u;
-            // the fourth NHWC channel is padding: its weights are zero, and masking it keeps a stray NaN out of the sum
-            const u32x4 u0 = {q0[gi].x, q0[gi].y & 0xFFFFu, q1[gi].x, q1[gi].y & 0xFFFFu};
-            const u32x4 u1 = {q2[gi].x, q2[gi].y & 0xFFFFu, 0u, 0u};
-            const f16x8 x0 = __builtin_bit_cast(f16x8, u0), x1 = __builtin_bit_cast(f16x8, u1);
-            f32x4 acc[4];
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sw0[ni], x0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sw1[ni], x1, acc[ni], 0, 0, 0);
-            }
-            f16x8 o0, o1;
-            float v16[16];
-            bias_act16(acc[0], acc[1], acc[2], acc[3], bv, true, v16);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v16[j]; o1[j] = (f16)v16[8 + j]; }
-            const unsigned keep = inmap ? 0xFFFFFFFFu : 0u;   // a select on the packed result: a `?:` around silu becomes 16 branches
-            const u32x4 k4 = {keep, keep, keep, keep};
-            char* row = smem + p * 128;
-            *reinterpret_cast<u32x4*>(row + (((2 * fq) ^ (p & 7)) << 4)) = __builtin_bit_cast(u32x4, o0) & k4;
-            *reinterpret_cast<u32x4*>(row + (((2 * fq + 1) ^ (p & 7)) << 4)) = __builtin_bit_cast(u32x4, o1) & k4;
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: 3x3 stride 2 over the LDS patch
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[ni][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int pl = wm * 4 * SD_PW + fr;                      // LDS row of (first output row of this wave, tap (0,0), column fr)
-    if (!(a.dbg & 2))
-#pragma unroll
-    for (int step = 0; step < 18; ++step) {
-        const int tap = step >> 1, h = step & 1, kh = tap / 3, kw = tap % 3;
-        if (step + SD_RING - 1 < 18) load_wa(wa[(step + SD_RING - 1) % SD_RING], step + SD_RING - 1);
-        __builtin_amdgcn_sched_barrier(0);                   // (left alone the compiler sinks each load to just before its MFMAs)
-        f16x8 xb[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int cm = (2 * (m >> 1) + kh) * SD_PW + (m & 1) * 16 + (kw == 1 ? SD_EVEN : (kw == 2 ? 1 : 0));
-            const int p = pl + cm;
-            xb[m] = *reinterpret_cast<const f16x8*>(smem + p * 128 + (((h * 4 + fq) ^ (p & 7)) << 4));
-        }
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                acc[ni][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[step % SD_RING][ni], xb[m], acc[ni][m], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-
-    const int cbase = wn * 64 + fq * 16;
-    float bv[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) bv[j] = a.bias1[cbase + j];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const int oy = oy0 + wm * 2 + (m >> 1), ox = ox0 + (m & 1) * 16 + fr;
-        if (oy >= a.Ho || ox >= a.Wo || (a.dbg & 4)) continue;
-        const long pix = ((long)b * a.Ho + oy) * a.Wo + ox;
-        f16x8 o0, o1;
-        float v16[16];
-        bias_act16(acc[0][m], acc[1][m], acc[2][m], acc[3][m], bv, true, v16);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { o0[j] = (f16)v16[j]; o1[j] = (f16)v16[8 + j]; }
-        f16* dst = reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase;
-        *reinterpret_cast<f16x8*>(dst) = o0;
-        *reinterpret_cast<f16x8*>(dst + 8) = o1;
-    }
-}
-
-// Two-group form of stem_down_kernel (same arithmetic, same outputs): the one-group kernel runs its three parts one after the other
-// on all eight waves -- stem pixels -> LDS 0.66 ms (gather latency + 144 SiLUs per lane), 3x3 s2 from LDS 0.47 ms (MFMAs, weights
-// from L2), epilogue + stores 0.30 ms per 256 tiles -- and its 138 KiB patch leaves no room for a second workgroup.  Here a
-// persistent workgroup (one per CU) has two groups of four waves (waves w and w + 4 share a SIMD), each with its own 72 KiB
-// patch of 8 x 16 output pixels; the patches of the workgroup alternate between the groups, and in every phase one group fills
-// its patch (VALU / memory latency) while the other convolves and stores its previous one (matrix cores): one barrier per phase.
-constexpr int S2_TH = 8, S2_TW = 16, S2_PH = 2 * S2_TH + 1, S2_PW = 2 * S2_TW + 1, S2_EVEN = S2_TW + 1;
-constexpr int S2_ROWS = S2_PH * S2_PW, S2_FRAGS = (S2_ROWS + 15) / 16, S2_BUF = S2_FRAGS * 16 * 128, S2_LDS = 2 * S2_BUF;
-static_assert(S2_FRAGS % 4 == 0, "fragments split evenly over the four waves of a group");
-
-__global__ __launch_bounds__(512) void stem_down2_kernel(const StemDownArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2, w4 = wave & 3, wn = w4 & 1, wm = w4 >> 1;
-    char* const buf = smem + grp * S2_BUF;                   // this group's patch
-    const int tiles_x = (a.Wo + S2_TW - 1) / S2_TW, tiles_y = (a.Ho + S2_TH - 1) / S2_TH;
-    const int npatch = a.B * tiles_y * tiles_x;
-    const int NP = (int)blockIdx.x < npatch ? (npatch - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;     // patches of this workgroup
-    const auto rsi = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.in), 0, a.in_bytes, 0x00020000);
-    const auto rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wgt32), 0, a.wgt32_bytes, 0x00020000);
-
-    // weight fragments of step (tap, h) of the 3x3 s2 conv: rows w4*32 + ni*16 + fr of chunk h, bytes fq*16..
-    // Round 3: a wave convolves ALL 8 output rows of the patch x 32 channels (was 4 rows x 64 channels).  The weight fragments come
-    // straight from L2, per wave and per patch: 4 fragments x 18 steps = 72 KB per wave, 288 KB per patch -- at the 16-17 B per cycle a
-    // CU's fetch path sustains (section 4 of DESIGN.md) that alone was ~9 us per patch, the whole phase.  Two fragments per step feeding
-    // eight pixel fragments halve it (the pixel fragments are LDS reads); outputs are bit-identical (same K order per output).
-    // Measured: 1.17-1.25 -> 1.09-1.11 ms per 256 tiles, less than the halved fetch promised: the FILL phase (27 eight-byte gathers per
-    // wave and patch + 144 SiLUs per lane) now sets the phase time.  A weight-STATIONARY form was built on that reading and thrown away
-    // again: four-wave workgroups, two per CU, 14 of the 18 K steps of a wave's 32-channel weight slice held in registers for the whole
-    // kernel (112 VGPRs), the stem panel in LDS, gathers three fragments at a time -- bit-identical, 1.20 ms (no fetch of weights per
-    // patch, but no fill / convolve overlap inside a workgroup either, and 32 B of scratch at the 256-register limit).
-    constexpr int RING = 4;
-    f16x8 wa[RING][2];
-    const unsigned wl = (unsigned)((w4 * 32 + fr) * 64 + fq * 16);
-    auto load_wa = [&](f16x8* dst, int step) {
-        const int h = step & 1, tap = step >> 1;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) dst[ni] = __builtin_bit_cast(f16x8, load_b128(rsw, wl + ni * 1024, (h * 9 + tap) * 8192));
-    };
-    const f16* wp = reinterpret_cast<const f16*>(a.wpk2);
-    const int t0 = 2 * fq, t1 = 2 * fq + 1;                  // the two taps of this lane's k-chunk; tap 8 rides in the second MFMA (fq = 0)
-    const int dh0 = t0 / 3 - 1, dw0 = t0 % 3 - 1, dh1 = t1 / 3 - 1, dw1 = t1 % 3 - 1;
-    const int d0 = (dh0 * a.Wi + dw0) * 8, d1 = (dh1 * a.Wi + dw1) * 8, d2 = (a.Wi + 1) * 8;
-
-    auto coords = [&](int n, int& b, int& oy0, int& ox0) {
-        int id = (int)blockIdx.x + n * (int)gridDim.x;
-        const int tx = id % tiles_x; id /= tiles_x;
-        oy0 = (id % tiles_y) * S2_TH; ox0 = tx * S2_TW; b = id / tiles_y;
-    };
-
-    // ---- fill: the 17 x 33 stem pixels under patch n -> this group's LDS patch (bias + SiLU applied, fp16, zeros outside the map)
-    auto fill = [&](int n) {
-        int b, oy0, ox0;
-        coords(n, b, oy0, ox0);
-        const int sy0 = 2 * oy0 - 1, sx0 = 2 * ox0 - 1;      // stem-map coordinates of LDS pixel (0, 0)
-        // stem panel and bias: re-read per patch (L2 hits, beside the gathers) rather than 48 registers held across the convolution
-        f16x8 sw0[4], sw1[4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            sw0[ni] = *reinterpret_cast<const f16x8*>(wp + (ni * 16 + fr) * 64 + fq * 8);
-            sw1[ni] = *reinterpret_cast<const f16x8*>(wp + (ni * 16 + fr) * 64 + 32 + fq * 8);
-        }
-        float bv0[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) bv0[j] = a.bias0[fq * 16 + j];
-        constexpr int NG = S2_FRAGS / 4;
-        u32x2 q0[NG], q1[NG], q2[NG];
-        unsigned inmask = 0;
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-            const int g = gi * 4 + w4, p = g * 16 + fr;
-            const int sy = p / S2_PW, q = p - sy * S2_PW;
-            const int sx = q < S2_EVEN ? 2 * q : 2 * (q - S2_EVEN) + 1;
-            const int Y = sy0 + sy, X = sx0 + sx;
-            const bool inmap = p < S2_ROWS && (unsigned)Y < (unsigned)a.H1 && (unsigned)X < (unsigned)a.W1;
-            inmask |= inmap ? (1u << gi) : 0u;
-            const int hc = 2 * Y, wc = 2 * X;
-            const int base = ((b * a.Hi + hc) * a.Wi + wc) * 8;
-            const bool ok0 = inmap && ((hc + dh0) | (wc + dw0)) >= 0, ok1 = inmap && ((hc + dh1) | (wc + dw1)) >= 0;
-            q0[gi] = load_b64(rsi, ok0 ? (unsigned)(base + d0) : CY_OOB);
-            q1[gi] = load_b64(rsi, ok1 ? (unsigned)(base + d1) : CY_OOB);
-            q2[gi] = load_b64(rsi, (inmap && fq == 0) ? (unsigned)(base + d2) : CY_OOB);
-        }
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-            const int g = gi * 4 + w4, p = g * 16 + fr;
-            const bool inmap = (inmask >> gi) & 1u;
-            // the fourth NHWC channel is padding: its weights are zero, and masking it keeps a stray NaN out of the sum
-            const u32x4 u0 = {q0[gi].x, q0[gi].y & 0xFFFFu, q1[gi].x, q1[gi].y & 0xFFFFu};
-            const u32x4 u1 = {q2[gi].x, q2[gi].y & 0xFFFFu, 0u, 0u};
-            const f16x8 x0 = __builtin_bit_cast(f16x8, u0), x1 = __builtin_bit_cast(f16x8, u1);
-            f32x4 acc[4];
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sw0[ni], x0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                acc[ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sw1[ni], x1, acc[ni], 0, 0, 0);
-            }
-            f16x8 o0, o1;
-            float v16[16];
-            bias_act16(acc[0], acc[1], acc[2], acc[3], bv0, true, v16);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { o0[j] = (f16)v16[j]; o1[j] = (f16)v16[8 + j]; }
-            const unsigned keep = inmap ? 0xFFFFFFFFu : 0u;
-            const u32x4 k4 = {keep, keep, keep, keep};
-            char* row = buf + p * 128;
-            *reinterpret_cast<u32x4*>(row + (((2 * fq) ^ (p & 7)) << 4)) = __builtin_bit_cast(u32x4, o0) & k4;
-            *reinterpret_cast<u32x4*>(row + (((2 * fq + 1) ^ (p & 7)) << 4)) = __builtin_bit_cast(u32x4, o1) & k4;
-        }
-        // the first weight fragments of the convolution that follows the barrier: in flight across it
-#pragma unroll
-        for (int st = 0; st < RING - 1; ++st) load_wa(wa[st], st);
-    };
-
-    // ---- convolve + store: 3x3 stride 2 over this group's patch (wave: 4 output rows x 16 columns x 64 channels)
-    auto conv_store = [&](int n) {
-        int b, oy0, ox0;
-        coords(n, b, oy0, ox0);
-        f32x4 acc[2][8];
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc[ni][m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        unsigned xrow[8];                                     // lane part of a pixel-fragment address for (row offset & 7) = c
-#pragma unroll
-        for (int c = 0; c < 8; ++c) xrow[c] = (unsigned)(fr * 128 + ((fq ^ ((fr + c) & 7)) << 4));
-#pragma unroll
-        for (int step = 0; step < 18; ++step) {
-            const int tap = step >> 1, h = step & 1, kh = tap / 3, kw = tap % 3;
-            if (step + RING - 1 < 18) load_wa(wa[(step + RING - 1) % RING], step + RING - 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mh = 0; mh < 2; ++mh) {                  // two half-steps of four pixel fragments (16 registers)
-                f16x8 xb[4];
-#pragma unroll
-                for (int m4 = 0; m4 < 4; ++m4) {
-                    const int m = mh * 4 + m4;
-                    const int cm = (2 * m + kh) * S2_PW + (kw == 1 ? S2_EVEN : (kw == 2 ? 1 : 0));
-                    // row p = fr + cm, chunk (h*4 + fq) ^ (p & 7): one of eight lane bases (by cm & 7), the second K half = bit 6 flipped
-                    xb[m4] = *reinterpret_cast<const f16x8*>(buf + ((xrow[cm & 7] ^ (unsigned)(h * 64)) + cm * 128));
-                }
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int m4 = 0; m4 < 4; ++m4)
-                        acc[ni][mh * 4 + m4] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[step % RING][ni], xb[m4], acc[ni][mh * 4 + m4], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // packed rows w4*32 + ni*16 + (4 fq + j) hold channels 64 (w4 >> 1) + 16 fq + 4 (2 (w4 & 1) + ni) + j: 8 contiguous channels per lane
-        const int cbase = (w4 >> 1) * 64 + fq * 16 + (w4 & 1) * 8;
-        f32x2 bv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[j] = f32x2{a.bias1[cbase + 2 * j], a.bias1[cbase + 2 * j + 1]};
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int oy = oy0 + m, ox = ox0 + fr;
-            if (oy >= a.Ho || ox >= a.Wo) continue;
-            const long pix = ((long)b * a.Ho + oy) * a.Wo + ox;
-            f16x8 o;
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {          // bias + SiLU, two values per instruction (as bias_act16)
-                    f32x2 t = f32x2{acc[ni][m][2 * hh], acc[ni][m][2 * hh + 1]} + bv[ni * 2 + hh];
-                    f32x2 e = t * f32x2{-1.44269504088896341f, -1.44269504088896341f};
-                    e = f32x2{__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])} + f32x2{1.0f, 1.0f};
-                    t = t * f32x2{__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
-                    o[ni * 4 + 2 * hh] = (f16)t[0]; o[ni * 4 + 2 * hh + 1] = (f16)t[1];
-                }
-            *reinterpret_cast<f16x8*>(reinterpret_cast<f16*>(a.out) + pix * a.out_ct + a.out_coff + cbase) = o;
-        }
-    };
-
-    // Patch n of the workgroup belongs to group n & 1; phase n: its group fills it, phase n + 1: the same group convolves it, so in
-    // every phase one group fills and the other convolves.  Phases 0 .. NP, one barrier each; every wave executes NP + 1 of them
-    // (group 1 sits out phase 0; the group that does not own the last patch sits out the last phase).  One straight-line loop
-    // body for both groups: with a per-phase branch on the role the two instruction streams cost 388 B of scratch.
-    auto phase_barrier = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    if (grp) phase_barrier();
-#pragma unroll 1
-    for (int n = grp; n < NP; n += 2) {
-        fill(n);
-        phase_barrier();
-        conv_store(n);
-        phase_barrier();
-    }
-    if (((NP + grp) & 1) == 0) phase_barrier();
-}
-
-long stem_down_blocks(const StemDownArgs& a) {
-    return (long)a.B * ((a.Ho + SD_TH - 1) / SD_TH) * ((a.Wo + SD_TW - 1) / SD_TW);
-}
-
-hipError_t launch_stem_down(const StemDownArgs& a, hipStream_t s) {
-    if (a.Hi != 2 * a.H1 || a.Wi != 2 * a.W1) return hipErrorInvalidValue;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(stem_down_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS);
-        attr_set = true;
-    }
-    StemDownArgs b2 = a; b2.dbg = dev_knob("CY_SD_DBG", 0);
-    // the two-group persistent form once every workgroup gets at least two patches (both wave groups busy), else the one-group
-    // form; their outputs are bit for bit the same, so the choice may depend on the launch size.  CY_STEM_V = 1 / 2 forces one
-    // (read per call: tests).  256 tiles of 512^2: 1.44-1.47 -> 1.18-1.20 ms alone, 2.38 -> 1.58 ms inside the pipelined pass.
-    const int v = env_knob("CY_STEM_V", 0);
-    const long np = (long)a.B * ((a.Ho + S2_TH - 1) / S2_TH) * ((a.Wo + S2_TW - 1) / S2_TW);
-    if (v == 2 || (v == 0 && np >= 512)) {
-        static bool set2 = false;
-        if (!set2) { hipFuncSetAttribute(reinterpret_cast<const void*>(stem_down2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS); set2 = true; }
-        hipLaunchKernelGGL(stem_down2_kernel, dim3((unsigned)(np < 256 ? np : 256)), dim3(512), S2_LDS, s, b2);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(stem_down_kernel, dim3((unsigned)stem_down_blocks(a)), dim3(512), SD_LDS, s, b2);
-    return hipGetLastError();
-}
-
-// stem panel of stem_down_kernel: [64 rows, permuted like pack_weights][64] fp16; k = tap*4 + c for taps 0..7, 32 + c for
-// tap 8 (c = NHWC4 channel, the fourth is zero)
-void pack_stem_weights2(const float* W, int cout, void* dst) {
-    f16* o = reinterpret_cast<f16*>(dst);
-    for (int row = 0; row < 64; ++row) {
-        const int ni = (row >> 4) & 3, rr = row & 15;
-        const int n = (rr >> 2) * 16 + ni * 4 + (rr & 3);
-        for (int k = 0; k < 64; ++k) {
-            const int tap = k < 32 ? k / 4 : 8, c = k < 32 ? k % 4 : k - 32;
-            float v = 0.0f;
-            if (n < cout && c < 3 && k < 36) v = W[((size_t)n * 3 + c) * 9 + tap];
-            o[row * 64 + k] = (f16)v;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ SPPF pool
-// MaxPool2d(kernel 5, stride 1, padding 2) with implicit -inf padding, slice -> slice of one NHWC buffer.
-template <typename T>
-__global__ __launch_bounds__(256) void pool5_kernel(const PoolArgs a) {
-    constexpr int V = 16 / sizeof(T);
-    typedef T vec __attribute__((ext_vector_type(V)));
-    const int cv = a.C / V;
-    const long total = (long)a.B * a.H * a.W * cv;
-    // (single-pass launch; workgroups in XCD-contiguous order: the 5 x 5 windows of neighbouring rows meet in one L2)
-    for (long idx = (long)xcd_contiguous(blockIdx.x, gridDim.x) * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % cv) * V;
-        const long pix = idx / cv;
-        const int w = (int)(pix % a.W), h = (int)((pix / a.W) % a.H), b = (int)(pix / ((long)a.W * a.H));
-        // window positions clamped into the image instead of skipped: a clamped position is another pixel of the same window, so the
-        // maximum is unchanged, and the 25 loads are unconditional (as `if (inside) load` each one had its own branch and a full wait)
-        const T* base = reinterpret_cast<const T*>(a.src) + a.src_coff + c;
-        vec m = *reinterpret_cast<const vec*>(base + (((long)b * a.H + h) * a.W + w) * a.ct);
-#pragma unroll
-        for (int dh = -2; dh <= 2; ++dh) {
-            int hh = h + dh;
-            hh = hh < 0 ? 0 : (hh >= a.H ? a.H - 1 : hh);
-#pragma unroll
-            for (int dw = -2; dw <= 2; ++dw) {
-                if (dh == 0 && dw == 0) continue;
-                int ww = w + dw;
-                ww = ww < 0 ? 0 : (ww >= a.W ? a.W - 1 : ww);
-                const vec v = *reinterpret_cast<const vec*>(base + (((long)b * a.H + hh) * a.W + ww) * a.ct);
-#pragma unroll
-                for (int j = 0; j < V; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
-            }
-        }
-        *reinterpret_cast<vec*>(reinterpret_cast<T*>(a.dst) + pix * a.ct + a.dst_coff + c) = m;
-    }
-}
-
-// fp16x3 context: the maximum of hi + lo, stored as the halves of the winning pixel (a max picks one of its inputs, so no rounding)
-__global__ __launch_bounds__(256) void pool5_x3_kernel(const PoolArgs a) {
-    const int cv = a.C / 8;
-    const long total = (long)a.B * a.H * a.W * cv;
-    // (single-pass launch; workgroups in XCD-contiguous order: the 5 x 5 windows of neighbouring rows meet in one L2)
-    for (long idx = (long)xcd_contiguous(blockIdx.x, gridDim.x) * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int c = (int)(idx % cv) * 8;
-        const long pix = idx / cv;
-        const int w = (int)(pix % a.W), h = (int)((pix / a.W) % a.H), b = (int)(pix / ((long)a.W * a.H));
-        float m[8]; f16x8 mh, ml;
-        bool first = true;
-        for (int dh = -2; dh <= 2; ++dh)
-            for (int dw = -2; dw <= 2; ++dw) {
-                const int hh = h + dh, ww = w + dw;
-                if ((unsigned)hh >= (unsigned)a.H || (unsigned)ww >= (unsigned)a.W) continue;
-                const f16* sp = reinterpret_cast<const f16*>(a.src) + (((long)b * a.H + hh) * a.W + ww) * a.ct + a.src_coff + c;
-                const f16x8 vh = *reinterpret_cast<const f16x8*>(sp), vl = *reinterpret_cast<const f16x8*>(sp + a.lo);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float v = (float)vh[j] + (float)vl[j];
-                    if (first || v > m[j]) { m[j] = v; mh[j] = vh[j]; ml[j] = vl[j]; }
-                }
-                first = false;
-            }
-        f16* dp = reinterpret_cast<f16*>(a.dst) + pix * a.ct + a.dst_coff + c;
-        *reinterpret_cast<f16x8*>(dp) = mh;
-        *reinterpret_cast<f16x8*>(dp + a.lo) = ml;
-    }
-}
-
-hipError_t launch_pool5(Precision p, const PoolArgs& a, hipStream_t s) {
-    if (p == PREC_F16X3) {
-        if (a.C % 8 || a.lo <= 0) return hipErrorInvalidValue;
-        const long total = (long)a.B * a.H * a.W * (a.C / 8);
-        hipLaunchKernelGGL(pool5_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    const int V = p == PREC_F16 ? 8 : 4;
-    if (a.C % V) return hipErrorInvalidValue;
-    const long total = (long)a.B * a.H * a.W * (a.C / V);
-    const int grid = (int)((total + 255) / 256);
-    if (p == PREC_F16) hipLaunchKernelGGL(pool5_kernel<f16>, dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(pool5_kernel<float>, dim3(grid), dim3(256), 0, s, a);
-    return hipGetLastError();
 }
 
 }  // namespace cy

@@ -139,14 +139,7 @@ hipError_t launch_background(const BackgroundArgs& a, hipStream_t s) {
     const long long cells = (long long)a.ncy * a.ncx;       // < 2^31 / 16
     if ((long long)a.cell * a.cell <= BKG_LDS_MAX) {
         const size_t lds = (size_t)a.cell * a.cell * sizeof(float);
-        static bool attr_set = false;
-        if (!attr_set) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(background_kernel<true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, BKG_LDS_MAX * (int)sizeof(float));
-            if (e != hipSuccess) return e;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(background_kernel<true>, dim3((unsigned)cells), dim3(BNT), lds, s, a);
+        return launch_lds<background_kernel<true>>(dim3((unsigned)cells), dim3(BNT), lds, BKG_LDS_MAX * sizeof(float), s, a);
     } else {
         hipLaunchKernelGGL(background_kernel<false>, dim3((unsigned)cells), dim3(BNT), 0, s, a);
     }

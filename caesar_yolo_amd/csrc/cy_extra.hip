@@ -1,22 +1,19 @@
-// YOLO11-only operators: depth-wise 3x3 convolution and the C2PSA attention core.
-// Both are a fraction of a percent of the network's work (the detect head's depth-wise branch moves ~100 MB per 64-tile
+// Layer operators that are not GEMMs: the YOLO11-only ones, depth-wise 3x3 convolution and the C2PSA attention
+// core, and -- at the end of the file -- the 5x5 max pool of SPPF.  The YOLO11 pair:
+// both are a fraction of a percent of the network's work (the detect head's depth-wise branch moves ~100 MB per 64-tile
 // batch, attention runs on the 16x16 stride-32 map only), so they are written for clarity: HBM-bound element kernels in
 // the activation type with fp32 arithmetic, not MFMA tiles.  Definitions follow the public ultralytics modules
 // (Conv with g = c, Attention in nn/modules/block.py); parity is against oracle/yolo11_ref.py (unpinned to ultralytics).
 #include "cy_kernels.h"
+#include "cy_conv_dev.h"
 #include <cstdlib>
 
 namespace cy {
-
-typedef _Float16 f16;
 
 template <typename T> struct Vec8;
 template <> struct Vec8<f16> { typedef f16 type __attribute__((ext_vector_type(8))); };
 template <> struct Vec8<float> { typedef float type __attribute__((ext_vector_type(8))); };
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
-// fp16 context: hardware exp2 / rcp (1 ulp each; the result is rounded to fp16 anyway), as in the convolution epilogues
-__device__ __forceinline__ float silu_fast_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896341f)); }
 // fp16x3 context (SPLIT): a value is the sum of two fp16 halves, the low one `lo` elements behind the high one (cy_kernels.h)
 template <bool SPLIT, typename T> __device__ __forceinline__ float ld1(const T* p, int lo) {
     if constexpr (SPLIT) return (float)p[0] + (float)p[lo]; else return (float)p[0];
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const DwArgs a) {
                 v8 ol;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float v = (a.act ? silu_f(acc[i][j]) : acc[i][j]) + rr[j];
+                    const float v = (a.act ? silu_exact(acc[i][j]) : acc[i][j]) + rr[j];
                     o[j] = (T)v; ol[j] = (T)(v - (float)o[j]);
                 }
                 T* op = reinterpret_cast<T*>(a.out) + opix * a.out_ct + a.out_coff + c;
@@ -127,10 +124,10 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const DwArgs a) {
             if (a.res) {
                 const v8 r = *reinterpret_cast<const v8*>(reinterpret_cast<const T*>(a.res) + opix * a.res_ct + a.res_coff + c);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (T)((a.act ? (sizeof(T) == 2 ? silu_fast_f(acc[i][j]) : silu_f(acc[i][j])) : acc[i][j]) + (float)r[j]);
+                for (int j = 0; j < 8; ++j) o[j] = (T)((a.act ? (sizeof(T) == 2 ? silu_fast(acc[i][j]) : silu_exact(acc[i][j])) : acc[i][j]) + (float)r[j]);
             } else {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (T)(a.act ? (sizeof(T) == 2 ? silu_fast_f(acc[i][j]) : silu_f(acc[i][j])) : acc[i][j]);
+                for (int j = 0; j < 8; ++j) o[j] = (T)(a.act ? (sizeof(T) == 2 ? silu_fast(acc[i][j]) : silu_exact(acc[i][j])) : acc[i][j]);
             }
             *reinterpret_cast<v8*>(reinterpret_cast<T*>(a.out) + opix * a.out_ct + a.out_coff + c) = o;
         }
@@ -255,33 +252,104 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(const AttnArgs a) {
 hipError_t launch_attention(Precision p, const AttnArgs& a, hipStream_t s) {
     const size_t fast_lds = (size_t)a.N * (a.kd + a.hd) * sizeof(float);
     if (a.kd == 32 && a.hd == 64 && fast_lds <= 160 * 1024 && !(getenv("CY_ATTN_SLOW") && atoi(getenv("CY_ATTN_SLOW")))) {
-        static bool fast_attr = false;
-        if (!fast_attr) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_lds_kernel<f16, 32, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_lds_kernel<float, 32, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_lds_kernel<f16, 32, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            fast_attr = true;
-        }
-        const int grid = a.B * a.heads;
-        if (p == PREC_F16) hipLaunchKernelGGL((attention_lds_kernel<f16, 32, 64>), dim3(grid), dim3(256), fast_lds, s, a);
-        else if (p == PREC_F16X3) hipLaunchKernelGGL((attention_lds_kernel<f16, 32, 64, true>), dim3(grid), dim3(256), fast_lds, s, a);
-        else hipLaunchKernelGGL((attention_lds_kernel<float, 32, 64>), dim3(grid), dim3(256), fast_lds, s, a);
-        return hipGetLastError();
+        lds_cap<attention_lds_kernel<f16, 32, 64>>(160 * 1024);          // all three before the first launch of any
+        lds_cap<attention_lds_kernel<float, 32, 64>>(160 * 1024);
+        lds_cap<attention_lds_kernel<f16, 32, 64, true>>(160 * 1024);
+        const dim3 grid(a.B * a.heads), block(256);
+        if (p == PREC_F16) return launch_lds<attention_lds_kernel<f16, 32, 64>>(grid, block, fast_lds, 160 * 1024, s, a);
+        if (p == PREC_F16X3) return launch_lds<attention_lds_kernel<f16, 32, 64, true>>(grid, block, fast_lds, 160 * 1024, s, a);
+        return launch_lds<attention_lds_kernel<float, 32, 64>>(grid, block, fast_lds, 160 * 1024, s, a);
     }
     if (a.kd > 64 || a.kd < 1 || a.hd < 1 || a.N < 1 || (size_t)a.N * 16 > 160 * 1024) return hipErrorInvalidValue;
     const long nq = (long)a.B * a.heads * a.N;
     const size_t lds = (size_t)4 * a.N * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<f16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
+    lds_cap<attention_kernel<f16>>(160 * 1024);                           // all three before the first launch of any
+    lds_cap<attention_kernel<float>>(160 * 1024);
+    lds_cap<attention_kernel<f16, true>>(160 * 1024);
+    const dim3 grid((unsigned)((nq + 3) / 4)), block(256);
+    if (p == PREC_F16) return launch_lds<attention_kernel<f16>>(grid, block, lds, 160 * 1024, s, a);
+    if (p == PREC_F16X3) return launch_lds<attention_kernel<f16, true>>(grid, block, lds, 160 * 1024, s, a);
+    return launch_lds<attention_kernel<float>>(grid, block, lds, 160 * 1024, s, a);
+}
+
+// ------------------------------------------------------------------------------------------------ SPPF pool
+// MaxPool2d(kernel 5, stride 1, padding 2) with implicit -inf padding, slice -> slice of one NHWC buffer.
+template <typename T>
+__global__ __launch_bounds__(256) void pool5_kernel(const PoolArgs a) {
+    constexpr int V = 16 / sizeof(T);
+    typedef T vec __attribute__((ext_vector_type(V)));
+    const int cv = a.C / V;
+    const long total = (long)a.B * a.H * a.W * cv;
+    // (single-pass launch; workgroups in XCD-contiguous order: the 5 x 5 windows of neighbouring rows meet in one L2)
+    for (long idx = (long)xcd_contiguous(blockIdx.x, gridDim.x) * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % cv) * V;
+        const long pix = idx / cv;
+        const int w = (int)(pix % a.W), h = (int)((pix / a.W) % a.H), b = (int)(pix / ((long)a.W * a.H));
+        // window positions clamped into the image instead of skipped: a clamped position is another pixel of the same window, so the
+        // maximum is unchanged, and the 25 loads are unconditional (as `if (inside) load` each one had its own branch and a full wait)
+        const T* base = reinterpret_cast<const T*>(a.src) + a.src_coff + c;
+        vec m = *reinterpret_cast<const vec*>(base + (((long)b * a.H + h) * a.W + w) * a.ct);
+#pragma unroll
+        for (int dh = -2; dh <= 2; ++dh) {
+            int hh = h + dh;
+            hh = hh < 0 ? 0 : (hh >= a.H ? a.H - 1 : hh);
+#pragma unroll
+            for (int dw = -2; dw <= 2; ++dw) {
+                if (dh == 0 && dw == 0) continue;
+                int ww = w + dw;
+                ww = ww < 0 ? 0 : (ww >= a.W ? a.W - 1 : ww);
+                const vec v = *reinterpret_cast<const vec*>(base + (((long)b * a.H + hh) * a.W + ww) * a.ct);
+#pragma unroll
+                for (int j = 0; j < V; ++j) m[j] = v[j] > m[j] ? v[j] : m[j];
+            }
+        }
+        *reinterpret_cast<vec*>(reinterpret_cast<T*>(a.dst) + pix * a.ct + a.dst_coff + c) = m;
     }
-    const int grid = (int)((nq + 3) / 4);
-    if (p == PREC_F16) hipLaunchKernelGGL(attention_kernel<f16>, dim3(grid), dim3(256), lds, s, a);
-    else if (p == PREC_F16X3) hipLaunchKernelGGL((attention_kernel<f16, true>), dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(attention_kernel<float>, dim3(grid), dim3(256), lds, s, a);
+}
+
+// fp16x3 context: the maximum of hi + lo, stored as the halves of the winning pixel (a max picks one of its inputs, so no rounding)
+__global__ __launch_bounds__(256) void pool5_x3_kernel(const PoolArgs a) {
+    const int cv = a.C / 8;
+    const long total = (long)a.B * a.H * a.W * cv;
+    // (single-pass launch; workgroups in XCD-contiguous order: the 5 x 5 windows of neighbouring rows meet in one L2)
+    for (long idx = (long)xcd_contiguous(blockIdx.x, gridDim.x) * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int c = (int)(idx % cv) * 8;
+        const long pix = idx / cv;
+        const int w = (int)(pix % a.W), h = (int)((pix / a.W) % a.H), b = (int)(pix / ((long)a.W * a.H));
+        float m[8]; f16x8 mh, ml;
+        bool first = true;
+        for (int dh = -2; dh <= 2; ++dh)
+            for (int dw = -2; dw <= 2; ++dw) {
+                const int hh = h + dh, ww = w + dw;
+                if ((unsigned)hh >= (unsigned)a.H || (unsigned)ww >= (unsigned)a.W) continue;
+                const f16* sp = reinterpret_cast<const f16*>(a.src) + (((long)b * a.H + hh) * a.W + ww) * a.ct + a.src_coff + c;
+                const f16x8 vh = *reinterpret_cast<const f16x8*>(sp), vl = *reinterpret_cast<const f16x8*>(sp + a.lo);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float v = (float)vh[j] + (float)vl[j];
+                    if (first || v > m[j]) { m[j] = v; mh[j] = vh[j]; ml[j] = vl[j]; }
+                }
+                first = false;
+            }
+        f16* dp = reinterpret_cast<f16*>(a.dst) + pix * a.ct + a.dst_coff + c;
+        *reinterpret_cast<f16x8*>(dp) = mh;
+        *reinterpret_cast<f16x8*>(dp + a.lo) = ml;
+    }
+}
+
+hipError_t launch_pool5(Precision p, const PoolArgs& a, hipStream_t s) {
+    if (p == PREC_F16X3) {
+        if (a.C % 8 || a.lo <= 0) return hipErrorInvalidValue;
+        const long total = (long)a.B * a.H * a.W * (a.C / 8);
+        hipLaunchKernelGGL(pool5_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    const int V = p == PREC_F16 ? 8 : 4;
+    if (a.C % V) return hipErrorInvalidValue;
+    const long total = (long)a.B * a.H * a.W * (a.C / V);
+    const int grid = (int)((total + 255) / 256);
+    if (p == PREC_F16) hipLaunchKernelGGL(pool5_kernel<f16>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(pool5_kernel<float>, dim3(grid), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -19,6 +19,24 @@ namespace cy {
 inline int env_knob(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 inline int dev_knob(const char* name, int dflt) { return CY_DEV_KNOBS ? env_knob(name, dflt) : dflt; }
 
+// Launch of a kernel that needs more dynamic LDS than the 64 KiB a kernel gets by default.  lds_cap(): raises the limit of one
+// kernel instantiation to `cap` bytes, once (the flag is a function-local static of a template keyed on the kernel: one per
+// instantiation; the attribute call's own status is not looked at: a launch above the limit fails and reports that).
+// launch_lds(): does that on the kernel's first launch, launches with `lds` bytes and returns the launch's error.
+// A launcher that picks among several instantiations at run time and wants all of them ready before the first launch calls
+// lds_cap() for each and then launch_lds() for the one it picked.
+template <auto Kernel> void lds_cap(size_t cap) {
+    static bool done = false;
+    if (done) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+    done = true;
+}
+template <auto Kernel, typename... A> hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, size_t cap, hipStream_t s, A... args) {
+    lds_cap<Kernel>(cap);
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
+
 // PREC_F16X3 ("fp16x3", the fast parity context): every activation is stored as TWO fp16 values hi = fp16(x), lo = fp16(x - hi)
 // (22 significand bits), weights likewise after a per-output-channel power-of-two scale that keeps their low halves out of the
 // fp16 subnormal range; a product x*w is evaluated as hi*hi + lo*hi + hi*lo on the fp16 matrix cores with fp32 accumulation

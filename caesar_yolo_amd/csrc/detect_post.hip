@@ -273,14 +273,8 @@ hipError_t launch_nms(const NmsArgs& a, hipStream_t s) {
     if (a.max_det > MAXDET) return hipErrorInvalidValue;
     int cp2 = 1;
     while (cp2 < a.cap) cp2 <<= 1;
-    static bool attr_set = false;
     const size_t lds = (size_t)NMS_LDS_KEYS * sizeof(uint64_t);
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds + 16384);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(nms_kernel, dim3(a.B), dim3(NMS_NT), lds, s, a, cp2);
-    return hipGetLastError();
+    return launch_lds<nms_kernel>(dim3(a.B), dim3(NMS_NT), lds, lds + 16384, s, a, cp2);
 }
 
 // ------------------------------------------------------------------------------------------------ IoU graph merge

@@ -22,7 +22,7 @@ version 2 (CYW1) / 3 (CYW2): every conv header carries a `flags` word in front o
 the bias, with W[n] = fl32(w16[n] * scale[n]) and w16 the checkpoint's own fp16 filter (ultralytics checkpoints are stored in fp16
 and Conv + BatchNorm are folded in fp32 when the model is loaded: scale = gamma / sqrt(var + eps)).  W and b are still the folded
 fp32 tensors every context and the oracle use; the scale only lets the fp16x3 context recognise that a layer's filter is exact in
-fp16 and run it in two passes instead of three (csrc/conv_igemm.hip: x3_passes).
+fp16 and run it in two passes instead of three (csrc/conv_weights.hip: x3_passes).
 """
 import json
 import os

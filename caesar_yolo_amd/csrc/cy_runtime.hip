@@ -75,6 +75,8 @@ struct cy_ctx {
     bool stem_fused_last = false;                        // the last forward ran model.0 + model.1 as one kernel (no model.0 tensor)
     int pw_fused_conv = -1;                              // the last forward ran this conv + the 1x1 behind it as one kernel (its tensor was not written)
     bool bneck_fused_last = false;                       // ... and 64-channel bottlenecks as one kernel each (their cv1 outputs do not exist)
+    int stop_after = 0;                                  // cy_debug_stop_after: cy_forward ends after this many plan ops (<= 0: the whole plan)
+    int ops_done = 0;                                    // plan ops the last cy_forward completed (a fused launch counts both of its ops)
     int prof_stride = 1; unsigned long fwd_calls = 0;   // profiling on: every prof_stride-th cy_forward call is timed
     std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
     struct ProfRec { size_t e0, e1; int kind; double flops; int conv; int lane; };    // lane: 0 main stream(s), 1 small-batch lane
@@ -679,12 +681,12 @@ int cy_mosaic_prepare(cy_ctx* c, float* d_data, size_t n, int big_endian, void* 
 }
 
 static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t s, char* ws, size_t ws_cap,
-                      bool may_profile);
+                      bool may_profile, int stop = 0);
 
 int cy_forward(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, void* stream) {
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
     c->split_last = false;
-    return forward_on(c, d_netin, B, H, W, d_pred, (hipStream_t)stream, c->ws, c->ws_bytes, true);
+    return forward_on(c, d_netin, B, H, W, d_pred, (hipStream_t)stream, c->ws, c->ws_bytes, true, c->stop_after);
 }
 
 // The forward of one batch as TWO half-batches on two streams (own workspace each).  Every layer is one kernel launch
@@ -746,12 +748,19 @@ static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, fl
     return CY_OK;
 }
 
+// stop > 0 (cy_debug_stop_after, through cy_forward only): the pass ends once `stop` plan ops have run.  A fused launch whose first
+// op lies below `stop` runs whole; a box-branch output convolution still deferred for its head pair is NOT launched (its
+// prediction rows stay as the caller left them), so a stopped pass never runs a launch the whole pass would not.
 static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t s, char* ws, size_t ws_cap,
-                      bool may_profile) {
+                      bool may_profile, int stop) {
     if (!d_netin || !d_pred || B < 1 || H % 32 || W % 32 || H < 32 || W < 32) return fail(c, CY_ERR_ARG, "bad forward arguments");
     int rc = layout_tensors(c, B, H, W, ws_cap);
     if (rc) return rc;
     const Plan& p = c->plan;
+    // a stopped pass (test hook) starts from a workspace of NaN bit patterns (0xFFFF / 0xFFFFFFFF), so that an element its ops
+    // leave unwritten cannot pass for the value an earlier pass over the same input left there
+    if (stop > 0 && (size_t)stop < p.ops.size() && !c->toff.empty())
+        HIPCHK(c, hipMemsetAsync(ws, 0xFF, c->toff.back() + c->tbytes.back(), s));
     const size_t es = esize(c->prec);
     const bool x3 = c->prec == PREC_F16X3;
     const int cm = x3 ? 2 : 1;                           // halves per activation value: pixel strides are cm * C, the low halves C behind
@@ -934,12 +943,16 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         }
         return CY_OK;
     };
-    for (size_t i = 0; i < p.ops.size(); ++i) {
+    const size_t n_run = stop > 0 && (size_t)stop < p.ops.size() ? (size_t)stop : p.ops.size();
+    size_t i = 0;
+    for (; i < n_run; ++i) {
         bool fused = false;
         rc = run_op(p.ops[i], i + 1 < p.ops.size() ? &p.ops[i + 1] : nullptr, &fused);
         if (rc) return rc;
         if (fused) ++i;                                      // the next op ran inside this one's kernel
     }
+    c->ops_done = (int)(i < p.ops.size() ? i : p.ops.size());
+    if (n_run < p.ops.size()) return CY_OK;                   // stopped: a deferred box branch stays unlaunched
     for (HeadPend& h : pend)                                  // a box branch whose class branch never came (no such plan today)
         if (h.on) { h.on = false; cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); }
     return CY_OK;
@@ -1011,6 +1024,47 @@ int cy_profile_layer_variant(cy_ctx* c, const char* conv_name, char* out, int ca
     return fail(c, CY_ERR_ARG, std::string("no such conv: ") + conv_name);
 }
 
+int cy_debug_stop_after(cy_ctx* c, int n_ops) {
+    if (!c) return CY_ERR_ARG;
+    c->stop_after = n_ops > 0 ? n_ops : 0;
+    return CY_OK;
+}
+
+int cy_debug_ops_done(cy_ctx* c) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_ARG, "bad arguments");
+    if (c->lastB == 0) return fail(c, CY_ERR_STATE, "no forward has run");
+    return c->ops_done;
+}
+
+int cy_debug_read_tensor(cy_ctx* c, int tensor, int coff, int C, float* h_out, size_t cap, int* dims4) {
+    if (!c || !c->loaded || !h_out) return fail(c, CY_ERR_ARG, "bad arguments");
+    if (c->lastB == 0) return fail(c, CY_ERR_STATE, "no forward has run");
+    if (c->split_last) return fail(c, CY_ERR_STATE, "the last batch ran as two half-batches (CY_DUAL_FORWARD=0 keeps it in one workspace)");
+    const Plan& p = c->plan;
+    if (tensor == 0) return fail(c, CY_ERR_ARG, "tensor 0 is the caller's network input, not a workspace tensor");
+    if (tensor < 0 || (size_t)tensor >= p.tensors.size()) return fail(c, CY_ERR_ARG, "no such tensor");
+    const Tensor& t = p.tensors[tensor];
+    if (coff < 0 || C < 1 || (long)coff + C > t.C) return fail(c, CY_ERR_ARG, "channel slice outside its tensor");
+    const int Ho = c->lastH >> t.level, Wo = c->lastW >> t.level, B = c->lastB;
+    const size_t n = (size_t)B * C * Ho * Wo;
+    if (n > cap) return fail(c, CY_ERR_ARG, "output buffer too small");
+    HIPCHK(c, hipDeviceSynchronize());
+    std::vector<char> host(c->tbytes[tensor]);
+    HIPCHK(c, hipMemcpy(host.data(), c->ws + c->toff[tensor], host.size(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) for (int h = 0; h < Ho; ++h) for (int w = 0; w < Wo; ++w) for (int ch = 0; ch < C; ++ch) {
+        const size_t px = ((size_t)b * Ho + h) * Wo + w;
+        float v;
+        if (c->prec == PREC_F16X3) {
+            const _Float16* hp = reinterpret_cast<_Float16*>(host.data()) + px * 2 * t.C + coff + ch;
+            v = (float)hp[0] + (float)hp[t.C];
+        } else v = c->prec == PREC_F16 ? (float)reinterpret_cast<_Float16*>(host.data())[px * t.C + coff + ch]
+                                       : reinterpret_cast<float*>(host.data())[px * t.C + coff + ch];
+        h_out[(((size_t)b * C + ch) * Ho + h) * Wo + w] = v;
+    }
+    if (dims4) { dims4[0] = B; dims4[1] = C; dims4[2] = Ho; dims4[3] = Wo; }
+    return CY_OK;
+}
+
 int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t cap, int* dims4) {
     if (!c || !c->loaded || !conv_name || !h_out) return fail(c, CY_ERR_ARG, "bad arguments");
     if (c->lastB == 0) return fail(c, CY_ERR_STATE, "no forward has run");
@@ -1031,25 +1085,7 @@ int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t ca
             return fail(c, CY_ERR_STATE, "this layer ran fused with the 1x1 convolution behind it: its output was not materialised; CY_FUSE_PW=0 runs the two layers apart");
         if (o.kind == OPK_STEM && c->stem_fused_last)
             return fail(c, CY_ERR_STATE, "the stem output was not materialised (fused into the next layer's kernel); set CY_STEM_FUSE=0");
-        const Tensor& t = p.tensors[o.out];
-        const int Ho = c->lastH >> t.level, Wo = c->lastW >> t.level, C = p.convs[o.conv].cout, B = c->lastB;
-        const size_t n = (size_t)B * C * Ho * Wo;
-        if (n > cap) return fail(c, CY_ERR_ARG, "output buffer too small");
-        HIPCHK(c, hipDeviceSynchronize());
-        std::vector<char> host(c->tbytes[o.out]);
-        HIPCHK(c, hipMemcpy(host.data(), c->ws + c->toff[o.out], host.size(), hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b) for (int h = 0; h < Ho; ++h) for (int w = 0; w < Wo; ++w) for (int ch = 0; ch < C; ++ch) {
-            const size_t src = (((size_t)b * Ho + h) * Wo + w) * t.C + o.out_coff + ch;
-            float v;
-            if (c->prec == PREC_F16X3) {
-                const _Float16* hp = reinterpret_cast<_Float16*>(host.data()) + (((size_t)b * Ho + h) * Wo + w) * 2 * t.C + o.out_coff + ch;
-                v = (float)hp[0] + (float)hp[t.C];
-            } else v = c->prec == PREC_F16 ? (float)reinterpret_cast<_Float16*>(host.data())[src]
-                                           : reinterpret_cast<float*>(host.data())[src];
-            h_out[(((size_t)b * C + ch) * Ho + h) * Wo + w] = v;
-        }
-        if (dims4) { dims4[0] = B; dims4[1] = C; dims4[2] = Ho; dims4[3] = Wo; }
-        return CY_OK;
+        return cy_debug_read_tensor(c, o.out, o.out_coff, p.convs[o.conv].cout, h_out, cap, dims4);
     }
     return fail(c, CY_ERR_ARG, std::string("no such conv: ") + conv_name);
 }

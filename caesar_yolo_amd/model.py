@@ -198,10 +198,12 @@ class HipDetector(object):
         self._chk(self.lib.cy_letterbox_pack(self.ctx, self._p(planes), B, h0, w0, imgsz, self._p(netin), self._stream()))
         return netin, lb
 
-    def forward(self, netin):
+    def forward(self, netin, out=None):
+        """out: the caller's prediction tensor [B, A, 64 + nc] fp32 (e.g. NaN-filled before a stopped pass), else a new one."""
         B, H, Wd, _ = netin.shape
         A = self.lib.cy_num_anchors(H, Wd)
-        pred = torch.empty((B, A, 64 + self.nc), dtype=torch.float32, device=self.tdev)
+        pred = out if out is not None else torch.empty((B, A, 64 + self.nc), dtype=torch.float32, device=self.tdev)
+        assert pred.shape == (B, A, 64 + self.nc) and pred.dtype == torch.float32 and pred.is_contiguous() and pred.device == self.tdev
         self._chk(self.lib.cy_forward(self.ctx, self._p(netin), B, H, Wd, self._p(pred), self._stream()))
         return pred
 
@@ -237,6 +239,23 @@ class HipDetector(object):
         dims = (C.c_int * 4)()
         self._chk(self.lib.cy_debug_read_conv(self.ctx, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_float)),
                                               buf.size, dims))
+        d = tuple(dims)
+        return buf[:int(np.prod(d))].reshape(d)
+
+    def stop_after(self, n_ops):
+        """Test hook: the following forward() calls end after the first n_ops plan ops (<= 0: the whole plan again)."""
+        self._chk(self.lib.cy_debug_stop_after(self.ctx, int(n_ops)))
+
+    def ops_done(self):
+        """Plan ops the last forward() completed (one more than asked for when a two-op launch straddled the stop)."""
+        return self._chk(self.lib.cy_debug_ops_done(self.ctx))
+
+    def read_tensor(self, tensor, coff, nch, shape_hint_elems):
+        """Channels [coff, coff + nch) of a plan tensor after the last forward() -> float32 [B, nch, h, w]."""
+        buf = np.zeros(shape_hint_elems, np.float32)
+        dims = (C.c_int * 4)()
+        self._chk(self.lib.cy_debug_read_tensor(self.ctx, int(tensor), int(coff), int(nch), buf.ctypes.data_as(C.POINTER(C.c_float)),
+                                                buf.size, dims))
         d = tuple(dims)
         return buf[:int(np.prod(d))].reshape(d)
 

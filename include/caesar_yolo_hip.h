@@ -130,6 +130,18 @@ int cy_profile_layers(cy_ctx* ctx, cy_prof_entry* out, int cap);    /* the same,
 int cy_profile_layer_variant(cy_ctx* ctx, const char* conv_name, char* out, int cap);
 /* copy the output of one named convolution of the last cy_forward to host as fp32 [B][C][Ho][Wo] (test hook) */
 int cy_debug_read_conv(cy_ctx* ctx, const char* conv_name, float* h_out, size_t cap_elems, int* dims4);
+/* test hooks for an op-by-op check of the forward pass (never set on the hot path).  cy_debug_stop_after: the following cy_forward
+ * calls end after the first n_ops ops of the plan (n_ops <= 0: the whole plan, the default).  A launch that runs two plan ops (stem +
+ * model.1, a back-to-back 1x1 pair, a fused bottleneck) whose first op lies below n_ops runs whole; a box-branch output convolution
+ * that waits for its class branch (the head pair) is not launched by a pass that stops before the class branch, so its rows of
+ * d_pred keep what the caller put there.  A stopped pass first fills the workspace with 0xFF bytes (NaN in fp16 and fp32), so what
+ * it leaves unwritten reads as NaN, and never runs as two half-batches.  cy_debug_ops_done: the number of plan
+ * ops the last cy_forward completed (n_ops + 1 after such a two-op launch), or a negative error code.
+ * cy_debug_read_tensor: channels [coff, coff + C) of plan tensor `tensor` as the last cy_forward left them, as fp32 [B][C][h][w]
+ * (fp16x3 context: high + low half); tensor 0, the caller's input, is refused. */
+int cy_debug_stop_after(cy_ctx* ctx, int n_ops);
+int cy_debug_ops_done(cy_ctx* ctx);
+int cy_debug_read_tensor(cy_ctx* ctx, int tensor, int coff, int C, float* h_out, size_t cap_elems, int* dims4);
 
 /* Detect decode + non_max_suppression + scale_boxes:
  * d_det [B][300][6], d_det_anchor [B][300] (anchor index of each kept box), d_count [B] */

@@ -150,6 +150,64 @@ def silu_allowance(z):
     return 2.0 ** -23 * ((1.0 + z.abs()) * (1.0 - torch.sigmoid(z)) + 1.5)
 
 
+def acc_term(x, w, S, s, pad, prec, passes, stem):
+    """Accumulation term of one convolution (module docstring); stem: the fp32 fmaf chain of the stem kernels."""
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    if prec != "fp16x3" or stem:
+        return (K + 1) * U * S
+    if passes == 2:
+        return (2 * K + 3) * U * (1 + 2.0 ** -10) * S
+    wmax = w.abs().amax(dim=(1, 2, 3)).view(1, -1, 1, 1)
+    sx = F.conv2d(x.abs(), torch.ones((1,) + tuple(w.shape[1:]), dtype=torch.float64), None, stride=s, padding=pad)
+    return (3 * K + 1) * U * (1 + 2.0 ** -10) * S + 2.0 ** -21 * S + 2.0 ** -38 * wmax * sx
+
+
+def conv_bound(name, t, w, b, s, act, res, prec, passes, stem, head):
+    """One convolution (+ bias, SiLU, residual) in float64 on the values that entered it.  t: Val (iv: the interval of an
+    unmaterialised input); w, b float64; res: float64 residual or None; stem: the stem kernels' accumulation; head: the output is
+    a block of prediction rows.  -> (y, e, st): the reference, the error bound before the store and the store term; the device's
+    value must lie within e + st of y.  Shared by the YOLOv8 walk below and the plan walk of tests/plan_ref.py."""
+    pad = w.shape[-1] // 2
+    x = t.v
+    z = F.conv2d(x, w, b, stride=s, padding=pad)
+    S = F.conv2d(x.abs(), w.abs(), b.abs(), stride=s, padding=pad)
+    ez = acc_term(x, w, S, s, pad, prec, passes, stem)
+    if t.iv is not None:
+        ez = ez + F.conv2d(t.iv, w.abs(), None, stride=s, padding=pad)
+    if act:
+        y = F.silu(z)
+        rel = silu_allowance(z)
+        used = torch.where(z < -87.0, torch.zeros_like(rel), rel)          # (below -87 the allowance is |y| itself, not rel |y|)
+        assert float(used.max()) < 2.0 ** -16, "%s: SiLU allowance %.3e is not below 2^-16" % (name, float(used.max()))
+        e = 1.1 * ez + torch.where(z < -87.0, y.abs(), rel * y.abs())
+    else:
+        y, e = z, ez
+    if res is not None:
+        y = y + res
+        e = e + U * (y.abs() + e)
+    st = torch.zeros_like(y) if (head and prec != "fp32") else store_term(y.abs() + e, prec)
+    return y, e, st
+
+
+def unmaterialised(y, e, st, prec):
+    """The value a reader gets of a layer the device never stored: the reference rounded to the storage type, with the interval
+    within which the device's intermediate may differ from it (module docstring)."""
+    iv = e + 2.0 * st
+    if prec == "fp16":
+        iv = torch.where(fp16_tie_distance(y) > e, torch.zeros_like(e), iv)
+    return Val(round_store(y, prec), iv)
+
+
+def compare(got, y, bound, K):
+    """-> the report entry of one materialised output: worst |got - y| / bound and where."""
+    ratio = (got - y).abs() / bound
+    ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, float("inf")))
+    i = int(ratio.argmax())
+    pos = tuple(int(v) for v in np.unravel_index(i, tuple(ratio.shape)))
+    return dict(materialised=True, ratio=float(ratio.flatten()[i]), pos=pos, got=float(got[pos]), ref=float(y[pos]),
+                bound=float(bound[pos]), K=K)
+
+
 class _Walk(object):
     def __init__(self, weights, provider, prec, passes):
         self.w, self.provider, self.prec, self.passes = context_weights(weights, prec), provider, prec, passes
@@ -171,55 +229,18 @@ class _Walk(object):
         assert t.iv is None
         return Val(F.max_pool2d(t.v, 5, 1, 2))
 
-    def acc_term(self, name, x, w, b, S, s, pad):
-        K = w.shape[1] * w.shape[2] * w.shape[3]
-        if self.prec != "fp16x3" or name == "model.0":
-            return (K + 1) * U * S
-        if self.passes == 2:
-            return (2 * K + 3) * U * (1 + 2.0 ** -10) * S
-        wmax = w.abs().amax(dim=(1, 2, 3)).view(1, -1, 1, 1)
-        sx = F.conv2d(x.abs(), torch.ones((1,) + tuple(w.shape[1:]), dtype=torch.float64), None, stride=s, padding=pad)
-        return (3 * K + 1) * U * (1 + 2.0 ** -10) * S + 2.0 ** -21 * S + 2.0 ** -38 * wmax * sx
-
     def conv(self, name, t, s=1, act=True, res=None):
         w, b = self.w[name]
-        pad = w.shape[-1] // 2
-        x = t.v
-        z = F.conv2d(x, w, b, stride=s, padding=pad)
-        S = F.conv2d(x.abs(), w.abs(), b.abs(), stride=s, padding=pad)
-        ez = self.acc_term(name, x, w, b, S, s, pad)
-        if t.iv is not None:
-            ez = ez + F.conv2d(t.iv, w.abs(), None, stride=s, padding=pad)
-        if act:
-            y = F.silu(z)
-            rel = silu_allowance(z)
-            assert float(rel.max()) < 2.0 ** -16, "%s: SiLU allowance %.3e is not below 2^-16" % (name, float(rel.max()))
-            e = 1.1 * ez + torch.where(z < -87.0, y.abs(), rel * y.abs())
-        else:
-            y, e = z, ez
-        if res is not None:
-            assert res.iv is None
-            y = y + res.v
-            e = e + U * (y.abs() + e)
+        assert res is None or res.iv is None
         head = name.startswith("model.22.") and name.endswith(".2")
-        st = torch.zeros_like(y) if (head and self.prec != "fp32") else store_term(y.abs() + e, self.prec)
-        bound = e + st
+        y, e, st = conv_bound(name, t, w, b, s, act, None if res is None else res.v, self.prec, self.passes, name == "model.0", head)
         got = self.provider(name, y)
         if got is None:
-            ref = round_store(y, self.prec)
-            iv = e + 2.0 * st
-            if self.prec == "fp16":
-                iv = torch.where(fp16_tie_distance(y) > e, torch.zeros_like(e), iv)
             self.report[name] = dict(materialised=False, ratio=None)
-            return Val(ref, iv)
+            return unmaterialised(y, e, st, self.prec)
         got = torch.as_tensor(got, dtype=torch.float64)
         assert tuple(got.shape) == tuple(y.shape), "%s: device shape %s, reference %s" % (name, tuple(got.shape), tuple(y.shape))
-        ratio = (got - y).abs() / bound
-        ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, float("inf")))
-        i = int(ratio.argmax())
-        pos = tuple(int(v) for v in np.unravel_index(i, tuple(ratio.shape)))
-        self.report[name] = dict(materialised=True, ratio=float(ratio.flatten()[i]), pos=pos, got=float(got[pos]), ref=float(y[pos]),
-                                 bound=float(bound[pos]), K=int(w.shape[1] * w.shape[2] * w.shape[3]))
+        self.report[name] = compare(got, y, e + st, int(w.shape[1] * w.shape[2] * w.shape[3]))
         return Val(got)
 
 

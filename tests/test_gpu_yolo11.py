@@ -10,7 +10,8 @@ from gpu_common import netin_from_chw
 from yolo11_common import seeded_folded
 
 pytestmark = pytest.mark.gpu
-# (convs whose output buffer is reused later, or that fuse a residual add, are not tapped: their buffer holds something else)
+# (ten taps of the whole pass against the oracle; every op of the plan, the ones whose buffer is reused or updated in place
+#  included, is checked on its own against float64 in tests/test_gpu_yolo11_layers.py)
 TAPS = ["model.1", "model.2.cv2", "model.9.cv2", "model.10.cv2", "model.13.cv2", "model.16.cv2", "model.19.cv2", "model.22.cv2",
         "model.23.cv3.0.0.0", "model.23.cv3.1.1.1"]
 

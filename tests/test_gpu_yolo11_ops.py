@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 from gpu_common import detector
+from plan_ref import attn_ref as _attn_ref, attn_bound as _attn_bound, dw_bound     # (shared with the plan walk of tests/plan_ref.py)
 from caesar_yolo_amd import lib as L
 
 pytestmark = pytest.mark.gpu
@@ -69,7 +70,7 @@ def _dw_case(prec, B, H, W, C, act, use_res, in_ct=None, in_coff=0, out_ct=None,
       fp16x3: + the split of x and r (x (1 + d), |d| <= 4 u; absolute 2^-25 sum |w| + 2^-25) and of the result (4 u |y| + 2^-25),
               again as independent roundings: 7 u A + 5 u |y| + 2^-25 (sum |w| + 2);
       fp16:   fp32-level error with the hardware exp2 / rcp SiLU (5 u A + 5 u |y|), then one fp16 rounding: + E16 |y| + 2^-25.
-    The test asserts max(err / bound) <= 1 and prints it."""
+    (plan_ref.dw_bound.)  The test asserts max(err / bound) <= 1 and prints it."""
     in_ct = in_ct or C
     out_ct = out_ct or C
     res_ct = res_ct or C
@@ -100,13 +101,7 @@ def _dw_case(prec, B, H, W, C, act, use_res, in_ct=None, in_coff=0, out_ct=None,
     got_all = out.cpu()
     _check_slice(got_all, out_coff, out_coff + C, prec, what)
     got = got_all[..., out_coff:out_coff + C].double().permute(0, 3, 1, 2)
-    ay = y.abs()
-    if prec == "fp32":
-        bound = U32 * (5 * A + 3 * ay)
-    elif prec == "fp16x3":
-        bound = U32 * (7 * A + 5 * ay) + 2.0 ** -25 * (w.double().abs().sum((1, 2, 3)).view(1, C, 1, 1) + 2)
-    else:
-        bound = U32 * (5 * A + 5 * ay) + E16 * ay + 2.0 ** -25
+    bound = dw_bound(prec, A, y, w.double().abs().sum((1, 2, 3)).view(1, C, 1, 1))
     err = (got - y).abs()
     ratio = float((err / bound).max())
     print("dw %s %s: max abs err %.3e, max err / bound %.3f" % (prec, what, float(err.max()), ratio))
@@ -178,38 +173,6 @@ def _attn_inputs(regime, B, N, heads, kd, hd, ct, coff, g):
         elif regime == "equal":          # every key the same: all scores equal, the output is the mean of v
             qkv[..., o + kd:o + 2 * kd] = qkv[:, :1, o + kd:o + 2 * kd]
     return qkv
-
-
-def _attn_ref(qkv, heads, kd, hd, coff, rows=None):
-    """softmax(q k^T kd^-0.5) v per head in float64, written out; rows: the query rows to compute (all keys).
-    -> out [B, nrows, heads*hd], max |score|, R = the largest half spread (max_m s - min_m s) / 2 of a query's score row."""
-    per = 2 * kd + hd
-    outs, smax, spread = [], 0.0, 0.0
-    for h in range(heads):
-        o = coff + h * per
-        q, k, v = qkv[..., o:o + kd], qkv[..., o + kd:o + 2 * kd], qkv[..., o + 2 * kd:o + per]
-        if rows is not None:
-            q = q[:, rows]
-        s = torch.matmul(q, k.transpose(1, 2)) * kd ** -0.5
-        e = torch.exp(s - s.max(-1, keepdim=True).values)
-        outs.append(torch.matmul(e, v) / e.sum(-1, keepdim=True))
-        smax = max(smax, float(s.abs().max()))
-        spread = max(spread, float((s.max(-1).values - s.min(-1).values).max()) / 2)
-    return torch.cat(outs, -1), smax, spread
-
-
-def _attn_bound(prec, y, vmax, R):
-    """Per-element bound of one attention output.  The softmax weights depend on score differences only; a computed score
-    carries an error of a few u |s| (kd fused multiply-adds and the scale, or the pre-scaled q of the fast kernel), so against a
-    row's centre the weights move by factors exp(+-c u R), R = half the score spread of the row, and expf, the running sums and
-    the final division add a few u: the output, a convex combination of v, moves by <= u vmax (4 + 4 R).  (The worst-case form
-    (kd + 2) u sum_d |q_d k_d| over N-term sums is 10-50x above every case here; the bound grows with the score range, which is
-    what the rescaling of the online softmax has to survive.)  fp16x3 adds the split of q, k, v (relative 4 u: u vmax (2 + R))
-    and of the output (4 u |y|); fp16 one rounding of the output (E16 |y| + 2^-25)."""
-    if prec == "fp16x3":
-        return U32 * vmax * (6 + 5 * R) + 4 * U32 * y.abs()
-    b = torch.full_like(y, U32 * vmax * (4 + 4 * R))
-    return b + E16 * y.abs() + 2.0 ** -25 if prec == "fp16" else b
 
 
 def _attn_case(prec, B, N, heads, regime="random", kd=32, hd=64, coff=0, extra=0, out_coff=0, out_extra=0, slow=False, rows=None,

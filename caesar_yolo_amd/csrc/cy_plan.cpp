@@ -1,5 +1,7 @@
-// Builds the conv list (canonical order) and the NHWC execution plan for a (scale, nc) pair.
+// Builds the conv list (canonical order) and the NHWC execution plan for a (scale, nc) pair; reads and checks the plan and the
+// conv records of a weight file, and marks the pairs of ops that one kernel can run.
 #include "cy_plan.h"
+#include <algorithm>
 #include <cmath>
 #include <map>
 
@@ -18,12 +20,6 @@ bool scale_of(char s, Scale* o) {
     return false;
 }
 int make_div8(double x) { return (int)std::ceil(x / 8.0) * 8; }
-int py_round(double x) {                     // Python round(): half to even
-    double f = std::floor(x), d = x - f;
-    if (d > 0.5) return (int)f + 1;
-    if (d < 0.5) return (int)f;
-    return ((long)f % 2 == 0) ? (int)f : (int)f + 1;
-}
 
 struct Builder {
     Plan p;
@@ -77,6 +73,13 @@ struct Builder {
     }
 };
 }  // namespace
+
+int py_round(double x) {
+    double f = std::floor(x), d = x - f;
+    if (d > 0.5) return (int)f + 1;
+    if (d < 0.5) return (int)f;
+    return ((long)f % 2 == 0) ? (int)f : (int)f + 1;
+}
 
 Plan build_plan(char scale, int nc) {
     Builder B;
@@ -183,6 +186,219 @@ Plan build_plan(char scale, int nc) {
     }
     p.ok = true;
     return p;
+}
+
+// ---- weight files
+namespace {
+constexpr uint32_t MAX_CHANNELS = 65536;               // of a tensor and of a convolution's input / output
+
+std::string parse_plan_v2(Reader& r, Plan* plan, FileHeader* h) {
+    const uint32_t version = r.u32();                    // 3: conv headers carry a flags word (bit 0: a per-channel scale vector follows the bias)
+    if (version != 2 && version != 3) return "unsupported CYW2 version";
+    h->has_flags = version == 3;
+    if (r.o + 12 > r.n) return "truncated weight file";
+    plan->arch = std::string((const char*)r.p + r.o, strnlen((const char*)r.p + r.o, 8)); r.o += 8;
+    plan->scale = (char)r.p[r.o]; r.o += 4;
+    const uint32_t nc = r.u32(), nnames = r.u32(), nt = r.u32(), nops = r.u32(), nconv = r.u32();
+    for (int l = 0; l < 3; ++l) plan->feat_level[l] = (int)r.u32();
+    if (r.bad || nc < 1 || nc > 1000 || nt < 2 || nt > 4096 || nops < 1 || nops > 8192 || nconv < 1 || nconv > 4096)
+        return "implausible CYW2 header";
+    plan->nc = (int)nc;
+    for (uint32_t i = 0; i < nnames && !r.bad; ++i) { uint32_t l = r.u32(); h->names.push_back(r.str(l)); }
+    for (uint32_t i = 0; i < nt; ++i) { const int lev = (int)r.u32(), C = (int)r.u32(); plan->tensors.push_back({lev, C}); }
+    for (uint32_t i = 0; i < nops; ++i) {
+        int v[20];
+        for (int j = 0; j < 20; ++j) v[j] = (int)r.u32();
+        if (r.bad || v[0] < 0 || v[0] > OPK_ATTN) return "malformed op in CYW2 plan";
+        Op o{};
+        o.kind = (OpKind)v[0]; o.conv = v[1]; o.in0 = v[2]; o.in0_coff = v[3]; o.c0 = v[4]; o.up0 = v[5];
+        o.in1 = v[6]; o.in1_coff = v[7]; o.c1 = v[8]; o.out = v[9]; o.out_coff = v[10]; o.res = v[11]; o.res_coff = v[12];
+        o.pred_level = v[13]; o.pred_coff = v[14]; o.p0 = v[15]; o.p1 = v[16]; o.p2 = v[17]; o.p3 = v[18];
+        const bool no_conv = o.kind == OPK_POOL || o.kind == OPK_ATTN;
+        auto tok = [&](int t, bool opt) { return (opt && t < 0) || (t >= 0 && t < (int)nt); };
+        if (!tok(o.in0, false) || !tok(o.in1, true) || !tok(o.out, true) || !tok(o.res, true) ||
+            (!no_conv && (o.conv < 0 || o.conv >= (int)nconv)) || (o.out < 0 && (o.pred_level < 0 || o.pred_level > 2)))
+            return "malformed op in CYW2 plan";
+        if (no_conv) o.conv = -1;                        // pool and attention ops carry no convolution: whatever the file says there is never an index
+        plan->ops.push_back(o);
+    }
+    for (auto& t : plan->tensors) if (t.level < 0 || t.level > 5 || t.C < 1 || t.C > (int)MAX_CHANNELS) return "malformed tensor in CYW2 plan";
+    h->nconv = nconv;
+    return "";
+}
+}  // namespace
+
+std::string parse_header(Reader& r, Plan* plan, FileHeader* h) {
+    if (r.n < 24 || (memcmp(r.p, "CYW1", 4) != 0 && memcmp(r.p, "CYW2", 4) != 0)) return "not a CYW weight file";
+    h->v2 = memcmp(r.p, "CYW2", 4) == 0;
+    r.o = 4;
+    plan->ok = false;
+    if (h->v2) {
+        const std::string msg = parse_plan_v2(r, plan, h);
+        plan->ok = msg.empty();
+        return msg;
+    }
+    const uint32_t version = r.u32();
+    if (version != 1 && version != 2) return "unsupported CYW version";
+    h->has_flags = version == 2;                         // a flags word per conv header, as CYW2 version 3
+    const char scale = (char)r.p[r.o]; r.o += 4;
+    const uint32_t nc = r.u32();
+    h->nconv = r.u32();
+    const uint32_t nnames = r.u32();
+    *plan = build_plan(scale, (int)nc);
+    if (!plan->ok) { h->unsupported = true; return plan->err; }
+    if (plan->convs.size() != h->nconv) return "weight file conv count does not match the graph";
+    for (uint32_t i = 0; i < nnames && !r.bad; ++i) { uint32_t l = r.u32(); h->names.push_back(r.str(l)); }
+    return "";
+}
+
+std::string next_conv(Reader& r, const FileHeader& h, Plan* plan, uint32_t i, ConvRecord* out) {
+    const uint32_t co = r.u32(), ci = r.u32(), k = r.u32(), s = r.u32(), act = r.u32();
+    const uint32_t groups = h.v2 ? r.u32() : 1u;
+    const uint32_t flags = h.has_flags ? r.u32() : 0u;
+    const uint32_t nl = r.u32();
+    const std::string name = r.str(nl);
+    if (r.bad) return "truncated weight file";
+    if (h.v2) {
+        if (co < 1 || ci < 1 || co > MAX_CHANNELS || ci > MAX_CHANNELS || groups < 1 || ci % groups || (k != 1 && k != 3) || (s != 1 && s != 2))
+            return "malformed conv header: " + name;
+        ConvDesc d; d.name = name; d.cin = (int)ci; d.cout = (int)co; d.k = (int)k; d.s = (int)s; d.act = (int)act; d.groups = (int)groups;
+        plan->convs.push_back(d);
+    } else {
+        const ConvDesc& d = plan->convs[i];
+        if (name != d.name || co != (uint32_t)d.cout || ci != (uint32_t)d.cin || k != (uint32_t)d.k || s != (uint32_t)d.s || act != (uint32_t)d.act)
+            return "weight file layer " + name + " does not match graph layer " + d.name;
+    }
+    out->d = plan->convs[i];
+    out->W = r.f32((size_t)co * (ci / groups) * k * k);      // (every factor is bounded above: at most 2^32 * 9 elements, no wrap)
+    out->b = r.f32(co);
+    // flags bit 0: scale[cout] with W[n] = fl32(w16[n] * scale[n]), w16 the checkpoint's fp16 filter (weights.py: fold(with_scale=True))
+    out->wscale = (flags & 1u) ? r.f32(co) : nullptr;
+    return r.bad ? "truncated weight file" : "";
+}
+
+// A CYW2 file carries its own execution plan; it is untrusted data.  Every channel slice an op names must lie inside its
+// tensor, or the kernels would address outside the workspace (the tensors' extents are the buffer-resource bounds).
+static std::string slice_fault(const Plan& p) {
+    auto T = [&](int t) -> const Tensor& { return p.tensors[t]; };
+    auto inside = [&](int t, int coff, long n) { return coff >= 0 && n >= 1 && (long)coff + n <= T(t).C; };      // (untrusted u32 fields: no int overflow)
+    auto small = [](int v) { return v >= 1 && v <= (int)MAX_CHANNELS; };
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        const Op& o = p.ops[i];
+        const std::string at = " in op " + std::to_string(i);
+        if (o.kind == OPK_POOL) {
+            if (o.out < 0 || !inside(o.in0, o.in0_coff, o.c0) || !inside(o.out, o.out_coff, o.c0) || T(o.in0).level != T(o.out).level)
+                return "pool slice outside its tensor" + at;
+            continue;
+        }
+        if (o.kind == OPK_ATTN) {
+            if (o.out < 0 || !small(o.p0) || !small(o.p1) || !small(o.p2) || !inside(o.in0, o.in0_coff, (long)o.p0 * (2L * o.p1 + o.p2)) ||
+                !inside(o.out, o.out_coff, (long)o.p0 * o.p2))
+                return "attention slice outside its tensor" + at;
+            continue;
+        }
+        const ConvDesc& d = p.convs[o.conv];
+        if (o.kind == OPK_DWCONV) {
+            // input channel of output channel ch: (ch / blk) * gstride + goff + ch % blk   (blk = 0: ch)
+            const int last = d.cout - 1;
+            const long cin_last = o.p0 > 0 ? (long)(last / o.p0) * o.p1 + o.p2 + last % o.p0 : last;
+            if (o.out < 0 || o.p0 < 0 || o.p1 < 0 || o.p2 < 0 || (o.p0 > 0 && o.p0 % 8) || o.in0_coff < 0 ||
+                o.in0_coff + cin_last + 1 > T(o.in0).C || !inside(o.out, o.out_coff, d.cout) ||
+                (o.res >= 0 && !inside(o.res, o.res_coff, d.cout)))
+                return "depth-wise slice outside its tensor" + at;
+            continue;
+        }
+        if (o.kind == OPK_STEM) {
+            if (o.out < 0 || !inside(o.out, o.out_coff, d.cout) || T(o.in0).C != 4 || d.cin != 3) return "malformed stem" + at;
+            continue;
+        }
+        if (!inside(o.in0, o.in0_coff, o.c0) || (o.in1 >= 0 ? !inside(o.in1, o.in1_coff, o.c1) : o.c1 != 0) || o.c0 + o.c1 != d.cin)
+            return "conv input slice does not match " + d.name + at;
+        if (o.in1 >= 0 && (d.k != 1 || o.c0 % 64)) return "two-segment input needs a 1x1 conv and a 64-aligned boundary" + at;
+        if (o.up0 && (d.k != 1 || T(o.in0).level < 1)) return "upsampled input needs a 1x1 conv" + at;
+        if (o.out >= 0 && !inside(o.out, o.out_coff, d.cout)) return "conv output slice outside its tensor" + at;
+        if (o.out < 0 && (o.pred_coff < 0 || (long)o.pred_coff + d.cout > 64 + p.nc)) return "head slice outside the prediction row" + at;
+        if (o.res >= 0 && (!inside(o.res, o.res_coff, d.cout) || (o.out >= 0 && T(o.res).level != T(o.out).level)))
+            return "residual slice outside its tensor" + at;
+    }
+    return "";
+}
+
+std::string validate_plan(const Plan& p) {
+    const std::string bad = slice_fault(p);
+    return bad.empty() ? bad : "malformed CYW2 plan: " + bad;
+}
+
+namespace {
+bool plain_conv_pair(const Op& o, const Op& n) {          // two convolutions into tensors, the second reading the slice the first writes
+    return n.kind == OPK_CONV && o.conv >= 0 && n.conv >= 0 && o.out >= 0 && n.out >= 0 && n.in0 == o.out && n.in0_coff == o.out_coff &&
+           n.in1 < 0 && !n.up0;
+}
+int readers_of(const Plan& p, int t) {
+    int readers = 0;
+    for (const Op& q : p.ops) readers += (q.in0 == t) + (q.in1 == t) + (q.res == t);
+    return readers;
+}
+
+// ops[i] = the stem, ops[i+1] = a 3x3 stride-2 SiLU convolution that is the ONLY reader of the stem's output and reads all of it:
+// the candidate of stem_down_kernel (model.0 + model.1 in one launch).  The kernel exists for 64 -> 128 channels in the fp16
+// context only; the forward pass sees that by the weight copies the loader packed for exactly those widths.
+bool stem_down_pair(const Plan& p, size_t i) {
+    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1];
+    if (o.kind != OPK_STEM || !plain_conv_pair(o, n) || n.res >= 0) return false;
+    const ConvDesc& d0 = p.convs[o.conv]; const ConvDesc& d = p.convs[n.conv];
+    if (d.k != 3 || d.s != 2 || !d.act || d.groups != 1 || d.cin != d0.cout || n.c0 != d0.cout) return false;
+    return p.tensors[o.in0].C == 4 && p.tensors[o.out].C == d0.cout && readers_of(p, o.out) == 1;
+}
+
+// ops[i], ops[i+1] = the two 3x3 convs of a 64-channel Bottleneck (x [+] cv2(cv1(x))) whose intermediate has no other reader:
+// with CY_BNECK_FUSE=1 they run as ONE kernel in the fp16 context (bneck64.hip; off by default: measured slower so far)
+bool bneck_pair(const Plan& p, size_t i) {
+    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1];
+    if (o.kind != OPK_CONV || !plain_conv_pair(o, n)) return false;
+    const ConvDesc& d1 = p.convs[o.conv]; const ConvDesc& d2 = p.convs[n.conv];
+    auto c64 = [](const ConvDesc& d) { return d.k == 3 && d.s == 1 && d.cin == 64 && d.cout == 64 && d.act && d.groups == 1; };
+    if (!c64(d1) || !c64(d2)) return false;
+    if (o.in1 >= 0 || o.up0 || o.res >= 0 || o.c0 != 64 || n.c0 != 64) return false;
+    if (p.tensors[o.in0].level != p.tensors[o.out].level || p.tensors[o.in0].level != p.tensors[n.out].level) return false;
+    if (n.res >= 0 && (n.res != o.in0 || n.res_coff != o.in0_coff)) return false;      // the shortcut adds the bottleneck's own input
+    if (n.out == o.in0 && n.out_coff == o.in0_coff) return false;                        // in place: patches would read overwritten halos
+    // the intermediate must be dead after cv2: the next op that touches its tensor (C2f reuses one scratch tensor for all its
+    // bottlenecks) has to overwrite exactly this slice before anything reads it
+    for (size_t j = i + 2; j < p.ops.size(); ++j) {
+        const Op& q = p.ops[j];
+        if (q.in0 == o.out || q.in1 == o.out || q.res == o.out) return false;
+        if (q.out == o.out) return q.out_coff == o.out_coff && q.conv >= 0 && p.convs[q.conv].cout == 64;
+    }
+    return true;
+}
+
+// ops[i] = a convolution whose 256 output channels all sit in one tile of the pixels-direct kernel (3x3 stride 2 or 1x1, SiLU, no
+// residual, one input segment), ops[i+1] = the 1x1 convolution (256 -> <= 256 channels, one input segment, no residual) that is the ONLY
+// reader of its output: in the fp16 context the pair runs as one kernel, the first layer's accumulators feeding the second GEMM in
+// registers (conv1x1_direct_kernel<..., FUSE2>; yolov8l: model.3 -> model.4.cv1).  CY_FUSE_PW=0 turns it off.
+bool pw_pair(const Plan& p, size_t i) {
+    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1];
+    if (o.kind != OPK_CONV || !plain_conv_pair(o, n)) return false;
+    const ConvDesc& d1 = p.convs[o.conv]; const ConvDesc& d2 = p.convs[n.conv];
+    if (d1.groups != 1 || d2.groups != 1 || d1.cout != 256 || !d1.act || d1.cin % 64) return false;
+    if (!((d1.k == 3 && d1.s == 2 && d1.cin >= 128) || (d1.k == 1 && d1.s == 1))) return false;
+    if (d2.k != 1 || d2.s != 1 || d2.cin != 256 || d2.cout > 256 || d2.cout % 16) return false;
+    if (o.in1 >= 0 || o.up0 || o.res >= 0 || n.res >= 0 || n.c0 != 256) return false;
+    if (p.tensors[o.out].level != p.tensors[n.out].level || n.out == o.out) return false;
+    return readers_of(p, o.out) == 1;                     // nothing else may read the first layer's output (a later op may overwrite that tensor)
+}
+}  // namespace
+
+void mark_fusions(Plan& p) {
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        Op& o = p.ops[i];
+        o.fuse = FUSE_NONE;
+        if (i + 1 >= p.ops.size()) continue;
+        if (bneck_pair(p, i)) o.fuse = FUSE_BNECK_PAIR;         // (the three exclude one another: 64 / 256 output channels, the stem)
+        else if (stem_down_pair(p, i)) o.fuse = FUSE_STEM_DOWN;
+        else if (pw_pair(p, i)) o.fuse = FUSE_PW_PAIR;
+    }
 }
 
 }  // namespace cy

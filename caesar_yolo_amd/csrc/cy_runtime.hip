@@ -14,6 +14,7 @@
 
 using namespace cy;
 
+// device copies of one convolution: views into cy_ctx::weights (load) or into the owner of a test entry call
 struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; float* stem_w = nullptr; void* w32 = nullptr; size_t w32bytes = 0;
                  float* oscale = nullptr;       // fp16x3 context: 2^-e per output channel (undoes the weight scale in the epilogue)
                  void* w2f = nullptr; size_t w2fbytes = 0;   // on the SECOND layer of a back-to-back pair: its weights in the first layer's accumulator order (pack_weights_fused2)
@@ -24,6 +25,35 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
 enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_COUNT };
 
+// Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
+// beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
+// scratch of that call, freed on every return path); the pointers handed out are views.  In the fp16x3 context the test entries take
+// fp32 [pix][ct] caller tensors and run the kernel on split copies [pix][2 ct] (high halves, then the low halves ct behind: the
+// forward's layout, channel offsets included); split() makes such a copy, the caller merges the written one back with launch_x3_merge.
+struct DevOwner {
+    std::vector<void*> p;
+    DevOwner() = default;
+    DevOwner(const DevOwner&) = delete;
+    DevOwner& operator=(const DevOwner&) = delete;
+    ~DevOwner() { reset(); }
+    void reset() { for (void* q : p) hipFree(q); p.clear(); }
+    template <class T> hipError_t alloc(size_t bytes, T** out) {
+        void* d = nullptr;
+        const hipError_t e = hipMalloc(&d, bytes);
+        if (e == hipSuccess) p.push_back(d);
+        *out = static_cast<T*>(d);
+        return e;
+    }
+    template <class T> hipError_t upload(const void* host, size_t bytes, T** out) {      // alloc + blocking copy of a host span
+        const hipError_t e = alloc(bytes, out);
+        return e == hipSuccess ? hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice) : e;
+    }
+    hipError_t split(const void* t, long npix, int ct, void** out, hipStream_t s) {
+        hipError_t e = alloc((size_t)npix * ct * 4, out);
+        return e == hipSuccess ? cy::launch_x3_split(reinterpret_cast<const float*>(t), *out, npix, ct, s) : e;
+    }
+};
+
 struct cy_ctx {
     int device = 0;
     cy_config cfg{};
@@ -33,6 +63,7 @@ struct cy_ctx {
     Plan plan;
     std::vector<std::string> names;
     std::vector<DevConv> dconv;
+    DevOwner weights, buffers, aug_mem, counter_mem;   // what `dconv` views / workspaces and stage buffers / augment buffers / `counters`
     // workspace
     char* ws = nullptr; size_t ws_bytes = 0;           // activations
     // second workspace + stream: cy_detect_tiles runs batches of 64..239 tiles as two concurrent half-batches (forward_split)
@@ -72,9 +103,8 @@ struct cy_ctx {
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
-    bool stem_fused_last = false;                        // the last forward ran model.0 + model.1 as one kernel (no model.0 tensor)
-    int pw_fused_conv = -1;                              // the last forward ran this conv + the 1x1 behind it as one kernel (its tensor was not written)
-    bool bneck_fused_last = false;                       // ... and 64-channel bottlenecks as one kernel each (their cv1 outputs do not exist)
+    std::vector<char> fused_last;                        // per plan op, of the last forward: it ran as the first of a fused launch (Op::fuse says which): its
+                                                         // output was not materialised, and the op behind it ran inside that launch
     int stop_after = 0;                                  // cy_debug_stop_after: cy_forward ends after this many plan ops (<= 0: the whole plan)
     int ops_done = 0;                                    // plan ops the last cy_forward completed (a fused launch counts both of its ops)
     int prof_stride = 1; unsigned long fwd_calls = 0;   // profiling on: every prof_stride-th cy_forward call is timed
@@ -100,23 +130,6 @@ std::vector<float> dw_weights(const float* W, int C) {
 }
 const char* const ATTN_TOO_LARGE = "attention map too large for this kernel (stride-32 map of the input must have <= 10240 pixels)";
 
-// Device scratch of one kernel-level test entry call, freed on every return path.  In the fp16x3 context the entries take fp32
-// [pix][ct] caller tensors and run the kernel on split copies [pix][2 ct] (high halves, then the low halves ct behind: the forward's
-// layout, channel offsets included); split() makes such a copy, the caller merges the written one back with launch_x3_merge.
-struct EntryScratch {
-    std::vector<void*> p;
-    ~EntryScratch() { for (void* q : p) hipFree(q); }
-    hipError_t alloc(size_t bytes, void** out) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc(out, bytes);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    hipError_t split(const void* t, long npix, int ct, void** out, hipStream_t s) {
-        hipError_t e = alloc((size_t)npix * ct * 4, out);
-        return e == hipSuccess ? launch_x3_split(reinterpret_cast<const float*>(t), *out, npix, ct, s) : e;
-    }
-};
 // synchronise, then report the first error of the call (as cy_conv_bn_silu)
 int entry_done(cy_ctx* c, hipError_t e, hipStream_t s) {
     const hipError_t e2 = hipStreamSynchronize(s);
@@ -136,7 +149,7 @@ struct TimedLaunch {
     struct Copy { void* dst; const void* src; size_t bytes; };      // src null: zero dst
     cy_ctx* c; hipStream_t st; hipError_t e;
     const char* early = nullptr;                                     // the call that failed before anything was queued
-    EntryScratch sc;
+    DevOwner sc;
     std::vector<Copy> before, after;
     TimedLaunch(cy_ctx* c_, void* stream) : c(c_), st((hipStream_t)stream), e(hipSetDevice(c_->device)) {
         if (e != hipSuccess) early = "hipSetDevice(c->device)";
@@ -180,343 +193,134 @@ struct TimedLaunch {
 };
 inline bool ch8(int v) { return v >= 0 && v % 8 == 0; }     // channel offset / stride usable by the 8-channel vector accesses
 
-int py_round_half_even(double x) {
-    double f = std::floor(x), d = x - f;
-    if (d > 0.5) return (int)f + 1;
-    if (d < 0.5) return (int)f;
-    return (((long)f) % 2 == 0) ? (int)f : (int)f + 1;
-}
-
-size_t tensor_elems_per_tile(const Plan& p, int H, int W) {
-    size_t t = 0;
-    for (auto& x : p.tensors) t += (size_t)(H >> x.level) * (W >> x.level) * x.C;
-    return t;
-}
-
 void free_all(cy_ctx* c) {
     for (auto e : c->ev_pool) hipEventDestroy(e);
     c->ev_pool.clear(); c->ev_used = 0; c->prof.clear();
-    for (auto& d : c->dconv) { if (d.w) hipFree(d.w); if (d.bias) hipFree(d.bias); if (d.stem_w) hipFree(d.stem_w); if (d.w32) hipFree(d.w32); if (d.dw_w) hipFree(d.dw_w); if (d.bneck) hipFree(d.bneck); if (d.oscale) hipFree(d.oscale); if (d.w2f) hipFree(d.w2f); }
     c->dconv.clear();
-    if (c->ws) hipFree(c->ws);
-    c->ws = nullptr;
-    if (c->ws2) hipFree(c->ws2);
-    c->ws2 = nullptr; c->ws2_bytes = 0;
+    c->weights.reset(); c->buffers.reset(); c->aug_mem.reset(); c->counter_mem.reset();
+    c->ws = c->ws2 = c->ws3 = nullptr; c->ws2_bytes = c->ws3_bytes = 0; c->counters = nullptr;
+    for (auto& b : c->sb) b = cy_ctx::StageBufs();
+    for (auto& b : c->ab) b = cy_ctx::AugBufs();
     if (c->s_fwd2) { hipStreamDestroy(c->s_fwd2); c->s_fwd2 = nullptr; }
-    if (c->ws3) hipFree(c->ws3);
-    c->ws3 = nullptr; c->ws3_bytes = 0;
     c->s_small = nullptr;                                   // (an alias of s_fwd2)
-    for (auto& e : c->ev_split) if (e) { hipEventDestroy(e); e = nullptr; }
-    for (auto& b : c->sb) {
-        void* ptrs[] = {b.netin, b.pred, b.cand, b.cand_anchor, b.cand_count, b.keys, b.det, b.det_anchor, b.det_count,
-                        b.merge_err, b.out_src, b.pre_params, b.pre_histeq, b.pre_scratch};
-        for (void* p : ptrs) if (p) hipFree(p);
-        b = cy_ctx::StageBufs();
-    }
-    for (auto& b : c->ab) {
-        void* ptrs[] = {b.view[0], b.view[1], b.pred[0], b.pred[1], b.src32, b.cand, b.cand_anchor, b.keys};
-        for (void* p : ptrs) if (p) hipFree(p);
-        b = cy_ctx::AugBufs();
-    }
-    c->aug = false; c->acap = 0; c->acap_pow2 = 0;
-    if (c->counters) { hipFree(c->counters); c->counters = nullptr; }
     if (c->s_pre) { hipStreamDestroy(c->s_pre); c->s_pre = nullptr; }
     if (c->s_post) { hipStreamDestroy(c->s_post); c->s_post = nullptr; }
-    hipEvent_t* evs[] = {&c->ev_call, &c->ev_pre[0], &c->ev_pre[1], &c->ev_pre[2], &c->ev_fwd[0], &c->ev_fwd[1], &c->ev_fwd[2], &c->ev_post[0], &c->ev_post[1], &c->ev_post[2]};
+    hipEvent_t* evs[] = {&c->ev_split[0], &c->ev_split[1], &c->ev_call, &c->ev_pre[0], &c->ev_pre[1], &c->ev_pre[2], &c->ev_fwd[0], &c->ev_fwd[1],
+                         &c->ev_fwd[2], &c->ev_post[0], &c->ev_post[1], &c->ev_post[2]};
     for (hipEvent_t* e : evs) if (*e) { hipEventDestroy(*e); *e = nullptr; }
     c->batches = 0; c->small_batches = 0;
+    c->loaded = false; c->aug = false; c->acap = 0; c->acap_pow2 = 0; c->lastB = 0;
 }
 
-struct Reader {
-    const unsigned char* p; size_t n, o = 0; bool bad = false;
-    uint32_t u32() { if (o + 4 > n) { bad = true; return 0; } uint32_t v; memcpy(&v, p + o, 4); o += 4; return v; }
-    std::string str(uint32_t len) { if (o + len > n) { bad = true; return ""; } std::string s((const char*)p + o, len); o += (len + 3) / 4 * 4; return s; }
-    const float* f32(size_t cnt) { if (o + 4 * cnt > n) { bad = true; return nullptr; } const float* r = (const float*)(p + o); o += 4 * cnt; return r; }
-};
-
-// CYW2: the execution plan travels in the file (caesar_yolo_amd/weights.py:write_cyw2, yolo11_graph.py)
-int parse_plan_v2(cy_ctx* c, Reader& r, Plan* plan, uint32_t* nconv_out, std::vector<std::string>* names, uint32_t* version) {
-    *version = r.u32();                                   // 3: conv headers carry a flags word (bit 0: a per-channel scale vector follows the bias)
-    if (*version != 2 && *version != 3) return fail(c, CY_ERR_IO, "unsupported CYW2 version");
-    if (r.o + 12 > r.n) return fail(c, CY_ERR_IO, "truncated weight file");
-    plan->arch = std::string((const char*)r.p + r.o, strnlen((const char*)r.p + r.o, 8)); r.o += 8;
-    plan->scale = (char)r.p[r.o]; r.o += 4;
-    const uint32_t nc = r.u32(), nnames = r.u32(), nt = r.u32(), nops = r.u32(), nconv = r.u32();
-    for (int l = 0; l < 3; ++l) plan->feat_level[l] = (int)r.u32();
-    if (r.bad || nc < 1 || nc > 1000 || nt < 2 || nt > 4096 || nops < 1 || nops > 8192 || nconv < 1 || nconv > 4096)
-        return fail(c, CY_ERR_IO, "implausible CYW2 header");
-    plan->nc = (int)nc;
-    for (uint32_t i = 0; i < nnames; ++i) { uint32_t l = r.u32(); names->push_back(r.str(l)); }
-    for (uint32_t i = 0; i < nt; ++i) { const int lev = (int)r.u32(), C = (int)r.u32(); plan->tensors.push_back({lev, C}); }
-    for (uint32_t i = 0; i < nops; ++i) {
-        int v[20];
-        for (int j = 0; j < 20; ++j) v[j] = (int)r.u32();
-        Op o{};
-        o.kind = (OpKind)v[0]; o.conv = v[1]; o.in0 = v[2]; o.in0_coff = v[3]; o.c0 = v[4]; o.up0 = v[5];
-        o.in1 = v[6]; o.in1_coff = v[7]; o.c1 = v[8]; o.out = v[9]; o.out_coff = v[10]; o.res = v[11]; o.res_coff = v[12];
-        o.pred_level = v[13]; o.pred_coff = v[14]; o.p0 = v[15]; o.p1 = v[16]; o.p2 = v[17]; o.p3 = v[18];
-        auto tok = [&](int t, bool opt) { return (opt && t < 0) || (t >= 0 && t < (int)nt); };
-        if (r.bad || v[0] < 0 || v[0] > OPK_ATTN || !tok(o.in0, false) || !tok(o.in1, true) || !tok(o.out, true) || !tok(o.res, true) ||
-            (o.kind != OPK_POOL && o.kind != OPK_ATTN && (o.conv < 0 || o.conv >= (int)nconv)) ||
-            (o.out < 0 && (o.pred_level < 0 || o.pred_level > 2)))
-            return fail(c, CY_ERR_IO, "malformed op in CYW2 plan");
-        plan->ops.push_back(o);
-    }
-    if (r.bad) return fail(c, CY_ERR_IO, "truncated weight file");
-    for (auto& t : plan->tensors) if (t.level < 0 || t.level > 5 || t.C < 1 || t.C > 65536) return fail(c, CY_ERR_IO, "malformed tensor in CYW2 plan");
-    *nconv_out = nconv;
-    plan->ok = true;
-    return CY_OK;
+// bias[cout] -> device, zero-padded to a multiple of 128 channels (the kernels read whole tiles of it)
+hipError_t upload_bias(DevOwner& own, const float* b, int co, float** out) {
+    std::vector<float> bias((co + 127) / 128 * 128, 0.0f);
+    memcpy(bias.data(), b, 4 * (size_t)co);
+    return own.upload(bias.data(), 4 * bias.size(), out);
 }
 
-// ops[i], ops[i+1] = the two 3x3 convs of a 64-channel Bottleneck (x [+] cv2(cv1(x))) whose intermediate has no other reader:
-// with CY_BNECK_FUSE=1 they run as ONE kernel in the fp16 context (bneck64.hip; off by default: measured slower so far)
-bool bneck_pair(const Plan& p, size_t i) {
-    if (i + 1 >= p.ops.size()) return false;
-    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1];
-    if (o.kind != OPK_CONV || n.kind != OPK_CONV || o.conv < 0 || n.conv < 0 || o.out < 0 || n.out < 0) return false;
-    const ConvDesc& d1 = p.convs[o.conv]; const ConvDesc& d2 = p.convs[n.conv];
-    auto c64 = [](const ConvDesc& d) { return d.k == 3 && d.s == 1 && d.cin == 64 && d.cout == 64 && d.act && d.groups == 1; };
-    if (!c64(d1) || !c64(d2)) return false;
-    if (o.in1 >= 0 || o.up0 || o.res >= 0 || o.c0 != 64 || n.in1 >= 0 || n.up0 || n.c0 != 64) return false;
-    if (n.in0 != o.out || n.in0_coff != o.out_coff) return false;
-    if (p.tensors[o.in0].level != p.tensors[o.out].level || p.tensors[o.in0].level != p.tensors[n.out].level) return false;
-    if (n.res >= 0 && (n.res != o.in0 || n.res_coff != o.in0_coff)) return false;      // the shortcut adds the bottleneck's own input
-    if (n.out == o.in0 && n.out_coff == o.in0_coff) return false;                        // in place: patches would read overwritten halos
-    // the intermediate must be dead after cv2: the next op that touches its tensor (C2f reuses one scratch tensor for all its
-    // bottlenecks) has to overwrite exactly this slice before anything reads it
-    for (size_t j = i + 2; j < p.ops.size(); ++j) {
-        const Op& q = p.ops[j];
-        if (q.in0 == o.out || q.in1 == o.out || q.res == o.out) return false;
-        if (q.out == o.out) return q.out_coff == o.out_coff && q.conv >= 0 && p.convs[q.conv].cout == 64;
-    }
-    return true;
-}
-
-// ops[i] = a convolution whose 256 output channels all sit in one tile of the pixels-direct kernel (3x3 stride 2 or 1x1, SiLU, no
-// residual, one input segment), ops[i+1] = the 1x1 convolution (256 -> <= 256 channels, one input segment, no residual) that is the ONLY
-// reader of its output: in the fp16 context the pair runs as one kernel, the first layer's accumulators feeding the second GEMM in
-// registers (conv1x1_direct_kernel<..., FUSE2>; yolov8l: model.3 -> model.4.cv1).  CY_FUSE_PW=0 turns it off.
-bool pw_pair(const Plan& p, size_t i) {
-    if (i + 1 >= p.ops.size()) return false;
-    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1];
-    if (o.kind != OPK_CONV || n.kind != OPK_CONV || o.conv < 0 || n.conv < 0 || o.out < 0 || n.out < 0) return false;
-    const ConvDesc& d1 = p.convs[o.conv]; const ConvDesc& d2 = p.convs[n.conv];
-    if (d1.groups != 1 || d2.groups != 1 || d1.cout != 256 || !d1.act || d1.cin % 64) return false;
-    if (!((d1.k == 3 && d1.s == 2 && d1.cin >= 128) || (d1.k == 1 && d1.s == 1))) return false;
-    if (d2.k != 1 || d2.s != 1 || d2.cin != 256 || d2.cout > 256 || d2.cout % 16) return false;
-    if (o.in1 >= 0 || o.up0 || o.res >= 0 || n.in1 >= 0 || n.up0 || n.res >= 0 || n.c0 != 256) return false;
-    if (n.in0 != o.out || n.in0_coff != o.out_coff || p.tensors[o.out].level != p.tensors[n.out].level) return false;
-    if (n.out == o.out) return false;
-    int readers = 0;                                         // nothing else may read the first layer's output slice
-    for (const Op& q : p.ops) readers += (q.in0 == o.out) + (q.in1 == o.out) + (q.res == o.out);
-    if (readers != 1) return false;
-    for (size_t j = i + 2; j < p.ops.size(); ++j)            // (a later op may overwrite that tensor; none may read it first: counted above)
-        if (p.ops[j].out == o.out) break;
-    return true;
-}
-
-// A CYW2 file carries its own execution plan; it is untrusted data.  Every channel slice an op names must lie inside its
-// tensor, or the kernels would address outside the workspace (the tensors' extents are the buffer-resource bounds).
-std::string validate_plan(const Plan& p) {
-    auto T = [&](int t) -> const Tensor& { return p.tensors[t]; };
-    auto inside = [&](int t, int coff, int n) { return coff >= 0 && n >= 1 && (long)coff + n <= T(t).C; };      // (untrusted u32 fields: no int overflow)
-    for (size_t i = 0; i < p.ops.size(); ++i) {
-        const Op& o = p.ops[i];
-        const std::string at = " in op " + std::to_string(i);
-        if (o.kind == OPK_POOL) {
-            if (o.out < 0 || !inside(o.in0, o.in0_coff, o.c0) || !inside(o.out, o.out_coff, o.c0) || T(o.in0).level != T(o.out).level)
-                return "pool slice outside its tensor" + at;
-            continue;
-        }
-        if (o.kind == OPK_ATTN) {
-            const long need = (long)o.p0 * (2L * o.p1 + o.p2);
-            if (o.out < 0 || o.p0 < 1 || o.p1 < 1 || o.p2 < 1 || need > 65536 || !inside(o.in0, o.in0_coff, (int)need) ||
-                (long)o.p0 * o.p2 > 65536 || !inside(o.out, o.out_coff, o.p0 * o.p2))
-                return "attention slice outside its tensor" + at;
-            continue;
-        }
-        const ConvDesc& d = p.convs[o.conv];
-        if (o.kind == OPK_DWCONV) {
-            // input channel of output channel ch: (ch / blk) * gstride + goff + ch % blk   (blk = 0: ch)
-            const int last = d.cout - 1;
-            const long cin_last = o.p0 > 0 ? (long)(last / o.p0) * o.p1 + o.p2 + last % o.p0 : last;
-            if (o.out < 0 || o.p0 < 0 || o.p1 < 0 || o.p2 < 0 || (o.p0 > 0 && o.p0 % 8) || o.in0_coff < 0 ||
-                o.in0_coff + cin_last + 1 > T(o.in0).C || !inside(o.out, o.out_coff, d.cout) ||
-                (o.res >= 0 && !inside(o.res, o.res_coff, d.cout)))
-                return "depth-wise slice outside its tensor" + at;
-            continue;
-        }
-        if (o.kind == OPK_STEM) {
-            if (o.out < 0 || !inside(o.out, o.out_coff, d.cout) || T(o.in0).C != 4 || d.cin != 3) return "malformed stem" + at;
-            continue;
-        }
-        if (!inside(o.in0, o.in0_coff, o.c0) || (o.in1 >= 0 ? !inside(o.in1, o.in1_coff, o.c1) : o.c1 != 0) || o.c0 + o.c1 != d.cin)
-            return "conv input slice does not match " + d.name + at;
-        if (o.in1 >= 0 && (d.k != 1 || o.c0 % 64)) return "two-segment input needs a 1x1 conv and a 64-aligned boundary" + at;
-        if (o.up0 && (d.k != 1 || T(o.in0).level < 1)) return "upsampled input needs a 1x1 conv" + at;
-        if (o.out >= 0 && !inside(o.out, o.out_coff, d.cout)) return "conv output slice outside its tensor" + at;
-        if (o.out < 0 && (o.pred_coff < 0 || o.pred_coff + d.cout > 64 + p.nc)) return "head slice outside the prediction row" + at;
-        if (o.res >= 0 && (!inside(o.res, o.res_coff, d.cout) || (o.out >= 0 && T(o.res).level != T(o.out).level)))
-            return "residual slice outside its tensor" + at;
-    }
-    return "";
-}
-
-int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
-    Reader r{(const unsigned char*)buf, nbytes};
-    if (nbytes < 24 || (memcmp(buf, "CYW1", 4) != 0 && memcmp(buf, "CYW2", 4) != 0)) return fail(c, CY_ERR_IO, "not a CYW weight file");
-    const bool v2 = memcmp(buf, "CYW2", 4) == 0;
-    r.o = 4;
-    Plan plan;
-    uint32_t nc = 0, nconv = 0, fver = 0;
-    std::vector<std::string> names;
-    bool has_flags = false;                                  // CYW1 version 2 / CYW2 version 3: a flags word per conv header
-    if (v2) {
-        plan.ok = false;
-        int rc = parse_plan_v2(c, r, &plan, &nconv, &names, &fver);
-        if (rc) return rc;
-        nc = (uint32_t)plan.nc;
-        has_flags = fver == 3;
-    } else {
-        fver = r.u32();
-        if (fver != 1 && fver != 2) return fail(c, CY_ERR_IO, "unsupported CYW version");
-        has_flags = fver == 2;
-        const char scale = (char)r.p[r.o]; r.o += 4;
-        nc = r.u32(); nconv = r.u32();
-        const uint32_t nnames = r.u32();
-        plan = build_plan(scale, (int)nc);
-        if (!plan.ok) return fail(c, CY_ERR_UNSUPPORTED, plan.err);
-        if (plan.convs.size() != nconv) return fail(c, CY_ERR_IO, "weight file conv count does not match the graph");
-        for (uint32_t i = 0; i < nnames; ++i) { uint32_t l = r.u32(); names.push_back(r.str(l)); }
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    free_all(c);
-    c->dconv.resize(nconv);
-    std::vector<const float*> Wsrc(nconv, nullptr);          // folded fp32 weights inside `buf` (for the fused-bottleneck packing below)
+// The device copies of one dense convolution (weight loader and cy_conv_bn_silu): bias, the packed main panel, and the second copy
+// with 64-byte K chunks for the kernels that read that form (conv3x3_wide_kernel / conv3x3_c64_kernel<32>); in the fp16x3 context
+// also the pass count and the per-channel output scale.  down_copy: the 3x3 s2 64 -> 128 layer gets the second copy too
+// (stem_down_kernel reads its weight fragments from it, and conv_variant looks at wgt32: the loader asks for it, the test entry not).
+hipError_t upload_conv(DevOwner& own, Precision prec, const float* W, const float* b, const float* wscale, int co, int ci, int k, int s,
+                       bool down_copy, DevConv& dc) {
+    hipError_t e = upload_bias(own, b, co, &dc.bias);
+    if (e != hipSuccess) return e;
+    const bool x3 = prec == PREC_F16X3;
+    std::vector<float> osc((co + 127) / 128 * 128);
     std::vector<char> packed;
+    // two passes when the filter is exactly an fp16 filter times a per-channel scale (CY_X3_PASSES=3 forces the general form)
+    if (x3) dc.passes = env_knob("CY_X3_PASSES", 0) == 3 ? 3 : x3_passes(W, co, ci, k, wscale);
+    auto panel = [&](int chunk, void** dst, size_t* bytes) {
+        *bytes = x3 ? packed_weight_bytes_x3(co, ci, k, chunk, dc.passes) : packed_weight_bytes(prec, co, ci, k, chunk);
+        packed.resize(*bytes);
+        if (x3) pack_weights_x3(W, co, ci, k, packed.data(), osc.data(), chunk, dc.passes, wscale);
+        else pack_weights(prec, W, co, ci, k, packed.data(), chunk);
+        return own.upload(packed.data(), *bytes, dst);
+    };
+    e = panel(128, &dc.w, &dc.wbytes);
+    if (e == hipSuccess && x3) e = own.upload(osc.data(), 4 * osc.size(), &dc.oscale);
+    const bool second = x3 ? (k == 3 && s == 1 && ci % 64 == 0)
+                           : prec == PREC_F16 && k == 3 && ((s == 1 && ((ci % 64 == 0 && co >= 33) || (ci == 32 && co <= 64))) ||
+                                                            (down_copy && s == 2 && ci == 64 && co == 128));
+    if (e == hipSuccess && second) e = panel(64, &dc.w32, &dc.w32bytes);
+    return e;
+}
+
+// Everything of a load behind the header, on a freed context: the conv records one by one (host checks in cy_plan.cpp, then the
+// device copies), the plan's checks, the extra weight forms of the marked pairs, workspace, stage buffers, streams and events.
+int build_model(cy_ctx* c, Reader& r, const FileHeader& h, Plan& plan) {
+    c->dconv.resize(h.nconv);
+    std::vector<const float*> Wsrc(h.nconv, nullptr);        // folded fp32 weights inside the file (for the pairs' packing below)
     int stem_conv = -1;
     for (auto& o : plan.ops) if (o.kind == OPK_STEM) stem_conv = o.conv;
-    for (uint32_t i = 0; i < nconv; ++i) {
-        const uint32_t co = r.u32(), ci = r.u32(), k = r.u32(), s = r.u32(), act = r.u32();
-        const uint32_t groups = v2 ? r.u32() : 1u;
-        const uint32_t flags = has_flags ? r.u32() : 0u;
-        const uint32_t nl = r.u32();
-        const std::string name = r.str(nl);
-        if (r.bad) return fail(c, CY_ERR_IO, "truncated weight file");
-        if (v2) {
-            if (co < 1 || ci < 1 || groups < 1 || ci % groups || (k != 1 && k != 3) || (s != 1 && s != 2))
-                return fail(c, CY_ERR_IO, "malformed conv header: " + name);
-            ConvDesc d; d.name = name; d.cin = (int)ci; d.cout = (int)co; d.k = (int)k; d.s = (int)s; d.act = (int)act; d.groups = (int)groups;
-            plan.convs.push_back(d);
-        } else {
-            const ConvDesc& d = plan.convs[i];
-            if (name != d.name || (int)co != d.cout || (int)ci != d.cin || (int)k != d.k || (int)s != d.s || (int)act != d.act)
-                return fail(c, CY_ERR_IO, "weight file layer " + name + " does not match graph layer " + d.name);
-        }
-        const float* W = r.f32((size_t)co * (ci / groups) * k * k);
-        const float* b = r.f32(co);
-        // flags bit 0: scale[cout] with W[n] = fl32(w16[n] * scale[n]), w16 the checkpoint's fp16 filter (weights.py: fold(with_scale=True))
-        const float* wscale = (flags & 1u) ? r.f32(co) : nullptr;
-        if (r.bad) return fail(c, CY_ERR_IO, "truncated weight file");
+    for (uint32_t i = 0; i < h.nconv; ++i) {
+        ConvRecord rec;
+        const std::string msg = next_conv(r, h, &plan, i, &rec);
+        if (!msg.empty()) return fail(c, CY_ERR_IO, msg);
+        const ConvDesc& d = rec.d;
+        const float* W = rec.W;
         Wsrc[i] = W;
         DevConv& dc = c->dconv[i];
-        const int cp = (co + 127) / 128 * 128;
-        std::vector<float> bias(cp, 0.0f);
-        memcpy(bias.data(), b, 4 * co);
-        HIPCHK(c, hipMalloc(&dc.bias, 4 * cp));
-        HIPCHK(c, hipMemcpy(dc.bias, bias.data(), 4 * cp, hipMemcpyHostToDevice));
-        if (groups > 1) {   // depth-wise 3x3 (YOLO11): [9][C] fp32 for dwconv3x3_kernel
-            if (groups != ci || co != ci || k != 3 || s != 1 || co % 8) return fail(c, CY_ERR_UNSUPPORTED, "only depth-wise 3x3 stride-1 grouped convs are supported: " + name);
-            const std::vector<float> dw = dw_weights(W, (int)co);
-            HIPCHK(c, hipMalloc(&dc.dw_w, 4 * dw.size()));
-            HIPCHK(c, hipMemcpy(dc.dw_w, dw.data(), 4 * dw.size(), hipMemcpyHostToDevice));
+        if (d.groups > 1) {   // depth-wise 3x3 (YOLO11): [9][C] fp32 for dwconv3x3_kernel
+            if (d.groups != d.cin || d.cout != d.cin || d.k != 3 || d.s != 1 || d.cout % 8) return fail(c, CY_ERR_UNSUPPORTED, "only depth-wise 3x3 stride-1 grouped convs are supported: " + d.name);
+            HIPCHK(c, upload_bias(c->weights, rec.b, d.cout, &dc.bias));
+            const std::vector<float> dw = dw_weights(W, d.cout);
+            HIPCHK(c, c->weights.upload(dw.data(), 4 * dw.size(), &dc.dw_w));
             continue;
         }
         if ((int)i == stem_conv) {   // stem: [27][Cout] fp32, t = (kh*3+kw)*3 + c over the 3 network input channels
-            if (co > 64 || co % 16) return fail(c, CY_ERR_UNSUPPORTED, "stem width not supported by the gfx950 stem kernel");
-            std::vector<float> sw(27 * co);
-            for (uint32_t o = 0; o < co; ++o) for (int cch = 0; cch < 3; ++cch) for (int t = 0; t < 9; ++t)
+            if (d.cout > 64 || d.cout % 16) return fail(c, CY_ERR_UNSUPPORTED, "stem width not supported by the gfx950 stem kernel");
+            HIPCHK(c, upload_bias(c->weights, rec.b, d.cout, &dc.bias));
+            const int co = d.cout;
+            std::vector<float> sw(27 * (size_t)co);
+            for (int o = 0; o < co; ++o) for (int cch = 0; cch < 3; ++cch) for (int t = 0; t < 9; ++t)
                 sw[(size_t)(t * 3 + cch) * co + o] = W[((size_t)o * 3 + cch) * 9 + t];
-            HIPCHK(c, hipMalloc(&dc.stem_w, 4 * sw.size()));
-            HIPCHK(c, hipMemcpy(dc.stem_w, sw.data(), 4 * sw.size(), hipMemcpyHostToDevice));
+            HIPCHK(c, c->weights.upload(sw.data(), 4 * sw.size(), &dc.stem_w));
             if (c->prec == PREC_F16 && co == 64) {
                 std::vector<char> pk(64 * 32 * 2 + 64 * 64 * 2);          // panel of stem_mfma_kernel, then the one of stem_down_kernel
-                pack_stem_weights(W, (int)co, pk.data());
-                pack_stem_weights2(W, (int)co, pk.data() + 64 * 32 * 2);
-                HIPCHK(c, hipMalloc(&dc.w, pk.size()));
-                HIPCHK(c, hipMemcpy(dc.w, pk.data(), pk.size(), hipMemcpyHostToDevice));
+                pack_stem_weights(W, co, pk.data());
+                pack_stem_weights2(W, co, pk.data() + 64 * 32 * 2);
+                HIPCHK(c, c->weights.upload(pk.data(), pk.size(), &dc.w));
             }
             continue;
         }
-        if (ci % 8) return fail(c, CY_ERR_UNSUPPORTED, "conv input channels must be a multiple of 8: " + name);
-        if (c->prec == PREC_F16X3) {
-            std::vector<float> osc(cp);
-            // two passes when the filter is exactly an fp16 filter times a per-channel scale (CY_X3_PASSES=3 forces the general form)
-            dc.passes = env_knob("CY_X3_PASSES", 0) == 3 ? 3 : x3_passes(W, (int)co, (int)ci, (int)k, wscale);
-            dc.wbytes = packed_weight_bytes_x3(co, ci, k, 128, dc.passes);
-            packed.resize(dc.wbytes);
-            pack_weights_x3(W, co, ci, k, packed.data(), osc.data(), 128, dc.passes, wscale);
-            HIPCHK(c, hipMalloc(&dc.w, dc.wbytes));
-            HIPCHK(c, hipMemcpy(dc.w, packed.data(), dc.wbytes, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMalloc(&dc.oscale, 4 * cp));
-            HIPCHK(c, hipMemcpy(dc.oscale, osc.data(), 4 * cp, hipMemcpyHostToDevice));
-            if (k == 3 && s == 1 && ci % 64 == 0) {          // second copy with 64-byte K chunks (conv3x3_wide_kernel)
-                dc.w32bytes = packed_weight_bytes_x3(co, ci, k, 64, dc.passes);
-                packed.resize(dc.w32bytes);
-                pack_weights_x3(W, co, ci, k, packed.data(), osc.data(), 64, dc.passes, wscale);
-                HIPCHK(c, hipMalloc(&dc.w32, dc.w32bytes));
-                HIPCHK(c, hipMemcpy(dc.w32, packed.data(), dc.w32bytes, hipMemcpyHostToDevice));
-            }
-            continue;
-        }
-        dc.wbytes = packed_weight_bytes(c->prec, co, ci, k);
-        packed.resize(dc.wbytes);
-        pack_weights(c->prec, W, co, ci, k, packed.data());
-        HIPCHK(c, hipMalloc(&dc.w, dc.wbytes));
-        HIPCHK(c, hipMemcpy(dc.w, packed.data(), dc.wbytes, hipMemcpyHostToDevice));
-        // (also the 3x3 s2 64->128 layer behind the stem: stem_down_kernel reads its weight fragments from this copy)
-        if (c->prec == PREC_F16 && k == 3 && ((s == 1 && ((ci % 64 == 0 && co >= 33) || (ci == 32 && co <= 64))) || (s == 2 && ci == 64 && co == 128))) {   // second copy (64-byte K chunks) for conv3x3_wide_kernel / conv3x3_c64_kernel<32>
-            dc.w32bytes = packed_weight_bytes(c->prec, co, ci, k, 64);
-            packed.resize(dc.w32bytes);
-            pack_weights(c->prec, W, co, ci, k, packed.data(), 64);
-            HIPCHK(c, hipMalloc(&dc.w32, dc.w32bytes));
-            HIPCHK(c, hipMemcpy(dc.w32, packed.data(), dc.w32bytes, hipMemcpyHostToDevice));
-        }
+        if (d.cin % 8) return fail(c, CY_ERR_UNSUPPORTED, "conv input channels must be a multiple of 8: " + d.name);
+        HIPCHK(c, upload_conv(c->weights, c->prec, W, rec.b, rec.wscale, d.cout, d.cin, d.k, d.s, true, dc));
     }
-    if (v2) {
+    if (h.v2) {
         const std::string bad = validate_plan(plan);
-        if (!bad.empty()) { free_all(c); return fail(c, CY_ERR_IO, "malformed CYW2 plan: " + bad); }
+        if (!bad.empty()) return fail(c, CY_ERR_IO, bad);
     }
+    mark_fusions(plan);
     if (c->prec == PREC_F16) {
-        for (size_t i = 0; i + 1 < plan.ops.size(); ++i) {      // back-to-back pairs: the second layer's weights in accumulator order
-            if (!pw_pair(plan, i)) continue;
+        for (size_t i = 0; i < plan.ops.size(); ++i) {          // back-to-back pairs: the second layer's weights in accumulator order
+            if (plan.ops[i].fuse != FUSE_PW_PAIR) continue;
             const int c2 = plan.ops[i + 1].conv;
             const ConvDesc& d2 = plan.convs[c2];
             DevConv& dc2 = c->dconv[c2];
             dc2.w2fbytes = packed_weight_bytes(PREC_F16, d2.cout, d2.cin, 1);
             std::vector<char> pk(dc2.w2fbytes);
             pack_weights_fused2(Wsrc[c2], d2.cout, d2.cin, pk.data());
-            HIPCHK(c, hipMalloc(&dc2.w2f, dc2.w2fbytes));
-            HIPCHK(c, hipMemcpy(dc2.w2f, pk.data(), dc2.w2fbytes, hipMemcpyHostToDevice));
+            HIPCHK(c, c->weights.upload(pk.data(), pk.size(), &dc2.w2f));
         }
         std::vector<char> wf(BNECK_WFRAG_BYTES);
-        for (size_t i = 0; i + 1 < plan.ops.size(); ++i) {
-            if (!bneck_pair(plan, i)) continue;
+        for (size_t i = 0; i < plan.ops.size(); ++i) {
+            if (plan.ops[i].fuse != FUSE_BNECK_PAIR) continue;
             const int c1 = plan.ops[i].conv, c2 = plan.ops[i + 1].conv;
             pack_bneck_weights(Wsrc[c1], Wsrc[c2], wf.data());
-            HIPCHK(c, hipMalloc(&c->dconv[c1].bneck, wf.size()));
-            HIPCHK(c, hipMemcpy(c->dconv[c1].bneck, wf.data(), wf.size(), hipMemcpyHostToDevice));
+            HIPCHK(c, c->weights.upload(wf.data(), wf.size(), &c->dconv[c1].bneck));
         }
     }
-    c->plan = plan; c->names = names;
+    c->plan = plan; c->names = h.names;
     // ---- workspace for (max_batch, max_h, max_w)
     const cy_config& g = c->cfg;
-    const size_t es = esize(c->prec);
+    const size_t es = esize(c->prec), nc = (size_t)plan.nc;
     size_t act = 0;
     for (auto& t : plan.tensors) act += align_up((size_t)g.max_batch * (g.max_h >> t.level) * (g.max_w >> t.level) * t.C * es, 256);
     c->ws_bytes = act;
-    HIPCHK(c, hipMalloc(&c->ws, c->ws_bytes));
+    HIPCHK(c, c->buffers.alloc(c->ws_bytes, &c->ws));
     const int A = cy_num_anchors(g.max_h, g.max_w);
     // candidates per tile: cap >= the anchor count of the largest letterboxed tile, so an overflow cannot happen; nms_kernel
     // sorts them all and keeps ultralytics' top max_nms = 30000 by score.  An explicit max_cand is honoured, and a tile that
@@ -526,23 +330,24 @@ int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
     c->cap_pow2 = 1; while (c->cap_pow2 < c->cap) c->cap_pow2 <<= 1;
     const size_t Bm = g.max_batch;
     c->pre_scratch_elems = Bm * 3 * (size_t)g.max_h * g.max_w;
+    DevOwner& own = c->buffers;
     for (auto& b : c->sb) {
-        HIPCHK(c, hipMalloc(&b.netin, Bm * g.max_h * g.max_w * 4 * es));
-        HIPCHK(c, hipMalloc(&b.pred, Bm * A * (64 + nc) * sizeof(float)));
-        HIPCHK(c, hipMalloc(&b.cand, Bm * c->cap * 6 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&b.cand_anchor, Bm * c->cap * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.cand_count, Bm * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.keys, Bm * c->cap_pow2 * sizeof(uint64_t)));
-        HIPCHK(c, hipMalloc(&b.det, Bm * CY_MAX_DET * 6 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&b.det_anchor, Bm * CY_MAX_DET * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.det_count, Bm * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.merge_err, Bm * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.out_src, Bm * CY_MAX_DET * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.pre_params, Bm * 3 * CY_MAX_STAGES * 4 * sizeof(double)));
-        HIPCHK(c, hipMalloc(&b.pre_histeq, Bm * 3 * 520 * sizeof(double)));
-        HIPCHK(c, hipMalloc(&b.pre_scratch, c->pre_scratch_elems * sizeof(double)));
+        HIPCHK(c, own.alloc(Bm * g.max_h * g.max_w * 4 * es, &b.netin));
+        HIPCHK(c, own.alloc(Bm * A * (64 + nc) * sizeof(float), &b.pred));
+        HIPCHK(c, own.alloc(Bm * c->cap * 6 * sizeof(float), &b.cand));
+        HIPCHK(c, own.alloc(Bm * c->cap * sizeof(int), &b.cand_anchor));
+        HIPCHK(c, own.alloc(Bm * sizeof(int), &b.cand_count));
+        HIPCHK(c, own.alloc(Bm * c->cap_pow2 * sizeof(uint64_t), &b.keys));
+        HIPCHK(c, own.alloc(Bm * CY_MAX_DET * 6 * sizeof(float), &b.det));
+        HIPCHK(c, own.alloc(Bm * CY_MAX_DET * sizeof(int), &b.det_anchor));
+        HIPCHK(c, own.alloc(Bm * sizeof(int), &b.det_count));
+        HIPCHK(c, own.alloc(Bm * sizeof(int), &b.merge_err));
+        HIPCHK(c, own.alloc(Bm * CY_MAX_DET * sizeof(int), &b.out_src));
+        HIPCHK(c, own.alloc(Bm * 3 * CY_MAX_STAGES * 4 * sizeof(double), &b.pre_params));
+        HIPCHK(c, own.alloc(Bm * 3 * 520 * sizeof(double), &b.pre_histeq));
+        HIPCHK(c, own.alloc(c->pre_scratch_elems * sizeof(double), &b.pre_scratch));
     }
-    HIPCHK(c, hipMalloc(&c->counters, 4 * sizeof(int)));
+    HIPCHK(c, c->counter_mem.alloc(4 * sizeof(int), &c->counters));
     HIPCHK(c, hipMemset(c->counters, 0, 4 * sizeof(int)));
     // side streams at the LOWEST priority: preprocessing and decode/NMS/merge fill the gaps of the conv stack on the caller's
     // stream instead of competing with it for CUs.  Round 4: confining them to a
@@ -556,6 +361,23 @@ int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
     for (hipEvent_t* e : evs) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     c->loaded = true;
     return CY_OK;
+}
+
+// Order of a load: what the header and plan section allow to be checked is checked BEFORE the old model is freed (a refused header
+// leaves the context as it was); then the old model goes first, so that the peak is one model and not two; then the new one is
+// built.  Any failure behind the free leaves the context freed and unloaded: every entry that needs a model refuses it, and a
+// later load of a sound file on the same context works.
+int upload_weights(cy_ctx* c, const void* buf, size_t nbytes) {
+    Reader r{(const unsigned char*)buf, nbytes};
+    Plan plan;
+    FileHeader h;
+    const std::string msg = parse_header(r, &plan, &h);
+    if (!msg.empty()) return fail(c, h.unsupported ? CY_ERR_UNSUPPORTED : CY_ERR_IO, msg);
+    HIPCHK(c, hipSetDevice(c->device));
+    free_all(c);
+    const int rc = build_model(c, r, h, plan);
+    if (rc) free_all(c);
+    return rc;
 }
 
 int layout_tensors(cy_ctx* c, int B, int H, int W, size_t capacity) {
@@ -657,13 +479,13 @@ int cy_letterbox_geometry(int h0, int w0, int imgsz, cy_letterbox* o) {
     // ultralytics LetterBox(auto=True, scaleup=True, center=True, stride=32): SURVEY.md Appendix A.1 step 2
     if (!o || h0 < 1 || w0 < 1 || imgsz < 32) return CY_ERR_ARG;
     const double r = std::fmin((double)imgsz / h0, (double)imgsz / w0);
-    o->new_w = py_round_half_even(w0 * r); o->new_h = py_round_half_even(h0 * r);
+    o->new_w = py_round(w0 * r); o->new_h = py_round(h0 * r);
     double dw = (imgsz - o->new_w) % 32, dh = (imgsz - o->new_h) % 32;
     if (dw < 0) dw += 32;
     if (dh < 0) dh += 32;
     dw /= 2; dh /= 2;
-    o->top = py_round_half_even(dh - 0.1); o->left = py_round_half_even(dw - 0.1);
-    const int bottom = py_round_half_even(dh + 0.1), right = py_round_half_even(dw + 0.1);
+    o->top = py_round(dh - 0.1); o->left = py_round(dw - 0.1);
+    const int bottom = py_round(dh + 0.1), right = py_round(dw + 0.1);
     o->H = o->new_h + o->top + bottom; o->W = o->new_w + o->left + right;
     return CY_OK;
 }
@@ -708,7 +530,7 @@ static int ensure_side_forward_stream(cy_ctx* c) {
 static int ensure_second_workspace(cy_ctx* c) {
     if (c->ws2) return CY_OK;
     c->ws2_bytes = c->ws_bytes / 2 + (1u << 20);            // the second half is never the larger one
-    HIPCHK(c, hipMalloc(&c->ws2, c->ws2_bytes));
+    HIPCHK(c, c->buffers.alloc(c->ws2_bytes, &c->ws2));
     int rc = ensure_side_forward_stream(c);
     if (rc) return rc;
     for (auto& ev : c->ev_split) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -719,13 +541,13 @@ static int ensure_second_workspace(cy_ctx* c) {
 static int ensure_small_lane(cy_ctx* c) {
     if (c->ws3) return CY_OK;
     c->ws3_bytes = c->ws_bytes / 3 + (1u << 20);            // a small batch holds at most max_batch / 3 tiles
-    HIPCHK(c, hipMalloc(&c->ws3, c->ws3_bytes));
+    HIPCHK(c, c->buffers.alloc(c->ws3_bytes, &c->ws3));
     int rc = ensure_side_forward_stream(c);
     if (rc) return rc;
     c->s_small = c->s_fwd2;                                 // (shared: see ensure_side_forward_stream)
     return CY_OK;
 }
-static int dual_mode() { const char* e = getenv("CY_DUAL_FORWARD"); return e ? atoi(e) : 1; }
+static int dual_mode() { return env_knob("CY_DUAL_FORWARD", 1); }
 
 static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t sm) {
     const int mode = dual_mode();
@@ -782,22 +604,12 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         c->prof.push_back({ev_prev, e, kind, flops, cur_conv, (c->ws3 && ws == c->ws3) ? 1 : 0});
         ev_prev = e;
     };
-    // model.0 + model.1 in one kernel (fp16 context) when the stem's only reader is a 3x3 s2 64->128 SiLU conv and the launch
-    // fills the chip.  CY_STEM_FUSE: 0 = off, 2 = regardless of size (parity tests); read per call.
-    const int fuse_env = getenv("CY_STEM_FUSE") ? atoi(getenv("CY_STEM_FUSE")) : 1;
-    auto stem_fusable = [&](const Op& o, const Op& n) -> bool {
-        if (c->prec != PREC_F16 || !fuse_env || o.kind != OPK_STEM || n.kind != OPK_CONV || n.conv < 0 || n.out < 0) return false;
-        const ConvDesc& d0 = p.convs[o.conv]; const ConvDesc& d = p.convs[n.conv];
-        if (d0.cout != 64 || !c->dconv[o.conv].w || !c->dconv[n.conv].w32) return false;
-        if (d.k != 3 || d.s != 2 || d.cin != 64 || d.cout != 128 || !d.act) return false;
-        if (n.in0 != o.out || n.in0_coff != o.out_coff || n.c0 != 64 || n.in1 >= 0 || n.res >= 0 || n.up0) return false;
-        if (p.tensors[o.out].C != 64) return false;
-        int readers = 0;
-        for (const Op& q : p.ops) readers += (q.in0 == o.out) + (q.in1 == o.out) + (q.res == o.out);
-        return readers == 1;
-    };
-    c->stem_fused_last = false;
-    c->pw_fused_conv = -1;
+    // The pairs of ops that one kernel can run carry a mark from the load (Op::fuse, cy_plan.cpp: the shape of the plan); here each
+    // mark meets its run-time gate, read per call.
+    // model.0 + model.1 in one kernel (fp16 context) when the stem's only reader is a 3x3 s2 64->128 SiLU conv (the widths the loader
+    // packed both weight forms for) and the launch fills the chip.  CY_STEM_FUSE: 0 = off, 2 = regardless of size (parity tests).
+    const int fuse_env = env_knob("CY_STEM_FUSE", 1);
+    c->fused_last.assign(p.ops.size(), 0);
     const int pw_env = env_knob("CY_FUSE_PW", 1);             // back-to-back pairs (pw_pair); read per call: the parity tests run both forms
 
     struct HeadPend { ConvArgs a; double flops; int conv; bool on; };
@@ -805,8 +617,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     const int bneck_env = env_knob("CY_BNECK_FUSE", 0);       // off by default (slower than two launches so far, see bneck64.hip); read per call: the parity tests run both forms
     auto run_op = [&](const Op& o, const Op* next, bool* fused) -> int {
         cur_conv = o.conv;
-        if (bneck_env && c->prec == PREC_F16 && o.kind == OPK_CONV && next && c->dconv[o.conv].bneck &&
-            bneck_pair(p, (size_t)(&o - p.ops.data()))) {
+        if (bneck_env && c->prec == PREC_F16 && o.fuse == FUSE_BNECK_PAIR && c->dconv[o.conv].bneck) {
             const Op& n = *next;
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[n.out];
             BneckArgs a{};
@@ -818,10 +629,10 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             a.shortcut = n.res >= 0;
             HIPCHK(c, launch_bneck64(a, s));
             prof_done(CONV_NUM_VARIANTS + 4, 2.0 * (2.0 * B * a.H * a.W * 64.0 * 64.0 * 9.0));
-            *fused = true; c->bneck_fused_last = true;
+            *fused = true;
             return CY_OK;
         }
-        if (o.kind == OPK_STEM && next && stem_fusable(o, *next)) {
+        if (o.fuse == FUSE_STEM_DOWN && c->prec == PREC_F16 && fuse_env && c->dconv[o.conv].w && c->dconv[next->conv].w32) {
             const Op& n = *next;
             const Tensor& ti = p.tensors[o.in0]; const Tensor& t1 = p.tensors[o.out]; const Tensor& to = p.tensors[n.out];
             StemDownArgs a{};
@@ -831,10 +642,10 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             a.wpk2 = reinterpret_cast<const char*>(c->dconv[o.conv].w) + 64 * 32 * 2; a.bias0 = c->dconv[o.conv].bias;
             a.wgt32 = c->dconv[n.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[n.conv].w32bytes; a.bias1 = c->dconv[n.conv].bias;
             a.out = tptr(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
-            if (ti.C == 4 && (fuse_env > 1 || batch_invariant() || stem_down_blocks(a) >= 256)) {
+            if (fuse_env > 1 || batch_invariant() || stem_down_blocks(a) >= 256) {
                 HIPCHK(c, launch_stem_down(a, s));
                 prof_done(CONV_NUM_VARIANTS, 2.0 * B * a.H1 * a.W1 * 64 * 27.0 + 2.0 * B * a.Ho * a.Wo * 128.0 * 64 * 9);
-                *fused = true; c->stem_fused_last = true;
+                *fused = true;
                 return CY_OK;
             }
         }
@@ -908,8 +719,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             }
             if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
             double flops = 2.0 * B * a.Ho * a.Wo * (double)a.Cout * a.Cin * a.k * a.k;
-            if (pw_env && c->prec == PREC_F16 && next && next->conv >= 0 && c->dconv[next->conv].w2f && conv_variant(c->prec, a) == CONV_DIRECT_256 &&
-                pw_pair(p, (size_t)(&o - p.ops.data()))) {
+            if (pw_env && c->prec == PREC_F16 && o.fuse == FUSE_PW_PAIR && c->dconv[next->conv].w2f && conv_variant(c->prec, a) == CONV_DIRECT_256) {
                 const Op& n = *next;
                 const ConvDesc& d2 = p.convs[n.conv];
                 const Tensor& to2 = p.tensors[n.out];
@@ -917,7 +727,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
                 a.act2 = d2.act; a.cout2 = d2.cout;
                 a.out2 = tptr(n.out); a.out2_ct = to2.C; a.out2_coff = n.out_coff;
                 flops += 2.0 * B * a.Ho * a.Wo * (double)d2.cout * d2.cin;
-                *fused = true; c->pw_fused_conv = o.conv;
+                *fused = true;
             }
             // the two output convolutions of a detect-head level (box branch at column 0, class branch at column 64 of the same
             // prediction rows) as ONE launch: the box branch's launch is deferred until the class branch's arguments are known
@@ -949,7 +759,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         bool fused = false;
         rc = run_op(p.ops[i], i + 1 < p.ops.size() ? &p.ops[i + 1] : nullptr, &fused);
         if (rc) return rc;
-        if (fused) ++i;                                      // the next op ran inside this one's kernel
+        if (fused) c->fused_last[i++] = 1;                   // the next op ran inside this one's kernel
     }
     c->ops_done = (int)(i < p.ops.size() ? i : p.ops.size());
     if (n_run < p.ops.size()) return CY_OK;                   // stopped: a deferred box branch stays unlaunched
@@ -1070,7 +880,8 @@ int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t ca
     if (c->lastB == 0) return fail(c, CY_ERR_STATE, "no forward has run");
     if (c->split_last) return fail(c, CY_ERR_STATE, "the last batch ran as two half-batches (CY_DUAL_FORWARD=0 keeps it in one workspace)");
     const Plan& p = c->plan;
-    for (const Op& o : p.ops) {
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        const Op& o = p.ops[i];
         if (o.conv < 0 || p.convs[o.conv].name != conv_name) continue;      // pool and attention ops carry no convolution
         if (o.out < 0) return fail(c, CY_ERR_UNSUPPORTED, "head outputs are read from d_pred");
         // the bottlenecks of one C2f share the buffer of their cv1 outputs: all but the last one's are gone after the pass
@@ -1079,12 +890,10 @@ int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t ca
             if (q->out == o.out && q->out_coff < o.out_coff + p.convs[o.conv].cout && o.out_coff < q->out_coff + qc)
                 return fail(c, CY_ERR_STATE, "this layer's output was not materialised beyond its reader: a later layer of the same block reuses its buffer");
         }
-        if (c->bneck_fused_last && c->dconv[o.conv].bneck && env_knob("CY_BNECK_FUSE", 0))
-            return fail(c, CY_ERR_STATE, "this bottleneck ran fused: its cv1 output was not materialised; unset CY_BNECK_FUSE");
-        if (o.conv == c->pw_fused_conv && c->pw_fused_conv >= 0 && env_knob("CY_FUSE_PW", 1))
-            return fail(c, CY_ERR_STATE, "this layer ran fused with the 1x1 convolution behind it: its output was not materialised; CY_FUSE_PW=0 runs the two layers apart");
-        if (o.kind == OPK_STEM && c->stem_fused_last)
-            return fail(c, CY_ERR_STATE, "the stem output was not materialised (fused into the next layer's kernel); set CY_STEM_FUSE=0");
+        if (i < c->fused_last.size() && c->fused_last[i])
+            return fail(c, CY_ERR_STATE, o.fuse == FUSE_BNECK_PAIR ? "this bottleneck ran fused: its cv1 output was not materialised; unset CY_BNECK_FUSE"
+                                         : o.fuse == FUSE_PW_PAIR ? "this layer ran fused with the 1x1 convolution behind it: its output was not materialised; CY_FUSE_PW=0 runs the two layers apart"
+                                         : "the stem output was not materialised (fused into the next layer's kernel); set CY_STEM_FUSE=0");
         return cy_debug_read_tensor(c, o.out, o.out_coff, p.convs[o.conv].cout, h_out, cap, dims4);
     }
     return fail(c, CY_ERR_ARG, std::string("no such conv: ") + conv_name);
@@ -1095,84 +904,31 @@ int cy_conv_bn_silu(cy_ctx* c, const void* d_in, int B, int Hi, int Wi, int Cin,
     if (!c || !d_in || !h_w || !h_b || !d_out) return fail(c, CY_ERR_ARG, "null argument");
     if ((k != 1 && k != 3) || (s != 1 && s != 2) || Cin % 8 || B < 1) return fail(c, CY_ERR_ARG, "unsupported conv geometry");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->prec == PREC_F16X3) {
-        // fp16x3 context: caller tensors are fp32 NHWC; they are split into high / low halves here, the layer runs on the split
-        // kernels exactly as inside the forward pass, and the result is merged back to fp32
-        hipStream_t st = (hipStream_t)stream;
-        const int pad = k / 2, Ho = (Hi + 2 * pad - k) / s + 1, Wo = (Wi + 2 * pad - k) / s + 1, cp = (Cout + 127) / 128 * 128;
-        const size_t nin = (size_t)B * Hi * Wi, nout = (size_t)B * Ho * Wo;
-        const int passes = env_knob("CY_X3_PASSES", 0) == 3 ? 3 : x3_passes(h_w, Cout, Cin, k, nullptr);     // 2 when every weight is an fp16 value
-        const size_t wb = packed_weight_bytes_x3(Cout, Cin, k, 128, passes), wb32 = (k == 3 && s == 1 && Cin % 64 == 0) ? packed_weight_bytes_x3(Cout, Cin, k, 64, passes) : 0;
-        std::vector<char> packed(wb), p32(wb32);
-        std::vector<float> osc(cp), bias(cp, 0.0f);
-        pack_weights_x3(h_w, Cout, Cin, k, packed.data(), osc.data(), 128, passes);
-        if (wb32) pack_weights_x3(h_w, Cout, Cin, k, p32.data(), osc.data(), 64, passes);
-        memcpy(bias.data(), h_b, 4 * Cout);
-        void *dw = nullptr, *dw32 = nullptr, *xin = nullptr, *xres = nullptr, *xout = nullptr; float *db = nullptr, *dsc = nullptr;
-        auto cleanup = [&]() { for (void* q : {dw, dw32, xin, xres, xout, (void*)db, (void*)dsc}) if (q) hipFree(q); };
-        hipError_t e = hipMalloc(&dw, wb);
-        if (e == hipSuccess && wb32) e = hipMalloc(&dw32, wb32);
-        if (e == hipSuccess) e = hipMalloc(&db, 4 * cp);
-        if (e == hipSuccess) e = hipMalloc(&dsc, 4 * cp);
-        if (e == hipSuccess) e = hipMalloc(&xin, nin * Cin * 4);
-        if (e == hipSuccess) e = hipMalloc(&xout, nout * Cout * 4);
-        if (e == hipSuccess && d_res) e = hipMalloc(&xres, nout * Cout * 4);
-        if (e == hipSuccess) e = hipMemcpy(dw, packed.data(), wb, hipMemcpyHostToDevice);
-        if (e == hipSuccess && wb32) e = hipMemcpy(dw32, p32.data(), wb32, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(db, bias.data(), 4 * cp, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsc, osc.data(), 4 * cp, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = launch_x3_split(reinterpret_cast<const float*>(d_in), xin, (long)nin, Cin, st);
-        if (e == hipSuccess && d_res) e = launch_x3_split(reinterpret_cast<const float*>(d_res), xres, (long)nout, Cout, st);
-        if (e == hipSuccess) {
-            ConvArgs a{};
-            a.in0 = xin; a.in0_ct = 2 * Cin; a.c0 = Cin; a.in0_bytes = (uint32_t)(nin * Cin * 4); a.in0_lo = Cin;
-            a.wgt = dw; a.wgt_bytes = (uint32_t)wb; a.bias = db; a.wgt32 = dw32; a.wgt32_bytes = (uint32_t)wb32; a.oscale = dsc; a.split = passes;
-            a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.k = k; a.s = s; a.act = act;
-            a.out = xout; a.out_ct = 2 * Cout; a.out_lo = Cout; a.out_bs = Ho * Wo;
-            if (d_res) { a.res = xres; a.res_ct = 2 * Cout; a.res_lo = Cout; }
-            e = launch_conv(c->prec, a, st);
-        }
-        if (e == hipSuccess) e = launch_x3_merge(xout, reinterpret_cast<float*>(d_out), (long)nout, Cout, st);
-        const hipError_t e2 = hipStreamSynchronize(st);
-        cleanup();
-        if (e != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
-        return CY_OK;
+    // fp16x3 context: caller tensors are fp32 NHWC; they are split into high / low halves here, the layer runs on the split
+    // kernels exactly as inside the forward pass, and the result is merged back to fp32
+    hipStream_t st = (hipStream_t)stream;
+    const bool x3 = c->prec == PREC_F16X3;
+    const int cm = x3 ? 2 : 1, pad = k / 2, Ho = (Hi + 2 * pad - k) / s + 1, Wo = (Wi + 2 * pad - k) / s + 1;
+    const long nin = (long)B * Hi * Wi, nout = (long)B * Ho * Wo;
+    DevOwner sc;
+    DevConv dc;
+    void *in = const_cast<void*>(d_in), *res = const_cast<void*>(d_res), *out = d_out;
+    hipError_t e = upload_conv(sc, c->prec, h_w, h_b, nullptr, Cout, Cin, k, s, false, dc);
+    if (e == hipSuccess && x3) e = sc.split(d_in, nin, Cin, &in, st);
+    if (e == hipSuccess && x3 && d_res) e = sc.split(d_res, nout, Cout, &res, st);
+    if (e == hipSuccess && x3) e = sc.alloc((size_t)nout * Cout * 4, &out);
+    if (e == hipSuccess) {
+        ConvArgs a{};
+        a.in0 = in; a.in0_ct = cm * Cin; a.c0 = Cin; a.in0_bytes = (uint32_t)((size_t)nin * Cin * esize(c->prec)); a.in0_lo = x3 ? Cin : 0;
+        a.wgt = dc.w; a.wgt_bytes = (uint32_t)dc.wbytes; a.bias = dc.bias; a.wgt32 = dc.w32; a.wgt32_bytes = (uint32_t)dc.w32bytes;
+        a.oscale = dc.oscale; a.split = x3 ? dc.passes : 0;
+        a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.k = k; a.s = s; a.act = act;
+        a.out = out; a.out_ct = cm * Cout; a.out_lo = x3 ? Cout : 0; a.out_bs = Ho * Wo;
+        if (d_res) { a.res = res; a.res_ct = cm * Cout; a.res_lo = x3 ? Cout : 0; }
+        e = launch_conv(c->prec, a, st);
     }
-    const size_t es = esize(c->prec);
-    const size_t wb = packed_weight_bytes(c->prec, Cout, Cin, k);
-    std::vector<char> packed(wb);
-    pack_weights(c->prec, h_w, Cout, Cin, k, packed.data());
-    const int cp = (Cout + 127) / 128 * 128;
-    std::vector<float> bias(cp, 0.0f);
-    memcpy(bias.data(), h_b, 4 * Cout);
-    void* dw = nullptr; float* db = nullptr;
-    HIPCHK(c, hipMalloc(&dw, wb));
-    HIPCHK(c, hipMalloc(&db, 4 * cp));
-    HIPCHK(c, hipMemcpy(dw, packed.data(), wb, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(db, bias.data(), 4 * cp, hipMemcpyHostToDevice));
-    void* dw32 = nullptr; size_t wb32 = 0;
-    if (c->prec == PREC_F16 && k == 3 && s == 1 && ((Cin % 64 == 0 && Cout >= 33) || (Cin == 32 && Cout <= 64))) {
-        wb32 = packed_weight_bytes(c->prec, Cout, Cin, k, 64);
-        std::vector<char> p32(wb32);
-        pack_weights(c->prec, h_w, Cout, Cin, k, p32.data(), 64);
-        HIPCHK(c, hipMalloc(&dw32, wb32));
-        HIPCHK(c, hipMemcpy(dw32, p32.data(), wb32, hipMemcpyHostToDevice));
-    }
-    ConvArgs a{};
-    const int pad = k / 2;
-    a.in0 = d_in; a.in0_ct = Cin; a.c0 = Cin; a.in0_bytes = (uint32_t)((size_t)B * Hi * Wi * Cin * es);
-    a.wgt = dw; a.wgt_bytes = (uint32_t)wb; a.bias = db; a.wgt32 = dw32; a.wgt32_bytes = (uint32_t)wb32;
-    a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = (Hi + 2 * pad - k) / s + 1; a.Wo = (Wi + 2 * pad - k) / s + 1;
-    a.Cin = Cin; a.Cout = Cout; a.k = k; a.s = s; a.act = act;
-    a.out = d_out; a.out_ct = Cout; a.out_bs = a.Ho * a.Wo;
-    if (d_res) { a.res = d_res; a.res_ct = Cout; }
-    hipError_t e = launch_conv(c->prec, a, (hipStream_t)stream);
-    hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(dw); hipFree(db); if (dw32) hipFree(dw32);
-    if (e != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
-    return CY_OK;
+    if (e == hipSuccess && x3) e = launch_x3_merge(out, reinterpret_cast<float*>(d_out), nout, Cout, st);
+    return entry_done(c, e, st);
 }
 
 int cy_bottleneck64(cy_ctx* c, const void* d_in, int B, int H, int W, const float* h_w1, const float* h_b1, const float* h_w2,
@@ -1182,22 +938,20 @@ int cy_bottleneck64(cy_ctx* c, const void* d_in, int B, int H, int W, const floa
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<char> wf(BNECK_WFRAG_BYTES);
     pack_bneck_weights(h_w1, h_w2, wf.data());
+    std::vector<float> bias(h_b1, h_b1 + 64);
+    bias.insert(bias.end(), h_b2, h_b2 + 64);
+    DevOwner sc;
     void* dw = nullptr; float* db = nullptr;
-    HIPCHK(c, hipMalloc(&dw, wf.size()));
-    HIPCHK(c, hipMalloc(&db, 128 * sizeof(float)));
-    HIPCHK(c, hipMemcpy(dw, wf.data(), wf.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(db, h_b1, 64 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(db + 64, h_b2, 64 * sizeof(float), hipMemcpyHostToDevice));
-    BneckArgs a{};
-    a.in = d_in; a.in_ct = 64; a.in_coff = 0; a.in_bytes = (uint32_t)((size_t)B * H * W * 64 * 2);
-    a.out = d_out; a.out_ct = 64; a.out_coff = 0; a.wfrag = dw; a.bias1 = db; a.bias2 = db + 64;
-    a.B = B; a.H = H; a.W = W; a.shortcut = shortcut != 0;
-    hipError_t e = launch_bneck64(a, (hipStream_t)stream);
-    hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-    hipFree(dw); hipFree(db);
-    if (e != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, CY_ERR_HIP, hipGetErrorString(e2));
-    return CY_OK;
+    hipError_t e = sc.upload(wf.data(), wf.size(), &dw);
+    if (e == hipSuccess) e = sc.upload(bias.data(), 128 * sizeof(float), &db);
+    if (e == hipSuccess) {
+        BneckArgs a{};
+        a.in = d_in; a.in_ct = 64; a.in_coff = 0; a.in_bytes = (uint32_t)((size_t)B * H * W * 64 * 2);
+        a.out = d_out; a.out_ct = 64; a.out_coff = 0; a.wfrag = dw; a.bias1 = db; a.bias2 = db + 64;
+        a.B = B; a.H = H; a.W = W; a.shortcut = shortcut != 0;
+        e = launch_bneck64(a, (hipStream_t)stream);
+    }
+    return entry_done(c, e, (hipStream_t)stream);
 }
 
 // ---- kernel-level test entries of the YOLO11 operators: one launch_dwconv / launch_attention / launch_pool5 with the argument
@@ -1218,7 +972,7 @@ int cy_dwconv3x3(cy_ctx* c, const void* d_in, int B, int H, int W, int C, int in
     const int cm = x3 ? 2 : 1;
     const long npix = (long)B * H * W;
     const std::vector<float> dw = dw_weights(h_w, C);
-    EntryScratch sc;
+    DevOwner sc;
     void *wd = nullptr, *bd = nullptr, *in = const_cast<void*>(d_in), *res = const_cast<void*>(d_res), *out = d_out;
     hipError_t e = sc.alloc(4 * dw.size(), &wd);
     if (e == hipSuccess) e = sc.alloc(4 * (size_t)C, &bd);
@@ -1253,7 +1007,7 @@ int cy_attention(cy_ctx* c, const void* d_qkv, int B, int N, int ct, int coff, i
     const bool x3 = c->prec == PREC_F16X3;
     const int cm = x3 ? 2 : 1;
     const long npix = (long)B * N;
-    EntryScratch sc;
+    DevOwner sc;
     void *qkv = const_cast<void*>(d_qkv), *out = d_out;
     hipError_t e = hipSuccess;
     if (x3) e = sc.split(d_qkv, npix, ct, &qkv, st);
@@ -1286,7 +1040,7 @@ int cy_maxpool5(cy_ctx* c, const void* d_src, int B, int H, int W, int C, int ct
     const bool x3 = c->prec == PREC_F16X3;
     const int cm = x3 ? 2 : 1;
     const long npix = (long)B * H * W;
-    EntryScratch sc;
+    DevOwner sc;
     void *src = const_cast<void*>(d_src), *dst = d_dst;
     hipError_t e = hipSuccess;
     if (x3) e = sc.split(d_dst, npix, ct, &dst, st);
@@ -1405,17 +1159,41 @@ int cy_preproc_planes(cy_ctx* c, const float* d_mosaic, int MH, int MW, const in
     return CY_OK;
 }
 
-int cy_letterbox_pack(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, void* d_netin, void* stream) {
+// planes -> the letterboxed network input of type out_prec
+static int letterbox_pack_as(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, void* d_out, Precision out_prec, void* stream) {
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
-    if (!d_planes || !d_netin || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
+    if (!d_planes || !d_out || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
     cy_letterbox lb;
     if (cy_letterbox_geometry(h0, w0, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad image/imgsz");
     if (lb.H > c->cfg.max_h || lb.W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "letterboxed image exceeds max_h/max_w of the context");
     PreArgs a{};
     a.B = B; a.th = h0; a.tw = w0; a.scratch = const_cast<double*>(d_planes);
-    a.out = d_netin; a.out_prec = io_prec(c->prec); a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
+    a.out = d_out; a.out_prec = out_prec; a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
     a.new_h = lb.new_h; a.new_w = lb.new_w;
     HIPCHK(c, launch_letterbox_pack(a, (hipStream_t)stream));
+    return CY_OK;
+}
+int cy_letterbox_pack(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, void* d_netin, void* stream) {
+    return letterbox_pack_as(c, d_planes, B, h0, w0, imgsz, d_netin, c ? io_prec(c->prec) : PREC_F32, stream);
+}
+int cy_letterbox_pack_f32(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, float* d_out, void* stream) {
+    return letterbox_pack_as(c, d_planes, B, h0, w0, imgsz, d_out, PREC_F32, stream);
+}
+
+// NMS over the candidates a decode left in (cand, cand_anchor, keys: capacity cap per tile) + ultralytics scale_boxes (gain / pad from
+// the letterboxed and the original shape), for the plain and the augmented decode
+static int nms_on(cy_ctx* c, const float* cand, const int* cand_anchor, uint64_t* keys, int cap, int B, int H, int W, int h0, int w0,
+                  float iou, float* d_det, int* d_det_anchor, int* d_count, hipStream_t s) {
+    NmsArgs n{};
+    n.cand = cand; n.cand_anchor = cand_anchor; n.cand_count = c->S().cand_count; n.cap = cap; n.B = B; n.iou = iou;
+    n.max_det = CY_MAX_DET;
+    const double gain = std::fmin((double)H / h0, (double)W / w0);
+    n.gain = (float)gain;
+    n.padw = py_round((W - w0 * gain) / 2 - 0.1); n.padh = py_round((H - h0 * gain) / 2 - 0.1);
+    n.w0 = w0; n.h0 = h0;
+    n.det = d_det; n.det_anchor = d_det_anchor; n.det_count = d_count; n.keys = keys; n.mask = nullptr;
+    n.counters = c->counters;
+    HIPCHK(c, launch_nms(n, s));
     return CY_OK;
 }
 
@@ -1431,18 +1209,7 @@ int cy_decode_nms(cy_ctx* c, const float* d_pred, int B, int H, int W, int h0, i
     d.cand = c->S().cand; d.cand_anchor = c->S().cand_anchor; d.cand_count = c->S().cand_count; d.cap = c->cap;
     HIPCHK(c, hipMemsetAsync(c->S().cand_count, 0, B * sizeof(int), s));
     HIPCHK(c, launch_decode(d, s));
-    NmsArgs n{};
-    n.cand = c->S().cand; n.cand_anchor = c->S().cand_anchor; n.cand_count = c->S().cand_count; n.cap = c->cap; n.B = B; n.iou = iou;
-    n.max_det = CY_MAX_DET;
-    // ultralytics scale_boxes: gain / pad from the letterboxed and original shapes
-    const double gain = std::fmin((double)H / h0, (double)W / w0);
-    n.gain = (float)gain;
-    n.padw = py_round_half_even((W - w0 * gain) / 2 - 0.1); n.padh = py_round_half_even((H - h0 * gain) / 2 - 0.1);
-    n.w0 = w0; n.h0 = h0;
-    n.det = d_det; n.det_anchor = d_det_anchor; n.det_count = d_count; n.keys = c->S().keys; n.mask = nullptr;
-    n.counters = c->counters;
-    HIPCHK(c, launch_nms(n, s));
-    return CY_OK;
+    return nms_on(c, c->S().cand, c->S().cand_anchor, c->S().keys, c->cap, B, H, W, h0, w0, iou, d_det, d_det_anchor, d_count, s);
 }
 
 int cy_iou_merge(cy_ctx* c, const float* d_det, const int* d_count, int B, float score_thr, double soft, double hard,
@@ -1457,18 +1224,18 @@ int cy_iou_merge(cy_ctx* c, const float* d_det, const int* d_count, int B, float
     return CY_OK;
 }
 
-int cy_detect_tiles(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw, int imgsz,
-                    const cy_preproc_cfg* cfg, float conf, float iou, double soft, double hard,
-                    float* d_out, int* d_out_count, int* d_status, void* stream) {
+// One batch of the pipelined detect pass, plain or augmented.  The callers differ in three places: `pack` queues what builds the
+// network input(s) on the preprocessing stream, `forwards` runs one forward per view through the lane's `fwd(in, H, W, pred)`, and
+// `decode` queues decode + NMS into the buffer set's detections on the post-processing stream.
+extern "C++" template <class Pack, class Forwards, class Decode>
+static int pipeline_batch(cy_ctx* c, const float* d_mosaic, int B, float conf, double soft, double hard, float* d_out, int* d_out_count,
+                          void* stream, Pack&& pack, Forwards&& forwards, Decode&& decode) {
     // Software pipeline over consecutive calls (batches): three streams, two buffer sets (+ the small-batch lane below).
     //   s_pre  : preprocessing of batch i      (waits: forward of batch i-2 has consumed this set's network input)
     //   stream : forward of batch i            (waits: preprocessing i; post-processing i-2 has consumed this set's head output)
     //   s_post : decode/NMS/IoU-merge of batch i (waits: forward i)
     // so the latency-bound statistics / NMS / merge kernels (a few dozen workgroups) run beside the conv stack of the
     // neighbouring batches instead of serialising with it.  Outputs are complete after cy_detect_flush(ctx, stream).
-    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
-    cy_letterbox lb;
-    if (cy_letterbox_geometry(th, tw, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad tile/imgsz");
     hipStream_t sm = (hipStream_t)stream;
     // Small batches (the ragged edge classes of a grid: 39 + 39 + 1 of the 1600 tiles of the 16k mosaic) take their own lane:
     // buffer set 2, forward on the second stream / workspace.  A batch of 1-39 tiles is a chain of ~105 kernels of a few
@@ -1495,6 +1262,7 @@ int cy_detect_tiles(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int*
     const int side_mode = env_knob("CY_SIDE_STREAMS", 2);
     if (side_mode == 3) { rc = ensure_side_forward_stream(c); if (rc) return rc; }
     hipStream_t spost = side_mode == 1 ? c->s_pre : (side_mode == 3 ? c->s_fwd2 : c->s_post);
+    struct SlotReset { cy_ctx* c; ~SlotReset() { c->slot = 0; } } slot_reset{c};      // the stage entry points use set 0 outside this call
     c->slot = sl;
     // order the side streams after whatever the caller already queued on `stream` -- only where that matters: the first batch
     // after load / flush, or after cy_mosaic_prepare.  Later batches are ordered by ev_fwd / ev_post alone, so that the
@@ -1510,27 +1278,37 @@ int cy_detect_tiles(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int*
         c->mosaic_dirty = false;
     }
     if (reuse) HIPCHK(c, hipStreamWaitEvent(c->s_pre, c->ev_fwd[sl], 0));
-    rc = cy_preproc(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, c->S().netin, d_status, c->s_pre);
-    if (rc) { c->slot = 0; return rc; }
+    rc = pack(c->s_pre);
+    if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev_pre[sl], c->s_pre));
     HIPCHK(c, hipStreamWaitEvent(sf, c->ev_pre[sl], 0));
     if (reuse) HIPCHK(c, hipStreamWaitEvent(sf, c->ev_post[sl], 0));
-    if (small) {
+    rc = forwards([&](const void* in, int H, int W, float* pred) -> int {
+        if (!small) return forward_split(c, in, B, H, W, pred, sm);
         c->split_last = false;
-        rc = forward_on(c, c->S().netin, B, lb.H, lb.W, c->S().pred, sf, c->ws3, c->ws3_bytes, true);      // (profiled like the main lane)
-    } else {
-        rc = forward_split(c, c->S().netin, B, lb.H, lb.W, c->S().pred, sm);
-    }
-    if (rc) { c->slot = 0; return rc; }
+        return forward_on(c, in, B, H, W, pred, sf, c->ws3, c->ws3_bytes, true);      // (profiled like the main lane)
+    });
+    if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev_fwd[sl], sf));
     HIPCHK(c, hipStreamWaitEvent(spost, c->ev_fwd[sl], 0));
-    rc = cy_decode_nms(c, c->S().pred, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, spost);
+    rc = decode(spost);
     if (!rc) rc = cy_iou_merge(c, c->S().det, c->S().det_count, B, conf, soft, hard, d_out, d_out_count, nullptr, spost);
-    if (rc) { c->slot = 0; return rc; }
+    if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev_post[sl], spost));
     if (small) c->small_batches++; else c->batches++;
-    c->slot = 0;
     return CY_OK;
+}
+
+int cy_detect_tiles(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int* h_tiles, int B, int th, int tw, int imgsz,
+                    const cy_preproc_cfg* cfg, float conf, float iou, double soft, double hard,
+                    float* d_out, int* d_out_count, int* d_status, void* stream) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    cy_letterbox lb;
+    if (cy_letterbox_geometry(th, tw, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad tile/imgsz");
+    return pipeline_batch(c, d_mosaic, B, conf, soft, hard, d_out, d_out_count, stream,
+        [&](hipStream_t s) { return cy_preproc(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, c->S().netin, d_status, s); },
+        [&](auto&& fwd) { return fwd(c->S().netin, lb.H, lb.W, c->S().pred); },
+        [&](hipStream_t s) { return cy_decode_nms(c, c->S().pred, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, s); });
 }
 
 int cy_detect_fence(cy_ctx* c, void* stream) {
@@ -1812,7 +1590,7 @@ int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int 
     const size_t bytes = (size_t)ncy * ncx * 2 * sizeof(double);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    EntryScratch sc;
+    DevOwner sc;
     void* d_mesh = nullptr;
     HIPCHK(c, sc.alloc(bytes, &d_mesh));
     hipError_t e = hipMemcpyAsync(d_mesh, h_mesh, bytes, hipMemcpyHostToDevice, st);
@@ -1869,32 +1647,20 @@ int cy_enable_augment(cy_ctx* c) {
     c->acap = cand_capacity(g.max_cand > 0 ? g.max_cand : ag.total);
     c->acap_pow2 = 1; while (c->acap_pow2 < c->acap) c->acap_pow2 <<= 1;
     const int nc = c->plan.nc;
+    c->aug_mem.reset();                                     // (what an earlier attempt that failed half-way left)
     for (auto& b : c->ab) {
+        b = cy_ctx::AugBufs();
         for (int k = 0; k < 2; ++k) {
             const cy_augment_view& v = ag.v[k + 1];
-            HIPCHK(c, hipMalloc(&b.view[k], Bm * v.Hp * v.Wp * 4 * es));
-            HIPCHK(c, hipMalloc(&b.pred[k], Bm * v.A * (64 + nc) * sizeof(float)));
+            HIPCHK(c, c->aug_mem.alloc(Bm * v.Hp * v.Wp * 4 * es, &b.view[k]));
+            HIPCHK(c, c->aug_mem.alloc(Bm * v.A * (64 + nc) * sizeof(float), &b.pred[k]));
         }
-        if (c->prec == PREC_F16) HIPCHK(c, hipMalloc(&b.src32, Bm * g.max_h * g.max_w * 4 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&b.cand, Bm * c->acap * 6 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&b.cand_anchor, Bm * c->acap * sizeof(int)));
-        HIPCHK(c, hipMalloc(&b.keys, Bm * c->acap_pow2 * sizeof(uint64_t)));
+        if (c->prec == PREC_F16) HIPCHK(c, c->aug_mem.alloc(Bm * g.max_h * g.max_w * 4 * sizeof(float), &b.src32));
+        HIPCHK(c, c->aug_mem.alloc(Bm * c->acap * 6 * sizeof(float), &b.cand));
+        HIPCHK(c, c->aug_mem.alloc(Bm * c->acap * sizeof(int), &b.cand_anchor));
+        HIPCHK(c, c->aug_mem.alloc(Bm * c->acap_pow2 * sizeof(uint64_t), &b.keys));
     }
     c->aug = true;
-    return CY_OK;
-}
-
-int cy_letterbox_pack_f32(cy_ctx* c, const double* d_planes, int B, int h0, int w0, int imgsz, float* d_out, void* stream) {
-    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
-    if (!d_planes || !d_out || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
-    cy_letterbox lb;
-    if (cy_letterbox_geometry(h0, w0, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad image/imgsz");
-    if (lb.H > c->cfg.max_h || lb.W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "letterboxed image exceeds max_h/max_w of the context");
-    PreArgs a{};
-    a.B = B; a.th = h0; a.tw = w0; a.scratch = const_cast<double*>(d_planes);
-    a.out = d_out; a.out_prec = PREC_F32; a.H = lb.H; a.W = lb.W; a.top = lb.top; a.left = lb.left;
-    a.new_h = lb.new_h; a.new_w = lb.new_w;
-    HIPCHK(c, launch_letterbox_pack(a, (hipStream_t)stream));
     return CY_OK;
 }
 
@@ -1941,17 +1707,7 @@ static int decode_nms_aug_on(cy_ctx* c, const float* const* d_pred, int B, int H
     d.cand = c->AB().cand; d.cand_anchor = c->AB().cand_anchor; d.cand_count = c->S().cand_count; d.cap = c->acap;
     HIPCHK(c, hipMemsetAsync(c->S().cand_count, 0, B * sizeof(int), s));
     HIPCHK(c, launch_decode_augmented(d, s));
-    NmsArgs n{};
-    n.cand = c->AB().cand; n.cand_anchor = c->AB().cand_anchor; n.cand_count = c->S().cand_count; n.cap = c->acap; n.B = B; n.iou = iou;
-    n.max_det = CY_MAX_DET;
-    const double gain = std::fmin((double)H / h0, (double)W / w0);         // scale_boxes against view 0, as cy_decode_nms
-    n.gain = (float)gain;
-    n.padw = py_round_half_even((W - w0 * gain) / 2 - 0.1); n.padh = py_round_half_even((H - h0 * gain) / 2 - 0.1);
-    n.w0 = w0; n.h0 = h0;
-    n.det = d_det; n.det_anchor = d_det_anchor; n.det_count = d_count; n.keys = c->AB().keys; n.mask = nullptr;
-    n.counters = c->counters;
-    HIPCHK(c, launch_nms(n, s));
-    return CY_OK;
+    return nms_on(c, c->AB().cand, c->AB().cand_anchor, c->AB().keys, c->acap, B, H, W, h0, w0, iou, d_det, d_det_anchor, d_count, s);      // (scale_boxes against view 0)
 }
 
 int cy_decode_nms_augmented(cy_ctx* c, const float* d_pred0, const float* d_pred1, const float* d_pred2, int B, int H, int W,
@@ -1970,10 +1726,10 @@ int cy_detect_tiles_augmented(cy_ctx* c, const float* d_mosaic, int MH, int MW, 
                               float* d_out, int* d_out_count, int* d_status, void* stream) {
     if (!augment)
         return cy_detect_tiles(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, conf, iou, soft, hard, d_out, d_out_count, d_status, stream);
-    // cy_detect_tiles' pipeline (streams, buffer sets, events, lanes: see there), with three views per batch: the view kernel runs
-    // on the preprocessing stream behind the letterbox pack, the three forwards back to back on the forward stream, and the
-    // augmented decode + NMS + IoU merge on the post-processing stream.  The view buffers belong to the buffer set, so the events
-    // that order a set's reuse order them too, and plain and augmented calls mix freely in one unflushed pipeline.
+    // cy_detect_tiles' pipeline (pipeline_batch), with three views per batch: the view kernel runs on the preprocessing stream
+    // behind the letterbox pack, the three forwards back to back on the forward stream, and the augmented decode + NMS + IoU merge
+    // on the post-processing stream.  The view buffers belong to the buffer set, so the events that order a set's reuse order
+    // them too, and plain and augmented calls mix freely in one unflushed pipeline.
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
     if (!c->aug) return fail(c, CY_ERR_STATE, "test-time augmentation not enabled on this context (cy_enable_augment)");
     cy_letterbox lb;
@@ -1981,58 +1737,25 @@ int cy_detect_tiles_augmented(cy_ctx* c, const float* d_mosaic, int MH, int MW, 
     if (lb.H > c->cfg.max_h || lb.W > c->cfg.max_w) return fail(c, CY_ERR_ARG, "letterboxed tile exceeds max_h/max_w of the context");
     cy_augment_geom ag;
     if (cy_augment_geometry(lb.H, lb.W, &ag)) return fail(c, CY_ERR_ARG, "bad letterboxed size");
-    hipStream_t sm = (hipStream_t)stream;
-    const bool small = env_knob("CY_SMALL_LANE", 1) && c->prec != PREC_F32 && B < 64 && (long)B * 3 <= c->cfg.max_batch;
-    int rc = CY_OK;
-    if (small) { rc = ensure_small_lane(c); if (rc) return rc; }
-    const int sl = small ? 2 : (int)(c->batches & 1);
-    const bool reuse = small ? c->small_batches >= 1 : c->batches >= 2;
-    hipStream_t sf = small ? c->s_small : sm;
-    const int side_mode = env_knob("CY_SIDE_STREAMS", 2);
-    if (side_mode == 3) { rc = ensure_side_forward_stream(c); if (rc) return rc; }
-    hipStream_t spost = side_mode == 1 ? c->s_pre : (side_mode == 3 ? c->s_fwd2 : c->s_post);
-    c->slot = sl;
-    bool seen = false;
-    for (int i = 0; i < c->n_seen; ++i) seen = seen || c->seen_mosaic[i] == (const void*)d_mosaic;
-    if (c->batches + c->small_batches == 0 || c->mosaic_dirty || !seen) {
-        HIPCHK(c, hipEventRecord(c->ev_call, sm));
-        HIPCHK(c, hipStreamWaitEvent(c->s_pre, c->ev_call, 0));
-        if (c->mosaic_dirty || c->batches + c->small_batches == 0) c->n_seen = 0;
-        if (c->n_seen < 16) c->seen_mosaic[c->n_seen++] = d_mosaic;
-        c->mosaic_dirty = false;
-    }
-    if (reuse) HIPCHK(c, hipStreamWaitEvent(c->s_pre, c->ev_fwd[sl], 0));
-    // view 0 = the letterboxed batch; in the fp16 context it is packed in fp32 first, and the view kernel writes all three views
-    const bool f16 = c->prec == PREC_F16;
-    float* src32 = f16 ? c->AB().src32 : (float*)c->S().netin;
-    rc = preproc_as(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, src32, PREC_F32, d_status, c->s_pre);
-    if (!rc) rc = augment_pack_on(c, src32, B, lb.H, lb.W, f16 ? c->S().netin : nullptr, c->AB().view[0], c->AB().view[1], c->s_pre);
-    if (rc) { c->slot = 0; return rc; }
-    HIPCHK(c, hipEventRecord(c->ev_pre[sl], c->s_pre));
-    HIPCHK(c, hipStreamWaitEvent(sf, c->ev_pre[sl], 0));
-    if (reuse) HIPCHK(c, hipStreamWaitEvent(sf, c->ev_post[sl], 0));
-    const void* vin[3] = {c->S().netin, c->AB().view[0], c->AB().view[1]};
-    float* vpred[3] = {c->S().pred, c->AB().pred[0], c->AB().pred[1]};
-    for (int k = 0; k < 3 && !rc; ++k) {
-        const int Hk = ag.v[k].Hp, Wk = ag.v[k].Wp;
-        if (small) {
-            c->split_last = false;
-            rc = forward_on(c, vin[k], B, Hk, Wk, vpred[k], sf, c->ws3, c->ws3_bytes, true);
-        } else {
-            rc = forward_split(c, vin[k], B, Hk, Wk, vpred[k], sm);
-        }
-    }
-    if (rc) { c->slot = 0; return rc; }
-    HIPCHK(c, hipEventRecord(c->ev_fwd[sl], sf));
-    HIPCHK(c, hipStreamWaitEvent(spost, c->ev_fwd[sl], 0));
-    const float* cpred[3] = {vpred[0], vpred[1], vpred[2]};
-    rc = decode_nms_aug_on(c, cpred, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, spost);
-    if (!rc) rc = cy_iou_merge(c, c->S().det, c->S().det_count, B, conf, soft, hard, d_out, d_out_count, nullptr, spost);
-    if (rc) { c->slot = 0; return rc; }
-    HIPCHK(c, hipEventRecord(c->ev_post[sl], spost));
-    if (small) c->small_batches++; else c->batches++;
-    c->slot = 0;
-    return CY_OK;
+    return pipeline_batch(c, d_mosaic, B, conf, soft, hard, d_out, d_out_count, stream,
+        [&](hipStream_t s) {
+            // view 0 = the letterboxed batch; in the fp16 context it is packed in fp32 first, and the view kernel writes all three views
+            const bool f16 = c->prec == PREC_F16;
+            float* src32 = f16 ? c->AB().src32 : (float*)c->S().netin;
+            const int rc = preproc_as(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, src32, PREC_F32, d_status, s);
+            return rc ? rc : augment_pack_on(c, src32, B, lb.H, lb.W, f16 ? c->S().netin : nullptr, c->AB().view[0], c->AB().view[1], s);
+        },
+        [&](auto&& fwd) {
+            const void* vin[3] = {c->S().netin, c->AB().view[0], c->AB().view[1]};
+            float* vpred[3] = {c->S().pred, c->AB().pred[0], c->AB().pred[1]};
+            int rc = CY_OK;
+            for (int k = 0; k < 3 && !rc; ++k) rc = fwd(vin[k], ag.v[k].Hp, ag.v[k].Wp, vpred[k]);
+            return rc;
+        },
+        [&](hipStream_t s) {
+            const float* preds[3] = {c->S().pred, c->AB().pred[0], c->AB().pred[1]};
+            return decode_nms_aug_on(c, preds, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, s);
+        });
 }
 
 }  // extern "C"

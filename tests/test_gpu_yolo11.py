@@ -186,6 +186,46 @@ def test_malformed_cyw2_plan_is_refused(tmp_path, field, delta):
         HipDetector(path, device=0, precision="fp16", max_batch=1, max_imgsz=64)
 
 
+@pytest.mark.parametrize("bad", ["plan", "cut"])
+def test_failed_reload_leaves_the_context_unloaded(tmp_path, bad):
+    """A load that fails behind the point where the old model is freed -- in the plan's slice checks, after every weight is
+    uploaded, or in the middle of the conv records -- leaves the context unloaded: every entry that needs a model refuses it, and a
+    load of the sound file on the same context gives the same forward, bit for bit."""
+    import copy
+    import ctypes as C
+    from caesar_yolo_amd import weights as W
+    from caesar_yolo_amd import lib as L
+    from caesar_yolo_amd.model import HipDetector
+    g, wd = seeded_folded("n", 3)
+    names = {0: "a", 1: "b", 2: "c"}
+    path = str(tmp_path / "good.cyw")
+    W.write_cyw2(path, g, [(cs, wd[cs.name][0], wd[cs.name][1]) for cs in g.convs], names)
+    good = open(path, "rb").read()
+    if bad == "plan":
+        g2 = copy.deepcopy(g)
+        k = [i for i, o in enumerate(g2.ops) if o["kind"] == 1 and o["out"] >= 0][3]
+        g2.ops[k]["out_coff"] += 8
+        W.write_cyw2(str(tmp_path / "bad.cyw"), g2, [(cs, wd[cs.name][0], wd[cs.name][1]) for cs in g2.convs], names)
+        image = open(str(tmp_path / "bad.cyw"), "rb").read()
+    else:
+        image = good[:len(good) // 2 // 4 * 4]              # (the plan section is a few KiB: the middle lies in the conv records)
+    det = HipDetector(path, device=0, precision="fp16", max_batch=1, max_imgsz=64)
+    rng = np.random.default_rng(13)
+    xin = netin_from_chw(torch.from_numpy(rng.uniform(0, 1, (1, 3, 64, 64)).astype(np.float32)), det.dtype)
+    want = det.forward(xin).cpu().clone()
+    torch.cuda.synchronize()
+    assert det.lib.cy_load_weights_mem(det.ctx, image, len(image)) != 0
+    assert ("malformed CYW2 plan" if bad == "plan" else "truncated weight file") in det.lib.cy_last_error(det.ctx).decode()
+    assert det.lib.cy_num_classes(det.ctx) == -1
+    assert det.lib.cy_pred_elems(det.ctx, 1, 64, 64) == 0
+    with pytest.raises(L.CyError, match="weights not loaded"):
+        det.forward(xin)
+    assert det.lib.cy_load_weights_mem(det.ctx, good, len(good)) == 0
+    got = det.forward(xin).cpu()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    det.close()
+
+
 @pytest.mark.parametrize("scale,prec", [("l", "fp16"), ("l", "fp16x3"), ("n", "fp16")])
 def test_narrow_1x1_layers_on_the_streaming_kernel_are_bit_identical(tmp_path, scale, prec, monkeypatch):
     """1x1 convolutions with <= 64 output channels inside the network (YOLO11l: the C3k branches of model.2 / model.4, 64 -> 32 and

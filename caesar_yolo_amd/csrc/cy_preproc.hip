@@ -24,6 +24,7 @@
 // accumulates the set's count and moments, and an even count selects ranks n/2-1 and n/2 together (two prefixes, two
 // histograms), so one sigma-clip iteration is 3 passes over the tile where the first version of this kernel made 9.
 #include "cy_kernels.h"
+#include "cy_select.h"                  // fkey32 / fkey32_inv: order-preserving float <-> u32
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -57,46 +58,56 @@ constexpr int NCAND = 24576;        // capacity of the median bracket (raw keys 
 
 __device__ __forceinline__ bool cond_of(double v) { return v != 0.0 && isfinite(v); }
 
-__device__ __forceinline__ double interp256(double x, const double* xp, const double* fp, float hinv = -1.0f) {
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// What a stage map reads besides its solved parameters, and how it divides by a per-tile constant and finds the HISTEQ knot and slope.
+// StageExact is the form of the statistics, plane and row-check kernels: `a / b` and a bisection over the 256 knots (heq: 256 bin
+// centres, then 256 cdf values).  The pack kernel's form is StagedMath (below, next to the tables it reads).  q0 / q1 are read where
+// the MINMAX stage uses them and not at the call: loaded ahead of the division they cost the pack kernel four registers.
+struct StageExact {
+    const double* heq; const double* pq0; const double* pq1;      // tables; the stage's p0, p1 (MINMAX: the output range)
+    __device__ __forceinline__ double q0() const { return *pq0; }
+    __device__ __forceinline__ double q1() const { return *pq1; }
+    __device__ __forceinline__ const double* knots() const { return heq; }
+    __device__ __forceinline__ double divisor(const double* sp) const { return sp[1] - sp[0]; }
+    __device__ __forceinline__ double div(double a, double b) const { return a / b; }
+    __device__ __forceinline__ int knot(double x) const {
+        int lo = 0, hi = 255;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (heq[mid] <= x) lo = mid; else hi = mid; }
+        return (heq[hi] <= x) ? hi : lo;
+    }
+    __device__ __forceinline__ double slope(int j) const { return (heq[256 + j + 1] - heq[256 + j]) / (heq[j + 1] - heq[j]); }
+};
+
+template <typename M> __device__ __forceinline__ double interp256(double x, const M& m) {
     // numpy.interp for 256 knots (compiled_base.c arr_interp): left/right clamps, exact knot hits, slope form
+    const double* xp = m.knots(); const double* fp = xp + 256;
     if (x > xp[255]) return fp[255];
     if (x < xp[0]) return fp[0];
-    int j;                                      // largest j with xp[j] <= x
-    if (hinv >= 0.0f) {
-        // the knots are bin centres, evenly spaced up to rounding: a float32 guess (hinv = 255 / (xp[255] - xp[0])) and a walk to the
-        // exact answer (zero or one step) instead of eight dependent table reads
-        j = (int)((float)(x - xp[0]) * hinv);
-        j = j < 0 ? 0 : (j > 255 ? 255 : j);
-        while (j < 255 && xp[j + 1] <= x) ++j;
-        while (j > 0 && xp[j] > x) --j;
-    } else {
-        int lo = 0, hi = 255;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (xp[mid] <= x) lo = mid; else hi = mid; }
-        j = (xp[hi] <= x) ? hi : lo;
-    }
+    const int j = m.knot(x);                    // largest j with xp[j] <= x
     if (j == 255) return fp[255];
     if (xp[j] == x) return fp[j];
-    const double slope = (fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j]);
-    return slope * (x - xp[j]) + fp[j];
+    return m.slope(j) * (x - xp[j]) + fp[j];
 }
 
-// stage k applied to its input value v, with solved parameters sp[4]
-__device__ __forceinline__ double apply_stage(int op, double q0, double q1, const double* sp, const double* heq, double v, float hinv = -1.0f) {
+// stage `op` (OP >= 0: known at compile time) applied to its input value v, with solved parameters sp[4]
+template <int OP = -1, typename M>
+__device__ __forceinline__ double stage_map(int op, const double* sp, const M& m, double v) {
     const bool c = cond_of(v);
     double o = v;
-    switch (op) {
+    switch (OP >= 0 ? OP : op) {
         case OP_BKG: o = v - sp[0]; break;
         case OP_SHIFT: o = v - sp[0]; if (o < 0.0) o = 0.0; break;
         case OP_CLIP: if (o < sp[0]) o = sp[0]; if (o > sp[1]) o = sp[1]; break;
         case OP_ZSCALE: {
             o = v - sp[0];
-            const double rng = sp[1] - sp[0];
-            if (rng != 0.0) o = o / rng;
+            const double rng = m.divisor(sp);
+            if (rng != 0.0) o = m.div(o, rng);
             o = fmin(fmax(o, 0.0), 1.0);
             break;
         }
-        case OP_HISTEQ: o = interp256(v, heq, heq + 256, hinv); break;
-        case OP_MINMAX: o = (v - sp[0]) / (sp[1] - sp[0]) * (q1 - q0) + q0; break;
+        case OP_HISTEQ: o = interp256(v, m); break;
+        case OP_MINMAX: o = m.div(v - sp[0], m.divisor(sp)) * (m.q1() - m.q0()) + m.q0(); break;
         default: break;
     }
     return c ? o : 0.0;
@@ -119,10 +130,36 @@ struct Smem {
     unsigned cand[NCAND];
 };
 
+// the first `upto` stages of a channel program applied to a raw pixel: the program in LDS (statistics kernel) ...
 __device__ __forceinline__ double chain_value(const Smem& s, int upto, double raw) {
     double v = raw;
-    for (int k = 0; k < upto; ++k) v = apply_stage(s.op[k], s.q0[k], s.q1[k], s.par + k * 4, s.heq, v);
+    for (int k = 0; k < upto; ++k) v = stage_map(s.op[k], s.par + k * 4, StageExact{s.heq, s.q0 + k, s.q1 + k}, v);
     return v;
+}
+// ... or in the argument block (plane and row-check kernels)
+__device__ __forceinline__ double chain_value(const PreProgram& pg, int upto, const double* params, const double* heq, double raw) {
+    double v = raw;
+    for (int k = 0; k < upto; ++k) v = stage_map(pg.st[k].op, params + k * 4, StageExact{heq, &pg.st[k].p0, &pg.st[k].p1}, v);
+    return v;
+}
+
+// Is the output of stage `op` with solved parameters (a, b) non-zero for the non-zero finite input v?  The stages that end in a
+// subtraction (BKG, SHIFT) or a division (ZSCALE) and HISTEQ have a closed form: -> true, the answer in nz.  false: CLIP, MINMAX: the
+// stage is evaluated.  (An int result with -1 for "evaluate" cost the statistics kernel 56 bytes of scratch per lane.)
+__device__ __forceinline__ bool last_stage_nonzero(int op, double a, double b, double v, bool& nz) {
+    switch (op) {
+        case OP_BKG: nz = v != a; return true;                     // fl(v - m) == 0 iff v == m
+        case OP_SHIFT: nz = v > a; return true;                    // v - m, negatives clamped to 0
+        case OP_ZSCALE: {                                          // fmin(fmax((v - vmin) / rng, 0), 1) (no division when rng == 0)
+            const double d = v - a, rng = b - a;
+            if (!(d > 0.0) || rng < 0.0) nz = false;
+            else if (rng != 0.0 && d < rng * 1e-290) nz = d / rng > 0.0;     // (a quotient that could underflow: decided by the division itself)
+            else nz = true;
+            return true;
+        }
+        case OP_HISTEQ: nz = true; return true;                    // interpolated cdf of a non-zero finite value: >= cdf[0] = (count of the first bin >= 1) / n > 0
+        default: return false;
+    }
 }
 
 // Is the chain's output for this raw pixel non-zero (= does the pixel count for a MINMAX stage behind the chain)?  Every stage but
@@ -134,21 +171,9 @@ __device__ __forceinline__ bool chain_nonzero(const Smem& s, int upto, float rf)
     double v = (double)rf;
     for (int k = 0; k < upto; ++k) {
         const double* sp = s.par + k * 4;
-        if (k + 1 == upto) {
-            switch (s.op[k]) {
-                case OP_BKG: return v != sp[0];                    // fl(v - m) == 0 iff v == m
-                case OP_SHIFT: return v > sp[0];                   // v - m, negatives clamped to 0
-                case OP_ZSCALE: {                                  // fmin(fmax((v - vmin) / rng, 0), 1) (no division when rng == 0)
-                    const double d = v - sp[0], rng = sp[1] - sp[0];
-                    if (!(d > 0.0) || rng < 0.0) return false;
-                    if (rng != 0.0 && d < rng * 1e-290) return d / rng > 0.0;     // (a quotient that could underflow: decided by the division itself)
-                    return true;
-                }
-                case OP_HISTEQ: return true;                       // interpolated cdf of a non-zero finite value: >= cdf[0] = (count of the first bin >= 1) / n > 0
-                default: break;                                    // CLIP, MINMAX: evaluated
-            }
-        }
-        v = apply_stage(s.op[k], s.q0[k], s.q1[k], sp, s.heq, v);
+        bool nz;                                                   // (set when the call returns true; initialised here it costs 64 bytes of scratch per lane)
+        if (k + 1 == upto && last_stage_nonzero(s.op[k], sp[0], sp[1], v, nz)) return nz;
+        v = stage_map(s.op[k], sp, StageExact{s.heq, s.q0 + k, s.q1 + k}, v);
         if (!cond_of(v)) return false;
     }
     return true;
@@ -181,18 +206,12 @@ __device__ __forceinline__ bool nz_test(const NzChain& c, float rf) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k >= c.n) break;
-        const bool last = k + 1 == c.n;
-        switch (c.op[k]) {
-            case OP_BKG: if (last) return v != c.a[k]; v = v - c.a[k]; break;
-            case OP_SHIFT: if (last) return v > c.a[k]; v = v - c.a[k]; if (v < 0.0) return false; break;
+        bool nz;
+        if (k + 1 == c.n && last_stage_nonzero(c.op[k], c.a[k], c.b[k], v, nz)) return nz;
+        switch (c.op[k]) {                                         // (ZSCALE and HISTEQ are last stages by construction)
+            case OP_BKG: v = v - c.a[k]; break;
+            case OP_SHIFT: v = v - c.a[k]; if (v < 0.0) return false; break;
             case OP_CLIP: if (v < c.a[k]) v = c.a[k]; if (v > c.b[k]) v = c.b[k]; break;
-            case OP_HISTEQ: return true;                           // (last stage by construction; see chain_nonzero)
-            case OP_ZSCALE: {                                      // (last stage by construction)
-                const double d = v - c.a[k], rng = c.b[k] - c.a[k];
-                if (!(d > 0.0) || rng < 0.0) return false;
-                if (rng != 0.0 && d < rng * 1e-290) return d / rng > 0.0;
-                return true;
-            }
             default: break;
         }
         if (!cond_of(v)) return false;
@@ -252,14 +271,6 @@ __device__ __forceinline__ void block_sum3(Smem& s, double& a, double& b, double
     __syncthreads();
 }
 
-__device__ __forceinline__ unsigned fkey(float f) {                     // order-preserving float -> u32
-    const unsigned b = __float_as_uint(f);
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(unsigned k) {
-    return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 struct TileView {
     const float* base; int MW, tw, th, npix;
     __amdgpu_buffer_rsrc_t rs;            // the tile's rows as a raw buffer (range-checked 16-byte loads)
@@ -292,7 +303,6 @@ constexpr int PXG = 2;
 constexpr int PXGP = CY_PXGP;       // groups per thread and step of the plain raw moments pass
 template <bool RAW, typename F>
 __device__ __forceinline__ void for_pixels(const Smem& s, const TileView& tv, int upto, const ClipSet* box, F&& f) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int GR = (tv.tw + 3) >> 2, NG = tv.th * GR;            // groups per row, groups in the tile
     // (y, gx) of the thread's next group, advanced by NT groups per load: one integer division per pass, not per group
     int y = (int)threadIdx.x / GR, gx = (int)threadIdx.x - y * GR;
@@ -403,7 +413,7 @@ __device__ __forceinline__ double set_median(Smem& s, const TileView& tv, int up
             __syncthreads();
             for_pixels<RAW>(s, tv, upto, &cs, [&](float rf, double v, bool inb, bool act) {
                 act = act && in_set<RAW>(cs, rf, v, inb);
-                const unsigned key = fkey(rf);
+                const unsigned key = fkey32(rf);
                 const unsigned bin = (key >> shift) & nbm;
                 hist_add(s.histA, bin, act && (key & pmask) == pA);
                 if (two) hist_add(s.histB, bin, act && (key & pmask) == pB);
@@ -416,10 +426,46 @@ __device__ __forceinline__ double set_median(Smem& s, const TileView& tv, int up
         kA -= befA; kB -= befB;
         pmask |= nbm << shift;
     }
-    const double a = chain_value(s, upto, (double)fkey_inv(pA));
+    const double a = chain_value(s, upto, (double)fkey32_inv(pA));
     if (pA == pB) return a;
-    const double b = chain_value(s, upto, (double)fkey_inv(pB));
+    const double b = chain_value(s, upto, (double)fkey32_inv(pB));
     return 0.5 * (a + b);
+}
+
+// ranks kA <= kB (0-based) among the nc raw keys in s.cand: three radix levels over LDS
+__device__ __forceinline__ void select_cand(Smem& s, unsigned nc, unsigned long long kA, unsigned long long kB, unsigned* keyA, unsigned* keyB) {
+    unsigned pA = 0u, pB = 0u, pmask = 0u;
+#pragma unroll 1
+    for (int lvl = 0; lvl < 3; ++lvl) {
+        const int shift = lvl == 0 ? 21 : (lvl == 1 ? 10 : 0), nbits = lvl == 2 ? 10 : 11;
+        const unsigned nbm = (1u << nbits) - 1u;
+        const bool two = pA != pB;
+        __syncthreads();
+        clear_hists(s, two);
+        __syncthreads();
+        for (unsigned i0 = 0; i0 < nc; i0 += NT) {               // whole waves stay in the loop: hist_add ballots
+            const unsigned i = i0 + threadIdx.x;
+            const bool act = i < nc;
+            const unsigned key = act ? s.cand[i] : 0u;
+            const unsigned bin = (key >> shift) & nbm;
+            // the leading level sees one or two bins (a bracket's keys share sign and exponent): one aggregation round; below it the
+            // bins are the keys' middle and low bits, evenly spread: plain atomics (three rounds everywhere: clip stage +9 %, round 4)
+            if (lvl == 0) {
+                hist_add<1>(s.histA, bin, act && (key & pmask) == pA);
+                if (two) hist_add<1>(s.histB, bin, act && (key & pmask) == pB);
+            } else {
+                hist_add<0>(s.histA, bin, act && (key & pmask) == pA);
+                if (two) hist_add<0>(s.histB, bin, act && (key & pmask) == pB);
+            }
+        }
+        __syncthreads();
+        unsigned binA, binB; unsigned long long befA, befB;
+        locate2(s, s.histA, two ? s.histB : s.histA, 1 << nbits, kA, kB, &binA, &befA, &binB, &befB);
+        pA |= binA << shift; pB |= binB << shift;
+        kA -= befA; kB -= befB;
+        pmask |= nbm << shift;
+    }
+    *keyA = pA; *keyB = pB;
 }
 
 struct ClipStats { double lo, hi, mean, median, std; unsigned long long n; int hits, misses; };   // hits / misses of the median bracket
@@ -441,7 +487,6 @@ struct Bracket { double vl, vh; bool on; float lf, hf; bool collect; };   // col
 template <bool RAW, int MODE>
 __device__ __forceinline__ void moments_loop(Smem& s, const TileView& tv, int upto, const ClipSet& cs, double K, const Bracket& br,
                                              double& s1, double& s2, unsigned& ucnt, unsigned& below, unsigned& ucand) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int GR = (tv.tw + 3) >> 2, NG = tv.th * GR;
     int y = (int)threadIdx.x / GR, gx = (int)threadIdx.x - y * GR;
     const int dy = NT / GR, dx = NT - dy * GR;
@@ -490,7 +535,7 @@ __device__ __forceinline__ void moments_loop(Smem& s, const TileView& tv, int up
                 }
                 if (MODE == 1) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) hist_add(s.histA, fkey(r[u][e]) >> 21, act[e]);
+                    for (int e = 0; e < 4; ++e) hist_add(s.histA, fkey32(r[u][e]) >> 21, act[e]);
                 }
                 if (MODE >= 2) {
 #pragma unroll
@@ -522,7 +567,7 @@ __device__ __forceinline__ void moments_loop(Smem& s, const TileView& tv, int up
                     base = (unsigned)__shfl((int)base, 0);
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if ((inmask >> e) & 1u) { const unsigned pos = base + my[e]; if (pos < (unsigned)NCAND) s.cand[pos] = fkey(r[u][e]); }
+                        if ((inmask >> e) & 1u) { const unsigned pos = base + my[e]; if (pos < (unsigned)NCAND) s.cand[pos] = fkey32(r[u][e]); }
                 }
             }
         }
@@ -540,7 +585,6 @@ __device__ __forceinline__ void moments_loop(Smem& s, const TileView& tv, int up
 template <int MODE, int G>
 __device__ __forceinline__ void moments_plain(Smem& s, const TileView& tv, const ClipSet& cs, double K, const Bracket& br,
                                               double& s1, double& s2, unsigned& ucnt, unsigned& below, unsigned& ucand) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int GR = tv.tw >> 2, NG = tv.th * GR;
     const int lane = (int)threadIdx.x & 63;
     const float Lf = cs.Lf, Uf = cs.Uf, blf = br.lf, bhf = br.hf;
@@ -600,7 +644,7 @@ __device__ __forceinline__ void moments_plain(Smem& s, const TileView& tv, const
                     if (base + tot <= (unsigned)NCAND) {                   // (an overflowing bracket is a miss anyway: s.ncand says so)
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            if (in[e]) s.cand[base + my[e]] = fkey(r[u][e]);
+                            if (in[e]) s.cand[base + my[e]] = fkey32(r[u][e]);
                     }
                 }
             }
@@ -657,42 +701,6 @@ __device__ __forceinline__ void set_moments(Smem& s, const TileView& tv, int upt
         if (var < 0.0) var = 0.0;
         *mean_out = K + m1; *std_out = sqrt(var);
     } else { *mean_out = NAN; *std_out = NAN; }
-}
-
-// ranks kA <= kB (0-based) among the nc raw keys in s.cand: three radix levels over LDS
-__device__ __forceinline__ void select_cand(Smem& s, unsigned nc, unsigned long long kA, unsigned long long kB, unsigned* keyA, unsigned* keyB) {
-    unsigned pA = 0u, pB = 0u, pmask = 0u;
-#pragma unroll 1
-    for (int lvl = 0; lvl < 3; ++lvl) {
-        const int shift = lvl == 0 ? 21 : (lvl == 1 ? 10 : 0), nbits = lvl == 2 ? 10 : 11;
-        const unsigned nbm = (1u << nbits) - 1u;
-        const bool two = pA != pB;
-        __syncthreads();
-        clear_hists(s, two);
-        __syncthreads();
-        for (unsigned i0 = 0; i0 < nc; i0 += NT) {               // whole waves stay in the loop: hist_add ballots
-            const unsigned i = i0 + threadIdx.x;
-            const bool act = i < nc;
-            const unsigned key = act ? s.cand[i] : 0u;
-            const unsigned bin = (key >> shift) & nbm;
-            // the leading level sees one or two bins (a bracket's keys share sign and exponent): one aggregation round; below it the
-            // bins are the keys' middle and low bits, evenly spread: plain atomics (three rounds everywhere: clip stage +9 %, round 4)
-            if (lvl == 0) {
-                hist_add<1>(s.histA, bin, act && (key & pmask) == pA);
-                if (two) hist_add<1>(s.histB, bin, act && (key & pmask) == pB);
-            } else {
-                hist_add<0>(s.histA, bin, act && (key & pmask) == pA);
-                if (two) hist_add<0>(s.histB, bin, act && (key & pmask) == pB);
-            }
-        }
-        __syncthreads();
-        unsigned binA, binB; unsigned long long befA, befB;
-        locate2(s, s.histA, two ? s.histB : s.histA, 1 << nbits, kA, kB, &binA, &befA, &binB, &befB);
-        pA |= binA << shift; pB |= binB << shift;
-        kA -= befA; kB -= befB;
-        pmask |= nbm << shift;
-    }
-    *keyA = pA; *keyB = pB;
 }
 
 // astropy SigmaClip._sigmaclip_noaxis (maxiters 5, median centre, std spread) + statistics of the survivors
@@ -757,7 +765,7 @@ __device__ __forceinline__ ClipStats sigma_clip_run(Smem& s, const TileView& tv,
                     if (lane == 0) base = atomicAdd(&s.ncand, (unsigned)__popcll(m));
                     base = (unsigned)__shfl((int)base, 0);
                     const unsigned pos = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                    if (a && pos < (unsigned)NCAND) s.cand[pos] = fkey(rf);
+                    if (a && pos < (unsigned)NCAND) s.cand[pos] = fkey32(rf);
                 }
             }
         __syncthreads();
@@ -769,7 +777,7 @@ __device__ __forceinline__ ClipStats sigma_clip_run(Smem& s, const TileView& tv,
             if (w < 0.015) w = 0.015;
             const unsigned long long ra = (unsigned long long)((0.5 - w) * (double)ns), rb = (unsigned long long)((0.5 + w) * (double)ns);
             select_cand(s, ns, ra, rb < ns ? rb : ns - 1, &keyA, &keyB);
-            br.lf = fkey_inv(keyA); br.hf = fkey_inv(keyB);
+            br.lf = fkey32_inv(keyA); br.hf = fkey32_inv(keyB);
             br.vl = (double)br.lf; br.vh = (double)br.hf;
             br.on = br.hf > br.lf; br.collect = true;
         }
@@ -821,8 +829,8 @@ __device__ __forceinline__ ClipStats sigma_clip_run(Smem& s, const TileView& tv,
                 ts = pre_now();
                 select_cand(s, ncand, kA - below, kB - below, &keyA, &keyB);
                 pre_acc(2, ts);
-                const double a = chain_value(s, upto, (double)fkey_inv(keyA));
-                med = keyA == keyB ? a : 0.5 * (a + chain_value(s, upto, (double)fkey_inv(keyB)));
+                const double a = chain_value(s, upto, (double)fkey32_inv(keyA));
+                med = keyA == keyB ? a : 0.5 * (a + chain_value(s, upto, (double)fkey32_inv(keyB)));
             } else {
                 half_ranks = HALF_RANKS;
                 if (!radix_trip) {            // the bracket missed (or overflowed): level-0 histogram first, then the two radix passes
@@ -962,7 +970,7 @@ __device__ __forceinline__ bool raw_threshold(const Smem& s, int upto, float* tf
             else if (vmin >= hi) return false;                     // none is: leave it to the general pass
             else T = vmin;
         } else if (op == OP_HISTEQ && last && k == 0) {
-            // interpolated cdf of a non-zero finite value: never zero (see chain_nonzero)
+            // interpolated cdf of a non-zero finite value: never zero (see last_stage_nonzero)
         } else return false;
     }
     *tf = T == -INFINITY ? -INFINITY : f_not_above(T);
@@ -972,7 +980,6 @@ __device__ __forceinline__ bool raw_threshold(const Smem& s, int upto, float* tf
 // ALL = true: every pixel of the tile counts, zeros included (the range of a HISTEQ stage); a NaN fails both compares
 template <bool ALL = false>
 __device__ __forceinline__ void minmax_plain(const TileView& tv, float tf, float& rmn, float& rmx) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int GR = tv.tw >> 2, NG = tv.th * GR;
     int gx, g = (int)threadIdx.x;
     unsigned off;
@@ -1019,7 +1026,6 @@ __device__ __forceinline__ void minmax_plain(const TileView& tv, float tf, float
 // step) and the aggregated increment -- instead of a float64 division, two edge evaluations and their compares.
 template <int ROUNDS>
 __device__ __forceinline__ void hist_plain(const TileView& tv, const float* thr, float firstf, float invf, unsigned* hist) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     const int GR = tv.tw >> 2, NG = tv.th * GR;
     int gx, g = (int)threadIdx.x;
     unsigned off;
@@ -1095,14 +1101,14 @@ __device__ __forceinline__ void histeq_run(Smem& s, const TileView& tv, int upto
         const int i = threadIdx.x;
         if (i >= 1 && i < 256) {
             // smallest key in [key(min), key(max)] whose bin is >= i; none: +inf (no pixel exceeds the maximum)
-            unsigned lo = fkey((float)mn), hi = fkey((float)mx);
+            unsigned lo = fkey32((float)mn), hi = fkey32((float)mx);
             float t = INFINITY;
-            if (bin_of((double)fkey_inv(hi)) >= i) {
+            if (bin_of((double)fkey32_inv(hi)) >= i) {
                 while (lo < hi) {
                     const unsigned mid = lo + ((hi - lo) >> 1);
-                    if (bin_of((double)fkey_inv(mid)) >= i) hi = mid; else lo = mid + 1;
+                    if (bin_of((double)fkey32_inv(mid)) >= i) hi = mid; else lo = mid + 1;
                 }
-                t = fkey_inv(hi);
+                t = fkey32_inv(hi);
             }
             thr[i] = t;
         }
@@ -1135,6 +1141,11 @@ __device__ __forceinline__ void histeq_run(Smem& s, const TileView& tv, int upto
 // The argument block is read through scalar fields and two copies into LDS only (the channel's program, the tile origin):
 // handing `a.prog[p]` to the routines above by reference made the compiler keep a private copy of the whole 3.3 KB block in
 // scratch memory (ScratchSize 3352 B per lane, ~570 MB of scratch writes per launch) and read every stage from there per pixel.
+// Dynamically indexed members of the argument block (prog[p].st[k], txy[2b]) are read straight from the kernel-argument segment.
+typedef const __attribute__((address_space(4))) char* kptr;
+__device__ __forceinline__ kptr kernarg() { return (kptr)__builtin_amdgcn_kernarg_segment_ptr(); }
+__device__ __forceinline__ int kint(kptr q) { return *(const __attribute__((address_space(4))) int*)q; }
+__device__ __forceinline__ double kdbl(kptr q) { return *(const __attribute__((address_space(4))) double*)q; }
 __global__ __launch_bounds__(NT) void pre_stats_kernel(const PreArgs a) {
     __shared__ Smem s;
     // job-major: the long sigma-clip jobs first, the short HISTEQ one last.  A job is one channel program -- or, when the host found
@@ -1143,11 +1154,7 @@ __global__ __launch_bounds__(NT) void pre_stats_kernel(const PreArgs a) {
     // batch's long jobs fit the CUs in one round instead of two.
     const int b = blockIdx.x % a.B, job = blockIdx.x / a.B;
     const int pfirst = a.fuse01 ? (job == 0 ? 0 : job + 1) : job, pcount = a.fuse01 && job == 0 ? 2 : 1;
-    // dynamically indexed members (prog[p].st[k], txy[2b]) are read straight from the kernel-argument segment
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
-    auto kint = [](kptr q) { return *(const __attribute__((address_space(4))) int*)q; };
-    auto kdbl = [](kptr q) { return *(const __attribute__((address_space(4))) double*)q; };
+    const kptr ka = kernarg();
     if (threadIdx.x == 0) s.variant = a.variant;
     const int tx0 = kint(ka + offsetof(PreArgs, txy) + (size_t)(2 * b) * 4), ty0 = kint(ka + offsetof(PreArgs, txy) + (size_t)(2 * b + 1) * 4);
     const float* tbase = a.mosaic + (size_t)ty0 * a.MW + tx0;
@@ -1243,12 +1250,6 @@ __global__ __launch_bounds__(NT) void pre_stats_kernel(const PreArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------- apply + letterbox + pack
-__device__ __forceinline__ double chain_value(const PreProgram& pg, int upto, const double* params, const double* heq, double raw) {
-    double v = raw;
-    for (int k = 0; k < upto; ++k) v = apply_stage(pg.st[k].op, pg.st[k].p0, pg.st[k].p1, params + k * 4, heq, v);
-    return v;
-}
-
 __device__ __forceinline__ void tile_channels(const PreArgs& a, int b, double raw, double out[3]) {
     if (a.nprog == 0) { out[0] = out[1] = out[2] = raw; return; }
     for (int c = 0; c < 3; ++c) {
@@ -1310,45 +1311,30 @@ struct PackChain {
     double heq[3][512];
     double hslope[3][256];                                                     // HISTEQ: slope between knots j and j + 1 (divided once per tile)
 };
-// apply_stage with the divisions of the per-tile constants taken from PackChain: same values, bit for bit
+// The stage map's arithmetic for stage k of program p with the per-tile constants taken from PackChain -- same values, bit for bit:
+// the quotients through fast_div, the HISTEQ knot by a guess and a walk, its slope from the staged table.
+struct StagedMath {
+    const PackChain& pc; int p, k;
+    __device__ __forceinline__ const double* knots() const { return pc.heq[p]; }
+    __device__ __forceinline__ double q0() const { return pc.q0[p][k]; }
+    __device__ __forceinline__ double q1() const { return pc.q1[p][k]; }
+    __device__ __forceinline__ double divisor(const double*) const { return pc.db[p][k]; }
+    __device__ __forceinline__ double div(double a, double b) const { return fast_div(a, b, -b, pc.dr[p][k], pc.dok[p][k]); }
+    __device__ __forceinline__ int knot(double x) const {
+        // the knots are bin centres, evenly spaced up to rounding: a float32 guess (hinv = 255 / (xp[255] - xp[0])) and a walk to the
+        // exact answer (zero or one step) instead of eight dependent table reads
+        const double* heq = pc.heq[p];
+        int j = (int)((float)(x - heq[0]) * pc.hinv[p]);
+        j = j < 0 ? 0 : (j > 255 ? 255 : j);
+        while (j < 255 && heq[j + 1] <= x) ++j;
+        while (j > 0 && heq[j] > x) --j;
+        return j;
+    }
+    __device__ __forceinline__ double slope(int j) const { return pc.hslope[p][j]; }
+};
 template <int OP = -1>
 __device__ __forceinline__ double apply_stage_pack(const PackChain& pc, int p, int k, double v) {
-    const int op = OP >= 0 ? OP : pc.op[p][k];
-    const double* sp = pc.par[p] + k * 4;
-    const bool c = cond_of(v);
-    double o = v;
-    switch (op) {
-        case OP_BKG: o = v - sp[0]; break;
-        case OP_SHIFT: o = v - sp[0]; if (o < 0.0) o = 0.0; break;
-        case OP_CLIP: if (o < sp[0]) o = sp[0]; if (o > sp[1]) o = sp[1]; break;
-        case OP_ZSCALE: {
-            o = v - sp[0];
-            const double rng = pc.db[p][k];
-            if (rng != 0.0) o = fast_div(o, rng, -rng, pc.dr[p][k], pc.dok[p][k]);
-            o = fmin(fmax(o, 0.0), 1.0);
-            break;
-        }
-        case OP_HISTEQ: {
-            const double* xp = pc.heq[p]; const double* fp = pc.heq[p] + 256;
-            if (v > xp[255]) { o = fp[255]; break; }
-            if (v < xp[0]) { o = fp[0]; break; }
-            int j = (int)((float)(v - xp[0]) * pc.hinv[p]);
-            j = j < 0 ? 0 : (j > 255 ? 255 : j);
-            while (j < 255 && xp[j + 1] <= v) ++j;
-            while (j > 0 && xp[j] > v) --j;
-            if (j == 255) { o = fp[255]; break; }
-            if (xp[j] == v) { o = fp[j]; break; }
-            o = pc.hslope[p][j] * (v - xp[j]) + fp[j];
-            break;
-        }
-        case OP_MINMAX: {
-            const double d = pc.db[p][k];
-            o = fast_div(v - sp[0], d, -d, pc.dr[p][k], pc.dok[p][k]) * (pc.q1[p][k] - pc.q0[p][k]) + pc.q0[p][k];
-            break;
-        }
-        default: break;
-    }
-    return c ? o : 0.0;
+    return stage_map<OP>(pc.op[p][k], pc.par[p] + k * 4, StagedMath{pc, p, k}, v);
 }
 
 // SIG: the shape of the channel programs, when it is one the host recognises -- 1: one program [ZSCALE, MINMAX] (the reference's default
@@ -1359,11 +1345,7 @@ __global__ __launch_bounds__(256) void pre_pack_kernel(const PreArgs a) {
     typedef T vec4 __attribute__((ext_vector_type(4)));
     __shared__ PackChain pc;
     const int b = blockIdx.y, np = a.nprog;
-    // (dynamically indexed members of the argument block are read through the kernel-argument segment: see pre_stats_kernel)
-    typedef const __attribute__((address_space(4))) char* kptr;
-    const kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
-    auto kint = [](kptr q) { return *(const __attribute__((address_space(4))) int*)q; };
-    auto kdbl = [](kptr q) { return *(const __attribute__((address_space(4))) double*)q; };
+    const kptr ka = kernarg();                      // (see pre_stats_kernel)
     for (int t = threadIdx.x; t < np * MAX_STAGES; t += 256) {
         const int p = t / MAX_STAGES, k = t - p * MAX_STAGES;
         const kptr kprog = ka + offsetof(PreArgs, prog) + (size_t)p * sizeof(PreProgram);
@@ -1524,21 +1506,35 @@ static int pre_fuse01(const PreArgs& a) {
     return bx == by && fx == fy;
 }
 
-hipError_t launch_preproc(const PreArgs& a0, hipStream_t s) {
-    PreArgs a = a0; a.variant = pre_variant(); a.fuse01 = pre_fuse01(a);
+// statistics + rejection checks; a.variant and a.fuse01 are set here
+static hipError_t launch_stats_and_checks(PreArgs& a, hipStream_t s) {
+    a.variant = pre_variant(); a.fuse01 = pre_fuse01(a);
     hipError_t e = hipMemsetAsync(a.status, 0, a.B * sizeof(int), s);
     if (e != hipSuccess) return e;
     if (a.nprog > 0) hipLaunchKernelGGL(pre_stats_kernel, dim3(a.B * (a.nprog - a.fuse01)), dim3(NT), 0, s, a);
     hipLaunchKernelGGL(pre_rowcheck_kernel, dim3(a.B), dim3(256), 0, s, a);
+    return hipSuccess;
+}
+static void launch_planes(const PreArgs& a, hipStream_t s) {
+    int gs = (a.th * a.tw + 255) / 256; if (gs > 1024) gs = 1024;
+    hipLaunchKernelGGL(pre_plane_kernel, dim3(gs, a.B), dim3(256), 0, s, a);
+}
+static void launch_resize_pack(const PreArgs& a, hipStream_t s) {
     const int npx = a.H * a.W;
     int gx = (npx + 255) / 256; if (gx > 1024) gx = 1024;
+    if (a.out_prec == PREC_F16) hipLaunchKernelGGL(pre_resize_pack_kernel<_Float16>, dim3(gx, a.B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(pre_resize_pack_kernel<float>, dim3(gx, a.B), dim3(256), 0, s, a);
+}
+
+hipError_t launch_preproc(const PreArgs& a0, hipStream_t s) {
+    PreArgs a = a0;
+    const hipError_t e = launch_stats_and_checks(a, s);
+    if (e != hipSuccess) return e;
     if (a.scratch) {
-        int gs = (a.th * a.tw + 255) / 256; if (gs > 1024) gs = 1024;
-        hipLaunchKernelGGL(pre_plane_kernel, dim3(gs, a.B), dim3(256), 0, s, a);
-        if (a.out_prec == PREC_F16) hipLaunchKernelGGL(pre_resize_pack_kernel<_Float16>, dim3(gx, a.B), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(pre_resize_pack_kernel<float>, dim3(gx, a.B), dim3(256), 0, s, a);
+        launch_planes(a, s);
+        launch_resize_pack(a, s);
     } else {
-        int gp = (npx + 4095) / 4096; if (gp > 1024) gp = 1024;      // 16 pixels per thread: the chain is staged in LDS once per workgroup
+        int gp = (a.H * a.W + 4095) / 4096; if (gp > 1024) gp = 1024;      // 16 pixels per thread: the chain is staged in LDS once per workgroup
         const int sig = (a.variant & 8192) ? 0 : pack_signature(a);
         if (a.out_prec == PREC_F16) {
             if (sig == 1) hipLaunchKernelGGL((pre_pack_kernel<_Float16, 1>), dim3(gp, a.B), dim3(256), 0, s, a);
@@ -1554,21 +1550,15 @@ hipError_t launch_preproc(const PreArgs& a0, hipStream_t s) {
 // statistics + rejection checks + the preprocessed image itself as float64 planes [B][3][th*tw] in a.scratch (what
 // DataPreprocessor returns to Analyzer.predict, caesar_yolo/evaluation.py:157-161): parity witness and the plotting input
 hipError_t launch_preproc_planes(const PreArgs& a0, hipStream_t s) {
-    PreArgs a = a0; a.variant = pre_variant(); a.fuse01 = pre_fuse01(a);
-    hipError_t e = hipMemsetAsync(a.status, 0, a.B * sizeof(int), s);
+    PreArgs a = a0;
+    const hipError_t e = launch_stats_and_checks(a, s);
     if (e != hipSuccess) return e;
-    if (a.nprog > 0) hipLaunchKernelGGL(pre_stats_kernel, dim3(a.B * (a.nprog - a.fuse01)), dim3(NT), 0, s, a);
-    hipLaunchKernelGGL(pre_rowcheck_kernel, dim3(a.B), dim3(256), 0, s, a);
-    int gs = (a.th * a.tw + 255) / 256; if (gs > 1024) gs = 1024;
-    hipLaunchKernelGGL(pre_plane_kernel, dim3(gs, a.B), dim3(256), 0, s, a);
+    launch_planes(a, s);
     return hipGetLastError();
 }
 
 hipError_t launch_letterbox_pack(const PreArgs& a, hipStream_t s) {
-    const int npx = a.H * a.W;
-    int gx = (npx + 255) / 256; if (gx > 1024) gx = 1024;
-    if (a.out_prec == PREC_F16) hipLaunchKernelGGL(pre_resize_pack_kernel<_Float16>, dim3(gx, a.B), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(pre_resize_pack_kernel<float>, dim3(gx, a.B), dim3(256), 0, s, a);
+    launch_resize_pack(a, s);
     return hipGetLastError();
 }
 

@@ -291,13 +291,16 @@ def test_lean_passes_agree_with_the_general_ones_other_pipelines(pname, monkeypa
         np.testing.assert_allclose(det.preproc_params(len(xy)), par0, rtol=1e-12, atol=0, err_msg="%s parameters, variant %d" % (pname, variant))
 
 
-@pytest.mark.parametrize("size", [512, 640, 132])
+@pytest.mark.parametrize("size", [512, 640, 132, 128])
 def test_lean_passes_agree_with_the_general_ones(size, monkeypatch):
     """Round 4: the statistics passes over raw whole-group tiles have lean forms (moments_plain, minmax_plain, hist_plain, the first
     sigma-clip trip about the sample bracket's midpoint, the narrower median bracket of later clips, and, opt-in, the two sigma-clip programs of chan3 in one workgroup with a shared initial set = bit 4096).
     CY_PRE_VARIANT switches them off (on)
     one bit at a time (read per launch); the preprocessed float64 image must not care: the HISTEQ channel is bit-identical (same bins,
-    same tables), the sigma-clip channels agree to 1e-12 (sums in another order, fma)."""
+    same tables), the sigma-clip channels agree to 1e-12 (sums in another order, fma).
+    Sizes: 132 ends the guarded loops on a ragged step; 128 is the smallest tile that takes hist_plain (4096 groups = exactly one step
+    of its unguarded loop, the second register set requested with no request after it), and its row sample yields exactly the 4096
+    keys at which the sample bracket switches on."""
     from caesar_yolo_amd import synth
     det = detector("fp32", max_imgsz=640)
     mos = synth.make_mosaic(2048, seed=20260105)

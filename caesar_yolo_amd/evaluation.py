@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import measure
 from .inference import objs_from_detections
 from .preprocessing import no_preprocessing
 
@@ -28,15 +29,8 @@ class Analyzer(object):
         self.device = config['devices'][0]
         self.iou_thr, self.score_thr = config['iou_thr'], config['score_thr']
         self.augment = bool(config.get('augment', False))         # NEW: test-time augmentation of the model call
-        # NEW: --measure_sources (measure.py); beam_area / wcs / wcs_origin are set by the caller that read the header (SFinder.run)
-        self.blends = bool(config.get('fit_blends', False))             # NEW: --fit_blends, touching components fitted jointly (implies the fits)
-        self.residual = bool(config.get('residual_map', False)) or bool(config.get('save_residual_maps', False))    # NEW: --residual_map, model and residual maps (implies the fits)
-        self.fit = bool(config.get('fit_components', False)) or self.blends or self.residual            # NEW: --fit_components, one Gaussian per component (implies the components)
-        self.deblend = bool(config.get('deblend_islands', False)) or self.fit       # NEW: --deblend_islands, the components (implies the islands)
-        self.islands = bool(config.get('measure_islands', False)) or self.deblend       # NEW: --measure_islands, the second step (implies the first)
-        self.bkg_map = bool(config.get('bkg_map', False)) or bool(config.get('save_bkg_maps', False))      # NEW: --bkg_map, between the two
-        self.measure = bool(config.get('measure_sources', False)) or self.islands or self.bkg_map
-        self.measure_ring = int(config.get('measure_ring', 8))
+        # NEW: --measure_sources and the steps after it (measure.plan, measure.Chain); beam_area / wcs / wcs_origin are set by the
+        # caller that read the header (SFinder.run)
         self.beam_area, self.wcs, self.wcs_origin = 0, None, (0, 0)
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
         self.merge_overlap_iou_thr_hard = config['merge_overlap_iou_thr_hard']
@@ -155,55 +149,19 @@ class Analyzer(object):
         self.labels_final = [self.class_names[c] for c in self.class_ids_final]
         self.results = {"image_id": self.image_id,
                         "objs": objs_from_detections(dd, self.class_names, nx, ny, xmin, ymin, self.obj_name_tag)}
-        if self.measure:
-            if frame is None:
-                logger.warning("Source measurement needs a 2-D frame: skipped for a 3-channel input image.")
-            else:
-                from . import measure
-                try:
-                    measure.measure_and_annotate(det, frame, self.results["objs"], self.measure_ring, self.beam_area, self.wcs,
-                                                 box_origin=(xmin, ymin), wcs_origin=self.wcs_origin)
-                    c = self.config
-                    if self.bkg_map:
-                        cell, k, niter, min_pix = measure.background_config(c)
-                        mesh, ndef = measure.background_and_annotate(det, frame, self.results["objs"], cell, k, niter, min_pix,
-                                                                     box_origin=(xmin, ymin))
-                        if ndef == 0:
-                            logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % min_pix)
-                        if c.get('save_bkg_maps', False):
-                            measure.save_background_maps(det, mesh, cell, frame.shape,
-                                                         self.outfile_json or ('out_' + str(self.image_id) + '.json'))
-                    if self.islands:
-                        measure.islands_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
-                                                     c.get('island_merge_sigma', 2.5), int(c.get('island_conn', 8)), self.beam_area,
-                                                     self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin, use_map=self.bkg_map)
-                    if self.deblend:
-                        k_peak, radius = measure.deblend_config(c)
-                        kept = measure.deblend_and_annotate(det, frame, self.results["objs"], c.get('island_seed_sigma', 5.0),
-                                                            c.get('island_merge_sigma', 2.5), k_peak, int(c.get('island_conn', 8)), radius,
-                                                            self.beam_area, self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
-                                                            use_map=self.bkg_map, return_raw=self.fit)
-                        if self.fit:
-                            _, rows = measure.fit_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], self.beam_area,
-                                                               self.wcs, box_origin=(xmin, ymin), wcs_origin=self.wcs_origin,
-                                                               use_map=self.bkg_map, max_iter=int(c.get('fit_max_iter', 64)),
-                                                               return_pixel_rows=True)
-                            brows = None
-                            if self.blends:
-                                _, brows = measure.blends_and_annotate(det, frame, self.results["objs"], kept[1], kept[2], kept[3], rows,
-                                                                       self.beam_area, self.wcs, box_origin=(xmin, ymin),
-                                                                       wcs_origin=self.wcs_origin, use_map=self.bkg_map,
-                                                                       max_iter=int(c.get('fit_max_iter', 64)), return_pixel_rows=True)
-                            if self.residual:
-                                bkg_dev = det.expand_background(mesh, cell, frame.shape, want=("bkg",))[0] if self.bkg_map else None
-                                model, resid, _ = measure.residuals_and_annotate(det, frame, self.results["objs"], kept[3], rows, brows,
-                                                                                 float(c.get('residual_nsigma', 5.0)), bkg_dev, self.beam_area,
-                                                                                 box_origin=(xmin, ymin), use_map=self.bkg_map)
-                                if c.get('save_residual_maps', False):
-                                    measure.save_residual_maps(model, resid, self.outfile_json or ('out_' + str(self.image_id) + '.json'))
-                except L.CyError as e:
-                    logger.warning("Source measurement failed (err=%s)..." % str(e))
-                    return -1
+        steps = measure.plan(self.config)
+        if steps and frame is None:
+            logger.warning("Source measurement needs a 2-D frame: skipped for a 3-channel input image.")
+        elif steps:
+            try:
+                chain = measure.Chain(det, frame, self.results["objs"], self.config, self.beam_area, self.wcs, box_origin=(xmin, ymin),
+                                      wcs_origin=self.wcs_origin).run(steps)
+                if chain.ndef == 0:
+                    logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
+                chain.save_maps(self.outfile_json or ('out_' + str(self.image_id) + '.json'))
+            except L.CyError as e:
+                logger.warning("Source measurement failed (err=%s)..." % str(e))
+                return -1
         if self.draw:                                             # caesar_yolo/evaluation.py:203-210
             self.draw_results(self.outfile or ('out_' + str(self.image_id) + '.png'))
         if self.write_to_json:

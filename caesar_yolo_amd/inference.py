@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import measure
 from . import utils
 from .preprocessing import no_preprocessing
 
@@ -570,75 +571,16 @@ class SFinder(object):
                     tid = grid_id[(x + ox, y + oy, th, tw)]
                     utils.write_fits_image('timg_' + str(self.image_id) + '_tid' + str(tid) + '.fits', ch0[b], bitpix=-64)
 
-    def _measure(self, det, mosaic, src):
-        """--measure_sources: the final merged catalog measured on the whole image (a region already resident is reused, otherwise
-        rank 0 uploads what it lacks), one kernel launch; adds the keys of measure.KEYS to every source."""
-        from . import measure
+    def _measure(self, det, mosaic, src, steps):
+        """--measure_sources and the steps after it (measure.plan): the final merged catalog measured on the whole image (a region
+        already resident is reused, otherwise rank 0 uploads what it lacks); adds the keys of every step to every source and its
+        times and counts to the stats."""
         t0 = time.time()
         img, ox, oy = mosaic.region(det, 0, self.nx, 0, self.ny)
-        measure.measure_and_annotate(det, img, src, int(self.config.get('measure_ring', 8)), self.beamArea, self.wcs, box_origin=(ox, oy))
-        self.stats["measure_ms"] = 1e3 * (time.time() - t0)
-        self.stats["measure_kernel_ms"] = det.measure_kernel_ms() if src else 0.0
-        c = self.config
-        use_map = bool(c.get('bkg_map', False)) or bool(c.get('save_bkg_maps', False))
-        if use_map:                                           # --bkg_map: the global mesh, between the two steps, same resident image
-            t1 = time.time()
-            cell, k, niter, min_pix = measure.background_config(c)
-            mesh, ndef = measure.background_and_annotate(det, img, src, cell, k, niter, min_pix, box_origin=(ox, oy))
-            if ndef == 0:
-                logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % min_pix)
-            self.stats["background_ms"] = 1e3 * (time.time() - t1)
-            self.stats["background_kernel_ms"] = det.background_kernel_ms()
-            if c.get('save_bkg_maps', False):
-                measure.save_background_maps(det, mesh, cell, img.shape, self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
-        residual = bool(c.get('residual_map', False)) or bool(c.get('save_residual_maps', False))      # --residual_map: implies the fits
-        if c.get('measure_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False) or residual:     # --measure_islands: the second step, on the same resident image
-            t1 = time.time()
-            measure.islands_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5),
-                                         int(c.get('island_conn', 8)), self.beamArea, self.wcs, box_origin=(ox, oy), use_map=use_map)
-            self.stats["islands_ms"] = 1e3 * (time.time() - t1)
-            self.stats["islands_kernel_ms"] = det.islands_kernel_ms() if src else 0.0
-        if c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False) or residual:     # --deblend_islands: the components, right after the island step
-            t1 = time.time()
-            k_peak, radius = measure.deblend_config(c)
-            blends = bool(c.get('fit_blends', False))         # --fit_blends: the joint fits, right after the single fits they start from
-            fit = bool(c.get('fit_components', False)) or blends or residual      # --fit_components: the raw rows and masks are kept for the fit step
-            kept = measure.deblend_and_annotate(det, img, src, c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5), k_peak,
-                                                int(c.get('island_conn', 8)), radius, self.beamArea, self.wcs, box_origin=(ox, oy),
-                                                use_map=use_map, return_raw=fit)
-            self.stats["deblend_ms"] = 1e3 * (time.time() - t1)
-            self.stats["deblend_kernel_ms"] = det.deblend_kernel_ms() if src else 0.0
-            if fit:
-                t1 = time.time()
-                rows, pixel_rows = measure.fit_and_annotate(det, img, src, kept[1], kept[2], kept[3], self.beamArea, self.wcs,
-                                                            box_origin=(ox, oy), use_map=use_map, max_iter=int(c.get('fit_max_iter', 64)),
-                                                            return_pixel_rows=True)
-                self.stats["fit_ms"] = 1e3 * (time.time() - t1)
-                self.stats["fit_kernel_ms"] = max(det.fit_kernel_ms(), 0.0) if src else 0.0
-                self.stats["fit_jobs"], self.stats["fit_niter_mean"], self.stats["fit_niter_max"] = measure.fit_iterations(rows)
-                blend_pixel_rows = None
-                if blends:
-                    t1 = time.time()
-                    brows, blend_pixel_rows = measure.blends_and_annotate(det, img, src, kept[1], kept[2], kept[3], pixel_rows, self.beamArea,
-                                                                          self.wcs, box_origin=(ox, oy), use_map=use_map,
-                                                                          max_iter=int(c.get('fit_max_iter', 64)), return_pixel_rows=True)
-                    self.stats["blend_ms"] = 1e3 * (time.time() - t1)
-                    self.stats["blend_kernel_ms"] = max(det.blend_kernel_ms(), 0.0) if src else 0.0
-                    (self.stats["blend_jobs"], self.stats["blend_niter_mean"], self.stats["blend_niter_max"],
-                     self.stats["blend_over_limit"]) = measure.blend_stats(brows)
-                if residual:                                  # --residual_map: the fitted components back on the sky, the last step
-                    t1 = time.time()
-                    bkg_dev = det.expand_background(mesh, cell, img.shape, want=("bkg",))[0] if use_map else None
-                    model, resid, rs = measure.residuals_and_annotate(det, img, src, kept[3], pixel_rows, blend_pixel_rows,
-                                                                      float(c.get('residual_nsigma', 5.0)), bkg_dev, self.beamArea,
-                                                                      box_origin=(ox, oy), use_map=use_map)
-                    self.stats["residual_ms"] = 1e3 * (time.time() - t1)
-                    self.stats["render_kernel_ms"] = det.render_kernel_ms()
-                    self.stats["residual_kernel_ms"] = det.residual_kernel_ms() if src else 0.0
-                    self.stats["residual_rendered"], self.stats["residual_duplicates"], self.stats["residual_capped"] = (
-                        rs["rendered"], rs["duplicates"], rs["capped"])
-                    if c.get('save_residual_maps', False):
-                        measure.save_residual_maps(model, resid, self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
+        chain = measure.Chain(det, img, src, self.config, self.beamArea, self.wcs, box_origin=(ox, oy)).run(steps, self.stats, t0)
+        if chain.ndef == 0:
+            logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
+        chain.save_maps(self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
 
     # ---- tiled (reference :578-658)
     def run_parallel(self):
@@ -674,10 +616,9 @@ class SFinder(object):
         if rank == 0:
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
-            if (c.get('measure_sources', False) or c.get('measure_islands', False) or c.get('bkg_map', False) or c.get('save_bkg_maps', False)
-                    or c.get('deblend_islands', False) or c.get('fit_components', False) or c.get('fit_blends', False)
-                    or c.get('residual_map', False) or c.get('save_residual_maps', False)):
-                self._measure(det, mosaic, src)
+            steps = measure.plan(c)
+            if steps:
+                self._measure(det, mosaic, src, steps)
             self.sources = {"sources": src}
             if self.write_to_json:
                 out = self.outfile_json or ('catalog_' + str(self.image_id) + '.json')

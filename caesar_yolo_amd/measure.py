@@ -32,10 +32,35 @@ map and forms the residual map; `cy_measure_residuals` (HipDetector.measure_resi
 box and island set, raw rows lib.RND_NAMES / lib.RES_NAMES, keys RESIDUAL_KEYS on every source and RENDER_ITEM_KEYS on every
 component dict (annotate_residuals).
 
-Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic."""
+Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
+
+plan() names the steps a config asks for and Chain runs them on one image: the one place that knows their order, what each hands to
+the next and the three frames (pixels of the measured image, catalog coordinates, the frame of the WCS)."""
 import math
+import os
+import time
+from types import SimpleNamespace
 
 import numpy as np
+
+from . import lib as L
+
+
+def _fields(names):
+    """The column of every named field of a raw row: _fields(L.MEAS_NAMES).bkg == 2."""
+    return SimpleNamespace(**{n: i for i, n in enumerate(names)})
+
+
+MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
+RND, RES, BKG = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES)
+_MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
+_MOMENTS = ("S", "Sx", "Sy", "Sxx", "Syy", "Sxy")
+_COMP_MOMENTS = [getattr(COMP, k) for k in _MOMENTS]
+_ISL_MOMENTS = [getattr(ISL, k) for k in _MOMENTS + ("S_main",)]
+_ISL_BOX = [ISL.xmin, ISL.xmax, ISL.ymin, ISL.ymax]
+_FIT_PARAMS = [getattr(FIT, k) for k in "A x0 y0 a b c".split()]
+_BLEND_PARAMS = [getattr(BLEND, k) for k in "A x0 y0 a b c".split()]
+_FITTED = (0.0, 2.0)               # status of a fit or blend row that holds a result: converged, or stopped at the iteration limit
 
 KEYS = ("npix", "bkg", "rms", "peak", "snr", "x_peak", "y_peak", "x0", "y0", "flux_sum", "flux", "ra", "dec")
 ISLAND_KEYS = ("island_count", "island_npix", "island_npix_main", "island_border", "island_x1", "island_x2", "island_y1", "island_y2",
@@ -59,6 +84,21 @@ def boxes_of(sources):
     return np.array([[s["x1"], s["y1"], s["x2"], s["y2"]] for s in sources], np.float64).reshape(-1, 4)
 
 
+def _sky(wcs, x, y, ox, oy):
+    """(ra, dec) of catalog position (x, y), (ox, oy) being catalog coordinate (0, 0) in the frame of the WCS; (None, None)
+    without a WCS."""
+    if wcs is None:
+        return None, None
+    a, d = wcs.wcs_pix2world(x + ox, y + oy, 0)
+    return float(a), float(d)
+
+
+def _rms_of(s, use_map):
+    """The noise a source's thresholds were formed with (rms, or rms_map with use_map) as a float; 0.0 when missing."""
+    rms = s.get("rms_map" if use_map else "rms")
+    return float(rms) if rms else 0.0
+
+
 def annotate(sources, raw, beam_area, wcs, origin=(0, 0)):
     """Adds KEYS to every source dict (in place; returns the list).  raw: [n, CY_MEAS_FIELDS] rows measured on the boxes (x1, y1,
     x2, y2) of `sources`, in the pixel frame of the measured image.
@@ -73,7 +113,7 @@ def annotate(sources, raw, beam_area, wcs, origin=(0, 0)):
     ox, oy = float(origin[0]), float(origin[1])
     ba = float(beam_area) if beam_area else 0.0
     for s, r in zip(sources, raw):
-        npix, _, bkg, rms, peak, xp, yp, total, sw, swx, swy = (float(v) for v in r[:11])
+        npix, bkg, rms, peak, xp, yp, total, sw, swx, swy = (float(r[k]) for k in _MEAS_USED)
         if sw == 0.0:
             x0, y0 = (float(s["x1"]) + float(s["x2"])) / 2.0, (float(s["y1"]) + float(s["y2"])) / 2.0
         else:
@@ -85,31 +125,8 @@ def annotate(sources, raw, beam_area, wcs, origin=(0, 0)):
         s["x0"], s["y0"] = x0, y0
         s["flux_sum"] = total
         s["flux"] = total / ba if ba > 0.0 else None
-        if wcs is not None:
-            a, d = wcs.wcs_pix2world(x0 + ox, y0 + oy, 0)
-            s["ra"], s["dec"] = float(a), float(d)
-        else:
-            s["ra"], s["dec"] = None, None
+        s["ra"], s["dec"] = _sky(wcs, x0, y0, ox, oy)
     return sources
-
-
-def measure_and_annotate(det, img_dev, sources, ring, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0)):
-    """One cy_measure_sources call over `sources` on the device image, then annotate().  box_origin: the catalog boxes'
-    coordinates of pixel [0, 0] of img_dev (subtracted before measuring; x_peak, y_peak, x0, y0 come back in catalog
-    coordinates).  wcs_origin: position of catalog coordinate (0, 0) in the frame of the WCS."""
-    if not sources:
-        return sources
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    raw = det.measure_sources(img_dev, boxes, ring=ring)
-    if bx or by:
-        raw = raw.copy()
-        has = raw[:, 0] > 0
-        raw[has, 5] += bx
-        raw[has, 6] += by
-        raw[:, 9] += bx * raw[:, 8]
-        raw[:, 10] += by * raw[:, 8]
-    return annotate(sources, raw, beam_area, wcs, wcs_origin)
 
 
 def box_window(box, MH, MW):
@@ -131,7 +148,11 @@ def island_shape(S, Sx, Sy, Sxx, Syy, Sxy):
     (Sx / S)^2 etc., their eigenvalues l1 >= l2 (a negative one, from rounding, counts as 0), major / minor = FWHM * sqrt(l) in
     pixels, pa = angle of the major axis from +x towards +y in degrees, in (-90, 90], 0 when l1 == l2."""
     mx, my = Sx / S, Sy / S
-    cxx, cyy, cxy = Sxx / S - mx * mx, Syy / S - my * my, Sxy / S - mx * my
+    return _axes(Sxx / S - mx * mx, Syy / S - my * my, Sxy / S - mx * my)
+
+
+def _axes(cxx, cyy, cxy):
+    """(major, minor, pa) of the covariance [[cxx, cxy], [cxy, cyy]]: the tail of island_shape() and gaussian_shape()."""
     half, d = (cxx + cyy) / 2.0, math.hypot((cxx - cyy) / 2.0, cxy)
     l1, l2 = max(half + d, 0.0), max(half - d, 0.0)
     pa = 0.0
@@ -162,13 +183,14 @@ def annotate_islands(sources, raw, win0, beam_area, wcs, origin=(0, 0)):
     for s, r, (wx0, wy0) in zip(sources, raw, win0):
         for k in ISLAND_KEYS:
             s[k] = None
-        if r[0] != 0.0:
+        if r[ISL.status] != 0.0:
             continue
-        s["island_count"], s["island_npix"], s["island_npix_main"], s["island_border"] = int(r[2]), int(r[3]), int(r[4]), bool(r[5] > 0)
-        if r[1] == 0.0:
+        s["island_count"], s["island_npix"], s["island_npix_main"] = int(r[ISL.nislands]), int(r[ISL.npix]), int(r[ISL.npix_main])
+        s["island_border"] = bool(r[ISL.nborder] > 0)
+        if r[ISL.nseed] == 0.0:
             continue
-        s["island_x1"], s["island_x2"], s["island_y1"], s["island_y2"] = (int(v) for v in r[6:10])
-        S, Sx, Sy, Sxx, Syy, Sxy, Sm = (float(v) for v in r[10:17])
+        s["island_x1"], s["island_x2"], s["island_y1"], s["island_y2"] = (int(v) for v in r[_ISL_BOX])
+        S, Sx, Sy, Sxx, Syy, Sxy, Sm = (float(v) for v in r[_ISL_MOMENTS])
         s["island_flux_sum"] = S
         if ba > 0.0:
             s["island_flux"], s["island_flux_main"] = S / ba, Sm / ba
@@ -176,48 +198,34 @@ def annotate_islands(sources, raw, win0, beam_area, wcs, origin=(0, 0)):
             continue
         s["x_isl"], s["y_isl"] = float(wx0) + Sx / S, float(wy0) + Sy / S
         s["major"], s["minor"], s["pa"] = island_shape(S, Sx, Sy, Sxx, Syy, Sxy)
-        if wcs is not None:
-            a, d = wcs.wcs_pix2world(s["x_isl"] + ox, s["y_isl"] + oy, 0)
-            s["ra_isl"], s["dec_isl"] = float(a), float(d)
+        s["ra_isl"], s["dec_isl"] = _sky(wcs, s["x_isl"], s["y_isl"], ox, oy)
     return sources
+
+
+def _bkg_of(sources, use_map):
+    """[n] float64: the background a source's thresholds are formed with: bkg of annotate(), or with use_map bkg_map of the mesh."""
+    return np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
+
+
+def _thresholds(sources, ks, use_map):
+    """(bkg [n], [bkg + k * rms for k in ks]) from bkg and rms of annotate(), or with use_map bkg_map and rms_map."""
+    bkg = _bkg_of(sources, use_map)
+    rms = np.array([s["rms_map" if use_map else "rms"] for s in sources], np.float64)
+    return bkg, [bkg + float(k) * rms for k in ks]
 
 
 def island_thresholds(sources, k_seed, k_merge, use_map=False):
     """[n, 3] float64 {seed_thr, merge_thr, bkg} from the bkg and rms the first step (annotate) left on the sources; use_map: from
     the bkg_map and rms_map of the background mesh (annotate_background) instead."""
-    kb, kr = ("bkg_map", "rms_map") if use_map else ("bkg", "rms")
-    bkg = np.array([s[kb] for s in sources], np.float64)
-    rms = np.array([s[kr] for s in sources], np.float64)
-    return np.stack([bkg + float(k_seed) * rms, bkg + float(k_merge) * rms, bkg], 1)
-
-
-def islands_and_annotate(det, img_dev, sources, k_seed, k_merge, conn, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0), use_map=False):
-    """The island step, after measure_and_annotate on the same sources and image: thresholds bkg + k * rms in numpy float64, one
-    cy_measure_islands call, then annotate_islands().  box_origin / wcs_origin as in measure_and_annotate: positions come back in
-    catalog coordinates.  use_map: thresholds (and the bkg of the sums) from bkg_map / rms_map, after background_and_annotate."""
-    if not sources:
-        return sources
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    raw = det.measure_islands(img_dev, boxes, island_thresholds(sources, k_seed, k_merge, use_map), conn=conn)
-    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
-    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
-    if bx or by:
-        raw = raw.copy()
-        has = raw[:, 3] > 0
-        raw[has, 6:8] += bx
-        raw[has, 8:10] += by
-    return annotate_islands(sources, raw, win0, beam_area, wcs, wcs_origin)
+    bkg, t = _thresholds(sources, (k_seed, k_merge), use_map)
+    return np.stack(t + [bkg], 1)
 
 
 # ---- source components (--deblend_islands)
 def deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map=False):
     """[n, 4] float64 {seed_thr, merge_thr, bkg, peak_thr}: island_thresholds() plus bkg + k_peak * rms."""
-    t = island_thresholds(sources, k_seed, k_merge, use_map)
-    kb, kr = ("bkg_map", "rms_map") if use_map else ("bkg", "rms")
-    bkg = np.array([s[kb] for s in sources], np.float64)
-    rms = np.array([s[kr] for s in sources], np.float64)
-    return np.concatenate([t.reshape(-1, 3), (bkg + float(k_peak) * rms).reshape(-1, 1)], 1)
+    bkg, t = _thresholds(sources, (k_seed, k_merge, k_peak), use_map)
+    return np.stack(t[:2] + [bkg, t[2]], 1)
 
 
 def annotate_components(sources, raw, comp, win0, beam_area, wcs, origin=(0, 0)):
@@ -236,71 +244,37 @@ def annotate_components(sources, raw, comp, win0, beam_area, wcs, origin=(0, 0))
         return sources
     n = len(sources)
     raw = np.asarray(raw, np.float64).reshape(n, -1)
-    comp = np.asarray(comp, np.float64).reshape(n, -1, 12)                # CY_DBL_COMP_FIELDS
+    comp = np.asarray(comp, np.float64).reshape(n, -1, L.CY_DBL_COMP_FIELDS)
     win0 = np.asarray(win0, np.float64).reshape(n, 2)
     ox, oy = float(origin[0]), float(origin[1])
     ba = float(beam_area) if beam_area else 0.0
     for s, r, cr, (wx0, wy0) in zip(sources, raw, comp, win0):
         for k in COMPONENT_KEYS:
             s[k] = None
-        if r[0] == 1.0:
+        if r[DBL.status] == 1.0:
             continue
-        s["npeaks"], s["ncomponents"], s["components_truncated"], s["components_unassigned_npix"] = int(r[2]), int(r[3]), bool(r[0] == 2.0), int(r[5])
+        s["npeaks"], s["ncomponents"], s["components_truncated"] = int(r[DBL.npeaks]), int(r[DBL.ncomp]), bool(r[DBL.status] == 2.0)
+        s["components_unassigned_npix"] = int(r[DBL.npix_unassigned])
         items = []
-        for c in cr[:int(r[3])]:
-            S, Sx, Sy, Sxx, Syy, Sxy = (float(v) for v in c[4:10])
+        for c in cr[:int(r[DBL.ncomp])]:
+            S, Sx, Sy, Sxx, Syy, Sxy = (float(v) for v in c[_COMP_MOMENTS])
             d = dict.fromkeys(COMPONENT_ITEM_KEYS)
-            d["peak"], d["x_peak"], d["y_peak"], d["npix"] = float(c[1]), int(c[2]), int(c[3]), int(c[0])
-            d["flux_sum"], d["main"], d["nsummits"] = S, bool(c[10] != 0.0), int(c[11])
+            d["peak"], d["x_peak"], d["y_peak"], d["npix"] = float(c[COMP.peak]), int(c[COMP.x_peak]), int(c[COMP.y_peak]), int(c[COMP.npix])
+            d["flux_sum"], d["main"], d["nsummits"] = S, bool(c[COMP.main] != 0.0), int(c[COMP.nsummits])
             if ba > 0.0:
                 d["flux"] = S / ba
             if S != 0.0:
                 d["x"], d["y"] = float(wx0) + Sx / S, float(wy0) + Sy / S
                 d["major"], d["minor"], d["pa"] = island_shape(S, Sx, Sy, Sxx, Syy, Sxy)
-                if wcs is not None:
-                    a, dd = wcs.wcs_pix2world(d["x"] + ox, d["y"] + oy, 0)
-                    d["ra"], d["dec"] = float(a), float(dd)
+                d["ra"], d["dec"] = _sky(wcs, d["x"], d["y"], ox, oy)
             items.append(d)
         s["components"] = items
     return sources
 
 
-def deblend_and_annotate(det, img_dev, sources, k_seed, k_merge, k_peak, conn, radius, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
-                         use_map=False, return_raw=False):
-    """The component step, after islands_and_annotate on the same sources and image: thresholds in numpy float64, one
-    cy_deblend_islands call, then annotate_components().  box_origin / wcs_origin / use_map as in islands_and_annotate: positions
-    come back in catalog coordinates.  return_raw: -> (sources, raw rows, component rows, masks) as HipDetector.deblend_islands
-    returns them with return_masks, in the pixel frame of img_dev: what fit_and_annotate() takes, so that the kernel runs once."""
-    if not sources:
-        return (sources, np.zeros((0, 8)), np.zeros((0, 16, 12)), []) if return_raw else sources
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    thr4 = deblend_thresholds(sources, k_seed, k_merge, k_peak, use_map)
-    if return_raw:
-        raw, comp, masks = det.deblend_islands(img_dev, boxes, thr4, conn=conn, radius=radius, return_masks=True)
-        keep = (sources, raw, comp, masks)
-    else:
-        raw, comp = det.deblend_islands(img_dev, boxes, thr4, conn=conn, radius=radius)
-    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
-    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2) + np.array([bx, by])
-    annotate_components(sources, raw, _shift_comp(raw, comp, bx, by), win0, beam_area, wcs, wcs_origin)
-    return keep if return_raw else sources
-
-
-def _shift_comp(raw, comp, bx, by):
-    """Component rows with the peak positions of the rows below ncomp moved by (bx, by); a copy when anything moves."""
-    if not (bx or by):
-        return comp
-    comp = comp.copy()
-    has = np.arange(comp.shape[1])[None, :] < raw[:, 3].astype(np.int64)[:, None]
-    comp[:, :, 2][has] += bx
-    comp[:, :, 3][has] += by
-    return comp
-
-
 # ---- component fits (--fit_components)
 def fit_start(comp_rows, bkg, win0):
-    """Start values {A, x0, y0, a, b, c} of the fit from component rows (lib.DBL_COMP_NAMES): comp_rows [..., 12], bkg [...] and
+    """Start values {A, x0, y0, a, b, c} of the fit from component rows (lib.DBL_COMP_NAMES): comp_rows [..., CY_DBL_COMP_FIELDS], bkg [...] and
     win0 [..., 2] (first column / row of the box window) broadcast against the leading axes; x0, y0 in the frame of win0 and of the
     rows' peak positions.  -> float64 [..., 6].
       A        peak - bkg
@@ -314,7 +288,7 @@ def fit_start(comp_rows, bkg, win0):
     bkg = np.broadcast_to(np.asarray(bkg, np.float64).reshape(np.shape(bkg) + (1,) * (len(lead) - np.ndim(bkg))), lead)
     w0 = np.asarray(win0, np.float64)
     w0 = np.broadcast_to(w0.reshape(w0.shape[:-1] + (1,) * (len(lead) - (w0.ndim - 1)) + (2,)), lead + (2,))
-    S, Sx, Sy, Sxx, Syy, Sxy = (r[..., k] for k in range(4, 10))
+    S, Sx, Sy, Sxx, Syy, Sxy = (r[..., k] for k in _COMP_MOMENTS)
     with np.errstate(all="ignore"):
         mx, my = Sx / S, Sy / S
         cxx, cyy, cxy = Sxx / S - mx * mx, Syy / S - my * my, Sxy / S - mx * my
@@ -327,9 +301,9 @@ def fit_start(comp_rows, bkg, win0):
         a, b, c = vyy / det, -vxy / det, vxx / det
         good = (S > 0.0) & np.isfinite(S) & np.isfinite(mx) & np.isfinite(my) & np.isfinite(a) & np.isfinite(b) & np.isfinite(c)
     out = np.empty(lead + (6,), np.float64)
-    out[..., 0] = r[..., 1] - bkg
-    out[..., 1] = np.where(good, w0[..., 0] + mx, r[..., 2])
-    out[..., 2] = np.where(good, w0[..., 1] + my, r[..., 3])
+    out[..., 0] = r[..., COMP.peak] - bkg
+    out[..., 1] = np.where(good, w0[..., 0] + mx, r[..., COMP.x_peak])
+    out[..., 2] = np.where(good, w0[..., 1] + my, r[..., COMP.y_peak])
     out[..., 3] = np.where(good, a, 1.0)
     out[..., 4] = np.where(good, b, 0.0)
     out[..., 5] = np.where(good, c, 1.0)
@@ -341,15 +315,7 @@ def gaussian_shape(a, b, c):
     covariance, in pixels; pa as island_shape(): angle of the major axis from +x towards +y in degrees, in (-90, 90], 0 for a
     circle."""
     det = a * c - b * b
-    cxx, cyy, cxy = c / det, a / det, -b / det
-    half, d = (cxx + cyy) / 2.0, math.hypot((cxx - cyy) / 2.0, cxy)
-    l1, l2 = max(half + d, 0.0), max(half - d, 0.0)
-    pa = 0.0
-    if l1 != l2:
-        pa = 0.5 * math.degrees(math.atan2(2.0 * cxy + 0.0, cxx - cyy))
-        if pa <= -90.0:
-            pa += 180.0
-    return FWHM * math.sqrt(l1), FWHM * math.sqrt(l2), pa
+    return _axes(c / det, a / det, -b / det)
 
 
 def fit_flux(p, beam_area):
@@ -367,7 +333,7 @@ def fit_covariance(row, rms):
     """rms^2 * inv(H) from a fit row (lib.FIT_NAMES), the covariance of the six parameters for uncorrelated noise of that rms; None
     when H is singular or not finite."""
     H = np.zeros((6, 6), np.float64)
-    H[np.triu_indices(6)] = np.asarray(row, np.float64)[11:32]
+    H[np.triu_indices(6)] = np.asarray(row, np.float64)[FIT.H00:FIT.H55 + 1]
     H = H + np.triu(H, 1).T
     if not np.isfinite(H).all():
         return None
@@ -392,69 +358,44 @@ def annotate_fits(sources, fit, beam_area, wcs, origin=(0, 0), use_map=False):
     the supported maximum) is left alone."""
     if not sources:
         return sources
-    fit = np.asarray(fit, np.float64).reshape(len(sources), -1, 32)       # CY_FIT_FIELDS
+    fit = np.asarray(fit, np.float64).reshape(len(sources), -1, L.CY_FIT_FIELDS)
     ox, oy = float(origin[0]), float(origin[1])
     ba = float(beam_area) if beam_area else 0.0
     for s, fr in zip(sources, fit):
-        rms = s.get("rms_map" if use_map else "rms")
-        rms = float(rms) if rms else 0.0
+        rms = _rms_of(s, use_map)
         for d, r in zip(s.get("components") or [], fr):
             for k in FIT_KEYS:
                 d[k] = None
-            st = int(r[0])
-            d["fit_status"], d["fit_niter"], d["fit_npix"] = st, int(r[1]), int(r[2])
-            if st not in (0, 2):
-                continue
-            p = [float(v) for v in r[5:11]]
-            d["fit_chi2"] = float(r[3]) / (rms * rms) if rms > 0.0 else None
-            d["fit_peak"], d["fit_x"], d["fit_y"] = p[0], p[1], p[2]
-            d["fit_major"], d["fit_minor"], d["fit_pa"] = gaussian_shape(p[3], p[4], p[5])
-            if wcs is not None:
-                a, dd = wcs.wcs_pix2world(p[1] + ox, p[2] + oy, 0)
-                d["fit_ra"], d["fit_dec"] = float(a), float(dd)
-            if ba > 0.0:
-                d["fit_flux"] = fit_flux(p, ba)
-            cov = fit_covariance(r, rms) if rms > 0.0 else None
-            if cov is not None:
-                d["fit_peak_err"], d["fit_x_err"], d["fit_y_err"] = (math.sqrt(cov[k, k]) for k in range(3))
-                if ba > 0.0:
-                    g = fit_flux_grad(p, ba)
-                    d["fit_flux_err"] = math.sqrt(max(float(g @ cov @ g), 0.0))
+            st = int(r[FIT.status])
+            d["fit_status"], d["fit_niter"], d["fit_npix"] = st, int(r[FIT.niter]), int(r[FIT.npix])
+            if st in (0, 2):
+                _gaussian_keys(d, "fit_", r, FIT.F, _FIT_PARAMS, fit_covariance, rms, ba, wcs, ox, oy)
     return sources
 
 
-def fit_and_annotate(det, img_dev, sources, raw, comp, masks, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0), use_map=False,
-                     max_iter=64, return_pixel_rows=False):
-    """The fit step, after deblend_and_annotate(..., return_raw=True) on the same sources and image, whose raw rows, component rows
-    and masks it takes (pixel frame of img_dev): fit_start(), one cy_fit_components call, then annotate_fits().  The background of
-    a source is the one its thresholds were formed with (bkg, or bkg_map with use_map).  -> the fit rows, centres in catalog
-    coordinates; with return_pixel_rows -> (those rows, the rows as the library gave them, in the pixel frame of img_dev: what
-    blends_and_annotate() takes)."""
-    n = len(sources)
-    if not n:
-        return (np.zeros((0, 16, 32), np.float64),) * 2 if return_pixel_rows else np.zeros((0, 16, 32), np.float64)
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
-    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2)
-    bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
-    raw = np.asarray(raw, np.float64).reshape(n, -1)
-    ncomp = np.where(raw[:, 0] == 1.0, 0, raw[:, 3]).astype(np.int32)
-    start = fit_start(np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
-    fit = det.fit_components(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
-    pixel_rows = fit.copy() if return_pixel_rows else None
-    if bx or by:
-        has = (np.arange(fit.shape[1])[None, :] < ncomp[:, None]) & (fit[:, :, 0] != 1.0)
-        fit[:, :, 6][has] += bx
-        fit[:, :, 7][has] += by
-    annotate_fits(sources, fit, beam_area, wcs, wcs_origin, use_map)
-    return (fit, pixel_rows) if return_pixel_rows else fit
+def _gaussian_keys(d, pre, r, F, params, covariance, rms, ba, wcs, ox, oy):
+    """The value and error keys <pre>chi2 .. <pre>flux_err of component dict d from its fitted row r of cy_fit_components (pre
+    "fit_") or cy_fit_blends ("blend_"): F, params are the row's columns of the sum of squares and of the six parameters,
+    covariance(r, rms) gives their covariance or None."""
+    p = [float(v) for v in r[params]]
+    d[pre + "chi2"] = float(r[F]) / (rms * rms) if rms > 0.0 else None
+    d[pre + "peak"], d[pre + "x"], d[pre + "y"] = p[0], p[1], p[2]
+    d[pre + "major"], d[pre + "minor"], d[pre + "pa"] = gaussian_shape(p[3], p[4], p[5])
+    d[pre + "ra"], d[pre + "dec"] = _sky(wcs, p[1], p[2], ox, oy)
+    if ba > 0.0:
+        d[pre + "flux"] = fit_flux(p, ba)
+    cov = covariance(r, rms) if rms > 0.0 else None
+    if cov is not None:
+        d[pre + "peak_err"], d[pre + "x_err"], d[pre + "y_err"] = (math.sqrt(cov[k, k]) for k in range(3))
+        if ba > 0.0:
+            g = fit_flux_grad(p, ba)
+            d[pre + "flux_err"] = math.sqrt(max(float(g @ cov @ g), 0.0))
 
 
 def fit_iterations(fit):
     """(jobs, mean niter, largest niter) over the fitted rows (status 0 or 2) of cy_fit_components; (0, 0.0, 0) without one."""
-    fit = np.asarray(fit, np.float64).reshape(-1, 32)
-    it = fit[(fit[:, 1] > 0) & ((fit[:, 0] == 0.0) | (fit[:, 0] == 2.0)), 1]
+    fit = np.asarray(fit, np.float64).reshape(-1, L.CY_FIT_FIELDS)
+    it = fit[(fit[:, FIT.niter] > 0) & np.isin(fit[:, FIT.status], _FITTED), FIT.niter]
     return (int(it.size), float(it.mean()), int(it.max())) if it.size else (0, 0.0, 0)
 
 
@@ -485,22 +426,22 @@ def blend_groups(mask, h, w, ncomp):
 
 def blend_start(fit_rows, comp_rows, bkg, win0):
     """One start {A, x0, y0, a, b, c} per component for cy_fit_blends: the parameters of its cy_fit_components row (fit_rows
-    [..., 32]) when that row's status is 0 or 2, else fit_start(comp_rows, bkg, win0).  Both in the same pixel frame.
+    [..., CY_FIT_FIELDS]) when that row's status is 0 or 2, else fit_start(comp_rows, bkg, win0).  Both in the same pixel frame.
     -> float64 [..., 6]."""
     fit_rows = np.asarray(fit_rows, np.float64)
     out = fit_start(comp_rows, bkg, win0)
-    use = ((fit_rows[..., 0] == 0.0) | (fit_rows[..., 0] == 2.0)) & (fit_rows[..., 1] > 0.0)     # niter 0: a row beyond ncomp
-    out[use] = fit_rows[..., 5:11][use]
+    use = np.isin(fit_rows[..., FIT.status], _FITTED) & (fit_rows[..., FIT.niter] > 0.0)     # niter 0: a row beyond ncomp
+    out[use] = fit_rows[..., _FIT_PARAMS][use]
     return out
 
 
 def blend_covariance(row, rms):
     """rms^2 times the member's 6 x 6 block of inv(H) from a blend row (lib.BLEND_NAMES); None when cov_ok is 0 or it is not finite."""
     row = np.asarray(row, np.float64)
-    if row[14] == 0.0:
+    if row[BLEND.cov_ok] == 0.0:
         return None
     C = np.zeros((6, 6), np.float64)
-    C[np.triu_indices(6)] = row[15:36]
+    C[np.triu_indices(6)] = row[BLEND.C00:BLEND.C55 + 1]
     C = (C + np.triu(C, 1).T) * (float(rms) * float(rms))
     return C if np.isfinite(C).all() and (np.diag(C) >= 0.0).all() else None
 
@@ -518,76 +459,32 @@ def annotate_blends(sources, rows, beam_area, wcs, origin=(0, 0), use_map=False)
     of columns describes every component.  Status 1, 3, 4 or 5: they are None.  A source whose components are None is left alone."""
     if not sources:
         return sources
-    rows = np.asarray(rows, np.float64).reshape(len(sources), -1, 36)     # CY_BLEND_FIELDS
+    rows = np.asarray(rows, np.float64).reshape(len(sources), -1, L.CY_BLEND_FIELDS)
     ox, oy = float(origin[0]), float(origin[1])
     ba = float(beam_area) if beam_area else 0.0
     for s, br in zip(sources, rows):
-        rms = s.get("rms_map" if use_map else "rms")
-        rms = float(rms) if rms else 0.0
+        rms = _rms_of(s, use_map)
         for d, r in zip(s.get("components") or [], br):
             for k in BLEND_KEYS:
                 d[k] = None
-            st = int(r[0])
-            d["blend_group"], d["blend_size"], d["blend_status"], d["blend_niter"], d["blend_npix"] = int(r[5]), int(r[6]), st, int(r[1]), int(r[2])
+            st = int(r[BLEND.status])
+            d["blend_group"], d["blend_size"], d["blend_status"] = int(r[BLEND.group]), int(r[BLEND.nmembers]), st
+            d["blend_niter"], d["blend_npix"] = int(r[BLEND.niter]), int(r[BLEND.npix])
             if st == 6:
-                for k in BLEND_KEYS[5:]:
-                    d[k] = d.get("fit_" + k[6:])
-                continue
-            if st not in (0, 2):
-                continue
-            p = [float(v) for v in r[8:14]]
-            d["blend_chi2"] = float(r[3]) / (rms * rms) if rms > 0.0 else None
-            d["blend_peak"], d["blend_x"], d["blend_y"] = p[0], p[1], p[2]
-            d["blend_major"], d["blend_minor"], d["blend_pa"] = gaussian_shape(p[3], p[4], p[5])
-            if wcs is not None:
-                a, dd = wcs.wcs_pix2world(p[1] + ox, p[2] + oy, 0)
-                d["blend_ra"], d["blend_dec"] = float(a), float(dd)
-            if ba > 0.0:
-                d["blend_flux"] = fit_flux(p, ba)
-            cov = blend_covariance(r, rms) if rms > 0.0 else None
-            if cov is not None:
-                d["blend_peak_err"], d["blend_x_err"], d["blend_y_err"] = (math.sqrt(cov[k, k]) for k in range(3))
-                if ba > 0.0:
-                    g = fit_flux_grad(p, ba)
-                    d["blend_flux_err"] = math.sqrt(max(float(g @ cov @ g), 0.0))
+                for k in BLEND_KEYS[BLEND_KEYS.index("blend_chi2"):]:
+                    d[k] = d.get("fit_" + k[len("blend_"):])
+            elif st in (0, 2):
+                _gaussian_keys(d, "blend_", r, BLEND.F, _BLEND_PARAMS, blend_covariance, rms, ba, wcs, ox, oy)
     return sources
-
-
-def blends_and_annotate(det, img_dev, sources, raw, comp, masks, fit_rows, beam_area, wcs, box_origin=(0, 0), wcs_origin=(0, 0),
-                        use_map=False, max_iter=64, return_pixel_rows=False):
-    """The joint-fit step, after fit_and_annotate(..., return_pixel_rows=True) on the same sources, image, raw rows, component
-    rows and masks, whose fit rows in the pixel frame of img_dev it takes: blend_start(), one cy_fit_blends call, then
-    annotate_blends().  -> the blend rows, centres in catalog coordinates; with return_pixel_rows -> (those rows, the rows as the
-    library gave them, in the pixel frame of img_dev: what residuals_and_annotate() takes)."""
-    n = len(sources)
-    if not n:
-        return (np.zeros((0, 16, 36), np.float64),) * 2 if return_pixel_rows else np.zeros((0, 16, 36), np.float64)
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-    MH, MW = int(img_dev.shape[0]), int(img_dev.shape[1])
-    win0 = np.array([box_window(b, MH, MW)[:2] for b in boxes], np.float64).reshape(-1, 2)
-    bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
-    raw = np.asarray(raw, np.float64).reshape(n, -1)
-    ncomp = np.where(raw[:, 0] == 1.0, 0, raw[:, 3]).astype(np.int32)
-    fit_rows = np.asarray(fit_rows, np.float64).reshape(n, -1, 32)
-    start = blend_start(fit_rows, np.asarray(comp, np.float64).reshape(n, -1, 12), bkg, win0)
-    rows = det.fit_blends(img_dev, boxes, bkg, ncomp, start, masks, max_iter=max_iter)
-    pixel_rows = rows.copy() if return_pixel_rows else None
-    if bx or by:
-        has = (np.arange(rows.shape[1])[None, :] < ncomp[:, None]) & np.isin(rows[:, :, 0], (0.0, 2.0, 3.0, 4.0, 5.0))
-        rows[:, :, 9][has] += bx
-        rows[:, :, 10][has] += by
-    annotate_blends(sources, rows, beam_area, wcs, wcs_origin, use_map)
-    return (rows, pixel_rows) if return_pixel_rows else rows
 
 
 def blend_stats(rows):
     """(jobs, mean niter, largest niter, groups above CY_BLEND_MAX_MEMBERS) over the rows of cy_fit_blends: a fitted job (status 0
     or 2) is counted once, on its slot-0 row, as is a group above the limit (status 5); (0, 0.0, 0, 0) without any."""
-    rows = np.asarray(rows, np.float64).reshape(-1, 36)
-    first = rows[:, 7] == 0.0
-    it = rows[first & (rows[:, 1] > 0) & ((rows[:, 0] == 0.0) | (rows[:, 0] == 2.0)), 1]
-    over = int((first & (rows[:, 0] == 5.0)).sum())
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_BLEND_FIELDS)
+    first = rows[:, BLEND.slot] == 0.0
+    it = rows[first & (rows[:, BLEND.niter] > 0) & np.isin(rows[:, BLEND.status], _FITTED), BLEND.niter]
+    over = int((first & (rows[:, BLEND.status] == 5.0)).sum())
     return (int(it.size), float(it.mean()), int(it.max()), over) if it.size else (0, 0.0, 0, over)
 
 
@@ -595,16 +492,16 @@ def blend_stats(rows):
 def _fitted_params(fit_row, blend_row):
     """The six parameters a component is rendered with: those of its blend row when that row's status is 0 or 2, else those of its
     fit row when that row's status is 0 or 2, else None."""
-    if blend_row is not None and blend_row[0] in (0.0, 2.0):
-        return blend_row[8:14]
-    if fit_row[0] in (0.0, 2.0):
-        return fit_row[5:11]
+    if blend_row is not None and blend_row[BLEND.status] in _FITTED:
+        return blend_row[_BLEND_PARAMS]
+    if fit_row[FIT.status] in _FITTED:
+        return fit_row[_FIT_PARAMS]
     return None
 
 
 def render_selection(sources, fit_rows, blend_rows=None):
-    """The components cy_render_gaussians is given, after annotate_components() on `sources`.  fit_rows [n, 16, CY_FIT_FIELDS] /
-    blend_rows [n, 16, CY_BLEND_FIELDS] (or None): the rows of cy_fit_components / cy_fit_blends with their centres in the pixel frame
+    """The components cy_render_gaussians is given, after annotate_components() on `sources`.  fit_rows [n, CY_DBL_MAX_COMP, CY_FIT_FIELDS] /
+    blend_rows [n, CY_DBL_MAX_COMP, CY_BLEND_FIELDS] (or None): the rows of cy_fit_components / cy_fit_blends with their centres in the pixel frame
     of the image that is rendered.  Per component of every source, in source order, then component order:
       parameters   the blend row's when its status is 0 or 2, else the fit row's when its status is 0 or 2, else it is not rendered
       duplicates   overlapping boxes share islands, so the same peak can be a component of two sources; a component whose kept peak
@@ -612,8 +509,8 @@ def render_selection(sources, fit_rows, blend_rows=None):
                    peak once
     -> (comp float64 [m, 6] {A, x0, y0, a, b, c}, index int64 [m, 2] {source, component}, the number of duplicates left out)."""
     n = len(sources)
-    fit_rows = np.asarray(fit_rows, np.float64).reshape(n, 16, 32)        # CY_DBL_MAX_COMP, CY_FIT_FIELDS
-    blend_rows = None if blend_rows is None else np.asarray(blend_rows, np.float64).reshape(n, 16, 36)     # CY_BLEND_FIELDS
+    fit_rows = np.asarray(fit_rows, np.float64).reshape(n, L.CY_DBL_MAX_COMP, L.CY_FIT_FIELDS)
+    blend_rows = None if blend_rows is None else np.asarray(blend_rows, np.float64).reshape(n, L.CY_DBL_MAX_COMP, L.CY_BLEND_FIELDS)
     comp, index, taken, ndup = [], [], set(), 0
     for i, s in enumerate(sources):
         for k, d in enumerate(s.get("components") or []):
@@ -646,60 +543,43 @@ def annotate_residuals(sources, raw, index, render_rows, beam_area, origin=(0, 0
     raw = np.asarray(raw, np.float64).reshape(len(sources), -1)
     ox, oy = int(origin[0]), int(origin[1])
     ba = float(beam_area) if beam_area else 0.0
-    status = {(int(i), int(k)): int(r[0]) for (i, k), r in zip(np.asarray(index).reshape(-1, 2), np.asarray(render_rows).reshape(-1, 8))}     # CY_RND_FIELDS
+    render_rows = np.asarray(render_rows).reshape(-1, L.CY_RND_FIELDS)
+    status = {(int(i), int(k)): int(r[RND.status]) for (i, k), r in zip(np.asarray(index).reshape(-1, 2), render_rows)}
     for i, (s, r) in enumerate(zip(sources, raw)):
         for k, d in enumerate(s.get("components") or []):
             st = status.get((i, k))
             d["rendered"], d["render_status"] = st in (0, 2), st
         for key in RESIDUAL_KEYS:
             s[key] = None
-        n_isl = int(r[2]) if r[0] == 0.0 else 0
+        n_isl = int(r[RES.npix_isl]) if r[RES.status] == 0.0 else 0
         s["res_npix"] = n_isl
         if n_isl == 0:
             continue
-        rms = s.get("rms_map" if use_map else "rms")
-        rms = float(rms) if rms else 0.0
-        s["res_mean"], s["res_rms"] = float(r[5]) / n_isl, math.sqrt(float(r[6]) / n_isl)
-        s["res_rms_box"] = math.sqrt(float(r[4]) / float(r[1])) if r[1] > 0 else None
-        s["res_max"], s["res_x_max"], s["res_y_max"] = float(r[7]), int(r[8]) + ox, int(r[9]) + oy
+        rms = _rms_of(s, use_map)
+        s["res_mean"], s["res_rms"] = float(r[RES.sum_isl]) / n_isl, math.sqrt(float(r[RES.sumsq_isl]) / n_isl)
+        s["res_rms_box"] = math.sqrt(float(r[RES.sumsq_win]) / float(r[RES.npix_win])) if r[RES.npix_win] > 0 else None
+        s["res_max"], s["res_x_max"], s["res_y_max"] = float(r[RES.maxabs_isl]), int(r[RES.x_max]) + ox, int(r[RES.y_max]) + oy
         if ba > 0.0:
-            s["res_flux"], s["res_model_flux"] = float(r[5]) / ba, float(r[10]) / ba
+            s["res_flux"], s["res_model_flux"] = float(r[RES.sum_isl]) / ba, float(r[RES.model_isl]) / ba
         s["res_ratio"] = s["res_rms"] / rms if rms > 0.0 else None
     return sources
 
 
-def residuals_and_annotate(det, img_dev, sources, masks, fit_rows, blend_rows=None, nsigma=5.0, bkg_dev=None, beam_area=0, box_origin=(0, 0),
-                           use_map=False):
-    """The residual step, after fit_and_annotate(..., return_pixel_rows=True) (and blends_and_annotate) on the same sources and
-    image: render_selection() on their rows in the pixel frame of img_dev (return_pixel_rows), one cy_render_gaussians call over the
-    whole image (bkg_dev: the expanded background map, or None: the residual keeps the background), one cy_measure_residuals
-    call on the boxes with the masks of deblend_and_annotate and the background the fits used, then annotate_residuals().
-    -> (model, resid device maps, {"rendered", "duplicates", "capped"})."""
-    n = len(sources)
-    bx, by = float(box_origin[0]), float(box_origin[1])
-    comp, index, ndup = render_selection(sources, fit_rows, blend_rows) if n else (np.zeros((0, 6)), np.zeros((0, 2), np.int64), 0)
-    rows, model, resid = det.render_gaussians(img_dev, comp, nsigma, bkg_dev)
-    if n:
-        boxes = boxes_of(sources) - np.array([bx, by, bx, by], np.float64)
-        bkg = np.array([s["bkg_map" if use_map else "bkg"] for s in sources], np.float64)
-        raw = det.measure_residuals(img_dev, model, boxes, bkg, masks)
-        annotate_residuals(sources, raw, index, rows, beam_area, box_origin, use_map)
-    stats = {"rendered": int(np.isin(rows[:, 0], (0.0, 2.0)).sum()), "duplicates": ndup, "capped": int((rows[:, 0] == 2.0).sum())}
-    return model, resid, stats
-
-
-def save_residual_maps(model, resid, catalog_path):
-    """--save_residual_maps: the two device maps written as fp32 FITS images model_<name>.fits / resid_<name>.fits beside the
-    catalog file, <name> = the catalog's file name without its extension.  -> the two paths."""
-    import os
+def _save_maps(tags, maps, catalog_path):
+    """Two device maps written as fp32 FITS images <tag><name>.fits beside the catalog file, <name> = the catalog's file name
+    without its extension.  -> the two paths."""
     from . import utils
     d, name = os.path.split(catalog_path)
     name = os.path.splitext(name)[0]
-    paths = []
-    for tag, m in zip(("model_", "resid_"), (model, resid)):
-        paths.append(os.path.join(d, tag + name + ".fits"))
-        utils.write_fits_image(paths[-1], m.cpu().numpy())
-    return tuple(paths)
+    paths = tuple(os.path.join(d, tag + name + ".fits") for tag in tags)
+    for path, m in zip(paths, maps):
+        utils.write_fits_image(path, m.cpu().numpy())
+    return paths
+
+
+def save_residual_maps(model, resid, catalog_path):
+    """--save_residual_maps: model_<name>.fits / resid_<name>.fits beside the catalog file (_save_maps).  -> the two paths."""
+    return _save_maps(("model_", "resid_"), (model, resid), catalog_path)
 
 
 def deblend_config(config):
@@ -716,11 +596,11 @@ def fill_mesh(raw, min_pix=64):
     raw = np.asarray(raw, np.float64)
     ncy, ncx = raw.shape[:2]
     mesh = np.zeros((ncy, ncx, 2), np.float64)
-    ok = raw[:, :, 1] >= float(min_pix)
+    ok = raw[:, :, BKG.n] >= float(min_pix)
     dy, dx = np.nonzero(ok)                                  # row-major order: the first minimum is the smallest index
     if dy.size == 0:
         return mesh, 0
-    mesh[ok] = raw[:, :, 2:4][ok]
+    mesh[ok] = raw[:, :, [BKG.bkg, BKG.rms]][ok]
     uy, ux = np.nonzero(~ok)
     for i in range(0, uy.size, 256):
         d = (uy[i:i + 256, None] - dy[None, :]) ** 2 + (ux[i:i + 256, None] - dx[None, :]) ** 2
@@ -773,31 +653,201 @@ def annotate_background(sources, mesh, cell, origin=(0, 0)):
     return sources
 
 
-def background_and_annotate(det, img_dev, sources, cell=128, k=3.0, niter=3, min_pix=64, box_origin=(0, 0)):
-    """The background step, after measure_and_annotate on the same sources and image: one cy_measure_background call, fill_mesh(),
-    annotate_background().  -> (filled mesh [ncy, ncx, 2], number of defined cells); box_origin as in measure_and_annotate."""
-    raw = det.measure_background(img_dev, cell=cell, k=k, niter=niter)
-    mesh, ndef = fill_mesh(raw, min_pix)
-    annotate_background(sources, mesh, cell, box_origin)
-    return mesh, ndef
-
-
 def save_background_maps(det, mesh, cell, shape, catalog_path):
-    """--save_bkg_maps: the mesh expanded on the GPU (HipDetector.expand_background) and written as fp32 FITS images
-    bkg_<name>.fits / rms_<name>.fits beside the catalog file, <name> = the catalog's file name without its extension.
-    -> the two paths."""
-    import os
-    from . import utils
-    d, name = os.path.split(catalog_path)
-    name = os.path.splitext(name)[0]
-    paths = []
-    for tag, m in zip(("bkg_", "rms_"), det.expand_background(mesh, cell, shape)):
-        paths.append(os.path.join(d, tag + name + ".fits"))
-        utils.write_fits_image(paths[-1], m.cpu().numpy())
-    return tuple(paths)
+    """--save_bkg_maps: the mesh expanded on the GPU (HipDetector.expand_background) and written as bkg_<name>.fits /
+    rms_<name>.fits beside the catalog file (_save_maps).  -> the two paths."""
+    return _save_maps(("bkg_", "rms_"), det.expand_background(mesh, cell, shape), catalog_path)
 
 
 def background_config(config):
     """(cell, k, niter, min_pix) of --bkg_map from a config dictionary."""
     return (int(config.get('bkg_cell', 128)), float(config.get('bkg_clip_sigma', 3.0)), int(config.get('bkg_clip_iters', 3)),
             int(config.get('bkg_min_pix', 64)))
+
+
+# ---- the chain of steps
+STEPS = ("measure", "background", "islands", "deblend", "fit", "blend", "residual")
+
+
+def plan(config):
+    """The steps a config dictionary (or the parsed arguments of scripts/run.py as a dictionary) asks for, a tuple of names out of
+    STEPS in the order they run.  Every later step implies the ones it builds on: save_residual_maps the residual step, residual
+    and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
+    save_bkg_maps the mesh, which implies the first measurement too."""
+    on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
+                      "residual_map", "save_residual_maps") if config.get(k, False)}
+    residual = bool(on & {"residual_map", "save_residual_maps"})
+    fit = residual or bool(on & {"fit_components", "fit_blends"})
+    deblend = fit or "deblend_islands" in on
+    islands = deblend or "measure_islands" in on
+    background = bool(on & {"bkg_map", "save_bkg_maps"})
+    want = (islands or background or "measure_sources" in on, background, islands, deblend, fit, "fit_blends" in on, residual)
+    return tuple(s for s, w in zip(STEPS, want) if w)
+
+
+class Chain(object):
+    """The measurement steps on one device image img_dev over the catalog dicts `sources`, which they annotate in place.  One
+    method per step of STEPS; a step reads what the earlier ones left on the sources and on this object, so a caller that starts
+    mid-chain (from a catalog that already carries bkg / rms, say) sets what it skipped and calls the later methods only.
+
+    Three frames: the detector is given boxes and start values in the pixels of img_dev and answers in them (boxes, win0, raw,
+    comp, masks, fit_pixel_rows, blend_pixel_rows, model, resid); the catalog's boxes and every position written into it are
+    those pixels + box_origin, the catalog coordinates of pixel [0, 0] of img_dev (fit_rows, blend_rows); sky positions are taken
+    at catalog coordinates + wcs_origin, the position of catalog coordinate (0, 0) in the frame of the WCS."""
+
+    def __init__(self, det, img_dev, sources, config, beam_area=0, wcs=None, box_origin=(0, 0), wcs_origin=(0, 0)):
+        c = config
+        self.det, self.img, self.sources, self.beam_area, self.wcs = det, img_dev, sources, beam_area, wcs
+        self.box_origin, self.wcs_origin = box_origin, wcs_origin
+        self.ring = int(c.get('measure_ring', 8))
+        self.cell, self.clip_sigma, self.clip_iters, self.min_pix = background_config(c)
+        self.k_seed, self.k_merge, self.conn = c.get('island_seed_sigma', 5.0), c.get('island_merge_sigma', 2.5), int(c.get('island_conn', 8))
+        self.k_peak, self.radius = deblend_config(c)
+        self.max_iter, self.nsigma = int(c.get('fit_max_iter', 64)), float(c.get('residual_nsigma', 5.0))
+        self.save_bkg, self.save_residual = bool(c.get('save_bkg_maps', False)), bool(c.get('save_residual_maps', False))
+        self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
+        self.bx, self.by = float(box_origin[0]), float(box_origin[1])
+        self.MH, self.MW = int(img_dev.shape[0]), int(img_dev.shape[1])
+        self.boxes = boxes_of(sources) - np.array([self.bx, self.by, self.bx, self.by], np.float64)
+        self.win0 = np.array([box_window(b, self.MH, self.MW)[:2] for b in self.boxes], np.float64).reshape(-1, 2)
+        self.mesh, self.ndef, self.keep_masks = None, None, True
+        self.raw, self.masks = np.zeros((0, L.CY_DBL_FIELDS)), []
+        self.comp = np.zeros((0, L.CY_DBL_MAX_COMP, L.CY_DBL_COMP_FIELDS))
+        self.fit_rows = self.fit_pixel_rows = np.zeros((0, L.CY_DBL_MAX_COMP, L.CY_FIT_FIELDS), np.float64)
+        self.blend_rows = self.blend_pixel_rows = None
+        self.model = self.resid = self.render_stats = None
+
+    def _moved(self, rows, has, xcols, ycols):
+        """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
+        itself when the two frames are one."""
+        if not (self.bx or self.by):
+            return rows
+        rows = rows.copy()
+        for cols, d in ((xcols, self.bx), (ycols, self.by)):
+            for k in cols:
+                rows[..., k][has] += d
+        return rows
+
+    def _ncomp(self):
+        raw = np.asarray(self.raw, np.float64).reshape(len(self.sources), -1)
+        return np.where(raw[:, DBL.status] == 1.0, 0, raw[:, DBL.ncomp]).astype(np.int32)
+
+    def measure(self):
+        """One cy_measure_sources call, then annotate()."""
+        if not self.sources:
+            return
+        raw = self.det.measure_sources(self.img, self.boxes, ring=self.ring)
+        raw = self._moved(raw, raw[:, MEAS.npix] > 0, (MEAS.x_peak,), (MEAS.y_peak,))
+        if self.bx or self.by:
+            raw[:, MEAS.swx] += self.bx * raw[:, MEAS.sw]
+            raw[:, MEAS.swy] += self.by * raw[:, MEAS.sw]
+        annotate(self.sources, raw, self.beam_area, self.wcs, self.wcs_origin)
+
+    def background(self):
+        """One cy_measure_background call, fill_mesh(), annotate_background(); leaves the filled mesh and the number of defined
+        cells in .mesh / .ndef."""
+        raw = self.det.measure_background(self.img, cell=self.cell, k=self.clip_sigma, niter=self.clip_iters)
+        self.mesh, self.ndef = fill_mesh(raw, self.min_pix)
+        annotate_background(self.sources, self.mesh, self.cell, self.box_origin)
+
+    def islands(self):
+        """Thresholds bkg + k * rms in numpy float64, one cy_measure_islands call, then annotate_islands()."""
+        if not self.sources:
+            return
+        raw = self.det.measure_islands(self.img, self.boxes, island_thresholds(self.sources, self.k_seed, self.k_merge, self.use_map), conn=self.conn)
+        raw = self._moved(raw, raw[:, ISL.npix] > 0, (ISL.xmin, ISL.xmax), (ISL.ymin, ISL.ymax))
+        annotate_islands(self.sources, raw, self.win0 + np.array([self.bx, self.by]), self.beam_area, self.wcs, self.wcs_origin)
+
+    def deblend(self):
+        """One cy_deblend_islands call, then annotate_components(); leaves .raw, .comp and .masks (None unless .keep_masks) as the
+        library gave them."""
+        if not self.sources:
+            return
+        thr4 = deblend_thresholds(self.sources, self.k_seed, self.k_merge, self.k_peak, self.use_map)
+        out = self.det.deblend_islands(self.img, self.boxes, thr4, conn=self.conn, radius=self.radius, return_masks=self.keep_masks)
+        self.raw, self.comp, self.masks = out if self.keep_masks else out + (None,)
+        has = np.arange(self.comp.shape[1])[None, :] < self.raw[:, DBL.ncomp].astype(np.int64)[:, None]
+        annotate_components(self.sources, self.raw, self._moved(self.comp, has, (COMP.x_peak,), (COMP.y_peak,)),
+                            self.win0 + np.array([self.bx, self.by]), self.beam_area, self.wcs, self.wcs_origin)
+
+    def _fit_call(self, entry, start):
+        """cy_fit_components / cy_fit_blends on the component step's masks with the background the thresholds were formed with."""
+        n = len(self.sources)
+        comp = np.asarray(self.comp, np.float64).reshape(n, -1, L.CY_DBL_COMP_FIELDS)
+        bkg, ncomp = _bkg_of(self.sources, self.use_map), self._ncomp()
+        rows = entry(self.img, self.boxes, bkg, ncomp, start(comp, bkg, self.win0), self.masks, max_iter=self.max_iter)
+        return rows, np.arange(rows.shape[1])[None, :] < ncomp[:, None]
+
+    def fit(self):
+        """fit_start(), one cy_fit_components call, then annotate_fits(); leaves .fit_pixel_rows and .fit_rows."""
+        if not self.sources:
+            return
+        rows, below = self._fit_call(self.det.fit_components, fit_start)
+        self.fit_pixel_rows = rows
+        self.fit_rows = self._moved(rows, below & (rows[:, :, FIT.status] != 1.0), (FIT.x0,), (FIT.y0,))
+        annotate_fits(self.sources, self.fit_rows, self.beam_area, self.wcs, self.wcs_origin, self.use_map)
+
+    def blend(self):
+        """blend_start() from .fit_pixel_rows, one cy_fit_blends call, then annotate_blends(); leaves .blend_pixel_rows and
+        .blend_rows."""
+        self.blend_rows = self.blend_pixel_rows = np.zeros((0, L.CY_DBL_MAX_COMP, L.CY_BLEND_FIELDS), np.float64)
+        if not self.sources:
+            return
+        fit_rows = np.asarray(self.fit_pixel_rows, np.float64).reshape(len(self.sources), -1, L.CY_FIT_FIELDS)
+        rows, below = self._fit_call(self.det.fit_blends, lambda comp, bkg, win0: blend_start(fit_rows, comp, bkg, win0))
+        self.blend_pixel_rows = rows
+        self.blend_rows = self._moved(rows, below & np.isin(rows[:, :, BLEND.status], (0.0, 2.0, 3.0, 4.0, 5.0)), (BLEND.x0,), (BLEND.y0,))
+        annotate_blends(self.sources, self.blend_rows, self.beam_area, self.wcs, self.wcs_origin, self.use_map)
+
+    def residual(self):
+        """render_selection() on the pixel rows, one cy_render_gaussians call over the whole image (minus the expanded mesh when
+        there is one: else the residual keeps the background), one cy_measure_residuals call, then annotate_residuals(); leaves
+        the device maps .model / .resid and .render_stats {"rendered", "duplicates", "capped"}."""
+        src = self.sources
+        comp, index, ndup = np.zeros((0, 6)), np.zeros((0, 2), np.int64), 0
+        if src:
+            comp, index, ndup = render_selection(src, self.fit_pixel_rows, self.blend_pixel_rows)
+        bkg_dev = self.det.expand_background(self.mesh, self.cell, self.img.shape, want=("bkg",))[0] if self.use_map else None
+        rows, self.model, self.resid = self.det.render_gaussians(self.img, comp, self.nsigma, bkg_dev)
+        if src:
+            raw = self.det.measure_residuals(self.img, self.model, self.boxes, _bkg_of(src, self.use_map), self.masks)
+            annotate_residuals(src, raw, index, rows, self.beam_area, self.box_origin, self.use_map)
+        st = rows[:, RND.status]
+        self.render_stats = {"rendered": int(np.isin(st, _FITTED).sum()), "duplicates": ndup, "capped": int((st == 2.0).sum())}
+
+    def run(self, steps, stats=None, t0=None):
+        """The steps named in `steps` (plan()) in the order of STEPS.  stats: a dictionary that takes, per step that ran, <step>_ms
+        (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
+        det, src = self.det, self.sources
+        self.keep_masks = "fit" in steps                     # the component step hands its masks on only when a step reads them
+        for step in STEPS:
+            if step not in steps:
+                continue
+            t1 = t0 if (step == "measure" and t0 is not None) else time.time()
+            getattr(self, step)()
+            if stats is None:
+                continue
+            stats[step + "_ms"] = 1e3 * (time.time() - t1)
+            if step == "background":
+                stats["background_kernel_ms"] = det.background_kernel_ms()
+            elif step == "fit":
+                stats["fit_kernel_ms"] = max(det.fit_kernel_ms(), 0.0) if src else 0.0
+                stats["fit_jobs"], stats["fit_niter_mean"], stats["fit_niter_max"] = fit_iterations(self.fit_rows)
+            elif step == "blend":
+                stats["blend_kernel_ms"] = max(det.blend_kernel_ms(), 0.0) if src else 0.0
+                stats["blend_jobs"], stats["blend_niter_mean"], stats["blend_niter_max"], stats["blend_over_limit"] = blend_stats(self.blend_rows)
+            elif step == "residual":
+                stats["render_kernel_ms"] = det.render_kernel_ms()
+                stats["residual_kernel_ms"] = det.residual_kernel_ms() if src else 0.0
+                for k, v in self.render_stats.items():
+                    stats["residual_" + k] = v
+            else:
+                stats[step + "_kernel_ms"] = getattr(det, step + "_kernel_ms")() if src else 0.0
+        return self
+
+    def save_maps(self, catalog_path):
+        """--save_bkg_maps / --save_residual_maps, after run(): the maps of the mesh and of the residual step beside the catalog."""
+        if self.save_bkg:
+            save_background_maps(self.det, self.mesh, self.cell, self.img.shape, catalog_path)
+        if self.save_residual:
+            save_residual_maps(self.model, self.resid, catalog_path)

@@ -59,6 +59,7 @@ from caesar_yolo_amd.config import CONFIG                                     # 
 from caesar_yolo_amd.preprocessing import (DataPreprocessor, BkgSubtractor, SigmaClipShifter, SigmaClipper, ChanResizer,  # noqa: E402
                                            ZScaleTransformer, Chan3Trasformer, MinMaxNormalizer)
 from caesar_yolo_amd.inference import SFinder                                 # noqa: E402
+from caesar_yolo_amd.measure import plan                                      # noqa: E402
 from caesar_yolo_amd.model import YOLO                                        # noqa: E402
 
 logging.basicConfig(format="%(asctime)-15s %(levelname)s - %(message)s", datefmt='%Y-%m-%d %H:%M:%S')
@@ -167,16 +168,9 @@ def parse_args(argv=None):
                    help='write the model and residual maps as model_<catalog name>.fits / resid_<catalog name>.fits beside the catalog '
                         '(implies --residual_map)')
     args = p.parse_args(argv)
-    if args.save_residual_maps:
-        args.residual_map = True
-    if args.residual_map:
-        args.fit_components = True
-    if args.fit_blends:
-        args.fit_components = True
-    if args.fit_components:
-        args.deblend_islands = True
-    if args.deblend_islands:
-        args.measure_islands = True
+    steps = plan(vars(args))                                  # the "implies" of the switches above: one rule, measure.plan
+    args.measure_sources, args.bkg_map, args.measure_islands = "measure" in steps, "background" in steps, "islands" in steps
+    args.deblend_islands, args.fit_components, args.residual_map = "deblend" in steps, "fit" in steps, "residual" in steps
     if args.deblend_peak_sigma is None:
         args.deblend_peak_sigma = args.island_seed_sigma
     return args
@@ -248,6 +242,16 @@ def build_preprocessor(args):
     return DataPreprocessor(st)
 
 
+MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_seed_sigma', 'island_merge_sigma', 'island_conn', 'deblend_islands',
+                'deblend_peak_sigma', 'deblend_radius', 'fit_components', 'fit_max_iter', 'fit_blends', 'residual_map', 'residual_nsigma',
+                'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps')
+
+
+def measure_config(args):
+    """The CONFIG entries of the measurement steps: the parsed arguments of the same names (parse_args set the implied ones)."""
+    return {k: getattr(args, k) for k in MEASURE_KEYS}
+
+
 def main(argv=None):
     args = parse_args(argv)
     if validate_args(args) < 0:
@@ -275,16 +279,8 @@ def main(argv=None):
               'save_plot': args.save_plots,
               'save_tile_catalog': args.save_tile_catalog, 'save_tile_region': args.save_tile_region,
               'save_tile_img': args.save_tile_img,
-              'precision': args.precision, 'augment': args.augment,
-              'measure_sources': args.measure_sources or args.measure_islands or args.bkg_map or args.save_bkg_maps,
-              'measure_ring': args.measure_ring,
-              'measure_islands': args.measure_islands, 'island_seed_sigma': args.island_seed_sigma,
-              'island_merge_sigma': args.island_merge_sigma, 'island_conn': args.island_conn,
-              'deblend_islands': args.deblend_islands, 'deblend_peak_sigma': args.deblend_peak_sigma, 'deblend_radius': args.deblend_radius,
-              'fit_components': args.fit_components, 'fit_max_iter': args.fit_max_iter, 'fit_blends': args.fit_blends,
-              'residual_map': args.residual_map, 'residual_nsigma': args.residual_nsigma, 'save_residual_maps': args.save_residual_maps,
-              'bkg_map': args.bkg_map or args.save_bkg_maps, 'bkg_cell': args.bkg_cell, 'bkg_clip_sigma': args.bkg_clip_sigma,
-              'bkg_clip_iters': args.bkg_clip_iters, 'bkg_min_pix': args.bkg_min_pix, 'save_bkg_maps': args.save_bkg_maps})
+              'precision': args.precision, 'augment': args.augment})
+    C.update(measure_config(args))
     model = YOLO(args.weights, precision=args.precision, max_batch=args.tile_batch if args.split_img_in_tiles else 1,
                  max_imgsz=max(args.imgsize, 32))
     sfinder = SFinder(model, C)

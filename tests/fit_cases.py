@@ -197,7 +197,7 @@ def random_thresholds(img, boxes):
 
 
 def random_inputs(img, boxes, thr4, rows, comp):
-    """(bkg, ncomp, start) of the fit from the component step's rows, as measure.fit_and_annotate forms them."""
+    """(bkg, ncomp, start) of the fit from the component step's rows, as measure.Chain.fit forms them."""
     win0 = np.array([box_window(b, img.shape[0], img.shape[1])[:2] for b in boxes], np.float64).reshape(-1, 2)
     return thr4[:, 2].copy(), rows[:, 3].astype(np.int32), measure.fit_start(comp, thr4[:, 2], win0)
 

@@ -1,6 +1,6 @@
 """--fit_blends end to end through scripts/run.py on the 2048 x 2048 synthetic FITS mosaic of tests/test_gpu_fit_cli.py (same
 recipe), tiled and serial, each with and without --bkg_map.  Every component carries measure.BLEND_KEYS; their values equal a
-direct deblend_and_annotate(return_raw=True) + fit_and_annotate + blends_and_annotate on the written catalog's boxes (the kernels
+the deblend, fit and blend steps of a measure.Chain started on the written catalog's boxes (the kernels
 are deterministic and the host arithmetic is the same code, so equal means equal); a --fit_components run writes the catalog the
 --fit_blends run writes with the blend_ keys deleted, byte for byte; and a run without the switch has no blend_ms in its stats."""
 import copy
@@ -46,11 +46,13 @@ def _direct(sources, img, beam, wcs, origin, use_map, k_seed=5.0, k_merge=2.5, k
     dev = det.mosaic_to_device(np.ascontiguousarray(img))
     torch.cuda.synchronize()
     want = copy.deepcopy(_strip(sources, measure.COMPONENT_KEYS))
-    _, raw, comp, masks = measure.deblend_and_annotate(det, dev, want, k_seed, k_merge, k_peak, conn, radius, beam, wcs, wcs_origin=origin,
-                                                       use_map=use_map, return_raw=True)
-    rows = measure.fit_and_annotate(det, dev, want, raw, comp, masks, beam, wcs, wcs_origin=origin, use_map=use_map, max_iter=max_iter)
-    brows = measure.blends_and_annotate(det, dev, want, raw, comp, masks, rows, beam, wcs, wcs_origin=origin, use_map=use_map, max_iter=max_iter)
-    return want, brows
+    config = {"bkg_map": use_map, "island_seed_sigma": k_seed, "island_merge_sigma": k_merge, "deblend_peak_sigma": k_peak, "island_conn": conn,
+              "deblend_radius": radius, "fit_max_iter": max_iter}
+    chain = measure.Chain(det, dev, want, config, beam, wcs, wcs_origin=origin)
+    chain.deblend()
+    chain.fit()
+    chain.blend()
+    return want, chain.blend_rows
 
 
 def _check(sources, want, brows):

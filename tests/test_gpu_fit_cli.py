@@ -1,6 +1,6 @@
 """--fit_components end to end through scripts/run.py on the 2048 x 2048 synthetic FITS mosaic of tests/test_gpu_islands_cli.py
 (same recipe), tiled and serial, each with and without --bkg_map.  Every component carries measure.FIT_KEYS; their values equal
-a direct deblend_and_annotate(return_raw=True) + fit_and_annotate on the written catalog's boxes (the kernels are deterministic and
+the deblend and fit steps of a measure.Chain started on the written catalog's boxes (the kernels are deterministic and
 the host arithmetic is the same code, so equal means equal); and a run with only --deblend_islands writes the catalog the
 --fit_components run writes with the fit_ keys deleted, byte for byte: the switch adds keys and changes nothing else."""
 import copy
@@ -46,10 +46,12 @@ def _direct(sources, img, beam, wcs, origin, use_map, k_seed=5.0, k_merge=2.5, k
     dev = det.mosaic_to_device(np.ascontiguousarray(img))
     torch.cuda.synchronize()
     want = copy.deepcopy(_strip(sources, measure.COMPONENT_KEYS))
-    _, raw, comp, masks = measure.deblend_and_annotate(det, dev, want, k_seed, k_merge, k_peak, conn, radius, beam, wcs, wcs_origin=origin,
-                                                       use_map=use_map, return_raw=True)
-    rows = measure.fit_and_annotate(det, dev, want, raw, comp, masks, beam, wcs, wcs_origin=origin, use_map=use_map, max_iter=max_iter)
-    return want, rows
+    config = {"bkg_map": use_map, "island_seed_sigma": k_seed, "island_merge_sigma": k_merge, "deblend_peak_sigma": k_peak, "island_conn": conn,
+              "deblend_radius": radius, "fit_max_iter": max_iter}
+    chain = measure.Chain(det, dev, want, config, beam, wcs, wcs_origin=origin)
+    chain.deblend()
+    chain.fit()
+    return want, chain.fit_rows
 
 
 def _check(sources, want, rows):

@@ -2,7 +2,7 @@
 tests/test_gpu_islands_cli.py at half the side: the smallest on which the catalog has a joint fit and a duplicated peak; both counts
 are asserted, so that nothing here passes emptily), tiled and serial, with --fit_blends and --bkg_map.
   - the --residual_map catalog with the new keys deleted equals the --fit_blends catalog byte for byte
-  - the saved FITS maps and the new keys equal a direct deblend / fit / blend / residuals_and_annotate call on the catalog's boxes
+  - the saved FITS maps and the new keys equal the deblend, fit, blend and residual steps of a measure.Chain started on the catalog's boxes
     (the kernels are deterministic and the host arithmetic is the same code, so equal means equal)
   - model + resid + bkg == image on valid pixels to within the two fp32 roundings: |sum - v| <= 2^-24 (|model| + |resid|) (1 + 2^-20)
     + 2^-148, the sum taken in float64
@@ -81,15 +81,12 @@ def _direct(sources, img, beam, wcs, origin, cell):
     dev = det.mosaic_to_device(np.ascontiguousarray(img))
     torch.cuda.synchronize()
     want = _without(sources)
-    mesh, _ = measure.fill_mesh(det.measure_background(dev, cell=cell, k=3.0, niter=3), 64)
-    bkg_dev = det.expand_background(mesh, cell, dev.shape, want=("bkg",))[0]
-    _, raw, comp, masks = measure.deblend_and_annotate(det, dev, want, 5.0, 2.5, 5.0, 8, 2, beam, wcs, wcs_origin=origin, use_map=True,
-                                                       return_raw=True)
-    _, prow = measure.fit_and_annotate(det, dev, want, raw, comp, masks, beam, wcs, wcs_origin=origin, use_map=True, return_pixel_rows=True)
-    _, brow = measure.blends_and_annotate(det, dev, want, raw, comp, masks, prow, beam, wcs, wcs_origin=origin, use_map=True,
-                                          return_pixel_rows=True)
-    model, resid, stats = measure.residuals_and_annotate(det, dev, want, masks, prow, brow, 5.0, bkg_dev, beam, use_map=True)
-    return want, model.cpu().numpy(), resid.cpu().numpy(), bkg_dev.cpu().numpy(), dev.cpu().numpy(), stats
+    chain = measure.Chain(det, dev, want, {"bkg_map": True, "bkg_cell": cell}, beam, wcs, wcs_origin=origin)
+    chain.mesh, _ = measure.fill_mesh(det.measure_background(dev, cell=cell, k=3.0, niter=3), 64)      # the mesh alone: bkg_map / rms_map stay the catalog's
+    bkg_dev = det.expand_background(chain.mesh, cell, dev.shape, want=("bkg",))[0]
+    for step in ("deblend", "fit", "blend", "residual"):
+        getattr(chain, step)()
+    return want, chain.model.cpu().numpy(), chain.resid.cpu().numpy(), bkg_dev.cpu().numpy(), dev.cpu().numpy(), chain.render_stats
 
 
 def _check(sources, d, name, img, beam, wcs, origin, cell):

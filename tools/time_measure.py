@@ -93,19 +93,8 @@ def main():
 
     def timed(self):
         rc = orig(self)
-        seen.append({"run_ms": 1e3 * self.runtime, "sources": len(self.sources["sources"]),
-                     "measure_ms": self.stats.get("measure_ms"), "kernel_ms": self.stats.get("measure_kernel_ms"),
-                     "islands_ms": self.stats.get("islands_ms"), "islands_kernel_ms": self.stats.get("islands_kernel_ms"),
-                     "background_ms": self.stats.get("background_ms"), "background_kernel_ms": self.stats.get("background_kernel_ms"),
-                     "deblend_ms": self.stats.get("deblend_ms"), "deblend_kernel_ms": self.stats.get("deblend_kernel_ms"),
-                     "fit_ms": self.stats.get("fit_ms"), "fit_kernel_ms": self.stats.get("fit_kernel_ms"), "fit_jobs": self.stats.get("fit_jobs"),
-                     "fit_niter_mean": self.stats.get("fit_niter_mean"), "fit_niter_max": self.stats.get("fit_niter_max"),
-                     "blend_ms": self.stats.get("blend_ms"), "blend_kernel_ms": self.stats.get("blend_kernel_ms"),
-                     "blend_jobs": self.stats.get("blend_jobs"), "blend_niter_mean": self.stats.get("blend_niter_mean"),
-                     "blend_niter_max": self.stats.get("blend_niter_max"), "blend_over_limit": self.stats.get("blend_over_limit"),
-                     "residual_ms": self.stats.get("residual_ms"), "render_kernel_ms": self.stats.get("render_kernel_ms"),
-                     "residual_kernel_ms": self.stats.get("residual_kernel_ms"), "residual_rendered": self.stats.get("residual_rendered"),
-                     "residual_duplicates": self.stats.get("residual_duplicates"), "residual_capped": self.stats.get("residual_capped")})
+        seen.append(dict({k: v for k, v in self.stats.items() if isinstance(v, (int, float))}, run_ms=1e3 * self.runtime,
+                         sources=len(self.sources["sources"]), kernel_ms=self.stats.get("measure_kernel_ms")))
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -121,19 +110,22 @@ def main():
         cwd = os.getcwd()
         os.chdir(d)
         try:
-            variants = [("off", base)] + ([] if args.off_only else [("on", base + on)])
-            if not (args.off_only or args.no_bkg):
-                variants.append(("bkg", base + on + ["--bkg_map"]))
-            if not (args.off_only or args.no_deblend):         # --deblend_islands implies the island step: both steps on the same boxes
-                variants.append(("deblend", base + on + ["--deblend_islands"]))
-            if not (args.off_only or args.no_deblend or args.no_fit):       # --fit_components implies the component step
-                variants.append(("fit", base + on + ["--fit_components"]))
-                if not args.no_blend:                         # --fit_blends implies the fit step
-                    variants.append(("blend", base + on + ["--fit_blends"]))
-                    if not args.no_residual:                  # --residual_map on top of the joint fits
-                        variants.append(("residual", base + on + ["--fit_blends", "--residual_map"]))
-            if not (args.off_only or args.no_islands):         # the last one: its catalog is read below
-                variants.append(("islands", base + on + ["--measure_islands"]))
+            # variant -> (extra flags, timed keys, count keys); every switch implies the steps before it (measure.plan), so a variant
+            # also reports the step its own builds on.  "islands" is the last one: its catalog is read below
+            table = {"on": ([], (), ()),
+                     "bkg": (["--bkg_map"], ("background_ms", "background_kernel_ms"), ()),
+                     "deblend": (["--deblend_islands"], ("islands_ms", "islands_kernel_ms", "deblend_ms", "deblend_kernel_ms"), ()),
+                     "fit": (["--fit_components"], ("deblend_ms", "deblend_kernel_ms", "fit_ms", "fit_kernel_ms"),
+                             ("fit_jobs", "fit_niter_mean", "fit_niter_max")),
+                     "blend": (["--fit_blends"], ("fit_ms", "fit_kernel_ms", "blend_ms", "blend_kernel_ms"),
+                               ("blend_jobs", "blend_niter_mean", "blend_niter_max", "blend_over_limit")),
+                     "residual": (["--fit_blends", "--residual_map"], ("blend_ms", "residual_ms", "render_kernel_ms", "residual_kernel_ms"),
+                                  ("residual_rendered", "residual_duplicates", "residual_capped")),
+                     "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
+            skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
+                    "blend": args.no_deblend or args.no_fit or args.no_blend,
+                    "residual": args.no_deblend or args.no_fit or args.no_blend or args.no_residual, "islands": args.no_islands}
+            variants = [("off", base)] + [(name, base + on + t[0]) for name, t in table.items() if not (args.off_only or skip.get(name))]
             for name, argv in variants:                    # warm-up of each variant
                 assert run.main(argv) == 0
             seen.clear()
@@ -145,50 +137,21 @@ def main():
             for name, rows in got.items():
                 res[name] = {"run_ms": [round(r["run_ms"], 1) for r in rows], "run_ms_median": statistics.median(r["run_ms"] for r in rows),
                              "sources": rows[0]["sources"]}
-                if name == "islands":
-                    for k in ("islands_ms", "islands_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                if name == "deblend":
-                    for k in ("islands_ms", "islands_kernel_ms", "deblend_ms", "deblend_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                if name == "bkg":
-                    for k in ("background_ms", "background_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                if name == "fit":
-                    for k in ("deblend_ms", "deblend_kernel_ms", "fit_ms", "fit_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                    res[name].update({k: rows[0][k] for k in ("fit_jobs", "fit_niter_mean", "fit_niter_max")})
-                if name == "blend":
-                    for k in ("fit_ms", "fit_kernel_ms", "blend_ms", "blend_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                    res[name].update({k: rows[0][k] for k in ("blend_jobs", "blend_niter_mean", "blend_niter_max", "blend_over_limit")})
-                if name == "residual":
-                    for k in ("blend_ms", "residual_ms", "render_kernel_ms", "residual_kernel_ms"):
-                        res[name][k] = [round(r[k], 3) for r in rows]
-                        res[name][k + "_median"] = statistics.median(r[k] for r in rows)
-                    res[name].update({k: rows[0][k] for k in ("residual_rendered", "residual_duplicates", "residual_capped")})
-                if name in ("on", "islands", "bkg", "deblend", "fit", "blend", "residual"):
-                    res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
-                    res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
-                    res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
-                    res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
-            if "on" in got:
-                res["added_ms"] = res["on"]["run_ms_median"] - res["off"]["run_ms_median"]
-            if "fit" in got:
-                res["fit_added_ms"] = res["fit"]["run_ms_median"] - res["off"]["run_ms_median"]
-            if "blend" in got:
-                res["blend_added_ms"] = res["blend"]["run_ms_median"] - res["off"]["run_ms_median"]
-            if "residual" in got:
-                res["residual_added_ms"] = res["residual"]["run_ms_median"] - res["off"]["run_ms_median"]
-            if "deblend" in got:
-                res["deblend_added_ms"] = res["deblend"]["run_ms_median"] - res["off"]["run_ms_median"]
+                if name == "off":
+                    continue
+                for k in table[name][1]:
+                    res[name][k] = [round(r[k], 3) for r in rows]
+                    res[name][k + "_median"] = statistics.median(r[k] for r in rows)
+                res[name].update({k: rows[0][k] for k in table[name][2]})
+                res[name]["measure_ms"] = [round(r["measure_ms"], 2) for r in rows]
+                res[name]["measure_ms_median"] = statistics.median(r["measure_ms"] for r in rows)
+                res[name]["kernel_ms"] = [round(r["kernel_ms"], 3) for r in rows]
+                res[name]["kernel_ms_median"] = statistics.median(r["kernel_ms"] for r in rows)
+            for name, key in (("on", "added_ms"), ("fit", "fit_added_ms"), ("blend", "blend_added_ms"), ("residual", "residual_added_ms"),
+                              ("deblend", "deblend_added_ms"), ("bkg", "bkg_added_ms")):
+                if name in got:
+                    res[key] = res[name]["run_ms_median"] - res["off"]["run_ms_median"]
             if "bkg" in got:
-                res["bkg_added_ms"] = res["bkg"]["run_ms_median"] - res["off"]["run_ms_median"]
                 res.update(background_kernels(img, args.runs, args.host_ref))
             if "islands" in got:                            # read before the next variant overwrites the catalog: it was the last to run
                 from caesar_yolo_amd import measure

@@ -364,6 +364,20 @@ struct ResidualArgs {
 };
 hipError_t launch_residual_stats(const ResidualArgs& a, hipStream_t s);
 
+// ---- residual peaks (cy_peaks.hip) -----------------------------------------------------------------
+// PEAK_FIELDS, PEAK_RADIUS_MAX, PEAK_SEG, PEAK_SEG_WORDS, PEAK_MAX_SEG: cy_measure_jobs.h
+struct PeakArgs {
+    const float* map; const float* rms; int MH, MW;   // two maps of one shape; MH * MW < 2^31
+    double k_sigma; int radius, sign;                 // k_sigma > 0; radius 1 .. PEAK_RADIUS_MAX; sign +1 or -1
+    int nsx, nseg;                  // segments of a row (ceil(MW / PEAK_SEG)) and of the image (MH * nsx <= PEAK_MAX_SEG); nsx * PEAK_SEG + radius fits int
+    unsigned* count;                // [nseg] peaks of every segment (count pass)
+    unsigned* offset;               // [nseg] peaks of the segments before it (scan pass)
+    unsigned long long* bits;       // [nseg][PEAK_SEG_WORDS] peak bitmap (count pass): word 4 w + j, bit l = pixel 4 (64 w + l) + j of the segment
+    long long* total;               // [1] peaks of the image (scan pass)
+    double* rows; int cap;          // [cap][PEAK_FIELDS]; cap == 0: the fill pass is not launched
+};
+hipError_t launch_peaks(const PeakArgs& a, hipStream_t s);     // the three passes, queued in order
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

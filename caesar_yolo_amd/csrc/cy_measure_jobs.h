@@ -18,6 +18,12 @@ constexpr int RND_TILE = 32;                   // side of an image tile of the r
 constexpr int RND_MAX_COMP = 1 << 20;          // most components of one cy_render_gaussians call
 constexpr long long RND_MAX_LIST = 1LL << 27;  // most entries of its tile table
 constexpr int RES_FIELDS = 12;                 // CY_RES_FIELDS
+constexpr int PEAK_FIELDS = 12;                // CY_PEAK_FIELDS
+constexpr int PEAK_RADIUS_MAX = 8;             // CY_PEAK_RADIUS_MAX
+constexpr int PEAK_CAP_MAX = 1 << 20;          // CY_PEAK_CAP_MAX
+constexpr int PEAK_SEG = 1024;                 // pixels of a segment of the peak search: one workgroup of 256 threads, four pixels each
+constexpr int PEAK_SEG_WORDS = PEAK_SEG / 64;  // 64-bit words of a segment's peak bitmap
+constexpr long long PEAK_MAX_SEG = 1LL << 24;  // most segments of one cy_find_peaks call
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list

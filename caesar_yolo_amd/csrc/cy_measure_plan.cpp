@@ -264,6 +264,19 @@ const char* plan_residuals(const double* boxes, const long long* mask_off, int n
     return plan_islands(boxes, no_thr, 0, mask_off, n, MH, MW, t);
 }
 
+const char* plan_peaks(int MH, int MW, int radius, int cap, PeakPlan& p) {
+    p = PeakPlan();
+    if ((long long)MH * MW >= (1LL << 31)) return "image of 2^31 pixels or more (32-bit pixel indices and peak counts)";
+    p.nsx = (int)(((long long)MW + PEAK_SEG - 1) / PEAK_SEG);
+    // the kernels hold columns in int: the last column a thread of the last segment names, plus the radius, has to fit
+    if ((long long)p.nsx * PEAK_SEG + radius > 2147483647LL) return "row too wide (its last segment ends beyond column 2^31 - 1 - radius)";
+    p.nseg = (long long)MH * p.nsx;
+    if (p.nseg > PEAK_MAX_SEG) return "segment table above 2^24 entries";
+    p.words = p.nseg * PEAK_SEG_WORDS;
+    p.row_values = (long long)cap * PEAK_FIELDS;
+    return nullptr;
+}
+
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
     for (int r = 0; r < nrows; ++r) {
         const size_t row = (size_t)rows[r];

@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -63,6 +63,19 @@ const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW
 // cy_measure_residuals: the box windows and checked mask offsets, as plan_islands gives them (off[i][0] is ISL_OFF_TOO_LARGE for a
 // window above ISL_MAX_AREA pixels, off[i][1] the window's first mask byte)
 const char* plan_residuals(const double* boxes, const long long* mask_off, int n, int MH, int MW, IslandTable& t);
+
+// cy_find_peaks.  The image is cut into segments of PEAK_SEG consecutive pixels of one row (the last of a row holds the remaining
+// MW - (nsx - 1) * PEAK_SEG), segment s = iy * nsx + sx, which is the row-major order of their pixels.  Sizes in 64-bit: a
+// (2^24) x 127 image has 2^24 segments of 127 pixels.  Returns the message of a limit: an image of 2^31 pixels or more, more than
+// PEAK_MAX_SEG segments, or a row so wide that a column of its last segment plus the radius leaves the 32-bit range the kernels
+// index columns in.  radius and cap are in range (the entry checks them before).
+struct PeakPlan {
+    int nsx = 0;                        // segments of a row: ceil(MW / PEAK_SEG)
+    long long nseg = 0;                 // MH * nsx: entries of the count table and of the offset table
+    long long words = 0;                // 64-bit words of the peak bitmap: nseg * PEAK_SEG_WORDS
+    long long row_values = 0;           // float64 values of the device row table: cap * PEAK_FIELDS
+};
+const char* plan_peaks(int MH, int MW, int radius, int cap, PeakPlan& p);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

@@ -23,7 +23,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_COUNT };
 
 // Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
 // beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
@@ -99,7 +99,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1372,6 +1372,8 @@ static_assert(CY_BLEND_FIELDS == BLEND_FIELDS && CY_BLEND_MAX_MEMBERS == BLEND_M
 static_assert(CY_BKG_FIELDS == BKG_FIELDS, "header and kernel disagree on the background row");
 static_assert(CY_RND_FIELDS == RND_FIELDS && CY_RND_HALF_MAX == RND_HALF_MAX, "header and planner disagree on the render row");
 static_assert(CY_RES_FIELDS == RES_FIELDS, "header and kernel disagree on the residual row");
+static_assert(CY_PEAK_FIELDS == PEAK_FIELDS && CY_PEAK_RADIUS_MAX == PEAK_RADIUS_MAX && CY_PEAK_CAP_MAX == PEAK_CAP_MAX,
+              "header and kernel disagree on the peak row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1566,6 +1568,35 @@ int cy_measure_residuals(cy_ctx* c, const float* d_img, const float* d_model, in
     return t.run(STEP_RESIDUAL, [&](hipStream_t s) { return launch_residual_stats(a, s); });
 }
 
+int cy_find_peaks(cy_ctx* c, const float* d_map, const float* d_rms, int MH, int MW, double k_sigma, int radius, int sign, int cap,
+                  double* h_rows, long long* h_total, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    if (MH <= 0 || MW <= 0 || radius < 1 || radius > PEAK_RADIUS_MAX || (sign != 1 && sign != -1) || !(k_sigma > 0.0) || !std::isfinite(k_sigma) ||
+        cap < 0 || cap > PEAK_CAP_MAX)
+        return fail(c, CY_ERR_ARG, "MH, MW > 0, 1 <= radius <= 8, sign +1 or -1, a finite k_sigma > 0 and 0 <= cap <= 2^20 required");
+    if (!d_map || !d_rms || !h_total || (cap > 0 && !h_rows)) return fail(c, CY_ERR_ARG, "null argument");
+    PeakPlan p;
+    if (const char* msg = plan_peaks(MH, MW, radius, cap, p)) return fail(c, CY_ERR_ARG, msg);
+    long long total = 0;
+    TimedLaunch t(c, stream);
+    PeakArgs a{};
+    a.map = d_map; a.rms = d_rms; a.MH = MH; a.MW = MW; a.k_sigma = k_sigma; a.radius = radius; a.sign = sign;
+    a.nsx = p.nsx; a.nseg = (int)p.nseg; a.cap = cap;
+    a.count = t.scratch<unsigned>((size_t)p.nseg);                             // every entry of the three tables is written before it is read
+    a.offset = t.scratch<unsigned>((size_t)p.nseg);
+    a.bits = t.scratch<unsigned long long>((size_t)p.words);
+    a.total = t.scratch<long long>(1);
+    a.rows = t.scratch<double>((size_t)p.row_values);
+    t.download(&total, a.total, 1);
+    const int rc = t.run(STEP_PEAKS, [&](hipStream_t s) { return launch_peaks(a, s); });
+    if (rc != CY_OK) return rc;
+    // the rows that exist, and no others: the rest of h_rows stays as it is (the tables live as long as t)
+    const long long nrows = std::min<long long>(total, cap);
+    if (nrows > 0) HIPCHK(c, hipMemcpy(h_rows, a.rows, (size_t)nrows * CY_PEAK_FIELDS * sizeof(double), hipMemcpyDeviceToHost));
+    *h_total = total;
+    return CY_OK;
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1580,6 +1611,7 @@ int cy_blend_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(
 int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_BACKGROUND, out_ms); }
 int cy_render_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RENDER, out_ms); }
 int cy_residual_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RESIDUAL, out_ms); }
+int cy_peaks_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKS, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

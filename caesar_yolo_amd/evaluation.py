@@ -159,6 +159,7 @@ class Analyzer(object):
                 if chain.ndef == 0:
                     logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
                 chain.save_maps(self.outfile_json or ('out_' + str(self.image_id) + '.json'))
+                self.results.update(measure.peak_lists(chain))
             except L.CyError as e:
                 logger.warning("Source measurement failed (err=%s)..." % str(e))
                 return -1

@@ -581,6 +581,7 @@ class SFinder(object):
         if chain.ndef == 0:
             logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
         chain.save_maps(self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
+        return chain
 
     # ---- tiled (reference :578-658)
     def run_parallel(self):
@@ -617,9 +618,9 @@ class SFinder(object):
             self._write_tile_outputs(eng)
             src, self.stats = eng.catalog(self.model.names)
             steps = measure.plan(c)
-            if steps:
-                self._measure(det, mosaic, src, steps)
+            chain = self._measure(det, mosaic, src, steps) if steps else None
             self.sources = {"sources": src}
+            self.sources.update(measure.peak_lists(chain))
             if self.write_to_json:
                 out = self.outfile_json or ('catalog_' + str(self.image_id) + '.json')
                 with open(out, 'w') as fp:

@@ -30,6 +30,8 @@ RND_NAMES = ("status", "sx0", "sx1", "sy0", "sy1", "ntiles", "reserved0", "reser
 CY_RES_FIELDS = 12
 RES_NAMES = ("status", "npix_win", "npix_isl", "sum_win", "sumsq_win", "sum_isl", "sumsq_isl", "maxabs_isl", "x_max", "y_max", "model_isl",
              "reserved")
+CY_PEAK_FIELDS, CY_PEAK_RADIUS_MAX, CY_PEAK_CAP_MAX = 12, 8, 1 << 20
+PEAK_NAMES = ("x", "y", "v", "rms", "snr", "npix", "nabove", "sum", "sw", "swx", "swy", "reserved")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -47,7 +49,7 @@ EXPORTS = [
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
     "cy_measure_islands", "cy_islands_kernel_ms", "cy_measure_background", "cy_background_kernel_ms", "cy_expand_background",
     "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
-    "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms",
+    "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
 ]
 
 
@@ -187,6 +189,8 @@ def load():
         "cy_render_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_residuals": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
         "cy_residual_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_find_peaks": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, dp, C.POINTER(C.c_longlong), vp]),
+        "cy_peaks_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

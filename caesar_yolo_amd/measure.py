@@ -32,6 +32,12 @@ map and forms the residual map; `cy_measure_residuals` (HipDetector.measure_resi
 box and island set, raw rows lib.RND_NAMES / lib.RES_NAMES, keys RESIDUAL_KEYS on every source and RENDER_ITEM_KEYS on every
 component dict (annotate_residuals).
 
+--residual_peaks searches the residual map for what the fitted model does not explain: `cy_find_peaks` (HipDetector.find_peaks)
+lists the local maxima of the residual at or above residual_peaks_sigma times the expanded rms map of the mesh, raw rows
+lib.PEAK_NAMES, a list of dicts with PEAK_KEYS beside the catalog and SOURCE_PEAK_KEYS on every source (annotate_peaks);
+--residual_holes does the same for the negated residual (SOURCE_HOLE_KEYS).  It is not one of STEPS: Chain.run() calls Chain.peaks()
+after them.
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
 plan() names the steps a config asks for and Chain runs them on one image: the one place that knows their order, what each hands to
@@ -52,7 +58,7 @@ def _fields(names):
 
 
 MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
-RND, RES, BKG = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES)
+RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
 _MOMENTS = ("S", "Sx", "Sy", "Sxx", "Syy", "Sxy")
 _COMP_MOMENTS = [getattr(COMP, k) for k in _MOMENTS]
@@ -75,6 +81,8 @@ BLEND_KEYS = ("blend_group", "blend_size", "blend_status", "blend_niter", "blend
               "blend_flux_err")
 RESIDUAL_KEYS = ("res_npix", "res_mean", "res_rms", "res_rms_box", "res_max", "res_x_max", "res_y_max", "res_flux", "res_model_flux", "res_ratio")
 RENDER_ITEM_KEYS = ("rendered", "render_status")
+PEAK_KEYS = ("x_peak", "y_peak", "x", "y", "ra", "dec", "peak", "rms", "snr", "npix", "nabove", "flux_sum", "flux", "in_source")
+SOURCE_PEAK_KEYS, SOURCE_HOLE_KEYS = ("res_npeaks", "res_peak_snr"), ("res_nholes", "res_hole_snr")
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
@@ -565,6 +573,84 @@ def annotate_residuals(sources, raw, index, render_rows, beam_area, origin=(0, 0
     return sources
 
 
+# ---- residual peaks (--residual_peaks, --residual_holes)
+def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0), holes=False):
+    """The peak list of a residual map, and the peak keys of every source.  rows: [n, CY_PEAK_FIELDS] rows of cy_find_peaks with x, y
+    in catalog coordinates, in the library's order; total: the number of peaks it counted (rows holds the first n of them).  A row
+    is kept when nabove >= min_above.  -> a list of dicts (PEAK_KEYS) in decreasing snr, equal snr in row order:
+      x_peak, y_peak   the pixel (ints);  x, y = x_peak + swx / sw, y_peak + swy / sw (sw > 0 at a peak)
+      ra, dec          wcs.wcs_pix2world(x + ox, y + oy, 0), None without a WCS; origin = (ox, oy) as in annotate()
+      peak             the signed value of the residual map;  rms, snr, npix, nabove as in the row
+      flux_sum         the signed sum over the neighbourhood (holes: minus the row's sum, which is taken of the negated map);
+                       flux = flux_sum / beam_area when beam_area > 0, else None
+      in_source        index of the first source whose box contains the peak pixel (x1 <= x_peak <= x2 and y1 <= y_peak <= y2), else None
+    Every source dict gets SOURCE_PEAK_KEYS (holes: SOURCE_HOLE_KEYS): the number of kept peaks inside its box (a peak counts for every
+    box that contains it) and the largest snr among them, None without one."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PEAK_FIELDS)
+    assert int(total) >= rows.shape[0]
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    sign = -1.0 if holes else 1.0
+    kept = rows[rows[:, PEAK.nabove] >= float(min_above)]
+    kept = kept[np.argsort(-kept[:, PEAK.snr], kind="stable")]
+    nkey, skey = SOURCE_HOLE_KEYS if holes else SOURCE_PEAK_KEYS
+    for s in sources:
+        s[nkey], s[skey] = 0, None
+    # which peaks lie in which box: the peaks sorted by column once, then per box a binary search for its columns and a test of the
+    # rows of those few; per peak the first such source, per source the count and the largest snr
+    boxes, n = boxes_of(sources), kept.shape[0]
+    xp, yp, snr = kept[:, PEAK.x], kept[:, PEAK.y], kept[:, PEAK.snr]
+    by_x = np.argsort(xp, kind="stable")
+    xs = xp[by_x]
+    first, count = np.full(n, -1, np.int64), np.zeros(len(sources), np.int64)
+    best = np.full(len(sources), -np.inf, np.float64)
+    for i, (x1, y1, x2, y2) in enumerate(boxes):
+        idx = by_x[np.searchsorted(xs, x1, "left"):np.searchsorted(xs, x2, "right")]
+        idx = idx[(y1 <= yp[idx]) & (yp[idx] <= y2)]
+        if idx.size:
+            count[i], best[i] = idx.size, snr[idx].max()
+            first[idx[first[idx] < 0]] = i                    # boxes come in source order: the first one stays
+    for s, c, m in zip(sources, count, best):
+        s[nkey], s[skey] = int(c), (float(m) if c else None)
+    out = []
+    for r, f in zip(kept, first):
+        xp_, yp_, sw = int(r[PEAK.x]), int(r[PEAK.y]), float(r[PEAK.sw])
+        d = dict.fromkeys(PEAK_KEYS)
+        d["x_peak"], d["y_peak"] = xp_, yp_
+        d["x"], d["y"] = xp_ + float(r[PEAK.swx]) / sw, yp_ + float(r[PEAK.swy]) / sw
+        d["ra"], d["dec"] = _sky(wcs, d["x"], d["y"], ox, oy)
+        d["peak"], d["rms"], d["snr"] = float(r[PEAK.v]), float(r[PEAK.rms]), float(r[PEAK.snr])
+        d["npix"], d["nabove"] = int(r[PEAK.npix]), int(r[PEAK.nabove])
+        d["flux_sum"] = sign * float(r[PEAK.sum])
+        if ba > 0.0:
+            d["flux"] = d["flux_sum"] / ba
+        d["in_source"] = int(f) if f >= 0 else None
+        out.append(d)
+    return out
+
+
+def peaks_config(config):
+    """(k_sigma, radius, min_above, cap) of --residual_peaks from a config dictionary."""
+    return (float(config.get('residual_peaks_sigma', 5.0)), int(config.get('residual_peaks_radius', 2)),
+            int(config.get('residual_peaks_min_above', 3)), int(config.get('residual_peaks_max', 65536)))
+
+
+def wants_peaks(config):
+    """Whether a config asks for the search of the residual map (residual_peaks or residual_holes)."""
+    return bool(config.get('residual_peaks', False) or config.get('residual_holes', False))
+
+
+def peak_lists(chain):
+    """What a catalog file carries beside its sources after Chain.run(): {"residual_peaks": [...]} and, when holes were searched,
+    "residual_holes"; empty when the chain (or None) did not search."""
+    out = {}
+    if chain is not None and chain.peak_list is not None:
+        out["residual_peaks"] = chain.peak_list
+    if chain is not None and chain.hole_list is not None:
+        out["residual_holes"] = chain.hole_list
+    return out
+
+
 def _save_maps(tags, maps, catalog_path):
     """Two device maps written as fp32 FITS images <tag><name>.fits beside the catalog file, <name> = the catalog's file name
     without its extension.  -> the two paths."""
@@ -673,14 +759,16 @@ def plan(config):
     """The steps a config dictionary (or the parsed arguments of scripts/run.py as a dictionary) asks for, a tuple of names out of
     STEPS in the order they run.  Every later step implies the ones it builds on: save_residual_maps the residual step, residual
     and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
-    save_bkg_maps the mesh, which implies the first measurement too."""
+    save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
+    step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
-                      "residual_map", "save_residual_maps") if config.get(k, False)}
-    residual = bool(on & {"residual_map", "save_residual_maps"})
+                      "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
+    peaks = bool(on & {"residual_peaks", "residual_holes"})
+    residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
     islands = deblend or "measure_islands" in on
-    background = bool(on & {"bkg_map", "save_bkg_maps"})
+    background = peaks or bool(on & {"bkg_map", "save_bkg_maps"})
     want = (islands or background or "measure_sources" in on, background, islands, deblend, fit, "fit_blends" in on, residual)
     return tuple(s for s, w in zip(STEPS, want) if w)
 
@@ -705,6 +793,8 @@ class Chain(object):
         self.k_peak, self.radius = deblend_config(c)
         self.max_iter, self.nsigma = int(c.get('fit_max_iter', 64)), float(c.get('residual_nsigma', 5.0))
         self.save_bkg, self.save_residual = bool(c.get('save_bkg_maps', False)), bool(c.get('save_residual_maps', False))
+        self.want_peaks, self.want_holes = wants_peaks(c), bool(c.get('residual_holes', False))
+        self.peak_sigma, self.peak_radius, self.peak_min_above, self.peak_cap = peaks_config(c)
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
         self.MH, self.MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -716,6 +806,7 @@ class Chain(object):
         self.fit_rows = self.fit_pixel_rows = np.zeros((0, L.CY_DBL_MAX_COMP, L.CY_FIT_FIELDS), np.float64)
         self.blend_rows = self.blend_pixel_rows = None
         self.model = self.resid = self.render_stats = None
+        self.peak_list = self.hole_list = self.peak_stats = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -815,8 +906,30 @@ class Chain(object):
         st = rows[:, RND.status]
         self.render_stats = {"rendered": int(np.isin(st, _FITTED).sum()), "duplicates": ndup, "capped": int((st == 2.0).sum())}
 
+    def peaks(self):
+        """After residual(): the rms map of the mesh expanded by a call of its own, one cy_find_peaks call on .resid (a second one with
+        sign -1 when holes are wanted), the rows moved to catalog coordinates, then annotate_peaks(); leaves .peak_list, .hole_list
+        (None unless holes are wanted) and .peak_stats {"peaks_ms", "peaks_kernel_ms", "peaks_found", "peaks_kept", "peaks_truncated"}
+        (and their holes_ counterparts; peaks_ms is wall time and includes the expansion of the rms map)."""
+        t1 = time.time()
+        rms_dev = self.det.expand_background(self.mesh, self.cell, self.img.shape, want=("rms",))[1]
+        self.peak_stats = {}
+        for pre, sign in (("peaks_", 1), ("holes_", -1))[:2 if self.want_holes else 1]:
+            rows, total = self.det.find_peaks(self.resid, rms_dev, k_sigma=self.peak_sigma, radius=self.peak_radius, sign=sign, cap=self.peak_cap)
+            kernel_ms = self.det.peaks_kernel_ms()
+            rows = self._moved(rows, np.ones(rows.shape[0], bool), (PEAK.x,), (PEAK.y,))
+            found = annotate_peaks(self.sources, rows, total, self.peak_min_above, self.beam_area, self.wcs, self.wcs_origin, holes=sign < 0)
+            if sign > 0:
+                self.peak_list = found
+            else:
+                self.hole_list = found
+            self.peak_stats.update({pre + "ms": 1e3 * (time.time() - t1), pre + "kernel_ms": kernel_ms, pre + "found": int(total), pre + "kept": len(found),
+                                    pre + "truncated": int(total > rows.shape[0])})
+            t1 = time.time()
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS.  stats: a dictionary that takes, per step that ran, <step>_ms
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks() when the config asks for it and the residual step
+        ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
         self.keep_masks = "fit" in steps                     # the component step hands its masks on only when a step reads them
@@ -843,6 +956,10 @@ class Chain(object):
                     stats["residual_" + k] = v
             else:
                 stats[step + "_kernel_ms"] = getattr(det, step + "_kernel_ms")() if src else 0.0
+        if self.want_peaks and "residual" in steps:
+            self.peaks()
+            if stats is not None:
+                stats.update(self.peak_stats)
         return self
 
     def save_maps(self, catalog_path):

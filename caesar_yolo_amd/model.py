@@ -523,6 +523,27 @@ class HipDetector(object):
         """Kernel time of the last measure_residuals call in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_residual_kernel_ms)
 
+    # ---- residual peaks (after the seventh measurement step)
+    def find_peaks(self, map_dev, rms_dev, k_sigma=5.0, radius=2, sign=1, cap=65536):
+        """The local maxima of sign * map_dev over (2 radius + 1)^2 neighbourhoods that lie at or above k_sigma * rms_dev
+        (cy_find_peaks).  map_dev, rms_dev: contiguous 2-D float32 device maps of one shape: the residual map of render_gaussians and
+        the rms map of expand_background.  -> (rows numpy float64 [min(total, cap), CY_PEAK_FIELDS] (lib.PEAK_NAMES) in increasing
+        (y, x), total: the number of peaks of the whole image)."""
+        MH, MW = self._image_2d(map_dev, "find_peaks")
+        if rms_dev.shape != map_dev.shape or self._image_2d(rms_dev, "find_peaks (rms_dev)") != (MH, MW):
+            raise L.CyError("find_peaks: rms_dev must have the shape of the map")
+        cap = int(cap)
+        rows = np.zeros((max(cap, 0), L.CY_PEAK_FIELDS), np.float64)
+        total = C.c_longlong(0)
+        self._chk(self.lib.cy_find_peaks(self.ctx, self._p(map_dev), self._p(rms_dev), MH, MW, float(k_sigma), int(radius), int(sign), cap,
+                                         rows.ctypes.data_as(C.POINTER(C.c_double)) if cap > 0 else None, C.byref(total), self._stream()))
+        total = int(total.value)
+        return rows[:min(total, cap)].copy(), total
+
+    def peaks_kernel_ms(self):
+        """Kernel time of the last find_peaks call in ms (hipEvents around its launches); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_peaks_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

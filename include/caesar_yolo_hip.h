@@ -529,6 +529,42 @@ int cy_measure_residuals(cy_ctx* ctx, const float* d_img, const float* d_model, 
 /* milliseconds the kernel of the last cy_measure_residuals call took (hipEvents around the launch); -1 before the first call */
 int cy_residual_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- residual peaks (an addition: the local maxima of a map above k_sigma times a noise map) -------------------------------
+ * d_map, d_rms: device fp32 maps [MH][MW]: the residual map of cy_render_gaussians and the rms map of cy_expand_background (any
+ * pair of maps of one shape will do).  Pixel index i = iy * MW + ix, a pixel's centre at its index.
+ *   u(p)       sign * d_map[p], sign +1 or -1 (the negation is exact; -1 finds holes, i.e. over-subtraction)
+ *   valid(p)   u(p) is non-zero and finite (the residual map is 0 on the invalid pixels of the image)
+ *   noisy(p)   d_rms[p] is finite and > 0
+ *   above(p)   valid(p), noisy(p) and (double)u(p) >= k_sigma * (double)d_rms[p]: one float64 product, then the comparison
+ *   rank       p outranks q when u(p) > u(q), or u(p) == u(q) and i(p) < i(q): the rule of cy_deblend_islands, over the whole image
+ *   N(p)       the pixels q of the image with |qx - px| <= radius and |qy - py| <= radius: clipped at the edges, p included
+ *   peak       above(p), and p outranks every valid q of N(p) other than itself (whether q is noisy does not matter here)
+ * h_rows row of a peak, CY_PEAK_FIELDS float64, rows in increasing (y, x), i.e. in increasing pixel index:
+ *   [0] x, [1] y   the pixel
+ *   [2] v = (double)d_map[p] (signed), [3] rms = (double)d_rms[p], [4] snr = (double)u(p) / rms: one division
+ *   [5] npix       valid q of N(p), [6] nabove   q of N(p) with above(q)
+ *   [7] sum        sum of (double)u(q) over the valid q of N(p)
+ *   [8] sw, [9] swx, [10] swy   sums of w, w * (qx - px), w * (qy - py) with w = max((double)u(q), 0) over the valid q of N(p)
+ *                  (the products are exact); sw > 0 at a peak
+ *   [11] reserved (0)
+ * *h_total: the number of peaks of the whole image.  The first min(total, cap) rows are written, the rest of h_rows is left
+ * untouched; cap == 0 only counts (h_rows may then be NULL).  Counts, positions, v, rms and snr do not depend on any order; the four
+ * sums are plain sequential float64 sums over N(p) row by row (two calls give the same bytes).
+ * The image is cut into segments of 1024 consecutive pixels of one row (the last of a row may be shorter), segments in row-major
+ * order.  Three launches: one workgroup per segment tests every pixel and counts the segment's peaks (only a pixel that is above
+ * reads its neighbourhood), one workgroup forms the exclusive prefix sum of the counts, one workgroup per segment writes its rows
+ * at the segment's offset.  No workgroup waits for another, no atomics; synchronous on `stream`.  A null ctx / d_map / d_rms /
+ * h_total, a null h_rows with cap > 0, MH / MW <= 0, radius outside [1, CY_PEAK_RADIUS_MAX], sign not +1 or -1, k_sigma not
+ * finite or <= 0, cap outside [0, CY_PEAK_CAP_MAX], an image of 2^31 pixels or more, one of more than 2^24 segments, or a row whose
+ * last segment plus the radius ends beyond column 2^31 - 1 (MW above 2^31 - 1024): CY_ERR_ARG.  Needs no loaded weights. */
+#define CY_PEAK_FIELDS 12      /* x y v rms snr npix nabove sum sw swx swy reserved */
+#define CY_PEAK_RADIUS_MAX 8
+#define CY_PEAK_CAP_MAX (1 << 20)
+int cy_find_peaks(cy_ctx* ctx, const float* d_map, const float* d_rms, int MH, int MW, double k_sigma, int radius, int sign,
+                  int cap, double* h_rows /* [cap][CY_PEAK_FIELDS] */, long long* h_total, void* stream);
+/* milliseconds the three kernels of the last cy_find_peaks call took (hipEvents around the launches); -1 before the first call */
+int cy_peaks_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

@@ -48,6 +48,13 @@ Differences that come with the MI355X engine:
              component rendered and render_status; with --bkg_map the residual is background-subtracted.  --save_residual_maps
              (implies --residual_map) writes model_<catalog name>.fits / resid_<catalog name>.fits beside the catalog
              (cy_render_gaussians, cy_measure_residuals; DESIGN.md "Model and residual maps").
+  --residual_peaks  (new; implies --residual_map and --bkg_map) the residual map searched for what the model does not explain: its
+             local maxima within --residual_peaks_radius pixels (default 2, 1..8) at or above --residual_peaks_sigma (default 5)
+             times the rms map of the mesh, at most --residual_peaks_max of them (default 65536, up to 2^20), kept when at least
+             --residual_peaks_min_above (default 3) pixels of the neighbourhood are above the threshold.  The catalog file gains a
+             list "residual_peaks" beside the sources (x_peak, y_peak, x, y, ra, dec, peak, rms, snr, npix, nabove, flux_sum, flux,
+             in_source) in decreasing snr, and every source res_npeaks and res_peak_snr.  --residual_holes (implies the same) also
+             searches the negated residual: "residual_holes", res_nholes, res_hole_snr (cy_find_peaks; DESIGN.md "Residual peaks").
 """
 import argparse
 import logging
@@ -167,6 +174,18 @@ def parse_args(argv=None):
     p.add_argument('--save_residual_maps', dest='save_residual_maps', action='store_true',
                    help='write the model and residual maps as model_<catalog name>.fits / resid_<catalog name>.fits beside the catalog '
                         '(implies --residual_map)')
+    p.add_argument('--residual_peaks', dest='residual_peaks', action='store_true',
+                   help='list the local maxima of the residual map above the noise map on the GPU (implies --residual_map and --bkg_map)')
+    p.add_argument('--residual_peaks_sigma', dest='residual_peaks_sigma', type=float, default=5.0,
+                   help='a residual peak lies at or above this many times the rms map (with --residual_peaks)')
+    p.add_argument('--residual_peaks_radius', dest='residual_peaks_radius', type=int, choices=list(range(1, 9)), default=2, metavar='R',
+                   help='a residual peak is the highest pixel within this many pixels in x and y, 1..8 (with --residual_peaks)')
+    p.add_argument('--residual_peaks_min_above', dest='residual_peaks_min_above', type=int, default=3,
+                   help='a residual peak is kept when this many pixels of its neighbourhood are above the threshold (with --residual_peaks)')
+    p.add_argument('--residual_peaks_max', dest='residual_peaks_max', type=int, default=65536,
+                   help='residual peaks read back at most, 0..2^20, in row-major order (with --residual_peaks)')
+    p.add_argument('--residual_holes', dest='residual_holes', action='store_true',
+                   help='also list the local minima of the residual map below minus the threshold (implies what --residual_peaks implies)')
     args = p.parse_args(argv)
     steps = plan(vars(args))                                  # the "implies" of the switches above: one rule, measure.plan
     args.measure_sources, args.bkg_map, args.measure_islands = "measure" in steps, "background" in steps, "islands" in steps
@@ -207,6 +226,12 @@ def validate_args(args):
     if args.bkg_min_pix < 1:
         logger.error("--bkg_min_pix must be >= 1!")
         return -1
+    if not (args.residual_peaks_sigma > 0 and args.residual_peaks_sigma < float("inf")):
+        logger.error("--residual_peaks_sigma must be > 0 and finite!")
+        return -1
+    if not 0 <= args.residual_peaks_max <= (1 << 20):
+        logger.error("--residual_peaks_max must be in [0, 2^20]!")
+        return -1
     if args.split_img_in_tiles and (args.xmin >= 0 or args.xmax >= 0 or args.ymin >= 0 or args.ymax >= 0):
         # serial runs crop like the reference (inference.py:499-505); the tiled run of the reference derives its grid from
         # attributes it has not set yet when a range is given (inference.py:374-381): refused here
@@ -244,7 +269,9 @@ def build_preprocessor(args):
 
 MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_seed_sigma', 'island_merge_sigma', 'island_conn', 'deblend_islands',
                 'deblend_peak_sigma', 'deblend_radius', 'fit_components', 'fit_max_iter', 'fit_blends', 'residual_map', 'residual_nsigma',
-                'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps')
+                'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps',
+                'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
+                'residual_holes')
 
 
 def measure_config(args):

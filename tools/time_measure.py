@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -14,6 +14,9 @@ the kernels alone on the same image: cy_measure_background at cell 64 / 128 / 25
 cell-128 mesh to both maps, `--runs` calls each after a warm-up; --host-ref then also times tests/bkg_ref.py at cell 128.
 Unless --no-residual (or --no-blend) is given there is a variant `residual`, --fit_blends --residual_map (residual_ms, render_kernel_ms,
 residual_kernel_ms, the numbers of rendered, duplicated and capped components beside the blend_ms of the same runs).
+Unless --no-peaks (or --no-residual) is given there is a variant `peaks`, --fit_blends --residual_map --residual_peaks (peaks_ms,
+peaks_kernel_ms, the numbers of peaks found and kept beside the render_kernel_ms of the same runs; the switch implies --bkg_map);
+peaks_added_ms is its run time over that of the `residual` variant.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
 their mean and largest niter beside the deblend_ms and deblend_kernel_ms of the same runs).
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("--no-fit", action="store_true")
     ap.add_argument("--no-blend", action="store_true")
     ap.add_argument("--no-residual", action="store_true")
+    ap.add_argument("--no-peaks", action="store_true")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -121,10 +125,13 @@ def main():
                                ("blend_jobs", "blend_niter_mean", "blend_niter_max", "blend_over_limit")),
                      "residual": (["--fit_blends", "--residual_map"], ("blend_ms", "residual_ms", "render_kernel_ms", "residual_kernel_ms"),
                                   ("residual_rendered", "residual_duplicates", "residual_capped")),
+                     "peaks": (["--fit_blends", "--residual_map", "--residual_peaks"], ("render_kernel_ms", "peaks_ms", "peaks_kernel_ms"),
+                               ("peaks_found", "peaks_kept")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
-                    "residual": args.no_deblend or args.no_fit or args.no_blend or args.no_residual, "islands": args.no_islands}
+                    "residual": args.no_deblend or args.no_fit or args.no_blend or args.no_residual,
+                    "peaks": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_peaks, "islands": args.no_islands}
             variants = [("off", base)] + [(name, base + on + t[0]) for name, t in table.items() if not (args.off_only or skip.get(name))]
             for name, argv in variants:                    # warm-up of each variant
                 assert run.main(argv) == 0
@@ -151,6 +158,8 @@ def main():
                               ("deblend", "deblend_added_ms"), ("bkg", "bkg_added_ms")):
                 if name in got:
                     res[key] = res[name]["run_ms_median"] - res["off"]["run_ms_median"]
+            if "peaks" in got and "residual" in got:
+                res["peaks_added_ms"] = res["peaks"]["run_ms_median"] - res["residual"]["run_ms_median"]
             if "bkg" in got:
                 res.update(background_kernels(img, args.runs, args.host_ref))
             if "islands" in got:                            # read before the next variant overwrites the catalog: it was the last to run

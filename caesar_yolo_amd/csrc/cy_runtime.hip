@@ -899,36 +899,95 @@ int cy_debug_read_conv(cy_ctx* c, const char* conv_name, float* h_out, size_t ca
     return fail(c, CY_ERR_ARG, std::string("no such conv: ") + conv_name);
 }
 
+// One launch_conv on caller buffers with the layout the plan executor gives a convolution: channel slices of wider NHWC buffers,
+// two input segments, the x2 upsample of segment 0, a residual slice, fp32 prediction rows.  Every rule below is checked on the
+// host before anything is uploaded or launched.  A dense output / residual tensor (ct == Cout, offset 0) may have any width, as
+// cy_conv_bn_silu always allowed (Cout = 5: no whole vector group is ever stored).
+int cy_conv_slices(cy_ctx* c, const cy_conv_layout* L, const float* h_w, const float* h_b, char* variant, int variant_cap,
+                   int* passes, void* stream) {
+    if (!c || !L || !L->d_in0 || !h_w || !h_b || !L->d_out) return fail(c, CY_ERR_ARG, "null argument");
+    const int B = L->B, Hi = L->Hi, Wi = L->Wi, Cin = L->Cin, Cout = L->Cout, k = L->k, s = L->s;
+    if ((k != 1 && k != 3) || (s != 1 && s != 2) || Cin % 8 || Cin < 8 || Cout < 1 || B < 1 || Hi < 1 || Wi < 1)
+        return fail(c, CY_ERR_ARG, "unsupported conv geometry");
+    const bool x3 = c->prec == PREC_F16X3, rows = L->rows != 0, has1 = L->c1 != 0;
+    const int cm = x3 ? 2 : 1, pad = k / 2, Ho = (Hi + 2 * pad - k) / s + 1, Wo = (Wi + 2 * pad - k) / s + 1;
+    const int chunk = c->prec == PREC_F32 ? 32 : 64;                // channels of one K chunk (BKE)
+    auto dense = [&](int ct, int coff) { return ct == Cout && coff == 0; };
+    if (!ch8(L->in0_ct) || !ch8(L->in0_coff) || !ch8(L->c0) || L->c0 < 8 || L->in0_coff + L->c0 > L->in0_ct)
+        return fail(c, CY_ERR_ARG, "segment 0: slice outside its tensor, or a channel count / offset not a multiple of 8");
+    if (L->c1 < 0 || (has1 && (!L->d_in1 || !ch8(L->in1_ct) || !ch8(L->in1_coff) || !ch8(L->c1) || L->in1_coff + L->c1 > L->in1_ct)))
+        return fail(c, CY_ERR_ARG, "segment 1: slice outside its tensor, or a channel count / offset not a multiple of 8");
+    if (L->c0 + L->c1 != Cin) return fail(c, CY_ERR_ARG, "c0 + c1 != Cin");
+    if (has1 && (k != 1 || s != 1 || L->c0 % chunk)) return fail(c, CY_ERR_ARG, "two segments: 1x1 stride 1 only, c0 a multiple of the K chunk (64 channels, 32 in fp32)");
+    if (L->up0 && (k != 1 || s != 1 || Hi % 2 || Wi % 2)) return fail(c, CY_ERR_ARG, "upsampled segment 0: 1x1 stride 1 on even maps only");
+    if (L->out_coff < 0 || L->out_coff + Cout > L->out_ct || (!rows && !dense(L->out_ct, L->out_coff) && (!ch8(L->out_ct) || !ch8(L->out_coff))))
+        return fail(c, CY_ERR_ARG, "output: slice outside its tensor, or a channel count / offset not a multiple of 8");
+    if (L->d_res && (L->res_coff < 0 || L->res_coff + Cout > L->res_ct || (!dense(L->res_ct, L->res_coff) && (!ch8(L->res_ct) || !ch8(L->res_coff)))))
+        return fail(c, CY_ERR_ARG, "residual: slice outside its tensor, or a channel count / offset not a multiple of 8");
+    if (rows && (L->out_ro < 0 || (long)L->out_ro + (long)Ho * Wo > L->out_bs || L->d_res || L->act))
+        return fail(c, CY_ERR_ARG, "prediction rows: out_ro + Ho * Wo must fit out_bs; no residual, no activation");
+    if (L->d_out == L->d_in0 || (has1 && L->d_out == L->d_in1)) return fail(c, CY_ERR_ARG, "the output must not alias an input");
+    if (L->d_res && L->d_res == L->d_out) {            // the C2f pattern: residual and output are disjoint slices of one buffer
+        if (L->res_ct != L->out_ct || (L->res_coff < L->out_coff + Cout && L->out_coff < L->res_coff + Cout))
+            return fail(c, CY_ERR_ARG, "residual and output in one buffer must be disjoint slices of the same width");
+    }
+    const int H0 = L->up0 ? Hi / 2 : Hi, W0 = L->up0 ? Wi / 2 : Wi;
+    const long n0 = (long)B * H0 * W0, n1 = (long)B * Hi * Wi, nout = (long)B * Ho * Wo;
+    const size_t es = esize(c->prec);
+    if ((size_t)n0 * L->in0_ct * es >= (1ull << 32) || (has1 && (size_t)n1 * L->in1_ct * es >= (1ull << 32)))
+        return fail(c, CY_ERR_ARG, "input buffer of 4 GiB or more");
+    HIPCHK(c, hipSetDevice(c->device));
+    // fp16x3 context: caller tensors are fp32 NHWC; every buffer is split whole into [ct high | ct low] halves here (the output
+    // buffer too, so that what lies outside the slice travels through), the layer runs on the split kernels exactly as inside the
+    // forward pass, and the output buffer is merged back to fp32.  Prediction rows are fp32 in every context.
+    hipStream_t st = (hipStream_t)stream;
+    DevOwner sc;
+    DevConv dc;
+    void *in0 = const_cast<void*>(L->d_in0), *in1 = const_cast<void*>(L->d_in1), *res = const_cast<void*>(L->d_res), *out = L->d_out;
+    const bool split_out = x3 && !rows;
+    hipError_t e = upload_conv(sc, c->prec, h_w, h_b, nullptr, Cout, Cin, k, s, false, dc);
+    if (e == hipSuccess && x3) e = sc.split(L->d_in0, n0, L->in0_ct, &in0, st);
+    if (e == hipSuccess && x3 && has1) e = sc.split(L->d_in1, n1, L->in1_ct, &in1, st);
+    if (e == hipSuccess && split_out) e = sc.split(L->d_out, nout, L->out_ct, &out, st);
+    if (e == hipSuccess && x3 && L->d_res) {
+        if (L->d_res == L->d_out) res = out;
+        else e = sc.split(L->d_res, nout, L->res_ct, &res, st);
+    }
+    if (e == hipSuccess) {
+        ConvArgs a{};
+        a.in0 = in0; a.in0_ct = cm * L->in0_ct; a.in0_coff = L->in0_coff; a.c0 = L->c0; a.up0 = L->up0 != 0;
+        a.in0_bytes = (uint32_t)((size_t)n0 * L->in0_ct * es); a.in0_lo = x3 ? L->in0_ct : 0;
+        if (has1) {
+            a.in1 = in1; a.in1_ct = cm * L->in1_ct; a.in1_coff = L->in1_coff; a.c1 = L->c1;
+            a.in1_bytes = (uint32_t)((size_t)n1 * L->in1_ct * es); a.in1_lo = x3 ? L->in1_ct : 0;
+        }
+        a.wgt = dc.w; a.wgt_bytes = (uint32_t)dc.wbytes; a.bias = dc.bias; a.wgt32 = dc.w32; a.wgt32_bytes = (uint32_t)dc.w32bytes;
+        a.oscale = dc.oscale; a.split = x3 ? dc.passes : 0;
+        a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.k = k; a.s = s; a.act = L->act;
+        a.out = out; a.out_coff = L->out_coff;
+        if (rows) { a.out_ct = L->out_ct; a.out_bs = L->out_bs; a.out_ro = L->out_ro; a.out_f32 = 1; }
+        else { a.out_ct = cm * L->out_ct; a.out_lo = x3 ? L->out_ct : 0; a.out_bs = Ho * Wo; }
+        if (L->d_res) { a.res = res; a.res_ct = cm * L->res_ct; a.res_coff = L->res_coff; a.res_lo = x3 ? L->res_ct : 0; }
+        if (variant && variant_cap > 0) snprintf(variant, (size_t)variant_cap, "%s", conv_variant_name(conv_variant(c->prec, a)));
+        if (passes) *passes = a.split;
+        e = launch_conv(c->prec, a, st);
+    }
+    if (e == hipSuccess && split_out) e = launch_x3_merge(out, reinterpret_cast<float*>(L->d_out), nout, L->out_ct, st);
+    return entry_done(c, e, st);
+}
+
+const char* cy_conv_variant_name(int idx) { return idx >= 0 && idx < CONV_NUM_VARIANTS ? conv_variant_name(idx) : nullptr; }
+
+// the dense call of cy_conv_slices: every ct the channel count, every offset 0, one segment, no rows
 int cy_conv_bn_silu(cy_ctx* c, const void* d_in, int B, int Hi, int Wi, int Cin, const float* h_w, const float* h_b,
                     int Cout, int k, int s, int act, const void* d_res, void* d_out, void* stream) {
     if (!c || !d_in || !h_w || !h_b || !d_out) return fail(c, CY_ERR_ARG, "null argument");
-    if ((k != 1 && k != 3) || (s != 1 && s != 2) || Cin % 8 || B < 1) return fail(c, CY_ERR_ARG, "unsupported conv geometry");
-    HIPCHK(c, hipSetDevice(c->device));
-    // fp16x3 context: caller tensors are fp32 NHWC; they are split into high / low halves here, the layer runs on the split
-    // kernels exactly as inside the forward pass, and the result is merged back to fp32
-    hipStream_t st = (hipStream_t)stream;
-    const bool x3 = c->prec == PREC_F16X3;
-    const int cm = x3 ? 2 : 1, pad = k / 2, Ho = (Hi + 2 * pad - k) / s + 1, Wo = (Wi + 2 * pad - k) / s + 1;
-    const long nin = (long)B * Hi * Wi, nout = (long)B * Ho * Wo;
-    DevOwner sc;
-    DevConv dc;
-    void *in = const_cast<void*>(d_in), *res = const_cast<void*>(d_res), *out = d_out;
-    hipError_t e = upload_conv(sc, c->prec, h_w, h_b, nullptr, Cout, Cin, k, s, false, dc);
-    if (e == hipSuccess && x3) e = sc.split(d_in, nin, Cin, &in, st);
-    if (e == hipSuccess && x3 && d_res) e = sc.split(d_res, nout, Cout, &res, st);
-    if (e == hipSuccess && x3) e = sc.alloc((size_t)nout * Cout * 4, &out);
-    if (e == hipSuccess) {
-        ConvArgs a{};
-        a.in0 = in; a.in0_ct = cm * Cin; a.c0 = Cin; a.in0_bytes = (uint32_t)((size_t)nin * Cin * esize(c->prec)); a.in0_lo = x3 ? Cin : 0;
-        a.wgt = dc.w; a.wgt_bytes = (uint32_t)dc.wbytes; a.bias = dc.bias; a.wgt32 = dc.w32; a.wgt32_bytes = (uint32_t)dc.w32bytes;
-        a.oscale = dc.oscale; a.split = x3 ? dc.passes : 0;
-        a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cout = Cout; a.k = k; a.s = s; a.act = act;
-        a.out = out; a.out_ct = cm * Cout; a.out_lo = x3 ? Cout : 0; a.out_bs = Ho * Wo;
-        if (d_res) { a.res = res; a.res_ct = cm * Cout; a.res_lo = x3 ? Cout : 0; }
-        e = launch_conv(c->prec, a, st);
-    }
-    if (e == hipSuccess && x3) e = launch_x3_merge(out, reinterpret_cast<float*>(d_out), nout, Cout, st);
-    return entry_done(c, e, st);
+    cy_conv_layout L{};
+    L.d_in0 = d_in; L.in0_ct = Cin; L.c0 = Cin;
+    L.d_res = d_res; L.res_ct = Cout;
+    L.d_out = d_out; L.out_ct = Cout;
+    L.B = B; L.Hi = Hi; L.Wi = Wi; L.Cin = Cin; L.Cout = Cout; L.k = k; L.s = s; L.act = act;
+    return cy_conv_slices(c, &L, h_w, h_b, nullptr, 0, nullptr, stream);
 }
 
 int cy_bottleneck64(cy_ctx* c, const void* d_in, int B, int H, int W, const float* h_w1, const float* h_b1, const float* h_w2,

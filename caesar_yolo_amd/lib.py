@@ -43,7 +43,7 @@ EXPORTS = [
     "cy_weight_passes", "cy_class_name", "cy_plan_num_convs", "cy_plan_conv_desc", "cy_letterbox_geometry", "cy_num_anchors",
     "cy_pred_elems", "cy_profile_enable", "cy_profile_summary", "cy_profile_summary_lane", "cy_profile_layers", "cy_profile_layer_variant", "cy_mosaic_prepare", "cy_letterbox_pack", "cy_preproc", "cy_preproc_planes", "cy_preproc_params", "cy_forward", "cy_debug_read_conv",
     "cy_debug_stop_after", "cy_debug_ops_done", "cy_debug_read_tensor",
-    "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_bottleneck64", "cy_dwconv3x3",
+    "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_conv_slices", "cy_conv_variant_name", "cy_bottleneck64", "cy_dwconv3x3",
     "cy_attention", "cy_maxpool5", "cy_make_tile_records",
     "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
@@ -76,6 +76,16 @@ class cy_preproc_cfg(C.Structure):
 
 class cy_conv_desc(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int), ("s", C.c_int),
+                ("act", C.c_int)]
+
+
+class cy_conv_layout(C.Structure):
+    _fields_ = [("d_in0", C.c_void_p), ("in0_ct", C.c_int), ("in0_coff", C.c_int), ("c0", C.c_int), ("up0", C.c_int),
+                ("d_in1", C.c_void_p), ("in1_ct", C.c_int), ("in1_coff", C.c_int), ("c1", C.c_int),
+                ("d_res", C.c_void_p), ("res_ct", C.c_int), ("res_coff", C.c_int),
+                ("d_out", C.c_void_p), ("out_ct", C.c_int), ("out_coff", C.c_int),
+                ("rows", C.c_int), ("out_bs", C.c_int), ("out_ro", C.c_int),
+                ("B", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("k", C.c_int), ("s", C.c_int),
                 ("act", C.c_int)]
 
 
@@ -159,6 +169,8 @@ def load():
         "cy_detect_counters": (C.c_int, [vp, C.POINTER(C.c_longlong), C.c_int]),
         "cy_conv_bn_silu": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int,
                                       C.c_int, vp, vp, vp]),
+        "cy_conv_slices": (C.c_int, [vp, C.POINTER(cy_conv_layout), fp, fp, C.c_char_p, C.c_int, ip, vp]),
+        "cy_conv_variant_name": (C.c_char_p, [C.c_int]),
         "cy_bottleneck64": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_int, vp, vp]),
         "cy_dwconv3x3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int,
                                    C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),

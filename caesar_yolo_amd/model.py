@@ -662,6 +662,31 @@ class HipDetector(object):
                                            self._p(out), self._stream()))
         return out
 
+    def conv_slices(self, w, b, k, s, act, in0, c0, out, in0_coff=0, up0=False, in1=None, in1_coff=0, c1=0, res=None, res_coff=0,
+                    out_coff=0, rows=None):
+        """One convolution in the forward's layout (cy_conv_slices): in0 [B,H0,W0,in0_ct] (H0 = Hi / 2 with up0), in1
+        [B,Hi,Wi,in1_ct], res [B,Ho,Wo,res_ct] (may be `out`), out [B,Ho,Wo,out_ct] written in place in its slice, or with
+        rows = out_ro the fp32 prediction rows [B,out_bs,out_ct].  -> (variant name, fp16x3 pass count)."""
+        B = in0.shape[0]
+        Hi, Wi = (in1.shape[1], in1.shape[2]) if in1 is not None else (in0.shape[1] << int(bool(up0)), in0.shape[2] << int(bool(up0)))
+        w = np.ascontiguousarray(w, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        a = L.cy_conv_layout()
+        a.d_in0, a.in0_ct, a.in0_coff, a.c0, a.up0 = in0.data_ptr(), in0.shape[-1], int(in0_coff), int(c0), int(bool(up0))
+        if in1 is not None:
+            a.d_in1, a.in1_ct, a.in1_coff, a.c1 = in1.data_ptr(), in1.shape[-1], int(in1_coff), int(c1)
+        if res is not None:
+            a.d_res, a.res_ct, a.res_coff = res.data_ptr(), res.shape[-1], int(res_coff)
+        a.d_out, a.out_ct, a.out_coff = out.data_ptr(), out.shape[-1], int(out_coff)
+        if rows is not None:
+            a.rows, a.out_bs, a.out_ro = 1, out.shape[1], int(rows)
+        a.B, a.Hi, a.Wi, a.Cin, a.Cout, a.k, a.s, a.act = B, Hi, Wi, w.shape[1], w.shape[0], int(k), int(s), int(bool(act))
+        name = C.create_string_buffer(128)
+        passes = C.c_int(0)
+        self._chk(self.lib.cy_conv_slices(self.ctx, C.byref(a), w.ctypes.data_as(C.POINTER(C.c_float)),
+                                          b.ctypes.data_as(C.POINTER(C.c_float)), name, 128, C.byref(passes), self._stream()))
+        return name.value.decode(), passes.value
+
     # kernel-level test entries of the YOLO11 / SPPF operators: NHWC tensors [B,H,W,ct] of the context dtype, the op on channel
     # slices of them (the forward's layout); the output tensor is written in place (channels outside its slice untouched)
     def dwconv3x3(self, x, nch, w, b, out, in_coff=0, out_coff=0, act=True, res=None, res_coff=0, chmap=(0, 0, 0)):

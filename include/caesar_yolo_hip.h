@@ -208,6 +208,34 @@ int cy_detect_counters(cy_ctx* ctx, long long* out4, int reset);
 int cy_conv_bn_silu(cy_ctx* ctx, const void* d_in, int B, int Hi, int Wi, int Cin, const float* h_w, const float* h_b,
                     int Cout, int k, int s, int act, const void* d_res, void* d_out, void* stream);
 
+/* the same layer in the layout the forward pass gives a convolution (kernel-level tests): channel slices of wider NHWC buffers.
+ * d_in0 [B][H0][W0][in0_ct], the c0 channels from in0_coff on; up0 != 0: read through the nearest x2 upsample, H0 = Hi / 2,
+ *   W0 = Wi / 2 (else H0 = Hi, W0 = Wi).  d_in1 [B][Hi][Wi][in1_ct] (c1 channels from in1_coff on; c1 == 0: absent): the input is
+ *   the channel concatenation of the two segments.  d_res optional [B][Ho][Wo][res_ct], the Cout channels from res_coff on; it may
+ *   be d_out itself with a disjoint slice (the C2f bottleneck pattern).  d_out [B][Ho][Wo][out_ct], the Cout channels from out_coff
+ *   on; or, rows != 0, fp32 prediction rows [B][out_bs][out_ct] in every context, pixel (ho, wo) of image b in row
+ *   b * out_bs + out_ro + ho * Wo + wo (no residual, no activation).  Buffers are exactly that large; what lies outside the output
+ *   slice is left as it was.  Tensors are in the context precision (fp32 in CY_F16X3: every buffer is split whole into high / low
+ *   halves, the output buffer too, and merged back).
+ * Refused with CY_ERR_ARG before anything is launched: a slice outside its ct; a ct, offset, c0 or c1 that is no multiple of 8
+ *   (a dense output / residual, ct == Cout at offset 0, may have any width; the ct of prediction rows is free); c0 + c1 != Cin;
+ *   c1 != 0 unless k == 1, s == 1 and c0 is a multiple of the K chunk (64 channels, 32 in CY_F32); up0 unless k == 1, s == 1 and
+ *   Hi, Wi even; rows with out_ro + Ho * Wo > out_bs, a residual or an activation; d_out equal to an input.
+ * variant (variant_cap bytes, may be null): the name of the kernel variant that ran; passes (may be null): passes over K of the
+ *   CY_F16X3 filter (2 or 3), 0 in the other contexts.  cy_conv_bn_silu is the dense call of this entry.
+ * cy_conv_variant_name: name of variant idx (host only), NULL past the last one. */
+typedef struct cy_conv_layout {
+    const void* d_in0; int in0_ct, in0_coff, c0, up0;
+    const void* d_in1; int in1_ct, in1_coff, c1;
+    const void* d_res; int res_ct, res_coff;
+    void* d_out; int out_ct, out_coff;
+    int rows, out_bs, out_ro;
+    int B, Hi, Wi, Cin, Cout, k, s, act;
+} cy_conv_layout;
+int cy_conv_slices(cy_ctx* ctx, const cy_conv_layout* layout, const float* h_w, const float* h_b, char* variant,
+                   int variant_cap, int* passes, void* stream);
+const char* cy_conv_variant_name(int idx);
+
 /* one fused Bottleneck(64, 64, shortcut) = x [+] SiLU(cv2(SiLU(cv1(x)))) with two folded 3x3 convs, as the forward runs the
  * stride-4 C2f blocks of yolov8l in the fp16 context (kernel-level parity tests).  d_in, d_out [B][H][W][64] fp16;
  * h_w1, h_w2 [64][64][3][3], h_b1, h_b2 [64] fp32 */

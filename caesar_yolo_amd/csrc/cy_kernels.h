@@ -187,6 +187,32 @@ struct DecodeArgs {
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 
+// ---- box branch of the detect head at candidate anchors only (detect_post.hip: mark; cy_sparse_box.hip: the three stages) ----
+enum BoxWalk { BOX_WALK_WIDE = 0, BOX_WALK_PP = 1, BOX_WALK_C64 = 2 };     // K walk + epilogue of the dense kernel of stage 1
+constexpr int BOX_GRID = 512;                   // workgroups (four waves of 64 list entries) per level and stage: a fixed grid, the
+                                                // waves stride over the lists by the device-side counts
+struct BoxLevel {
+    int sparse;                                 // 0: this level's box branch ran dense in the forward pass; nothing is done here
+    int H, W, a_off;                            // map of the level, its first anchor in a prediction block
+    int cap;                                    // B * H * W: entries the lists, the slot map and s1 / s2 hold
+    const void* feat; int feat_ct, feat_coff, cin; uint32_t feat_bytes;      // input of stage 1: NHWC fp16 feature map, channel slice
+    const void* w1; uint32_t w1_bytes; const float* b1; int walk1;           // cv2.l.0: wgt32 (BOX_WALK_WIDE) or wgt, bias
+    const void* w2; uint32_t w2_bytes; const float* b2;                      // cv2.l.1: wgt (128-byte K chunks), bias
+    const void* w3; uint32_t w3_bytes; const float* b3;                      // cv2.l.2: wgt, bias
+    int* map;                                   // [cap] slot of a listed pixel in plist / s1, -1: not needed (set by the caller), -2: flagged; the three
+                                                // levels' maps are ONE array of B * A words: L[l].map = L[0].map + B * L[l].a_off
+    int* plist; int* clist;                     // [cap] stage-1 pixels (entry = slot) / candidate pixels, as b * H * W + y * W + x, in the atomics' order
+    int* counts;                                // [2] entries of plist, of clist (zeroed by the caller)
+    void* s1; void* s2;                         // [cap][64] fp16: stage-1 values by slot, stage-2 values by candidate entry
+};
+struct BoxArgs {
+    BoxLevel L[3];
+    float* pred; int B, A, nc;                  // [B][A][64+nc]: class columns are final, box columns are written at candidates
+    float conf;
+};
+hipError_t launch_box_mark(const BoxArgs& a, hipStream_t s);      // candidate test of decode_kernel -> clist, map, plist, counts
+hipError_t launch_box_sparse(const BoxArgs& a, hipStream_t s);    // stages 1-3 over the lists
+
 struct NmsArgs {
     const float* cand; const int* cand_anchor; const int* cand_count; int cap;   // from decode
     int B; float iou; int max_det;

@@ -388,12 +388,36 @@ bool pw_pair(const Plan& p, size_t i) {
     if (p.tensors[o.out].level != p.tensors[n.out].level || n.out == o.out) return false;
     return readers_of(p, o.out) == 1;                     // nothing else may read the first layer's output (a later op may overwrite that tensor)
 }
+
+// ops[i], ops[i+1], ops[i+2] = the box branch of one detect-head level: a 3x3 s1 SiLU conv reading a feature map into a tensor of its
+// own, a 3x3 s1 SiLU 64 -> 64 conv as its only reader, and the 1x1 (no activation) of THAT tensor's only reader into columns 0..63 of
+// the prediction rows.  decode_kernel reads those columns at candidate anchors only, so the detect pass may compute the branch there
+// alone (cy_sparse_box.hip; the gate is the forward pass's).
+bool box_branch(const Plan& p, size_t i) {
+    if (i + 2 >= p.ops.size()) return false;
+    const Op& o = p.ops[i]; const Op& n = p.ops[i + 1]; const Op& h = p.ops[i + 2];
+    if (o.kind != OPK_CONV || !plain_conv_pair(o, n) || h.kind != OPK_CONV || h.conv < 0) return false;
+    const ConvDesc& d0 = p.convs[o.conv]; const ConvDesc& d1 = p.convs[n.conv]; const ConvDesc& d2 = p.convs[h.conv];
+    auto c3 = [](const ConvDesc& d) { return d.k == 3 && d.s == 1 && d.act && d.groups == 1 && d.cout == 64; };
+    if (!c3(d0) || !c3(d1) || d1.cin != 64 || d0.cin % 64 || o.c0 != d0.cin || n.c0 != 64) return false;
+    if (d2.k != 1 || d2.s != 1 || d2.act || d2.groups != 1 || d2.cin != 64 || d2.cout != 64) return false;
+    if (o.in1 >= 0 || o.up0 || o.res >= 0 || n.res >= 0 || o.out_coff != 0 || n.out_coff != 0) return false;
+    if (h.out >= 0 || h.pred_coff != 0 || h.in0 != n.out || h.in0_coff != 0 || h.c0 != 64 || h.in1 >= 0 || h.up0 || h.res >= 0) return false;
+    if (p.tensors[o.out].C != 64 || p.tensors[n.out].C != 64 || o.out == n.out || o.in0 == o.out || o.in0 == n.out) return false;
+    const int lev = p.tensors[o.in0].level;
+    if (lev != 3 + h.pred_level || p.tensors[o.out].level != lev || p.tensors[n.out].level != lev) return false;
+    // the two intermediates belong to the branch: written by it alone, read by it alone
+    int writers0 = 0, writers1 = 0;
+    for (const Op& q : p.ops) { writers0 += q.out == o.out; writers1 += q.out == n.out; }
+    return writers0 == 1 && writers1 == 1 && readers_of(p, o.out) == 1 && readers_of(p, n.out) == 1;
+}
 }  // namespace
 
 void mark_fusions(Plan& p) {
     for (size_t i = 0; i < p.ops.size(); ++i) {
         Op& o = p.ops[i];
         o.fuse = FUSE_NONE;
+        if (o.box == 0 && box_branch(p, i)) { o.box = 1; p.ops[i + 1].box = 2; p.ops[i + 2].box = 3; }
         if (i + 1 >= p.ops.size()) continue;
         if (bneck_pair(p, i)) o.fuse = FUSE_BNECK_PAIR;         // (the three exclude one another: 64 / 256 output channels, the stem)
         else if (stem_down_pair(p, i)) o.fuse = FUSE_STEM_DOWN;

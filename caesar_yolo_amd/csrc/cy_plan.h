@@ -31,6 +31,8 @@ struct Op {
     int pred_level, pred_coff;                 // when out == -1: which stride level, channel offset inside [64+nc]
     int p0 = 0, p1 = 0, p2 = 0, p3 = 0;        // DWCONV: input channel map (blk, gstride, goff); ATTN: heads, key_dim, head_dim
     FuseMark fuse = FUSE_NONE;                 // this op is the first of a pair that one kernel can run (mark_fusions)
+    int box = 0;                               // 1, 2, 3: the three ops of a detect-head box branch (3x3, 3x3 64->64, 1x1 into columns 0..63) whose
+                                               // result is read at candidate anchors only (mark_fusions); 0: any other op
 };
 
 struct Plan {
@@ -65,6 +67,6 @@ std::string parse_header(Reader& r, Plan* plan, FileHeader* h);
 // the i-th conv record, read where `r` stands; CYW2: checked and appended to plan->convs, CYW1: compared with plan->convs[i]
 std::string next_conv(Reader& r, const FileHeader& h, Plan* plan, uint32_t i, ConvRecord* out);
 std::string validate_plan(const Plan& p);      // CYW2, once every conv is known: each op's channel slices lie inside its tensors
-void mark_fusions(Plan& p);                    // sets Op::fuse of every op; the plan is accepted
+void mark_fusions(Plan& p);                    // sets Op::fuse and Op::box of every op; the plan is accepted
 
 }  // namespace cy

@@ -69,6 +69,7 @@ struct cy_ctx {
     // second workspace + stream: cy_detect_tiles runs batches of 64..239 tiles as two concurrent half-batches (forward_split)
     char* ws2 = nullptr; size_t ws2_bytes = 0; hipStream_t s_fwd2 = nullptr; hipEvent_t ev_split[2] = {nullptr, nullptr};
     char* ws3 = nullptr; size_t ws3_bytes = 0; hipStream_t s_small = nullptr;     // small-batch lane: its own workspace and (lowest-priority) stream
+    int* box_scr[3] = {nullptr, nullptr, nullptr};      // per workspace (ws, ws2, ws3): slot maps, work lists and counts of the deferred box branch (box_scratch)
     std::vector<size_t> toff; std::vector<size_t> tbytes;   // per tensor, for the last forward geometry
     int lastB = 0, lastH = 0, lastW = 0;
     // stage buffers (sized at load for max_batch), two sets: cy_detect_tiles software-pipelines consecutive batches
@@ -199,6 +200,7 @@ void free_all(cy_ctx* c) {
     c->dconv.clear();
     c->weights.reset(); c->buffers.reset(); c->aug_mem.reset(); c->counter_mem.reset();
     c->ws = c->ws2 = c->ws3 = nullptr; c->ws2_bytes = c->ws3_bytes = 0; c->counters = nullptr;
+    c->box_scr[0] = c->box_scr[1] = c->box_scr[2] = nullptr;
     for (auto& b : c->sb) b = cy_ctx::StageBufs();
     for (auto& b : c->ab) b = cy_ctx::AugBufs();
     if (c->s_fwd2) { hipStreamDestroy(c->s_fwd2); c->s_fwd2 = nullptr; }
@@ -502,8 +504,27 @@ int cy_mosaic_prepare(cy_ctx* c, float* d_data, size_t n, int big_endian, void* 
     return CY_OK;
 }
 
+// A request to compute the box branch of the detect head at candidate anchors only (forward_on): the confidence threshold of the
+// decode that will read the rows; sparse[l] is set to whether level l was deferred (else it ran dense).
+struct BoxReq { float conf; int sparse[3]; int force = 0; };      // force: as CY_SPARSE_BOX=2 (test entry)
+// The lowest confidence threshold from which on the deferred form is taken by default: with every anchor a candidate the gather
+// kernels do the dense pixel count at lower efficiency.  Measured on the benchmark's tiles (profiles/sparse_box.md).
+constexpr float BOX_CONF_FLOOR = 0.25f;
+
 static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t s, char* ws, size_t ws_cap,
-                      bool may_profile, int stop = 0);
+                      bool may_profile, int stop = 0, BoxReq* box = nullptr);
+
+// slot maps [B * A], the two work lists [B * A each] and the counts [8] of a pass on workspace `ws`, allocated on first use for the
+// context's largest batch; *out stays null when this pass holds more anchors than that (the pass then runs dense)
+static int box_scratch(cy_ctx* c, const char* ws, size_t tot, int** out) {
+    const size_t max_tot = (size_t)c->cfg.max_batch * cy_num_anchors(c->cfg.max_h, c->cfg.max_w);
+    *out = nullptr;
+    if (tot > max_tot) return CY_OK;
+    const int k = ws == c->ws ? 0 : (ws == c->ws2 ? 1 : 2);
+    if (!c->box_scr[k]) HIPCHK(c, c->buffers.alloc((3 * max_tot + 8) * sizeof(int), &c->box_scr[k]));
+    *out = c->box_scr[k];
+    return CY_OK;
+}
 
 int cy_forward(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, void* stream) {
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
@@ -549,11 +570,11 @@ static int ensure_small_lane(cy_ctx* c) {
 }
 static int dual_mode() { return env_knob("CY_DUAL_FORWARD", 1); }
 
-static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t sm) {
+static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t sm, BoxReq* box = nullptr) {
     const int mode = dual_mode();
     const bool split = c->prec == PREC_F16 && mode != 0 && B >= 2 && (mode > 1 || (B >= 64 && B < 240));      // (fp16x3: a 128-tile batch already fills the chip 3x longer per launch)
     c->split_last = split;
-    if (!split) return forward_on(c, d_netin, B, H, W, d_pred, sm, c->ws, c->ws_bytes, true);
+    if (!split) return forward_on(c, d_netin, B, H, W, d_pred, sm, c->ws, c->ws_bytes, true, 0, box);
     int rc0 = ensure_second_workspace(c);
     if (rc0) return rc0;
     const int h = B - B / 2;
@@ -561,9 +582,9 @@ static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, fl
     const size_t pred_half = (size_t)h * cy_num_anchors(H, W) * (64 + c->plan.nc);
     HIPCHK(c, hipEventRecord(c->ev_split[0], sm));           // everything the forward waits for is already queued on sm
     HIPCHK(c, hipStreamWaitEvent(c->s_fwd2, c->ev_split[0], 0));
-    int rc = forward_on(c, d_netin, h, H, W, d_pred, sm, c->ws, c->ws_bytes, true);
+    int rc = forward_on(c, d_netin, h, H, W, d_pred, sm, c->ws, c->ws_bytes, true, 0, box);
     if (rc) return rc;
-    rc = forward_on(c, (const char*)d_netin + in_half, B - h, H, W, d_pred + pred_half, c->s_fwd2, c->ws2, c->ws2_bytes, false);
+    rc = forward_on(c, (const char*)d_netin + in_half, B - h, H, W, d_pred + pred_half, c->s_fwd2, c->ws2, c->ws2_bytes, false, 0, box);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev_split[1], c->s_fwd2));
     HIPCHK(c, hipStreamWaitEvent(sm, c->ev_split[1], 0));
@@ -574,7 +595,7 @@ static int forward_split(cy_ctx* c, const void* d_netin, int B, int H, int W, fl
 // op lies below `stop` runs whole; a box-branch output convolution still deferred for its head pair is NOT launched (its
 // prediction rows stay as the caller left them), so a stopped pass never runs a launch the whole pass would not.
 static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, hipStream_t s, char* ws, size_t ws_cap,
-                      bool may_profile, int stop) {
+                      bool may_profile, int stop, BoxReq* box) {
     if (!d_netin || !d_pred || B < 1 || H % 32 || W % 32 || H < 32 || W < 32) return fail(c, CY_ERR_ARG, "bad forward arguments");
     int rc = layout_tensors(c, B, H, W, ws_cap);
     if (rc) return rc;
@@ -612,11 +633,91 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     c->fused_last.assign(p.ops.size(), 0);
     const int pw_env = env_knob("CY_FUSE_PW", 1);             // back-to-back pairs (pw_pair); read per call: the parity tests run both forms
 
+    auto conv_args = [&](const Op& o) -> ConvArgs {           // the launch arguments of a convolution op of this pass
+        const ConvDesc& d = p.convs[o.conv];
+        ConvArgs a{};
+        const Tensor& t0 = p.tensors[o.in0];
+        auto span = [&](int t) -> uint32_t {           // bytes addressable from tptr(t) for B images
+            const Tensor& tt = p.tensors[t];
+            return (uint32_t)((size_t)B * (H >> tt.level) * (W >> tt.level) * tt.C * es);
+        };
+        a.in0 = tptr(o.in0); a.in0_ct = cm * t0.C; a.in0_coff = o.in0_coff; a.c0 = o.c0; a.up0 = o.up0;
+        a.in0_bytes = span(o.in0);
+        a.split = x3 ? c->dconv[o.conv].passes : 0; a.in0_lo = t0.C; a.oscale = c->dconv[o.conv].oscale;
+        int lev_in = o.up0 ? t0.level - 1 : t0.level;
+        if (o.in1 >= 0) {
+            const Tensor& t1 = p.tensors[o.in1];
+            a.in1 = tptr(o.in1); a.in1_ct = cm * t1.C; a.in1_coff = o.in1_coff; a.c1 = o.c1; a.in1_bytes = span(o.in1); a.in1_lo = t1.C;
+            lev_in = t1.level;
+        }
+        a.wgt = c->dconv[o.conv].w; a.wgt_bytes = (uint32_t)c->dconv[o.conv].wbytes; a.bias = c->dconv[o.conv].bias;
+        a.wgt32 = c->dconv[o.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[o.conv].w32bytes;
+        a.B = B; a.Hi = H >> lev_in; a.Wi = W >> lev_in; a.k = d.k; a.s = d.s; a.act = d.act;
+        a.Ho = d.s == 2 ? a.Hi / 2 : a.Hi; a.Wo = d.s == 2 ? a.Wi / 2 : a.Wi;
+        a.Cin = d.cin; a.Cout = d.cout;
+        if (o.out >= 0) {
+            const Tensor& to = p.tensors[o.out];
+            a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_bs = a.Ho * a.Wo; a.out_ro = 0; a.out_f32 = 0; a.out_lo = to.C;
+        } else {
+            a.out = d_pred; a.out_ct = 64 + p.nc; a.out_coff = o.pred_coff; a.out_bs = A; a.out_ro = a_off[o.pred_level]; a.out_f32 = 1;
+        }
+        if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
+        return a;
+    };
+
+    // Deferred box branch (box != null: the plain detect path, cy_detect_tiles, and the test entry cy_debug_sparse_box).  decode_kernel
+    // reads an anchor's 64 box logits only when its class scores pass `conf`, so the three marked ops of a level (Op::box) are not
+    // launched; behind the pass, on the same stream, the candidates and the pixels they need are listed from the finished class
+    // columns and the branch is computed there (cy_sparse_box.hip), bit for bit what the dense kernels write.  A level is taken when
+    // its three dense variants are ones the sparse kernels reproduce: by geometry only, so a tile's path does not depend on its batch.
+    // CY_SPARSE_BOX (read per call): 0 dense, 1 (default) sparse from conf >= BOX_CONF_FLOOR on, 2 sparse at any conf (tests).
+    auto box_level = [&](const Op& o) { return o.box == 3 ? o.pred_level : p.tensors[o.in0].level - 3; };
+    bool box_sparse[3] = {false, false, false};
+    BoxArgs bx{};
+    if (box && c->prec == PREC_F16 && !(stop > 0)) {
+        const int mode = box->force ? 2 : env_knob("CY_SPARSE_BOX", 1);
+        int* scr = nullptr;
+        const size_t tot = (size_t)B * A;                      // list entries / map words of the three levels together
+        if (mode >= 2 || (mode == 1 && box->conf >= BOX_CONF_FLOOR)) {
+            rc = box_scratch(c, ws, tot, &scr);
+            if (rc) return rc;
+        }
+        if (scr) {
+            bx.pred = d_pred; bx.B = B; bx.A = A; bx.nc = p.nc; bx.conf = box->conf;
+            for (int l = 0; l < 3; ++l) {
+                BoxLevel& L = bx.L[l];
+                L.H = H >> (3 + l); L.W = W >> (3 + l); L.a_off = a_off[l]; L.cap = B * L.H * L.W;
+                L.map = scr + (size_t)B * a_off[l]; L.plist = L.map + tot; L.clist = L.map + 2 * tot; L.counts = scr + 3 * tot + 2 * l;
+            }
+            for (size_t i = 0; i + 2 < p.ops.size(); ++i) {
+                if (p.ops[i].box != 1) continue;
+                const Op& o1 = p.ops[i]; const Op& o2 = p.ops[i + 1]; const Op& o3 = p.ops[i + 2];
+                const int l = o3.pred_level;
+                const ConvArgs a1 = conv_args(o1), a2 = conv_args(o2), a3 = conv_args(o3);
+                const int v1 = conv_variant(c->prec, a1);
+                if (v1 != CONV_WIDE_64 && v1 != CONV_PP_64 && v1 != CONV_C64_PERSIST) continue;
+                if (v1 == CONV_C64_PERSIST && a1.Cin != 64) continue;
+                if (conv_variant(c->prec, a2) != CONV_C64_PERSIST || a2.Cin != 64 || conv_variant(c->prec, a3) != CONV_HEAD_1X1) continue;
+                BoxLevel& L = bx.L[l];
+                L.sparse = 1;
+                L.feat = a1.in0; L.feat_ct = a1.in0_ct; L.feat_coff = a1.in0_coff; L.cin = a1.Cin; L.feat_bytes = a1.in0_bytes;
+                L.walk1 = v1 == CONV_WIDE_64 ? BOX_WALK_WIDE : (v1 == CONV_PP_64 ? BOX_WALK_PP : BOX_WALK_C64);
+                L.w1 = v1 == CONV_WIDE_64 ? a1.wgt32 : a1.wgt; L.w1_bytes = v1 == CONV_WIDE_64 ? a1.wgt32_bytes : a1.wgt_bytes; L.b1 = a1.bias;
+                L.w2 = a2.wgt; L.w2_bytes = a2.wgt_bytes; L.b2 = a2.bias;
+                L.w3 = a3.wgt; L.w3_bytes = a3.wgt_bytes; L.b3 = a3.bias;
+                L.s1 = a1.out; L.s2 = a2.out;                  // the branch's own (now unused) tensors: [cap][64] fp16 each
+                box_sparse[l] = true;
+            }
+        }
+    }
+    if (box) for (int l = 0; l < 3; ++l) box->sparse[l] = box_sparse[l];
+
     struct HeadPend { ConvArgs a; double flops; int conv; bool on; };
     HeadPend pend[3] = {};                                    // deferred box-branch output convolutions, per stride level
     const int bneck_env = env_knob("CY_BNECK_FUSE", 0);       // off by default (slower than two launches so far, see bneck64.hip); read per call: the parity tests run both forms
     auto run_op = [&](const Op& o, const Op* next, bool* fused) -> int {
         cur_conv = o.conv;
+        if (o.box && box_sparse[box_level(o)]) return CY_OK;      // computed at the candidate anchors, behind the pass (below)
         if (bneck_env && c->prec == PREC_F16 && o.fuse == FUSE_BNECK_PAIR && c->dconv[o.conv].bneck) {
             const Op& n = *next;
             const Tensor& ti = p.tensors[o.in0]; const Tensor& to = p.tensors[n.out];
@@ -690,34 +791,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             HIPCHK(c, e);
             prof_done(CONV_NUM_VARIANTS + 3, 2.0 * B * a.heads * (double)a.N * a.N * (a.kd + a.hd));
         } else {
-            const ConvDesc& d = p.convs[o.conv];
-            ConvArgs a{};
-            const Tensor& t0 = p.tensors[o.in0];
-            auto span = [&](int t) -> uint32_t {           // bytes addressable from tptr(t) for B images
-                const Tensor& tt = p.tensors[t];
-                return (uint32_t)((size_t)B * (H >> tt.level) * (W >> tt.level) * tt.C * es);
-            };
-            a.in0 = tptr(o.in0); a.in0_ct = cm * t0.C; a.in0_coff = o.in0_coff; a.c0 = o.c0; a.up0 = o.up0;
-            a.in0_bytes = span(o.in0);
-            a.split = x3 ? c->dconv[o.conv].passes : 0; a.in0_lo = t0.C; a.oscale = c->dconv[o.conv].oscale;
-            int lev_in = o.up0 ? t0.level - 1 : t0.level;
-            if (o.in1 >= 0) {
-                const Tensor& t1 = p.tensors[o.in1];
-                a.in1 = tptr(o.in1); a.in1_ct = cm * t1.C; a.in1_coff = o.in1_coff; a.c1 = o.c1; a.in1_bytes = span(o.in1); a.in1_lo = t1.C;
-                lev_in = t1.level;
-            }
-            a.wgt = c->dconv[o.conv].w; a.wgt_bytes = (uint32_t)c->dconv[o.conv].wbytes; a.bias = c->dconv[o.conv].bias;
-            a.wgt32 = c->dconv[o.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[o.conv].w32bytes;
-            a.B = B; a.Hi = H >> lev_in; a.Wi = W >> lev_in; a.k = d.k; a.s = d.s; a.act = d.act;
-            a.Ho = d.s == 2 ? a.Hi / 2 : a.Hi; a.Wo = d.s == 2 ? a.Wi / 2 : a.Wi;
-            a.Cin = d.cin; a.Cout = d.cout;
-            if (o.out >= 0) {
-                const Tensor& to = p.tensors[o.out];
-                a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_bs = a.Ho * a.Wo; a.out_ro = 0; a.out_f32 = 0; a.out_lo = to.C;
-            } else {
-                a.out = d_pred; a.out_ct = 64 + p.nc; a.out_coff = o.pred_coff; a.out_bs = A; a.out_ro = a_off[o.pred_level]; a.out_f32 = 1;
-            }
-            if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
+            ConvArgs a = conv_args(o);
             double flops = 2.0 * B * a.Ho * a.Wo * (double)a.Cout * a.Cin * a.k * a.k;
             if (pw_env && c->prec == PREC_F16 && o.fuse == FUSE_PW_PAIR && c->dconv[next->conv].w2f && conv_variant(c->prec, a) == CONV_DIRECT_256) {
                 const Op& n = *next;
@@ -765,6 +839,15 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     if (n_run < p.ops.size()) return CY_OK;                   // stopped: a deferred box branch stays unlaunched
     for (HeadPend& h : pend)                                  // a box branch whose class branch never came (no such plan today)
         if (h.on) { h.on = false; cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); }
+    if (box_sparse[0] || box_sparse[1] || box_sparse[2]) {
+        // the deferred box branches, behind the class columns on the same stream (the next pass on this stream overwrites the feature
+        // maps they read): slot maps to -1, counts to 0, then mark and the three stages.  No host read, no synchronisation; untimed in the
+        // profile summary.
+        HIPCHK(c, hipMemsetAsync(bx.L[0].map, 0xFF, (size_t)B * A * sizeof(int), s));
+        HIPCHK(c, hipMemsetAsync(bx.L[0].counts, 0, 8 * sizeof(int), s));
+        HIPCHK(c, launch_box_mark(bx, s));
+        HIPCHK(c, launch_box_sparse(bx, s));
+    }
     return CY_OK;
 }
 
@@ -838,6 +921,16 @@ int cy_debug_stop_after(cy_ctx* c, int n_ops) {
     if (!c) return CY_ERR_ARG;
     c->stop_after = n_ops > 0 ? n_ops : 0;
     return CY_OK;
+}
+
+int cy_debug_sparse_box(cy_ctx* c, const void* d_netin, int B, int H, int W, float* d_pred, float conf, int* h_sparse3, void* stream) {
+    if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
+    if (!h_sparse3) return fail(c, CY_ERR_ARG, "null argument");
+    c->split_last = false;
+    BoxReq box{conf, {0, 0, 0}, 1};
+    const int rc = forward_on(c, d_netin, B, H, W, d_pred, (hipStream_t)stream, c->ws, c->ws_bytes, false, 0, &box);
+    for (int l = 0; l < 3; ++l) h_sparse3[l] = box.sparse[l];
+    return rc;
 }
 
 int cy_debug_ops_done(cy_ctx* c) {
@@ -1342,10 +1435,10 @@ static int pipeline_batch(cy_ctx* c, const float* d_mosaic, int B, float conf, d
     HIPCHK(c, hipEventRecord(c->ev_pre[sl], c->s_pre));
     HIPCHK(c, hipStreamWaitEvent(sf, c->ev_pre[sl], 0));
     if (reuse) HIPCHK(c, hipStreamWaitEvent(sf, c->ev_post[sl], 0));
-    rc = forwards([&](const void* in, int H, int W, float* pred) -> int {
-        if (!small) return forward_split(c, in, B, H, W, pred, sm);
+    rc = forwards([&](const void* in, int H, int W, float* pred, BoxReq* box = nullptr) -> int {
+        if (!small) return forward_split(c, in, B, H, W, pred, sm, box);
         c->split_last = false;
-        return forward_on(c, in, B, H, W, pred, sf, c->ws3, c->ws3_bytes, true);      // (profiled like the main lane)
+        return forward_on(c, in, B, H, W, pred, sf, c->ws3, c->ws3_bytes, true, 0, box);      // (profiled like the main lane)
     });
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev_fwd[sl], sf));
@@ -1364,9 +1457,10 @@ int cy_detect_tiles(cy_ctx* c, const float* d_mosaic, int MH, int MW, const int*
     if (!c || !c->loaded) return fail(c, CY_ERR_STATE, "weights not loaded");
     cy_letterbox lb;
     if (cy_letterbox_geometry(th, tw, imgsz, &lb)) return fail(c, CY_ERR_ARG, "bad tile/imgsz");
+    BoxReq box{conf, {0, 0, 0}};
     return pipeline_batch(c, d_mosaic, B, conf, soft, hard, d_out, d_out_count, stream,
         [&](hipStream_t s) { return cy_preproc(c, d_mosaic, MH, MW, h_tiles, B, th, tw, imgsz, cfg, c->S().netin, d_status, s); },
-        [&](auto&& fwd) { return fwd(c->S().netin, lb.H, lb.W, c->S().pred); },
+        [&](auto&& fwd) { return fwd(c->S().netin, lb.H, lb.W, c->S().pred, &box); },      // the plain path: box logits at this call's candidates only
         [&](hipStream_t s) { return cy_decode_nms(c, c->S().pred, B, lb.H, lb.W, th, tw, conf, iou, c->S().det, c->S().det_anchor, c->S().det_count, s); });
 }
 

@@ -19,6 +19,82 @@ constexpr int MAXDET = 300;          // ultralytics max_det (CY_MAX_DET)
 constexpr int MAX_NMS = 30000;       // ultralytics max_nms
 constexpr float MAX_WH = 7680.0f;    // ultralytics max_wh (class offset)
 
+// ------------------------------------------------------------------------------------------------ candidate test
+// The confidence filter of non_max_suppression on one prediction row p (64 box logits, nc class logits): best sigmoid score and its
+// class (first maximum wins, as torch.max(1)), true when the anchor is a candidate.  A NaN score never is.  The ONE definition for
+// the decode kernels and for box_mark_kernel, which decides where the box logits are computed at all.
+__device__ __forceinline__ bool class_candidate(const float* p, int nc, float conf, float& best, int& bj) {
+    best = -1.0f; bj = 0;
+    for (int c = 0; c < nc; ++c) {
+        const float s = 1.0f / (1.0f + expf(-p[64 + c]));
+        if (s > best) { best = s; bj = c; }
+    }
+    return best > conf;
+}
+
+// ------------------------------------------------------------------------------------------------ box-branch work lists
+// Two launches, after the class columns of the prediction rows are written.  box_mark_kernel, one thread per anchor of the sparse
+// levels (cy_sparse_box.hip): a candidate is appended to its level's clist and flags the pixels of its in-map 3x3 neighbourhood in
+// the slot map (-1 -> -2, plain stores: every writer writes the same value).  box_compact_kernel, one thread per map word: a flagged
+// pixel is appended to its level's plist and its slot written back to the map, so each needed pixel is listed once however many
+// candidates share it.  Appends are aggregated per wave (one atomic per wave and level); the order of the lists is whatever the
+// atomics give and enters no value.
+__device__ __forceinline__ int wave_append(int* count, bool on, int lane) {      // slot of every `on` lane; wave-uniform call
+    const unsigned long long m = __ballot(on);
+    if (m == 0ull) return 0;
+    const int first = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == first) base = atomicAdd(count, __popcll(m));
+    return __shfl(base, first) + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(256) void box_mark_kernel(const BoxArgs a) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    int lvl = 0, r = i < a.A ? i : 0;
+    const int n0 = a.L[0].H * a.L[0].W, n1 = a.L[1].H * a.L[1].W;
+    if (r >= n0) { r -= n0; lvl = 1; if (r >= n1) { r -= n1; lvl = 2; } }
+    const BoxLevel& L = lvl == 0 ? a.L[0] : (lvl == 1 ? a.L[1] : a.L[2]);
+    float best; int bj;
+    const bool cand = i < a.A && L.sparse && class_candidate(a.pred + ((size_t)b * a.A + i) * (64 + a.nc), a.nc, a.conf, best, bj);
+    if (__ballot(cand) == 0ull) return;
+    const int HW = L.H * L.W, y = r / L.W, x = r - y * L.W;
+    for (int l = 0; l < 3; ++l) {                              // a wave may straddle two levels
+        const int slot = wave_append(a.L[l].counts + 1, cand && lvl == l, lane);
+        if (cand && lvl == l) L.clist[slot] = b * HW + r;
+    }
+    if (!cand) return;
+    for (int tap = 0; tap < 9; ++tap) {
+        const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+        if ((unsigned)yy < (unsigned)L.H && (unsigned)xx < (unsigned)L.W) L.map[b * HW + yy * L.W + xx] = -2;
+    }
+}
+
+__global__ __launch_bounds__(256) void box_compact_kernel(const BoxArgs a) {      // the three maps are one array of B * A words (launch_box_mark)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, tot = (long)a.B * a.A;
+    const int lane = threadIdx.x & 63;
+    const long e1 = (long)a.B * a.L[1].a_off, e2 = (long)a.B * a.L[2].a_off;
+    const int lvl = i >= e2 ? 2 : (i >= e1 ? 1 : 0);
+    const bool on = i < tot && a.L[0].map[i] == -2;
+    if (__ballot(on) == 0ull) return;
+    for (int l = 0; l < 3; ++l) {
+        const int slot = wave_append(a.L[l].counts, on && lvl == l, lane);
+        if (on && lvl == l) { a.L[l].plist[slot] = (int)(i - (long)a.B * a.L[l].a_off); a.L[0].map[i] = slot; }
+    }
+}
+
+hipError_t launch_box_mark(const BoxArgs& a, hipStream_t s) {
+    int A = 0;
+    for (int l = 0; l < 3; ++l) {
+        const BoxLevel& L = a.L[l];
+        if (L.H < 1 || L.W < 1 || L.a_off != A || (long)a.B * L.H * L.W != L.cap || L.map != a.L[0].map + (long)a.B * L.a_off) return hipErrorInvalidValue;
+        A += L.H * L.W;
+    }
+    if (A != a.A || a.B < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(box_mark_kernel, dim3((a.A + 255) / 256, a.B), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(box_compact_kernel, dim3((unsigned)(((long)a.B * a.A + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ decode
 // One thread per anchor, class logits first.  Alone on the GPU the kernel takes 59 us per 256 tiles of 512^2 (it touches the cache
 // lines that hold the class logits: 190 MB, 3.2 TB/s); inside the pipelined pass, on the low-priority post-processing stream beside the
@@ -37,12 +113,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
     const float stride = (float)(8 << lvl);
     const float* p = a.pred + ((size_t)b * a.A + i) * (64 + a.nc);
     // class scores first: most anchors fail the confidence test and skip the DFL work
-    float best = -1.0f; int bj = 0;
-    for (int c = 0; c < a.nc; ++c) {
-        const float s = 1.0f / (1.0f + expf(-p[64 + c]));
-        if (s > best) { best = s; bj = c; }        // first maximum wins, as torch.max(1)
-    }
-    if (!(best > a.conf)) return;
+    float best; int bj;
+    if (!class_candidate(p, a.nc, a.conf, best, bj)) return;
     float d[4];
 #pragma unroll
     for (int side = 0; side < 4; ++side) {
@@ -96,12 +168,8 @@ __global__ __launch_bounds__(256) void decode_augmented_kernel(const AugDecodeAr
     const float ax = (float)(r % gw) + 0.5f, ay = (float)(r / gw) + 0.5f;
     const float stride = (float)(8 << lvl);
     const float* p = v.pred + ((size_t)b * v.A + i) * (64 + a.nc);
-    float best = -1.0f; int bj = 0;
-    for (int c = 0; c < a.nc; ++c) {
-        const float s = 1.0f / (1.0f + expf(-p[64 + c]));
-        if (s > best) { best = s; bj = c; }
-    }
-    if (!(best > a.conf)) return;
+    float best; int bj;
+    if (!class_candidate(p, a.nc, a.conf, best, bj)) return;
     float d[4];
 #pragma unroll
     for (int side = 0; side < 4; ++side) {

@@ -207,6 +207,17 @@ class HipDetector(object):
         self._chk(self.lib.cy_forward(self.ctx, self._p(netin), B, H, Wd, self._p(pred), self._stream()))
         return pred
 
+    def forward_sparse_box(self, netin, conf, out):
+        """Test hook (cy_debug_sparse_box): the forward pass with the box branch of the detect head computed only at the anchors
+        whose best class score passes `conf`, into the caller's prediction tensor `out` (e.g. NaN-filled).  Returns (out, sparse)
+        with sparse[l] = 1 where stride level l was deferred and 0 where its shape kept the dense branch."""
+        B, H, Wd, _ = netin.shape
+        A = self.lib.cy_num_anchors(H, Wd)
+        assert out.shape == (B, A, 64 + self.nc) and out.dtype == torch.float32 and out.is_contiguous() and out.device == self.tdev
+        sparse = (C.c_int * 3)()
+        self._chk(self.lib.cy_debug_sparse_box(self.ctx, self._p(netin), B, H, Wd, self._p(out), float(conf), sparse, self._stream()))
+        return out, [int(v) for v in sparse]
+
     def weight_passes(self):
         """fp16x3 context: (convolutions on the two-pass form, on the three-pass form); (0, 0) in the other contexts."""
         out = (C.c_int * 2)()

@@ -140,6 +140,12 @@ int cy_debug_read_conv(cy_ctx* ctx, const char* conv_name, float* h_out, size_t 
  * cy_debug_read_tensor: channels [coff, coff + C) of plan tensor `tensor` as the last cy_forward left them, as fp32 [B][C][h][w]
  * (fp16x3 context: high + low half); tensor 0, the caller's input, is refused. */
 int cy_debug_stop_after(cy_ctx* ctx, int n_ops);
+/* test hook for the deferred box branch of the plain detect path (fp16 context): cy_forward's pass with the box branch of every
+ * supported level computed ONLY at the anchors whose best class score passes `conf` (as CY_SPARSE_BOX=2 does inside
+ * cy_detect_tiles).  Class columns of d_pred are written at every anchor; box columns (0..63) of a deferred level at candidates
+ * only, the rest keep what the caller put there.  h_sparse3[l] = 1 when level l was deferred, 0 when its shape kept the dense
+ * branch (then all of its box columns are written).  Other contexts: all levels dense. */
+int cy_debug_sparse_box(cy_ctx* ctx, const void* d_netin, int B, int H, int W, float* d_pred, float conf, int* h_sparse3, void* stream);
 int cy_debug_ops_done(cy_ctx* ctx);
 int cy_debug_read_tensor(cy_ctx* ctx, int tensor, int coff, int C, float* h_out, size_t cap_elems, int* dims4);
 

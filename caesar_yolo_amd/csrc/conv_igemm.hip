@@ -18,7 +18,8 @@
 // fragment reads are conflict-free (slot = chunk ^ (row & 7): conflict-free for any 16 consecutive rows, whatever the first row -- the 3x3 taps of the
 // halo kernels read at arbitrary row offsets; a 256-byte bank row holds two 128-byte tile rows).
 //
-// This file holds the implicit-GEMM kernels, their launchers and the dispatch (conv_variant, launch_conv) and nothing else: the
+// This file holds the implicit-GEMM kernels and their launchers, and launch_conv, which makes the launcher call that a ConvChoice
+// names (the decision itself is host code without HIP: conv_choose, cy_conv_plan.cpp), and nothing else: the
 // device prelude and the shared epilogue steps are in cy_conv_dev.h, the stem kernels in conv_stem.hip, weight packing in
 // conv_weights.hip, the SPPF pool with the other non-GEMM layer operators in cy_extra.hip.
 #include "cy_kernels.h"
@@ -2152,23 +2153,13 @@ static hipError_t launch_widep(const ConvArgs& a, hipStream_t s) {
     return a.split ? launch_widep_t<0, true>(a, s, total, StripGeo{}) : launch_widep_t<0>(a, s, total, StripGeo{});
 }
 
-// idle share of the MFMA lanes of the 2-D patch form (16 x 32-pixel patches) and of the strip form on an H x W map
-static double wide2d_cover(int H, int W) { return (double)((H + 15) / 16 * 16) * ((W + 31) / 32 * 32) / ((double)H * W); }
-static double strip_cover(int H, int W) { return (double)(H + 1) * (W + 1) / ((double)H * W); }
-// maps from 17 px wide (narrower ones down to 13 px belong to the dual-image / two-tap kernels), and the maps of a few pixels that no
-// patch shape fits (8 x 8 and 4 x 4: the stride-16 / 32 levels of 128- and 256-px inputs): 27 % / 56 % idle lanes there instead of 75 % / 94 %
-static bool strip_small(const ConvArgs& a) { return a.Wi >= 3 && a.Wi <= 12 && a.Hi >= 3 && a.Hi <= 126; }
-static bool strip_fits(const ConvArgs& a) {
-    return ((a.Wi >= 17 && a.Hi >= 17 && a.Wi <= 126) || strip_small(a)) && a.Cout % 16 == 0 && (long)a.B * (a.Hi + 1) * (a.Wi + 1) < (1L << 22);
-}
-
+template <int STRIP, bool SPLIT = false>
 static hipError_t launch_strip(const ConvArgs& a, hipStream_t s) {
     StripGeo sg;
     sg.RS = a.Wi + 1; sg.IS = (a.Hi + 1) * sg.RS; sg.NE = a.B * sg.IS;
     sg.mRS = ((1ull << 40) + sg.RS - 1) / sg.RS; sg.mIS = ((1ull << 40) + sg.IS - 1) / sg.IS;
     const int total = ((sg.NE + 511) / 512) * ((pad64(a.Cout) + 127) / 128);
-    if (a.split) return a.Wi <= 62 ? launch_widep_t<10, true>(a, s, total, sg) : launch_widep_t<12, true>(a, s, total, sg);
-    return a.Wi <= 62 ? launch_widep_t<10>(a, s, total, sg) : launch_widep_t<12>(a, s, total, sg);
+    return launch_widep_t<STRIP, SPLIT>(a, s, total, sg);
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 (and 3x3 stride 2), pixels direct to registers
@@ -2577,17 +2568,7 @@ static hipError_t launch_t(const ConvArgs& a, hipStream_t s) {
     return launch_lds<conv_igemm_kernel<T, WM, WN, MI, NSTAGE, SPLIT>>(dim3(ntm * ntn), dim3(WM * WN * 64), lds, lds, s, a);
 }
 
-// head1x1_kernel: which layers it takes, and its launch -- the detect head's output 1x1s (fp32 prediction rows, no activation) and, since
-// the end of round 4, every other single-segment 1x1 with <= 64 output channels and Cin a multiple of 64 (fp16 / split outputs into a
-// channel slice, SiLU, residual).  Geometry only (no batch threshold), so a tile's result does not depend on its batch.
-static int head_rows(const ConvArgs& a) { const int c = a.Cout < 16 ? a.Cout : 16; const int g = (c + 3) / 4; return 16 * (g < 4 ? g : 4); }
-static bool head_direct(const ConvArgs& a, int passes) {
-    if (!env_knob("CY_HEAD_DIRECT", 1)) return false;             // read per call: the parity tests run both forms
-    if (!(a.k == 1 && a.s == 1 && a.c1 == 0 && !a.up0 && a.Cin >= 64 && a.Cin % 64 == 0 && a.c0 == a.Cin && pad64(a.Cout) == 64 && a.Ho == a.Hi && a.Wo == a.Wi))
-        return false;
-    if (a.out_f32 ? (a.res || a.act) : (a.out_bs != a.Ho * a.Wo || a.out_ro != 0 || !env_knob("CY_NARROW_DIRECT", 1))) return false;      // head rows: no residual / activation; inside the network: plain pixel order
-    return (size_t)passes * (a.Cin / 64) * head_rows(a) * 128 <= 65536;
-}
+// head1x1_kernel's launch (which layers it takes: head_direct, cy_conv_plan.cpp)
 template <bool SPLIT>
 static hipError_t launch_head(const ConvArgs& a, hipStream_t s) {
     const int nrows = head_rows(a);
@@ -2598,19 +2579,7 @@ static hipError_t launch_head(const ConvArgs& a, hipStream_t s) {
 }
 
 // the two output convolutions of a stride level as one launch (head1x1_pair_kernel): a = box branch (64 channels at column 0),
-// b = class branch (nc channels at column 64) of the same pixels and prediction rows
-static int head_pair_pitch(int rowlen) { int tp = rowlen; while (tp % 8 != 4) ++tp; return tp; }      // conflict-free b128 rows
-static size_t head_pair_lds(Precision p, const ConvArgs& a, const ConvArgs& b) {
-    const size_t pa = p == PREC_F16X3 ? a.split : 1, pb = p == PREC_F16X3 ? b.split : 1;
-    return pa * (a.Cin / 64) * 64 * 128 + pb * (b.Cin / 64) * head_rows(b) * 128 + (size_t)8 * 16 * head_pair_pitch(a.out_ct) * 4;
-}
-bool head_pair_ok(Precision p, const ConvArgs& a, const ConvArgs& b) {
-    if (p == PREC_F32 || !env_knob("CY_HEAD_PAIR", 1)) return false;       // read per call: the parity tests run both forms
-    if (conv_variant(p, a) != CONV_HEAD_1X1 || conv_variant(p, b) != CONV_HEAD_1X1) return false;
-    if (a.B != b.B || a.Ho != b.Ho || a.Wo != b.Wo || a.out != b.out || a.out_ct != b.out_ct || a.out_bs != b.out_bs || a.out_ro != b.out_ro) return false;
-    if (a.out_coff != 0 || a.Cout != 64 || b.out_coff != 64 || b.Cout < 1 || b.Cout != a.out_ct - 64) return false;
-    return head_pair_lds(p, a, b) <= 128 * 1024;
-}
+// b = class branch (nc channels at column 64) of the same pixels and prediction rows (head_pair_ok, cy_conv_plan.cpp)
 hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, hipStream_t s) {
     const size_t lds = head_pair_lds(p, a, b);
     lds_cap<head1x1_pair_kernel<false>>(128 * 1024);              // both before the first launch of either
@@ -2622,163 +2591,36 @@ hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, h
     return launch_lds<head1x1_pair_kernel<false>>(dim3(grid), dim3(512), lds, 128 * 1024, s, a, b, head_rows(b), head_pair_pitch(a.out_ct));
 }
 
-// Kernel variants (also the keys of the profiling summary)
-static const char* const kVariantNames[CONV_NUM_VARIANTS] = {
-    "conv_igemm_kernel<2,2,4> generic 128x128", "conv_igemm_kernel<4,1,2> generic 128x64",
-    "conv3x3_halo2_kernel 3x3 s1 16x16px x128ch (halo<2,2> for odd slab counts)", "conv3x3_pp_kernel<2> 3x3 s1 16x16px x64ch",
-    "conv3x3_c64_kernel<64|32> 3x3 s1 persistent, Cin 64 or 32", "conv_igemm_kernel<4,2,4,3> generic 256x128, 3-slab ring",
-    "conv3x3_wide_kernel 3x3 s1 16x32px x128ch, K slabs of 32",
-    "conv1x1_direct_kernel<4,2> 1x1 256px x256ch, pixels to regs", "conv1x1_direct_kernel<2,2> 1x1 256px x128ch, pixels to regs",
-    "conv3x3_wide_kernel<WN=1> 3x3 s1 16x32px x64ch", "conv3x3_wide_kernel<dual> 3x3 s1 2 images x 16x16px x128ch",
-    "conv3x3_widep_kernel<strip> 3x3 s1 512 flattened px x128ch, persistent",
-    "head1x1_kernel detect-head output 1x1, weights stationary in LDS, fp32 rows"};
-const char* conv_variant_name(int v) { return v >= 0 && v < CONV_NUM_VARIANTS ? kVariantNames[v] : "?"; }
+// The launcher call a ConvChoice names: one per kernel value, no decision.  Only the instantiation follows from the precision: the
+// three-pass (SPLIT) form in the fp16x3 context, the float form of the generic kernel in fp32 (conv_choose gives a context the
+// kernels it has).  with_dbg: the developer ablation bits of the kernels that look at them (0 in the product binary).
+static ConvArgs with_dbg(const ConvArgs& a) { ConvArgs b = a; b.dbg = dev_knob("CY_DBG", 0); return b; }
 
-// Batch-invariant kernel selection (default; CY_BATCH_INVARIANT=0 turns it off): every batch-size threshold below (and the
-// stem fusion) is evaluated as if the batch held >= 256 tiles, so a layer always runs the SAME kernel and a tile's fp16
-// results do not depend on how many tiles share its batch: catalogs are identical for any world size / batch split, as the
-// reference's are for any MPI size.  Price: big-batch kernels on small batches (1 % of the 16k-mosaic rate; a single
-// image runs kernels tuned for 256).  With 0 the thresholds see the real batch: fastest per batch size, last-bit differences
-// between batch sizes.
-bool batch_invariant() { const char* e = getenv("CY_BATCH_INVARIANT"); return !e || atoi(e) != 0; }
-
-// fp16x3 context: the kernels that carry the three-pass K walk -- the 512-px wide 3x3 kernel (128- / 64-channel / dual-image forms),
-// the pixels-direct 1x1 / strided-3x3 kernel and the generic implicit GEMM for everything else.  The choice depends on the layer's
-// geometry only, so a tile's result does not depend on the batch it travels in -- with one bound: the strip form addresses the
-// flattened batch with 22 bits (strip_fits: B * (H + 1) * (W + 1) < 2^22), which a launch can only exceed beyond the 4 GiB a tensor
-// may hold in this context (128 tiles of 640^2: 2^19.6 entries on the largest strip-form map), where cy_forward refuses the batch.
-static int conv_variant_x3(const ConvArgs& a) {
-    const bool narrow = pad64(a.Cout) <= 64;
-    if (a.k == 3 && a.s == 1 && a.c1 == 0 && !a.up0 && !a.out_f32 && a.Cin % 64 == 0 && a.wgt32 && a.out_bs == a.Ho * a.Wo && a.out_ro == 0) {
-        const int wpad = (a.Wi + 31) / 32 * 32;
-        const bool fits = (wpad - a.Wi) * 8 <= a.Wi;
-        if (narrow && a.Wi % 32 == 0) return CONV_WIDE_64;
-        if (narrow && a.Cin >= 128 && env_knob("CY_STRIP", 1) && strip_small(a) && strip_fits(a)) return CONV_STRIP_128;       // (see conv_variant)
-        // strip form where 16 x 32 patches would idle > 4 % more lanes (geometry only: no batch threshold in this context)
-        if (!narrow && env_knob("CY_STRIP", 1) && strip_fits(a) && strip_cover(a.Hi, a.Wi) + 0.04 < wide2d_cover(a.Hi, a.Wi)) return CONV_STRIP_128;
-        if (!narrow && fits) return CONV_WIDE_128;
-        if (!narrow && a.Wi <= 16 && a.Wi >= 14) return CONV_WIDE_DUAL;
-    }
-    if (!a.out_f32 && a.Cin % 64 == 0 && !narrow &&
-        ((a.k == 1 && a.s == 1 && (a.c1 == 0 || a.c0 % 64 == 0)) || (a.k == 3 && a.s == 2 && a.c1 == 0 && !a.up0)))
-        return pad64(a.Cout) >= 256 ? CONV_DIRECT_256 : CONV_DIRECT_128;
-    if (head_direct(a, a.split)) return CONV_HEAD_1X1;
-    return narrow ? CONV_GENERIC_64 : CONV_GENERIC_128;
-}
-
-int conv_variant(Precision p, const ConvArgs& a) {
-    if (p == PREC_F16X3) return conv_variant_x3(a);
-    const bool narrow = pad64(a.Cout) <= 64;
-    const long Bv = batch_invariant() && a.B < 256 ? 256 : a.B;     // the batch size the thresholds see
-    // 3x3 stride-1 layers (fp16 context; the fp32 parity context keeps the generic kernel): halo-reuse kernels.
-    //   Cout <= 64  : ping-pong kernel with 64-channel tiles (256 px x 64 ch per workgroup)
-    //   Cout >= 128 : 8x16-pixel patches x 128 channels, two workgroups per CU
-    if (p == PREC_F16 && a.k == 3 && a.s == 1 && a.c1 == 0 && !a.up0 && !a.out_f32 && a.Cin == 32 && narrow && a.wgt32 &&
-        a.out_bs == a.Ho * a.Wo && a.out_ro == 0)
-        return CONV_C64_PERSIST;                             // 32-channel variant of the persistent kernel
-    if (p == PREC_F16 && a.k == 3 && a.s == 1 && a.c1 == 0 && !a.up0 && !a.out_f32 && a.Cin % 64 == 0 &&
-        a.out_bs == a.Ho * a.Wo && a.out_ro == 0) {
-        // 64-channel variant of the wide kernel for the box-head convs with deep inputs, when it fills the chip
-        if (narrow && a.wgt32 && a.Cin >= 128 && a.Wi % 32 == 0 && Bv * ((a.Hi + 15) / 16) * (a.Wi / 32) >= 256) return CONV_WIDE_64;
-        // 64 output channels on maps of a few pixels with deep inputs (the box head of 128- / 256-px inputs): the strip form with half
-        // of its channel tile empty still beats the 16 x 16-pixel patches of the 64-channel kernels there (68 -> ~250 TFLOP/s on 4 x 4 maps)
-        if (narrow && a.wgt32 && a.Cin >= 128 && env_knob("CY_STRIP", 1) && strip_small(a) && strip_fits(a)) return CONV_STRIP_128;
-        if (narrow && a.Cin == 64) return CONV_C64_PERSIST;
-        if (narrow) return CONV_PP_64;
-        // strip form of the wide kernel (maps flattened to one dimension) where 16 x 32-pixel patches would leave > 4 % more of the MFMA
-        // lanes idle: 80 / 40 / 20-px maps of 640-px inputs, 52 x 64 / 26 x 32 maps of the ragged 416 x 512 tiles.  CY_STRIP: 0 off,
-        // 2 regardless of the launch size (tests); read per call.
-        const int strip = env_knob("CY_STRIP", 1);
-        if (strip && a.wgt32 && strip_fits(a) && strip_cover(a.Hi, a.Wi) + 0.04 < wide2d_cover(a.Hi, a.Wi) &&
-            (strip > 1 || strip_small(a) || Bv * (long)(a.Hi + 1) * (a.Wi + 1) / 512 * ((pad64(a.Cout) + 127) / 128) >= 200))      // (about one strip per CU; tiny maps: every alternative idles more)
-            return CONV_STRIP_128;
-        const int wpad = (a.Wi + 31) / 32 * 32;
-        if (a.wgt32 && (wpad - a.Wi) * 8 <= a.Wi) return CONV_WIDE_128;     // <= 12.5 % of the patch columns idle
-        const int dual = getenv("CY_WIDE_DUAL") ? atoi(getenv("CY_WIDE_DUAL")) : 1;      // read per call: 2 forces it (tests)
-        // two 16-px-wide images side by side: +8 % over the two-tap halo kernel once it still fills the chip (half as many
-        // workgroups), slower below that
-        if (dual && a.wgt32 && a.Wi <= 16 && a.Wi >= 14 &&
-            ((Bv + 1) / 2) * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + 127) / 128) >= (dual > 1 ? 1 : 224))
-            return CONV_WIDE_DUAL;
-        return CONV_HALO8_128;
-    }
-    if (p == PREC_F16 && head_direct(a, 1)) return CONV_HEAD_1X1;
-    if (narrow) return CONV_GENERIC_64;
-    // 1x1: pixels-direct kernel once there is at least one 256-pixel tile per CU (below that the 128x128 tiles of the generic
-    // kernel fill the chip better).  CY_DIRECT_MIN_BLOCKS is read per call so that the parity tests can force the path.
-    if (p == PREC_F16 && !a.out_f32 && a.Cin % 64 == 0 &&
-        ((a.k == 1 && a.s == 1 && (a.c1 == 0 || a.c0 % 64 == 0)) || (a.k == 3 && a.s == 2 && a.c1 == 0 && !a.up0 && (a.Cin >= 128 || pad64(a.Cout) < 256)))) {
-        const char* e = getenv("CY_DIRECT_MIN_BLOCKS");
-        const long min_blocks = e ? atol(e) : 256;
-        const int bn = pad64(a.Cout) >= 256 ? 256 : 128;
-        const long blocks = ((Bv * a.Ho * a.Wo + 255) / 256) * ((pad64(a.Cout) + bn - 1) / bn);
-        if (min_blocks >= 0 && blocks >= min_blocks) return bn == 256 ? CONV_DIRECT_256 : CONV_DIRECT_128;
-    }
-    // 1x1 and strided convs with enough 256-pixel tiles to fill the chip: deeper-pipelined 256x128 tile
-    const long M = Bv * a.Ho * a.Wo;
-    if (p == PREC_F16 && (M / 256) * ((pad64(a.Cout) + 127) / 128) >= 256) return CONV_GENERIC_BIG;
-    return CONV_GENERIC_128;
-}
-
-hipError_t launch_conv(Precision p, const ConvArgs& a, hipStream_t s) {
-    if (p == PREC_F16X3) {
-        if ((a.split != 2 && a.split != 3) || !a.oscale) return hipErrorInvalidValue;
-        switch (conv_variant_x3(a)) {
-            case CONV_WIDE_128:      // persistent form (bit-identical) with CY_X3_PERSIST=1: measured before it became a default
-                if (env_knob("CY_X3_PERSIST", 0) && a.Cout % 16 == 0) return launch_widep(a, s);
-                return launch_wide<2, false, true>(a, s);
-            case CONV_STRIP_128: return launch_strip(a, s);
-            case CONV_WIDE_64: return launch_wide<1, false, true>(a, s);
-            case CONV_WIDE_DUAL: return launch_wide<2, true, true>(a, s);
-            case CONV_DIRECT_256: return a.k == 3 ? launch_direct<4, 2, 3, true, true>(a, s) : launch_direct<4, 2, 3, false, true>(a, s);
-            case CONV_DIRECT_128: return a.k == 3 ? launch_direct<2, 4, 2, true, true>(a, s) : launch_direct<2, 2, 2, false, true>(a, s);
-            case CONV_HEAD_1X1: return launch_head<true>(a, s);
-            case CONV_GENERIC_64: return launch_t<f16, 4, 1, 2, 2, true>(a, s);
-            default: return launch_t<f16, 2, 2, 4, 2, true>(a, s);
-        }
-    }
-    switch (conv_variant(p, a)) {
-        case CONV_C64_PERSIST: return a.Cin == 32 ? launch_c64<32>(a, s) : launch_c64<64>(a, s);
-        case CONV_PP_64: return launch_pp<2>(a, s);
-        case CONV_HALO8_128: {
-            ConvArgs b2 = a; b2.dbg = dev_knob("CY_DBG", 0);
-            if ((a.Cin / 64) % 2 == 0) return launch_halo2(b2, s);      // two taps per barrier: walks the 64-channel slabs in pairs
-            return launch_halo<2, 2>(b2, s);
-        }
-        case CONV_GENERIC_BIG: return launch_t<f16, 4, 2, 4, 3>(a, s);
-        case CONV_WIDE_128: {
-            ConvArgs b2 = a; b2.dbg = dev_knob("CY_DBG", 0);
-            // persistent form (same arithmetic in the same order: bit-identical outputs) when every CU gets at least two patches
-            // and the output tile has whole 16-channel groups; CY_WIDE_PERSIST: 0 off, 2 regardless of the launch size (tests)
-            const int wp = env_knob("CY_WIDE_PERSIST", 1);
-            const long patches = (long)a.B * ((a.Wi + 31) / 32) * ((a.Hi + 15) / 16) * ((pad64(a.Cout) + 127) / 128);
-            // Measured per layer at batch 256: 18-stage layers (Cin 128: model.4 / model.15 bottlenecks) -4..-6 %, 36-stage ones
-            // -1.7..+1.5 %: taken for up to two slab pairs.
-            if (wp && a.Cout % 16 == 0 && (wp > 1 || (patches >= 512 && a.Cin <= 128))) return launch_widep(b2, s);
-            return launch_wide<2>(b2, s);
-        }
-        case CONV_STRIP_128: return launch_strip(a, s);
-        case CONV_WIDE_64: return launch_wide<1>(a, s);
-        case CONV_WIDE_DUAL: return launch_wide<2, true>(a, s);
-        case CONV_DIRECT_256: {
-            ConvArgs a2 = a; a2.dbg = dev_knob("CY_DBG", 0);
-            // (tried, not kept: 128 px x 256 ch tiles with two workgroups per CU, 2-12 % slower on every 256-channel 1x1 layer but
-            // model.4.cv1 (-4 %): twice the weight pieces per MFMA cost more than the overlap buys; a 4-slot ring for this tile:
-            // 256 VGPRs with spills, 3-10 % slower)
-            // weight requests on 4 waves (one per SIMD) for the strided 3x3 layers, on all 8 for the 1x1s (same bits either way).  Measured
-            // per layer at batch 256: four requesting waves are 2-5 % faster on model.5 / model.7 and 1-6 % slower on the 1x1s
-            // back-to-back pair (the runtime sets wgt2 when this layer's only reader is a 256 -> <= 256 1x1 and the tile holds all channels)
-            if (a.wgt2 && pad64(a.Cout) == 256 && a.c1 == 0 && !a.res && !a.out_f32)
-                return a.k == 3 ? launch_direct<4, 2, 3, true, false, 4, true>(a2, s) : launch_direct<4, 2, 3, false, false, 8, true>(a2, s);
-            return a.k == 3 ? launch_direct<4, 2, 3, true, false, 4>(a2, s) : launch_direct<4, 2, 3, false>(a2, s);
-        }
-        case CONV_DIRECT_128:     // strided 3x3 (model.1): 64 px per wave, so every weight fragment feeds four MFMAs (-8 % vs 32 px)
-            // 1x1 with a 128-channel tile = the HBM-bound layers (model.2.cv1/cv2): two workgroups per CU (126 VGPRs, one chunk
-            // ahead) overlap each other's prologue/epilogue: -12 % against one workgroup with a 4-chunk ring
-            return a.k == 3 ? launch_direct<2, 4, 2, true>(a, s) : launch_direct<2, 2, 2, false>(a, s);
-        case CONV_HEAD_1X1: return launch_head<false>(a, s);
-        case CONV_GENERIC_64: return p == PREC_F16 ? launch_t<f16, 4, 1, 2>(a, s) : launch_t<float, 4, 1, 2>(a, s);
-        default: return p == PREC_F16 ? launch_t<f16, 2, 2, 4>(a, s) : launch_t<float, 2, 2, 4>(a, s);
+hipError_t launch_conv(Precision p, const ConvChoice& choice, const ConvArgs& a, hipStream_t s) {
+    const bool x3 = p == PREC_F16X3, f32 = p == PREC_F32;
+    switch (choice.kernel) {
+        case CK_WIDE_128: return x3 ? launch_wide<2, false, true>(a, s) : launch_wide<2>(with_dbg(a), s);
+        case CK_WIDE_128_PERSIST: return x3 ? launch_widep(a, s) : launch_widep(with_dbg(a), s);
+        case CK_STRIP_10: return x3 ? launch_strip<10, true>(a, s) : launch_strip<10>(a, s);
+        case CK_STRIP_12: return x3 ? launch_strip<12, true>(a, s) : launch_strip<12>(a, s);
+        case CK_WIDE_64: return x3 ? launch_wide<1, false, true>(a, s) : launch_wide<1>(a, s);
+        case CK_WIDE_DUAL: return x3 ? launch_wide<2, true, true>(a, s) : launch_wide<2, true>(a, s);
+        case CK_HALO2: return launch_halo2(with_dbg(a), s);
+        case CK_HALO_2_2: return launch_halo<2, 2>(with_dbg(a), s);
+        case CK_PP_2: return launch_pp<2>(a, s);
+        case CK_C64_64: return launch_c64<64>(a, s);
+        case CK_C64_32: return launch_c64<32>(a, s);
+        case CK_DIRECT_256_K1: return x3 ? launch_direct<4, 2, 3, false, true>(a, s) : launch_direct<4, 2, 3, false>(with_dbg(a), s);
+        case CK_DIRECT_256_K3: return x3 ? launch_direct<4, 2, 3, true, true>(a, s) : launch_direct<4, 2, 3, true, false, 4>(with_dbg(a), s);
+        case CK_DIRECT_256_K1_FUSE2: return launch_direct<4, 2, 3, false, false, 8, true>(with_dbg(a), s);
+        case CK_DIRECT_256_K3_FUSE2: return launch_direct<4, 2, 3, true, false, 4, true>(with_dbg(a), s);
+        case CK_DIRECT_128_K1: return x3 ? launch_direct<2, 2, 2, false, true>(a, s) : launch_direct<2, 2, 2, false>(a, s);
+        case CK_DIRECT_128_K3: return x3 ? launch_direct<2, 4, 2, true, true>(a, s) : launch_direct<2, 4, 2, true>(a, s);
+        case CK_HEAD: return x3 ? launch_head<true>(a, s) : launch_head<false>(a, s);
+        case CK_GENERIC_BIG: return launch_t<f16, 4, 2, 4, 3>(a, s);
+        case CK_GENERIC_64: return x3 ? launch_t<f16, 4, 1, 2, 2, true>(a, s) : f32 ? launch_t<float, 4, 1, 2>(a, s) : launch_t<f16, 4, 1, 2>(a, s);
+        case CK_GENERIC_128: return x3 ? launch_t<f16, 2, 2, 4, 2, true>(a, s) : f32 ? launch_t<float, 2, 2, 4>(a, s) : launch_t<f16, 2, 2, 4>(a, s);
+        default: return hipErrorInvalidValue;      // CK_BAD_ARGS
     }
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "cy_measure_jobs.h"
+#include "cy_conv_plan.h"      // Precision, ConvArgs, ConvVariant, ConvChoice, pad64 / pad128: the conv dispatch (host code without HIP)
 
 namespace cy {
 
@@ -36,43 +37,6 @@ template <auto Kernel, typename... A> hipError_t launch_lds(dim3 grid, dim3 bloc
     hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
     return hipGetLastError();
 }
-
-// PREC_F16X3 ("fp16x3", the fast parity context): every activation is stored as TWO fp16 values hi = fp16(x), lo = fp16(x - hi)
-// (22 significand bits), weights likewise after a per-output-channel power-of-two scale that keeps their low halves out of the
-// fp16 subnormal range; a product x*w is evaluated as hi*hi + lo*hi + hi*lo on the fp16 matrix cores with fp32 accumulation
-// (the dropped lo*lo term is 2^-22 relative), i.e. a layer is the tuned fp16 kernel over 3x the K.  Activation buffers keep the
-// NHWC channel-slice scheme with 2*C halves per pixel: [C high halves | C low halves].
-enum Precision { PREC_F16 = 0, PREC_F32 = 1, PREC_F16X3 = 2 };
-
-// One fused Conv2d(+folded BN bias)(+SiLU)(+residual) over NHWC activations, as an implicit GEMM:
-//   out[pix, n] = act( sum_{tap,c} in[pix(tap), c] * w[n, tap, c] + bias[n] ) (+ res[pix, n])
-// Input may be the channel-concat of two NHWC segments (k == 1 only); segment 0 may be read through a
-// nearest x2 upsample (nn.Upsample + Concat of yolov8 layers 10-11 / 13-14 folded into the consumer).
-struct ConvArgs {
-    const void* in0; int in0_ct, in0_coff, c0, up0;   // segment 0: base, channels per pixel of the buffer, channel offset, #channels
-    const void* in1; int in1_ct, in1_coff, c1;        // segment 1 (c1 == 0: absent)
-    const void* wgt;                                   // packed [K chunk][k*k][Cout_pad128][128 B]; rows permuted per 64 (pack_weights)
-    const void* wgt32; uint32_t wgt32_bytes;           // second copy with 64-byte K chunks (3x3 s1 fp16 layers, conv3x3_wide_kernel) or null
-    const float* bias;                                 // [Cout_pad64]
-    void* out; int out_ct, out_coff;                   // NHWC destination slice
-    int out_bs, out_ro;                                // destination pixel = b*out_bs + out_ro + (ho*Wo+wo)
-    int out_f32;                                       // 1: store fp32 regardless of the activation type (detect head)
-    const void* res; int res_ct, res_coff;             // residual source (same pixel grid) or null
-    int B, Hi, Wi, Ho, Wo, Cin, Cout, k, s, act;
-    uint32_t in0_bytes, in1_bytes, wgt_bytes;          // buffer extents for the hardware range check
-    int dbg;                                           // developer ablation bits (0 in production)
-    // fp16x3 context (split = passes over K: 3, or 2 when the layer's weights are fp16-exact up to a per-channel scale; 0 elsewhere): *_ct are in halves (2 * channels of the tensor); the low halves of a slice sit *_lo halves behind
-    // its high halves.  wgt / wgt32 then hold 3 passes over K: [w_hi | w_lo | w_hi] against inputs [x_lo | x_hi | x_hi]; oscale[n] is
-    // the power of two that undoes the weight scale of output channel n (applied to the accumulator before the bias).
-    int split, in0_lo, in1_lo, out_lo, res_lo;
-    const float* oscale;                               // [Cout_pad128] or null
-    // back-to-back fusion (fp16 context, pixels-direct kernel with a 256-channel tile that holds ALL output channels of its pixels): the
-    // fused Conv+bias+SiLU result of this layer is not stored but multiplied, in registers, by the 1x1 convolution that is its only
-    // reader: wgt2 = that layer's packed weights with its INPUT channels permuted to the accumulator order of the kernel
-    // (pack_weights_fused2), bias2 / act2 / out2* its bias, activation and destination slice (same pixel grid).  wgt2 == null: off.
-    const void* wgt2; uint32_t wgt2_bytes; const float* bias2; int act2, cout2;
-    void* out2; int out2_ct, out2_coff;
-};
 
 // First layer (Cin = 3 stored as 4, k=3, s=2): direct convolution.
 struct StemArgs {
@@ -126,12 +90,8 @@ struct AttnArgs {   // softmax(q^T k * scale) applied to v, per head; qkv channe
 hipError_t launch_dwconv(Precision p, const DwArgs& a, hipStream_t s);
 hipError_t launch_attention(Precision p, const AttnArgs& a, hipStream_t s);
 
-hipError_t launch_conv(Precision p, const ConvArgs& a, hipStream_t s);
-enum ConvVariant { CONV_GENERIC_128 = 0, CONV_GENERIC_64, CONV_HALO8_128, CONV_PP_64, CONV_C64_PERSIST, CONV_GENERIC_BIG, CONV_WIDE_128, CONV_DIRECT_256, CONV_DIRECT_128, CONV_WIDE_64, CONV_WIDE_DUAL, CONV_STRIP_128, CONV_HEAD_1X1, CONV_NUM_VARIANTS };
-int conv_variant(Precision p, const ConvArgs& a);          // which kernel launch_conv picks
-const char* conv_variant_name(int v);
-// the two output 1x1s of a detect-head level (box branch a, class branch b) in one launch of head1x1_pair_kernel (conv_igemm.hip)
-bool head_pair_ok(Precision p, const ConvArgs& a, const ConvArgs& b);
+hipError_t launch_conv(Precision p, const ConvChoice& choice, const ConvArgs& a, hipStream_t s);      // the launcher call conv_choose named (cy_conv_plan.h)
+// the two output 1x1s of a detect-head level (box branch a, class branch b) in one launch of head1x1_pair_kernel (conv_igemm.hip), where head_pair_ok
 hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, hipStream_t s);
 void debug_read_stamps(unsigned long long* out8, bool reset);
 void debug_read_wg_stamps(unsigned long long* out, int n);      // raw per-workgroup phase records (n x 4), stamped builds   // developer diagnostics (CY_DBG=64)
@@ -140,7 +100,6 @@ void debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, double*
 hipError_t launch_stem(Precision p, const StemArgs& a, hipStream_t s);
 hipError_t launch_stem_down(const StemDownArgs& a, hipStream_t s);
 long stem_down_blocks(const StemDownArgs& a);
-bool batch_invariant();                                            // CY_BATCH_INVARIANT=1 (conv_igemm.hip)
 void pack_stem_weights2(const float* W, int cout, void* dst);     // 64*64 fp16, k = tap*4 + c (taps 0..7), 32 + c (tap 8)
 hipError_t launch_pool5(Precision p, const PoolArgs& a, hipStream_t s);
 
@@ -170,8 +129,6 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
 }
-__host__ __device__ inline int pad64(int c) { return (c + 63) / 64 * 64; }
-__host__ __device__ inline int pad128(int c) { return (c + 127) / 128 * 128; }
 
 // ---- detection post-processing --------------------------------------------------------------
 struct DecodeArgs {

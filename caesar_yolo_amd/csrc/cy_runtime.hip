@@ -224,7 +224,8 @@ hipError_t upload_bias(DevOwner& own, const float* b, int co, float** out) {
 // The device copies of one dense convolution (weight loader and cy_conv_bn_silu): bias, the packed main panel, and the second copy
 // with 64-byte K chunks for the kernels that read that form (conv3x3_wide_kernel / conv3x3_c64_kernel<32>); in the fp16x3 context
 // also the pass count and the per-channel output scale.  down_copy: the 3x3 s2 64 -> 128 layer gets the second copy too
-// (stem_down_kernel reads its weight fragments from it, and conv_variant looks at wgt32: the loader asks for it, the test entry not).
+// (stem_down_kernel reads its weight fragments from it, and conv_choose looks at wgt32: the loader asks for it, the test entry not).
+// Which layers get the second copy: conv_second_copy (cy_conv_plan.cpp), beside the variant conditions that rely on it.
 hipError_t upload_conv(DevOwner& own, Precision prec, const float* W, const float* b, const float* wscale, int co, int ci, int k, int s,
                        bool down_copy, DevConv& dc) {
     hipError_t e = upload_bias(own, b, co, &dc.bias);
@@ -243,10 +244,7 @@ hipError_t upload_conv(DevOwner& own, Precision prec, const float* W, const floa
     };
     e = panel(128, &dc.w, &dc.wbytes);
     if (e == hipSuccess && x3) e = own.upload(osc.data(), 4 * osc.size(), &dc.oscale);
-    const bool second = x3 ? (k == 3 && s == 1 && ci % 64 == 0)
-                           : prec == PREC_F16 && k == 3 && ((s == 1 && ((ci % 64 == 0 && co >= 33) || (ci == 32 && co <= 64))) ||
-                                                            (down_copy && s == 2 && ci == 64 && co == 128));
-    if (e == hipSuccess && second) e = panel(64, &dc.w32, &dc.w32bytes);
+    if (e == hipSuccess && conv_second_copy(prec, ci, co, k, s, down_copy)) e = panel(64, &dc.w32, &dc.w32bytes);
     return e;
 }
 
@@ -632,36 +630,21 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     const int fuse_env = env_knob("CY_STEM_FUSE", 1);
     c->fused_last.assign(p.ops.size(), 0);
     const int pw_env = env_knob("CY_FUSE_PW", 1);             // back-to-back pairs (pw_pair); read per call: the parity tests run both forms
+    const ConvKnobs knobs = conv_knobs_env();                 // the switches of the conv dispatch, likewise: one read for the whole pass
 
     auto conv_args = [&](const Op& o) -> ConvArgs {           // the launch arguments of a convolution op of this pass
-        const ConvDesc& d = p.convs[o.conv];
-        ConvArgs a{};
-        const Tensor& t0 = p.tensors[o.in0];
+        ConvArgs a = conv_geometry(p, o, B, H, W, cm, A, a_off);      // every non-pointer field
         auto span = [&](int t) -> uint32_t {           // bytes addressable from tptr(t) for B images
             const Tensor& tt = p.tensors[t];
             return (uint32_t)((size_t)B * (H >> tt.level) * (W >> tt.level) * tt.C * es);
         };
-        a.in0 = tptr(o.in0); a.in0_ct = cm * t0.C; a.in0_coff = o.in0_coff; a.c0 = o.c0; a.up0 = o.up0;
-        a.in0_bytes = span(o.in0);
-        a.split = x3 ? c->dconv[o.conv].passes : 0; a.in0_lo = t0.C; a.oscale = c->dconv[o.conv].oscale;
-        int lev_in = o.up0 ? t0.level - 1 : t0.level;
-        if (o.in1 >= 0) {
-            const Tensor& t1 = p.tensors[o.in1];
-            a.in1 = tptr(o.in1); a.in1_ct = cm * t1.C; a.in1_coff = o.in1_coff; a.c1 = o.c1; a.in1_bytes = span(o.in1); a.in1_lo = t1.C;
-            lev_in = t1.level;
-        }
+        a.in0 = tptr(o.in0); a.in0_bytes = span(o.in0);
+        a.split = x3 ? c->dconv[o.conv].passes : 0; a.oscale = c->dconv[o.conv].oscale;
+        if (o.in1 >= 0) { a.in1 = tptr(o.in1); a.in1_bytes = span(o.in1); }
         a.wgt = c->dconv[o.conv].w; a.wgt_bytes = (uint32_t)c->dconv[o.conv].wbytes; a.bias = c->dconv[o.conv].bias;
         a.wgt32 = c->dconv[o.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[o.conv].w32bytes;
-        a.B = B; a.Hi = H >> lev_in; a.Wi = W >> lev_in; a.k = d.k; a.s = d.s; a.act = d.act;
-        a.Ho = d.s == 2 ? a.Hi / 2 : a.Hi; a.Wo = d.s == 2 ? a.Wi / 2 : a.Wi;
-        a.Cin = d.cin; a.Cout = d.cout;
-        if (o.out >= 0) {
-            const Tensor& to = p.tensors[o.out];
-            a.out = tptr(o.out); a.out_ct = cm * to.C; a.out_coff = o.out_coff; a.out_bs = a.Ho * a.Wo; a.out_ro = 0; a.out_f32 = 0; a.out_lo = to.C;
-        } else {
-            a.out = d_pred; a.out_ct = 64 + p.nc; a.out_coff = o.pred_coff; a.out_bs = A; a.out_ro = a_off[o.pred_level]; a.out_f32 = 1;
-        }
-        if (o.res >= 0) { a.res = tptr(o.res); a.res_ct = cm * p.tensors[o.res].C; a.res_coff = o.res_coff; a.res_lo = p.tensors[o.res].C; }
+        a.out = o.out >= 0 ? tptr(o.out) : (void*)d_pred;
+        if (o.res >= 0) a.res = tptr(o.res);
         return a;
     };
 
@@ -694,10 +677,10 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
                 const Op& o1 = p.ops[i]; const Op& o2 = p.ops[i + 1]; const Op& o3 = p.ops[i + 2];
                 const int l = o3.pred_level;
                 const ConvArgs a1 = conv_args(o1), a2 = conv_args(o2), a3 = conv_args(o3);
-                const int v1 = conv_variant(c->prec, a1);
+                const int v1 = conv_choose(c->prec, a1, knobs).variant;
                 if (v1 != CONV_WIDE_64 && v1 != CONV_PP_64 && v1 != CONV_C64_PERSIST) continue;
                 if (v1 == CONV_C64_PERSIST && a1.Cin != 64) continue;
-                if (conv_variant(c->prec, a2) != CONV_C64_PERSIST || a2.Cin != 64 || conv_variant(c->prec, a3) != CONV_HEAD_1X1) continue;
+                if (conv_choose(c->prec, a2, knobs).variant != CONV_C64_PERSIST || a2.Cin != 64 || conv_choose(c->prec, a3, knobs).variant != CONV_HEAD_1X1) continue;
                 BoxLevel& L = bx.L[l];
                 L.sparse = 1;
                 L.feat = a1.in0; L.feat_ct = a1.in0_ct; L.feat_coff = a1.in0_coff; L.cin = a1.Cin; L.feat_bytes = a1.in0_bytes;
@@ -712,7 +695,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     }
     if (box) for (int l = 0; l < 3; ++l) box->sparse[l] = box_sparse[l];
 
-    struct HeadPend { ConvArgs a; double flops; int conv; bool on; };
+    struct HeadPend { ConvArgs a; ConvChoice ch; double flops; int conv; bool on; };
     HeadPend pend[3] = {};                                    // deferred box-branch output convolutions, per stride level
     const int bneck_env = env_knob("CY_BNECK_FUSE", 0);       // off by default (slower than two launches so far, see bneck64.hip); read per call: the parity tests run both forms
     auto run_op = [&](const Op& o, const Op* next, bool* fused) -> int {
@@ -743,7 +726,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
             a.wpk2 = reinterpret_cast<const char*>(c->dconv[o.conv].w) + 64 * 32 * 2; a.bias0 = c->dconv[o.conv].bias;
             a.wgt32 = c->dconv[n.conv].w32; a.wgt32_bytes = (uint32_t)c->dconv[n.conv].w32bytes; a.bias1 = c->dconv[n.conv].bias;
             a.out = tptr(n.out); a.out_ct = to.C; a.out_coff = n.out_coff;
-            if (fuse_env > 1 || batch_invariant() || stem_down_blocks(a) >= 256) {
+            if (fuse_env > 1 || knobs.batch_invariant || stem_down_blocks(a) >= 256) {
                 HIPCHK(c, launch_stem_down(a, s));
                 prof_done(CONV_NUM_VARIANTS, 2.0 * B * a.H1 * a.W1 * 64 * 27.0 + 2.0 * B * a.Ho * a.Wo * 128.0 * 64 * 9);
                 *fused = true;
@@ -793,7 +776,8 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
         } else {
             ConvArgs a = conv_args(o);
             double flops = 2.0 * B * a.Ho * a.Wo * (double)a.Cout * a.Cin * a.k * a.k;
-            if (pw_env && c->prec == PREC_F16 && o.fuse == FUSE_PW_PAIR && c->dconv[next->conv].w2f && conv_variant(c->prec, a) == CONV_DIRECT_256) {
+            ConvChoice ch = conv_choose(c->prec, a, knobs);        // the op's kernel: decided here, launched and named in the profile from this value
+            if (pw_env && c->prec == PREC_F16 && o.fuse == FUSE_PW_PAIR && c->dconv[next->conv].w2f && ch.variant == CONV_DIRECT_256) {
                 const Op& n = *next;
                 const ConvDesc& d2 = p.convs[n.conv];
                 const Tensor& to2 = p.tensors[n.out];
@@ -801,29 +785,30 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
                 a.act2 = d2.act; a.cout2 = d2.cout;
                 a.out2 = tptr(n.out); a.out2_ct = to2.C; a.out2_coff = n.out_coff;
                 flops += 2.0 * B * a.Ho * a.Wo * (double)d2.cout * d2.cin;
+                ch = conv_choose(c->prec, a, knobs);                 // with wgt2 set: the fused-pair instantiation
                 *fused = true;
             }
             // the two output convolutions of a detect-head level (box branch at column 0, class branch at column 64 of the same
             // prediction rows) as ONE launch: the box branch's launch is deferred until the class branch's arguments are known
             // (nothing else reads the prediction rows inside the forward pass); CY_HEAD_PAIR=0 / other shapes: one launch each
-            if (o.out < 0 && o.pred_coff == 0 && c->prec != PREC_F32 && env_knob("CY_HEAD_PAIR", 1) && conv_variant(c->prec, a) == CONV_HEAD_1X1) {
+            if (o.out < 0 && o.pred_coff == 0 && c->prec != PREC_F32 && knobs.head_pair && ch.variant == CONV_HEAD_1X1) {
                 HeadPend& h = pend[o.pred_level];
-                if (h.on) { cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); cur_conv = o.conv; }
-                h.a = a; h.flops = flops; h.conv = o.conv; h.on = true;
+                if (h.on) { cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.ch, h.a, s)); prof_done(h.ch.variant, h.flops); cur_conv = o.conv; }
+                h.a = a; h.ch = ch; h.flops = flops; h.conv = o.conv; h.on = true;
                 return CY_OK;
             }
             if (o.out < 0 && o.pred_coff == 64 && pend[o.pred_level].on) {
                 HeadPend& h = pend[o.pred_level];
                 h.on = false;
-                if (head_pair_ok(c->prec, h.a, a)) {
+                if (head_pair_ok(c->prec, h.a, h.ch, a, ch, knobs)) {
                     HIPCHK(c, launch_head_pair(c->prec, h.a, a, s));
                     prof_done(CONV_HEAD_1X1, flops + h.flops);
                     return CY_OK;
                 }
-                cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); cur_conv = o.conv;
+                cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.ch, h.a, s)); prof_done(h.ch.variant, h.flops); cur_conv = o.conv;
             }
-            HIPCHK(c, launch_conv(c->prec, a, s));
-            prof_done(conv_variant(c->prec, a), flops);
+            HIPCHK(c, launch_conv(c->prec, ch, a, s));
+            prof_done(ch.variant, flops);
         }
         return CY_OK;
     };
@@ -838,7 +823,7 @@ static int forward_on(cy_ctx* c, const void* d_netin, int B, int H, int W, float
     c->ops_done = (int)(i < p.ops.size() ? i : p.ops.size());
     if (n_run < p.ops.size()) return CY_OK;                   // stopped: a deferred box branch stays unlaunched
     for (HeadPend& h : pend)                                  // a box branch whose class branch never came (no such plan today)
-        if (h.on) { h.on = false; cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.a, s)); prof_done(conv_variant(c->prec, h.a), h.flops); }
+        if (h.on) { h.on = false; cur_conv = h.conv; HIPCHK(c, launch_conv(c->prec, h.ch, h.a, s)); prof_done(h.ch.variant, h.flops); }
     if (box_sparse[0] || box_sparse[1] || box_sparse[2]) {
         // the deferred box branches, behind the class columns on the same stream (the next pass on this stream overwrites the feature
         // maps they read): slot maps to -1, counts to 0, then mark and the three stages.  No host read, no synchronisation; untimed in the
@@ -1061,9 +1046,10 @@ int cy_conv_slices(cy_ctx* c, const cy_conv_layout* L, const float* h_w, const f
         if (rows) { a.out_ct = L->out_ct; a.out_bs = L->out_bs; a.out_ro = L->out_ro; a.out_f32 = 1; }
         else { a.out_ct = cm * L->out_ct; a.out_lo = x3 ? L->out_ct : 0; a.out_bs = Ho * Wo; }
         if (L->d_res) { a.res = res; a.res_ct = cm * L->res_ct; a.res_coff = L->res_coff; a.res_lo = x3 ? L->res_ct : 0; }
-        if (variant && variant_cap > 0) snprintf(variant, (size_t)variant_cap, "%s", conv_variant_name(conv_variant(c->prec, a)));
+        const ConvChoice ch = conv_choose(c->prec, a, conv_knobs_env());
+        if (variant && variant_cap > 0) snprintf(variant, (size_t)variant_cap, "%s", conv_variant_name(ch.variant));
         if (passes) *passes = a.split;
-        e = launch_conv(c->prec, a, st);
+        e = launch_conv(c->prec, ch, a, st);
     }
     if (e == hipSuccess && split_out) e = launch_x3_merge(out, reinterpret_cast<float*>(L->d_out), nout, L->out_ct, st);
     return entry_done(c, e, st);

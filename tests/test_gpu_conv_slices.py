@@ -3,7 +3,8 @@ forward pass uses (tests/conv_slices_ref.py: dense, slices, shared, concat, upca
 per-element bound, with every guard element of the output buffer compared bit for bit and NaN in every input and residual
 channel outside the slices.
 
-One table.  Every case names the variant its shape and switches must select (the first word of conv_variant_name's label) and the
+One table (SHAPES, X3, F32, ROW_CASES of tests/conv_slices_ref.py, which tests/test_conv_plan_cpu.py reads too).  Every case names
+the variant its shape and switches must select (the first word of conv_variant_name's label) and the
 test asserts the name the entry reports; test_table_covers_every_variant compares the names asserted with the names the library
 lists.  Shapes: the smallest that select each kernel (tests/test_gpu_conv_tail.py: Cout 200 / 72 / 40 leave one lane group full,
 one ragged and one empty), at B >= 2 and on maps that are no multiples of the kernel's patch, so that pixel index x ct runs across
@@ -16,39 +17,7 @@ from gpu_common import detector
 
 pytestmark = pytest.mark.gpu
 
-G128, G64, HALO, PP, C64, BIG, WIDE, D256, D128, WIDE64, DUAL, STRIP, HEAD = (
-    "conv_igemm_kernel<2,2,4>", "conv_igemm_kernel<4,1,2>", "conv3x3_halo2_kernel", "conv3x3_pp_kernel<2>", "conv3x3_c64_kernel<64|32>",
-    "conv_igemm_kernel<4,2,4,3>", "conv3x3_wide_kernel", "conv1x1_direct_kernel<4,2>", "conv1x1_direct_kernel<2,2>",
-    "conv3x3_wide_kernel<WN=1>", "conv3x3_wide_kernel<dual>", "conv3x3_widep_kernel<strip>", "head1x1_kernel")
-DIRECT = {"CY_DIRECT_MIN_BLOCKS": "1"}
-TWO = ("concat", "upcat")
-
-# name: ((B, H, W, Cin, Cout, k, s), CY_BATCH_INVARIANT, further switches, variant, takes two segments / the upsample)
-SHAPES = {
-    "wide": ((2, 10, 30, 128, 200, 3, 1), "1", {}, WIDE, False),                  # ragged rows and columns of the 16 x 32 patch; Cout % 16 != 0: not persistent
-    "wide-persist": ((2, 10, 30, 128, 208, 3, 1), "1", {"CY_WIDE_PERSIST": "2"}, WIDE, False),
-    "dual": ((3, 9, 15, 128, 200, 3, 1), "1", {"CY_WIDE_DUAL": "2"}, DUAL, False),      # odd batch: the last pair has one image
-    "halo2": ((2, 10, 20, 128, 200, 3, 1), "1", {}, HALO, False),                 # two taps per barrier (two 64-channel slabs)
-    "halo": ((2, 10, 20, 64, 200, 3, 1), "1", {}, HALO, False),                   # conv3x3_halo_kernel<2, 2> (one slab)
-    "wide64": ((2, 10, 32, 128, 40, 3, 1), "1", {}, WIDE64, False),
-    "pp": ((2, 10, 18, 128, 40, 3, 1), "1", {}, PP, False),
-    "c64": ((2, 20, 18, 64, 40, 3, 1), "1", {}, C64, False),
-    "c64<32>": ((2, 20, 18, 32, 40, 3, 1), "1", {}, C64, False),
-    "strip": ((2, 19, 21, 128, 208, 3, 1), "1", {"CY_STRIP": "2"}, STRIP, False),
-    "direct256": ((2, 9, 11, 128, 200, 1, 1), "1", DIRECT, D256, True),
-    "direct128": ((2, 9, 11, 128, 72, 1, 1), "1", DIRECT, D128, True),
-    "direct256-3x3s2": ((2, 18, 22, 128, 200, 3, 2), "1", DIRECT, D256, False),
-    "direct128-3x3s2": ((2, 18, 22, 128, 72, 3, 2), "1", DIRECT, D128, False),
-    "head-inside": ((2, 9, 11, 128, 40, 1, 1), "1", {}, HEAD, False),             # head1x1_kernel inside the network: fp16 slice, SiLU, residual
-    "generic-big": ((2, 9, 15, 72, 200, 1, 1), "1", {}, BIG, True),
-    "generic64": ((2, 9, 11, 72, 40, 1, 1), "1", {}, G64, True),
-    "generic128": ((2, 9, 11, 72, 200, 1, 1), "0", {}, G128, True),               # thresholds see the real batch
-}
-# fp16x3 selects by geometry alone: no CY_DIRECT_MIN_BLOCKS, no CY_STRIP=2; CY_X3_PERSIST=1 is the persistent launch of the wide kernel
-X3 = {n: SHAPES[n] for n in ("wide", "dual", "wide64", "strip", "direct256", "direct128", "direct256-3x3s2", "direct128-3x3s2",
-                             "head-inside", "generic128", "generic64")}
-X3["wide-persist"] = (SHAPES["wide-persist"][0], "1", {"CY_X3_PERSIST": "1"}, WIDE, False)
-F32 = {n: SHAPES[n] for n in ("generic128", "generic64")}
+from conv_slices_ref import SHAPES, X3, F32, ROW_CASES, TWO, G128, G64, WIDE, DUAL, WIDE64, STRIP, D256, D128, HEAD      # the tables: shared with test_conv_plan_cpu.py
 
 
 def _even(g):
@@ -61,20 +30,6 @@ for prec, table in (("fp16", SHAPES), ("fp16x3", X3), ("fp32", F32)):
         for j, layout in enumerate(("dense", "slices", "shared") + (TWO if two else ())):
             CASES.append(("%s-%s-%s" % (prec, name, layout), prec, _even(geom) if layout == "upcat" else geom, inv if prec == "fp16" else "1",
                           env, variant, layout, (i + j) % 2 == 0, 100 * i + j))
-
-# the head's output convolutions: prediction rows [B][out_bs][64 + nc] with rows before and behind the level's block
-ROW_CASES = []      # (id, prec, geom, head_direct, variant, rows, seed)
-for prec in ("fp16", "fp16x3", "fp32"):
-    for hd in (1, 0):
-        for mi, (h, w) in enumerate(((3, 5), (8, 8), (13, 16))):
-            for bi, (cin, cout, nc) in enumerate(((64, 64, 5), (128, 1, 1), (128, 5, 5), (128, 80, 80))):      # box branch, class branches
-                coff = 0 if bi == 0 else 64
-                direct = hd == 1 and prec != "fp32" and cout <= 64
-                variant = HEAD if direct else (G64 if cout <= 64 else G128)
-                rows = dict(out_ct=64 + nc, out_coff=coff, out_bs=h * w + 29, out_ro=17)
-                ROW_CASES.append(("%s-hd%d-%dx%d-%s" % (prec, hd, h, w, "box" if bi == 0 else "nc%d" % nc), prec, (2, h, w, cin, cout, 1, 1), hd,
-                                  variant, rows, 1000 + 10 * mi + bi))
-
 
 def _run(t, det):
     """One call of the entry on device copies of the case's buffers -> (output buffer on the host, variant, passes)."""

@@ -353,4 +353,30 @@ hipError_t launch_pool5(Precision p, const PoolArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ test hook: the LDS history
+// Every workgroup writes `pattern` over all of its dynamic LDS (`words` dwords) and ends.  The kernels behind it on the same CUs
+// then find that pattern where they have not written yet (observed on this GPU: LDS is not cleared between kernels; no contract
+// says so).  Plain ds_write stores (a volatile LDS array would go through the flat aperture).
+__global__ __launch_bounds__(256) void lds_fill_kernel(unsigned pattern, int words) {
+    extern __shared__ unsigned lds_fill_words[];
+    for (int i = threadIdx.x; i < words; i += 256) lds_fill_words[i] = pattern;
+    __asm__ volatile("" ::: "memory");                 // nothing reads the stores back: the empty statement stands for a reader and keeps them
+}
+
+// one workgroup per CU, each with the largest dynamic LDS the device grants a workgroup (so no two share a CU while they run);
+// *bytes: that size
+hipError_t launch_lds_fill(unsigned pattern, hipStream_t s, int* bytes) {
+    int dev = 0, cus = 0, lds = 0, optin = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    if (e != hipSuccess) return e;
+    if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess) { optin = 0; (void)hipGetLastError(); }
+    if (optin > lds) lds = optin;
+    lds &= ~15;
+    if (cus < 1 || lds < 16) return hipErrorInvalidValue;
+    if (bytes) *bytes = lds;
+    return launch_lds<lds_fill_kernel>(dim3((unsigned)cus), dim3(256), (size_t)lds, (size_t)lds, s, pattern, lds / 4);
+}
+
 }  // namespace cy

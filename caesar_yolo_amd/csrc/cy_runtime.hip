@@ -1207,6 +1207,15 @@ int cy_debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, doubl
     return hipGetLastError() == hipSuccess ? CY_OK : CY_ERR_HIP;
 }
 
+// asynchronous on `stream`, like cy_forward: the point is what the kernels queued behind it find in LDS
+int cy_debug_lds_fill(cy_ctx* c, unsigned pattern32, void* stream) {
+    if (!c) return CY_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    int bytes = 0;
+    HIPCHK(c, launch_lds_fill(pattern32, (hipStream_t)stream, &bytes));
+    return bytes;
+}
+
 int cy_debug_cand_counts(cy_ctx* c, int* h_out, int B) {
     if (!c || !c->loaded || !h_out || B < 1 || B > c->cfg.max_batch) return fail(c, CY_ERR_ARG, "bad arguments");
     HIPCHK(c, hipDeviceSynchronize());

@@ -270,6 +270,11 @@ class HipDetector(object):
         d = tuple(dims)
         return buf[:int(np.prod(d))].reshape(d)
 
+    def lds_fill(self, pattern):
+        """Test hook (cy_debug_lds_fill): queue one workgroup per CU on the current stream that writes the 32-bit `pattern` over
+        all of its LDS, so that the kernels behind it inherit that pattern.  -> LDS bytes written per workgroup.  Not waited for."""
+        return self._chk(self.lib.cy_debug_lds_fill(self.ctx, int(pattern) & 0xFFFFFFFF, self._stream()))
+
     def _det_out(self, B, out):
         """(det [B,300,6] fp32, index [B,300] int32, count [B] int32): the caller's tensors (out) or zero-filled new ones."""
         if out is not None:

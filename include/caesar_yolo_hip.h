@@ -159,6 +159,13 @@ int cy_debug_stamps(unsigned long long* out8, int reset);
 /* developer diagnostics: the pack kernel's quotient by a per-tile constant (d_fast) beside the float64 division (d_ref), element-wise on
  * device arrays of n doubles: must agree bit for bit (tests/test_gpu_preproc.py) */
 int cy_debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, double* d_ref, int n);
+/* test hook (never called on the hot path): sets what the kernels queued behind it on `stream` inherit in LDS.  One kernel, one
+ * workgroup per CU, each with the largest dynamic LDS the device grants a workgroup (queried, not assumed), writes pattern32 over
+ * all of it with plain vector LDS stores.  Returns that size in bytes (> 0), or a negative error code; it does not wait for the
+ * kernel.  That LDS keeps its bytes across a kernel boundary is observed behaviour of this GPU and no contract: a test may use the
+ * hook to make a read of LDS the workgroup did not write visible, never to pass data.  Which CU a workgroup lands on is the
+ * dispatcher's choice; a CU busy with another stream's work may be missed. */
+int cy_debug_lds_fill(cy_ctx* ctx, unsigned pattern32, void* stream);
 /* number of pre-NMS candidates per tile of the last cy_decode_nms call (diagnostics) */
 int cy_debug_cand_counts(cy_ctx* ctx, int* h_out, int B);
 

@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace cy {
@@ -39,6 +40,7 @@ namespace cy {
 __device__ unsigned long long g_stamps[8];
 constexpr int WG_STAMP_SLOTS = 4096;
 __device__ unsigned long long g_wg_stamps[WG_STAMP_SLOTS * 4];     // per-workgroup phase records of the wide kernel (stamped builds)
+__device__ unsigned long long g_wg_life[WG_STAMP_SLOTS * 3];       // pixels-direct kernel: entry, exit (100 MHz counter) and CU of each workgroup
 __device__ __forceinline__ unsigned long long stamp_now() {
     unsigned long long t;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
@@ -48,6 +50,14 @@ __device__ __forceinline__ unsigned long long stamp_real() {       // constant 1
     unsigned long long t;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return t;
+}
+
+// the lane's number from the hardware (not from threadIdx.x, and not hoisted): for code that runs once per tile inside a loop whose
+// registers are all taken, so that no lane constant is carried -- or spilled -- across the loop
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
 }
 
 // NSTAGE = 2: the slab for step s+1 is requested while step s computes and drained at the barrier (two workgroups of
@@ -2178,9 +2188,36 @@ static hipError_t launch_strip(const ConvArgs& a, hipStream_t s) {
 // movement.  The second layer's four weight chunks (128 KB) are requested into the dead ring (+ one slot) right behind the loop and
 // land under the first epilogue's arithmetic; its result is stored through the same epilogue form.  The 256-channel map between the
 // two layers (2 MB per 512^2 tile) is never written or read.
-template <int NB, int MI, int RING, bool K3, bool SPLIT = false, int NDW = 8, bool FUSE2 = false>
+// PERSIST (fp16 context, the 256-channel tile, not FUSE2; CY_DIRECT_PERSIST): one workgroup per CU walks tiles blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the order the one-tile form launches them in, and the request stream does not stop at a tile
+// boundary.  The ring slot of a chunk is its running number over the workgroup's tiles mod RING (one flat loop over all the chunks,
+// its RING steps written out; a tile ends behind whichever step its last chunk falls on), so the WAR / RAW argument of the one-tile
+// loop holds across the boundary unchanged:
+// a slot is requested into one barrier after its last read, and read one barrier after the counted wait that covers it.  While the
+// last DIST chunks of a tile are computed, the requests going out are chunks 0 .. DIST-1 of the next tile (lane addresses, tap
+// cursor and weight rows rebased at that point: nothing of the current tile is requested after it) and, ahead of them from wave 0,
+// its bias slice into the other of two bias buffers -- the oldest request of the tile, so every counted wait of the tile covers it,
+// as in the one-tile form.  The epilogue's stores (and residual loads) sit in the in-order vmcnt queue BEHIND the next tile's first
+// DIST chunks and AHEAD of what its first iterations request: the steady-state count then waits for more than it needs (for part of
+// the stores as well), never for less; a wait assumes only requests that were issued.  Chunk order, K order, MFMA order and
+// epilogue are the one-tile form's: the outputs are bit-identical (tests/test_gpu_direct_persist.py).  Tiles of fewer than RING
+// chunks keep the one-tile form (direct_persist_form, cy_conv_plan.cpp).
+// Anatomy of the one-tile form at batch 256 (stamped build, us per workgroup; profiles/direct_persist.md): 512 -> 512 on 32 x 32:
+// entry -> loop 3.8 | loop 19.7 | epilogue 3.9 | exit -> entry of the CU's next workgroup 2.2; 2048 -> 512: 3.6 | 81.5 | 4.0 | 2.2;
+// 640 -> 256 on 64 x 64: 4.2 | 25.4 | 3.8 | 2.2; 3x3 s2 256 -> 512: 3.4 | 86.6 | 4.0 | 2.3 -- about 10 us per tile outside the loop.
+// What the persistent form gains per layer (-6..-14 % on the 1x1 layers, -19..-22 % on the strided 3x3 ones) is that AND the exact
+// vmcnt counts of its unconditional requests (see the step).  Tried and dropped on the way: the one-tile loop entered at a ring phase
+// per tile with `c >= 0 && c < chunks` guards on the unrolled steps (the skipped-step paths make the compiler wait vmcnt(4..11) for
+// the pixel registers: it waits for the weight pieces just requested); the flat loop as an unrolled `for` with an exit (not
+// unrolled: the pixel ring went to scratch); four requesting waves in the strided form (the count that is safe for the other four
+// makes the requesting ones wait for half of the pieces just requested).
+// Registers: 251-256 VGPRs, no scratch -- the per-tile code (lane_addrs, the rebase, the epilogue) takes the lane's number from
+// lane_now() and its divisors through an opaque copy, so that no lane constant or reciprocal is carried over the K loop; the bias
+// values are read per pixel group and the residual one half at a time.
+template <int NB, int MI, int RING, bool K3, bool SPLIT = false, int NDW = 8, bool FUSE2 = false, bool PERSIST = false>
 __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv1x1_direct_kernel(const ConvArgs a) {
     static_assert(!FUSE2 || (NB == 4 && !SPLIT), "back-to-back fusion: 256-channel tile, fp16 context");
+    static_assert(!PERSIST || (NB == 4 && RING == 3 && !SPLIT && !FUSE2), "persistent form: 256-channel tile, fp16 context, not the fused pair");
     // NDW = number of waves that request the weight chunks (LDS-DMA): 8 = every wave its share; 4 = waves 0-3 only (one per SIMD),
     // so that a request waiting for room in the memory pipeline holds one wave of a SIMD while its partner keeps the matrix pipe busy
     // SPLIT (fp16x3 context): three passes over the K chunks -- pixels [x_lo | x_hi | x_hi] (the low halves a.in*_lo halves behind
@@ -2197,8 +2234,10 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
     const int HoWo = a.Ho * a.Wo, M = a.B * HoWo;
     const int cpad = pad128(a.Cout);
     const int ntn = (pad64(a.Cout) + BN - 1) / BN;
-    const int id = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (id / ntn) * BM, n0 = (id % ntn) * BN;
+    const int total = PERSIST ? ((M + BM - 1) / BM) * ntn : (int)gridDim.x;       // tiles of the launch
+    int tile = blockIdx.x;                                                       // PERSIST: the tile being computed
+    const int id = xcd_remap(tile, total);
+    int m0 = (id / ntn) * BM, n0 = (id % ntn) * BN;
     // K chunk c = slab * taps + tap (the order of the packed weights).  k = 3 (strided 3x3 layers): every tap is the same
     // per-lane centre-pixel address plus a UNIFORM shift, which rides in soffset; soffset is unsigned, so the resource base
     // is moved back by the largest negative shift (one row + one pixel) and the shift is biased by the same amount.  Lanes
@@ -2215,14 +2254,19 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
     const auto rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.c1 ? a.in1 : a.in0), 0,
                                                        a.c1 ? a.in1_bytes : a.in0_bytes, 0x00020000);
     const auto rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wgt), 0, a.wgt_bytes, 0x00020000);
-    unsigned v0[MI], v1[MI], vmask[MI];
+    unsigned v0[MI], v1[MI], vmask[MI];                     // lane addresses of the tile whose chunks are being REQUESTED
+    auto lane_addrs = [&](int mt) __attribute__((always_inline)) {
+    const int ln = PERSIST ? lane_now() : lane;
+    int fr = ln & 15, fq = ln >> 4, HoWo = a.Ho * a.Wo, Wo = a.Wo;
+    // PERSIST: recomputed per tile -- neither the lane parts nor the reciprocals of the two divisors are kept in registers over the K loop
+    if constexpr (PERSIST) asm volatile("" : "+s"(HoWo), "+s"(Wo));
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-        const int m = m0 + (wave * MI + mi) * 16 + fr;
+        const int m = mt + (wave * MI + mi) * 16 + fr;
         v0[mi] = v1[mi] = CY_OOB;
         vmask[mi] = 0;
         if (m < M) {
-            const int b = m / HoWo, r = m - b * HoWo, ho = r / a.Wo, wo = r - ho * a.Wo;
+            const int b = m / HoWo, r = m - b * HoWo, ho = r / Wo, wo = r - ho * Wo;
             int p0;
             if (a.up0) p0 = (b * (a.Hi >> 1) + (ho >> 1)) * (a.Wi >> 1) + (wo >> 1);
             else p0 = (b * a.Hi + ho * a.s) * a.Wi + wo * a.s;                      // centre tap: always inside the image
@@ -2238,6 +2282,8 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
             vmask[mi] = vm;
         }
     }
+    };
+    lane_addrs(m0);
     // piece j of requesting wave w = rows (j * NDW + w) * 8 .. +7 of the chunk: the lane part (row & 7 = lane >> 3) is the same for
     // every j, the rest is uniform and rides in soffset
     // developer ablation (diagnostic builds; results invalid): bit 0 no weight requests in the loop, bit 1 no weight fragment reads,
@@ -2263,7 +2309,8 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
     const bool no_dma = CY_STAMPS_ENABLED && (a.dbg & 1), no_rd = CY_STAMPS_ENABLED && (a.dbg & 2), no_mma = CY_STAMPS_ENABLED && (a.dbg & 4),
                no_px = CY_STAMPS_ENABLED && (a.dbg & 8);
     const bool reqw = wave < NDW;
-    const unsigned woff0 = (unsigned)((n0 + wave * 8 + (lane >> 3)) * 128 + ((lane & 7) ^ (lane >> 3)) * 16);
+    auto weight_rows = [&](int nt, int ln) { return (unsigned)((nt + wave * 8 + (ln >> 3)) * 128 + ((ln & 7) ^ (ln >> 3)) * 16); };
+    unsigned woff0 = weight_rows(n0, lane);                       // (PERSIST: of the tile whose chunks are being requested)
     u32x4 xa[RING][MI][2];
     int ltap = 0, lslab = 0;                                // cursor of load_a (called for c = 0, 1, 2, ... in order)
     auto load_a = [&](int slot, int cv) {                   // the uniform part of the address rides in soffset (not range-checked)
@@ -2271,7 +2318,22 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
         int lo = 0;
         const int c = SPLIT ? x3_chunk(cv, pchunks, lo) : cv;           // physical chunk (the weights are packed per virtual chunk)
         const unsigned lo0 = SPLIT && lo ? (unsigned)a.in0_lo * 2u : 0u, lo1 = SPLIT && lo ? (unsigned)a.in1_lo * 2u : 0u;
-        if (c >= c0chunks) {
+        if constexpr (PERSIST && !K3) {                     // the segment selected, not branched on: one group of loads on every path (see the steps)
+            const bool seg1 = c >= c0chunks;
+            if (c == c0chunks) {                            // first chunk of the second segment: its lane addresses from here to the tile's end
+#pragma unroll                                              // (load_a is called for c = 0, 1, 2, ... in order; lane_addrs restores v0 for the next tile)
+                for (int mi = 0; mi < MI; ++mi) v0[mi] = v1[mi];
+            }
+            const auto rs = seg1 ? rs1 : rs0;
+            const unsigned so = (unsigned)((seg1 ? c - c0chunks : c) * 128);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk)
+                    xa[slot][mi][kk] = load_b128(rs, v0[mi], so + kk * 64);
+            return;
+        }
+        if (!(PERSIST && K3) && c >= c0chunks) {            // (no strided 3x3 layer has a second segment: its persistent form keeps no v1)
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -2354,13 +2416,14 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
     // prologue: chunks 0..DIST-1 requested (weights first, then pixels, per chunk: the order the counted waits assume)
 #pragma unroll
     for (int d = 0; d < DIST; ++d)
-        if (d < chunks) { dma_w(d, d); load_a(d, d); }
+        if (PERSIST || d < chunks) { dma_w(d, d); load_a(d, d); }       // (PERSIST: at least RING chunks)
     // weights of chunk 0 landed; what was requested after them may stay in flight (DIST is 2 or 3)
     if (chunks >= DIST) wait_w(APW + (DIST - 1) * PER);
     else if (DIST == 3 && chunks == 2) wait_w(APW + PER);
     else wait_w(APW);
     __builtin_amdgcn_s_barrier();
     const unsigned long long t_loop = stamps ? stamp_real() : 0, c_loop = stamps ? stamp_now() : 0;
+    if constexpr (!PERSIST) {
 #pragma unroll 1
     for (int cb = 0; cb < chunks; cb += RING) {
 #pragma unroll
@@ -2379,6 +2442,7 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+    }
     }
 
     const unsigned long long t_epi = stamps ? stamp_real() : 0, c_epi = stamps ? stamp_now() : 0;
@@ -2464,16 +2528,23 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
         return;
     }
     // ---- epilogue: per 64-channel block the same 16-contiguous-channels-per-lane layout as the other kernels
+    auto epilogue = [&](const float* bias_l) __attribute__((always_inline)) {
+    const int ln = PERSIST ? lane_now() : lane;
+    int fr = ln & 15, fq = ln >> 4, HoWo = a.Ho * a.Wo;
+    if constexpr (PERSIST) asm volatile("" : "+s"(HoWo));      // (as in lane_addrs)
 #pragma unroll
     for (int g = 0; g < NB; ++g) {
         const int cbase = n0 + g * 64 + fq * 16;
         if (cbase >= pad64(a.Cout)) continue;
         float bv[16];
+        auto load_bv = [&](int off) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(bias_lds + g * 64 + fq * 16 + j * 4);
+            const f32x4 t = *reinterpret_cast<const f32x4*>(bias_l + off + j * 4);
             bv[j * 4] = t[0]; bv[j * 4 + 1] = t[1]; bv[j * 4 + 2] = t[2]; bv[j * 4 + 3] = t[3];
         }
+        };
+        if constexpr (!PERSIST) load_bv(g * 64 + fq * 16);
         float sc[SPLIT ? 16 : 1];
         if constexpr (SPLIT) {
 #pragma unroll
@@ -2509,14 +2580,29 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
                 }
                 continue;
             }
+            if constexpr (PERSIST) {        // the 16 bias values read again per pixel group (the same values): not held in registers across the
+                int off = g * 64 + fq * 16;     // stores and residual loads of the group before, where the next tile's first pixel chunks are live too
+                asm volatile("" : "+v"(off));
+                load_bv(off);
+            }
             bias_act16(acc[g * 4][mi], acc[g * 4 + 1][mi], acc[g * 4 + 2][mi], acc[g * 4 + 3][mi], bv, a.act != 0, v);
             if (cbase + 16 <= a.Cout) {
                 f16* dst = reinterpret_cast<f16*>(a.out) + opix * a.out_ct + a.out_coff + cbase;
                 if (a.res) {
                     const f16* rp = reinterpret_cast<const f16*>(a.res) + (long)m * a.res_ct + a.res_coff + cbase;
+                    if constexpr (PERSIST) {        // one half at a time: the next tile's first pixel chunks are live in registers here
+                        const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) v[j] += (float)r0v[j];
+                        __builtin_amdgcn_sched_barrier(0);
+                        const f16x8 r1v = *reinterpret_cast<const f16x8*>(rp + 8);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) v[8 + j] += (float)r1v[j];
+                    } else {
                     const f16x8 r0v = *reinterpret_cast<const f16x8*>(rp), r1v = *reinterpret_cast<const f16x8*>(rp + 8);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) { v[j] += (float)r0v[j]; v[8 + j] += (float)r1v[j]; }
+                    }
                 }
                 f16x8 o0, o1;
 #pragma unroll
@@ -2535,9 +2621,89 @@ __global__ __launch_bounds__(512, (NB * MI <= 4 && RING == 2) ? 2 : 1) void conv
             }
         }
     }
+    };
+    if constexpr (!PERSIST) {
+        epilogue(bias_lds);
+    } else {
+        const int stride = gridDim.x;
+        int bsel = 0, c = 0;                                // bias buffer of the tile; chunk of the tile
+        int tnext = tile + stride;
+        bool more = tnext < total;
+        // One flat loop over the chunks of all the workgroup's tiles: the chunk with running number g sits in slot g % RING = u, and a
+        // tile ends (epilogue, accumulators cleared, next tile) behind whichever step its last chunk falls on.  No step is ever skipped,
+        // so the compiler's count of the loads in flight is the same on every path.
+        // (the steps are written out, not an unrolled loop: an unrolled loop with an exit in its body is not unrolled, and a
+        // run-time slot index puts the pixel ring into scratch)
+                auto step = [&](auto U) __attribute__((always_inline)) -> bool {           // one chunk in slot U; true behind the workgroup's last tile
+                    constexpr int u = decltype(U)::value;
+                    {
+                        // one request per step, always: chunk c + DIST of this tile, or chunk c + DIST - chunks of the NEXT tile (same slot
+                        // arithmetic), or -- behind the workgroup's last tile -- the same instructions with out-of-range lane addresses
+                        // (zeros into a dead slot and dead registers, no memory traffic).  With the request unconditional the compiler
+                        // counts the pixel loads in flight exactly; behind a conditional one it waits vmcnt(0) for the pixel registers
+                        // of every RING-th chunk, as it does in the one-tile form.
+                        int cq = c + DIST;
+                        if (cq >= chunks) {
+                            cq -= chunks;
+                            if (cq == 0) {                  // first request past the tile: rebase the request state, bias slice first
+                                ltap = 0; lslab = 0;
+                                if (more) {
+                                    const int idn = xcd_remap(tnext, total);
+                                    const int ln = lane_now();         // (as in lane_addrs: nothing kept in registers over the K loop)
+                                    lane_addrs((idn / ntn) * BM);
+                                    woff0 = weight_rows((idn % ntn) * BN, ln);
+                                    if (wave == 0) {
+                                        const auto rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.bias), 0, (unsigned)pad64(a.Cout) * 4u, 0x00020000);
+                                        dma_piece(rsb, (lds_ptr_t*)(bias_lds + (bsel ^ 1) * 256), ln * 16 < BN * 4 ? (unsigned)((idn % ntn) * BN * 4 + ln * 16) : CY_OOB, 0);
+                                    }
+                                } else {
+                                    lane_addrs(M);          // every lane out of range
+                                    woff0 = CY_OOB;
+                                }
+                            }
+                        }
+                        dma_w((u + DIST) % RING, cq); load_a((u + DIST) % RING, cq);
+                        compute(u);
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        // weights of the next chunk (of this tile or of the next) must have landed; what was requested after them may
+                        // stay in flight.  Behind a tile boundary the epilogue's stores and residual loads are among the younger
+                        // operations as well: the wait then covers more than it needs
+                        wait_w(APW + (DIST - 1) * PER);
+                        __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_s_barrier();
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (++c == chunks) {                // the tile's last chunk
+                            epilogue(bias_lds + bsel * 256);
+                            if (!more) return true;
+#pragma unroll
+                            for (int ni = 0; ni < NB * 4; ++ni)
+#pragma unroll
+                                for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+                            tile = tnext; tnext = tile + stride; more = tnext < total;
+                            const int idn = xcd_remap(tile, total);
+                            m0 = (idn / ntn) * BM; n0 = (idn % ntn) * BN;
+                            c = 0; bsel ^= 1;
+                        }
+                    }
+                    return false;
+                };
+        static_assert(!PERSIST || RING == 3, "three steps written out");
+#pragma unroll 1
+        for (;;) {
+            if (step(std::integral_constant<int, 0>{})) break;
+            if (step(std::integral_constant<int, 1>{})) break;
+            if (step(std::integral_constant<int, 2>{})) break;
+        }
+        CY_WAIT_VM(0);                                     // the zero requests behind the last tile: landed before the workgroup gives its LDS back
+    }
     if (stamps && tid == 0) {
         unsigned long long* rec = g_wg_stamps + (size_t)(blockIdx.x % WG_STAMP_SLOTS) * 4;
-        rec[0] = t_loop - t_entry; rec[1] = t_epi - t_loop; rec[2] = stamp_real() - t_epi; rec[3] = c_epi - c_loop;
+        const unsigned long long t_exit = stamp_real();
+        rec[0] = t_loop - t_entry; rec[1] = t_epi - t_loop; rec[2] = t_exit - t_epi; rec[3] = c_epi - c_loop;
+        // the workgroup's whole life and where it ran: entry, exit, (XCC id << 16) | (SE, SH, CU fields of HW_ID)
+        unsigned long long* life = g_wg_life + (size_t)(blockIdx.x % WG_STAMP_SLOTS) * 3;
+        life[0] = t_entry; life[1] = t_exit;
+        life[2] = ((unsigned long long)(__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15u) << 16) | (__builtin_amdgcn_s_getreg(4 | (31 << 11)) & 0xff00u);
     }
 }
 
@@ -2548,6 +2714,21 @@ static hipError_t launch_direct(const ConvArgs& a, hipStream_t s) {
     const int M = a.B * a.Ho * a.Wo;
     const int blocks = ((M + BM - 1) / BM) * ((pad64(a.Cout) + BN - 1) / BN);
     return launch_lds<conv1x1_direct_kernel<NB, MI, RING, K3, SPLIT, NDW, FUSE2>>(dim3(blocks), dim3(512), lds, lds, s, a);
+}
+
+// persistent form of the 256-channel tile (fp16 context): one workgroup per CU walks the tiles; grid_cap > 0 (CY_DIRECT_PERSIST_GRID,
+// tests) caps the grid so that small launches walk several tiles per workgroup
+template <bool K3, int NDW>
+static hipError_t launch_direct_persist(const ConvArgs& a, hipStream_t s, int grid_cap) {
+    constexpr int BN = 256, BM = 256, RING = 3;
+    const size_t lds = RING * BN * 128 + 2048;                            // weight ring, two bias buffers
+    const int M = a.B * a.Ho * a.Wo;
+    const int tiles = ((M + BM - 1) / BM) * ((pad64(a.Cout) + BN - 1) / BN);
+    if ((a.Cin / 64) * (K3 ? 9 : 1) < RING || (K3 && a.c1)) return hipErrorInvalidValue;      // (conv_kernel never chooses it there)
+    static const int ncu = [] { int dev = 0, n = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    const int cap = grid_cap > 0 ? grid_cap : ncu;
+    const int grid = tiles < cap ? tiles : cap;
+    return launch_lds<conv1x1_direct_kernel<4, 2, RING, K3, false, NDW, false, true>>(dim3(grid), dim3(512), lds, lds, s, a);
 }
 
 template <int WM, int RING>
@@ -2610,8 +2791,12 @@ hipError_t launch_conv(Precision p, const ConvChoice& choice, const ConvArgs& a,
         case CK_PP_2: return launch_pp<2>(a, s);
         case CK_C64_64: return launch_c64<64>(a, s);
         case CK_C64_32: return launch_c64<32>(a, s);
-        case CK_DIRECT_256_K1: return x3 ? launch_direct<4, 2, 3, false, true>(a, s) : launch_direct<4, 2, 3, false>(with_dbg(a), s);
-        case CK_DIRECT_256_K3: return x3 ? launch_direct<4, 2, 3, true, true>(a, s) : launch_direct<4, 2, 3, true, false, 4>(with_dbg(a), s);
+        // (the persistent form of the 256-channel tile: every wave requests in the strided form too, so that the compiler's count of the
+        // pixel loads in flight holds for all waves)
+        case CK_DIRECT_256_K1: return x3 ? launch_direct<4, 2, 3, false, true>(a, s) : choice.direct_persist ? launch_direct_persist<false, 8>(with_dbg(a), s, choice.persist_grid)
+                                                                                       : launch_direct<4, 2, 3, false>(with_dbg(a), s);
+        case CK_DIRECT_256_K3: return x3 ? launch_direct<4, 2, 3, true, true>(a, s) : choice.direct_persist ? launch_direct_persist<true, 8>(with_dbg(a), s, choice.persist_grid)
+                                                                                      : launch_direct<4, 2, 3, true, false, 4>(with_dbg(a), s);
         case CK_DIRECT_256_K1_FUSE2: return launch_direct<4, 2, 3, false, false, 8, true>(with_dbg(a), s);
         case CK_DIRECT_256_K3_FUSE2: return launch_direct<4, 2, 3, true, false, 4, true>(with_dbg(a), s);
         case CK_DIRECT_128_K1: return x3 ? launch_direct<2, 2, 2, false, true>(a, s) : launch_direct<2, 2, 2, false>(a, s);
@@ -2627,6 +2812,11 @@ hipError_t launch_conv(Precision p, const ConvChoice& choice, const ConvArgs& a,
 void debug_read_wg_stamps(unsigned long long* out, int n) {      // raw per-workgroup records (n x 4) of stamped builds
     hipDeviceSynchronize();
     hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_stamps), (size_t)(n < WG_STAMP_SLOTS ? n : WG_STAMP_SLOTS) * 4 * sizeof(unsigned long long));
+}
+
+void debug_read_wg_life(unsigned long long* out, int n) {        // entry, exit, CU of the pixels-direct kernel's workgroups (n x 3), stamped builds
+    hipDeviceSynchronize();
+    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg_life), (size_t)(n < WG_STAMP_SLOTS ? n : WG_STAMP_SLOTS) * 3 * sizeof(unsigned long long));
 }
 
 void debug_read_stamps(unsigned long long* out8, bool reset) {

@@ -40,6 +40,7 @@ ConvKnobs conv_knobs_env() {
     if (const char* e = getenv("CY_DIRECT_MIN_BLOCKS")) k.direct_min_blocks = atol(e);
     k.head_direct = knob("CY_HEAD_DIRECT", 1); k.narrow_direct = knob("CY_NARROW_DIRECT", 1); k.head_pair = knob("CY_HEAD_PAIR", 1);
     k.wide_persist = knob("CY_WIDE_PERSIST", 1); k.x3_persist = knob("CY_X3_PERSIST", 0);
+    k.direct_persist = knob("CY_DIRECT_PERSIST", 1); k.direct_persist_grid = knob("CY_DIRECT_PERSIST_GRID", 0);
     return k;
 }
 
@@ -190,6 +191,29 @@ static int conv_variant(Precision p, const ConvArgs& a, const ConvKnobs& k) {
     return CONV_GENERIC_128;
 }
 
+// Persistent form of the pixels-direct 256-channel tile (conv1x1_direct_kernel<4,2,3,...,PERSIST>; same arithmetic in the same order:
+// bit-identical outputs; fp16 context, not the fused pair): one workgroup per CU walks the tiles and requests the next tile's first
+// chunks and bias under the current tile's last chunks and epilogue.  Taken when every CU gets at least two tiles (512 tiles: 256
+// CUs) and a tile has at least as many K chunks as the ring has slots (the boundary logic assumes a tile's own prologue is behind
+// it); CY_DIRECT_PERSIST: 0 off, 2 regardless of the launch size (tests).  The real batch counts, under batch invariance too: the
+// two forms give the same bits.  Measured per layer at batch 256 on 512-px tiles, three processes, against the one-tile form's own
+// range (profiles/direct_persist.md): 1x1 layers -6..-14 %, strided 3x3 layers -19..-22 %, faster in at least two of three
+// processes each; the one layer that was not is excluded by the chunk condition below.
+static long direct_tiles(const ConvArgs& a) { return (((long)a.B * a.Ho * a.Wo + 255) / 256) * ((pad64(a.Cout) + 255) / 256); }
+static bool direct_persist_form(Precision p, ConvKernel kernel, const ConvArgs& a, const ConvKnobs& k) {
+    if (p != PREC_F16 || (kernel != CK_DIRECT_256_K1 && kernel != CK_DIRECT_256_K3) || !k.direct_persist || a.out_f32) return false;
+    if ((a.Cin / 64) * (a.k == 3 ? 9 : 1) < 3 || (a.k == 3 && a.c1)) return false;
+    // at two or three tiles per CU only from 16 chunks on: 512 -> 512 on 16 x 16 maps (model.8.cv1: 512 tiles of 8 chunks) measured
+    // 0.054-0.057 ms against the one-tile form's 0.053 in three of three processes, while the 16- and 20-chunk layers on the same
+    // maps (model.8.cv2, 9.cv2, 21.cv1, 21.cv2) are 6-10 % faster and 8-chunk layers with eight tiles per CU (model.6.cv1) 8 % faster
+    const long tiles = direct_tiles(a), chunks = (a.Cin / 64) * (a.k == 3 ? 9 : 1);
+    return k.direct_persist > 1 || (tiles >= 512 && (tiles >= 1024 || chunks >= 16));
+}
+const char* conv_choice_name(const ConvChoice& c) {
+    if (c.direct_persist) return c.kernel == CK_DIRECT_256_K3 ? "conv1x1_direct_kernel<4,2,3,K3,PERSIST>" : "conv1x1_direct_kernel<4,2,3,PERSIST>";
+    return conv_kernel_name(c.kernel);
+}
+
 // the instantiation below the variant
 static ConvKernel conv_kernel(Precision p, int variant, const ConvArgs& a, const ConvKnobs& k) {
     const bool x3 = p == PREC_F16X3;
@@ -236,6 +260,8 @@ ConvChoice conv_choose(Precision p, const ConvArgs& a, const ConvKnobs& k) {
     ConvChoice c;
     c.variant = conv_variant(p, a, k);
     c.kernel = p == PREC_F16X3 && ((a.split != 2 && a.split != 3) || !a.oscale) ? CK_BAD_ARGS : conv_kernel(p, c.variant, a, k);
+    c.direct_persist = direct_persist_form(p, c.kernel, a, k) ? 1 : 0;
+    c.persist_grid = k.direct_persist_grid;
     return c;
 }
 

@@ -83,10 +83,15 @@ struct ConvKnobs {
     int head_pair = 1;              // CY_HEAD_PAIR
     int wide_persist = 1;           // CY_WIDE_PERSIST: 0 off, 2 regardless of the launch size
     int x3_persist = 0;             // CY_X3_PERSIST: 1 = persistent wide kernel in the fp16x3 context
+    int direct_persist = 1;         // CY_DIRECT_PERSIST: persistent form of the pixels-direct 256-channel tile; 0 off, 2 regardless of the launch size
+    int direct_persist_grid = 0;    // CY_DIRECT_PERSIST_GRID: workgroups of that form (tests: several tiles per workgroup in a small launch); 0 = one per CU
 };
 ConvKnobs conv_knobs_env();
 
-struct ConvChoice { int variant; ConvKernel kernel; };
+// direct_persist: CK_DIRECT_256_K1 / _K3 in the fp16 context run in their persistent form (same kernel template, trailing argument; same
+// bits) -- a form below the kernel value, as the ACT / RES instantiations are; persist_grid: ConvKnobs::direct_persist_grid, for the launcher
+struct ConvChoice { int variant; ConvKernel kernel; int direct_persist = 0; int persist_grid = 0; };
+const char* conv_choice_name(const ConvChoice& c);      // conv_kernel_name, with the persistent form named
 ConvChoice conv_choose(Precision p, const ConvArgs& a, const ConvKnobs& k);     // the whole decision, once
 
 // whether upload_conv makes the second weight copy (64-byte K chunks, ConvArgs::wgt32) of a layer; down_copy: the loader's

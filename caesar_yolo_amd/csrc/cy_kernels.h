@@ -94,7 +94,8 @@ hipError_t launch_conv(Precision p, const ConvChoice& choice, const ConvArgs& a,
 // the two output 1x1s of a detect-head level (box branch a, class branch b) in one launch of head1x1_pair_kernel (conv_igemm.hip), where head_pair_ok
 hipError_t launch_head_pair(Precision p, const ConvArgs& a, const ConvArgs& b, hipStream_t s);
 void debug_read_stamps(unsigned long long* out8, bool reset);
-void debug_read_wg_stamps(unsigned long long* out, int n);      // raw per-workgroup phase records (n x 4), stamped builds   // developer diagnostics (CY_DBG=64)
+void debug_read_wg_life(unsigned long long* out, int n);        // entry, exit, CU per workgroup of the pixels-direct kernel (n x 3), stamped builds
+void debug_read_wg_stamps(unsigned long long* out, int n);     // raw per-workgroup phase records (n x 4), stamped builds   // developer diagnostics (CY_DBG=64)
 void debug_read_pre_stamps(unsigned long long* out8, bool reset);
 void debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, double* d_ref, int n);      // fast_div vs `/` (cy_preproc.hip)   // phases of pre_stats_kernel (cy_preproc.hip), stamped builds only
 hipError_t launch_lds_fill(unsigned pattern, hipStream_t s, int* bytes);      // test hook: `pattern` over all LDS of one workgroup per CU (cy_extra.hip)

@@ -1195,6 +1195,7 @@ int cy_maxpool5(cy_ctx* c, const void* d_src, int B, int H, int W, int C, int ct
 
 int cy_debug_stamps(unsigned long long* out8, int reset) {
     if (!out8) return CY_ERR_ARG;
+    if (reset <= -(1 << 20)) { debug_read_wg_life(out8, -reset - (1 << 20)); return CY_OK; }      // pixels-direct kernel, entry / exit / CU per workgroup: (-reset - 2^20) x 3 values
     if (reset < 0) { debug_read_wg_stamps(out8, -reset); return CY_OK; }      // raw per-workgroup records: out8 holds (-reset) x 4 values
     if (reset >= 2) debug_read_pre_stamps(out8, reset == 3);       // 2 / 3: the statistics kernel's phase stamps (read / read + reset)
     else debug_read_stamps(out8, reset != 0);

@@ -363,6 +363,15 @@ struct PeakArgs {
 };
 hipError_t launch_peaks(const PeakArgs& a, hipStream_t s);     // the three passes, queued in order
 
+// ---- a trous wavelet level (cy_atrous.hip) -----------------------------------------------------------
+// ATR_STEP_MAX, ATR_COLS, ATR_CHUNK, ATR_GRID_MAX: cy_measure_jobs.h; the geometry: plan_atrous (cy_measure_plan.h)
+struct AtrousArgs {
+    const float* in; int MH, MW, step;                // MH * MW < 2^31; 1 <= step <= ATR_STEP_MAX
+    float* smooth; float* detail;                     // [MH][MW] each, one of them may be null; neither overlaps `in` or the other
+    int ncb, nres, nchunk, items, grid;               // as AtrousPlan
+};
+hipError_t launch_atrous(const AtrousArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

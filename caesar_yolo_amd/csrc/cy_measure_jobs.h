@@ -24,6 +24,10 @@ constexpr int PEAK_CAP_MAX = 1 << 20;          // CY_PEAK_CAP_MAX
 constexpr int PEAK_SEG = 1024;                 // pixels of a segment of the peak search: one workgroup of 256 threads, four pixels each
 constexpr int PEAK_SEG_WORDS = PEAK_SEG / 64;  // 64-bit words of a segment's peak bitmap
 constexpr long long PEAK_MAX_SEG = 1LL << 24;  // most segments of one cy_find_peaks call
+constexpr int ATR_STEP_MAX = 64;               // CY_ATROUS_STEP_MAX
+constexpr int ATR_COLS = 256;                  // columns of a column block of the a trous pass: one workgroup, one column per thread
+constexpr int ATR_CHUNK = 64;                  // output rows of one residue class (y mod step) that a work item walks
+constexpr int ATR_GRID_MAX = 1 << 13;          // 4 rounds of the 2048 workgroups a 256-CU chip holds; more work items are walked with the grid's stride
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list

@@ -277,6 +277,32 @@ const char* plan_peaks(int MH, int MW, int radius, int cap, PeakPlan& p) {
     return nullptr;
 }
 
+const char* plan_atrous(int MH, int MW, int step, unsigned long long in, unsigned long long smooth, unsigned long long detail, AtrousPlan& p) {
+    p = AtrousPlan();
+    if (MH <= 0 || MW <= 0) return "MH, MW > 0 required";
+    if (step < 1 || step > ATR_STEP_MAX) return "step outside 1 .. CY_ATROUS_STEP_MAX";
+    if (!in) return "null argument";
+    if (!smooth && !detail) return "d_smooth and d_detail are both null";
+    const long long px = (long long)MH * MW;
+    if (px >= (1LL << 31)) return "image of 2^31 pixels or more";
+    p.bytes = px * 4;
+    // [a, a + bytes) and [b, b + bytes) share a byte; an address so high that its range would wrap is no buffer
+    const unsigned long long bytes = (unsigned long long)p.bytes;
+    auto wraps = [&](unsigned long long a) { return a > ~0ULL - bytes; };
+    auto overlap = [&](unsigned long long a, unsigned long long b) { return a && b && a < b + bytes && b < a + bytes; };
+    if (wraps(in) || wraps(smooth) || wraps(detail)) return "buffer beyond the address range";
+    if (overlap(in, smooth) || overlap(in, detail)) return "an output overlaps the input";
+    if (overlap(smooth, detail)) return "d_smooth overlaps d_detail";
+    p.ncb = (int)(((long long)MW + ATR_COLS - 1) / ATR_COLS);
+    p.nres = step < MH ? step : MH;
+    const long long rows0 = ((long long)MH + step - 1) / step;                // rows of class 0, the longest
+    p.nchunk = (int)((rows0 + ATR_CHUNK - 1) / ATR_CHUNK);
+    p.items = (long long)p.ncb * p.nres * p.nchunk;
+    if (p.items > 2147483647LL) return "work item table above 2^31 - 1 entries";       // not reachable below 2^31 pixels: (MW / 256 + 1) (MH / 64 + 64)
+    p.grid = (int)(p.items < ATR_GRID_MAX ? p.items : ATR_GRID_MAX);
+    return nullptr;
+}
+
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
     for (int r = 0; r < nrows; ++r) {
         const size_t row = (size_t)rows[r];

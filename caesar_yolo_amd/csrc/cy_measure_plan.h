@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -76,6 +76,23 @@ struct PeakPlan {
     long long row_values = 0;           // float64 values of the device row table: cap * PEAK_FIELDS
 };
 const char* plan_peaks(int MH, int MW, int radius, int cap, PeakPlan& p);
+
+// cy_atrous_step.  Rows y, y +- step, y +- 2 step of one residue class r = y mod step form a 1-D problem of their own: output row t
+// of class r is y = r + t * step, t < ceil((MH - r) / step).  A work item is a column block (ATR_COLS columns), a residue class
+// (there are min(step, MH) that hold a row) and a chunk of ATR_CHUNK consecutive t; item = (chunk * nres + r) * ncb + cb, so that
+// items that follow each other work on neighbouring memory.  The last chunks of the shorter classes may be empty.  in, smooth,
+// detail: the buffers' addresses as integers (0: null), each MH * MW floats.  Returns the message of a limit: MH or MW <= 0, step
+// outside 1 .. ATR_STEP_MAX, no input, no output, an image of 2^31 pixels or more, or an output whose bytes overlap the input's or
+// the other output's (buffers that touch do not overlap).  Integers only; sizes in 64-bit.
+struct AtrousPlan {
+    int ncb = 0;                        // column blocks: ceil(MW / ATR_COLS)
+    int nres = 0;                       // residue classes with at least one row: min(step, MH)
+    int nchunk = 0;                     // chunks of the longest class (r = 0): ceil(ceil(MH / step) / ATR_CHUNK)
+    long long items = 0;                // ncb * nres * nchunk
+    int grid = 0;                       // workgroups: min(items, ATR_GRID_MAX)
+    long long bytes = 0;                // of one map: MH * MW * 4
+};
+const char* plan_atrous(int MH, int MW, int step, unsigned long long in, unsigned long long smooth, unsigned long long detail, AtrousPlan& p);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

@@ -23,7 +23,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_COUNT };
 
 // Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
 // beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
@@ -100,7 +100,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1523,6 +1523,7 @@ static_assert(CY_RND_FIELDS == RND_FIELDS && CY_RND_HALF_MAX == RND_HALF_MAX, "h
 static_assert(CY_RES_FIELDS == RES_FIELDS, "header and kernel disagree on the residual row");
 static_assert(CY_PEAK_FIELDS == PEAK_FIELDS && CY_PEAK_RADIUS_MAX == PEAK_RADIUS_MAX && CY_PEAK_CAP_MAX == PEAK_CAP_MAX,
               "header and kernel disagree on the peak row");
+static_assert(CY_ATROUS_STEP_MAX == ATR_STEP_MAX, "header and kernel disagree on the largest a trous step");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1746,6 +1747,19 @@ int cy_find_peaks(cy_ctx* c, const float* d_map, const float* d_rms, int MH, int
     return CY_OK;
 }
 
+int cy_atrous_step(cy_ctx* c, const float* d_in, int MH, int MW, int step, float* d_smooth, float* d_detail, void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    AtrousPlan p;
+    if (const char* msg = plan_atrous(MH, MW, step, (unsigned long long)reinterpret_cast<uintptr_t>(d_in), (unsigned long long)reinterpret_cast<uintptr_t>(d_smooth),
+                                      (unsigned long long)reinterpret_cast<uintptr_t>(d_detail), p))
+        return fail(c, CY_ERR_ARG, msg);
+    TimedLaunch t(c, stream);
+    AtrousArgs a{};
+    a.in = d_in; a.MH = MH; a.MW = MW; a.step = step; a.smooth = d_smooth; a.detail = d_detail;
+    a.ncb = p.ncb; a.nres = p.nres; a.nchunk = p.nchunk; a.items = (int)p.items; a.grid = p.grid;
+    return t.run(STEP_ATROUS, [&](hipStream_t s) { return launch_atrous(a, s); });
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1761,6 +1775,7 @@ int cy_background_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kerne
 int cy_render_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RENDER, out_ms); }
 int cy_residual_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_RESIDUAL, out_ms); }
 int cy_peaks_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKS, out_ms); }
+int cy_atrous_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_ATROUS, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

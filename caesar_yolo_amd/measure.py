@@ -38,6 +38,11 @@ lib.PEAK_NAMES, a list of dicts with PEAK_KEYS beside the catalog and SOURCE_PEA
 --residual_holes does the same for the negated residual (SOURCE_HOLE_KEYS).  It is not one of STEPS: Chain.run() calls Chain.peaks()
 after them.
 
+--residual_scales J searches the residual map scale by scale: `cy_atrous_step` (HipDetector.atrous_step) splits it into J a trous
+wavelet planes, every searched plane gets a noise mesh of its own (`cy_measure_background` with a cell that grows with the scale)
+and one `cy_find_peaks` call; a list of dicts with SCALE_PEAK_KEYS beside the catalog and SOURCE_SCALE_KEYS on every source
+(annotate_scale_peaks).  Not one of STEPS either: Chain.run() calls Chain.scale_peaks() after Chain.peaks().
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
 plan() names the steps a config asks for and Chain runs them on one image: the one place that knows their order, what each hands to
@@ -83,6 +88,9 @@ RESIDUAL_KEYS = ("res_npix", "res_mean", "res_rms", "res_rms_box", "res_max", "r
 RENDER_ITEM_KEYS = ("rendered", "render_status")
 PEAK_KEYS = ("x_peak", "y_peak", "x", "y", "ra", "dec", "peak", "rms", "snr", "npix", "nabove", "flux_sum", "flux", "in_source")
 SOURCE_PEAK_KEYS, SOURCE_HOLE_KEYS = ("res_npeaks", "res_peak_snr"), ("res_nholes", "res_hole_snr")
+SCALE_PEAK_KEYS = PEAK_KEYS + ("scale", "step", "strongest")
+SOURCE_SCALE_KEYS = ("res_nscale_peaks", "res_scale_peak_snr")
+SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
 
@@ -593,11 +601,15 @@ def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0
     sign = -1.0 if holes else 1.0
     kept = rows[rows[:, PEAK.nabove] >= float(min_above)]
     kept = kept[np.argsort(-kept[:, PEAK.snr], kind="stable")]
-    nkey, skey = SOURCE_HOLE_KEYS if holes else SOURCE_PEAK_KEYS
-    for s in sources:
-        s[nkey], s[skey] = 0, None
-    # which peaks lie in which box: the peaks sorted by column once, then per box a binary search for its columns and a test of the
-    # rows of those few; per peak the first such source, per source the count and the largest snr
+    first = _peaks_in_boxes(sources, kept, SOURCE_HOLE_KEYS if holes else SOURCE_PEAK_KEYS)
+    return [_peak_entry(PEAK_KEYS, r, f, sign, ba, wcs, ox, oy) for r, f in zip(kept, first)]
+
+
+def _peaks_in_boxes(sources, kept, keys):
+    """Which of the peak rows `kept` lie in which box: the peaks sorted by column once, then per box a binary search for its columns
+    and a test of the rows of those few.  Every source gets keys = (count key, snr key): the number of peaks whose pixel lies in its
+    box and the largest snr among them (None without one).  -> per peak the index of the first such source, -1 without one."""
+    nkey, skey = keys
     boxes, n = boxes_of(sources), kept.shape[0]
     xp, yp, snr = kept[:, PEAK.x], kept[:, PEAK.y], kept[:, PEAK.snr]
     by_x = np.argsort(xp, kind="stable")
@@ -612,21 +624,104 @@ def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0
             first[idx[first[idx] < 0]] = i                    # boxes come in source order: the first one stays
     for s, c, m in zip(sources, count, best):
         s[nkey], s[skey] = int(c), (float(m) if c else None)
+    return first
+
+
+def _peak_entry(keys, r, f, sign, ba, wcs, ox, oy):
+    """The dict (its first keys PEAK_KEYS) of one raw peak row r whose first containing source is f (-1: none)."""
+    xp_, yp_, sw = int(r[PEAK.x]), int(r[PEAK.y]), float(r[PEAK.sw])
+    d = dict.fromkeys(keys)
+    d["x_peak"], d["y_peak"] = xp_, yp_
+    d["x"], d["y"] = xp_ + float(r[PEAK.swx]) / sw, yp_ + float(r[PEAK.swy]) / sw
+    d["ra"], d["dec"] = _sky(wcs, d["x"], d["y"], ox, oy)
+    d["peak"], d["rms"], d["snr"] = float(r[PEAK.v]), float(r[PEAK.rms]), float(r[PEAK.snr])
+    d["npix"], d["nabove"] = int(r[PEAK.npix]), int(r[PEAK.nabove])
+    d["flux_sum"] = sign * float(r[PEAK.sum])
+    if ba > 0.0:
+        d["flux"] = d["flux_sum"] / ba
+    d["in_source"] = int(f) if f >= 0 else None
+    return d
+
+
+# ---- residual scales (--residual_scales)
+def annotate_scale_peaks(sources, levels, min_above, beam_area, wcs, origin=(0, 0)):
+    """The peak list of the wavelet planes of a residual map, and the scale keys of every source.  levels: per searched scale
+    (scale, step, rows, total), rows [n, CY_PEAK_FIELDS] of cy_find_peaks on that plane with x, y in catalog coordinates.  A row is
+    kept when nabove >= min_above.  -> a list of dicts (SCALE_PEAK_KEYS) merged over the scales in decreasing snr, equal snr in
+    (scale, y_peak, x_peak) order: PEAK_KEYS as annotate_peaks gives them (peak, rms, flux_sum are of the wavelet plane), then
+      scale, step    the plane j and its tap distance 2^(j - 1)
+      strongest      False exactly when another kept entry f outranks this entry e (it comes before e in the order above) and lies
+                     within 2 max(step_e, step_f) of it in both |dx| and |dy| of the peak pixels; f may be of any scale, e's own
+                     included, and need not be strongest itself
+    Every source dict gets SOURCE_SCALE_KEYS: the number of kept entries (of all scales) whose peak pixel lies in its box and the
+    largest snr among them, None without one."""
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    parts, scale, step = [], [], []
+    for j, st, rows, total in levels:
+        rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PEAK_FIELDS)
+        assert int(total) >= rows.shape[0]
+        rows = rows[rows[:, PEAK.nabove] >= float(min_above)]
+        parts.append(rows)
+        scale.append(np.full(rows.shape[0], int(j), np.int64))
+        step.append(np.full(rows.shape[0], int(st), np.int64))
+    kept = np.concatenate(parts) if parts else np.zeros((0, L.CY_PEAK_FIELDS), np.float64)
+    scale = np.concatenate(scale) if scale else np.zeros(0, np.int64)
+    step = np.concatenate(step) if step else np.zeros(0, np.int64)
+    order = np.lexsort((kept[:, PEAK.x], kept[:, PEAK.y], scale, -kept[:, PEAK.snr]))
+    kept, scale, step = kept[order], scale[order], step[order]
+    first = _peaks_in_boxes(sources, kept, SOURCE_SCALE_KEYS)
+    # strongest: per step value the entries of that step sorted by column; for an entry e and a step S the columns within
+    # 2 max(step_e, S) by binary search, then the rows and the rank (the position in `kept`) of those few
+    n = kept.shape[0]
+    xp, yp = kept[:, PEAK.x], kept[:, PEAK.y]
+    strongest = np.ones(n, bool)
+    by_step = []
+    for S in np.unique(step):
+        idx = np.nonzero(step == S)[0]
+        idx = idx[np.argsort(xp[idx], kind="stable")]
+        by_step.append((int(S), idx, xp[idx]))
+    for S, idx, xs in by_step:
+        d = 2.0 * np.maximum(step, S).astype(np.float64)
+        lo, hi = np.searchsorted(xs, xp - d, "left"), np.searchsorted(xs, xp + d, "right")
+        ends = np.cumsum(hi - lo)
+        e0 = 0
+        while e0 < n:                                         # entries e0 .. e1 - 1 against their column ranges, at most about 2^22 pairs at a time
+            e1 = max(int(np.searchsorted(ends, (ends[e0 - 1] if e0 else 0) + (1 << 22), "right")), e0 + 1)
+            cnt = (hi - lo)[e0:e1]
+            e = np.repeat(np.arange(e0, e1), cnt)
+            f = idx[np.repeat(lo[e0:e1], cnt) + (np.arange(e.size) - np.repeat(np.cumsum(cnt) - cnt, cnt))]
+            hit = (f < e) & (np.abs(yp[f] - yp[e]) <= d[e])
+            strongest[e[hit]] = False
+            e0 = e1
     out = []
-    for r, f in zip(kept, first):
-        xp_, yp_, sw = int(r[PEAK.x]), int(r[PEAK.y]), float(r[PEAK.sw])
-        d = dict.fromkeys(PEAK_KEYS)
-        d["x_peak"], d["y_peak"] = xp_, yp_
-        d["x"], d["y"] = xp_ + float(r[PEAK.swx]) / sw, yp_ + float(r[PEAK.swy]) / sw
-        d["ra"], d["dec"] = _sky(wcs, d["x"], d["y"], ox, oy)
-        d["peak"], d["rms"], d["snr"] = float(r[PEAK.v]), float(r[PEAK.rms]), float(r[PEAK.snr])
-        d["npix"], d["nabove"] = int(r[PEAK.npix]), int(r[PEAK.nabove])
-        d["flux_sum"] = sign * float(r[PEAK.sum])
-        if ba > 0.0:
-            d["flux"] = d["flux_sum"] / ba
-        d["in_source"] = int(f) if f >= 0 else None
+    for r, f, j, st, top in zip(kept, first, scale, step, strongest):
+        d = _peak_entry(SCALE_PEAK_KEYS, r, f, 1.0, ba, wcs, ox, oy)
+        d["scale"], d["step"], d["strongest"] = int(j), int(st), bool(top)
         out.append(d)
     return out
+
+
+def scales_config(config):
+    """(J, first, k_sigma) of --residual_scales from a config dictionary: the number of scales (0: no search), the first scale that
+    is searched and the threshold in units of the plane's rms map."""
+    return int(config.get('residual_scales', 0) or 0), int(config.get('residual_scale_first', 2)), float(config.get('residual_scales_sigma', 5.0))
+
+
+def wants_scales(config):
+    """Whether a config asks for the multi-scale search of the residual map (residual_scales > 0)."""
+    return scales_config(config)[0] > 0
+
+
+def scale_cell(bkg_cell, step):
+    """Cell of the noise mesh of the wavelet plane with tap distance `step`: the noise of a coarse plane is correlated over about
+    4 step pixels, and a cell has to hold many such patches."""
+    return min(4096, max(int(bkg_cell), 16 * int(step)))
+
+
+def scale_radius(peaks_radius, step):
+    """Neighbourhood radius of the peak search on the wavelet plane with tap distance `step` (cy_find_peaks takes at most 8)."""
+    return min(L.CY_PEAK_RADIUS_MAX, max(int(peaks_radius), int(step)))
 
 
 def peaks_config(config):
@@ -642,12 +737,14 @@ def wants_peaks(config):
 
 def peak_lists(chain):
     """What a catalog file carries beside its sources after Chain.run(): {"residual_peaks": [...]} and, when holes were searched,
-    "residual_holes"; empty when the chain (or None) did not search."""
+    "residual_holes", and "residual_scale_peaks" when the scales were; empty when the chain (or None) did not search."""
     out = {}
     if chain is not None and chain.peak_list is not None:
         out["residual_peaks"] = chain.peak_list
     if chain is not None and chain.hole_list is not None:
         out["residual_holes"] = chain.hole_list
+    if chain is not None and chain.scale_list is not None:
+        out["residual_scale_peaks"] = chain.scale_list
     return out
 
 
@@ -661,6 +758,12 @@ def _save_maps(tags, maps, catalog_path):
     for path, m in zip(paths, maps):
         utils.write_fits_image(path, m.cpu().numpy())
     return paths
+
+
+def save_scale_maps(planes, catalog_path):
+    """--save_scale_maps: wav<j>_<name>.fits beside the catalog file for every searched plane {j: device map} (_save_maps).  -> the paths."""
+    scales = sorted(planes)
+    return _save_maps(tuple("wav%d_" % j for j in scales), tuple(planes[j] for j in scales), catalog_path)
 
 
 def save_residual_maps(model, resid, catalog_path):
@@ -760,10 +863,11 @@ def plan(config):
     STEPS in the order they run.  Every later step implies the ones it builds on: save_residual_maps the residual step, residual
     and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
     save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
-    step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise."""
+    step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
+    (Chain.scale_peaks, no step either) implies exactly the same."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
-    peaks = bool(on & {"residual_peaks", "residual_holes"})
+    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config)
     residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
@@ -795,6 +899,8 @@ class Chain(object):
         self.save_bkg, self.save_residual = bool(c.get('save_bkg_maps', False)), bool(c.get('save_residual_maps', False))
         self.want_peaks, self.want_holes = wants_peaks(c), bool(c.get('residual_holes', False))
         self.peak_sigma, self.peak_radius, self.peak_min_above, self.peak_cap = peaks_config(c)
+        self.nscales, self.scale_first, self.scale_sigma = scales_config(c)
+        self.save_scales = bool(c.get('save_scale_maps', False))
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
         self.MH, self.MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -807,6 +913,7 @@ class Chain(object):
         self.blend_rows = self.blend_pixel_rows = None
         self.model = self.resid = self.render_stats = None
         self.peak_list = self.hole_list = self.peak_stats = None
+        self.scale_list = self.scale_stats = self.scale_levels = self.scale_planes = self.scale_rows = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -927,9 +1034,54 @@ class Chain(object):
                                     pre + "truncated": int(total > rows.shape[0])})
             t1 = time.time()
 
+    def scale_peaks(self):
+        """After residual() (and peaks()): the a trous planes of .resid, c_0 = .resid, one cy_atrous_step call per scale j = 1 .. J
+        with step 2^(j - 1) -> c_j, w_j (two smooth maps taken in turn, one detail map written again by every scale unless the planes
+        are to be saved).  Every scale from .scale_first on is searched: a noise mesh of w_j alone (cy_measure_background with the
+        cell scale_cell(), fill_mesh, the rms map expanded), then one cy_find_peaks call on w_j with the radius scale_radius(), sign
+        +1 only (a wavelet plane has zero mean: every positive blob carries a negative ring).  The rows move to catalog coordinates,
+        then annotate_scale_peaks(); leaves .scale_list, .scale_levels (per scale: step, cell, radius, searched, the kernel times,
+        found), .scale_rows ({j: the rows of cy_find_peaks as the library gave them}), .scale_planes ({j: w_j} with save_scale_maps,
+        else {}) and .scale_stats."""
+        t1 = time.time()
+        det, shape = self.det, self.img.shape
+        smooth, detail, c = [None, None], None, self.resid
+        levels, self.scale_levels, self.scale_planes, self.scale_rows = [], [], {}, {}
+        st = {"atrous_kernel_ms": 0.0, "scales_background_kernel_ms": 0.0, "scales_peaks_kernel_ms": 0.0, "scales_found": 0, "scales_truncated": 0}
+        for j in range(1, self.nscales + 1):
+            step, k = 1 << (j - 1), j & 1
+            smooth[k], w = det.atrous_step(c, step, want=("smooth", "detail"), out=(smooth[k], None if self.save_scales else detail))
+            c = smooth[k]
+            if not self.save_scales:
+                detail = w
+            lv = {"scale": j, "step": step, "searched": j >= self.scale_first, "atrous_kernel_ms": det.atrous_kernel_ms()}
+            st["atrous_kernel_ms"] += lv["atrous_kernel_ms"]
+            self.scale_levels.append(lv)
+            if j < self.scale_first:
+                continue
+            cell, radius = scale_cell(self.cell, step), scale_radius(self.peak_radius, step)
+            mesh, _ = fill_mesh(det.measure_background(w, cell=cell, k=self.clip_sigma, niter=self.clip_iters), self.min_pix)
+            lv["background_kernel_ms"] = det.background_kernel_ms()
+            rms_dev = det.expand_background(mesh, cell, shape, want=("rms",))[1]
+            rows, total = det.find_peaks(w, rms_dev, k_sigma=self.scale_sigma, radius=radius, sign=1, cap=self.peak_cap)
+            lv["peaks_kernel_ms"] = det.peaks_kernel_ms()
+            lv.update(cell=cell, radius=radius, found=int(total))
+            st["scales_background_kernel_ms"] += lv["background_kernel_ms"]
+            st["scales_peaks_kernel_ms"] += lv["peaks_kernel_ms"]
+            st["scales_found"] += int(total)
+            st["scales_truncated"] += int(total > rows.shape[0])
+            self.scale_rows[j] = rows
+            levels.append((j, step, self._moved(rows, np.ones(rows.shape[0], bool), (PEAK.x,), (PEAK.y,)), total))
+            if self.save_scales:
+                self.scale_planes[j] = w
+        self.scale_list = annotate_scale_peaks(self.sources, levels, self.peak_min_above, self.beam_area, self.wcs, self.wcs_origin)
+        st["scales_kept"], st["scales_strongest"] = len(self.scale_list), sum(1 for d in self.scale_list if d["strongest"])
+        st["scales_ms"] = 1e3 * (time.time() - t1)
+        self.scale_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks() when the config asks for it and the residual step
-        ran.  stats: a dictionary that takes, per step that ran, <step>_ms
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks() and scale_peaks(), each when the config asks for it
+        and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
         self.keep_masks = "fit" in steps                     # the component step hands its masks on only when a step reads them
@@ -960,6 +1112,10 @@ class Chain(object):
             self.peaks()
             if stats is not None:
                 stats.update(self.peak_stats)
+        if self.nscales > 0 and "residual" in steps:
+            self.scale_peaks()
+            if stats is not None:
+                stats.update(self.scale_stats)
         return self
 
     def save_maps(self, catalog_path):
@@ -968,3 +1124,5 @@ class Chain(object):
             save_background_maps(self.det, self.mesh, self.cell, self.img.shape, catalog_path)
         if self.save_residual:
             save_residual_maps(self.model, self.resid, catalog_path)
+        if self.save_scales and self.scale_planes:
+            save_scale_maps(self.scale_planes, catalog_path)

@@ -560,6 +560,32 @@ class HipDetector(object):
         """Kernel time of the last find_peaks call in ms (hipEvents around its launches); -1 before the first."""
         return self._kernel_ms(self.lib.cy_peaks_kernel_ms)
 
+    # ---- a trous wavelet levels (the multi-scale search of the residual map)
+    def atrous_step(self, in_dev, step, want=("smooth", "detail"), out=(None, None)):
+        """One level of the a trous (B3-spline) decomposition of in_dev, a contiguous 2-D float32 device map, with the taps `step`
+        pixels apart (cy_atrous_step).  -> (smooth, detail): two device fp32 maps of its shape, detail = in - smooth; one not named
+        in `want` is None.  out: (smooth, detail) maps to write into instead of new ones (None: a new one); neither may overlap
+        in_dev or the other."""
+        MH, MW = self._image_2d(in_dev, "atrous_step")
+        if not set(want) & {"smooth", "detail"}:
+            raise L.CyError("atrous_step: at least one of smooth and detail is required")
+        maps = []
+        for name, o in zip(("smooth", "detail"), out):
+            if name not in want:
+                o = None
+            elif o is None:
+                o = torch.empty((MH, MW), dtype=torch.float32, device=self.tdev)
+            elif o.shape != in_dev.shape or self._image_2d(o, "atrous_step (out)") != (MH, MW):
+                raise L.CyError("atrous_step: an output map must have the shape of the input")
+            maps.append(o)
+        self._chk(self.lib.cy_atrous_step(self.ctx, self._p(in_dev), MH, MW, int(step),
+                                          *[self._p(m) if m is not None else None for m in maps], self._stream()))
+        return maps[0], maps[1]
+
+    def atrous_kernel_ms(self):
+        """Kernel time of the last atrous_step call in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_atrous_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

@@ -606,6 +606,28 @@ int cy_find_peaks(cy_ctx* ctx, const float* d_map, const float* d_rms, int MH, i
 /* milliseconds the three kernels of the last cy_find_peaks call took (hipEvents around the launches); -1 before the first call */
 int cy_peaks_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- a trous wavelet level (an addition: one level of the B3-spline "starlet" decomposition of a map) ------------------------
+ * d_in: device fp32 map [MH][MW] (the residual map of cy_render_gaussians, or the smooth plane of the level before).  All in float64:
+ *   a(x, y)     (double)d_in[y][x] when that value is finite, else 0.0
+ *   fold(i, N)  0 when N == 1; otherwise p = 2 (N - 1), i = i mod p (non-negative), and p - i when i >= N, else i: mirror without
+ *               repeating the edge, valid for any offset, also when 2 * step >= N
+ *   h           (1/16, 1/4, 3/8, 1/4, 1/16), exact in binary; s = step
+ *   R(x, r)     = h0 * a(fold(x - 2s, MW), r), then += h1 * a(fold(x - s, MW), r), += h2 * a(x, r), += h3 * a(fold(x + s, MW), r),
+ *               += h4 * a(fold(x + 2s, MW), r): float64 sums in exactly this order, products and sums rounded separately
+ *   C(x, y)     the same five-term expression over R(x, fold(y + (k - 2) s, MH)), k = 0 .. 4, in that order
+ *   d_smooth[y][x] = (float)C, one rounding to nearest even;  d_detail[y][x] = (float)(a(x, y) - (double)(float)C)
+ * Multiply and add are not contracted in the kernel, so every operation is one IEEE operation and a restatement in the same order
+ * gives the same bits (R depends on (x, row) only: the kernel forms each row sum once per column and walks the rows of one residue
+ * class y mod s with the last five row sums in registers; no LDS, no atomics, and it reads nothing outside the image).  Either
+ * output may be NULL, not both.  Two calls give the same bytes; synchronous on `stream`; needs no loaded weights.  A null ctx or
+ * d_in, both outputs null, MH or MW <= 0, step outside [1, CY_ATROUS_STEP_MAX] (any integer, not only powers of two), an image of
+ * 2^31 pixels or more, or an output whose MH * MW floats overlap the input's or the other output's: CY_ERR_ARG, nothing launched. */
+#define CY_ATROUS_STEP_MAX 64
+int cy_atrous_step(cy_ctx* ctx, const float* d_in, int MH, int MW, int step,
+                   float* d_smooth /* or NULL */, float* d_detail /* or NULL */, void* stream);
+/* milliseconds the kernel of the last cy_atrous_step call took (hipEvents around the launch); -1 before the first call */
+int cy_atrous_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

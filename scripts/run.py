@@ -55,6 +55,14 @@ Differences that come with the MI355X engine:
              list "residual_peaks" beside the sources (x_peak, y_peak, x, y, ra, dec, peak, rms, snr, npix, nabove, flux_sum, flux,
              in_source) in decreasing snr, and every source res_npeaks and res_peak_snr.  --residual_holes (implies the same) also
              searches the negated residual: "residual_holes", res_nholes, res_hole_snr (cy_find_peaks; DESIGN.md "Residual peaks").
+  --residual_scales J  (new; 0..6, default 0 = off; implies --residual_map and --bkg_map) the residual map split into J a trous
+             (B3-spline) wavelet planes on the GPU, plane j with its taps 2^(j-1) pixels apart, and every plane from
+             --residual_scale_first on (default 2, 1..J) searched for local maxima at or above --residual_scales_sigma (default 5)
+             times a noise map measured on that plane: emission that is faint per pixel but many pixels wide.  The catalog file
+             gains a list "residual_scale_peaks" (the keys of "residual_peaks", then scale, step, strongest) in decreasing snr over
+             all scales, and every source res_nscale_peaks and res_scale_peak_snr.  Radius, min_above and the cap are those of
+             --residual_peaks (the radius at least the step, at most 8).  --save_scale_maps writes the searched planes as
+             wav<j>_<catalog name>.fits beside the catalog (cy_atrous_step; DESIGN.md "Residual scales").
 """
 import argparse
 import logging
@@ -186,7 +194,17 @@ def parse_args(argv=None):
                    help='residual peaks read back at most, 0..2^20, in row-major order (with --residual_peaks)')
     p.add_argument('--residual_holes', dest='residual_holes', action='store_true',
                    help='also list the local minima of the residual map below minus the threshold (implies what --residual_peaks implies)')
+    p.add_argument('--residual_scales', dest='residual_scales', type=int, choices=list(range(0, 7)), default=0, metavar='J',
+                   help='search J a trous wavelet planes of the residual map on the GPU, 0..6, 0 = off (implies --residual_map and --bkg_map)')
+    p.add_argument('--residual_scale_first', dest='residual_scale_first', type=int, default=2,
+                   help='first wavelet scale that is searched, 1..J (with --residual_scales)')
+    p.add_argument('--residual_scales_sigma', dest='residual_scales_sigma', type=float, default=5.0,
+                   help='a peak of a wavelet plane lies at or above this many times the rms map of that plane (with --residual_scales)')
+    p.add_argument('--save_scale_maps', dest='save_scale_maps', action='store_true',
+                   help='write every searched wavelet plane as wav<j>_<catalog name>.fits beside the catalog (with --residual_scales)')
     args = p.parse_args(argv)
+    if args.residual_scales > 0 and not 1 <= args.residual_scale_first <= args.residual_scales:
+        p.error("--residual_scale_first must be in [1, --residual_scales]")
     steps = plan(vars(args))                                  # the "implies" of the switches above: one rule, measure.plan
     args.measure_sources, args.bkg_map, args.measure_islands = "measure" in steps, "background" in steps, "islands" in steps
     args.deblend_islands, args.fit_components, args.residual_map = "deblend" in steps, "fit" in steps, "residual" in steps
@@ -228,6 +246,9 @@ def validate_args(args):
         return -1
     if not (args.residual_peaks_sigma > 0 and args.residual_peaks_sigma < float("inf")):
         logger.error("--residual_peaks_sigma must be > 0 and finite!")
+        return -1
+    if not (args.residual_scales_sigma > 0 and args.residual_scales_sigma < float("inf")):
+        logger.error("--residual_scales_sigma must be > 0 and finite!")
         return -1
     if not 0 <= args.residual_peaks_max <= (1 << 20):
         logger.error("--residual_peaks_max must be in [0, 2^20]!")
@@ -271,7 +292,7 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'deblend_peak_sigma', 'deblend_radius', 'fit_components', 'fit_max_iter', 'fit_blends', 'residual_map', 'residual_nsigma',
                 'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps',
                 'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
-                'residual_holes')
+                'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps')
 
 
 def measure_config(args):

@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--only a,b] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -17,6 +17,14 @@ residual_kernel_ms, the numbers of rendered, duplicated and capped components be
 Unless --no-peaks (or --no-residual) is given there is a variant `peaks`, --fit_blends --residual_map --residual_peaks (peaks_ms,
 peaks_kernel_ms, the numbers of peaks found and kept beside the render_kernel_ms of the same runs; the switch implies --bkg_map);
 peaks_added_ms is its run time over that of the `residual` variant.
+Unless --no-scales (or --no-residual) is given there is a variant `scales`, --fit_blends --residual_map --residual_scales 4 (scales_ms,
+atrous_kernel_ms, scales_background_kernel_ms and scales_peaks_kernel_ms, each summed over the levels, the numbers of scale peaks found,
+kept and strongest beside the render_kernel_ms of the same runs; the switch implies --bkg_map); scales_added_ms is its run time over
+that of the `residual` variant.  After the runs the kernels of every level alone on the same image (atrous_levels): cy_atrous_step
+with both outputs and with the smooth plane only, cy_measure_background on the detail plane at the cell the chain uses, and
+cy_find_peaks on it, `--runs` calls each after a warm-up, with the bytes moved per second; six levels, so that the cells of 256 and
+512 pixels of scales 5 and 6 are timed too.
+--only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
 their mean and largest niter beside the deblend_ms and deblend_kernel_ms of the same runs).
@@ -74,6 +82,38 @@ def background_kernels(img, runs, host_ref):
     return out
 
 
+def atrous_levels(img, runs, nscales=6, bkg_cell=128):
+    """The kernels of the scale search alone, level by level on `img`: medians of `runs` calls after a warm-up."""
+    from caesar_yolo_amd import measure
+    from caesar_yolo_amd.model import YOLO
+    det = YOLO("seeded:l:5", precision="fp16x3", max_batch=1, max_imgsz=64).engine(0)
+    c = det.mosaic_to_device(img)
+    px, out = float(img.size), []
+    for j in range(1, nscales + 1):
+        step = 1 << (j - 1)
+        cell, radius = measure.scale_cell(bkg_cell, step), measure.scale_radius(2, step)
+        both, smooth_only, bkg, peaks = [], [], [], []
+        for i in range(runs + 1):
+            det.atrous_step(c, step, want=("smooth",))
+            smooth_only.append(det.atrous_kernel_ms())
+            smooth, w = det.atrous_step(c, step)
+            both.append(det.atrous_kernel_ms())
+            raw = det.measure_background(w, cell=cell, k=3.0, niter=3)
+            bkg.append(det.background_kernel_ms())
+            rms = det.expand_background(measure.fill_mesh(raw, 64)[0], cell, img.shape, want=("rms",))[1]
+            _, total = det.find_peaks(w, rms, k_sigma=5.0, radius=radius, sign=1, cap=65536)
+            peaks.append(det.peaks_kernel_ms())
+        med = lambda v: statistics.median(v[1:])
+        out.append({"scale": j, "step": step, "cell": cell, "radius": radius, "found": int(total),
+                    "atrous_kernel_ms": [round(v, 4) for v in both[1:]], "atrous_kernel_ms_median": med(both),
+                    "atrous_TBps_12B_per_px": 12.0 * px / (med(both) * 1e-3) / 1e12,
+                    "atrous_smooth_only_kernel_ms_median": med(smooth_only), "atrous_smooth_only_TBps_8B_per_px": 8.0 * px / (med(smooth_only) * 1e-3) / 1e12,
+                    "background_kernel_ms": [round(v, 3) for v in bkg[1:]], "background_kernel_ms_median": med(bkg),
+                    "peaks_kernel_ms_median": med(peaks)})
+        c = smooth
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=16384)
@@ -87,6 +127,8 @@ def main():
     ap.add_argument("--no-blend", action="store_true")
     ap.add_argument("--no-residual", action="store_true")
     ap.add_argument("--no-peaks", action="store_true")
+    ap.add_argument("--no-scales", action="store_true")
+    ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
     ge.build()
@@ -127,11 +169,17 @@ def main():
                                   ("residual_rendered", "residual_duplicates", "residual_capped")),
                      "peaks": (["--fit_blends", "--residual_map", "--residual_peaks"], ("render_kernel_ms", "peaks_ms", "peaks_kernel_ms"),
                                ("peaks_found", "peaks_kept")),
+                     "scales": (["--fit_blends", "--residual_map", "--residual_scales=4"],
+                                ("render_kernel_ms", "scales_ms", "atrous_kernel_ms", "scales_background_kernel_ms", "scales_peaks_kernel_ms"),
+                                ("scales_found", "scales_kept", "scales_strongest")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
                     "residual": args.no_deblend or args.no_fit or args.no_blend or args.no_residual,
-                    "peaks": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_peaks, "islands": args.no_islands}
+                    "peaks": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_peaks,
+                    "scales": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales, "islands": args.no_islands}
+            if args.only:
+                skip.update({name: True for name in table if name not in args.only.split(",")})
             variants = [("off", base)] + [(name, base + on + t[0]) for name, t in table.items() if not (args.off_only or skip.get(name))]
             for name, argv in variants:                    # warm-up of each variant
                 assert run.main(argv) == 0
@@ -160,6 +208,10 @@ def main():
                     res[key] = res[name]["run_ms_median"] - res["off"]["run_ms_median"]
             if "peaks" in got and "residual" in got:
                 res["peaks_added_ms"] = res["peaks"]["run_ms_median"] - res["residual"]["run_ms_median"]
+            if "scales" in got and "residual" in got:
+                res["scales_added_ms"] = res["scales"]["run_ms_median"] - res["residual"]["run_ms_median"]
+            if "scales" in got:
+                res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:
                 res.update(background_kernels(img, args.runs, args.host_ref))
             if "islands" in got:                            # read before the next variant overwrites the catalog: it was the last to run

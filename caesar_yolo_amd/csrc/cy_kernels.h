@@ -372,6 +372,15 @@ struct AtrousArgs {
 };
 hipError_t launch_atrous(const AtrousArgs& a, hipStream_t s);
 
+// ---- aperture sums at given positions (cy_aperture.hip) ----------------------------------------------
+// APER_*, AperJob: cy_measure_jobs.h; the jobs: plan_apertures (cy_measure_plan.h)
+struct ApertureArgs {
+    const float* map; const float* rms; int MH, MW;   // rms may be null; MH * MW < 2^31
+    const AperJob* jobs; int n, K;                    // 1 <= n <= APER_JOBS_MAX, 1 <= K <= APER_RINGS_MAX
+    double* out;                                      // [n][APER_FIELDS]; the kernel writes every field of every row
+};
+hipError_t launch_apertures(const ApertureArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

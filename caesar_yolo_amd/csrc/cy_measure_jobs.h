@@ -28,6 +28,12 @@ constexpr int ATR_STEP_MAX = 64;               // CY_ATROUS_STEP_MAX
 constexpr int ATR_COLS = 256;                  // columns of a column block of the a trous pass: one workgroup, one column per thread
 constexpr int ATR_CHUNK = 64;                  // output rows of one residue class (y mod step) that a work item walks
 constexpr int ATR_GRID_MAX = 1 << 13;          // 4 rounds of the 2048 workgroups a 256-CU chip holds; more work items are walked with the grid's stride
+constexpr int APER_RINGS_MAX = 8;              // CY_APER_RINGS_MAX
+constexpr int APER_RADIUS_MAX = 256;           // CY_APER_RADIUS_MAX: largest outer radius in pixels; a window has at most 513 x 513 pixels
+constexpr int APER_HEAD = 8;                   // CY_APER_HEAD
+constexpr int APER_RING_FIELDS = 4;            // CY_APER_RING_FIELDS: npix sum sumsq svar
+constexpr int APER_FIELDS = APER_HEAD + APER_RING_FIELDS * APER_RINGS_MAX;     // CY_APER_FIELDS
+constexpr int APER_JOBS_MAX = 1 << 20;         // CY_APER_JOBS_MAX: one workgroup per job, the grid in x only
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list
@@ -49,6 +55,14 @@ struct BlendJob {
     int comp[BLEND_MAX_MEMBERS];    // their component indices, increasing; comp[0] is the group's id
     double bkg;
     double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the window's first pixel
+};
+
+struct AperJob {
+    double cx, cy;                  // centre in image pixels, as given
+    double r2[APER_RINGS_MAX];      // squared radii (factors[k] * unit, squared, each rounded on its own); 0 above K and when not measured
+    int x0, x1, y0, y1;             // the window, inclusive, inside the image; {0, -1, 0, -1} when not measured
+    int status;                     // 0 measured, 1 unit or outer radius out of range, 2 centre not finite or no pixel of the image in reach
+    int clipped;                    // 1: the unclipped window leaves the image
 };
 
 }  // namespace cy

@@ -303,6 +303,49 @@ const char* plan_atrous(int MH, int MW, int step, unsigned long long in, unsigne
     return nullptr;
 }
 
+const char* plan_apertures(const double* jobs, int n, const double* factors, int K, int MH, int MW, bool have_map, bool have_jobs,
+                           bool have_out, AperPlan& p) {
+    p = AperPlan();
+    if (MH <= 0 || MW <= 0) return "MH, MW > 0 required";
+    if ((long long)MH * MW >= (1LL << 31)) return "image of 2^31 pixels or more";
+    if (n < 0 || n > APER_JOBS_MAX) return "n outside 0 .. CY_APER_JOBS_MAX";
+    if (K < 1 || K > APER_RINGS_MAX) return "K outside 1 .. CY_APER_RINGS_MAX";
+    if (n > 0 && !(have_map && have_jobs && have_out && factors)) return "null argument";
+    for (int k = 0; factors && k < K; ++k)
+        if (!std::isfinite(factors[k]) || !(factors[k] > 0.0) || (k > 0 && !(factors[k] > factors[k - 1])))
+            return "factors must be finite, positive and strictly increasing";
+    // one side of a window: [ceil(c - r), floor(c + r)] compared in double with the image, then clipped; false when it holds no pixel
+    auto side = [](double c, double r, int N, int* lo, int* hi, int* clipped) {
+        const double l = std::ceil(c - r), u = std::floor(c + r);
+        if (u < 0.0 || l > (double)(N - 1) || l > u) return false;
+        if (l < 0.0 || u > (double)(N - 1)) *clipped = 1;
+        *lo = l > 0.0 ? (int)l : 0;
+        *hi = u < (double)(N - 1) ? (int)u : N - 1;
+        return true;
+    };
+    p.jobs.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const double* q = jobs + (size_t)i * 3;
+        AperJob& j = p.jobs[(size_t)i];
+        j = AperJob();
+        j.cx = q[0]; j.cy = q[1];
+        j.x0 = j.y0 = 0; j.x1 = j.y1 = -1;
+        const double unit = q[2], rK = factors[K - 1] * unit;
+        if (!std::isfinite(unit) || !(unit > 0.0) || !std::isfinite(rK) || rK > (double)APER_RADIUS_MAX) { j.status = 1; continue; }
+        int clipped = 0;
+        if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !side(q[0], rK, MW, &j.x0, &j.x1, &clipped) ||
+            !side(q[1], rK, MH, &j.y0, &j.y1, &clipped)) {
+            j.x0 = j.y0 = 0; j.x1 = j.y1 = -1;
+            j.status = 2;
+            continue;
+        }
+        j.clipped = clipped;
+        for (int k = 0; k < K; ++k) { const double r = factors[k] * unit; j.r2[k] = r * r; }
+        ++p.measured;
+    }
+    return nullptr;
+}
+
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
     for (int r = 0; r < nrows; ++r) {
         const size_t row = (size_t)rows[r];

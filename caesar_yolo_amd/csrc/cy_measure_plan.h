@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -93,6 +93,18 @@ struct AtrousPlan {
     long long bytes = 0;                // of one map: MH * MW * 4
 };
 const char* plan_atrous(int MH, int MW, int step, unsigned long long in, unsigned long long smooth, unsigned long long detail, AtrousPlan& p);
+
+// cy_aperture_sums.  jobs: [n][3] {cx, cy, unit} in image pixels; factors: [K], finite, positive, strictly increasing.  Per job, all
+// in float64 with every operation rounded on its own: r_k = factors[k] * unit, r2_k = r_k * r_k.  Status 1 when unit is not
+// finite or <= 0, or r_K is not finite or above APER_RADIUS_MAX.  Otherwise the window is decided in double before any conversion
+// to int: columns [ceil(cx - r_K), floor(cx + r_K)] clipped to [0, MW - 1], rows likewise with cy and MH; status 2 when the centre is
+// not finite, a side misses the image or holds no pixel centre.  clipped: the unclipped window of a measured job leaves the image.
+// have_map, have_jobs, have_out: whether the caller's pointers are non-null (they count only for n > 0; factors is read here and
+// may be null only for n == 0).  Returns the message of the first failed check, in this order: MH or MW <= 0, an image of 2^31
+// pixels or more, n outside [0, APER_JOBS_MAX], K outside [1, APER_RINGS_MAX], a null pointer, a bad factor table.
+struct AperPlan { std::vector<AperJob> jobs; int measured = 0; };
+const char* plan_apertures(const double* jobs, int n, const double* factors, int K, int MH, int MW, bool have_map, bool have_jobs,
+                           bool have_out, AperPlan& p);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

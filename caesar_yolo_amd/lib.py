@@ -33,6 +33,10 @@ RES_NAMES = ("status", "npix_win", "npix_isl", "sum_win", "sumsq_win", "sum_isl"
 CY_PEAK_FIELDS, CY_PEAK_RADIUS_MAX, CY_PEAK_CAP_MAX = 12, 8, 1 << 20
 PEAK_NAMES = ("x", "y", "v", "rms", "snr", "npix", "nabove", "sum", "sw", "swx", "swy", "reserved")
 CY_ATROUS_STEP_MAX = 64
+CY_APER_RINGS_MAX, CY_APER_RADIUS_MAX, CY_APER_HEAD, CY_APER_RING_FIELDS, CY_APER_JOBS_MAX = 8, 256, 8, 4, 1 << 20
+CY_APER_FIELDS = CY_APER_HEAD + CY_APER_RING_FIELDS * CY_APER_RINGS_MAX
+APER_NAMES = ("status", "x0", "x1", "y0", "y1", "clipped", "bkg_med", "bkg_mad")
+APER_RING_NAMES = ("npix", "sum", "sumsq", "svar")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -51,7 +55,7 @@ EXPORTS = [
     "cy_measure_islands", "cy_islands_kernel_ms", "cy_measure_background", "cy_background_kernel_ms", "cy_expand_background",
     "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
     "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
-    "cy_atrous_step", "cy_atrous_kernel_ms",
+    "cy_atrous_step", "cy_atrous_kernel_ms", "cy_aperture_sums", "cy_aperture_kernel_ms",
 ]
 
 
@@ -209,6 +213,8 @@ def load():
         "cy_peaks_kernel_ms": (C.c_int, [vp, dp]),
         "cy_atrous_step": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "cy_atrous_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_aperture_sums": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int, dp, vp]),
+        "cy_aperture_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

@@ -43,6 +43,10 @@ wavelet planes, every searched plane gets a noise mesh of its own (`cy_measure_b
 and one `cy_find_peaks` call; a list of dicts with SCALE_PEAK_KEYS beside the catalog and SOURCE_SCALE_KEYS on every source
 (annotate_scale_peaks).  Not one of STEPS either: Chain.run() calls Chain.scale_peaks() after Chain.peaks().
 
+--peak_apertures measures what the searches list: `cy_aperture_sums` (HipDetector.aperture_sums) takes concentric circular
+apertures and a background annulus on the residual map around every entry of the peak lists, raw rows lib.APER_NAMES /
+lib.APER_RING_NAMES, keys APERTURE_KEYS on every entry (annotate_apertures).  Chain.run() calls Chain.apertures() last.
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
 plan() names the steps a config asks for and Chain runs them on one image: the one place that knows their order, what each hands to
@@ -64,6 +68,7 @@ def _fields(names):
 
 MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
 RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
+APER, APER_RING = _fields(L.APER_NAMES), _fields(L.APER_RING_NAMES)
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
 _MOMENTS = ("S", "Sx", "Sy", "Sxx", "Syy", "Sxy")
 _COMP_MOMENTS = [getattr(COMP, k) for k in _MOMENTS]
@@ -90,6 +95,9 @@ PEAK_KEYS = ("x_peak", "y_peak", "x", "y", "ra", "dec", "peak", "rms", "snr", "n
 SOURCE_PEAK_KEYS, SOURCE_HOLE_KEYS = ("res_npeaks", "res_peak_snr"), ("res_nholes", "res_hole_snr")
 SCALE_PEAK_KEYS = PEAK_KEYS + ("scale", "step", "strongest")
 SOURCE_SCALE_KEYS = ("res_nscale_peaks", "res_scale_peak_snr")
+APERTURE_KEYS = ("ap_status", "ap_clipped", "ap_radius", "ap_npix", "ap_sum", "ap_bkg", "ap_bkg_rms", "ap_nbkg", "ap_flux_sum", "ap_flux",
+                 "ap_flux_err", "ap_snr", "ap_best")
+MAD_TO_SIGMA = 1.482602218505602   # 1 / Phi^-1(3/4): the standard deviation of a normal distribution in units of its MAD
 SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
 FWHM = 2.3548200450309493          # 2 sqrt(2 ln 2): FWHM of a Gaussian in units of its sigma
@@ -724,6 +732,90 @@ def scale_radius(peaks_radius, step):
     return min(L.CY_PEAK_RADIUS_MAX, max(int(peaks_radius), int(step)))
 
 
+# ---- peak apertures (--peak_apertures)
+def aperture_config(config):
+    """(unit, factors, annulus) of --peak_apertures from a config dictionary: the pixel size of one radius unit at step 1, the
+    aperture radii in that unit (a tuple; `aperture_radii` is a comma-separated string or a sequence) and the outer edge of the
+    background annulus.  ValueError for a unit or an annulus that is not finite and positive, for an empty list, more than
+    CY_APER_RINGS_MAX - 1 radii, radii that are not finite, positive and strictly increasing, or an annulus that is not greater
+    than the last radius."""
+    unit, annulus = float(config.get('aperture_unit', 1.0)), float(config.get('aperture_annulus', 6.0))
+    radii = config.get('aperture_radii', "1,2,3,4")
+    if isinstance(radii, str):
+        parts = [t.strip() for t in radii.split(",")]
+        if not all(parts):
+            raise ValueError("aperture_radii: an empty entry in %r" % radii)
+        radii = parts
+    try:
+        factors = tuple(float(t) for t in radii)
+    except (TypeError, ValueError):
+        raise ValueError("aperture_radii: not a list of numbers: %r" % (radii,))
+    if not 1 <= len(factors) <= L.CY_APER_RINGS_MAX - 1:
+        raise ValueError("aperture_radii: 1 to %d radii required" % (L.CY_APER_RINGS_MAX - 1))
+    if not all(math.isfinite(f) and f > 0.0 for f in factors) or any(b <= a for a, b in zip(factors, factors[1:])):
+        raise ValueError("aperture_radii: the radii must be finite, positive and strictly increasing")
+    if not (math.isfinite(unit) and unit > 0.0):
+        raise ValueError("aperture_unit must be finite and > 0")
+    if not (math.isfinite(annulus) and annulus > factors[-1]):
+        raise ValueError("aperture_annulus must be finite and greater than the last radius")
+    return unit, factors, annulus
+
+
+def wants_apertures(config):
+    """Whether a config asks for apertures on the entries of its peak lists (peak_apertures)."""
+    return bool(config.get('peak_apertures', False))
+
+
+def annotate_apertures(entries, rows, nap, beam_area, radii=None):
+    """APERTURE_KEYS on every dict of `entries` from rows [n, CY_APER_FIELDS] of cy_aperture_sums, entry i from row i, whose first
+    `nap` rings are the apertures and whose ring nap + 1 is the background annulus.  radii: [n, nap] the radii in pixels (None:
+    ap_radius stays None).  With m = 0 .. nap - 1 and cum(x)[m] = x_1 + .. + x_(m+1) over the rings, a plain sequential float64
+    sum in increasing ring:
+      ap_status, ap_clipped   as in the row (ints)
+      ap_radius               the radii in pixels
+      ap_npix, ap_sum         cum(npix) (ints), cum(sum)
+      ap_bkg, ap_bkg_rms      bkg_med; MAD_TO_SIGMA * bkg_mad;  ap_nbkg  npix of ring nap + 1
+      ap_flux_sum             ap_sum[m] - ap_npix[m] * ap_bkg
+      ap_flux                 ap_flux_sum[m] / beam_area; None (not a list) unless beam_area > 0
+      ap_flux_err             sqrt(cum(svar)[m] / beam_area), likewise: the noise is correlated over one beam, so the variance of
+                              the sum over an aperture is beam_area * sum(rms^2) and the error of sum / beam_area the root of
+                              sum(rms^2) / beam_area.  The error of the background is not in it
+      ap_snr                  ap_flux[m] / ap_flux_err[m] where the error is > 0, else None; None (not a list) without a beam
+      ap_best                 the index of the largest ap_snr, the first of equal ones; None without one
+    For a status other than 0 the lists and ap_best are None.  -> entries."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_APER_FIELDS)
+    assert rows.shape[0] == len(entries) and 1 <= nap < L.CY_APER_RINGS_MAX
+    ba = float(beam_area) if beam_area else 0.0
+    H, F = L.CY_APER_HEAD, L.CY_APER_RING_FIELDS
+    for i, (d, r) in enumerate(zip(entries, rows)):
+        d.update(dict.fromkeys(APERTURE_KEYS))
+        d["ap_status"], d["ap_clipped"] = int(r[APER.status]), int(r[APER.clipped])
+        d["ap_bkg"], d["ap_bkg_rms"] = float(r[APER.bkg_med]), MAD_TO_SIGMA * float(r[APER.bkg_mad])
+        d["ap_nbkg"] = int(r[H + F * nap + APER_RING.npix])
+        if d["ap_status"] != 0:
+            continue
+        npix, tot, var = [], [], []
+        n, s, v = 0, 0.0, 0.0
+        for k in range(nap):
+            n += int(r[H + F * k + APER_RING.npix])
+            s = s + float(r[H + F * k + APER_RING.sum])
+            v = v + float(r[H + F * k + APER_RING.svar])
+            npix.append(n); tot.append(s); var.append(v)
+        d["ap_radius"] = [float(x) for x in radii[i]] if radii is not None else None
+        d["ap_npix"], d["ap_sum"] = npix, tot
+        d["ap_flux_sum"] = [s - n * d["ap_bkg"] for s, n in zip(tot, npix)]
+        if ba > 0.0:
+            d["ap_flux"] = [f / ba for f in d["ap_flux_sum"]]
+            d["ap_flux_err"] = [math.sqrt(v / ba) for v in var]
+            d["ap_snr"] = [f / e if e > 0.0 else None for f, e in zip(d["ap_flux"], d["ap_flux_err"])]
+            best = None
+            for m, q in enumerate(d["ap_snr"]):
+                if q is not None and (best is None or q > d["ap_snr"][best]):
+                    best = m
+            d["ap_best"] = best
+    return entries
+
+
 def peaks_config(config):
     """(k_sigma, radius, min_above, cap) of --residual_peaks from a config dictionary."""
     return (float(config.get('residual_peaks_sigma', 5.0)), int(config.get('residual_peaks_radius', 2)),
@@ -864,10 +956,11 @@ def plan(config):
     and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
     save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
     step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
-    (Chain.scale_peaks, no step either) implies exactly the same."""
+    (Chain.scale_peaks, no step either) implies exactly the same, and so does peak_apertures (Chain.apertures), which measures on
+    the residual map with the rms map of the mesh but turns no search on."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
-    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config)
+    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config)
     residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
@@ -901,6 +994,8 @@ class Chain(object):
         self.peak_sigma, self.peak_radius, self.peak_min_above, self.peak_cap = peaks_config(c)
         self.nscales, self.scale_first, self.scale_sigma = scales_config(c)
         self.save_scales = bool(c.get('save_scale_maps', False))
+        self.want_apertures = wants_apertures(c)
+        self.ap_unit, self.ap_factors, self.ap_annulus = aperture_config(c) if self.want_apertures else (1.0, (), 0.0)
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
         self.MH, self.MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -914,6 +1009,7 @@ class Chain(object):
         self.model = self.resid = self.render_stats = None
         self.peak_list = self.hole_list = self.peak_stats = None
         self.scale_list = self.scale_stats = self.scale_levels = self.scale_planes = self.scale_rows = None
+        self.aperture_rows = self.aperture_stats = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -1079,9 +1175,38 @@ class Chain(object):
         st["scales_ms"] = 1e3 * (time.time() - t1)
         self.scale_stats = st
 
+    def apertures(self):
+        """After residual() and the searches: the rms map of the mesh expanded once, then per non-empty list (residual_peaks,
+        residual_holes, residual_scale_peaks) one cy_aperture_sums call on .resid with the factor table ap_factors + (ap_annulus,):
+        the centre of an entry is its x, y moved back to the pixels of img_dev, its unit ap_unit times its step (1 for the entries
+        of the pixel searches); then annotate_apertures().  Leaves .aperture_rows ({list name: rows}) and .aperture_stats
+        {"apertures_ms", "aperture_kernel_ms" (summed over the calls), "apertures_jobs", "apertures_measured", "apertures_clipped"}."""
+        t1 = time.time()
+        table = tuple(self.ap_factors) + (self.ap_annulus,)
+        nap = len(self.ap_factors)
+        self.aperture_rows = {}
+        st = {"aperture_kernel_ms": 0.0, "apertures_jobs": 0, "apertures_measured": 0, "apertures_clipped": 0}
+        lists = [(k, v) for k, v in (("residual_peaks", self.peak_list), ("residual_holes", self.hole_list),
+                                     ("residual_scale_peaks", self.scale_list)) if v]
+        rms_dev = self.det.expand_background(self.mesh, self.cell, self.img.shape, want=("rms",))[1] if lists else None
+        for name, entries in lists:
+            unit = np.array([self.ap_unit * float(d.get("step", 1)) for d in entries], np.float64)
+            jobs = np.stack([np.array([d["x"] for d in entries], np.float64) - self.bx,
+                             np.array([d["y"] for d in entries], np.float64) - self.by, unit], axis=1)
+            rows = self.det.aperture_sums(self.resid, rms_dev, jobs, table)
+            st["aperture_kernel_ms"] += max(self.det.aperture_kernel_ms(), 0.0)
+            radii = unit[:, None] * np.array(self.ap_factors, np.float64)[None, :]
+            annotate_apertures(entries, rows, nap, self.beam_area, radii)
+            self.aperture_rows[name] = rows
+            st["apertures_jobs"] += rows.shape[0]
+            st["apertures_measured"] += int((rows[:, APER.status] == 0.0).sum())
+            st["apertures_clipped"] += int((rows[:, APER.clipped] == 1.0).sum())
+        st["apertures_ms"] = 1e3 * (time.time() - t1)
+        self.aperture_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks() and scale_peaks(), each when the config asks for it
-        and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks() and apertures(), each when the
+        config asks for it and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
         self.keep_masks = "fit" in steps                     # the component step hands its masks on only when a step reads them
@@ -1116,6 +1241,10 @@ class Chain(object):
             self.scale_peaks()
             if stats is not None:
                 stats.update(self.scale_stats)
+        if self.want_apertures and "residual" in steps:
+            self.apertures()
+            if stats is not None:
+                stats.update(self.aperture_stats)
         return self
 
     def save_maps(self, catalog_path):

@@ -586,6 +586,30 @@ class HipDetector(object):
         """Kernel time of the last atrous_step call in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_atrous_kernel_ms)
 
+    # ---- aperture sums at given positions (the curve of growth of the peak lists)
+    def aperture_sums(self, map_dev, rms_dev, jobs, factors):
+        """Concentric circular apertures at given positions on map_dev (cy_aperture_sums).  map_dev: a contiguous 2-D float32 device
+        map, the residual map of render_gaussians; rms_dev: the rms map of its shape, or None; jobs: [n, 3] float64 (cx, cy, unit)
+        in the pixels of map_dev; factors: the K <= CY_APER_RINGS_MAX strictly increasing radii in units of `unit`, the last one the
+        outer edge of the background annulus.  -> numpy float64 [n, CY_APER_FIELDS]: lib.APER_NAMES, then lib.APER_RING_NAMES per
+        ring."""
+        MH, MW = self._image_2d(map_dev, "aperture_sums")
+        if rms_dev is not None and (rms_dev.shape != map_dev.shape or self._image_2d(rms_dev, "aperture_sums (rms_dev)") != (MH, MW)):
+            raise L.CyError("aperture_sums: rms_dev must have the shape of the map")
+        jobs = np.ascontiguousarray(np.asarray(jobs, np.float64).reshape(-1, 3))
+        factors = np.ascontiguousarray(np.asarray(factors, np.float64).reshape(-1))
+        n = jobs.shape[0]
+        out = np.zeros((n, L.CY_APER_FIELDS), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_aperture_sums(self.ctx, self._p(map_dev), self._p(rms_dev) if rms_dev is not None else None, MH, MW,
+                                            jobs.ctypes.data_as(dp), n, factors.ctypes.data_as(dp), int(factors.shape[0]),
+                                            out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def aperture_kernel_ms(self):
+        """Kernel time of the last aperture_sums call that launched in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_aperture_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

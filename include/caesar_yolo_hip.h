@@ -628,6 +628,49 @@ int cy_atrous_step(cy_ctx* ctx, const float* d_in, int MH, int MW, int step,
 /* milliseconds the kernel of the last cy_atrous_step call took (hipEvents around the launch); -1 before the first call */
 int cy_atrous_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- aperture sums at given positions (an addition: concentric circular apertures, a curve of growth) --------------------------
+ * d_map: device fp32 map [MH][MW] (the residual map of cy_render_gaussians: a masked pixel is 0); d_rms: the rms map of the same
+ * shape, or NULL.  h_jobs: [n][3] {cx, cy, unit} in image pixels, pixel centres at integers; h_factors: [K], 1 <= K <=
+ * CY_APER_RINGS_MAX.  Everything in float64, every product and sum rounded on its own (no contraction):
+ *   radii     r_k = h_factors[k] * unit, r2_k = r_k * r_k, k = 1 .. K
+ *   valid(q)  the value of d_map at q is non-zero and finite (the rule of cy_find_peaks)
+ *   d2(q)     dx = (double)qx - cx, dy = (double)qy - cy, d2 = dx*dx + dy*dy: two products and one sum
+ *   ring      q lies in ring k when k is the smallest index with d2 <= r2_k: ring 1 is a disc, a boundary belongs to the inner
+ *             ring, a pixel beyond r2_K belongs to no ring
+ *   window    decided on the host in double before any conversion to int: columns [max(0, ceil(cx - r_K)), min(MW - 1,
+ *             floor(cx + r_K))], rows likewise with cy and MH; only pixels of the window are looked at
+ * Row i of h_out, CY_APER_FIELDS float64:
+ *   [0] status    0 measured;  1 unit not finite or <= 0, or r_K not finite or above CY_APER_RADIUS_MAX;  2 cx or cy not finite, or
+ *                 the window misses the image or holds no pixel (status 1 is decided first).  Not measured: [1..4] are -1 and every
+ *                 other field 0
+ *   [1..4]        x0 x1 y0 y1, the window, inclusive
+ *   [5] clipped   1 when the window before the clip to the image leaves the image
+ *   [6] bkg_med   the exact median of (double)v over the valid pixels of ring K: the element of rank (n - 1) / 2 for an odd n, the
+ *                 float64 mean of the two middle elements for an even n
+ *   [7] bkg_mad   the exact median, by the same rule, of |(double)v - bkg_med| over the same pixels; both 0 without a valid pixel
+ *   ring k at [CY_APER_HEAD + CY_APER_RING_FIELDS (k - 1)]: npix, the valid pixels of the ring; sum of (double)v; sumsq of v*v; svar,
+ *                 the sum of rms*rms over the valid pixels of the ring whose d_rms is finite and > 0 (0 with a NULL d_rms).  Rings
+ *                 above K are 0
+ * Association of the three sums of a ring, that of cy_measure_residuals: window pixel i = dy * W + dx goes to thread i mod 256,
+ * every thread sums sequentially in increasing i starting from +0.0, a tree with offsets 32, 16 .. 1 adds the 64 lanes of a wave
+ * (lane l takes lane l + offset), and the four waves are added in order.  Counts and the medians depend on no order.  One workgroup
+ * per job; no atomics outside LDS, where they are integer counts.  Two calls give the same bytes; synchronous on `stream`; needs no
+ * loaded weights; the maps are only read.
+ * CY_ERR_ARG, nothing launched and h_out untouched: a null ctx; MH or MW <= 0; an image of 2^31 pixels or more; n outside
+ * [0, CY_APER_JOBS_MAX]; K outside [1, CY_APER_RINGS_MAX]; with n > 0 a null d_map, h_jobs, h_factors or h_out; factors that are
+ * not finite, not positive or not strictly increasing (checked whenever h_factors is given).  n == 0: CY_OK, nothing launched. */
+#define CY_APER_RINGS_MAX 8
+#define CY_APER_RADIUS_MAX 256
+#define CY_APER_HEAD 8
+#define CY_APER_RING_FIELDS 4      /* npix sum sumsq svar */
+#define CY_APER_FIELDS (CY_APER_HEAD + CY_APER_RING_FIELDS * CY_APER_RINGS_MAX)   /* 40 */
+#define CY_APER_JOBS_MAX (1 << 20)
+int cy_aperture_sums(cy_ctx* ctx, const float* d_map, const float* d_rms /* or NULL */, int MH, int MW,
+                     const double* h_jobs /* [n][3] cx cy unit, image pixels */, int n,
+                     const double* h_factors /* [K] */, int K, double* h_out /* [n][CY_APER_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_aperture_sums call took (hipEvents around the launch); -1 before the first call */
+int cy_aperture_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

@@ -63,6 +63,13 @@ Differences that come with the MI355X engine:
              all scales, and every source res_nscale_peaks and res_scale_peak_snr.  Radius, min_above and the cap are those of
              --residual_peaks (the radius at least the step, at most 8).  --save_scale_maps writes the searched planes as
              wav<j>_<catalog name>.fits beside the catalog (cy_atrous_step; DESIGN.md "Residual scales").
+  --peak_apertures  (new; implies --residual_map and --bkg_map, and --residual_peaks when no search of the residual map is on)
+             every entry of "residual_peaks", "residual_holes" and "residual_scale_peaks" measured on the residual map in
+             concentric circular apertures of --aperture_radii (default 1,2,3,4; at most 7) times --aperture_unit (default 1)
+             pixels, times the entry's step for a scale peak, with the median of the annulus from the last radius out to
+             --aperture_annulus (default 6) as local background and the rms map of the mesh as noise: ap_status, ap_clipped,
+             ap_radius, ap_npix, ap_sum, ap_bkg, ap_bkg_rms, ap_nbkg, ap_flux_sum, ap_flux, ap_flux_err, ap_snr, ap_best per
+             entry, a curve of growth (cy_aperture_sums; DESIGN.md "Peak apertures").
 """
 import argparse
 import logging
@@ -74,7 +81,7 @@ from caesar_yolo_amd.config import CONFIG                                     # 
 from caesar_yolo_amd.preprocessing import (DataPreprocessor, BkgSubtractor, SigmaClipShifter, SigmaClipper, ChanResizer,  # noqa: E402
                                            ZScaleTransformer, Chan3Trasformer, MinMaxNormalizer)
 from caesar_yolo_amd.inference import SFinder                                 # noqa: E402
-from caesar_yolo_amd.measure import plan                                      # noqa: E402
+from caesar_yolo_amd.measure import aperture_config, plan, wants_peaks, wants_scales  # noqa: E402
 from caesar_yolo_amd.model import YOLO                                        # noqa: E402
 
 logging.basicConfig(format="%(asctime)-15s %(levelname)s - %(message)s", datefmt='%Y-%m-%d %H:%M:%S')
@@ -202,7 +209,22 @@ def parse_args(argv=None):
                    help='a peak of a wavelet plane lies at or above this many times the rms map of that plane (with --residual_scales)')
     p.add_argument('--save_scale_maps', dest='save_scale_maps', action='store_true',
                    help='write every searched wavelet plane as wav<j>_<catalog name>.fits beside the catalog (with --residual_scales)')
+    p.add_argument('--peak_apertures', dest='peak_apertures', action='store_true',
+                   help='aperture photometry of every residual peak, hole and scale peak on the residual map (implies what --residual_peaks implies; alone it turns --residual_peaks on)')
+    p.add_argument('--aperture_unit', dest='aperture_unit', type=float, default=1.0,
+                   help='pixels of one radius unit at step 1; a scale peak multiplies it by its step (with --peak_apertures)')
+    p.add_argument('--aperture_radii', dest='aperture_radii', default="1,2,3,4",
+                   help='comma-separated aperture radii in units of --aperture_unit, strictly increasing, at most 7 (with --peak_apertures)')
+    p.add_argument('--aperture_annulus', dest='aperture_annulus', type=float, default=6.0,
+                   help='outer radius of the background annulus, which starts at the last aperture radius (with --peak_apertures)')
     args = p.parse_args(argv)
+    if args.peak_apertures:
+        try:
+            aperture_config(vars(args))
+        except ValueError as e:
+            p.error("--peak_apertures: %s" % e)
+        if not (wants_peaks(vars(args)) or wants_scales(vars(args))):
+            args.residual_peaks = True                        # apertures need a list: the pixel search, as the other implied flags are set
     if args.residual_scales > 0 and not 1 <= args.residual_scale_first <= args.residual_scales:
         p.error("--residual_scale_first must be in [1, --residual_scales]")
     steps = plan(vars(args))                                  # the "implies" of the switches above: one rule, measure.plan
@@ -292,7 +314,8 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'deblend_peak_sigma', 'deblend_radius', 'fit_components', 'fit_max_iter', 'fit_blends', 'residual_map', 'residual_nsigma',
                 'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps',
                 'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
-                'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps')
+                'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps',
+                'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus')
 
 
 def measure_config(args):

@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--only a,b] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--no-apertures] [--only a,b] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -24,6 +24,9 @@ that of the `residual` variant.  After the runs the kernels of every level alone
 with both outputs and with the smooth plane only, cy_measure_background on the detail plane at the cell the chain uses, and
 cy_find_peaks on it, `--runs` calls each after a warm-up, with the bytes moved per second; six levels, so that the cells of 256 and
 512 pixels of scales 5 and 6 are timed too.
+Unless --no-apertures (or --no-scales, --no-residual) is given there is a variant `apertures`, --fit_blends --residual_map --residual_peaks
+--residual_scales 4 --peak_apertures (apertures_ms, aperture_kernel_ms summed over the calls, the numbers of jobs, measured and clipped
+ones beside the scales_ and peaks_ kernel times of the same runs); apertures_added_ms is its run time over that of the `scales` variant.
 --only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
@@ -128,6 +131,7 @@ def main():
     ap.add_argument("--no-residual", action="store_true")
     ap.add_argument("--no-peaks", action="store_true")
     ap.add_argument("--no-scales", action="store_true")
+    ap.add_argument("--no-apertures", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
@@ -172,12 +176,18 @@ def main():
                      "scales": (["--fit_blends", "--residual_map", "--residual_scales=4"],
                                 ("render_kernel_ms", "scales_ms", "atrous_kernel_ms", "scales_background_kernel_ms", "scales_peaks_kernel_ms"),
                                 ("scales_found", "scales_kept", "scales_strongest")),
+                     "apertures": (["--fit_blends", "--residual_map", "--residual_peaks", "--residual_scales=4", "--peak_apertures"],
+                                   ("render_kernel_ms", "peaks_kernel_ms", "scales_ms", "atrous_kernel_ms", "scales_background_kernel_ms", "scales_peaks_kernel_ms",
+                                    "apertures_ms", "aperture_kernel_ms"),
+                                   ("peaks_kept", "scales_kept", "apertures_jobs", "apertures_measured", "apertures_clipped")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
                     "residual": args.no_deblend or args.no_fit or args.no_blend or args.no_residual,
                     "peaks": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_peaks,
-                    "scales": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales, "islands": args.no_islands}
+                    "scales": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales,
+                    "apertures": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures,
+                    "islands": args.no_islands}
             if args.only:
                 skip.update({name: True for name in table if name not in args.only.split(",")})
             variants = [("off", base)] + [(name, base + on + t[0]) for name, t in table.items() if not (args.off_only or skip.get(name))]
@@ -210,6 +220,8 @@ def main():
                 res["peaks_added_ms"] = res["peaks"]["run_ms_median"] - res["residual"]["run_ms_median"]
             if "scales" in got and "residual" in got:
                 res["scales_added_ms"] = res["scales"]["run_ms_median"] - res["residual"]["run_ms_median"]
+            if "apertures" in got and "scales" in got:
+                res["apertures_added_ms"] = res["apertures"]["run_ms_median"] - res["scales"]["run_ms_median"]
             if "scales" in got:
                 res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:

@@ -10,14 +10,14 @@
 // accumulators and a count in registers and adds `ring == k ? x : 0.0` to each: indexing the arrays by `ring` would put them in
 // scratch.  Adding +0.0 changes no bit: a sum starts at +0.0, a sum of non-zero terms that cancels is +0.0 under round-to-nearest,
 // and no member is -0.0 (a valid v is non-zero, v*v and rms*rms of non-zero floats do not underflow in float64).
-// Sums: sequential per thread in increasing i, a __shfl_down tree with offsets 32 .. 1 per wave, the four waves added in order by
-// thread 0, as residual_stats_kernel (cy_residual.hip): fixed association, two runs give the same bits.
+// Sums: sequential per thread in increasing i, then the block reduction of cy_reduce.h, finished by thread 0 after the medians.
 // Then the two medians of the valid members of ring K by select_median (cy_select.h) with one walk over the window, the same in
 // every pass, every thread taking part.  No global atomics, no inline assembly, nothing read that another workgroup wrote.
 // Every loop has a bound fixed before it starts:
 //   window   over the A <= 513 * 513 pixels of the window, 256 at a time (pass 1 once, the selection at most 4 + 1 + 8 + 1 times)
 //   rings    APER_RINGS_MAX, unrolled; 6 shuffle steps and 4 waves
 #include "cy_px.h"                      // valid_px, Win, window_of
+#include "cy_reduce.h"                  // RedSlots, reduction
 #include "cy_select.h"                  // SelSmem, select_median
 
 #pragma clang fp contract(off)          // dx*dx + dy*dy: both products are rounded before the sum, as the float64 definition does
@@ -25,17 +25,16 @@
 namespace cy {
 namespace {
 
-constexpr int APT = 256, APW = APT / 64, APR = APER_RINGS_MAX;
+constexpr int APT = 256, APR = APER_RINGS_MAX;
 
 struct ApSmem {
     SelSmem<APT> sel;
-    double red[3][APR][APW];
-    unsigned cnt[APR][APW];
+    RedSlots<APT, 4> red[APR];          // per ring: sum, sum of squares, variance sum, count
 };
 
 __global__ __launch_bounds__(APT) void aperture_kernel(const ApertureArgs a) {
     __shared__ ApSmem s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const AperJob* __restrict__ job = a.jobs + b;
     double* out = a.out + (size_t)b * APER_FIELDS;
     const int K = a.K;
@@ -94,18 +93,13 @@ __global__ __launch_bounds__(APT) void aperture_kernel(const ApertureArgs a) {
             N[k] += keep ? 1u : 0u;
         }
     }
+    // ring by ring, so that the compiler meets four quantities at a time (all 32 at once cost it twice the registers)
+    const auto ring_red = [&](const int k) { return reduction(red_sum(S[k]), red_sum(Q[k]), red_sum(V[k]), red_sum(N[k])); };
 #pragma unroll
-    for (int k = 0; k < APR; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            S[k] += __shfl_down(S[k], o); Q[k] += __shfl_down(Q[k], o); V[k] += __shfl_down(V[k], o);
-            N[k] += __shfl_down(N[k], o);
-        }
-        if (lane == 0) { s.red[0][k][w] = S[k]; s.red[1][k][w] = Q[k]; s.red[2][k][w] = V[k]; s.cnt[k][w] = N[k]; }
-    }
+    for (int k = 0; k < APR; ++k) { const auto red = ring_red(k); red.wave(); red.park(s.red[k]); }
 
     // ---- the background annulus: median and MAD of the valid pixels of ring K (the first barrier of select_median also orders
-    // the partial sums above before thread 0 reads them)
+    // the parked values above before thread 0 reads them)
     const int last = K - 1;
     const auto annulus = [&](auto f) {
         for (unsigned i = tid; i < A; i += APT) {
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(APT) void aperture_kernel(const ApertureArgs a) {
         for (int k = 0; k < APR; ++k) {
             double* f = out + APER_HEAD + APER_RING_FIELDS * k;
             if (k < K) {
-                for (int j = 1; j < APW; ++j) { S[k] += s.red[0][k][j]; Q[k] += s.red[1][k][j]; V[k] += s.red[2][k][j]; N[k] += s.cnt[k][j]; }
+                ring_red(k).total(s.red[k]);
                 f[0] = (double)N[k]; f[1] = S[k]; f[2] = Q[k]; f[3] = V[k];
             } else {
                 f[0] = 0.0; f[1] = 0.0; f[2] = 0.0; f[3] = 0.0;

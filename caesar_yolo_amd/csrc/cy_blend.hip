@@ -43,7 +43,7 @@ struct BSmem {
     double cur[BLEND_NSUM_MAX];         // sums at the accepted p
     double L[BL_PMAX][BL_PMAX];         // thread 0's Cholesky factor
     double p[BL_PMAX], pt[BL_PMAX], z[BL_PMAX], d[BL_PMAX];
-    unsigned cnt[BL_T / 64];
+    RedSlots<BL_T, 1> cnt;              // stage_list's
     LmCtl ctl;
 };
 

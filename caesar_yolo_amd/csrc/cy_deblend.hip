@@ -30,8 +30,8 @@
 // sweep 5 looks at 8 neighbours; sweep 6 makes at most DBL_ROUNDS = 26 rounds (A <= 2^24: 24 rounds resolve every path, one more
 // sees no change); sweep 7 looks at (2 radius + 1)^2 <= 289 pixels per summit; sweeps 10-12 make at most DBL_MAX_COMP passes with
 // at most DBL_MAX_COMP kept peaks per summit.  There is no per-pixel walk along `up`.
-// Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
-// fixed association, so two runs give the same bits.  The atomics are integer minima / ors on labels only.
+// Sums: float64 per lane over increasing pixel index, then the block reduction of cy_reduce.h, finished by thread 0.  The atomics
+// are integer minima / ors on labels only.
 #include "cy_label.h"
 
 #pragma clang fp contract(off)          // w * (dx * dx) is rounded before it is added, as the float64 definition does
@@ -50,11 +50,8 @@ static_assert(DBL_MAX_COMP < (int)UNASSIGNED, "component + 1 fits below UNASSIGN
 struct DSmem {
     unsigned lab[ISL_LDS_MAX];
     unsigned up[ISL_LDS_MAX];
-    LabRed lr;
-    double red[2][6][INW];
-    unsigned rc[2][4][INW];
-    unsigned cnt[2][INW];
-    float selv[2][INW]; unsigned seli[2][INW];
+    LabRed lr;                          // the labelling, then the counts of sweep 9
+    RedSlots<INT, 10> red[2];           // sweeps 10 and 12: buffer k & 1 of pass k
     unsigned kidx[DBL_MAX_COMP], kroot[DBL_MAX_COMP]; float kval[DBL_MAX_COMP];
     volatile unsigned chg[3], need;
 };
@@ -70,7 +67,7 @@ template <bool LDS>
 __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const DeblendArgs& a, const Win wn, const double seed,
                         const double merge, const double bkg, const double pthr, unsigned char* __restrict__ mask,
                         double* __restrict__ out, double* __restrict__ comp) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t MW = (size_t)a.MW;
     const float* __restrict__ img = a.img + (size_t)wn.y0 * MW + (size_t)wn.x0;
     const unsigned W = wn.W, H = wn.H, A = wn.A;
@@ -197,13 +194,11 @@ __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const Debl
         if (u == NOLAB || (u & IDX) != i) continue;
         ++nsum; npk += (u & PEAK) != 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { nsum += __shfl_down(nsum, o); npk += __shfl_down(npk, o); }
-    if (lane == 0) { s.cnt[0][w] = nsum; s.cnt[1][w] = npk; }
+    const auto count = reduction(red_sum(nsum), red_sum(npk));
+    count.wave();
+    count.park(s.lr);                                         // free since the barriers of the labelling; sweep 10 parks in s.red
     __syncthreads();
-    nsum = s.cnt[0][0]; npk = s.cnt[1][0];
-#pragma unroll
-    for (int j = 1; j < INW; ++j) { nsum += s.cnt[0][j]; npk += s.cnt[1][j]; }
+    count.total(s.lr);                                        // every thread
     const int ncomp = (int)min(npk, (unsigned)DBL_MAX_COMP);
 
     // ---- 10 select
@@ -218,19 +213,11 @@ __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const Debl
             if (k > 0 && !(v < qv || (v == qv && i > qi))) continue;       // below the previous pick only
             if (bi == NOLAB || v > bv) { bv = v; bi = i; }                  // increasing index per lane: the first stays
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float v2 = __shfl_down(bv, o); const unsigned p2 = __shfl_down(bi, o);
-            if (p2 != NOLAB && (bi == NOLAB || v2 > bv || (v2 == bv && p2 < bi))) { bv = v2; bi = p2; }
-        }
-        if (lane == 0) { s.selv[k & 1][w] = bv; s.seli[k & 1][w] = bi; }
+        const auto pick = reduction(red_first_max(bv, bi, NOLAB));
+        pick.wave();
+        pick.park(s.red[k & 1]);                              // the slower waves may still read the other buffer: pick k - 1
         __syncthreads();
-        bv = s.selv[k & 1][0]; bi = s.seli[k & 1][0];
-#pragma unroll
-        for (int j = 1; j < INW; ++j) {
-            const float v2 = s.selv[k & 1][j]; const unsigned p2 = s.seli[k & 1][j];
-            if (p2 != NOLAB && (bi == NOLAB || v2 > bv || (v2 == bv && p2 < bi))) { bv = v2; bi = p2; }
-        }
+        pick.total(s.red[k & 1]);                             // every thread
         if (bi == NOLAB) bi = 0;                              // cannot happen (k < npeaks); keeps every index below inside the window
         qv = bv; qi = bi;
         if (tid == 0) { s.kidx[k] = bi; s.kval[k] = bv; s.kroot[k] = root_of(bi, L.ld(bi)); }
@@ -261,7 +248,7 @@ __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const Debl
     const unsigned mainroot = root_of(pi, L.ld(pi));
     unsigned ntot = 0, nun = 0;
     for (int k = 0; k < ncomp; ++k) {
-        double S = 0.0, Sx = 0.0, Sy = 0.0, Sxx = 0.0, Syy = 0.0, Sxy = 0.0;
+        Moments M;
         unsigned np = 0, ns = 0;
         for (unsigned i = tid; i < A; i += INT) {
             const unsigned u = U.ld(i);
@@ -275,33 +262,22 @@ __device__ void deblend(DSmem& s, const Lab<LDS> L, const Lab<LDS> U, const Debl
             if (code != (unsigned)k + 1) continue;
             const unsigned dy = i / W, dx = i - dy * W;
             const double wt = (double)img[(size_t)dy * MW + dx] - bkg, fx = (double)dx, fy = (double)dy;
-            S += wt; Sx += wt * fx; Sy += wt * fy; Sxx += wt * (fx * fx); Syy += wt * (fy * fy); Sxy += wt * (fx * fy);
+            M.add(wt, fx, fy);
             ++np; ns += si == i;
             if (mask) mask[i] = (unsigned char)(k + 1);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            S += __shfl_down(S, o); Sx += __shfl_down(Sx, o); Sy += __shfl_down(Sy, o); Sxx += __shfl_down(Sxx, o);
-            Syy += __shfl_down(Syy, o); Sxy += __shfl_down(Sxy, o);
-            np += __shfl_down(np, o); ns += __shfl_down(ns, o);
-            if (k == 0) { ntot += __shfl_down(ntot, o); nun += __shfl_down(nun, o); }
-        }
-        const int b = k & 1;                                  // thread 0 reads buffer b while the waves fill the other one
-        if (lane == 0) {
-            s.red[b][0][w] = S; s.red[b][1][w] = Sx; s.red[b][2][w] = Sy; s.red[b][3][w] = Sxx; s.red[b][4][w] = Syy; s.red[b][5][w] = Sxy;
-            s.rc[b][0][w] = np; s.rc[b][1][w] = ns; s.rc[b][2][w] = ntot; s.rc[b][3][w] = nun;
-        }
+        unsigned ct = ntot, cu = nun;                         // complete after pass 0; the later passes reduce copies nobody reads
+        const auto red = reduction(red_sum(M.m), red_sum(np), red_sum(ns), red_sum(ct), red_sum(cu));
+        red.wave();
+        red.park(s.red[k & 1]);                               // thread 0 reads buffer k & 1 while the waves fill the other one
         __syncthreads();
         if (tid == 0) {
-            for (int j = 1; j < INW; ++j) {
-                S += s.red[b][0][j]; Sx += s.red[b][1][j]; Sy += s.red[b][2][j]; Sxx += s.red[b][3][j]; Syy += s.red[b][4][j]; Sxy += s.red[b][5][j];
-                np += s.rc[b][0][j]; ns += s.rc[b][1][j];
-                if (k == 0) { ntot += s.rc[b][2][j]; nun += s.rc[b][3][j]; }
-            }
+            red.total(s.red[k & 1]);
+            if (k == 0) { ntot = ct; nun = cu; }
             const unsigned kt = s.kidx[k], ky = kt / W, kx = kt - ky * W;
             double* c = comp + (size_t)k * DBL_COMP_FIELDS;
             c[0] = (double)np; c[1] = (double)s.kval[k]; c[2] = (double)(wn.x0 + (int)kx); c[3] = (double)(wn.y0 + (int)ky);
-            c[4] = S; c[5] = Sx; c[6] = Sy; c[7] = Sxx; c[8] = Syy; c[9] = Sxy;
+            M.store(c + 4);
             c[10] = s.kroot[k] == mainroot ? 1.0 : 0.0; c[11] = (double)ns;
         }
     }

@@ -13,15 +13,15 @@
 // the reduction scratch 34 KiB per workgroup: the 160 KiB of a CU would hold four); a larger one re-reads list and
 // image, which L2 serves from the second sweep on.
 // Registers: 28 float64 accumulators are 56 VGPRs per lane; with the six Jacobian entries, exp's temporaries and thread 0's 6 x 6
-// factor the build reports 180 VGPRs and no spill (the 96 bytes of scratch hold the job record, read once).  Of the 512 registers
+// factor the build reports 176 VGPRs and no spill (the 96 bytes of scratch hold the job record, read once).  Of the 512 registers
 // per lane of a SIMD that leaves two waves per SIMD, so two workgroups (68 KiB of LDS) are resident per CU.  Holding the kernel
 // to 128 VGPRs for four waves spills 25 registers and was not kept.
 // Every loop has a bound fixed before it starts:
 //   iteration   it = 1 .. max_iter (<= FIT_MAX_ITER = 256); every lambda escalation is one iteration, so there is no inner loop
 //   sweeps      over the npos list entries of the job, npos <= 2^24; at most max_iter + 1 sweeps per job
 //   reductions  6 shuffle steps and FIT_T / 64 = 4 waves;  Cholesky and the two triangular solves: 6 x 6, fully unrolled
-// Sums: float64 per lane over increasing list position (entry q belongs to thread q mod 256), __shfl_down tree per wave, the
-// four waves added in order by thread 0: fixed association, so two runs give the same bits.  No atomics.
+// Sums: float64 per lane over increasing list position (entry q belongs to thread q mod 256), then the block reduction of
+// cy_reduce.h, finished by thread 0.  No atomics.
 #include "cy_lm.h"                      // gauss_terms, stage_list, lm_iterate
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
@@ -29,16 +29,16 @@
 namespace cy {
 namespace {
 
-constexpr int FIT_T = 256, FIT_W = FIT_T / 64;
+constexpr int FIT_T = 256;
 
 struct FSmem {
     float val[FIT_LDS_MAX];
     unsigned idx[FIT_LDS_MAX];
-    double red[FIT_NSUM][FIT_W];
+    RedSlots<FIT_T, FIT_NSUM> red;      // sweep's
     double tot[FIT_NSUM];               // sums of the last sweep
     double cur[FIT_NSUM];               // sums at the accepted p
     double p[6], pt[6];                 // accepted and trial parameters
-    unsigned cnt[FIT_W];
+    RedSlots<FIT_T, 1> cnt;             // stage_list's
     LmCtl ctl;
 };
 
@@ -49,7 +49,7 @@ static_assert(hidx(0, 0) == 7 && hidx(5, 5) == FIT_NSUM - 1, "F, g (6), H upper 
 template <bool LDS>
 __device__ __forceinline__ void sweep(FSmem& s, const double* pp, const unsigned* __restrict__ list, const unsigned npos,
                                       const float* __restrict__ img, const size_t MW, const unsigned W, const unsigned A, const double bkg) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const double pA = pp[0], x0 = pp[1], y0 = pp[2], a = pp[3], b = pp[4], c = pp[5];
     double acc[FIT_NSUM];
 #pragma unroll
@@ -70,21 +70,14 @@ __device__ __forceinline__ void sweep(FSmem& s, const double* pp, const unsigned
             for (int jj = ii; jj < 6; ++jj) acc[hidx(ii, jj)] += J[ii] * J[jj];
         }
     }
-#pragma unroll
-    for (int k = 0; k < FIT_NSUM; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
-        if (lane == 0) s.red[k][w] = acc[k];
-    }
+    const auto red = reduction(red_sum(acc));
+    red.wave();
+    red.park(s.red);                                          // the slots of the sweep before: lm_iterate's barrier follows thread 0's read
     __syncthreads();
     if (tid == 0) {
+        red.total(s.red);
 #pragma unroll
-        for (int k = 0; k < FIT_NSUM; ++k) {
-            double t = acc[k];
-#pragma unroll
-            for (int j = 1; j < FIT_W; ++j) t += s.red[k][j];
-            s.tot[k] = t;
-        }
+        for (int k = 0; k < FIT_NSUM; ++k) s.tot[k] = acc[k];
     }
 }
 

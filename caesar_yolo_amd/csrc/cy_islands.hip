@@ -17,9 +17,9 @@
 // Every loop has a bound fixed before it starts: sweeps run over the A pixels of the window, a walk to the root follows strictly
 // decreasing labels (at most A steps), and unite() lowers the larger of its two roots with every retry (at most A retries).
 // Workspace labels are read and written with agent-scope atomics (they go to L2, never to a stale line of the vector cache).
-// Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
-// fixed association, so two runs give the same bits.  The atomics are integer minima / ors on labels only.
-#include "cy_label.h"                   // Lab, label_window: sweeps 1-4, shared with cy_deblend.hip; Win, window_of (cy_px.h)
+// Sums: float64 per lane over increasing pixel index, then the block reduction of cy_reduce.h, finished by thread 0.  The atomics
+// are integer minima / ors on labels only.
+#include "cy_label.h"                   // Lab, label_window: sweeps 1-4, and Moments, shared with cy_deblend.hip; Win, window_of (cy_px.h)
 
 #pragma clang fp contract(off)          // w * (dx * dx) is rounded before it is added, as the float64 definition does
 
@@ -29,15 +29,13 @@ namespace {
 struct ISmem {
     unsigned lab[ISL_LDS_MAX];
     LabRed lr;
-    double red[7][INW];
-    unsigned cnt[5][INW];
-    int box[4][INW];
+    RedSlots<INT, 15> red;
 };
 
 template <bool LDS>
 __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const Win wn, const double seed, const double merge,
                         const double bkg, unsigned char* __restrict__ mask, double* __restrict__ out) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t MW = (size_t)a.MW;
     const float* __restrict__ img = a.img + (size_t)wn.y0 * MW + (size_t)wn.x0;
     const unsigned W = wn.W, A = wn.A;
@@ -52,7 +50,8 @@ __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const W
 
     // ---- 5 sums (the peak pixel is a seed, so its component is in the island set)
     const unsigned mainroot = L.ld(pi) & ROOT;
-    double S = 0.0, Sx = 0.0, Sy = 0.0, Sxx = 0.0, Syy = 0.0, Sxy = 0.0, Sm = 0.0;
+    Moments M;
+    double Sm = 0.0;
     unsigned nisl = 0, npix = 0, nmain = 0, nborder = 0;
     int xmin = INT_MAX, xmax = -1, ymin = INT_MAX, ymax = -1;
     for (unsigned i = tid; i < A; i += INT) {
@@ -63,36 +62,23 @@ __device__ void islands(ISmem& s, const Lab<LDS> L, const IslandArgs& a, const W
         const unsigned dy = i / W, dx = i - dy * W;
         const double wt = (double)img[(size_t)dy * MW + dx] - bkg, fx = (double)dx, fy = (double)dy;
         const bool mn = r == mainroot;
-        S += wt; Sx += wt * fx; Sy += wt * fy; Sxx += wt * (fx * fx); Syy += wt * (fy * fy); Sxy += wt * (fx * fy);
+        M.add(wt, fx, fy);
         if (mn) { Sm += wt; ++nmain; }
         ++npix; nisl += r == i;
         nborder += dx == 0 || dy == 0 || dx == W - 1 || dy == wn.H - 1;
         xmin = min(xmin, (int)dx); xmax = max(xmax, (int)dx); ymin = min(ymin, (int)dy); ymax = max(ymax, (int)dy);
         if (mask) mask[i] = mn ? 2 : 1;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        S += __shfl_down(S, o); Sx += __shfl_down(Sx, o); Sy += __shfl_down(Sy, o); Sxx += __shfl_down(Sxx, o);
-        Syy += __shfl_down(Syy, o); Sxy += __shfl_down(Sxy, o); Sm += __shfl_down(Sm, o);
-        nisl += __shfl_down(nisl, o); npix += __shfl_down(npix, o); nmain += __shfl_down(nmain, o); nborder += __shfl_down(nborder, o);
-        xmin = min(xmin, __shfl_down(xmin, o)); xmax = max(xmax, __shfl_down(xmax, o));
-        ymin = min(ymin, __shfl_down(ymin, o)); ymax = max(ymax, __shfl_down(ymax, o));
-    }
-    if (lane == 0) {
-        s.red[0][w] = S; s.red[1][w] = Sx; s.red[2][w] = Sy; s.red[3][w] = Sxx; s.red[4][w] = Syy; s.red[5][w] = Sxy; s.red[6][w] = Sm;
-        s.cnt[1][w] = nisl; s.cnt[2][w] = npix; s.cnt[3][w] = nmain; s.cnt[4][w] = nborder;
-        s.box[0][w] = xmin; s.box[1][w] = xmax; s.box[2][w] = ymin; s.box[3][w] = ymax;
-    }
+    const auto red = reduction(red_sum(M.m), red_sum(Sm), red_sum(nisl), red_sum(npix), red_sum(nmain), red_sum(nborder),
+                               red_min(xmin), red_max(xmax), red_min(ymin), red_max(ymax));
+    red.wave();
+    red.park(s.red);
     __syncthreads();
     if (tid == 0) {
-        for (int j = 1; j < INW; ++j) {
-            S += s.red[0][j]; Sx += s.red[1][j]; Sy += s.red[2][j]; Sxx += s.red[3][j]; Syy += s.red[4][j]; Sxy += s.red[5][j]; Sm += s.red[6][j];
-            nisl += s.cnt[1][j]; npix += s.cnt[2][j]; nmain += s.cnt[3][j]; nborder += s.cnt[4][j];
-            xmin = min(xmin, s.box[0][j]); xmax = max(xmax, s.box[1][j]); ymin = min(ymin, s.box[2][j]); ymax = max(ymax, s.box[3][j]);
-        }
+        red.total(s.red);
         out[0] = 0.0; out[1] = (double)nseed; out[2] = (double)nisl; out[3] = (double)npix; out[4] = (double)nmain; out[5] = (double)nborder;
         out[6] = (double)(wn.x0 + xmin); out[7] = (double)(wn.x0 + xmax); out[8] = (double)(wn.y0 + ymin); out[9] = (double)(wn.y0 + ymax);
-        out[10] = S; out[11] = Sx; out[12] = Sy; out[13] = Sxx; out[14] = Syy; out[15] = Sxy; out[16] = Sm;
+        M.store(out + 10); out[16] = Sm;
         out[17] = 0.0; out[18] = 0.0; out[19] = 0.0;
     }
 }

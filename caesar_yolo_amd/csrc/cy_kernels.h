@@ -98,6 +98,7 @@ void debug_read_wg_life(unsigned long long* out, int n);        // entry, exit, 
 void debug_read_wg_stamps(unsigned long long* out, int n);     // raw per-workgroup phase records (n x 4), stamped builds   // developer diagnostics (CY_DBG=64)
 void debug_read_pre_stamps(unsigned long long* out8, bool reset);
 void debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, double* d_ref, int n);      // fast_div vs `/` (cy_preproc.hip)   // phases of pre_stats_kernel (cy_preproc.hip), stamped builds only
+void debug_reduce(const double* d_val, const float* d_key, int nrows, int len, unsigned long long* d_out);      // cy_reduce.h on its own (cy_measure.hip)
 hipError_t launch_lds_fill(unsigned pattern, hipStream_t s, int* bytes);      // test hook: `pattern` over all LDS of one workgroup per CU (cy_extra.hip)
 hipError_t launch_stem(Precision p, const StemArgs& a, hipStream_t s);
 hipError_t launch_stem_down(const StemDownArgs& a, hipStream_t s);

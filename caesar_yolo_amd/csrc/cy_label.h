@@ -9,18 +9,32 @@
 // Workspace labels are read and written with agent-scope atomics (they go to L2, never to a stale line of the vector cache).
 #pragma once
 #include "cy_px.h"                      // valid_px, Win, window_of
+#include "cy_reduce.h"                  // RedSlots, reduction
 #include <climits>
+
+#pragma clang fp contract(off)          // as in both files that include this one (Moments::add)
 
 namespace cy {
 namespace {
 
-constexpr int INT = 256, INW = INT / 64;
+constexpr int INT = 256;
 constexpr unsigned NOLAB = 0xFFFFFFFFu, SEEDED = 0x80000000u, ROOT = 0x7FFFFFFFu;
 static_assert(ISL_MAX_AREA < (long long)SEEDED, "bit 31 of a label is the seed flag");
 
-struct LabRed {                         // reduction scratch of label_window
-    unsigned cnt[INW];
-    float pv[INW]; unsigned pi[INW];
+using LabRed = RedSlots<INT, 3>;        // reduction scratch of label_window: the seed count and the peak pixel
+
+// The moments of the weights wt at window position (fx, fy), as islands and components carry them: S, Sx, Sy, Sxx, Syy, Sxy.  Every
+// product is rounded before it is added, and fx * fx before it meets wt, as the float64 definition does
+struct Moments {
+    double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    __device__ __forceinline__ void add(const double wt, const double fx, const double fy) {
+        m[0] += wt; m[1] += wt * fx; m[2] += wt * fy;
+        m[3] += wt * (fx * fx); m[4] += wt * (fy * fy); m[5] += wt * (fx * fy);
+    }
+    __device__ __forceinline__ void store(double* out) const {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out[k] = m[k];
+    }
 };
 
 // label accesses: LDS (workgroup scope) or this workgroup's slice of the global workspace (agent scope: served by L2)
@@ -53,7 +67,7 @@ template <bool LDS> struct Lab {
 template <bool LDS>
 __device__ __forceinline__ unsigned label_window(LabRed& s, const Lab<LDS> L, const float* __restrict__ img, const size_t MW, const bool c8,
                                                  const Win wn, const double seed, const double merge, float& pv, unsigned& pi) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const unsigned W = wn.W, A = wn.A;
 
     // ---- 1 init
@@ -70,20 +84,11 @@ __device__ __forceinline__ unsigned label_window(LabRed& s, const Lab<LDS> L, co
         const unsigned long long starts = __ballot(cand && !joins);
         if (i < A) L.st(i, cand ? i - lane + (63u - (unsigned)__clzll((long long)(starts & (~0ull >> (63 - lane))))) : NOLAB);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nseed += __shfl_down(nseed, o);
-        const float v2 = __shfl_down(pv, o); const unsigned p2 = __shfl_down(pi, o);
-        if (v2 > pv || (v2 == pv && p2 < pi)) { pv = v2; pi = p2; }
-    }
-    if (lane == 0) { s.cnt[w] = nseed; s.pv[w] = pv; s.pi[w] = pi; }
+    const auto red = reduction(red_sum(nseed), red_first_max(pv, pi, NOLAB));
+    red.wave();
+    red.park(s);
     __syncthreads();                                          // also: the labels of sweep 1 are in place
-    nseed = s.cnt[0]; pv = s.pv[0]; pi = s.pi[0];
-#pragma unroll
-    for (int j = 1; j < INW; ++j) {
-        nseed += s.cnt[j];
-        if (s.pv[j] > pv || (s.pv[j] == pv && s.pi[j] < pi)) { pv = s.pv[j]; pi = s.pi[j]; }
-    }
+    red.total(s);                                             // every thread
     if (nseed == 0) return 0;
 
     // ---- 2 link

@@ -11,6 +11,7 @@
 // reach the other threads through the two LDS words of LmCtl, read after a barrier (uniform).
 #pragma once
 #include "cy_px.h"
+#include "cy_reduce.h"                  // RedSlots, reduction
 #include <cfloat>
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
@@ -50,11 +51,12 @@ __device__ __forceinline__ unsigned list_pixel(const unsigned* __restrict__ list
 }
 
 // The valid pixels of the list, counted (and, LDS, {value, index} of every entry parked in val / idx).  Ends with a barrier after
-// which every thread holds the count: what the caller wrote to LDS before the call is visible to everyone after it
+// which every thread holds the count: what the caller wrote to LDS before the call is visible to everyone after it.  No barrier
+// follows the last read of cnt, so these slots are cnt's alone: a sweep that parked in them could overtake a slower wave's read
 template <int NT, bool LDS>
-__device__ __forceinline__ unsigned stage_list(float* val, unsigned* idx, unsigned* cnt, const unsigned* __restrict__ list, const unsigned npos,
+__device__ __forceinline__ unsigned stage_list(float* val, unsigned* idx, RedSlots<NT, 1>& cnt, const unsigned* __restrict__ list, const unsigned npos,
                                                const float* __restrict__ img, const size_t MW, const unsigned W, const unsigned A) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     unsigned np = 0;
     for (unsigned q = tid; q < npos; q += NT) {
         float fv;
@@ -62,13 +64,11 @@ __device__ __forceinline__ unsigned stage_list(float* val, unsigned* idx, unsign
         if (LDS) { idx[q] = i; val[q] = fv; }
         np += i != LM_BAD;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) np += __shfl_down(np, o);
-    if (lane == 0) cnt[w] = np;
+    const auto red = reduction(red_sum(np));
+    red.wave();
+    red.park(cnt);
     __syncthreads();
-    np = cnt[0];
-#pragma unroll
-    for (int k = 1; k < NT / 64; ++k) np += cnt[k];
+    red.total(cnt);                                           // every thread
     return np;
 }
 

@@ -8,9 +8,10 @@
 // is a few KiB and stays in the vector cache / L2), 64-bit pixel offsets throughout (the 32k mosaic is one 4 GiB allocation).
 // Medians are the exact radix selections of cy_select.h (pixels: 4 passes, deviations: 8 passes, one more for the upper middle
 // element of an even count when it is a different value); the ring hands its valid pixels to them.
-// Sums: float64 per lane over increasing pixel index, __shfl_down tree per wave, the four waves added in order by thread 0:
-// fixed association, so two runs give the same bits.  Nothing here is atomic outside LDS, and the LDS atomics are integer counts.
+// Sums: float64 per lane over increasing pixel index, then the block reduction of cy_reduce.h, finished by thread 0.  Nothing here
+// is atomic outside LDS, and the LDS atomics are integer counts.
 #include "cy_px.h"                      // valid_px
+#include "cy_reduce.h"                  // RedSlots, reduction
 #include "cy_select.h"                  // SelSmem, select_median
 #include <climits>
 
@@ -19,13 +20,11 @@
 namespace cy {
 namespace {
 
-constexpr int MNT = 256, MNW = MNT / 64, MUNROLL = 4;
+constexpr int MNT = 256, MUNROLL = 4;
 
 struct MSmem {
     SelSmem<MNT> sel;
-    double red[4][MNW];
-    unsigned cnt[MNW];
-    float pv[MNW]; long long pp[MNW];
+    RedSlots<MNT, 7> red;
 };
 
 // The ring = grown window minus box window, as four rectangles walked one after the other with consecutive lanes on consecutive
@@ -56,7 +55,7 @@ __device__ __forceinline__ void ring_for_each(const float* __restrict__ img, siz
 
 __global__ __launch_bounds__(MNT) void measure_kernel(const MeasureArgs a) {
     __shared__ MSmem s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int* wn = a.win + (size_t)b * 8;
     // the host's windows are already inside the image; clamped again so that no index can leave it whatever arrives here
     const int bx0 = max(wn[0], 0), bx1 = min(wn[1], a.MW - 1), by0 = max(wn[2], 0), by1 = min(wn[3], a.MH - 1);
@@ -102,21 +101,13 @@ __global__ __launch_bounds__(MNT) void measure_kernel(const MeasureArgs a) {
             if (d > 0.0) { sw += d; swx += d * (double)ix[u]; swy += d * (double)iy[u]; }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o); sw += __shfl_down(sw, o); swx += __shfl_down(swx, o); swy += __shfl_down(swy, o);
-        npix += __shfl_down(npix, o);
-        const float v2 = __shfl_down(pv, o); const long long p2 = __shfl_down(pp, o);
-        if (v2 > pv || (v2 == pv && p2 < pp)) { pv = v2; pp = p2; }
-    }
+    const auto red = reduction(red_sum(sum), red_sum(sw), red_sum(swx), red_sum(swy), red_sum(npix), red_first_max(pv, pp, (long long)LLONG_MAX));
+    red.wave();
     __syncthreads();
-    if (lane == 0) { s.red[0][w] = sum; s.red[1][w] = sw; s.red[2][w] = swx; s.red[3][w] = swy; s.cnt[w] = npix; s.pv[w] = pv; s.pp[w] = pp; }
+    red.park(s.red);
     __syncthreads();
     if (tid == 0) {
-        for (int j = 1; j < MNW; ++j) {
-            sum += s.red[0][j]; sw += s.red[1][j]; swx += s.red[2][j]; swy += s.red[3][j]; npix += s.cnt[j];
-            if (s.pv[j] > pv || (s.pv[j] == pv && s.pp[j] < pp)) { pv = s.pv[j]; pp = s.pp[j]; }
-        }
+        red.total(s.red);
         out[0] = (double)npix; out[1] = (double)nring; out[2] = bkg; out[3] = rms;
         if (npix) {
             out[4] = (double)pv; out[5] = (double)(pp % a.MW); out[6] = (double)(pp / a.MW);
@@ -128,7 +119,49 @@ __global__ __launch_bounds__(MNT) void measure_kernel(const MeasureArgs a) {
     }
 }
 
+// cy_debug_reduce: cy_reduce.h on its own, one workgroup per row of `len` entries, thread t on entries t, t + 256, ..  Per row and
+// finishing style (0: thread 0 after the barrier, 1: every thread, read back from the last one) eight 64-bit words: the float64 sum
+// of val (bits), the entry count, the first maximum of the valid keys (float bits, index; none: -inf, 0xFFFFFFFF), the smallest
+// and the largest index of a valid key (int; none: INT_MAX, -1), the first maximum again with a long long index (none:
+// LLONG_MAX), and the smallest such index as unsigned long long (none: all ones)
+__global__ __launch_bounds__(MNT) void reduce_probe_kernel(const double* __restrict__ val, const float* __restrict__ key, const int len,
+                                                           unsigned long long* __restrict__ out) {
+    __shared__ RedSlots<MNT, 9> s;
+    const int tid = threadIdx.x;
+    const size_t row = (size_t)blockIdx.x * (size_t)len;
+    double sum = 0.0;
+    unsigned n = 0, pi = 0xFFFFFFFFu;
+    float pv = -INFINITY, qv = -INFINITY;
+    int imin = INT_MAX, imax = -1;
+    long long qi = LLONG_MAX;
+    unsigned long long umin = ~0ull;
+    for (int i = tid; i < len; i += MNT) {
+        sum += val[row + i]; ++n;
+        const float k = key[row + i];
+        if (!valid_px(k)) continue;
+        if (k > pv) { pv = k; pi = (unsigned)i; qv = k; qi = i; }                   // increasing index per lane: the first stays
+        imin = min(imin, i); imax = max(imax, i);
+        if ((unsigned long long)i < umin) umin = (unsigned long long)i;
+    }
+    const auto red = reduction(red_sum(sum), red_sum(n), red_first_max(pv, pi, 0xFFFFFFFFu), red_min(imin), red_max(imax),
+                               red_first_max(qv, qi, (long long)LLONG_MAX), red_min(umin));
+    red.wave();
+    red.park(s);
+    __syncthreads();
+    for (int style = 0; style < 2; ++style) {                // thread 0 overwrites only its own registers in between
+        if (tid != (style ? MNT - 1 : 0)) continue;
+        red.total(s);
+        unsigned long long* o = out + ((size_t)blockIdx.x * 2 + style) * 8;
+        o[0] = (unsigned long long)__double_as_longlong(sum); o[1] = n; o[2] = __float_as_uint(pv); o[3] = pi;
+        o[4] = (unsigned long long)(long long)imin; o[5] = (unsigned long long)(long long)imax; o[6] = (unsigned long long)qi; o[7] = umin;
+    }
+}
+
 }  // namespace
+
+void debug_reduce(const double* d_val, const float* d_key, int nrows, int len, unsigned long long* d_out) {
+    hipLaunchKernelGGL(reduce_probe_kernel, dim3(nrows), dim3(MNT), 0, 0, d_val, d_key, len, d_out);
+}
 
 hipError_t launch_measure(const MeasureArgs& a, hipStream_t s) {
     if (a.n < 1 || a.MH < 1 || a.MW < 1) return hipErrorInvalidValue;

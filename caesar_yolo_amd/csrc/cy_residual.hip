@@ -15,14 +15,15 @@
 // are 16-byte aligned the four pixels move as one 16-byte access (a quad is then inside the row or outside it); otherwise pixel
 // by pixel.  Partial edge tiles: a pixel at or beyond MW / MH is neither read nor written.
 // residual_stats_kernel: one workgroup of 256 threads per source, modelled on the sums of cy_islands.hip: float64 per lane over
-// increasing window index (pixel i on thread i mod 256), __shfl_down tree per wave, the four waves added in order by thread 0: fixed
-// association, so two runs give the same bits.  The largest |r| travels with its window index; the smaller index wins a tie.
+// increasing window index (pixel i on thread i mod 256), then the block reduction of cy_reduce.h, finished by thread 0.  The largest
+// |r| travels with its window index as a first maximum: the smaller index wins a tie.
 // Every loop has a bound fixed before it starts:
 //   tiles       tile = blockIdx.x, += gridDim.x, below ntx * nty (< 2^27 for an image below 2^31 pixels)
 //   chunks      over the tile's list entries, tile_off[t] .. tile_off[t + 1] (the whole table holds at most 2^27), 64 at a time
 //   components  at most 64 per chunk, four pixels each
 //   statistics  over the A <= 2^24 pixels of the window, 256 at a time; 6 shuffle steps and 4 waves
 #include "cy_px.h"                      // valid_px, Win, window_of
+#include "cy_reduce.h"                  // RedSlots, reduction
 #include <cstdint>
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
@@ -31,7 +32,7 @@ namespace cy {
 namespace {
 
 constexpr int RND_T = 256, RND_GRID_MAX = 1 << 20;
-constexpr int RES_T = 256, RES_W = RES_T / 64;
+constexpr int RES_T = 256;
 static_assert(RND_T == (RND_TILE / 4) * RND_TILE, "one thread per four pixels of a tile row");
 static_assert(RND_CHUNK <= RND_T, "thread j loads entry j of a chunk");
 
@@ -111,16 +112,9 @@ __global__ __launch_bounds__(RND_T) void render_kernel(const RenderArgs a) {
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) render_tile<VEC>(s, a, tile);
 }
 
-struct StSmem {
-    double red[5][RES_W];
-    double mx[RES_W];
-    unsigned mi[RES_W];
-    unsigned cnt[2][RES_W];
-};
-
 __global__ __launch_bounds__(RES_T) void residual_stats_kernel(const ResidualArgs a) {
-    __shared__ StSmem s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ RedSlots<RES_T, 9> s;
+    const int b = blockIdx.x, tid = threadIdx.x;
     Win wn;
     const long long area = window_of(a.win + (size_t)b * 4, a.MW, a.MH, wn);      // held inside the image (cy_px.h)
     double* out = a.out + (size_t)b * RES_FIELDS;
@@ -149,24 +143,13 @@ __global__ __launch_bounds__(RES_T) void residual_stats_kernel(const ResidualArg
             if (ar > best) { best = ar; bi = i; }             // i increases: the first occurrence stays
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Sw += __shfl_down(Sw, o); Qw += __shfl_down(Qw, o); Si += __shfl_down(Si, o); Qi += __shfl_down(Qi, o); Mi += __shfl_down(Mi, o);
-        nw += __shfl_down(nw, o); ni += __shfl_down(ni, o);
-        const double ob = __shfl_down(best, o); const unsigned oi = __shfl_down(bi, o);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) {
-        s.red[0][w] = Sw; s.red[1][w] = Qw; s.red[2][w] = Si; s.red[3][w] = Qi; s.red[4][w] = Mi;
-        s.mx[w] = best; s.mi[w] = bi; s.cnt[0][w] = nw; s.cnt[1][w] = ni;
-    }
+    const auto red = reduction(red_sum(Sw), red_sum(Qw), red_sum(Si), red_sum(Qi), red_sum(Mi), red_sum(nw), red_sum(ni),
+                               red_first_max(best, bi, 0xFFFFFFFFu));
+    red.wave();
+    red.park(s);
     __syncthreads();
     if (tid == 0) {
-        for (int j = 1; j < RES_W; ++j) {
-            Sw += s.red[0][j]; Qw += s.red[1][j]; Si += s.red[2][j]; Qi += s.red[3][j]; Mi += s.red[4][j];
-            nw += s.cnt[0][j]; ni += s.cnt[1][j];
-            if (s.mx[j] > best || (s.mx[j] == best && s.mi[j] < bi)) { best = s.mx[j]; bi = s.mi[j]; }
-        }
+        red.total(s);
         const bool has = ni > 0 && bi < A;
         out[0] = 0.0; out[1] = (double)nw; out[2] = (double)ni; out[3] = Sw; out[4] = Qw; out[5] = Si; out[6] = Qi;
         out[7] = has ? best : 0.0;

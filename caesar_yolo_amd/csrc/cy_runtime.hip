@@ -1208,6 +1208,12 @@ int cy_debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, doubl
     return hipGetLastError() == hipSuccess ? CY_OK : CY_ERR_HIP;
 }
 
+int cy_debug_reduce(const double* d_val, const float* d_key, int nrows, int len, unsigned long long* d_out) {
+    if (!d_out || nrows < 1 || len < 0 || (len > 0 && (!d_val || !d_key))) return CY_ERR_ARG;
+    debug_reduce(d_val, d_key, nrows, len, d_out);
+    return hipGetLastError() == hipSuccess ? CY_OK : CY_ERR_HIP;
+}
+
 // asynchronous on `stream`, like cy_forward: the point is what the kernels queued behind it find in LDS
 int cy_debug_lds_fill(cy_ctx* c, unsigned pattern32, void* stream) {
     if (!c) return CY_ERR_ARG;

@@ -7,7 +7,7 @@
 // Counts and single rounded operations only: nothing depends on the order in which the walk visits the members.  The LDS atomics
 // are integer counts.  A workgroup of NT >= 256 threads; the first 256 own one bin each.
 #pragma once
-#include "cy_kernels.h"
+#include "cy_reduce.h"                  // RedSlots, reduction: the minimum at the end
 
 #pragma clang fp contract(off)          // as in every file that includes this one
 
@@ -33,7 +33,7 @@ template <int NT> struct SelSmem {
     unsigned hist[256];
     unsigned wsum[4];
     unsigned sel[4];                     // digit, rank inside the bin, elements below the bin, elements in the bin
-    unsigned long long umin[NT / 64];
+    RedSlots<NT, 1> umin;
 };
 
 // Exact median of the keys of the members; n = their count (0: returns 0).  n == stop_at: returns 0 after the counting pass (the
@@ -82,13 +82,11 @@ __device__ double select_median(SelSmem<NT>& s, Walk walk, const double centre, 
     if ((n & 1u) || below + eq > n / 2) return a;           // odd count, or the upper middle element has the same value
     unsigned long long m = ~0ull;                           // smallest key above `prefix`
     walk([&](float v) { const unsigned long long key = sel_key<MODE>(v, centre); if (key > prefix && key < m) m = key; });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_down(m, o); m = t < m ? t : m; }
-    if (lane == 0) s.umin[w] = m;
+    const auto red = reduction(red_min(m));
+    red.wave();
+    red.park(s.umin);
     __syncthreads();
-    m = s.umin[0];
-#pragma unroll
-    for (int j = 1; j < NT / 64; ++j) m = s.umin[j] < m ? s.umin[j] : m;
+    red.total(s.umin);                                      // every thread
     return (a + key_value<MODE>(m)) / 2.0;
 }
 

@@ -48,7 +48,7 @@ EXPORTS = [
     "cy_weight_passes", "cy_class_name", "cy_plan_num_convs", "cy_plan_conv_desc", "cy_letterbox_geometry", "cy_num_anchors",
     "cy_pred_elems", "cy_profile_enable", "cy_profile_summary", "cy_profile_summary_lane", "cy_profile_layers", "cy_profile_layer_variant", "cy_mosaic_prepare", "cy_letterbox_pack", "cy_preproc", "cy_preproc_planes", "cy_preproc_params", "cy_forward", "cy_debug_read_conv",
     "cy_debug_stop_after", "cy_debug_ops_done", "cy_debug_read_tensor", "cy_debug_sparse_box",
-    "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_lds_fill", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_conv_slices", "cy_conv_variant_name", "cy_bottleneck64", "cy_dwconv3x3",
+    "cy_decode_nms", "cy_debug_stamps", "cy_debug_fastdiv", "cy_debug_reduce", "cy_debug_lds_fill", "cy_debug_cand_counts", "cy_iou_merge", "cy_detect_tiles", "cy_detect_flush", "cy_detect_fence", "cy_compact_records", "cy_compact_records_ctx", "cy_detect_counters", "cy_conv_bn_silu", "cy_conv_slices", "cy_conv_variant_name", "cy_bottleneck64", "cy_dwconv3x3",
     "cy_attention", "cy_maxpool5", "cy_make_tile_records",
     "cy_merge_edge_sources", "cy_augment_geometry", "cy_enable_augment", "cy_letterbox_pack_f32", "cy_augment_pack",
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
@@ -166,6 +166,7 @@ def load():
         "cy_debug_lds_fill": (C.c_int, [vp, C.c_uint, vp]),
         "cy_debug_stamps": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
         "cy_debug_fastdiv": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "cy_debug_reduce": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "cy_iou_merge": (C.c_int, [vp, vp, vp, C.c_int, C.c_float, C.c_double, C.c_double, vp, vp, vp, vp]),
         "cy_detect_tiles": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(cy_preproc_cfg), C.c_float, C.c_float, C.c_double, C.c_double,

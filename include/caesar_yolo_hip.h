@@ -159,6 +159,14 @@ int cy_debug_stamps(unsigned long long* out8, int reset);
 /* developer diagnostics: the pack kernel's quotient by a per-tile constant (d_fast) beside the float64 division (d_ref), element-wise on
  * device arrays of n doubles: must agree bit for bit (tests/test_gpu_preproc.py) */
 int cy_debug_fastdiv(const double* d_a, const double* d_b, double* d_fast, double* d_ref, int n);
+/* developer diagnostics: the block reduction of the measurement kernels (csrc/cy_reduce.h) on its own.  d_val (float64) and d_key
+ * (float32) hold nrows rows of len entries, len >= 0; one workgroup of 256 threads per row, thread t on entries t, t + 256, ..  d_out
+ * [nrows][2][8] 64-bit words, per finishing style (0: thread 0, 1: every thread, as the last thread sees it): bits of the float64 sum
+ * of d_val, entry count, first maximum of the valid keys (non-zero and finite): float bits and index (none: -inf, 0xFFFFFFFF),
+ * smallest and largest index of a valid key (none: INT_MAX, -1, sign-extended), the first maximum's index again as a 64-bit
+ * reduction (none: LLONG_MAX) and the smallest valid index as an unsigned one (none: all ones).  Launched on the null stream, not
+ * waited for.  tests/test_gpu_reduce.py compares every word with tests/reduce_ref.py */
+int cy_debug_reduce(const double* d_val, const float* d_key, int nrows, int len, unsigned long long* d_out);
 /* test hook (never called on the hot path): sets what the kernels queued behind it on `stream` inherit in LDS.  One kernel, one
  * workgroup per CU, each with the largest dynamic LDS the device grants a workgroup (queried, not assumed), writes pattern32 over
  * all of it with plain vector LDS stores.  Returns that size in bytes (> 0), or a negative error code; it does not wait for the

@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from reduce_ref import tree_sum      # the kernel's association (caesar_yolo_amd/csrc/cy_reduce.h)
+
 RINGS_MAX, RADIUS_MAX, HEAD, RING_FIELDS, JOBS_MAX = 8, 256, 8, 4, 1 << 20
 FIELDS = HEAD + RING_FIELDS * RINGS_MAX
 T, LANES = 256, 64
@@ -47,25 +49,6 @@ def median_rule(values):
         return 0.0
     a = v[(n - 1) // 2]
     return a if n % 2 else (a + v[n // 2]) / 2.0
-
-
-def tree_sum(t):
-    """Sums of the rows of t [k, n] in the kernel's association."""
-    k, n = t.shape
-    rows = max(-(-n // T), 1)
-    x = np.zeros((k, rows * T), np.float64)
-    x[:, :n] = t
-    x = x.reshape(k, rows, T)
-    acc = np.zeros((k, T), np.float64)
-    for r in range(rows):
-        acc = acc + x[:, r]
-    acc = acc.reshape(k, T // LANES, LANES)
-    for o in (32, 16, 8, 4, 2, 1):
-        acc[:, :, :o] = acc[:, :, :o] + acc[:, :, o:2 * o]
-    out = acc[:, 0, 0]
-    for w in range(1, T // LANES):
-        out = out + acc[:, w, 0]
-    return out
 
 
 def _head(row, st, x0, x1, y0, y1, clipped):

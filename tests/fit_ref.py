@@ -17,6 +17,7 @@ import math
 import numpy as np
 
 from caesar_yolo_amd.measure import box_window
+from reduce_ref import tree_sum      # the kernel's association (caesar_yolo_amd/csrc/cy_reduce.h)
 
 FIELDS = ("status", "niter", "npix", "F", "lambda", "A", "x0", "y0", "a", "b", "c") + tuple(
     "H%d%d" % (i, j) for i in range(6) for j in range(i, 6))
@@ -26,22 +27,6 @@ VARIANTS = (("tree", None), ("np", None), ("fsum", None), ("np", 12345))
 MEASURED = 2.13e-7      # measured 2.121e-7, on the random scene (the drawn jobs compared with TOL stay below 1e-8)
 TOL = 16 * MEASURED
 IU = [(i, j) for i in range(6) for j in range(i, 6)]
-
-
-def tree_sum(t):
-    """Sums of the rows of t [k, n] in the kernel's association."""
-    k, n = t.shape
-    rows = max(-(-n // 256), 1)
-    x = np.zeros((k, rows * 256), np.float64)
-    x[:, :n] = t
-    x = x.reshape(k, rows, 256)
-    acc = np.zeros((k, 256), np.float64)
-    for r in range(rows):
-        acc = acc + x[:, r]
-    acc = acc.reshape(k, 4, 64)
-    for o in (32, 16, 8, 4, 2, 1):
-        acc[:, :, :o] = acc[:, :, :o] + acc[:, :, o:2 * o]
-    return ((acc[:, 0, 0] + acc[:, 1, 0]) + acc[:, 2, 0]) + acc[:, 3, 0]
 
 
 def admissible(p):

@@ -5,7 +5,8 @@
 //   sweep    F = sum r^2, g = J^T r, H = J^T J (upper triangle) at one p over the job's pixels: FIT_NSUM = 28 float64 sums
 //   step     thread 0: 6 x 6 Cholesky of H + lambda diag(H), d, `small`, admissibility of p + d; everyone: sweep at the trial;
 //            thread 0: accept / reject, lambda, convergence: lm_iterate of cy_lm.h, which states the rule and owns the loop
-// The Gaussian and its Jacobian (gauss_terms) and the staging of the list (list_pixel, stage_list) are in cy_lm.h as well.
+// The Gaussian and its Jacobian (gauss_terms), the staging of the list (list_pixel, stage_list), the place of H in the sums (hidx)
+// and the 6 x 6 solve (lm_solve) are in cy_lm.h as well: the fit of a peak at a position (cy_peakfit.hip) uses them too.
 // One workgroup of 256 threads owns one job of the job table from start to finish; no workgroup reads what another one wrote.
 // The job's pixels arrive as a list of window indices i = dy * W + dx in increasing order, built by the runtime from the mask: the
 // kernel never searches a window.  A list entry whose pixel is not valid (0 or non-finite) keeps its list position and contributes
@@ -22,7 +23,7 @@
 //   reductions  6 shuffle steps and FIT_T / 64 = 4 waves;  Cholesky and the two triangular solves: 6 x 6, fully unrolled
 // Sums: float64 per lane over increasing list position (entry q belongs to thread q mod 256), then the block reduction of
 // cy_reduce.h, finished by thread 0.  No atomics.
-#include "cy_lm.h"                      // gauss_terms, stage_list, lm_iterate
+#include "cy_lm.h"                      // gauss_terms, stage_list, hidx, lm_solve, lm_iterate
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
 
@@ -41,9 +42,6 @@ struct FSmem {
     RedSlots<FIT_T, 1> cnt;             // stage_list's
     LmCtl ctl;
 };
-
-__host__ __device__ constexpr int hidx(int i, int j) { return 7 + i * 6 - i * (i - 1) / 2 + (j - i); }   // H(i, j), i <= j, in the 28 sums
-static_assert(hidx(0, 0) == 7 && hidx(5, 5) == FIT_NSUM - 1, "F, g (6), H upper triangle row-major (21)");
 
 // F, g, H at pp (LDS, uniform) over the job's list; the totals land in s.tot (valid for thread 0 after the barrier inside)
 template <bool LDS>
@@ -79,43 +77,6 @@ __device__ __forceinline__ void sweep(FSmem& s, const double* pp, const unsigned
 #pragma unroll
         for (int k = 0; k < FIT_NSUM; ++k) s.tot[k] = acc[k];
     }
-}
-
-// thread 0: d of (H + lam diag(H)) d = g by Cholesky (row by row, every inner sum subtracted term by term in increasing k); false
-// on a pivot that is not positive and finite
-__device__ __forceinline__ bool lm_solve(const double* cur, const double lam, double* d) {
-    double L[6][6], z[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const double hjj = cur[hidx(j, j)];
-        double t = hjj + lam * hjj;
-#pragma unroll
-        for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k];
-        if (!(t > 0.0) || !fin(t)) return false;
-        L[j][j] = sqrt(t);
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double q = cur[hidx(j, i)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) q -= L[i][k] * L[j][k];
-            L[i][j] = q / L[j][j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double q = cur[1 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) q -= L[i][k] * z[k];
-        z[i] = q / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double q = z[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) q -= L[k][i] * d[k];
-        d[i] = q / L[i][i];
-    }
-    return true;
 }
 
 template <bool LDS>

@@ -382,6 +382,18 @@ struct ApertureArgs {
 };
 hipError_t launch_apertures(const ApertureArgs& a, hipStream_t s);
 
+// ---- Gaussian fits at given positions (cy_peakfit.hip) ------------------------------------------------
+// PFIT_*, PeakFitJob: cy_measure_jobs.h; the jobs: plan_peak_fits (cy_measure_plan.h)
+constexpr int PFIT_LDS_MAX = 8192;             // largest window (pixels) whose member values live in LDS: 32 KiB per workgroup (R <= 44)
+struct PeakFitArgs {
+    const float* map; int MH, MW;   // MH * MW < 2^31
+    const PeakFitJob* jobs; int n;  // the whole job table: a neighbour is named by its index in it
+    const int* run; int nrun;       // the jobs that are fitted, one workgroup each: 1 <= nrun <= n <= PFIT_JOBS_MAX
+    int max_iter;                   // 1 .. FIT_MAX_ITER
+    double* out;                    // [nrun][PFIT_FIELDS]: workgroup t writes every field of row t
+};
+hipError_t launch_peak_fits(const PeakFitArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

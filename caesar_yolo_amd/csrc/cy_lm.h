@@ -1,5 +1,6 @@
-// What the component fit (cy_fit.hip) and the joint fit of a blend (cy_blend.hip) share: the elliptical Gaussian and its Jacobian,
-// the staging of a job's pixel list, and the Levenberg-Marquardt decision loop.  The rule of that loop is part of what a fitted
+// What the component fit (cy_fit.hip), the joint fit of a blend (cy_blend.hip) and the fit of a peak at a position (cy_peakfit.hip)
+// share: the elliptical Gaussian and its Jacobian, the staging of a job's pixel list, the 6 x 6 solve of the single-Gaussian fits
+// and the Levenberg-Marquardt decision loop.  The rule of that loop is part of what a fitted
 // number means and stands here once:
 //   start     lambda = 1e-3, status 2, niter = max_iter
 //   step      thread 0 solves (H + lambda diag(H)) d = g; `small`: every |d_k| <= 1e-10 (|p_k| + 1e-6); the trial is p + d
@@ -80,6 +81,46 @@ __device__ __forceinline__ bool lm_trial(const int P, const double* p, const dou
         pt[k] = p[k] + d[k];
     }
     return small;
+}
+
+__host__ __device__ constexpr int hidx(int i, int j) { return 7 + i * 6 - i * (i - 1) / 2 + (j - i); }   // H(i, j), i <= j, in the 28 sums
+static_assert(hidx(0, 0) == 7 && hidx(5, 5) == FIT_NSUM - 1, "F, g (6), H upper triangle row-major (21)");
+
+// thread 0: d of (H + lam diag(H)) d = g by Cholesky (row by row, every inner sum subtracted term by term in increasing k); false
+// on a pivot that is not positive and finite
+__device__ __forceinline__ bool lm_solve(const double* cur, const double lam, double* d) {
+    double L[6][6], z[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const double hjj = cur[hidx(j, j)];
+        double t = hjj + lam * hjj;
+#pragma unroll
+        for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k];
+        if (!(t > 0.0) || !fin(t)) return false;
+        L[j][j] = sqrt(t);
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double q = cur[hidx(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) q -= L[i][k] * L[j][k];
+            L[i][j] = q / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double q = cur[1 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) q -= L[i][k] * z[k];
+        z[i] = q / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double q = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) q -= L[k][i] * d[k];
+        d[i] = q / L[i][i];
+    }
+    return true;
 }
 
 // The loop of the header comment, run by the whole workgroup after the sums at the start are in place and ctl is {ACT_NONE, 0}.

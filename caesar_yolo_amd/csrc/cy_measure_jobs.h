@@ -1,4 +1,5 @@
-// Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip) and the
+// Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip, cy_aperture.hip,
+// cy_peakfit.hip) and the
 // host-side planner that fills them (cy_measure_plan.cpp).  No HIP include: the planner also builds as plain C++.
 #pragma once
 
@@ -34,6 +35,11 @@ constexpr int APER_HEAD = 8;                   // CY_APER_HEAD
 constexpr int APER_RING_FIELDS = 4;            // CY_APER_RING_FIELDS: npix sum sumsq svar
 constexpr int APER_FIELDS = APER_HEAD + APER_RING_FIELDS * APER_RINGS_MAX;     // CY_APER_FIELDS
 constexpr int APER_JOBS_MAX = 1 << 20;         // CY_APER_JOBS_MAX: one workgroup per job, the grid in x only
+constexpr int PFIT_JOB_FIELDS = 11;            // CY_PFIT_JOB_FIELDS: cx cy R bkg sign A x0 y0 a b c
+constexpr int PFIT_FIELDS = 40;                // CY_PFIT_FIELDS
+constexpr int PFIT_RADIUS_MAX = 256;           // CY_PFIT_RADIUS_MAX: largest disc radius in pixels; a window has at most 513 x 513 pixels
+constexpr int PFIT_NEIGH_MAX = 8;              // CY_PFIT_NEIGH_MAX: neighbours a job shares its disc with
+constexpr int PFIT_JOBS_MAX = 1 << 20;         // CY_PFIT_JOBS_MAX: one workgroup per fitted job, the grid in x only
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list
@@ -63,6 +69,18 @@ struct AperJob {
     int x0, x1, y0, y1;             // the window, inclusive, inside the image; {0, -1, 0, -1} when not measured
     int status;                     // 0 measured, 1 unit or outer radius out of range, 2 centre not finite or no pixel of the image in reach
     int clipped;                    // 1: the unclipped window leaves the image
+};
+
+struct PeakFitJob {
+    double cx, cy;                  // centre in image pixels, as given
+    double r2;                      // R * R
+    double bkg, sign;               // y = sign * (v - bkg); sign is +1 or -1
+    double p0[6];                   // start {A, x0, y0, a, b, c}, x0 / y0 relative to the window's first pixel
+    int x0, x1, y0, y1;             // the window, inclusive, inside the image; {0, -1, 0, -1} when not fitted
+    int status;                     // 0 fitted, 1 R, sign or bkg out of range, 5 centre not finite or no pixel of the image in reach
+    int clipped;                    // 1: the unclipped window leaves the image
+    int nneigh, crowded;            // kept neighbours; 1: there were more than PFIT_NEIGH_MAX
+    int neigh[PFIT_NEIGH_MAX];      // their job indices in (squared distance, index) order; -1 beyond nneigh
 };
 
 }  // namespace cy

@@ -346,6 +346,96 @@ const char* plan_apertures(const double* jobs, int n, const double* factors, int
     return nullptr;
 }
 
+const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakFitPlan& p) {
+#pragma clang fp contract(off)          // R*R and dx*dx + dy*dy: every product is rounded before it is used, whatever the build's default
+    p = PeakFitPlan();
+    if (MH <= 0 || MW <= 0) return "MH, MW > 0 required";
+    if ((long long)MH * MW >= (1LL << 31)) return "image of 2^31 pixels or more";
+    if (n < 0 || n > PFIT_JOBS_MAX) return "n outside 0 .. CY_PFIT_JOBS_MAX";
+    if (max_iter < 1 || max_iter > 256) return "max_iter outside 1 .. 256";
+    if (n > 0 && !(have_map && jobs && have_out)) return "null argument";
+    // one side of a window, as plan_apertures decides it
+    auto side = [](double c, double r, int N, int* lo, int* hi, int* clipped) {
+        const double l = std::ceil(c - r), u = std::floor(c + r);
+        if (u < 0.0 || l > (double)(N - 1) || l > u) return false;
+        if (l < 0.0 || u > (double)(N - 1)) *clipped = 1;
+        *lo = l > 0.0 ? (int)l : 0;
+        *hi = u < (double)(N - 1) ? (int)u : N - 1;
+        return true;
+    };
+    p.jobs.resize((size_t)n);
+    std::vector<double> lim((size_t)n, 0.0);                  // 2 R of the fitted jobs
+    for (int i = 0; i < n; ++i) {
+        const double* q = jobs + (size_t)i * PFIT_JOB_FIELDS;
+        PeakFitJob& j = p.jobs[(size_t)i];
+        j = PeakFitJob();
+        j.cx = q[0]; j.cy = q[1]; j.bkg = q[3]; j.sign = q[4];
+        j.x0 = j.y0 = 0; j.x1 = j.y1 = -1;
+        for (int k = 0; k < PFIT_NEIGH_MAX; ++k) j.neigh[k] = -1;
+        const double R = q[2];
+        if (!std::isfinite(R) || !(R > 0.0) || R > (double)PFIT_RADIUS_MAX || !(q[4] == 1.0 || q[4] == -1.0) || !std::isfinite(q[3])) { j.status = 1; continue; }
+        int clipped = 0;
+        if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !side(q[0], R, MW, &j.x0, &j.x1, &clipped) || !side(q[1], R, MH, &j.y0, &j.y1, &clipped)) {
+            j.x0 = j.y0 = 0; j.x1 = j.y1 = -1;
+            j.status = 5;
+            continue;
+        }
+        j.clipped = clipped;
+        j.r2 = R * R;
+        for (int t = 0; t < 6; ++t) j.p0[t] = q[5 + t];
+        j.p0[1] = q[6] - (double)j.x0; j.p0[2] = q[7] - (double)j.y0;
+        lim[(size_t)i] = 2.0 * R;
+        p.run.push_back(i);
+    }
+    // neighbours: the fitted jobs sorted by column; job e looks at the stretch whose |cx_f - cx_e| (as the test below rounds it) is
+    // below 2 R_e, which holds every f with D2 < 4 R_e^2 because dx*dx <= D2 and rounding is monotonic
+    std::vector<int> by_x(p.run);
+    std::sort(by_x.begin(), by_x.end(), [&](int a, int b) { return p.jobs[(size_t)a].cx < p.jobs[(size_t)b].cx || (p.jobs[(size_t)a].cx == p.jobs[(size_t)b].cx && a < b); });
+    const size_t m = by_x.size();
+    std::vector<std::pair<double, int>> cand;
+    for (size_t s = 0; s < m; ++s) {
+        const int e = by_x[s];
+        PeakFitJob& j = p.jobs[(size_t)e];
+        const double band = lim[(size_t)e], limit = 4.0 * j.r2;
+        // the band's left end by bisection on the sorted columns (it does not move monotonically when the radii differ)
+        size_t lo = 0, hi = s;
+        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (j.cx - p.jobs[(size_t)by_x[mid]].cx < band) hi = mid; else lo = mid + 1; }
+        cand.clear();
+        for (size_t t = lo; t < m; ++t) {
+            const int f = by_x[t];
+            if (f == e) continue;
+            const PeakFitJob& g = p.jobs[(size_t)f];
+            const double dx = g.cx - j.cx, dy = g.cy - j.cy;
+            if (t > s && !(dx < band)) break;
+            const double xx = dx * dx, yy = dy * dy;
+            const double D2 = xx + yy;
+            if (D2 < limit) cand.emplace_back(D2, f);
+        }
+        const size_t keep = std::min<size_t>(cand.size(), (size_t)PFIT_NEIGH_MAX);
+        std::partial_sort(cand.begin(), cand.begin() + (long)keep, cand.end());
+        j.nneigh = (int)keep; j.crowded = cand.size() > (size_t)PFIT_NEIGH_MAX ? 1 : 0;
+        for (size_t k = 0; k < keep; ++k) j.neigh[k] = cand[k].second;
+    }
+    return nullptr;
+}
+
+void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, double* row) {
+    for (int f = 0; f < PFIT_FIELDS; ++f) row[f] = 0.0;
+    if (!got) {
+        row[0] = (double)j.status;
+        row[32] = row[33] = row[34] = row[35] = -1.0;
+        return;
+    }
+    for (int f = 0; f < PFIT_FIELDS; ++f) row[f] = got[f];
+    if (got[0] == 3.0 || got[0] == 4.0) {
+        for (int f = 0; f < 6; ++f) row[5 + f] = job[5 + f];
+    } else {
+        row[6] = got[6] + (double)j.x0; row[7] = got[7] + (double)j.y0;
+    }
+    row[32] = (double)j.x0; row[33] = (double)j.x1; row[34] = (double)j.y0; row[35] = (double)j.y1;
+    row[36] = (double)j.clipped; row[37] = (double)j.nneigh; row[38] = (double)j.crowded;
+}
+
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {
     for (int r = 0; r < nrows; ++r) {
         const size_t row = (size_t)rows[r];

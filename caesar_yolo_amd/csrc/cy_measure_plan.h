@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -105,6 +105,26 @@ const char* plan_atrous(int MH, int MW, int step, unsigned long long in, unsigne
 struct AperPlan { std::vector<AperJob> jobs; int measured = 0; };
 const char* plan_apertures(const double* jobs, int n, const double* factors, int K, int MH, int MW, bool have_map, bool have_jobs,
                            bool have_out, AperPlan& p);
+
+// cy_fit_peaks.  jobs: [n][PFIT_JOB_FIELDS] {cx, cy, R, bkg, sign, A, x0, y0, a, b, c}, positions in image pixels.  Per job, in
+// float64 with every operation rounded on its own: status 1 when R is not finite, <= 0 or above PFIT_RADIUS_MAX, sign is not exactly
+// +1 or -1, or bkg is not finite.  Otherwise the window is decided in double before any conversion to int: columns [ceil(cx - R),
+// floor(cx + R)] clipped to [0, MW - 1], rows likewise with cy and MH; status 5 when the centre is not finite, a side misses the
+// image or holds no pixel centre.  clipped: the unclipped window of a status 0 job leaves the image.  The neighbours of a status 0
+// job e are the other status 0 jobs f with D2 = (cx_f - cx_e)^2 + (cy_f - cy_e)^2 < 4 * (R_e * R_e), ordered by (D2, f); the first
+// PFIT_NEIGH_MAX are kept, crowded says that there were more.  They are found by a scan of the jobs sorted by column over the columns
+// within 2 R_e, so the cost is the number of jobs in such a band, not n, per job.  run: the status 0 jobs in increasing index, one
+// workgroup each.  have_map, have_out: whether the caller's pointers are non-null (they and `jobs` count only for n > 0).  Returns
+// the message of the first failed check, in this order: MH or MW <= 0, an image of 2^31 pixels or more, n outside
+// [0, PFIT_JOBS_MAX], max_iter outside [1, 256], a null pointer.
+struct PeakFitPlan { std::vector<PeakFitJob> jobs; std::vector<int> run; };
+const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakFitPlan& p);
+
+// Row [PFIT_FIELDS] of cy_fit_peaks for job j.  A job the planner turned away (status 1 or 5, got == null): the status, the window
+// as -1 and zeros elsewhere.  Otherwise `got` is the row the kernel wrote: taken over, with the window, clipped, nneigh and crowded
+// of the plan, the centre back in image pixels, and for the kernel's status 3 or 4 the start exactly as given in `job`
+// ([PFIT_JOB_FIELDS]).
+void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, double* row);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

@@ -45,7 +45,12 @@ and one `cy_find_peaks` call; a list of dicts with SCALE_PEAK_KEYS beside the ca
 
 --peak_apertures measures what the searches list: `cy_aperture_sums` (HipDetector.aperture_sums) takes concentric circular
 apertures and a background annulus on the residual map around every entry of the peak lists, raw rows lib.APER_NAMES /
-lib.APER_RING_NAMES, keys APERTURE_KEYS on every entry (annotate_apertures).  Chain.run() calls Chain.apertures() last.
+lib.APER_RING_NAMES, keys APERTURE_KEYS on every entry (annotate_apertures).  Chain.run() calls Chain.apertures() after the searches.
+
+--fit_peaks gives the entries of those lists a shape: `cy_fit_peaks` (HipDetector.fit_peaks) fits one elliptical Gaussian to the
+residual map on a disc around every entry (of the scale peaks: the strongest ones), a disc it shares with neighbouring entries by
+a nearest-centre rule; a hole is fitted with sign -1.  Raw rows lib.PFIT_NAMES, keys GFIT_KEYS on every entry
+(annotate_peak_fits).  Chain.run() calls Chain.peak_fits() last, so that the local background of the apertures is there when they ran.
 
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
@@ -69,6 +74,8 @@ def _fields(names):
 MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
 RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
 APER, APER_RING = _fields(L.APER_NAMES), _fields(L.APER_RING_NAMES)
+PFIT, PFIT_JOB = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES)
+_PFIT_PARAMS = [getattr(PFIT, k) for k in "A x0 y0 a b c".split()]
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
 _MOMENTS = ("S", "Sx", "Sy", "Sxx", "Syy", "Sxy")
 _COMP_MOMENTS = [getattr(COMP, k) for k in _MOMENTS]
@@ -97,6 +104,9 @@ SCALE_PEAK_KEYS = PEAK_KEYS + ("scale", "step", "strongest")
 SOURCE_SCALE_KEYS = ("res_nscale_peaks", "res_scale_peak_snr")
 APERTURE_KEYS = ("ap_status", "ap_clipped", "ap_radius", "ap_npix", "ap_sum", "ap_bkg", "ap_bkg_rms", "ap_nbkg", "ap_flux_sum", "ap_flux",
                  "ap_flux_err", "ap_snr", "ap_best")
+GFIT_KEYS = ("gfit_status", "gfit_niter", "gfit_npix", "gfit_nexcluded", "gfit_nneigh", "gfit_crowded", "gfit_clipped", "gfit_radius", "gfit_bkg",
+             "gfit_chi2", "gfit_peak", "gfit_x", "gfit_y", "gfit_ra", "gfit_dec", "gfit_major", "gfit_minor", "gfit_pa", "gfit_flux", "gfit_peak_err",
+             "gfit_x_err", "gfit_y_err", "gfit_flux_err")
 MAD_TO_SIGMA = 1.482602218505602   # 1 / Phi^-1(3/4): the standard deviation of a normal distribution in units of its MAD
 SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
@@ -816,6 +826,102 @@ def annotate_apertures(entries, rows, nap, beam_area, radii=None):
     return entries
 
 
+# ---- peak fits (--fit_peaks)
+def peakfit_config(config):
+    """(radius, sigma0, max_iter) of --fit_peaks from a config dictionary: the radius of the fitted disc and the sigma of the
+    circular start, both in pixels at step 1, and the iteration limit.  ValueError for a radius or a sigma that is not finite and
+    positive, or a max_iter outside 1 .. 256."""
+    radius, sigma0 = float(config.get('fit_peaks_radius', 6.0)), float(config.get('fit_peaks_sigma', 1.5))
+    max_iter = config.get('fit_peaks_max_iter', 64)
+    if not (math.isfinite(radius) and radius > 0.0):
+        raise ValueError("fit_peaks_radius must be finite and > 0")
+    if not (math.isfinite(sigma0) and sigma0 > 0.0):
+        raise ValueError("fit_peaks_sigma must be finite and > 0")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= 256:
+        raise ValueError("fit_peaks_max_iter must be an integer in [1, 256]")
+    return radius, sigma0, int(max_iter)
+
+
+def wants_peak_fits(config):
+    """Whether a config asks for a Gaussian fit of the entries of its peak lists (fit_peaks)."""
+    return bool(config.get('fit_peaks', False))
+
+
+def peak_fit_jobs(entries, sign, radius, sigma0, at_peak, origin=(0, 0)):
+    """[n, CY_PFIT_JOB_FIELDS] float64 (lib.PFIT_JOB_NAMES), one job of cy_fit_peaks per entry of a peak list, in the pixel frame
+    (catalog coordinates - origin).  at_peak: [n] the map's value at every entry's peak pixel.
+      centre   the entry's x, y;  R = radius * step (step 1 for the entries of the pixel searches)
+      bkg      the entry's ap_bkg when the apertures ran and it is not None, else 0.0;  sign as given (-1 for holes)
+      start    A = sign * (at_peak - bkg), |entry["peak"]| when that is not > 0;  x0, y0 the centre;  a = c = 1 / (sigma0 * step)^2,
+               b = 0"""
+    bx, by = float(origin[0]), float(origin[1])
+    n = len(entries)
+    jobs = np.zeros((n, L.CY_PFIT_JOB_FIELDS), np.float64)
+    at_peak = np.asarray(at_peak, np.float64).reshape(n)
+    for i, d in enumerate(entries):
+        step = float(d.get("step", 1))
+        bkg = d.get("ap_bkg")
+        bkg = float(bkg) if bkg is not None else 0.0
+        A = float(sign) * (float(at_peak[i]) - bkg)
+        if not A > 0.0:
+            A = abs(float(d["peak"]))
+        a = 1.0 / ((float(sigma0) * step) * (float(sigma0) * step))
+        cx, cy = float(d["x"]) - bx, float(d["y"]) - by
+        jobs[i] = [cx, cy, float(radius) * step, bkg, float(sign), A, cx, cy, a, 0.0, a]
+    return jobs
+
+
+def annotate_peak_fits(entries, rows, jobs, rms, sign, beam_area, wcs, origin=(0, 0), select=None):
+    """GFIT_KEYS on every dict of `entries`.  rows: [m, CY_PFIT_FIELDS] rows of cy_fit_peaks with x0, y0 in catalog coordinates,
+    jobs: [m, CY_PFIT_JOB_FIELDS] what was asked for, rms: [m] the noise at the peak pixels; row t belongs to entries[select[t]]
+    (select None: entry t).  An entry without a row (a scale peak that is not the strongest of its place) gets every key None.
+      gfit_status, gfit_niter, gfit_npix, gfit_nexcluded, gfit_nneigh, gfit_crowded, gfit_clipped   as in the row (ints)
+      gfit_radius, gfit_bkg    R and bkg of the job
+      gfit_chi2 .. gfit_flux_err   as the fit_ keys of annotate_fits() (_gaussian_keys) with that rms; gfit_peak and gfit_flux carry
+                               the sign: negative for a hole
+    With status 1, 3, 4 or 5 the keys from gfit_chi2 on are None.  -> entries."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PFIT_FIELDS)
+    jobs = np.asarray(jobs, np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS)
+    rms = np.asarray(rms, np.float64).reshape(-1)
+    select = list(range(len(entries))) if select is None else [int(i) for i in select]
+    assert rows.shape[0] == jobs.shape[0] == rms.shape[0] == len(select)
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for d in entries:
+        d.update(dict.fromkeys(GFIT_KEYS))
+    for i, r, job, noise in zip(select, rows, jobs, rms):
+        d = entries[i]
+        st = int(r[PFIT.status])
+        d["gfit_status"], d["gfit_niter"], d["gfit_npix"], d["gfit_nexcluded"] = st, int(r[PFIT.niter]), int(r[PFIT.npix]), int(r[PFIT.nexcluded])
+        d["gfit_nneigh"], d["gfit_crowded"], d["gfit_clipped"] = int(r[PFIT.nneigh]), int(r[PFIT.crowded]), int(r[PFIT.clipped])
+        d["gfit_radius"], d["gfit_bkg"] = float(job[PFIT_JOB.R]), float(job[PFIT_JOB.bkg])
+        if st in (0, 2):
+            noise = float(noise) if math.isfinite(noise) and noise > 0.0 else 0.0
+            _gaussian_keys(d, "gfit_", r, PFIT.F, _PFIT_PARAMS, fit_covariance, noise, ba, wcs, ox, oy)
+            if sign < 0:
+                d["gfit_peak"] = -d["gfit_peak"]
+                if d["gfit_flux"] is not None:
+                    d["gfit_flux"] = -d["gfit_flux"]
+    return entries
+
+
+def peak_fit_stats(rows):
+    """(jobs, converged, mean niter, largest niter, crowded) over rows [n, CY_PFIT_FIELDS] of cy_fit_peaks; the iterations over the
+    fitted rows (status 0 or 2)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PFIT_FIELDS)
+    it = rows[np.isin(rows[:, PFIT.status], _FITTED), PFIT.niter]
+    return (int(rows.shape[0]), int((rows[:, PFIT.status] == 0.0).sum()), float(it.mean()) if it.size else 0.0, int(it.max()) if it.size else 0,
+            int((rows[:, PFIT.crowded] == 1.0).sum()))
+
+
+def _read_at(m, iy, ix):
+    """m[iy, ix] of a device map (or a host array) as numpy float64: one indexed read."""
+    if hasattr(m, "is_cuda"):
+        import torch
+        return m[torch.as_tensor(iy, device=m.device), torch.as_tensor(ix, device=m.device)].cpu().numpy().astype(np.float64)
+    return np.asarray(m)[iy, ix].astype(np.float64)
+
+
 def peaks_config(config):
     """(k_sigma, radius, min_above, cap) of --residual_peaks from a config dictionary."""
     return (float(config.get('residual_peaks_sigma', 5.0)), int(config.get('residual_peaks_radius', 2)),
@@ -956,11 +1062,11 @@ def plan(config):
     and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
     save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
     step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
-    (Chain.scale_peaks, no step either) implies exactly the same, and so does peak_apertures (Chain.apertures), which measures on
-    the residual map with the rms map of the mesh but turns no search on."""
+    (Chain.scale_peaks, no step either) implies exactly the same, and so do peak_apertures (Chain.apertures) and fit_peaks
+    (Chain.peak_fits), which measure on the residual map with the rms map of the mesh but turn no search on."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
-    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config)
+    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config)
     residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
@@ -996,6 +1102,8 @@ class Chain(object):
         self.save_scales = bool(c.get('save_scale_maps', False))
         self.want_apertures = wants_apertures(c)
         self.ap_unit, self.ap_factors, self.ap_annulus = aperture_config(c) if self.want_apertures else (1.0, (), 0.0)
+        self.want_peak_fits = wants_peak_fits(c)
+        self.pf_radius, self.pf_sigma, self.pf_max_iter = peakfit_config(c) if self.want_peak_fits else (6.0, 1.5, 64)
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
         self.MH, self.MW = int(img_dev.shape[0]), int(img_dev.shape[1])
@@ -1010,6 +1118,7 @@ class Chain(object):
         self.peak_list = self.hole_list = self.peak_stats = None
         self.scale_list = self.scale_stats = self.scale_levels = self.scale_planes = self.scale_rows = None
         self.aperture_rows = self.aperture_stats = None
+        self.peakfit_rows = self.peakfit_jobs = self.peakfit_select = self.peakfit_stats = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -1204,8 +1313,44 @@ class Chain(object):
         st["apertures_ms"] = 1e3 * (time.time() - t1)
         self.aperture_stats = st
 
+    def peak_fits(self):
+        """After residual(), the searches and apertures(): the rms map of the mesh expanded once, then per non-empty list
+        (residual_peaks, residual_holes with sign -1, residual_scale_peaks: its strongest entries only) one indexed read of .resid
+        and one of the rms map at the entries' peak pixels, peak_fit_jobs(), one cy_fit_peaks call on .resid, the rows moved to
+        catalog coordinates, then annotate_peak_fits().  Leaves .peakfit_rows, .peakfit_jobs (both as the library saw them, in the
+        pixels of img_dev) and .peakfit_select ({list name: ...}; select: the entries that were fitted) and .peakfit_stats
+        {"peakfit_ms", "peakfit_kernel_ms" (summed over the calls), "peakfit_jobs", "peakfit_converged", "peakfit_niter_mean",
+        "peakfit_niter_max", "peakfit_crowded"}."""
+        t1 = time.time()
+        self.peakfit_rows, self.peakfit_jobs, self.peakfit_select = {}, {}, {}
+        st = {"peakfit_kernel_ms": 0.0}
+        lists = [(k, v, sg) for k, v, sg in (("residual_peaks", self.peak_list, 1.0), ("residual_holes", self.hole_list, -1.0),
+                                             ("residual_scale_peaks", self.scale_list, 1.0)) if v]
+        rms_dev = self.det.expand_background(self.mesh, self.cell, self.img.shape, want=("rms",))[1] if lists else None
+        every = []
+        for name, entries, sign in lists:
+            select = [i for i, d in enumerate(entries) if d.get("strongest", True)]
+            chosen = [entries[i] for i in select]
+            ix = np.clip(np.array([int(round(d["x_peak"] - self.bx)) for d in chosen], np.int64), 0, self.MW - 1)
+            iy = np.clip(np.array([int(round(d["y_peak"] - self.by)) for d in chosen], np.int64), 0, self.MH - 1)
+            at_peak, rms = _read_at(self.resid, iy, ix), _read_at(rms_dev, iy, ix)
+            jobs = peak_fit_jobs(chosen, sign, self.pf_radius, self.pf_sigma, at_peak, self.box_origin)
+            rows = np.zeros((0, L.CY_PFIT_FIELDS), np.float64)
+            if select:                                        # a scale list may hold no strongest entry: no call, no kernel time
+                rows = self.det.fit_peaks(self.resid, jobs, max_iter=self.pf_max_iter)
+                st["peakfit_kernel_ms"] += max(self.det.peakfit_kernel_ms(), 0.0)
+            has = ~np.isin(rows[:, PFIT.status], (1.0, 5.0))
+            moved = self._moved(rows, has, (PFIT.x0, PFIT.wx0, PFIT.wx1), (PFIT.y0, PFIT.wy0, PFIT.wy1))
+            annotate_peak_fits(entries, moved, jobs, rms, sign, self.beam_area, self.wcs, self.wcs_origin, select)
+            self.peakfit_rows[name], self.peakfit_jobs[name], self.peakfit_select[name] = rows, jobs, select
+            every.append(rows)
+        every = np.concatenate(every) if every else np.zeros((0, L.CY_PFIT_FIELDS), np.float64)
+        (st["peakfit_jobs"], st["peakfit_converged"], st["peakfit_niter_mean"], st["peakfit_niter_max"], st["peakfit_crowded"]) = peak_fit_stats(every)
+        st["peakfit_ms"] = 1e3 * (time.time() - t1)
+        self.peakfit_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks() and apertures(), each when the
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures() and peak_fits(), each when the
         config asks for it and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
@@ -1245,6 +1390,10 @@ class Chain(object):
             self.apertures()
             if stats is not None:
                 stats.update(self.aperture_stats)
+        if self.want_peak_fits and "residual" in steps:
+            self.peak_fits()
+            if stats is not None:
+                stats.update(self.peakfit_stats)
         return self
 
     def save_maps(self, catalog_path):

@@ -610,6 +610,25 @@ class HipDetector(object):
         """Kernel time of the last aperture_sums call that launched in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_aperture_kernel_ms)
 
+    # ---- Gaussian fits at given positions (a shape for every entry of the peak lists)
+    def fit_peaks(self, map_dev, jobs, max_iter=64):
+        """One elliptical Gaussian per job on the pixels of a disc around a given position of map_dev (cy_fit_peaks).  map_dev: a
+        contiguous 2-D float32 device map, the residual map of render_gaussians; jobs: [n, CY_PFIT_JOB_FIELDS] float64
+        (lib.PFIT_JOB_NAMES): the centre and radius of the disc, the background, the sign (-1 fits a hole) and the start, all
+        positions in the pixels of map_dev.  -> numpy float64 [n, CY_PFIT_FIELDS] (lib.PFIT_NAMES)."""
+        MH, MW = self._image_2d(map_dev, "fit_peaks")
+        jobs = np.ascontiguousarray(np.asarray(jobs, np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS))
+        n = jobs.shape[0]
+        out = np.zeros((n, L.CY_PFIT_FIELDS), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_fit_peaks(self.ctx, self._p(map_dev), MH, MW, jobs.ctypes.data_as(dp), n, int(max_iter),
+                                        out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def peakfit_kernel_ms(self):
+        """Kernel time of the last fit_peaks call that launched in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_peakfit_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

@@ -679,6 +679,47 @@ int cy_aperture_sums(cy_ctx* ctx, const float* d_map, const float* d_rms /* or N
 /* milliseconds the kernel of the last cy_aperture_sums call took (hipEvents around the launch); -1 before the first call */
 int cy_aperture_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- Gaussian fits at given positions (an addition: a shape for every residual and scale peak) --------------------------------
+ * One elliptical Gaussian per job, fitted to the pixels of a disc around the job's centre on d_map (device fp32 [MH][MW], the
+ * residual map of cy_render_gaussians).  h_jobs: [n][CY_PFIT_JOB_FIELDS] {cx, cy, R, bkg, sign, A, x0, y0, a, b, c}: the centre and
+ * radius of the disc, and the start of the fit with x0, y0 in image pixels.  Everything in float64, every product and sum rounded
+ * on its own (no contraction); valid pixel and pixel-centre convention as cy_aperture_sums.
+ *   planner    on the host, before any device work.  Status 1: R not finite, <= 0 or > CY_PFIT_RADIUS_MAX, sign not exactly +1 or
+ *              -1, or bkg not finite.  Status 5 (status 1 is tested first): cx or cy not finite, or the window holds no pixel of
+ *              the image.  The window is columns [ceil(cx - R), floor(cx + R)], rows likewise with cy, clipped to the image;
+ *              clipped = 1 when the unclipped window leaves the image.  A job with status 1 or 5 reports the window as -1 and
+ *              zeros elsewhere and launches no work
+ *   neighbours of a job e with planner status 0: the other jobs f of the call with planner status 0 and D2 = (cx_f - cx_e)^2 +
+ *              (cy_f - cy_e)^2 < 4 * (R_e * R_e), ordered by (D2, job index); the first CY_PFIT_NEIGH_MAX are kept, nneigh =
+ *              min(count, 8), crowded = 1 when count > 8.  Coincident centres (D2 = 0) are neighbours
+ *   pixel set  window pixel (qx, qy) is a member of job e when d2_e = (qx - cx_e)^2 + (qy - cy_e)^2 <= R_e * R_e and d2_f >= d2_e
+ *              for every kept neighbour f; distances in image coordinates; a pixel that ties belongs to both jobs.  npix: the
+ *              valid members; nexcluded: the valid pixels inside the disc that a neighbour took
+ *   data       y = sign * ((double)v - bkg).  Model, "admissible", the 28 sums, the 6 x 6 Cholesky and the iteration are word for
+ *              word those of cy_fit_components; the fit runs on x0 - wx0, y0 - wy0 (relative to the window's first pixel) and
+ *              reports image pixels.  A is reported positive: the caller applies the sign
+ *   LIST and ASSOCIATION   the job's list is every pixel of the window in increasing window index i = dy * W + dx, entry i on
+ *              thread i mod 256; a pixel that is not a valid member keeps its position and contributes nothing; then the block
+ *              reduction of the measurement kernels.  Two calls give the same bytes
+ *   after the planner   status 4: the start is not admissible (tested before 3); 3: npix < 7; 0: converged; 2: max_iter or the
+ *              lambda limit reached.  With 3 and 4 the start is reported as given, niter = 0 and F, lambda and H are 0
+ * Row i of h_out, CY_PFIT_FIELDS float64: [0] status, [1] niter, [2] npix, [3] F, [4] lambda, [5..10] A x0 y0 a b c, [11..31] H
+ * upper triangle row-major, [32..35] wx0 wx1 wy0 wy1, [36] clipped, [37] nneigh, [38] crowded, [39] nexcluded.
+ * One launch: one workgroup of 256 threads per planner-status-0 job; a window of up to 8192 pixels keeps its members' values in
+ * LDS, a larger one evaluates membership again in every sweep.  Synchronous on `stream`; needs no loaded weights; the map is only
+ * read.  CY_ERR_ARG with a message (cy_last_error), nothing launched and h_out untouched, checked in this order after a null ctx:
+ * MH or MW <= 0; an image of 2^31 pixels or more; n outside [0, CY_PFIT_JOBS_MAX]; max_iter outside [1, 256]; with n > 0 a null
+ * d_map, h_jobs or h_out.  n == 0: CY_OK, nothing launched. */
+#define CY_PFIT_JOB_FIELDS 11    /* cx cy R bkg sign A x0 y0 a b c   (x0, y0 in image pixels) */
+#define CY_PFIT_FIELDS     40
+#define CY_PFIT_RADIUS_MAX 256
+#define CY_PFIT_NEIGH_MAX  8
+#define CY_PFIT_JOBS_MAX   (1 << 20)
+int cy_fit_peaks(cy_ctx* ctx, const float* d_map, int MH, int MW, const double* h_jobs /* [n][CY_PFIT_JOB_FIELDS] */, int n,
+                 int max_iter, double* h_out /* [n][CY_PFIT_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_fit_peaks call that launched one took (hipEvents around the launch); -1 before it */
+int cy_peakfit_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

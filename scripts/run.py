@@ -70,6 +70,11 @@ Differences that come with the MI355X engine:
              --aperture_annulus (default 6) as local background and the rms map of the mesh as noise: ap_status, ap_clipped,
              ap_radius, ap_npix, ap_sum, ap_bkg, ap_bkg_rms, ap_nbkg, ap_flux_sum, ap_flux, ap_flux_err, ap_snr, ap_best per
              entry, a curve of growth (cy_aperture_sums; DESIGN.md "Peak apertures").
+  --fit_peaks  (new; implies what --peak_apertures implies) one elliptical Gaussian fitted on the GPU to the residual map around every
+             entry of the peak lists (of "residual_scale_peaks" the strongest ones), inside a disc of --fit_peaks_radius (default 6)
+             pixels times the entry's step that it shares with neighbouring entries by a nearest-centre rule, from a circular start
+             of --fit_peaks_sigma (default 1.5) pixels, at most --fit_peaks_max_iter (default 64) iterations; holes are fitted with
+             a sign: gfit_status .. gfit_flux_err per entry (cy_fit_peaks; DESIGN.md "Peak fits").
 """
 import argparse
 import logging
@@ -81,7 +86,7 @@ from caesar_yolo_amd.config import CONFIG                                     # 
 from caesar_yolo_amd.preprocessing import (DataPreprocessor, BkgSubtractor, SigmaClipShifter, SigmaClipper, ChanResizer,  # noqa: E402
                                            ZScaleTransformer, Chan3Trasformer, MinMaxNormalizer)
 from caesar_yolo_amd.inference import SFinder                                 # noqa: E402
-from caesar_yolo_amd.measure import aperture_config, plan, wants_peaks, wants_scales  # noqa: E402
+from caesar_yolo_amd.measure import aperture_config, peakfit_config, plan, wants_peaks, wants_scales  # noqa: E402
 from caesar_yolo_amd.model import YOLO                                        # noqa: E402
 
 logging.basicConfig(format="%(asctime)-15s %(levelname)s - %(message)s", datefmt='%Y-%m-%d %H:%M:%S')
@@ -217,7 +222,22 @@ def parse_args(argv=None):
                    help='comma-separated aperture radii in units of --aperture_unit, strictly increasing, at most 7 (with --peak_apertures)')
     p.add_argument('--aperture_annulus', dest='aperture_annulus', type=float, default=6.0,
                    help='outer radius of the background annulus, which starts at the last aperture radius (with --peak_apertures)')
+    p.add_argument('--fit_peaks', dest='fit_peaks', action='store_true',
+                   help='fit a Gaussian to the residual map around every residual peak, hole and strongest scale peak (implies what --peak_apertures implies; alone it turns --residual_peaks on)')
+    p.add_argument('--fit_peaks_radius', dest='fit_peaks_radius', type=float, default=6.0,
+                   help='radius in pixels of the disc that is fitted at step 1; a scale peak multiplies it by its step (with --fit_peaks)')
+    p.add_argument('--fit_peaks_sigma', dest='fit_peaks_sigma', type=float, default=1.5,
+                   help='sigma in pixels of the circular start at step 1; a scale peak multiplies it by its step (with --fit_peaks)')
+    p.add_argument('--fit_peaks_max_iter', dest='fit_peaks_max_iter', type=int, default=64,
+                   help='iterations of a peak fit at most, 1..256 (with --fit_peaks)')
     args = p.parse_args(argv)
+    if args.fit_peaks:
+        try:
+            peakfit_config(vars(args))
+        except ValueError as e:
+            p.error("--fit_peaks: %s" % e)
+        if not (wants_peaks(vars(args)) or wants_scales(vars(args))):
+            args.residual_peaks = True                        # fits need a list, as apertures do
     if args.peak_apertures:
         try:
             aperture_config(vars(args))
@@ -315,7 +335,8 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'save_residual_maps', 'bkg_map', 'bkg_cell', 'bkg_clip_sigma', 'bkg_clip_iters', 'bkg_min_pix', 'save_bkg_maps',
                 'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
                 'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps',
-                'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus')
+                'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus',
+                'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter')
 
 
 def measure_config(args):

@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--no-apertures] [--only a,b] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--no-apertures] [--no-peakfits] [--only a,b] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -27,6 +27,9 @@ cy_find_peaks on it, `--runs` calls each after a warm-up, with the bytes moved p
 Unless --no-apertures (or --no-scales, --no-residual) is given there is a variant `apertures`, --fit_blends --residual_map --residual_peaks
 --residual_scales 4 --peak_apertures (apertures_ms, aperture_kernel_ms summed over the calls, the numbers of jobs, measured and clipped
 ones beside the scales_ and peaks_ kernel times of the same runs); apertures_added_ms is its run time over that of the `scales` variant.
+Unless --no-peakfits (or --no-apertures, --no-scales, --no-residual) is given there is a variant `peakfits`, the flags of `apertures` plus
+--fit_peaks (peakfit_ms, peakfit_kernel_ms summed over the calls, the numbers of jobs, converged and crowded ones and the iterations);
+peakfits_added_ms is its run time over that of the `apertures` variant of the same runs.
 --only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
@@ -132,6 +135,7 @@ def main():
     ap.add_argument("--no-peaks", action="store_true")
     ap.add_argument("--no-scales", action="store_true")
     ap.add_argument("--no-apertures", action="store_true")
+    ap.add_argument("--no-peakfits", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
@@ -180,6 +184,10 @@ def main():
                                    ("render_kernel_ms", "peaks_kernel_ms", "scales_ms", "atrous_kernel_ms", "scales_background_kernel_ms", "scales_peaks_kernel_ms",
                                     "apertures_ms", "aperture_kernel_ms"),
                                    ("peaks_kept", "scales_kept", "apertures_jobs", "apertures_measured", "apertures_clipped")),
+                     "peakfits": (["--fit_blends", "--residual_map", "--residual_peaks", "--residual_scales=4", "--peak_apertures", "--fit_peaks"],
+                                  ("apertures_ms", "aperture_kernel_ms", "peakfit_ms", "peakfit_kernel_ms"),
+                                  ("peaks_kept", "scales_kept", "scales_strongest", "peakfit_jobs", "peakfit_converged", "peakfit_niter_mean", "peakfit_niter_max",
+                                   "peakfit_crowded")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
@@ -187,6 +195,8 @@ def main():
                     "peaks": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_peaks,
                     "scales": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales,
                     "apertures": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures,
+                    "peakfits": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
+                                 args.no_peakfits),
                     "islands": args.no_islands}
             if args.only:
                 skip.update({name: True for name in table if name not in args.only.split(",")})
@@ -222,6 +232,8 @@ def main():
                 res["scales_added_ms"] = res["scales"]["run_ms_median"] - res["residual"]["run_ms_median"]
             if "apertures" in got and "scales" in got:
                 res["apertures_added_ms"] = res["apertures"]["run_ms_median"] - res["scales"]["run_ms_median"]
+            if "peakfits" in got and "apertures" in got:
+                res["peakfits_added_ms"] = res["peakfits"]["run_ms_median"] - res["apertures"]["run_ms_median"]
             if "scales" in got:
                 res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:

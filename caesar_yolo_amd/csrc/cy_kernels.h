@@ -394,6 +394,19 @@ struct PeakFitArgs {
 };
 hipError_t launch_peak_fits(const PeakFitArgs& a, hipStream_t s);
 
+// ---- joint fits of groups of peaks (cy_peakgroup.hip) --------------------------------------------------
+// PGRP_FIELDS, PeakGroupJob: cy_measure_jobs.h; the groups: plan_peak_groups (cy_measure_plan.h)
+constexpr int PGRP_LDS_MAX = 8192;             // largest group window (pixels) whose member values live in LDS: 32 KiB per workgroup
+struct PeakGroupArgs {
+    const float* map; int MH, MW;   // MH * MW < 2^31
+    const PeakFitJob* jobs; int n;  // the whole job table: members and outside neighbours are named by their indices in it
+    const PeakGroupJob* groups; int ngroups;       // one workgroup each: 1 <= ngroups <= n / 2
+    int max_iter;                   // 1 .. FIT_MAX_ITER
+    double* out;                    // [ngroups][BLEND_MAX_MEMBERS][PGRP_FIELDS]: workgroup t writes the rows of its M members
+                                    // (fields 0 .. 35 and nexcluded; the others are the host's), zeroed by the caller
+};
+hipError_t launch_peak_groups(const PeakGroupArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

@@ -1,5 +1,5 @@
 // Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip, cy_aperture.hip,
-// cy_peakfit.hip) and the
+// cy_peakfit.hip, cy_peakgroup.hip) and the
 // host-side planner that fills them (cy_measure_plan.cpp).  No HIP include: the planner also builds as plain C++.
 #pragma once
 
@@ -40,6 +40,7 @@ constexpr int PFIT_FIELDS = 40;                // CY_PFIT_FIELDS
 constexpr int PFIT_RADIUS_MAX = 256;           // CY_PFIT_RADIUS_MAX: largest disc radius in pixels; a window has at most 513 x 513 pixels
 constexpr int PFIT_NEIGH_MAX = 8;              // CY_PFIT_NEIGH_MAX: neighbours a job shares its disc with
 constexpr int PFIT_JOBS_MAX = 1 << 20;         // CY_PFIT_JOBS_MAX: one workgroup per fitted job, the grid in x only
+constexpr int PGRP_FIELDS = 44;                // CY_PGRP_FIELDS: the 36 fields of a blend row, wx0 wx1 wy0 wy1 clipped nexcluded nlinked 0
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list
@@ -81,6 +82,16 @@ struct PeakFitJob {
     int clipped;                    // 1: the unclipped window leaves the image
     int nneigh, crowded;            // kept neighbours; 1: there were more than PFIT_NEIGH_MAX
     int neigh[PFIT_NEIGH_MAX];      // their job indices in (squared distance, index) order; -1 beyond nneigh
+};
+
+struct PeakGroupJob {
+    int M;                          // members, 2 .. BLEND_MAX_MEMBERS
+    int member[BLEND_MAX_MEMBERS];  // their indices in the PeakFitJob table, increasing; member[0] is the group's id; -1 beyond M
+    int nout[BLEND_MAX_MEMBERS];    // per member: its kept neighbours that are not members of the group
+    int out[BLEND_MAX_MEMBERS][PFIT_NEIGH_MAX];     // their indices in the PeakFitJob table, in the member's own order; -1 beyond nout
+    int x0, x1, y0, y1;             // the group window: the bounding box of the members' windows, inclusive, inside the image
+    double bkg, sign;               // those of the member in slot 0
+    double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the group window's first pixel
 };
 
 }  // namespace cy

@@ -346,13 +346,51 @@ const char* plan_apertures(const double* jobs, int n, const double* factors, int
     return nullptr;
 }
 
-const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakFitPlan& p) {
-#pragma clang fp contract(off)          // R*R and dx*dx + dy*dy: every product is rounded before it is used, whatever the build's default
-    p = PeakFitPlan();
+namespace {
+// the checks of cy_fit_peaks that come before its pointers, in their order
+const char* peak_fit_sizes(int n, int max_iter, int MH, int MW) {
     if (MH <= 0 || MW <= 0) return "MH, MW > 0 required";
     if ((long long)MH * MW >= (1LL << 31)) return "image of 2^31 pixels or more";
     if (n < 0 || n > PFIT_JOBS_MAX) return "n outside 0 .. CY_PFIT_JOBS_MAX";
     if (max_iter < 1 || max_iter > 256) return "max_iter outside 1 .. 256";
+    return nullptr;
+}
+
+// the fitted jobs sorted by column (ties by index)
+std::vector<int> sorted_by_column(const PeakFitPlan& p) {
+    std::vector<int> by_x(p.run);
+    std::sort(by_x.begin(), by_x.end(), [&](int a, int b) { return p.jobs[(size_t)a].cx < p.jobs[(size_t)b].cx || (p.jobs[(size_t)a].cx == p.jobs[(size_t)b].cx && a < b); });
+    return by_x;
+}
+
+// Job e = by_x[s] looks at the stretch of the sorted jobs whose |cx_f - cx_e| (as the test below rounds it) is below `band`:
+// visit(f, D2) for every other job f in it, D2 = (cx_f - cx_e)^2 + (cy_f - cy_e)^2.  The stretch holds every f with D2 < band^2,
+// because dx*dx <= D2 and rounding is monotonic
+template <class Visit>
+void scan_band(const std::vector<PeakFitJob>& jobs, const std::vector<int>& by_x, size_t s, double band, Visit&& visit) {
+#pragma clang fp contract(off)          // dx*dx + dy*dy: every product is rounded before it is used, whatever the build's default
+    const size_t m = by_x.size();
+    const int e = by_x[s];
+    const PeakFitJob& j = jobs[(size_t)e];
+    // the band's left end by bisection on the sorted columns (it does not move monotonically when the radii differ)
+    size_t lo = 0, hi = s;
+    while (lo < hi) { const size_t mid = (lo + hi) / 2; if (j.cx - jobs[(size_t)by_x[mid]].cx < band) hi = mid; else lo = mid + 1; }
+    for (size_t t = lo; t < m; ++t) {
+        const int f = by_x[t];
+        if (f == e) continue;
+        const PeakFitJob& g = jobs[(size_t)f];
+        const double dx = g.cx - j.cx, dy = g.cy - j.cy;
+        if (t > s && !(dx < band)) break;
+        const double xx = dx * dx, yy = dy * dy;
+        visit(f, xx + yy);
+    }
+}
+}  // namespace
+
+const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakFitPlan& p) {
+#pragma clang fp contract(off)          // R*R: every product is rounded before it is used, whatever the build's default
+    p = PeakFitPlan();
+    if (const char* msg = peak_fit_sizes(n, max_iter, MH, MW)) return msg;
     if (n > 0 && !(have_map && jobs && have_out)) return "null argument";
     // one side of a window, as plan_apertures decides it
     auto side = [](double c, double r, int N, int* lo, int* hi, int* clipped) {
@@ -387,30 +425,16 @@ const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int 
         lim[(size_t)i] = 2.0 * R;
         p.run.push_back(i);
     }
-    // neighbours: the fitted jobs sorted by column; job e looks at the stretch whose |cx_f - cx_e| (as the test below rounds it) is
-    // below 2 R_e, which holds every f with D2 < 4 R_e^2 because dx*dx <= D2 and rounding is monotonic
-    std::vector<int> by_x(p.run);
-    std::sort(by_x.begin(), by_x.end(), [&](int a, int b) { return p.jobs[(size_t)a].cx < p.jobs[(size_t)b].cx || (p.jobs[(size_t)a].cx == p.jobs[(size_t)b].cx && a < b); });
+    // neighbours: the fitted jobs sorted by column; job e looks at the stretch within 2 R_e, which holds every f with D2 < 4 R_e^2
+    const std::vector<int> by_x = sorted_by_column(p);
     const size_t m = by_x.size();
     std::vector<std::pair<double, int>> cand;
     for (size_t s = 0; s < m; ++s) {
         const int e = by_x[s];
         PeakFitJob& j = p.jobs[(size_t)e];
-        const double band = lim[(size_t)e], limit = 4.0 * j.r2;
-        // the band's left end by bisection on the sorted columns (it does not move monotonically when the radii differ)
-        size_t lo = 0, hi = s;
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (j.cx - p.jobs[(size_t)by_x[mid]].cx < band) hi = mid; else lo = mid + 1; }
+        const double limit = 4.0 * j.r2;
         cand.clear();
-        for (size_t t = lo; t < m; ++t) {
-            const int f = by_x[t];
-            if (f == e) continue;
-            const PeakFitJob& g = p.jobs[(size_t)f];
-            const double dx = g.cx - j.cx, dy = g.cy - j.cy;
-            if (t > s && !(dx < band)) break;
-            const double xx = dx * dx, yy = dy * dy;
-            const double D2 = xx + yy;
-            if (D2 < limit) cand.emplace_back(D2, f);
-        }
+        scan_band(p.jobs, by_x, s, lim[(size_t)e], [&](int f, double D2) { if (D2 < limit) cand.emplace_back(D2, f); });
         const size_t keep = std::min<size_t>(cand.size(), (size_t)PFIT_NEIGH_MAX);
         std::partial_sort(cand.begin(), cand.begin() + (long)keep, cand.end());
         j.nneigh = (int)keep; j.crowded = cand.size() > (size_t)PFIT_NEIGH_MAX ? 1 : 0;
@@ -434,6 +458,104 @@ void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, dou
     }
     row[32] = (double)j.x0; row[33] = (double)j.x1; row[34] = (double)j.y0; row[35] = (double)j.y1;
     row[36] = (double)j.clipped; row[37] = (double)j.nneigh; row[38] = (double)j.crowded;
+}
+
+const char* plan_peak_groups(const double* jobs, int n, double link, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakGroupPlan& p) {
+#pragma clang fp contract(off)          // link * R and Lm * Lm: every product is rounded before it is used, whatever the build's default
+    p = PeakGroupPlan();
+    if (const char* msg = peak_fit_sizes(n, max_iter, MH, MW)) return msg;
+    if (!std::isfinite(link) || !(link > 0.0) || link > 2.0) return "link outside (0, 2]";
+    if (const char* msg = plan_peak_fits(jobs, n, max_iter, MH, MW, have_map, have_out, p.fits)) return msg;
+    const std::vector<PeakFitJob>& J = p.fits.jobs;
+    const size_t N = (size_t)n;
+    p.group.assign(N, 0); p.size.assign(N, 0); p.slot.assign(N, 0); p.nlinked.assign(N, 0); p.status.assign(N, 0); p.job_of.assign(N, -1);
+    p.rows.assign(N * PGRP_FIELDS, 0.0);
+    std::vector<int>& root = p.group;
+    for (int i = 0; i < n; ++i) root[(size_t)i] = i;
+    auto find = [&](int k) { while (root[(size_t)k] != k) k = root[(size_t)k] = root[(size_t)root[(size_t)k]]; return k; };
+    auto radius = [&](int i) { return jobs[(size_t)i * PFIT_JOB_FIELDS + 2]; };
+    // links: a pair is found from the side of its larger radius, whose band link * R holds it
+    const std::vector<int> by_x = sorted_by_column(p.fits);
+    for (size_t s = 0; s < by_x.size(); ++s) {
+        const int e = by_x[s];
+        const double Re = radius(e), Lm = link * Re;
+        const double Lm2 = Lm * Lm;
+        scan_band(J, by_x, s, Lm, [&](int f, double D2) {
+            const double Rf = radius(f);
+            if (Rf > Re || (Rf == Re && f < e)) return;       // job f finds this pair
+            if (J[(size_t)f].sign != J[(size_t)e].sign || !(D2 < Lm2)) return;
+            ++p.nlinked[(size_t)e]; ++p.nlinked[(size_t)f];
+            const int a = find(e), b = find(f);
+            if (a != b) root[(size_t)std::max(a, b)] = std::min(a, b);           // the root of a group is its lowest member
+        });
+    }
+    // groups, slots, statuses; the bounding box and the clipped flag of every group, kept at its root
+    std::vector<int> box(N * 5, 0);
+    for (int i = 0; i < n; ++i) {
+        const PeakFitJob& j = J[(size_t)i];
+        const int g = root[(size_t)i] = find(i);
+        p.slot[(size_t)i] = p.size[(size_t)g]++;
+        if (j.status != 0) continue;
+        int* b = &box[(size_t)g * 5];
+        if (g == i) { b[0] = j.x0; b[1] = j.x1; b[2] = j.y0; b[3] = j.y1; b[4] = j.clipped; }
+        else { b[0] = std::min(b[0], j.x0); b[1] = std::max(b[1], j.x1); b[2] = std::min(b[2], j.y0); b[3] = std::max(b[3], j.y1); b[4] |= j.clipped; }
+    }
+    for (int i = 0; i < n; ++i) {
+        const PeakFitJob& j = J[(size_t)i];
+        const int g = root[(size_t)i], M = p.size[(size_t)i] = p.size[(size_t)g];   // g <= i: the root's size is final
+        double* row = &p.rows[(size_t)i * PGRP_FIELDS];
+        if (j.status != 0) {
+            p.status[(size_t)i] = j.status;
+            row[0] = (double)j.status; row[36] = row[37] = row[38] = row[39] = -1.0;
+            continue;
+        }
+        const int st = p.status[(size_t)i] = M == 1 ? 6 : M > BLEND_MAX_MEMBERS ? 7 : 0;
+        const int* b = &box[(size_t)g * 5];
+        row[0] = (double)st; row[5] = (double)g; row[6] = (double)M; row[7] = (double)p.slot[(size_t)i];
+        for (int t = 0; t < 4; ++t) row[36 + t] = (double)b[t];
+        row[40] = (double)b[4]; row[42] = (double)p.nlinked[(size_t)i];
+        const double* q = jobs + (size_t)i * PFIT_JOB_FIELDS;
+        if (st == 7)
+            for (int t = 0; t < 6; ++t) row[8 + t] = q[5 + t];
+        if (st != 0) continue;
+        if (g == i) {
+            PeakGroupJob gj{};
+            gj.M = M; gj.x0 = b[0]; gj.x1 = b[1]; gj.y0 = b[2]; gj.y1 = b[3]; gj.bkg = j.bkg; gj.sign = j.sign;
+            for (int t = 0; t < BLEND_MAX_MEMBERS; ++t) {
+                gj.member[t] = -1;
+                for (int k = 0; k < PFIT_NEIGH_MAX; ++k) gj.out[t][k] = -1;
+            }
+            p.job_of[(size_t)g] = (int)p.groups.size();
+            p.groups.push_back(gj);
+        }
+        const int at = p.job_of[(size_t)i] = p.job_of[(size_t)g];
+        PeakGroupJob& gj = p.groups[(size_t)at];
+        const int s = p.slot[(size_t)i];
+        gj.member[s] = i;
+        for (int k = 0; k < j.nneigh; ++k)
+            if (root[(size_t)j.neigh[k]] != g) gj.out[s][gj.nout[s]++] = j.neigh[k];
+        double* p0 = gj.p0 + 6 * s;
+        for (int t = 0; t < 6; ++t) p0[t] = q[5 + t];
+        p0[1] = q[6] - (double)gj.x0; p0[2] = q[7] - (double)gj.y0;
+    }
+    return nullptr;
+}
+
+void peak_group_rows(const PeakGroupPlan& p, const double* jobs, const double* got, double* out) {
+    for (size_t t = 0; t < p.groups.size(); ++t) {
+        const PeakGroupJob& g = p.groups[t];
+        for (int s = 0; s < g.M; ++s) {
+            const double* src = got + (t * BLEND_MAX_MEMBERS + (size_t)s) * PGRP_FIELDS;
+            double* row = out + (size_t)g.member[s] * PGRP_FIELDS;
+            for (int f = 0; f < BLEND_FIELDS; ++f) row[f] = src[f];
+            row[41] = src[41];
+            if (src[0] == 3.0 || src[0] == 4.0) {
+                for (int f = 0; f < 6; ++f) row[8 + f] = jobs[(size_t)g.member[s] * PFIT_JOB_FIELDS + 5 + f];
+            } else {
+                row[9] = src[9] + (double)g.x0; row[10] = src[10] + (double)g.y0;
+            }
+        }
+    }
 }
 
 void write_back(const double* got, const double* start, const int* win0, int width, int par, const int* rows, int nrows, double* out) {

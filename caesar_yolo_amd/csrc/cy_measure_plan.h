@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks, cy_fit_peak_groups): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -125,6 +125,33 @@ const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int 
 // of the plan, the centre back in image pixels, and for the kernel's status 3 or 4 the start exactly as given in `job`
 // ([PFIT_JOB_FIELDS]).
 void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, double* row);
+
+// cy_fit_peak_groups.  jobs as for plan_peak_fits, whose statuses (1 / 5), windows, clipped flags and kept-neighbour lists are taken
+// over (p.fits).  Two status 0 jobs e, f with equal sign are LINKED when D2 < Lm * Lm, Lm = link * max(R_e, R_f), D2 formed as
+// plan_peak_fits forms it; strict, symmetric, coincident centres are linked.  A pair is looked for from the side of its larger
+// radius (from the lower index when the radii are equal), in the stretch of the jobs sorted by column whose |cx_f - cx_e| is
+// below link * R_e, found by bisection: the cost per job is the number of jobs in such a band, not n.  A GROUP is a connected set
+// of the link graph (union-find); its id is its lowest job index, its members are taken in increasing job index (slot).  Per job:
+// group, size (members of its group), slot, nlinked (jobs directly linked to it) and status: 1 / 5 the planner's, 6 alone, 7 in a
+// group above BLEND_MAX_MEMBERS, 0 member of a group job.  groups: one PeakGroupJob per group with 2 .. BLEND_MAX_MEMBERS members,
+// in increasing id: the bounding box of the members' windows, per member its kept neighbours that are not members (indices, in
+// its own order), the starts relative to the group window, bkg and sign of slot 0.  job_of: [n] index into groups, -1 without one.
+// rows: [n][PGRP_FIELDS] what the host decides for every job: status 1 / 5 as peak_fit_row writes them (the window, fields 36 ..
+// 39, as -1); otherwise group, size and slot in fields 5 .. 7, the window of the group (the job's own for status 6), clipped (any
+// member's), nlinked, and for status 7 the start as given in fields 8 .. 13.  Returns the message of the first failed check, in
+// this order: those of plan_peak_fits up to max_iter, link not finite, <= 0 or > 2, a null pointer.
+struct PeakGroupPlan {
+    PeakFitPlan fits;
+    std::vector<int> group, size, slot, nlinked, status, job_of;
+    std::vector<PeakGroupJob> groups;
+    std::vector<double> rows;
+};
+const char* plan_peak_groups(const double* jobs, int n, double link, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakGroupPlan& p);
+
+// The rows of the members of every group job from the device's table `got` ([groups][BLEND_MAX_MEMBERS][PGRP_FIELDS]) into `out`
+// ([n][PGRP_FIELDS], already holding p.rows): fields 0 .. 35 and nexcluded taken over, the centre back in image pixels; a row that
+// was not fitted (status 3, 4) reports its start exactly as given in `jobs`.
+void peak_group_rows(const PeakGroupPlan& p, const double* jobs, const double* got, double* out);
 
 // Rows `rows[0 .. nrows)` of one job (source = row / DBL_MAX_COMP) from the device's table `got` into `out`, both [..][width]: the
 // centre (fields par + 1, par + 2) back in image pixels; a row that was not fitted (status 3, 4) reports its start exactly as given.

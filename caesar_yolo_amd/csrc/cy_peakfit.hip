@@ -31,13 +31,14 @@
 // Sums: float64 per lane over increasing window index, then the block reduction of cy_reduce.h, finished by thread 0: two calls
 // give the same bytes.
 #include "cy_lm.h"                      // gauss_terms, hidx, lm_solve, lm_trial, lm_iterate
+#include "cy_disc.h"                    // Disc, member: the membership test, shared with cy_peakgroup.hip
 
 #pragma clang fp contract(off)          // every product is rounded before it is added, as the float64 definition does
 
 namespace cy {
 namespace {
 
-constexpr int PF_T = 256, PF_NB = PFIT_NEIGH_MAX;
+constexpr int PF_T = 256, PF_NB = DISC_NB;
 constexpr int PF_SIDE_MAX = 2 * PFIT_RADIUS_MAX + 1;
 
 struct PSmem {
@@ -49,33 +50,6 @@ struct PSmem {
     RedSlots<PF_T, 2> cnt;              // the staging pass's: npix, nexcluded
     LmCtl ctl;
 };
-
-// what membership needs, all uniform: the window's first pixel and width, the job's centre and squared radius, its neighbours
-struct Disc {
-    int bx0, by0; unsigned W;
-    double cx, cy, r2;
-    int nn;
-    double ncx[PF_NB], ncy[PF_NB];
-};
-
-// window pixel i: inside the disc (in) and nearer to no kept neighbour than to the job's own centre (returned)
-__device__ __forceinline__ bool member(const Disc& d, const unsigned i, unsigned& wx, unsigned& wy, bool& in) {
-    wy = i / d.W; wx = i - wy * d.W;
-    const double qx = (double)(d.bx0 + (int)wx), qy = (double)(d.by0 + (int)wy);
-    const double ex = qx - d.cx, ey = qy - d.cy;
-    const double exx = ex * ex, eyy = ey * ey;
-    const double d2 = exx + eyy;
-    in = d2 <= d.r2;
-    bool mine = in;
-#pragma unroll
-    for (int k = 0; k < PF_NB; ++k) {
-        const double fx = qx - d.ncx[k], fy = qy - d.ncy[k];
-        const double fxx = fx * fx, fyy = fy * fy;
-        const double f2 = fxx + fyy;
-        mine = mine && (k >= d.nn || f2 >= d2);
-    }
-    return mine;
-}
 
 // F, g, H at pp (LDS, uniform) over the window; the totals land in s.tot (valid for thread 0 after the barrier inside)
 template <bool LDS>

@@ -23,7 +23,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_PEAKGROUP, STEP_COUNT };
 
 // Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
 // beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
@@ -100,7 +100,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1535,6 +1535,7 @@ static_assert(CY_APER_RINGS_MAX == APER_RINGS_MAX && CY_APER_RADIUS_MAX == APER_
               "header and kernel disagree on the aperture row");
 static_assert(CY_PFIT_JOB_FIELDS == PFIT_JOB_FIELDS && CY_PFIT_FIELDS == PFIT_FIELDS && CY_PFIT_RADIUS_MAX == PFIT_RADIUS_MAX &&
               CY_PFIT_NEIGH_MAX == PFIT_NEIGH_MAX && CY_PFIT_JOBS_MAX == PFIT_JOBS_MAX, "header and kernel disagree on the peak fit row");
+static_assert(CY_PGRP_FIELDS == PGRP_FIELDS && CY_PGRP_FIELDS == CY_BLEND_FIELDS + 8, "header and kernel disagree on the peak group row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1814,6 +1815,29 @@ int cy_fit_peaks(cy_ctx* c, const float* d_map, int MH, int MW, const double* h_
     return CY_OK;
 }
 
+int cy_fit_peak_groups(cy_ctx* c, const float* d_map, int MH, int MW, const double* h_jobs, int n, double link, int max_iter, double* h_out,
+                       void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    PeakGroupPlan p;
+    if (const char* msg = plan_peak_groups(h_jobs, n, link, max_iter, MH, MW, d_map != nullptr, h_out != nullptr, p)) return fail(c, CY_ERR_ARG, msg);
+    if (n == 0) return CY_OK;
+    std::vector<double> got(p.groups.size() * CY_BLEND_MAX_MEMBERS * CY_PGRP_FIELDS);
+    if (!p.groups.empty()) {
+        TimedLaunch t(c, stream);
+        PeakGroupArgs a{};
+        a.map = d_map; a.MH = MH; a.MW = MW; a.n = n; a.ngroups = (int)p.groups.size(); a.max_iter = max_iter;
+        a.jobs = t.upload(p.fits.jobs.data(), p.fits.jobs.size());
+        a.groups = t.upload(p.groups.data(), p.groups.size());
+        a.out = t.zeros<double>(got.size());                                   // the kernel writes the members' rows only
+        t.download(got.data(), a.out, got.size());
+        const int rc = t.run(STEP_PEAKGROUP, [&](hipStream_t s) { return launch_peak_groups(a, s); });
+        if (rc != CY_OK) return rc;                                            // h_out as it was
+    }
+    std::memcpy(h_out, p.rows.data(), p.rows.size() * sizeof(double));
+    peak_group_rows(p, h_jobs, got.data(), h_out);
+    return CY_OK;
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1832,6 +1856,7 @@ int cy_peaks_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(
 int cy_atrous_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_ATROUS, out_ms); }
 int cy_aperture_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_APERTURE, out_ms); }
 int cy_peakfit_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKFIT, out_ms); }
+int cy_peakgroup_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKGROUP, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

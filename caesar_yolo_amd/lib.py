@@ -40,6 +40,8 @@ APER_RING_NAMES = ("npix", "sum", "sumsq", "svar")
 CY_PFIT_JOB_FIELDS, CY_PFIT_FIELDS, CY_PFIT_RADIUS_MAX, CY_PFIT_NEIGH_MAX, CY_PFIT_JOBS_MAX = 11, 40, 256, 8, 1 << 20
 PFIT_JOB_NAMES = ("cx", "cy", "R", "bkg", "sign", "A", "x0", "y0", "a", "b", "c")
 PFIT_NAMES = FIT_NAMES + ("wx0", "wx1", "wy0", "wy1", "clipped", "nneigh", "crowded", "nexcluded")
+CY_PGRP_FIELDS = 44
+PGRP_NAMES = BLEND_NAMES + ("wx0", "wx1", "wy0", "wy1", "clipped", "nexcluded", "nlinked", "reserved")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -59,7 +61,7 @@ EXPORTS = [
     "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
     "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
     "cy_atrous_step", "cy_atrous_kernel_ms", "cy_aperture_sums", "cy_aperture_kernel_ms",
-    "cy_fit_peaks", "cy_peakfit_kernel_ms",
+    "cy_fit_peaks", "cy_peakfit_kernel_ms", "cy_fit_peak_groups", "cy_peakgroup_kernel_ms",
 ]
 
 
@@ -222,6 +224,8 @@ def load():
         "cy_aperture_kernel_ms": (C.c_int, [vp, dp]),
         "cy_fit_peaks": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_int, dp, vp]),
         "cy_peakfit_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_fit_peak_groups": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, dp, vp]),
+        "cy_peakgroup_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

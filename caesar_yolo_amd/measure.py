@@ -50,7 +50,12 @@ lib.APER_RING_NAMES, keys APERTURE_KEYS on every entry (annotate_apertures).  Ch
 --fit_peaks gives the entries of those lists a shape: `cy_fit_peaks` (HipDetector.fit_peaks) fits one elliptical Gaussian to the
 residual map on a disc around every entry (of the scale peaks: the strongest ones), a disc it shares with neighbouring entries by
 a nearest-centre rule; a hole is fitted with sign -1.  Raw rows lib.PFIT_NAMES, keys GFIT_KEYS on every entry
-(annotate_peak_fits).  Chain.run() calls Chain.peak_fits() last, so that the local background of the apertures is there when they ran.
+(annotate_peak_fits).  Chain.run() calls Chain.peak_fits() after the apertures, so that their local background is there when they ran.
+
+--fit_peak_groups (which implies --fit_peaks) then fits the entries of a list that lie closer than fit_peaks_link times their disc
+radius together: `cy_fit_peak_groups` (HipDetector.fit_peak_groups) fits the sum of two to four Gaussians on the union of their
+discs, started from the single fits.  Raw rows lib.PGRP_NAMES, keys GBLEND_KEYS on every entry (annotate_peak_groups).
+Chain.run() calls Chain.peak_groups() last.
 
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
@@ -74,7 +79,8 @@ def _fields(names):
 MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
 RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
 APER, APER_RING = _fields(L.APER_NAMES), _fields(L.APER_RING_NAMES)
-PFIT, PFIT_JOB = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES)
+PFIT, PFIT_JOB, PGRP = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES), _fields(L.PGRP_NAMES)
+_PFIT_JOB_PARAMS = [getattr(PFIT_JOB, k) for k in "A x0 y0 a b c".split()]
 _PFIT_PARAMS = [getattr(PFIT, k) for k in "A x0 y0 a b c".split()]
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
 _MOMENTS = ("S", "Sx", "Sy", "Sxx", "Syy", "Sxy")
@@ -107,6 +113,9 @@ APERTURE_KEYS = ("ap_status", "ap_clipped", "ap_radius", "ap_npix", "ap_sum", "a
 GFIT_KEYS = ("gfit_status", "gfit_niter", "gfit_npix", "gfit_nexcluded", "gfit_nneigh", "gfit_crowded", "gfit_clipped", "gfit_radius", "gfit_bkg",
              "gfit_chi2", "gfit_peak", "gfit_x", "gfit_y", "gfit_ra", "gfit_dec", "gfit_major", "gfit_minor", "gfit_pa", "gfit_flux", "gfit_peak_err",
              "gfit_x_err", "gfit_y_err", "gfit_flux_err")
+GBLEND_KEYS = ("gblend_group", "gblend_size", "gblend_slot", "gblend_status", "gblend_niter", "gblend_npix", "gblend_nexcluded", "gblend_chi2",
+               "gblend_peak", "gblend_x", "gblend_y", "gblend_ra", "gblend_dec", "gblend_major", "gblend_minor", "gblend_pa", "gblend_flux",
+               "gblend_peak_err", "gblend_x_err", "gblend_y_err", "gblend_flux_err")
 MAD_TO_SIGMA = 1.482602218505602   # 1 / Phi^-1(3/4): the standard deviation of a normal distribution in units of its MAD
 SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
@@ -914,6 +923,85 @@ def peak_fit_stats(rows):
             int((rows[:, PFIT.crowded] == 1.0).sum()))
 
 
+# ---- joint fits of neighbouring peaks (--fit_peak_groups)
+def peakgroup_config(config):
+    """link of --fit_peak_groups from a config dictionary (fit_peaks_link, default 1.5): two entries of a list are fitted together
+    when their centres are closer than link times the larger of their disc radii.  The default rests on the bias of the single
+    fits measured on clean pairs (R = 6, sigma 1.6): 0.85 px at 4 px apart, 0.31 px at 5, 0.04 px at 7, negligible at 9; with R = 6
+    it links entries closer than 9 px.  ValueError outside (0, 2]."""
+    link = float(config.get('fit_peaks_link', 1.5))
+    if not (math.isfinite(link) and 0.0 < link <= 2.0):
+        raise ValueError("fit_peaks_link must be in (0, 2]")
+    return link
+
+
+def wants_peak_groups(config):
+    """Whether a config asks for the joint fit of neighbouring entries of its peak lists (fit_peak_groups)."""
+    return bool(config.get('fit_peak_groups', False))
+
+
+def peak_group_jobs(jobs, rows):
+    """The jobs of cy_fit_peak_groups for one list: those of cy_fit_peaks (jobs, [n, CY_PFIT_JOB_FIELDS]) with the start of every job
+    whose cy_fit_peaks row (rows, [n, CY_PFIT_FIELDS]) has status 0 or 2 replaced by that row's parameters.  Both in the same pixel
+    frame, as blend_start() does for components."""
+    jobs = np.array(jobs, np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS)
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PFIT_FIELDS)
+    use = np.isin(rows[:, PFIT.status], _FITTED)
+    jobs[np.ix_(use, _PFIT_JOB_PARAMS)] = rows[np.ix_(use, _PFIT_PARAMS)]
+    return jobs
+
+
+def annotate_peak_groups(entries, rows, rms, sign, beam_area, wcs, origin=(0, 0), select=None):
+    """GBLEND_KEYS on every dict of `entries`, after annotate_peak_fits().  rows: [m, CY_PGRP_FIELDS] rows of cy_fit_peak_groups with
+    x0, y0 in catalog coordinates, rms: [m] the noise at the peak pixels; row t belongs to entries[select[t]] (select None: entry
+    t).  An entry without a row (a scale peak that is not the strongest of its place) gets every key None.
+      gblend_group   the index in `entries` of the group's first member (the entry's own when it is alone); gblend_size, gblend_slot,
+                     gblend_status, gblend_niter, gblend_npix, gblend_nexcluded   as in the row (ints); group, size and slot are None
+                     with status 1 or 5, which have no group
+      gblend_chi2 .. gblend_flux_err   as their gfit_ namesakes, from the member's parameters of the joint fit (_gaussian_keys), the
+                     errors from rms^2 times the member's block of C (blend_covariance); gblend_peak and gblend_flux carry the sign
+    Status 6 (the entry is alone): the keys from gblend_chi2 on repeat the entry's gfit_ values.  Status 1, 3, 4, 5 or 7: they are
+    None.  -> entries."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PGRP_FIELDS)
+    rms = np.asarray(rms, np.float64).reshape(-1)
+    select = list(range(len(entries))) if select is None else [int(i) for i in select]
+    assert rows.shape[0] == rms.shape[0] == len(select)
+    ox, oy = float(origin[0]), float(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    values = GBLEND_KEYS[GBLEND_KEYS.index("gblend_chi2"):]
+    for d in entries:
+        d.update(dict.fromkeys(GBLEND_KEYS))
+    for i, r, noise in zip(select, rows, rms):
+        d = entries[i]
+        st = int(r[PGRP.status])
+        d["gblend_status"], d["gblend_niter"], d["gblend_npix"], d["gblend_nexcluded"] = st, int(r[PGRP.niter]), int(r[PGRP.npix]), int(r[PGRP.nexcluded])
+        if st not in (1, 5):
+            d["gblend_group"], d["gblend_size"], d["gblend_slot"] = select[int(r[PGRP.group])], int(r[PGRP.nmembers]), int(r[PGRP.slot])
+        if st == 6:
+            for k in values:
+                d[k] = d.get("gfit_" + k[len("gblend_"):])
+        elif st in (0, 2):
+            noise = float(noise) if math.isfinite(noise) and noise > 0.0 else 0.0
+            _gaussian_keys(d, "gblend_", r, PGRP.F, _BLEND_PARAMS, blend_covariance, noise, ba, wcs, ox, oy)
+            if sign < 0:
+                d["gblend_peak"] = -d["gblend_peak"]
+                if d["gblend_flux"] is not None:
+                    d["gblend_flux"] = -d["gblend_flux"]
+    return entries
+
+
+def peak_group_stats(rows):
+    """(jobs, members, converged, mean niter, largest niter, groups above CY_BLEND_MAX_MEMBERS) over rows [n, CY_PGRP_FIELDS] of
+    cy_fit_peak_groups: a group job (status 0, 2, 3 or 4) is counted once, on its slot-0 row, as is a group above the limit (status
+    7); members: the rows of the group jobs; the iterations over the fitted jobs (status 0 or 2)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PGRP_FIELDS)
+    job = np.isin(rows[:, PGRP.status], (0.0, 2.0, 3.0, 4.0))
+    first = rows[:, PGRP.slot] == 0.0
+    it = rows[first & np.isin(rows[:, PGRP.status], _FITTED), PGRP.niter]
+    return (int((job & first).sum()), int(job.sum()), int((first & (rows[:, PGRP.status] == 0.0)).sum()), float(it.mean()) if it.size else 0.0,
+            int(it.max()) if it.size else 0, int((first & (rows[:, PGRP.status] == 7.0)).sum()))
+
+
 def _read_at(m, iy, ix):
     """m[iy, ix] of a device map (or a host array) as numpy float64: one indexed read."""
     if hasattr(m, "is_cuda"):
@@ -1062,11 +1150,12 @@ def plan(config):
     and blend the fits, the fits the components, the components the islands, the islands the first measurement; bkg_map or
     save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
     step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
-    (Chain.scale_peaks, no step either) implies exactly the same, and so do peak_apertures (Chain.apertures) and fit_peaks
-    (Chain.peak_fits), which measure on the residual map with the rms map of the mesh but turn no search on."""
+    (Chain.scale_peaks, no step either) implies exactly the same, and so do peak_apertures (Chain.apertures), fit_peaks
+    (Chain.peak_fits) and fit_peak_groups (Chain.peak_groups, which implies fit_peaks), which measure on the residual map with the
+    rms map of the mesh but turn no search on."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
-    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config)
+    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config) or wants_peak_groups(config)
     residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
@@ -1102,7 +1191,9 @@ class Chain(object):
         self.save_scales = bool(c.get('save_scale_maps', False))
         self.want_apertures = wants_apertures(c)
         self.ap_unit, self.ap_factors, self.ap_annulus = aperture_config(c) if self.want_apertures else (1.0, (), 0.0)
-        self.want_peak_fits = wants_peak_fits(c)
+        self.want_peak_groups = wants_peak_groups(c)
+        self.pg_link = peakgroup_config(c) if self.want_peak_groups else 1.5
+        self.want_peak_fits = wants_peak_fits(c) or self.want_peak_groups
         self.pf_radius, self.pf_sigma, self.pf_max_iter = peakfit_config(c) if self.want_peak_fits else (6.0, 1.5, 64)
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
@@ -1118,7 +1209,8 @@ class Chain(object):
         self.peak_list = self.hole_list = self.peak_stats = None
         self.scale_list = self.scale_stats = self.scale_levels = self.scale_planes = self.scale_rows = None
         self.aperture_rows = self.aperture_stats = None
-        self.peakfit_rows = self.peakfit_jobs = self.peakfit_select = self.peakfit_stats = None
+        self.peakfit_rows = self.peakfit_jobs = self.peakfit_select = self.peakfit_stats = self.peakfit_rms = None
+        self.peakgroup_rows = self.peakgroup_jobs = self.peakgroup_stats = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -1322,7 +1414,7 @@ class Chain(object):
         {"peakfit_ms", "peakfit_kernel_ms" (summed over the calls), "peakfit_jobs", "peakfit_converged", "peakfit_niter_mean",
         "peakfit_niter_max", "peakfit_crowded"}."""
         t1 = time.time()
-        self.peakfit_rows, self.peakfit_jobs, self.peakfit_select = {}, {}, {}
+        self.peakfit_rows, self.peakfit_jobs, self.peakfit_select, self.peakfit_rms = {}, {}, {}, {}
         st = {"peakfit_kernel_ms": 0.0}
         lists = [(k, v, sg) for k, v, sg in (("residual_peaks", self.peak_list, 1.0), ("residual_holes", self.hole_list, -1.0),
                                              ("residual_scale_peaks", self.scale_list, 1.0)) if v]
@@ -1342,15 +1434,46 @@ class Chain(object):
             has = ~np.isin(rows[:, PFIT.status], (1.0, 5.0))
             moved = self._moved(rows, has, (PFIT.x0, PFIT.wx0, PFIT.wx1), (PFIT.y0, PFIT.wy0, PFIT.wy1))
             annotate_peak_fits(entries, moved, jobs, rms, sign, self.beam_area, self.wcs, self.wcs_origin, select)
-            self.peakfit_rows[name], self.peakfit_jobs[name], self.peakfit_select[name] = rows, jobs, select
+            self.peakfit_rows[name], self.peakfit_jobs[name], self.peakfit_select[name], self.peakfit_rms[name] = rows, jobs, select, rms
             every.append(rows)
         every = np.concatenate(every) if every else np.zeros((0, L.CY_PFIT_FIELDS), np.float64)
         (st["peakfit_jobs"], st["peakfit_converged"], st["peakfit_niter_mean"], st["peakfit_niter_max"], st["peakfit_crowded"]) = peak_fit_stats(every)
         st["peakfit_ms"] = 1e3 * (time.time() - t1)
         self.peakfit_stats = st
 
+    def peak_groups(self):
+        """After peak_fits(): per non-empty list peak_group_jobs() (the jobs of peak_fits() started from its rows), one
+        cy_fit_peak_groups call on .resid, the rows moved to catalog coordinates, then annotate_peak_groups().  Leaves .peakgroup_rows
+        and .peakgroup_jobs (as the library saw them, in the pixels of img_dev) and .peakgroup_stats {"peakgroup_ms",
+        "peakgroup_kernel_ms" (summed over the calls that launched), "peakgroup_jobs", "peakgroup_members", "peakgroup_converged",
+        "peakgroup_niter_mean", "peakgroup_niter_max", "peakgroup_over_limit"}."""
+        t1 = time.time()
+        self.peakgroup_rows, self.peakgroup_jobs = {}, {}
+        st = {"peakgroup_kernel_ms": 0.0}
+        lists = {"residual_peaks": (self.peak_list, 1.0), "residual_holes": (self.hole_list, -1.0), "residual_scale_peaks": (self.scale_list, 1.0)}
+        every = []
+        for name, single in self.peakfit_rows.items():
+            entries, sign = lists[name]
+            select = self.peakfit_select[name]
+            jobs = peak_group_jobs(self.peakfit_jobs[name], single)
+            rows = np.zeros((0, L.CY_PGRP_FIELDS), np.float64)
+            if select:
+                rows = self.det.fit_peak_groups(self.resid, jobs, link=self.pg_link, max_iter=self.pf_max_iter)
+                if np.isin(rows[:, PGRP.status], (0.0, 2.0, 3.0, 4.0)).any():       # a call without a group job launches nothing
+                    st["peakgroup_kernel_ms"] += max(self.det.peakgroup_kernel_ms(), 0.0)
+            has = ~np.isin(rows[:, PGRP.status], (1.0, 5.0))
+            moved = self._moved(rows, has, (PGRP.x0, PGRP.wx0, PGRP.wx1), (PGRP.y0, PGRP.wy0, PGRP.wy1))
+            annotate_peak_groups(entries, moved, self.peakfit_rms[name], sign, self.beam_area, self.wcs, self.wcs_origin, select)
+            self.peakgroup_rows[name], self.peakgroup_jobs[name] = rows, jobs
+            every.append(rows)
+        every = np.concatenate(every) if every else np.zeros((0, L.CY_PGRP_FIELDS), np.float64)
+        (st["peakgroup_jobs"], st["peakgroup_members"], st["peakgroup_converged"], st["peakgroup_niter_mean"], st["peakgroup_niter_max"],
+         st["peakgroup_over_limit"]) = peak_group_stats(every)
+        st["peakgroup_ms"] = 1e3 * (time.time() - t1)
+        self.peakgroup_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures() and peak_fits(), each when the
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures(), peak_fits() and peak_groups(), each when the
         config asks for it and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
@@ -1394,6 +1517,10 @@ class Chain(object):
             self.peak_fits()
             if stats is not None:
                 stats.update(self.peakfit_stats)
+        if self.want_peak_groups and "residual" in steps:
+            self.peak_groups()
+            if stats is not None:
+                stats.update(self.peakgroup_stats)
         return self
 
     def save_maps(self, catalog_path):

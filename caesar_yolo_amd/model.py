@@ -629,6 +629,25 @@ class HipDetector(object):
         """Kernel time of the last fit_peaks call that launched in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_peakfit_kernel_ms)
 
+    # ---- joint fits of groups of peaks (neighbouring entries of a peak list fitted together)
+    def fit_peak_groups(self, map_dev, jobs, link=1.5, max_iter=64):
+        """The sum of 2 .. CY_BLEND_MAX_MEMBERS elliptical Gaussians per group of linked jobs on the union of their discs
+        (cy_fit_peak_groups).  map_dev and jobs as fit_peaks, the starts usually that call's results; two jobs of equal sign are
+        linked when their centres are closer than link times the larger of their radii.  -> numpy float64 [n, CY_PGRP_FIELDS]
+        (lib.PGRP_NAMES), one row per job."""
+        MH, MW = self._image_2d(map_dev, "fit_peak_groups")
+        jobs = np.ascontiguousarray(np.asarray(jobs, np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS))
+        n = jobs.shape[0]
+        out = np.zeros((n, L.CY_PGRP_FIELDS), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_fit_peak_groups(self.ctx, self._p(map_dev), MH, MW, jobs.ctypes.data_as(dp), n, float(link), int(max_iter),
+                                              out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def peakgroup_kernel_ms(self):
+        """Kernel time of the last fit_peak_groups call that launched in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_peakgroup_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

@@ -720,6 +720,44 @@ int cy_fit_peaks(cy_ctx* ctx, const float* d_map, int MH, int MW, const double* 
 /* milliseconds the kernel of the last cy_fit_peaks call that launched one took (hipEvents around the launch); -1 before it */
 int cy_peakfit_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- joint fits of groups of peaks (an addition: neighbouring peaks are fitted together, not on halves of their shared pixels) --
+ * The sum of M elliptical Gaussians fitted to the union of the discs of M linked jobs on d_map.  h_jobs: as cy_fit_peaks, the start
+ * usually that call's result.  Everything in float64, every product and sum rounded on its own.
+ *   planner    per job the status (1 / 5), the window, clipped and the kept-neighbour list are those of cy_fit_peaks
+ *   link       two planner-status-0 jobs e, f with equal sign are LINKED when D2 < Lm * Lm, Lm = link * max(R_e, R_f), D2 =
+ *              (cx_f - cx_e)^2 + (cy_f - cy_e)^2 formed as for the neighbours.  Strict; symmetric; coincident centres are linked.
+ *              nlinked: the jobs directly linked to a job
+ *   group      a connected set of the link graph.  Its id is its lowest job index; its M members are taken in increasing job
+ *              index, a member's slot is its position in that order
+ *   job        one per group with 2 <= M <= CY_BLEND_MAX_MEMBERS.  Its window is the bounding box of the members' windows.
+ *              Window pixel q belongs to the group's pixel set when for some member e: d2_e <= R_e * R_e, and d2_f >= d2_e for
+ *              every kept neighbour f of e that is NOT a member of the group.  Jobs outside the group keep their nearest-centre
+ *              share; inside the group nothing is divided.  npix: the valid pixels of the set; nexcluded: the valid pixels inside
+ *              some member's disc that are in no member's share
+ *   data       y = sign * ((double)v - bkg) with bkg (and sign) of the member in slot 0
+ *   model and algebra   the sums (w = (r, J_0 .. J_{P-1}), upper triangle of w^T w row-major), the solve, the iteration, `small`,
+ *              the convergence test and the covariance blocks (C = inv(H), each member's own 6 x 6 block) are word for word those
+ *              of cy_fit_blends.  The job's LIST is every pixel of the group window in increasing window index; a pixel that is
+ *              not a valid member keeps its position and contributes nothing; every sum is one plain sequential sum in list
+ *              order.  Two calls give the same bytes.  The fit runs relative to the window's first pixel and reports image
+ *              pixels; A is reported positive
+ *   status     tested in this order: 1 and 5 as cy_fit_peaks; 6 the job is alone (no launch, group = own index, nmembers = 1,
+ *              the job's own window and clipped flag); 7 the group has more than CY_BLEND_MAX_MEMBERS members (the start reported
+ *              as given); 4 some member's start is not admissible (tested before 3); 3 npix < 6 M + 1; 0 converged; 2 max_iter
+ *              or the lambda limit reached.  3, 4 and 7 report the starts bit for bit, niter = 0, F, lambda, cov_ok and C are 0
+ * Row i of h_out, CY_PGRP_FIELDS float64: [0 .. 35] the fields of a cy_fit_blends row (`group` is a job index), [36..39] wx0 wx1
+ * wy0 wy1 of the group window, [40] clipped (any member's), [41] nexcluded, [42] nlinked, [43] 0.  Rows of statuses 1 and 5: the
+ * status, the window as -1 and zeros elsewhere.
+ * One launch: one workgroup of 256 threads per group job; a group window of up to 8192 pixels keeps its members' values in LDS, a
+ * larger one evaluates membership again in every sweep.  Synchronous on `stream`; needs no loaded weights; the map is only read.
+ * CY_ERR_ARG with a message, nothing launched and h_out untouched, checked in the order of cy_fit_peaks, with link not finite,
+ * <= 0 or > 2 after max_iter.  n == 0, or no group job: CY_OK, nothing launched. */
+#define CY_PGRP_FIELDS 44
+int cy_fit_peak_groups(cy_ctx* ctx, const float* d_map, int MH, int MW, const double* h_jobs /* [n][CY_PFIT_JOB_FIELDS], as cy_fit_peaks */,
+                       int n, double link, int max_iter, double* h_out /* [n][CY_PGRP_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_fit_peak_groups call that launched one took (hipEvents around the launch); -1 before it */
+int cy_peakgroup_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

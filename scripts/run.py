@@ -75,6 +75,10 @@ Differences that come with the MI355X engine:
              pixels times the entry's step that it shares with neighbouring entries by a nearest-centre rule, from a circular start
              of --fit_peaks_sigma (default 1.5) pixels, at most --fit_peaks_max_iter (default 64) iterations; holes are fitted with
              a sign: gfit_status .. gfit_flux_err per entry (cy_fit_peaks; DESIGN.md "Peak fits").
+  --fit_peak_groups  (new; implies --fit_peaks) the entries of a list whose centres are closer than --fit_peaks_link (default 1.5, at
+             most 2) times the larger of their disc radii are fitted together on the GPU, two to four Gaussians on the union of
+             their discs, started from the single fits; larger groups keep their single fits: gblend_group, gblend_size,
+             gblend_slot, gblend_status .. gblend_flux_err per entry (cy_fit_peak_groups; DESIGN.md "Peak groups").
 """
 import argparse
 import logging
@@ -86,7 +90,7 @@ from caesar_yolo_amd.config import CONFIG                                     # 
 from caesar_yolo_amd.preprocessing import (DataPreprocessor, BkgSubtractor, SigmaClipShifter, SigmaClipper, ChanResizer,  # noqa: E402
                                            ZScaleTransformer, Chan3Trasformer, MinMaxNormalizer)
 from caesar_yolo_amd.inference import SFinder                                 # noqa: E402
-from caesar_yolo_amd.measure import aperture_config, peakfit_config, plan, wants_peaks, wants_scales  # noqa: E402
+from caesar_yolo_amd.measure import aperture_config, peakfit_config, peakgroup_config, plan, wants_peaks, wants_scales  # noqa: E402
 from caesar_yolo_amd.model import YOLO                                        # noqa: E402
 
 logging.basicConfig(format="%(asctime)-15s %(levelname)s - %(message)s", datefmt='%Y-%m-%d %H:%M:%S')
@@ -230,7 +234,17 @@ def parse_args(argv=None):
                    help='sigma in pixels of the circular start at step 1; a scale peak multiplies it by its step (with --fit_peaks)')
     p.add_argument('--fit_peaks_max_iter', dest='fit_peaks_max_iter', type=int, default=64,
                    help='iterations of a peak fit at most, 1..256 (with --fit_peaks)')
+    p.add_argument('--fit_peak_groups', dest='fit_peak_groups', action='store_true',
+                   help='fit neighbouring entries of a peak list jointly, two to four Gaussians on the union of their discs (implies --fit_peaks)')
+    p.add_argument('--fit_peaks_link', dest='fit_peaks_link', type=float, default=1.5,
+                   help='entries closer than this times the larger of their disc radii are fitted together, in (0, 2] (with --fit_peak_groups)')
     args = p.parse_args(argv)
+    if args.fit_peak_groups:
+        try:
+            peakgroup_config(vars(args))
+        except ValueError as e:
+            p.error("--fit_peak_groups: %s" % e)
+        args.fit_peaks = True                                 # the joint fits start from the single ones
     if args.fit_peaks:
         try:
             peakfit_config(vars(args))
@@ -336,7 +350,7 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
                 'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps',
                 'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus',
-                'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter')
+                'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter', 'fit_peak_groups', 'fit_peaks_link')
 
 
 def measure_config(args):

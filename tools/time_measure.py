@@ -2,7 +2,7 @@
 seeded:l:5, zscale + minmax, 512-px tiles at step 0.8) in ONE process, switches off / --measure_sources / --measure_islands
 alternating, `--runs` timed runs each after a warm-up.
 
-    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--no-apertures] [--no-peakfits] [--only a,b] [--host-ref]
+    python tools/time_measure.py [--size 16384] [--runs 3] [--ring 8] [--off-only] [--no-islands] [--no-bkg] [--no-deblend] [--no-fit] [--no-blend] [--no-residual] [--no-peaks] [--no-scales] [--no-apertures] [--no-peakfits] [--no-peakgroups] [--only a,b] [--host-ref]
 
 Per run: SFinder.run_parallel's own wall time (image ingest, detect pass, gather, catalog, measurement, files).  With the switch on
 also the measurement step's wall time (resident image looked up or uploaded + kernel + copies + annotate), the kernel's time
@@ -30,6 +30,10 @@ ones beside the scales_ and peaks_ kernel times of the same runs); apertures_add
 Unless --no-peakfits (or --no-apertures, --no-scales, --no-residual) is given there is a variant `peakfits`, the flags of `apertures` plus
 --fit_peaks (peakfit_ms, peakfit_kernel_ms summed over the calls, the numbers of jobs, converged and crowded ones and the iterations);
 peakfits_added_ms is its run time over that of the `apertures` variant of the same runs.
+Unless --no-peakgroups (or --no-peakfits, ..) is given there is a variant `peakgroups`, the flags of `peakfits` plus --fit_peak_groups
+(peakgroup_ms, peakgroup_kernel_ms summed over the calls beside peakfit_kernel_ms of the same runs, the numbers of group jobs, members,
+converged jobs and groups above the member limit, the iterations, and peakgroup_groups: the groups of the catalog counted by size and
+status); peakgroups_added_ms is its run time over that of the `peakfits` variant of the same runs.
 --only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
@@ -136,6 +140,7 @@ def main():
     ap.add_argument("--no-scales", action="store_true")
     ap.add_argument("--no-apertures", action="store_true")
     ap.add_argument("--no-peakfits", action="store_true")
+    ap.add_argument("--no-peakgroups", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
@@ -149,6 +154,14 @@ def main():
         rc = orig(self)
         seen.append(dict({k: v for k, v in self.stats.items() if isinstance(v, (int, float))}, run_ms=1e3 * self.runtime,
                          sources=len(self.sources["sources"]), kernel_ms=self.stats.get("measure_kernel_ms")))
+        if "peakgroup_jobs" in self.stats:                  # the groups by size and status, counted on their first members
+            groups = {}
+            for lst in ("residual_peaks", "residual_holes", "residual_scale_peaks"):
+                for e in self.sources.get(lst) or []:
+                    if e.get("gblend_slot") == 0:
+                        key = "size %d status %d" % (e["gblend_size"], e["gblend_status"])
+                        groups[key] = groups.get(key, 0) + 1
+            seen[-1]["peakgroup_groups"] = dict(sorted(groups.items()))
         return rc
     inference.SFinder.run_parallel = timed
     res = {"size": args.size, "runs": args.runs, "ring": args.ring}
@@ -188,6 +201,11 @@ def main():
                                   ("apertures_ms", "aperture_kernel_ms", "peakfit_ms", "peakfit_kernel_ms"),
                                   ("peaks_kept", "scales_kept", "scales_strongest", "peakfit_jobs", "peakfit_converged", "peakfit_niter_mean", "peakfit_niter_max",
                                    "peakfit_crowded")),
+                     "peakgroups": (["--fit_blends", "--residual_map", "--residual_peaks", "--residual_scales=4", "--peak_apertures", "--fit_peaks",
+                                     "--fit_peak_groups"],
+                                    ("peakfit_ms", "peakfit_kernel_ms", "peakgroup_ms", "peakgroup_kernel_ms"),
+                                    ("peakfit_jobs", "peakfit_crowded", "peakgroup_jobs", "peakgroup_members", "peakgroup_converged", "peakgroup_niter_mean",
+                                     "peakgroup_niter_max", "peakgroup_over_limit", "peakgroup_groups")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
@@ -197,6 +215,8 @@ def main():
                     "apertures": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures,
                     "peakfits": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
                                  args.no_peakfits),
+                    "peakgroups": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
+                                   args.no_peakfits or args.no_peakgroups),
                     "islands": args.no_islands}
             if args.only:
                 skip.update({name: True for name in table if name not in args.only.split(",")})
@@ -234,6 +254,8 @@ def main():
                 res["apertures_added_ms"] = res["apertures"]["run_ms_median"] - res["scales"]["run_ms_median"]
             if "peakfits" in got and "apertures" in got:
                 res["peakfits_added_ms"] = res["peakfits"]["run_ms_median"] - res["apertures"]["run_ms_median"]
+            if "peakgroups" in got and "peakfits" in got:
+                res["peakgroups_added_ms"] = res["peakgroups"]["run_ms_median"] - res["peakfits"]["run_ms_median"]
             if "scales" in got:
                 res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:

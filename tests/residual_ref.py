@@ -97,14 +97,20 @@ def valid(img):
     return (img != 0) & np.isfinite(img)
 
 
-def model_map(comp, rows, MH, MW, nudge=0):
-    """The float64 model [MH, MW]."""
+def model_map(comp, rows, MH, MW, nudge=0, origin=(0, 0)):
+    """The float64 model [MH, MW].  origin = (y0, x0): the map is the crop [y0, y0 + MH) x [x0, x0 + MW) of the image that comp and
+    rows (rectangles() on the whole image) speak of; every pixel is computed from its true coordinates, so the crop of the full
+    model and the model of the crop are the same numbers."""
     comp = np.asarray(comp, np.float64).reshape(-1, 6)
     model = np.zeros((MH, MW), np.float64)
+    oy, ox = int(origin[0]), int(origin[1])
     for p, r in zip(comp, rows):
         if r[0] in (1.0, 3.0):
             continue
         sx0, sx1, sy0, sy1 = (int(v) for v in r[1:5])
+        sx0, sx1, sy0, sy1 = max(sx0, ox), min(sx1, ox + MW - 1), max(sy0, oy), min(sy1, oy + MH - 1)
+        if sx1 < sx0 or sy1 < sy0:
+            continue
         A, x0, y0, a, b, c = (float(v) for v in p)
         u = np.arange(sx0, sx1 + 1, dtype=np.float64)[None, :] - x0
         v = np.arange(sy0, sy1 + 1, dtype=np.float64)[:, None] - y0
@@ -112,16 +118,18 @@ def model_map(comp, rows, MH, MW, nudge=0):
             e = np.exp(-0.5 * (((a * u) * u + ((2.0 * b) * u) * v) + (c * v) * v))
             for _ in range(abs(nudge)):
                 e = np.nextafter(e, np.inf if nudge > 0 else -np.inf)
-            model[sy0:sy1 + 1, sx0:sx1 + 1] += A * e
+            model[sy0 - oy:sy1 + 1 - oy, sx0 - ox:sx1 + 1 - ox] += A * e
     return model
 
 
-def render(img, comp, nsigma, bkg=None, nudge=0):
-    """-> (rows [m, 8], model float64 [MH, MW], resid float64 [MH, MW]); what the device stores is their fp32 rounding."""
+def render(img, comp, nsigma, bkg=None, nudge=0, origin=(0, 0), full=None):
+    """-> (rows [m, 8], model float64 [MH, MW], resid float64 [MH, MW]); what the device stores is their fp32 rounding.
+    origin, full: img (and bkg) is the crop at origin = (y0, x0) of an image of shape full = (MH, MW); comp and rows stay in that
+    image's coordinates (model_map)."""
     img = np.asarray(img, np.float32)
     MH, MW = img.shape
-    rows = rectangles(comp, nsigma, MH, MW)
-    model = model_map(comp, rows, MH, MW, nudge)
+    rows = rectangles(comp, nsigma, *(full or (MH, MW)))
+    model = model_map(comp, rows, MH, MW, nudge, origin)
     ok = valid(img)
     b = np.zeros((MH, MW), np.float64) if bkg is None else np.asarray(bkg, np.float32).astype(np.float64)
     with np.errstate(all="ignore"):
@@ -181,3 +189,16 @@ def residual_stats(img, model, boxes, bkg, masks):
             j = int(np.argmax(ar))                            # the first maximum in row-major order
             out[i, 7], out[i, 8], out[i, 9] = ar.flat[j], x0 + j % w, y0 + j // w
     return out, ab
+
+
+def compare_stats(got, ref, ab, names):
+    """The rule of the GPU tests for rows of cy_measure_residuals against residual_stats(): status, the two counts, the largest
+    |residual| with its position and the reserved field equal; the five sums within 2 m 2^-53 sum|t_i| of the reference, m the
+    number of their terms (both sides add the same float64 terms in some order)."""
+    assert got.shape == ref.shape
+    for i, nm in enumerate(names):
+        g, r = got[i], ref[i]
+        assert np.array_equal(g[[0, 1, 2, 7, 8, 9, 11]], r[[0, 1, 2, 7, 8, 9, 11]]), "%s: %s, reference %s" % (nm, g, r)
+        for f, t, cnt in ((3, 0, r[1]), (4, 1, r[1]), (5, 2, r[2]), (6, 3, r[2]), (10, 4, r[2])):
+            bound = 2.0 * cnt * 2.0 ** -53 * ab[i, t]
+            assert abs(g[f] - r[f]) <= bound, "%s: field %d %r, reference %r, bound %g" % (nm, f, g[f], r[f], bound)

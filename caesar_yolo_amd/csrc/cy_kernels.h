@@ -407,6 +407,16 @@ struct PeakGroupArgs {
 };
 hipError_t launch_peak_groups(const PeakGroupArgs& a, hipStream_t s);
 
+// ---- residuals on the discs of given jobs (cy_disc_residual.hip) -----------------------------------------
+// DRES_FIELDS, PeakFitJob: cy_measure_jobs.h; the jobs: plan_peak_fits (cy_measure_plan.h)
+struct DiscResidualArgs {
+    const float* map; const float* model; int MH, MW;      // model may be null; MH * MW < 2^31
+    const PeakFitJob* jobs; int n;  // the whole job table: a neighbour is named by its index in it
+    const int* run; int nrun;       // the jobs that are measured, one workgroup each: 1 <= nrun <= n <= PFIT_JOBS_MAX
+    double* out;                    // [nrun][DRES_FIELDS]: workgroup t writes every field of row t
+};
+hipError_t launch_disc_residuals(const DiscResidualArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

@@ -1,5 +1,5 @@
 // Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip, cy_aperture.hip,
-// cy_peakfit.hip, cy_peakgroup.hip) and the
+// cy_peakfit.hip, cy_peakgroup.hip, cy_disc_residual.hip) and the
 // host-side planner that fills them (cy_measure_plan.cpp).  No HIP include: the planner also builds as plain C++.
 #pragma once
 
@@ -41,6 +41,7 @@ constexpr int PFIT_RADIUS_MAX = 256;           // CY_PFIT_RADIUS_MAX: largest di
 constexpr int PFIT_NEIGH_MAX = 8;              // CY_PFIT_NEIGH_MAX: neighbours a job shares its disc with
 constexpr int PFIT_JOBS_MAX = 1 << 20;         // CY_PFIT_JOBS_MAX: one workgroup per fitted job, the grid in x only
 constexpr int PGRP_FIELDS = 44;                // CY_PGRP_FIELDS: the 36 fields of a blend row, wx0 wx1 wy0 wy1 clipped nexcluded nlinked 0
+constexpr int DRES_FIELDS = 16;                // CY_DRES_FIELDS: status npix nexcluded sum sumsq maxabs x_max y_max model_sum 0, wx0 wx1 wy0 wy1 clipped nneigh
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list

@@ -199,7 +199,7 @@ const char* plan_blend(const FitInputs& in, BlendPlan& p) {
         });
 }
 
-const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p) {
+const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p, bool signed_amp) {
 #pragma clang fp contract(off)          // a*c - b*b: both products are rounded before the subtraction, whatever the build's default
     p.rows.clear(); p.rect.clear(); p.tile_off.clear(); p.tile_list.clear();
     p.ntx = (MW + RND_TILE - 1) / RND_TILE; p.nty = (MH + RND_TILE - 1) / RND_TILE;
@@ -228,7 +228,7 @@ const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW
         const double a = q[3], b = q[4], c = q[5];
         const double ac = a * c, bb = b * b;
         const double det = ac - bb;
-        if (!(fin && q[0] > 0.0 && a > 0.0 && c > 0.0 && det > 0.0)) { row[0] = 1.0; continue; }
+        if (!(fin && (signed_amp ? q[0] != 0.0 : q[0] > 0.0) && a > 0.0 && c > 0.0 && det > 0.0)) { row[0] = 1.0; continue; }
         double hx = std::ceil(nsigma * std::sqrt(c / det)), hy = std::ceil(nsigma * std::sqrt(a / det));
         bool capped = false;
         if (!(hx <= (double)RND_HALF_MAX)) { hx = (double)RND_HALF_MAX; capped = true; }      // a half-width that is not finite is above the cap
@@ -458,6 +458,19 @@ void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, dou
     }
     row[32] = (double)j.x0; row[33] = (double)j.x1; row[34] = (double)j.y0; row[35] = (double)j.y1;
     row[36] = (double)j.clipped; row[37] = (double)j.nneigh; row[38] = (double)j.crowded;
+}
+
+void disc_residual_row(const PeakFitJob& j, const double* got, double* row) {
+    for (int f = 0; f < DRES_FIELDS; ++f) row[f] = 0.0;
+    if (!got) {
+        row[0] = (double)j.status;
+        row[6] = row[7] = -1.0;
+        row[10] = row[11] = row[12] = row[13] = -1.0;
+        return;
+    }
+    for (int f = 0; f < DRES_FIELDS; ++f) row[f] = got[f];
+    row[10] = (double)j.x0; row[11] = (double)j.x1; row[12] = (double)j.y0; row[13] = (double)j.y1;
+    row[14] = (double)j.clipped; row[15] = (double)j.nneigh;
 }
 
 const char* plan_peak_groups(const double* jobs, int n, double link, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakGroupPlan& p) {

@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks, cy_fit_peak_groups): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks, cy_fit_peak_groups, cy_disc_residuals): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -58,7 +58,8 @@ struct RenderPlan {
     std::vector<int> tile_list;
     int ntx = 0, nty = 0;
 };
-const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p);
+// signed_amp (cy_render_signed_gaussians): a component is admissible with A < 0 too (A != 0 in place of A > 0); nothing else differs.
+const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p, bool signed_amp = false);
 
 // cy_measure_residuals: the box windows and checked mask offsets, as plan_islands gives them (off[i][0] is ISL_OFF_TOO_LARGE for a
 // window above ISL_MAX_AREA pixels, off[i][1] the window's first mask byte)
@@ -125,6 +126,12 @@ const char* plan_peak_fits(const double* jobs, int n, int max_iter, int MH, int 
 // of the plan, the centre back in image pixels, and for the kernel's status 3 or 4 the start exactly as given in `job`
 // ([PFIT_JOB_FIELDS]).
 void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, double* row);
+
+// Row [DRES_FIELDS] of cy_disc_residuals for job j of plan_peak_fits, which that entry reuses as it stands (max_iter 1; the start of a
+// job is planned and ignored).  A job the planner turned away (status 1 or 5, got == null): the status, the window and the
+// position of the largest |r| as -1 and zeros elsewhere.  Otherwise `got` is the row the kernel wrote: taken over, with the window,
+// clipped and nneigh of the plan.
+void disc_residual_row(const PeakFitJob& j, const double* got, double* row);
 
 // cy_fit_peak_groups.  jobs as for plan_peak_fits, whose statuses (1 / 5), windows, clipped flags and kept-neighbour lists are taken
 // over (p.fits).  Two status 0 jobs e, f with equal sign are LINKED when D2 < Lm * Lm, Lm = link * max(R_e, R_f), D2 formed as

@@ -23,7 +23,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_PEAKGROUP, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_PEAKGROUP, STEP_DISCRES, STEP_COUNT };
 
 // Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
 // beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
@@ -100,7 +100,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1536,6 +1536,7 @@ static_assert(CY_APER_RINGS_MAX == APER_RINGS_MAX && CY_APER_RADIUS_MAX == APER_
 static_assert(CY_PFIT_JOB_FIELDS == PFIT_JOB_FIELDS && CY_PFIT_FIELDS == PFIT_FIELDS && CY_PFIT_RADIUS_MAX == PFIT_RADIUS_MAX &&
               CY_PFIT_NEIGH_MAX == PFIT_NEIGH_MAX && CY_PFIT_JOBS_MAX == PFIT_JOBS_MAX, "header and kernel disagree on the peak fit row");
 static_assert(CY_PGRP_FIELDS == PGRP_FIELDS && CY_PGRP_FIELDS == CY_BLEND_FIELDS + 8, "header and kernel disagree on the peak group row");
+static_assert(CY_DRES_FIELDS == DRES_FIELDS, "header and kernel disagree on the disc residual row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1689,14 +1690,15 @@ int cy_measure_background(cy_ctx* c, const float* d_img, int MH, int MW, int cel
     return t.run(STEP_BACKGROUND, [&](hipStream_t s) { return launch_background(a, s); });
 }
 
-int cy_render_gaussians(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_comp, int m, double nsigma, const float* d_bkg,
-                        float* d_model, float* d_resid, double* h_rows, void* stream) {
+// cy_render_gaussians and cy_render_signed_gaussians: one body, the planner told which amplitudes it admits
+static int render_entry(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_comp, int m, double nsigma, const float* d_bkg,
+                        float* d_model, float* d_resid, double* h_rows, void* stream, bool signed_amp) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
     if (MH <= 0 || MW <= 0 || !(nsigma >= 1.0 && nsigma <= 8.0)) return fail(c, CY_ERR_ARG, "MH, MW > 0 and 1 <= nsigma <= 8 required");
     if (!d_img || (!d_model && !d_resid) || (m > 0 && (!h_comp || !h_rows))) return fail(c, CY_ERR_ARG, "null argument");
     if ((long long)MH * MW >= (1LL << 31)) return fail(c, CY_ERR_ARG, "image of 2^31 pixels or more");
     RenderPlan p;
-    if (const char* msg = plan_render(h_comp, m, nsigma, MH, MW, p)) return fail(c, CY_ERR_ARG, msg);
+    if (const char* msg = plan_render(h_comp, m, nsigma, MH, MW, p, signed_amp)) return fail(c, CY_ERR_ARG, msg);
     TimedLaunch t(c, stream);
     RenderArgs a{};
     a.img = d_img; a.MH = MH; a.MW = MW; a.ntx = p.ntx; a.nty = p.nty; a.bkg = d_bkg; a.model = d_model; a.resid = d_resid;
@@ -1707,6 +1709,16 @@ int cy_render_gaussians(cy_ctx* c, const float* d_img, int MH, int MW, const dou
     const int rc = t.run(STEP_RENDER, [&](hipStream_t s) { return launch_render(a, s); });
     if (rc == CY_OK && m > 0) std::memcpy(h_rows, p.rows.data(), p.rows.size() * sizeof(double));      // rows only beside maps that were written
     return rc;
+}
+
+int cy_render_gaussians(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_comp, int m, double nsigma, const float* d_bkg,
+                        float* d_model, float* d_resid, double* h_rows, void* stream) {
+    return render_entry(c, d_img, MH, MW, h_comp, m, nsigma, d_bkg, d_model, d_resid, h_rows, stream, false);
+}
+
+int cy_render_signed_gaussians(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_comp, int m, double nsigma, const float* d_bkg,
+                               float* d_model, float* d_resid, double* h_rows, void* stream) {
+    return render_entry(c, d_img, MH, MW, h_comp, m, nsigma, d_bkg, d_model, d_resid, h_rows, stream, true);
 }
 
 int cy_measure_residuals(cy_ctx* c, const float* d_img, const float* d_model, int MH, int MW, const double* h_boxes, const double* h_bkg,
@@ -1838,6 +1850,33 @@ int cy_fit_peak_groups(cy_ctx* c, const float* d_map, int MH, int MW, const doub
     return CY_OK;
 }
 
+int cy_disc_residuals(cy_ctx* c, const float* d_map, const float* d_model, int MH, int MW, const double* h_jobs, int n, double* h_out,
+                      void* stream) {
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    PeakFitPlan p;                                                             // the planner of cy_fit_peaks as it stands; no iteration here: max_iter 1
+    if (const char* msg = plan_peak_fits(h_jobs, n, 1, MH, MW, d_map != nullptr, h_out != nullptr, p)) return fail(c, CY_ERR_ARG, msg);
+    if (n == 0) return CY_OK;
+    std::vector<double> got(p.run.size() * CY_DRES_FIELDS);
+    if (!p.run.empty()) {
+        TimedLaunch t(c, stream);
+        DiscResidualArgs a{};
+        a.map = d_map; a.model = d_model; a.MH = MH; a.MW = MW; a.n = n; a.nrun = (int)p.run.size();
+        a.jobs = t.upload(p.jobs.data(), p.jobs.size());
+        a.run = t.upload(p.run.data(), p.run.size());
+        a.out = t.scratch<double>(got.size());
+        t.download(got.data(), a.out, got.size());
+        const int rc = t.run(STEP_DISCRES, [&](hipStream_t s) { return launch_disc_residuals(a, s); });
+        if (rc != CY_OK) return rc;                                            // h_out as it was
+    }
+    size_t next = 0;                                                           // p.run is in increasing job index
+    for (int i = 0; i < n; ++i) {
+        const bool ran = next < p.run.size() && p.run[next] == i;
+        disc_residual_row(p.jobs[(size_t)i], ran ? &got[next * CY_DRES_FIELDS] : nullptr, h_out + (size_t)i * CY_DRES_FIELDS);
+        next += ran;
+    }
+    return CY_OK;
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1857,6 +1896,7 @@ int cy_atrous_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms
 int cy_aperture_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_APERTURE, out_ms); }
 int cy_peakfit_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKFIT, out_ms); }
 int cy_peakgroup_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKGROUP, out_ms); }
+int cy_disc_residual_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_DISCRES, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

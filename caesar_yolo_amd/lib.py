@@ -42,6 +42,9 @@ PFIT_JOB_NAMES = ("cx", "cy", "R", "bkg", "sign", "A", "x0", "y0", "a", "b", "c"
 PFIT_NAMES = FIT_NAMES + ("wx0", "wx1", "wy0", "wy1", "clipped", "nneigh", "crowded", "nexcluded")
 CY_PGRP_FIELDS = 44
 PGRP_NAMES = BLEND_NAMES + ("wx0", "wx1", "wy0", "wy1", "clipped", "nexcluded", "nlinked", "reserved")
+CY_DRES_FIELDS = 16
+DRES_NAMES = ("status", "npix", "nexcluded", "sum", "sumsq", "maxabs", "x_max", "y_max", "model_sum", "reserved", "wx0", "wx1", "wy0", "wy1",
+              "clipped", "nneigh")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -59,9 +62,10 @@ EXPORTS = [
     "cy_decode_nms_augmented", "cy_detect_tiles_augmented", "cy_measure_sources", "cy_measure_kernel_ms",
     "cy_measure_islands", "cy_islands_kernel_ms", "cy_measure_background", "cy_background_kernel_ms", "cy_expand_background",
     "cy_deblend_islands", "cy_deblend_kernel_ms", "cy_fit_components", "cy_fit_kernel_ms", "cy_fit_blends", "cy_blend_kernel_ms",
-    "cy_render_gaussians", "cy_render_kernel_ms", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
+    "cy_render_gaussians", "cy_render_kernel_ms", "cy_render_signed_gaussians", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
     "cy_atrous_step", "cy_atrous_kernel_ms", "cy_aperture_sums", "cy_aperture_kernel_ms",
     "cy_fit_peaks", "cy_peakfit_kernel_ms", "cy_fit_peak_groups", "cy_peakgroup_kernel_ms",
+    "cy_disc_residuals", "cy_disc_residual_kernel_ms",
 ]
 
 
@@ -214,6 +218,7 @@ def load():
         "cy_blend_kernel_ms": (C.c_int, [vp, dp]),
         "cy_render_gaussians": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, vp, vp, vp, dp, vp]),
         "cy_render_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_render_signed_gaussians": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, vp, vp, vp, dp, vp]),
         "cy_measure_residuals": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, vp, C.POINTER(C.c_longlong), dp, vp]),
         "cy_residual_kernel_ms": (C.c_int, [vp, dp]),
         "cy_find_peaks": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, dp, C.POINTER(C.c_longlong), vp]),
@@ -226,6 +231,8 @@ def load():
         "cy_peakfit_kernel_ms": (C.c_int, [vp, dp]),
         "cy_fit_peak_groups": (C.c_int, [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_peakgroup_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_disc_residuals": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, C.c_int, dp, vp]),
+        "cy_disc_residual_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

@@ -55,7 +55,13 @@ a nearest-centre rule; a hole is fitted with sign -1.  Raw rows lib.PFIT_NAMES, 
 --fit_peak_groups (which implies --fit_peaks) then fits the entries of a list that lie closer than fit_peaks_link times their disc
 radius together: `cy_fit_peak_groups` (HipDetector.fit_peak_groups) fits the sum of two to four Gaussians on the union of their
 discs, started from the single fits.  Raw rows lib.PGRP_NAMES, keys GBLEND_KEYS on every entry (annotate_peak_groups).
-Chain.run() calls Chain.peak_groups() last.
+Chain.run() calls Chain.peak_groups() after the single fits.
+
+--subtract_peaks (which implies --fit_peaks) renders the fitted peaks into a second residual: peak_render_selection() picks per
+fitted entry the group fit where there is one, else the single fit, `cy_render_signed_gaussians` subtracts them from the residual map,
+`cy_disc_residuals` (HipDetector.disc_residuals) measures that second residual on the pixels every fit used, raw rows
+lib.DRES_NAMES, keys GRES_KEYS on every entry (annotate_peak_residuals), and `cy_find_peaks` searches it in both signs: the lists
+"residual_peaks_left" / "residual_holes_left" and SOURCE_LEFT_KEYS on every source.  Chain.run() calls Chain.subtract() last.
 
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
@@ -79,7 +85,7 @@ def _fields(names):
 MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAMES, L.DBL_NAMES, L.DBL_COMP_NAMES, L.FIT_NAMES, L.BLEND_NAMES))
 RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
 APER, APER_RING = _fields(L.APER_NAMES), _fields(L.APER_RING_NAMES)
-PFIT, PFIT_JOB, PGRP = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES), _fields(L.PGRP_NAMES)
+PFIT, PFIT_JOB, PGRP, DRES = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES), _fields(L.PGRP_NAMES), _fields(L.DRES_NAMES)
 _PFIT_JOB_PARAMS = [getattr(PFIT_JOB, k) for k in "A x0 y0 a b c".split()]
 _PFIT_PARAMS = [getattr(PFIT, k) for k in "A x0 y0 a b c".split()]
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
@@ -116,6 +122,10 @@ GFIT_KEYS = ("gfit_status", "gfit_niter", "gfit_npix", "gfit_nexcluded", "gfit_n
 GBLEND_KEYS = ("gblend_group", "gblend_size", "gblend_slot", "gblend_status", "gblend_niter", "gblend_npix", "gblend_nexcluded", "gblend_chi2",
                "gblend_peak", "gblend_x", "gblend_y", "gblend_ra", "gblend_dec", "gblend_major", "gblend_minor", "gblend_pa", "gblend_flux",
                "gblend_peak_err", "gblend_x_err", "gblend_y_err", "gblend_flux_err")
+GRES_KEYS = ("gres_subtracted", "gres_source", "gres_render_status", "gres_npix", "gres_mean", "gres_rms", "gres_max", "gres_x_max", "gres_y_max",
+             "gres_ratio", "gres_chi2", "gres_model_flux")
+SOURCE_LEFT_KEYS = ("res_npeaks_left", "res_nholes_left")
+PEAK_LIST_NAMES = ("residual_peaks", "residual_holes", "residual_scale_peaks")     # the order the fitted lists are walked in
 MAD_TO_SIGMA = 1.482602218505602   # 1 / Phi^-1(3/4): the standard deviation of a normal distribution in units of its MAD
 SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
 FIT_SIGMA2_MIN = 0.25              # px^2: floor of the eigenvalues of a start covariance
@@ -609,7 +619,7 @@ def annotate_residuals(sources, raw, index, render_rows, beam_area, origin=(0, 0
 
 
 # ---- residual peaks (--residual_peaks, --residual_holes)
-def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0), holes=False):
+def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0), holes=False, keys=None):
     """The peak list of a residual map, and the peak keys of every source.  rows: [n, CY_PEAK_FIELDS] rows of cy_find_peaks with x, y
     in catalog coordinates, in the library's order; total: the number of peaks it counted (rows holds the first n of them).  A row
     is kept when nabove >= min_above.  -> a list of dicts (PEAK_KEYS) in decreasing snr, equal snr in row order:
@@ -620,7 +630,8 @@ def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0
                        flux = flux_sum / beam_area when beam_area > 0, else None
       in_source        index of the first source whose box contains the peak pixel (x1 <= x_peak <= x2 and y1 <= y_peak <= y2), else None
     Every source dict gets SOURCE_PEAK_KEYS (holes: SOURCE_HOLE_KEYS): the number of kept peaks inside its box (a peak counts for every
-    box that contains it) and the largest snr among them, None without one."""
+    box that contains it) and the largest snr among them, None without one.  keys: other names for those two (count key, snr key);
+    a key that is None is not written (the search of the second residual writes a count only, under a name of its own)."""
     rows = np.asarray(rows, np.float64).reshape(-1, L.CY_PEAK_FIELDS)
     assert int(total) >= rows.shape[0]
     ox, oy = float(origin[0]), float(origin[1])
@@ -628,7 +639,7 @@ def annotate_peaks(sources, rows, total, min_above, beam_area, wcs, origin=(0, 0
     sign = -1.0 if holes else 1.0
     kept = rows[rows[:, PEAK.nabove] >= float(min_above)]
     kept = kept[np.argsort(-kept[:, PEAK.snr], kind="stable")]
-    first = _peaks_in_boxes(sources, kept, SOURCE_HOLE_KEYS if holes else SOURCE_PEAK_KEYS)
+    first = _peaks_in_boxes(sources, kept, keys if keys is not None else SOURCE_HOLE_KEYS if holes else SOURCE_PEAK_KEYS)
     return [_peak_entry(PEAK_KEYS, r, f, sign, ba, wcs, ox, oy) for r, f in zip(kept, first)]
 
 
@@ -650,7 +661,10 @@ def _peaks_in_boxes(sources, kept, keys):
             count[i], best[i] = idx.size, snr[idx].max()
             first[idx[first[idx] < 0]] = i                    # boxes come in source order: the first one stays
     for s, c, m in zip(sources, count, best):
-        s[nkey], s[skey] = int(c), (float(m) if c else None)
+        if nkey is not None:
+            s[nkey] = int(c)
+        if skey is not None:
+            s[skey] = float(m) if c else None
     return first
 
 
@@ -1002,6 +1016,108 @@ def peak_group_stats(rows):
             int(it.max()) if it.size else 0, int((first & (rows[:, PGRP.status] == 7.0)).sum()))
 
 
+# ---- the second residual (--subtract_peaks)
+def wants_subtract(config):
+    """Whether a config asks for the second residual: the fitted peaks subtracted from the residual map (subtract_peaks)."""
+    return bool(config.get('subtract_peaks', False))
+
+
+def peak_render_selection(chain):
+    """The Gaussians the second residual subtracts, after Chain.peak_fits() (and Chain.peak_groups() when it ran): the fitted
+    entries of the lists in the order residual_peaks, residual_holes, residual_scale_peaks (PEAK_LIST_NAMES), inside a list in the
+    order of its jobs.  Everything in the pixel frame of chain.img, as the library answered (.peakfit_rows, .peakgroup_rows,
+    .peakfit_jobs).  Per fitted entry, tested in this order:
+      parameters   its cy_fit_peak_groups row's when the groups ran and that row's status is 0 or 2, else its cy_fit_peaks row's when
+                   that status is 0 or 2, else the entry is not selected (the rule of _fitted_params; a status 6 row carries no
+                   parameters of its own, so the single fit is used)
+      wandered     left out when the fitted centre lies farther than the job's R from the job's centre: dx * dx + dy * dy > R * R
+      duplicates   a scale entry is left out when a component already selected from the two pixel lists has its centre within
+                   that scale entry's R of its job centre (dx * dx + dy * dy <= R * R): the same emission is subtracted once
+      sign         A is multiplied by the list's sign: holes are rendered negative (cy_render_signed_gaussians admits them)
+    -> (comp float64 [m, 6] {A, x0, y0, a, b, c}, index: m tuples (list name, entry index), counts {"wandered", "duplicates",
+    "sources": per component "group" or "single", the fit its parameters came from})."""
+    comp, index, counts = [], [], {"wandered": 0, "duplicates": 0, "sources": []}
+    pixel_centres, by_x = [], None                            # the selected centres of the two pixel lists; sorted by column for the scale list
+    fits, groups = chain.peakfit_rows or {}, chain.peakgroup_rows or {}
+    for name in PEAK_LIST_NAMES:
+        if name not in fits:
+            continue
+        sign = -1.0 if name == "residual_holes" else 1.0
+        single = np.asarray(fits[name], np.float64).reshape(-1, L.CY_PFIT_FIELDS)
+        joint = np.asarray(groups[name], np.float64).reshape(-1, L.CY_PGRP_FIELDS) if name in groups else None
+        jobs = np.asarray(chain.peakfit_jobs[name], np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS)
+        for t, i in enumerate(chain.peakfit_select[name]):
+            if joint is not None and joint[t, PGRP.status] in _FITTED:
+                p, source = joint[t, _BLEND_PARAMS].copy(), "group"
+            elif single[t, PFIT.status] in _FITTED:
+                p, source = single[t, _PFIT_PARAMS].copy(), "single"
+            else:
+                continue
+            cx, cy, R = (float(jobs[t, k]) for k in (PFIT_JOB.cx, PFIT_JOB.cy, PFIT_JOB.R))
+            dx, dy = float(p[1]) - cx, float(p[2]) - cy
+            if not dx * dx + dy * dy <= R * R:
+                counts["wandered"] += 1
+                continue
+            if name == "residual_scale_peaks":
+                if by_x is None:
+                    by_x = np.array(sorted(pixel_centres), np.float64).reshape(-1, 2)
+                # the stretch of columns within R (one more on either side: the test below decides, this only narrows it)
+                near = by_x[np.searchsorted(by_x[:, 0], cx - R - 1.0, "left"):np.searchsorted(by_x[:, 0], cx + R + 1.0, "right")]
+                qx, qy = near[:, 0] - cx, near[:, 1] - cy
+                if (qx * qx + qy * qy <= R * R).any():
+                    counts["duplicates"] += 1
+                    continue
+            else:
+                pixel_centres.append((float(p[1]), float(p[2])))
+            p[0] *= sign
+            comp.append(p)
+            index.append((name, int(i)))
+            counts["sources"].append(source)
+    return np.array(comp, np.float64).reshape(-1, 6), index, counts
+
+
+def annotate_peak_residuals(entries, rows, rms, picked, beam_area, origin=(0, 0), select=None):
+    """GRES_KEYS on every dict of `entries`, after annotate_peak_fits().  rows: [m, CY_DRES_FIELDS] rows of cy_disc_residuals on the
+    second residual, in the pixels of the measured image; rms: [m] the noise at the peak pixels; row t belongs to
+    entries[select[t]] (select None: entry t).  picked: {entry index: (source, render status)} for the entries
+    peak_render_selection() chose, with the status of their cy_render_gaussians rows.  An entry without a row (one that was never
+    fitted) gets every key None.
+      gres_subtracted      whether the entry's Gaussian is part of the peak model (chosen, and render status 0 or 2)
+      gres_source          "group" or "single": the fit it was rendered from; None when it was not chosen
+      gres_render_status   the status of its render row (0, 2: rendered; 1, 3: skipped by the library); None when it was not chosen
+      gres_npix            valid pixels of the entry's share of its disc: the pixels its single fit used (0 with status 1 or 5)
+      gres_mean = sum / npix, gres_rms = sqrt(sumsq / npix) of r = v - bkg on the second residual over those pixels
+      gres_max             the largest |r|; gres_x_max, gres_y_max its position (+ origin)
+      gres_ratio = gres_rms / rms, gres_chi2 = sumsq / rms^2; None when that rms is not finite and > 0
+      gres_model_flux = model_sum / beam_area, what the peak model holds on those pixels; None without a beam
+    With npix == 0 the keys from gres_mean on are None.  -> entries."""
+    rows = np.asarray(rows, np.float64).reshape(-1, L.CY_DRES_FIELDS)
+    rms = np.asarray(rms, np.float64).reshape(-1)
+    select = list(range(len(entries))) if select is None else [int(i) for i in select]
+    assert rows.shape[0] == rms.shape[0] == len(select)
+    ox, oy = int(origin[0]), int(origin[1])
+    ba = float(beam_area) if beam_area else 0.0
+    for d in entries:
+        d.update(dict.fromkeys(GRES_KEYS))
+    for i, r, noise in zip(select, rows, rms):
+        d = entries[i]
+        source, st = picked.get(i, (None, None))
+        d["gres_subtracted"], d["gres_source"], d["gres_render_status"] = st in (0, 2), source, st
+        npix = int(r[DRES.npix]) if r[DRES.status] == 0.0 else 0
+        d["gres_npix"] = npix
+        if npix == 0:
+            continue
+        sumsq = float(r[DRES.sumsq])
+        d["gres_mean"], d["gres_rms"] = float(r[DRES.sum]) / npix, math.sqrt(sumsq / npix)
+        d["gres_max"], d["gres_x_max"], d["gres_y_max"] = float(r[DRES.maxabs]), int(r[DRES.x_max]) + ox, int(r[DRES.y_max]) + oy
+        noise = float(noise)
+        if math.isfinite(noise) and noise > 0.0:
+            d["gres_ratio"], d["gres_chi2"] = d["gres_rms"] / noise, sumsq / (noise * noise)
+        if ba > 0.0:
+            d["gres_model_flux"] = float(r[DRES.model_sum]) / ba
+    return entries
+
+
 def _read_at(m, iy, ix):
     """m[iy, ix] of a device map (or a host array) as numpy float64: one indexed read."""
     if hasattr(m, "is_cuda"):
@@ -1023,7 +1139,8 @@ def wants_peaks(config):
 
 def peak_lists(chain):
     """What a catalog file carries beside its sources after Chain.run(): {"residual_peaks": [...]} and, when holes were searched,
-    "residual_holes", and "residual_scale_peaks" when the scales were; empty when the chain (or None) did not search."""
+    "residual_holes", and "residual_scale_peaks" when the scales were, and "residual_peaks_left" / "residual_holes_left" when the
+    fitted peaks were subtracted; empty when the chain (or None) did not search."""
     out = {}
     if chain is not None and chain.peak_list is not None:
         out["residual_peaks"] = chain.peak_list
@@ -1031,6 +1148,8 @@ def peak_lists(chain):
         out["residual_holes"] = chain.hole_list
     if chain is not None and chain.scale_list is not None:
         out["residual_scale_peaks"] = chain.scale_list
+    if chain is not None and chain.left_peak_list is not None:
+        out["residual_peaks_left"], out["residual_holes_left"] = chain.left_peak_list, chain.left_hole_list
     return out
 
 
@@ -1055,6 +1174,12 @@ def save_scale_maps(planes, catalog_path):
 def save_residual_maps(model, resid, catalog_path):
     """--save_residual_maps: model_<name>.fits / resid_<name>.fits beside the catalog file (_save_maps).  -> the two paths."""
     return _save_maps(("model_", "resid_"), (model, resid), catalog_path)
+
+
+def save_second_residual_maps(peak_model, resid2, catalog_path):
+    """--save_residual_maps with --subtract_peaks: peakmodel_<name>.fits / resid2_<name>.fits beside the catalog file (_save_maps).
+    -> the two paths."""
+    return _save_maps(("peakmodel_", "resid2_"), (peak_model, resid2), catalog_path)
 
 
 def deblend_config(config):
@@ -1151,11 +1276,11 @@ def plan(config):
     save_bkg_maps the mesh, which implies the first measurement too.  residual_peaks and residual_holes (Chain.peaks, which is no
     step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
     (Chain.scale_peaks, no step either) implies exactly the same, and so do peak_apertures (Chain.apertures), fit_peaks
-    (Chain.peak_fits) and fit_peak_groups (Chain.peak_groups, which implies fit_peaks), which measure on the residual map with the
-    rms map of the mesh but turn no search on."""
+    (Chain.peak_fits), fit_peak_groups (Chain.peak_groups, which implies fit_peaks) and subtract_peaks (Chain.subtract, which
+    implies fit_peaks too), which measure on the residual map with the rms map of the mesh but turn no search on."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
-    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config) or wants_peak_groups(config)
+    peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config) or wants_peak_groups(config) or wants_subtract(config)
     residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
@@ -1193,7 +1318,8 @@ class Chain(object):
         self.ap_unit, self.ap_factors, self.ap_annulus = aperture_config(c) if self.want_apertures else (1.0, (), 0.0)
         self.want_peak_groups = wants_peak_groups(c)
         self.pg_link = peakgroup_config(c) if self.want_peak_groups else 1.5
-        self.want_peak_fits = wants_peak_fits(c) or self.want_peak_groups
+        self.want_subtract = wants_subtract(c)
+        self.want_peak_fits = wants_peak_fits(c) or self.want_peak_groups or self.want_subtract
         self.pf_radius, self.pf_sigma, self.pf_max_iter = peakfit_config(c) if self.want_peak_fits else (6.0, 1.5, 64)
         self.use_map = "background" in plan(c)               # thresholds, fit backgrounds and chi2 from bkg_map / rms_map
         self.bx, self.by = float(box_origin[0]), float(box_origin[1])
@@ -1211,6 +1337,8 @@ class Chain(object):
         self.aperture_rows = self.aperture_stats = None
         self.peakfit_rows = self.peakfit_jobs = self.peakfit_select = self.peakfit_stats = self.peakfit_rms = None
         self.peakgroup_rows = self.peakgroup_jobs = self.peakgroup_stats = None
+        self.peak_model = self.resid2 = self.subtract_comp = self.subtract_index = self.subtract_render_rows = None
+        self.disc_rows = self.left_rows = self.left_peak_list = self.left_hole_list = self.subtract_stats = None
 
     def _moved(self, rows, has, xcols, ycols):
         """rows with the columns xcols / ycols of the rows `has` moved from the pixels of img_dev to catalog coordinates; rows
@@ -1472,8 +1600,56 @@ class Chain(object):
         st["peakgroup_ms"] = 1e3 * (time.time() - t1)
         self.peakgroup_stats = st
 
+    def subtract(self):
+        """After peak_fits() (and peak_groups()): peak_render_selection(), one cy_render_signed_gaussians call (holes carry a negative amplitude)
+        with .resid as the image, no background and the nsigma of the residual step (made with no component too: the second residual is then the first), then
+        per fitted list one cy_disc_residuals call on the second residual and the peak model with that list's jobs and
+        annotate_peak_residuals().  Then the rms map of the mesh expanded once and cy_find_peaks on the second residual with the
+        threshold, radius and cap of the pixel search, always in both signs (an over-subtraction only shows as a hole): the rows
+        moved to catalog coordinates and annotate_peaks() with count keys of their own (SOURCE_LEFT_KEYS).  The apertures, the fits
+        and the groups measured on the first residual, which stays as it is.  Leaves the device maps .peak_model / .resid2,
+        .subtract_comp / .subtract_index / .subtract_render_rows (what was rendered), .disc_rows ({list name: rows} as the library
+        gave them), .left_rows ({sign: the rows of cy_find_peaks}), .left_peak_list / .left_hole_list and .subtract_stats
+        {"subtract_ms", "subtract_render_kernel_ms", "disc_residual_kernel_ms" (summed over the calls that launched),
+        "subtract_selected", "subtract_rendered", "subtract_wandered", "subtract_duplicates", "left_peaks_kernel_ms" (both signs),
+        "left_peaks", "left_holes" (kept entries), "left_truncated"}."""
+        t1 = time.time()
+        det = self.det
+        comp, index, counts = peak_render_selection(self)
+        rows, self.peak_model, self.resid2 = det.render_gaussians(self.resid, comp, self.nsigma, None, signed=True)
+        self.subtract_comp, self.subtract_index, self.subtract_render_rows = comp, index, rows
+        st = {"subtract_render_kernel_ms": det.render_kernel_ms(), "disc_residual_kernel_ms": 0.0, "subtract_selected": len(index),
+              "subtract_rendered": int(np.isin(rows[:, RND.status], _FITTED).sum()), "subtract_wandered": counts["wandered"],
+              "subtract_duplicates": counts["duplicates"]}
+        lists = {"residual_peaks": self.peak_list, "residual_holes": self.hole_list, "residual_scale_peaks": self.scale_list}
+        self.disc_rows = {}
+        for name, jobs in self.peakfit_jobs.items():
+            entries, select = lists[name], self.peakfit_select[name]
+            raw = np.zeros((0, L.CY_DRES_FIELDS), np.float64)
+            if select:
+                raw = det.disc_residuals(self.resid2, self.peak_model, jobs)
+                if (raw[:, DRES.status] == 0.0).any():                # a call without a measured job launches nothing
+                    st["disc_residual_kernel_ms"] += max(det.disc_residual_kernel_ms(), 0.0)
+            picked = {i: (source, int(r[RND.status])) for (nm, i), source, r in zip(index, counts["sources"], rows) if nm == name}
+            annotate_peak_residuals(entries, raw, self.peakfit_rms[name], picked, self.beam_area, self.box_origin, select)
+            self.disc_rows[name] = raw
+        rms_dev = det.expand_background(self.mesh, self.cell, self.img.shape, want=("rms",))[1]
+        self.left_rows, found, st["left_peaks_kernel_ms"], st["left_truncated"] = {}, {}, 0.0, 0
+        for sign, key in ((1, SOURCE_LEFT_KEYS[0]), (-1, SOURCE_LEFT_KEYS[1])):
+            raw, total = det.find_peaks(self.resid2, rms_dev, k_sigma=self.peak_sigma, radius=self.peak_radius, sign=sign, cap=self.peak_cap)
+            st["left_peaks_kernel_ms"] += max(det.peaks_kernel_ms(), 0.0)
+            st["left_truncated"] += int(total > raw.shape[0])
+            self.left_rows[sign] = raw
+            moved = self._moved(raw, np.ones(raw.shape[0], bool), (PEAK.x,), (PEAK.y,))
+            found[sign] = annotate_peaks(self.sources, moved, total, self.peak_min_above, self.beam_area, self.wcs, self.wcs_origin, holes=sign < 0,
+                                         keys=(key, None))
+        self.left_peak_list, self.left_hole_list = found[1], found[-1]
+        st["left_peaks"], st["left_holes"] = len(found[1]), len(found[-1])
+        st["subtract_ms"] = 1e3 * (time.time() - t1)
+        self.subtract_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures(), peak_fits() and peak_groups(), each when the
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures(), peak_fits(), peak_groups() and subtract(), each when the
         config asks for it and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
@@ -1521,13 +1697,20 @@ class Chain(object):
             self.peak_groups()
             if stats is not None:
                 stats.update(self.peakgroup_stats)
+        if self.want_subtract and "residual" in steps:
+            self.subtract()
+            if stats is not None:
+                stats.update(self.subtract_stats)
         return self
 
     def save_maps(self, catalog_path):
-        """--save_bkg_maps / --save_residual_maps, after run(): the maps of the mesh and of the residual step beside the catalog."""
+        """--save_bkg_maps / --save_residual_maps, after run(): the maps of the mesh and of the residual step (and, when the fitted peaks were
+        subtracted, the peak model and the second residual) beside the catalog."""
         if self.save_bkg:
             save_background_maps(self.det, self.mesh, self.cell, self.img.shape, catalog_path)
         if self.save_residual:
             save_residual_maps(self.model, self.resid, catalog_path)
+            if self.resid2 is not None:
+                save_second_residual_maps(self.peak_model, self.resid2, catalog_path)
         if self.save_scales and self.scale_planes:
             save_scale_maps(self.scale_planes, catalog_path)

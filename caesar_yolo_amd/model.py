@@ -489,11 +489,12 @@ class HipDetector(object):
         return self._kernel_ms(self.lib.cy_blend_kernel_ms)
 
     # ---- model and residual maps (the seventh measurement step)
-    def render_gaussians(self, img_dev, comp, nsigma=5.0, bkg_dev=None, want=("model", "resid")):
+    def render_gaussians(self, img_dev, comp, nsigma=5.0, bkg_dev=None, want=("model", "resid"), signed=False):
         """The sum of the Gaussians comp [m, 6] float64 {A, x0, y0, a, b, c} (x0, y0 in image pixels) over the whole image, each
         inside its support rectangle of nsigma marginal sigmas (cy_render_gaussians).  img_dev: as measure_sources; bkg_dev: a
         device fp32 map of its shape, or None (0).  -> (rows numpy float64 [m, CY_RND_FIELDS] (lib.RND_NAMES), model, resid): the two
-        device fp32 maps [MH, MW]; one not named in `want` is None."""
+        device fp32 maps [MH, MW]; one not named in `want` is None.  signed: amplitudes of either sign are rendered
+        (cy_render_signed_gaussians: A != 0 in place of A > 0), as the second residual needs them for fitted holes."""
         MH, MW = self._image_2d(img_dev, "render_gaussians")
         comp = np.ascontiguousarray(np.asarray(comp, np.float64).reshape(-1, 6))
         m = comp.shape[0]
@@ -502,10 +503,10 @@ class HipDetector(object):
         rows = np.zeros((m, L.CY_RND_FIELDS), np.float64)
         maps = [torch.empty((MH, MW), dtype=torch.float32, device=self.tdev) if n in want else None for n in ("model", "resid")]
         dp = C.POINTER(C.c_double)
-        self._chk(self.lib.cy_render_gaussians(self.ctx, self._p(img_dev), MH, MW, comp.ctypes.data_as(dp) if m else None, m, float(nsigma),
-                                               self._p(bkg_dev) if bkg_dev is not None else None,
-                                               *[self._p(t) if t is not None else None for t in maps],
-                                               rows.ctypes.data_as(dp) if m else None, self._stream()))
+        entry = self.lib.cy_render_signed_gaussians if signed else self.lib.cy_render_gaussians
+        self._chk(entry(self.ctx, self._p(img_dev), MH, MW, comp.ctypes.data_as(dp) if m else None, m, float(nsigma),
+                        self._p(bkg_dev) if bkg_dev is not None else None, *[self._p(t) if t is not None else None for t in maps],
+                        rows.ctypes.data_as(dp) if m else None, self._stream()))
         return rows, maps[0], maps[1]
 
     def render_kernel_ms(self):
@@ -647,6 +648,27 @@ class HipDetector(object):
     def peakgroup_kernel_ms(self):
         """Kernel time of the last fit_peak_groups call that launched in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_peakgroup_kernel_ms)
+
+    # ---- residuals on the discs of given jobs (what the second residual holds where a peak was fitted)
+    def disc_residuals(self, map_dev, model_dev, jobs):
+        """Count, sum, sum of squares and largest |v - bkg| of map_dev on the pixel set of every job, and the sum of model_dev over
+        the same pixels (cy_disc_residuals).  map_dev: a contiguous 2-D float32 device map, the second residual of
+        measure.Chain.subtract(); model_dev: a map of its shape (the peak model), or None; jobs: [n, CY_PFIT_JOB_FIELDS] float64 as
+        fit_peaks takes them (the start is ignored).  -> numpy float64 [n, CY_DRES_FIELDS] (lib.DRES_NAMES)."""
+        MH, MW = self._image_2d(map_dev, "disc_residuals")
+        if model_dev is not None and (model_dev.shape != map_dev.shape or self._image_2d(model_dev, "disc_residuals (model_dev)") != (MH, MW)):
+            raise L.CyError("disc_residuals: model_dev must have the shape of the map")
+        jobs = np.ascontiguousarray(np.asarray(jobs, np.float64).reshape(-1, L.CY_PFIT_JOB_FIELDS))
+        n = jobs.shape[0]
+        out = np.zeros((n, L.CY_DRES_FIELDS), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_disc_residuals(self.ctx, self._p(map_dev), self._p(model_dev) if model_dev is not None else None, MH, MW,
+                                             jobs.ctypes.data_as(dp), n, out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def disc_residual_kernel_ms(self):
+        """Kernel time of the last disc_residuals call that launched in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_disc_residual_kernel_ms)
 
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):

@@ -553,6 +553,12 @@ int cy_render_gaussians(cy_ctx* ctx, const float* d_img, int MH, int MW,
                         double* h_rows /* [m][CY_RND_FIELDS] */, void* stream);
 /* milliseconds the kernel of the last cy_render_gaussians call took (hipEvents around the launch); -1 before the first call */
 int cy_render_kernel_ms(const cy_ctx* ctx, double* out_ms);
+/* cy_render_gaussians with amplitudes of either sign: a component is admissible with A != 0 in place of A > 0, and a negative one
+ * lowers the model where a positive one raises it.  Everything else, word for word: the other conditions of "admissible", the
+ * support rectangles, the rows, the order of the sum, the residual, the checks and cy_render_kernel_ms, which both entries set.
+ * The second residual (--subtract_peaks) subtracts fitted peaks and fitted holes in one such call. */
+int cy_render_signed_gaussians(cy_ctx* ctx, const float* d_img, int MH, int MW, const double* h_comp /* [m][6] */, int m, double nsigma,
+                               const float* d_bkg, float* d_model, float* d_resid, double* h_rows /* [m][CY_RND_FIELDS] */, void* stream);
 
 /* The residual of n catalog boxes against a model map d_model [MH][MW] (as cy_render_gaussians writes it).  Box window as
  * cy_measure_sources; h_mask / h_mask_off laid out as cy_deblend_islands writes them (both required; h_mask_off is checked
@@ -757,6 +763,39 @@ int cy_fit_peak_groups(cy_ctx* ctx, const float* d_map, int MH, int MW, const do
                        int n, double link, int max_iter, double* h_out /* [n][CY_PGRP_FIELDS] */, void* stream);
 /* milliseconds the kernel of the last cy_fit_peak_groups call that launched one took (hipEvents around the launch); -1 before it */
 int cy_peakgroup_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
+/* ---- residuals on the discs of given jobs (an addition: what a map still holds where a peak was fitted) -------------------------
+ * Count, sum, sum of squares and largest |r| of d_map (device fp32 [MH][MW]) on the pixel set of every job, and the sum of a
+ * second map d_model (same shape, or NULL) over the same pixels.  The chain gives it the second residual (the residual map minus
+ * the fitted peaks, cy_render_signed_gaussians with d_img = the residual map) and the peak model, with the jobs of cy_fit_peaks: a row
+ * then says what the fit of that job left behind on exactly the pixels it was fitted to.  h_jobs: [n][CY_PFIT_JOB_FIELDS] as
+ * cy_fit_peaks; only cx, cy, R, bkg and sign are read, sign is validated and otherwise unused, the start is ignored.  Everything in
+ * float64, every product and sum rounded on its own (no contraction); valid pixel and pixel-centre convention as
+ * cy_aperture_sums.
+ *   planner    that of cy_fit_peaks, word for word: statuses 1 and 5, the window, clipped, the neighbours (nneigh) and with them
+ *              the PIXEL SET: window pixel (qx, qy) is a member of job e when d2_e <= R_e * R_e and d2_f >= d2_e for every kept
+ *              neighbour f; a pixel that ties belongs to both jobs.  npix: the valid members; nexcluded: the valid pixels inside
+ *              the disc that a neighbour took
+ *   data       on a valid member p: r = (double)v - bkg, one rounded operation, no sign applied
+ *   LIST and ASSOCIATION   window pixel i = dy * W + dx sits on thread i mod 256, every sum runs sequentially per thread over
+ *              increasing i; then the block reduction of the measurement kernels: sums for the three sums and the two counts,
+ *              the first maximum for |r| with the window index.  Two calls give the same bytes
+ * Row i of h_out, CY_DRES_FIELDS float64: [0] status (0 measured; 1 / 5 the planner's), [1] npix, [2] nexcluded, [3] sum r,
+ * [4] sum r * r, [5] maxabs = the largest |r|, [6] x_max, [7] y_max its first occurrence in window-index order, in image pixels
+ * (npix == 0: -1, -1 and maxabs 0), [8] model_sum = the sum of (double)d_model[p] over the members (0 when d_model is NULL),
+ * [9] reserved (0), [10..13] wx0 wx1 wy0 wy1, [14] clipped, [15] nneigh.  Rows of statuses 1 and 5: the status, the window and the
+ * position as -1 and zeros elsewhere.
+ * One launch: one workgroup of 256 threads per planner-status-0 job, one sweep over its window, pixel addresses formed in 64 bits.
+ * Synchronous on `stream`; needs no loaded weights; the maps are only read.  CY_ERR_ARG with a message (cy_last_error), nothing
+ * launched and h_out untouched, checked in this order after a null ctx: MH or MW <= 0; an image of 2^31 pixels or more; n outside
+ * [0, CY_PFIT_JOBS_MAX]; with n > 0 a null d_map, h_jobs or h_out.  n == 0, or no planner-status-0 job: CY_OK, nothing launched,
+ * and cy_disc_residual_kernel_ms keeps its value. */
+#define CY_DRES_FIELDS 16   /* status npix nexcluded sum sumsq maxabs x_max y_max model_sum reserved wx0 wx1 wy0 wy1 clipped nneigh */
+int cy_disc_residuals(cy_ctx* ctx, const float* d_map, const float* d_model /* or NULL */, int MH, int MW,
+                      const double* h_jobs /* [n][CY_PFIT_JOB_FIELDS], as cy_fit_peaks */, int n,
+                      double* h_out /* [n][CY_DRES_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_disc_residuals call that launched one took (hipEvents around the launch); -1 before it */
+int cy_disc_residual_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel

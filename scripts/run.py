@@ -79,6 +79,16 @@ Differences that come with the MI355X engine:
              most 2) times the larger of their disc radii are fitted together on the GPU, two to four Gaussians on the union of
              their discs, started from the single fits; larger groups keep their single fits: gblend_group, gblend_size,
              gblend_slot, gblend_status .. gblend_flux_err per entry (cy_fit_peak_groups; DESIGN.md "Peak groups").
+  --subtract_peaks  (new; implies --fit_peaks) the fitted peaks (the group fit of an entry where there is one, else its single fit;
+             a fit that left its disc and a scale peak that repeats a pixel peak left out) are rendered on the GPU and subtracted
+             from the residual map: a second residual.  Holes are rendered with a negative amplitude, so the emission they were
+             fitted on is subtracted as well.  Every fitted entry gains gres_subtracted, gres_source,
+             gres_render_status, gres_npix, gres_mean, gres_rms, gres_max, gres_x_max, gres_y_max, gres_ratio, gres_chi2 and
+             gres_model_flux, measured on the second residual over the pixels of its fit; the catalog file gains the lists
+             "residual_peaks_left" and "residual_holes_left" (the keys of "residual_peaks"), the search of --residual_peaks run
+             on the second residual in both signs, and every source res_npeaks_left and res_nholes_left.  With
+             --save_residual_maps the peak model and the second residual are written as peakmodel_<catalog name>.fits and
+             resid2_<catalog name>.fits (cy_render_gaussians, cy_disc_residuals; DESIGN.md "Second residual").
 """
 import argparse
 import logging
@@ -238,7 +248,11 @@ def parse_args(argv=None):
                    help='fit neighbouring entries of a peak list jointly, two to four Gaussians on the union of their discs (implies --fit_peaks)')
     p.add_argument('--fit_peaks_link', dest='fit_peaks_link', type=float, default=1.5,
                    help='entries closer than this times the larger of their disc radii are fitted together, in (0, 2] (with --fit_peak_groups)')
+    p.add_argument('--subtract_peaks', dest='subtract_peaks', action='store_true',
+                   help='subtract the fitted peaks from the residual map, measure every fit on that second residual and search it again in both signs (implies --fit_peaks)')
     args = p.parse_args(argv)
+    if args.subtract_peaks:
+        args.fit_peaks = True                                 # what is subtracted are the fits
     if args.fit_peak_groups:
         try:
             peakgroup_config(vars(args))
@@ -350,7 +364,8 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'residual_peaks', 'residual_peaks_sigma', 'residual_peaks_radius', 'residual_peaks_min_above', 'residual_peaks_max',
                 'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps',
                 'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus',
-                'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter', 'fit_peak_groups', 'fit_peaks_link')
+                'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter', 'fit_peak_groups', 'fit_peaks_link',
+                'subtract_peaks')
 
 
 def measure_config(args):

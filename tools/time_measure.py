@@ -34,6 +34,10 @@ Unless --no-peakgroups (or --no-peakfits, ..) is given there is a variant `peakg
 (peakgroup_ms, peakgroup_kernel_ms summed over the calls beside peakfit_kernel_ms of the same runs, the numbers of group jobs, members,
 converged jobs and groups above the member limit, the iterations, and peakgroup_groups: the groups of the catalog counted by size and
 status); peakgroups_added_ms is its run time over that of the `peakfits` variant of the same runs.
+Unless --no-subtract (or --no-peakgroups, ..) is given there is a variant `subtract`, the flags of `peakgroups` plus --subtract_peaks
+(subtract_ms, subtract_render_kernel_ms, disc_residual_kernel_ms summed over the calls, left_peaks_kernel_ms of the two searches beside
+peakgroup_kernel_ms of the same runs, the numbers of selected, rendered, wandered and duplicate components and of the entries of the
+two left lists); subtract_added_ms is its run time over that of the `peakgroups` variant of the same runs.
 --only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
@@ -141,6 +145,7 @@ def main():
     ap.add_argument("--no-apertures", action="store_true")
     ap.add_argument("--no-peakfits", action="store_true")
     ap.add_argument("--no-peakgroups", action="store_true")
+    ap.add_argument("--no-subtract", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
@@ -206,6 +211,12 @@ def main():
                                     ("peakfit_ms", "peakfit_kernel_ms", "peakgroup_ms", "peakgroup_kernel_ms"),
                                     ("peakfit_jobs", "peakfit_crowded", "peakgroup_jobs", "peakgroup_members", "peakgroup_converged", "peakgroup_niter_mean",
                                      "peakgroup_niter_max", "peakgroup_over_limit", "peakgroup_groups")),
+                     "subtract": (["--fit_blends", "--residual_map", "--residual_peaks", "--residual_scales=4", "--peak_apertures", "--fit_peaks",
+                                   "--fit_peak_groups", "--subtract_peaks"],
+                                  ("peakgroup_ms", "peakgroup_kernel_ms", "subtract_ms", "subtract_render_kernel_ms", "disc_residual_kernel_ms",
+                                   "left_peaks_kernel_ms"),
+                                  ("peakfit_jobs", "subtract_selected", "subtract_rendered", "subtract_wandered", "subtract_duplicates", "left_peaks",
+                                   "left_holes", "left_truncated")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
@@ -217,6 +228,8 @@ def main():
                                  args.no_peakfits),
                     "peakgroups": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
                                    args.no_peakfits or args.no_peakgroups),
+                    "subtract": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
+                                 args.no_peakfits or args.no_peakgroups or args.no_subtract),
                     "islands": args.no_islands}
             if args.only:
                 skip.update({name: True for name in table if name not in args.only.split(",")})
@@ -256,6 +269,8 @@ def main():
                 res["peakfits_added_ms"] = res["peakfits"]["run_ms_median"] - res["apertures"]["run_ms_median"]
             if "peakgroups" in got and "peakfits" in got:
                 res["peakgroups_added_ms"] = res["peakgroups"]["run_ms_median"] - res["peakfits"]["run_ms_median"]
+            if "subtract" in got and "peakgroups" in got:
+                res["subtract_added_ms"] = res["subtract"]["run_ms_median"] - res["peakgroups"]["run_ms_median"]
             if "scales" in got:
                 res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:

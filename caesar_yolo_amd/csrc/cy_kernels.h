@@ -417,6 +417,17 @@ struct DiscResidualArgs {
 };
 hipError_t launch_disc_residuals(const DiscResidualArgs& a, hipStream_t s);
 
+// ---- forced photometry: linear fits of fixed shapes (cy_forced.hip) ---------------------------------------
+// FORCED_*, ForcedJob: cy_measure_jobs.h; the jobs: plan_forced (cy_measure_plan.h)
+struct ForcedArgs {
+    const float* map; const float* rms; int MH, MW;        // rms may be null; MH * MW < 2^31
+    const ForcedJob* jobs; int n;   // the whole job table: a neighbour is named by its index in it
+    const int* run; int nrun;       // the jobs that are fitted, one workgroup each: 1 <= nrun <= n <= FORCED_JOBS_MAX
+    double ns2; int fit_bkg;        // nsigma * nsigma, rounded once on the host; 0 or 1
+    double* out;                    // [nrun][FORCED_FIELDS]: workgroup t writes every field of row t
+};
+hipError_t launch_forced(const ForcedArgs& a, hipStream_t s);
+
 // ---- background and noise mesh (cy_background.hip) -------------------------------------------------
 constexpr int BKG_FIELDS = 8;                 // CY_BKG_FIELDS
 constexpr int BKG_CELL_MIN = 4, BKG_CELL_MAX = 4096, BKG_NITER_MAX = 32;

@@ -1,5 +1,5 @@
 // Job records and limits shared by the measurement kernels (cy_islands.hip, cy_deblend.hip, cy_fit.hip, cy_blend.hip, cy_aperture.hip,
-// cy_peakfit.hip, cy_peakgroup.hip, cy_disc_residual.hip) and the
+// cy_peakfit.hip, cy_peakgroup.hip, cy_disc_residual.hip, cy_forced.hip) and the
 // host-side planner that fills them (cy_measure_plan.cpp).  No HIP include: the planner also builds as plain C++.
 #pragma once
 
@@ -42,6 +42,11 @@ constexpr int PFIT_NEIGH_MAX = 8;              // CY_PFIT_NEIGH_MAX: neighbours 
 constexpr int PFIT_JOBS_MAX = 1 << 20;         // CY_PFIT_JOBS_MAX: one workgroup per fitted job, the grid in x only
 constexpr int PGRP_FIELDS = 44;                // CY_PGRP_FIELDS: the 36 fields of a blend row, wx0 wx1 wy0 wy1 clipped nexcluded nlinked 0
 constexpr int DRES_FIELDS = 16;                // CY_DRES_FIELDS: status npix nexcluded sum sumsq maxabs x_max y_max model_sum 0, wx0 wx1 wy0 wy1 clipped nneigh
+constexpr int FORCED_JOB_FIELDS = 6;            // CY_FORCED_JOB_FIELDS: x0 y0 a b c bkg
+constexpr int FORCED_FIELDS = 24;               // CY_FORCED_FIELDS
+constexpr int FORCED_NEIGH_MAX = 7;             // CY_FORCED_NEIGH_MAX: neighbours whose amplitudes are solved with a job's
+constexpr int FORCED_JOBS_MAX = 1 << 20;        // CY_FORCED_JOBS_MAX: one workgroup per runnable job, the grid in x only
+constexpr int FORCED_SIDE_MAX = 2 * RND_HALF_MAX + 2;      // a support rectangle has at most 514 x 514 pixels
 
 struct FitJob {
     long long list_off;             // first list entry of the job in FitArgs::list
@@ -93,6 +98,15 @@ struct PeakGroupJob {
     int x0, x1, y0, y1;             // the group window: the bounding box of the members' windows, inclusive, inside the image
     double bkg, sign;               // those of the member in slot 0
     double p0[6 * BLEND_MAX_MEMBERS];   // starts in slot order, x0 / y0 relative to the group window's first pixel
+};
+
+struct ForcedJob {
+    double cx, cy, a, b, c;         // x0, y0 (image pixels) and the shape, as given
+    double bkg;                     // y = (double)v - bkg
+    int x0, x1, y0, y1;             // the support rectangle, inclusive, inside the image; {0, -1, 0, -1} when not run
+    int status;                     // 0 run, 1 not admissible, 2 run with a capped half-width, 3 the rectangle misses the image
+    int nneigh, crowded, ndup;      // kept neighbours; 1: there were more than FORCED_NEIGH_MAX; exact duplicates dropped
+    int neigh[FORCED_NEIGH_MAX];    // their job indices in (squared centre distance, index) order; -1 beyond nneigh
 };
 
 }  // namespace cy

@@ -199,15 +199,8 @@ const char* plan_blend(const FitInputs& in, BlendPlan& p) {
         });
 }
 
-const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p, bool signed_amp) {
+int support_rect(const double* q, double nsigma, int MH, int MW, int* r, double* hx_out) {
 #pragma clang fp contract(off)          // a*c - b*b: both products are rounded before the subtraction, whatever the build's default
-    p.rows.clear(); p.rect.clear(); p.tile_off.clear(); p.tile_list.clear();
-    p.ntx = (MW + RND_TILE - 1) / RND_TILE; p.nty = (MH + RND_TILE - 1) / RND_TILE;
-    if (m < 0 || m > RND_MAX_COMP) return "m outside 0 .. 2^20";
-    p.rows.assign((size_t)m * RND_FIELDS, 0.0);
-    p.rect.assign((size_t)m * 4, 0);
-    const size_t ntiles = (size_t)p.ntx * p.nty;
-    p.tile_off.assign(ntiles + 1, 0);
     // one side of a rectangle: [max(0, floor(c0) - h), min(N - 1, floor(c0) + 1 + h)], compared in double; false when it misses
     auto side = [](double c0, double h, int N, int* lo, int* hi) {
         const double f = std::floor(c0), l = f - h, u = (f + 1.0) + h;
@@ -216,6 +209,33 @@ const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW
         *hi = u < (double)(N - 1) ? (int)u : N - 1;
         return true;
     };
+    r[0] = r[2] = 0; r[1] = r[3] = -1;
+    bool fin = true;
+    for (int t = 0; t < 5; ++t) fin = fin && std::isfinite(q[t]);
+    const double a = q[2], b = q[3], c = q[4];
+    const double ac = a * c, bb = b * b;
+    const double det = ac - bb;
+    if (!(fin && a > 0.0 && c > 0.0 && det > 0.0)) return 1;
+    double hx = std::ceil(nsigma * std::sqrt(c / det)), hy = std::ceil(nsigma * std::sqrt(a / det));
+    bool capped = false;
+    if (!(hx <= (double)RND_HALF_MAX)) { hx = (double)RND_HALF_MAX; capped = true; }      // a half-width that is not finite is above the cap
+    if (!(hy <= (double)RND_HALF_MAX)) { hy = (double)RND_HALF_MAX; capped = true; }
+    if (hx_out) *hx_out = hx;
+    if (!side(q[0], hx, MW, &r[0], &r[1]) || !side(q[1], hy, MH, &r[2], &r[3])) {
+        r[0] = r[2] = 0; r[1] = r[3] = -1;
+        return 3;
+    }
+    return capped ? 2 : 0;
+}
+
+const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p, bool signed_amp) {
+    p.rows.clear(); p.rect.clear(); p.tile_off.clear(); p.tile_list.clear();
+    p.ntx = (MW + RND_TILE - 1) / RND_TILE; p.nty = (MH + RND_TILE - 1) / RND_TILE;
+    if (m < 0 || m > RND_MAX_COMP) return "m outside 0 .. 2^20";
+    p.rows.assign((size_t)m * RND_FIELDS, 0.0);
+    p.rect.assign((size_t)m * 4, 0);
+    const size_t ntiles = (size_t)p.ntx * p.nty;
+    p.tile_off.assign(ntiles + 1, 0);
     long long total = 0;
     for (int k = 0; k < m; ++k) {
         const double* q = comp + (size_t)k * 6;
@@ -223,22 +243,10 @@ const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW
         int* r = &p.rect[(size_t)k * 4];
         r[0] = r[2] = 0; r[1] = r[3] = -1;
         row[1] = row[2] = row[3] = row[4] = -1.0;
-        bool fin = true;
-        for (int t = 0; t < 6; ++t) fin = fin && std::isfinite(q[t]);
-        const double a = q[3], b = q[4], c = q[5];
-        const double ac = a * c, bb = b * b;
-        const double det = ac - bb;
-        if (!(fin && (signed_amp ? q[0] != 0.0 : q[0] > 0.0) && a > 0.0 && c > 0.0 && det > 0.0)) { row[0] = 1.0; continue; }
-        double hx = std::ceil(nsigma * std::sqrt(c / det)), hy = std::ceil(nsigma * std::sqrt(a / det));
-        bool capped = false;
-        if (!(hx <= (double)RND_HALF_MAX)) { hx = (double)RND_HALF_MAX; capped = true; }      // a half-width that is not finite is above the cap
-        if (!(hy <= (double)RND_HALF_MAX)) { hy = (double)RND_HALF_MAX; capped = true; }
-        if (!side(q[1], hx, MW, &r[0], &r[1]) || !side(q[2], hy, MH, &r[2], &r[3])) {
-            r[0] = r[2] = 0; r[1] = r[3] = -1;
-            row[0] = 3.0;
-            continue;
-        }
-        row[0] = capped ? 2.0 : 0.0;
+        const bool amp = std::isfinite(q[0]) && (signed_amp ? q[0] != 0.0 : q[0] > 0.0);
+        const int st = amp ? support_rect(q + 1, nsigma, MH, MW, r) : 1;
+        row[0] = (double)st;
+        if (st == 1 || st == 3) continue;
         for (int t = 0; t < 4; ++t) row[1 + t] = (double)r[t];
         const int tx0 = r[0] / RND_TILE, tx1 = r[1] / RND_TILE, ty0 = r[2] / RND_TILE, ty1 = r[3] / RND_TILE;
         row[5] = (double)((long long)(tx1 - tx0 + 1) * (ty1 - ty0 + 1));
@@ -356,29 +364,31 @@ const char* peak_fit_sizes(int n, int max_iter, int MH, int MW) {
     return nullptr;
 }
 
-// the fitted jobs sorted by column (ties by index)
-std::vector<int> sorted_by_column(const PeakFitPlan& p) {
-    std::vector<int> by_x(p.run);
-    std::sort(by_x.begin(), by_x.end(), [&](int a, int b) { return p.jobs[(size_t)a].cx < p.jobs[(size_t)b].cx || (p.jobs[(size_t)a].cx == p.jobs[(size_t)b].cx && a < b); });
+// the run jobs (PeakFitJob or ForcedJob: anything with a centre cx, cy) sorted by column (ties by index)
+template <class Job>
+std::vector<int> sorted_by_column(const std::vector<Job>& jobs, const std::vector<int>& run) {
+    std::vector<int> by_x(run);
+    std::sort(by_x.begin(), by_x.end(), [&](int a, int b) { return jobs[(size_t)a].cx < jobs[(size_t)b].cx || (jobs[(size_t)a].cx == jobs[(size_t)b].cx && a < b); });
     return by_x;
 }
+std::vector<int> sorted_by_column(const PeakFitPlan& p) { return sorted_by_column(p.jobs, p.run); }
 
 // Job e = by_x[s] looks at the stretch of the sorted jobs whose |cx_f - cx_e| (as the test below rounds it) is below `band`:
 // visit(f, D2) for every other job f in it, D2 = (cx_f - cx_e)^2 + (cy_f - cy_e)^2.  The stretch holds every f with D2 < band^2,
 // because dx*dx <= D2 and rounding is monotonic
-template <class Visit>
-void scan_band(const std::vector<PeakFitJob>& jobs, const std::vector<int>& by_x, size_t s, double band, Visit&& visit) {
+template <class Job, class Visit>
+void scan_band(const std::vector<Job>& jobs, const std::vector<int>& by_x, size_t s, double band, Visit&& visit) {
 #pragma clang fp contract(off)          // dx*dx + dy*dy: every product is rounded before it is used, whatever the build's default
     const size_t m = by_x.size();
     const int e = by_x[s];
-    const PeakFitJob& j = jobs[(size_t)e];
+    const Job& j = jobs[(size_t)e];
     // the band's left end by bisection on the sorted columns (it does not move monotonically when the radii differ)
     size_t lo = 0, hi = s;
     while (lo < hi) { const size_t mid = (lo + hi) / 2; if (j.cx - jobs[(size_t)by_x[mid]].cx < band) hi = mid; else lo = mid + 1; }
     for (size_t t = lo; t < m; ++t) {
         const int f = by_x[t];
         if (f == e) continue;
-        const PeakFitJob& g = jobs[(size_t)f];
+        const Job& g = jobs[(size_t)f];
         const double dx = g.cx - j.cx, dy = g.cy - j.cy;
         if (t > s && !(dx < band)) break;
         const double xx = dx * dx, yy = dy * dy;
@@ -471,6 +481,70 @@ void disc_residual_row(const PeakFitJob& j, const double* got, double* row) {
     for (int f = 0; f < DRES_FIELDS; ++f) row[f] = got[f];
     row[10] = (double)j.x0; row[11] = (double)j.x1; row[12] = (double)j.y0; row[13] = (double)j.y1;
     row[14] = (double)j.clipped; row[15] = (double)j.nneigh;
+}
+
+const char* plan_forced(const double* jobs, int n, double nsigma, int fit_bkg, int MH, int MW, bool have_map, bool have_out, ForcedPlan& p) {
+    p = ForcedPlan();
+    if (!have_map) return "null argument";
+    if (MH <= 0 || MW <= 0) return "MH, MW > 0 required";
+    if ((long long)MH * MW >= (1LL << 31)) return "image of 2^31 pixels or more";
+    if (!(nsigma >= 1.0 && nsigma <= 8.0)) return "nsigma outside [1, 8]";
+    if (fit_bkg != 0 && fit_bkg != 1) return "fit_bkg must be 0 or 1";
+    if (n < 0 || n > FORCED_JOBS_MAX) return "n outside 0 .. CY_FORCED_JOBS_MAX";
+    if (n > 0 && !(jobs && have_out)) return "null argument";
+    p.jobs.resize((size_t)n);
+    std::vector<double> half((size_t)n, 0.0);                 // hx of the run jobs
+    double hmax = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double* q = jobs + (size_t)i * FORCED_JOB_FIELDS;
+        ForcedJob& j = p.jobs[(size_t)i];
+        j = ForcedJob();
+        j.cx = q[0]; j.cy = q[1]; j.a = q[2]; j.b = q[3]; j.c = q[4]; j.bkg = q[5];
+        for (int k = 0; k < FORCED_NEIGH_MAX; ++k) j.neigh[k] = -1;
+        int r[4] = {0, -1, 0, -1};
+        j.status = std::isfinite(q[5]) ? support_rect(q, nsigma, MH, MW, r, &half[(size_t)i]) : 1;
+        j.x0 = r[0]; j.x1 = r[1]; j.y0 = r[2]; j.y1 = r[3];
+        if (j.status == 1 || j.status == 3) continue;
+        hmax = std::max(hmax, half[(size_t)i]);
+        p.run.push_back(i);
+    }
+    // neighbours: the run jobs sorted by column.  The rectangles of e and f share a column only when |floor(cx_e) - floor(cx_f)| <=
+    // hx_e + hx_f + 1, so |cx_f - cx_e| < hx_e + hmax + 2 as a real number and <= that once rounded: the band is one wider
+    const std::vector<int> by_x = sorted_by_column(p.jobs, p.run);
+    auto same = [](const ForcedJob& u, const ForcedJob& v) { return u.cx == v.cx && u.cy == v.cy && u.a == v.a && u.b == v.b && u.c == v.c; };
+    std::vector<std::pair<double, int>> cand;
+    for (size_t s = 0; s < by_x.size(); ++s) {
+        const int e = by_x[s];
+        ForcedJob& j = p.jobs[(size_t)e];
+        cand.clear();
+        scan_band(p.jobs, by_x, s, half[(size_t)e] + hmax + 3.0, [&](int f, double D2) {
+            const ForcedJob& g = p.jobs[(size_t)f];
+            if (g.x0 <= j.x1 && j.x0 <= g.x1 && g.y0 <= j.y1 && j.y0 <= g.y1) cand.emplace_back(D2, f);
+        });
+        std::partial_sort(cand.begin(), cand.end(), cand.end());      // all of them: a duplicate is dropped wherever it stands in the order
+        for (const std::pair<double, int>& cd : cand) {
+            const ForcedJob& g = p.jobs[(size_t)cd.second];
+            bool dup = same(g, j);
+            for (int k = 0; k < j.nneigh && !dup; ++k) dup = same(g, p.jobs[(size_t)j.neigh[k]]);
+            if (dup) ++j.ndup;
+            else if (j.nneigh < FORCED_NEIGH_MAX) j.neigh[j.nneigh++] = cd.second;
+            else j.crowded = 1;
+        }
+    }
+    return nullptr;
+}
+
+void forced_row(const ForcedJob& j, int fit_bkg, const double* got, double* row) {
+    for (int f = 0; f < FORCED_FIELDS; ++f) row[f] = 0.0;
+    if (!got) {
+        row[0] = (double)j.status;
+        row[17] = row[18] = row[19] = row[20] = -1.0;
+        return;
+    }
+    for (int f = 0; f < FORCED_FIELDS; ++f) row[f] = got[f];
+    row[3] = (double)(1 + j.nneigh + fit_bkg); row[4] = (double)j.nneigh; row[5] = (double)j.crowded; row[6] = (double)j.ndup;
+    row[17] = (double)j.x0; row[18] = (double)j.x1; row[19] = (double)j.y0; row[20] = (double)j.y1;
+    row[21] = j.status == 2 ? 1.0 : 0.0;
 }
 
 const char* plan_peak_groups(const double* jobs, int n, double link, int max_iter, int MH, int MW, bool have_map, bool have_out, PeakGroupPlan& p) {

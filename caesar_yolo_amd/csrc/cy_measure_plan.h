@@ -1,5 +1,5 @@
 // Host-side planning of the measurement entries (cy_measure_sources, cy_measure_islands, cy_deblend_islands, cy_fit_components,
-// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks, cy_fit_peak_groups, cy_disc_residuals): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
+// cy_fit_blends, cy_render_gaussians, cy_measure_residuals, cy_find_peaks, cy_atrous_step, cy_aperture_sums, cy_fit_peaks, cy_fit_peak_groups, cy_disc_residuals, cy_forced_fit): box windows, the island table, the fit and blend job tables with their pixel lists, and the write-back of the
 // fitted rows.  Plain C++: host pointers in, vectors out, no context and no HIP type, so that tests/host/measure_plan_main.cpp runs
 // it under the host sanitizers.  A planner returns null, or the message of the first source (in index order) it rejects.
 #pragma once
@@ -60,6 +60,12 @@ struct RenderPlan {
 };
 // signed_amp (cy_render_signed_gaussians): a component is admissible with A < 0 too (A != 0 in place of A > 0); nothing else differs.
 const char* plan_render(const double* comp, int m, double nsigma, int MH, int MW, RenderPlan& p, bool signed_amp = false);
+
+// The support rectangle of one Gaussian, shared by plan_render and plan_forced.  q: {x0, y0, a, b, c}; r: the rectangle {sx0, sx1,
+// sy0, sy1} as plan_render describes it, {0, -1, 0, -1} when there is none.  Returns 0, 1 (a field not finite, a <= 0, c <= 0 or
+// a*c - b*b <= 0), 2 (a capped half-width) or 3 (the rectangle misses the image).  hx_out, when given and the status is not 1: the
+// half-width in columns after the cap.
+int support_rect(const double* q, double nsigma, int MH, int MW, int* r, double* hx_out = nullptr);
 
 // cy_measure_residuals: the box windows and checked mask offsets, as plan_islands gives them (off[i][0] is ISL_OFF_TOO_LARGE for a
 // window above ISL_MAX_AREA pixels, off[i][1] the window's first mask byte)
@@ -132,6 +138,25 @@ void peak_fit_row(const PeakFitJob& j, const double* job, const double* got, dou
 // position of the largest |r| as -1 and zeros elsewhere.  Otherwise `got` is the row the kernel wrote: taken over, with the window,
 // clipped and nneigh of the plan.
 void disc_residual_row(const PeakFitJob& j, const double* got, double* row);
+
+// cy_forced_fit.  jobs: [n][FORCED_JOB_FIELDS] {x0, y0, a, b, c, bkg}, positions in image pixels.  Per job: status 1 when one of the
+// six fields is not finite or the shape is not admissible, otherwise the status and rectangle of support_rect (0, 2 or 3).  run: the
+// jobs of status 0 and 2 in increasing index, one workgroup each.  The NEIGHBOURS of a run job e are the other run jobs f whose
+// rectangle intersects e's (both clipped to the image), ordered by (D2, f) with D2 = dx*dx + dy*dy of the centres, every operation
+// rounded on its own.  Walking that order: a candidate whose x0, y0, a, b, c compare equal to e's or to those of a neighbour kept
+// before it is dropped and counted in ndup; otherwise it is kept while fewer than FORCED_NEIGH_MAX are, and sets crowded when they
+// are full.  Candidates come from the scan of the run jobs sorted by column (scan_band) over |cx_f - cx_e| < hx_e + hmax + 3, hmax
+// the largest half-width of a run job: the cost per job is the number of jobs in such a band, not n.  have_map, have_out: whether
+// the caller's pointers are non-null.  Returns the message of the first failed check, in this order: a null map; MH or MW <= 0; an
+// image of 2^31 pixels or more; nsigma outside [1, 8] or NaN; fit_bkg not 0 or 1; n outside [0, FORCED_JOBS_MAX]; with n > 0 a null
+// jobs or out pointer.
+struct ForcedPlan { std::vector<ForcedJob> jobs; std::vector<int> run; };
+const char* plan_forced(const double* jobs, int n, double nsigma, int fit_bkg, int MH, int MW, bool have_map, bool have_out, ForcedPlan& p);
+
+// Row [FORCED_FIELDS] of cy_forced_fit for job j.  A job the planner turned away (status 1 or 3, got == null): the status, the
+// window (fields 17 .. 20) as -1 and zeros elsewhere.  Otherwise `got` is the row the kernel wrote: taken over, with K, nneigh,
+// crowded, ndup, the window and capped of the plan.
+void forced_row(const ForcedJob& j, int fit_bkg, const double* got, double* row);
 
 // cy_fit_peak_groups.  jobs as for plan_peak_fits, whose statuses (1 / 5), windows, clipped flags and kept-neighbour lists are taken
 // over (p.fits).  Two status 0 jobs e, f with equal sign are LINKED when D2 < Lm * Lm, Lm = link * max(R_e, R_f), D2 formed as

@@ -33,7 +33,6 @@ constexpr int PK_GRID_MAX = 1 << 16;    // 32 rounds of the 2048 workgroups a 25
 constexpr int SCAN_T = 1024, SCAN_W = SCAN_T / 64;
 static_assert(PK_W * 4 == PEAK_SEG_WORDS, "one bitmap word per wave and pixel slot");
 
-__device__ __forceinline__ bool noisy_px(float r) { return r > 0.0f && r <= FLT_MAX; }      // NaN fails both tests
 __device__ __forceinline__ bool above_px(float u, float r, double k) { return valid_px(u) && noisy_px(r) && (double)u >= k * (double)r; }
 
 // the four values at p .. p + 3 of row-major map m, p being column ix of its row; 0 at and beyond column MW

@@ -1,5 +1,5 @@
 // The pixel test and the box window of the measurement kernels (cy_measure, cy_background, cy_islands, cy_deblend, cy_fit, cy_blend,
-// cy_residual): what "valid" means and how a window that arrives from the host is held inside the image, once.
+// cy_residual, cy_peaks, cy_forced): what "valid" means and how a window that arrives from the host is held inside the image, once.
 #pragma once
 #include "cy_kernels.h"
 #include <cfloat>
@@ -8,6 +8,7 @@ namespace cy {
 namespace {
 
 __device__ __forceinline__ bool valid_px(float v) { return v != 0.0f && fabsf(v) <= FLT_MAX; }      // NaN fails the second test
+__device__ __forceinline__ bool noisy_px(float r) { return r > 0.0f && r <= FLT_MAX; }             // a usable rms (cy_peaks, cy_forced); NaN fails both tests
 
 struct Win { int x0, y0; unsigned W, H, A; };
 

@@ -23,7 +23,7 @@ struct DevConv { void* w = nullptr; float* bias = nullptr; size_t wbytes = 0; fl
                  void* bneck = nullptr; };      // on a bottleneck's cv1: register-fragment weights of the fused cv1+cv2 kernel (bneck64.hip)
 
 // the measurement steps whose kernel time the context keeps (cy_ctx::step_ms)
-enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_PEAKGROUP, STEP_DISCRES, STEP_COUNT };
+enum MeasureStep { STEP_SOURCES = 0, STEP_ISLANDS, STEP_DEBLEND, STEP_FIT, STEP_BLEND, STEP_BACKGROUND, STEP_RENDER, STEP_RESIDUAL, STEP_PEAKS, STEP_ATROUS, STEP_APERTURE, STEP_PEAKFIT, STEP_PEAKGROUP, STEP_DISCRES, STEP_FORCED, STEP_COUNT };
 
 // Owner of device allocations: one hipMalloc per buffer, every one freed on destruction or reset().  Whoever needs device memory
 // beyond one launch holds one (the context: model weights, stage buffers and workspaces, counters; a kernel-level test entry: the
@@ -100,7 +100,7 @@ struct cy_ctx {
     bool mosaic_dirty = true;                           // cy_mosaic_prepare / cy_detect_fence ran on the caller's stream since the last cy_detect_tiles
     const void* seen_mosaic[16] = {nullptr}; int n_seen = 0;   // mosaic buffers already ordered behind the caller's stream in this pipeline
     int* counters = nullptr;                            // device: [0] degenerate boxes dropped by the IoU merge, [1] tiles whose candidates overflowed `cap`
-    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
+    double step_ms[STEP_COUNT] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // kernel time of the last launch of each measurement step (cy_*_kernel_ms)
     // optional per-launch timing of the forward ops (hipEvents on the caller's stream)
     bool profiling = false;
     bool split_last = false;                             // the last forward ran as two half-batches (debug reads see only one)
@@ -1537,6 +1537,8 @@ static_assert(CY_PFIT_JOB_FIELDS == PFIT_JOB_FIELDS && CY_PFIT_FIELDS == PFIT_FI
               CY_PFIT_NEIGH_MAX == PFIT_NEIGH_MAX && CY_PFIT_JOBS_MAX == PFIT_JOBS_MAX, "header and kernel disagree on the peak fit row");
 static_assert(CY_PGRP_FIELDS == PGRP_FIELDS && CY_PGRP_FIELDS == CY_BLEND_FIELDS + 8, "header and kernel disagree on the peak group row");
 static_assert(CY_DRES_FIELDS == DRES_FIELDS, "header and kernel disagree on the disc residual row");
+static_assert(CY_FORCED_JOB_FIELDS == FORCED_JOB_FIELDS && CY_FORCED_FIELDS == FORCED_FIELDS && CY_FORCED_NEIGH_MAX == FORCED_NEIGH_MAX &&
+              CY_FORCED_JOBS_MAX == FORCED_JOBS_MAX, "header and kernel disagree on the forced fit row");
 
 int cy_measure_sources(cy_ctx* c, const float* d_img, int MH, int MW, const double* h_boxes, int n, int ring, double* h_out, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");
@@ -1877,6 +1879,35 @@ int cy_disc_residuals(cy_ctx* c, const float* d_map, const float* d_model, int M
     return CY_OK;
 }
 
+int cy_forced_fit(cy_ctx* c, const float* d_map, const float* d_rms, int MH, int MW, const double* h_jobs, int n, double nsigma, int fit_bkg,
+                  double* h_out, void* stream) {
+#pragma clang fp contract(off)          // nsigma * nsigma is rounded once
+    if (!c) return fail(c, CY_ERR_ARG, "null argument");
+    ForcedPlan p;
+    if (const char* msg = plan_forced(h_jobs, n, nsigma, fit_bkg, MH, MW, d_map != nullptr, h_out != nullptr, p)) return fail(c, CY_ERR_ARG, msg);
+    if (n == 0) return CY_OK;
+    std::vector<double> got(p.run.size() * CY_FORCED_FIELDS);
+    if (!p.run.empty()) {
+        TimedLaunch t(c, stream);
+        ForcedArgs a{};
+        a.map = d_map; a.rms = d_rms; a.MH = MH; a.MW = MW; a.n = n; a.nrun = (int)p.run.size();
+        a.ns2 = nsigma * nsigma; a.fit_bkg = fit_bkg;
+        a.jobs = t.upload(p.jobs.data(), p.jobs.size());
+        a.run = t.upload(p.run.data(), p.run.size());
+        a.out = t.scratch<double>(got.size());
+        t.download(got.data(), a.out, got.size());
+        const int rc = t.run(STEP_FORCED, [&](hipStream_t s) { return launch_forced(a, s); });
+        if (rc != CY_OK) return rc;                                            // h_out as it was
+    }
+    size_t next = 0;                                                           // p.run is in increasing job index
+    for (int i = 0; i < n; ++i) {
+        const bool ran = next < p.run.size() && p.run[next] == i;
+        forced_row(p.jobs[(size_t)i], fit_bkg, ran ? &got[next * CY_FORCED_FIELDS] : nullptr, h_out + (size_t)i * CY_FORCED_FIELDS);
+        next += ran;
+    }
+    return CY_OK;
+}
+
 // kernel time of the last call of a measurement step that launched (hipEvents around the launch); -1 before it and after a failed call
 static int step_kernel_ms(const cy_ctx* c, MeasureStep step, double* out_ms) {
     if (!c || !out_ms) return CY_ERR_ARG;
@@ -1897,6 +1928,7 @@ int cy_aperture_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_
 int cy_peakfit_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKFIT, out_ms); }
 int cy_peakgroup_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_PEAKGROUP, out_ms); }
 int cy_disc_residual_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_DISCRES, out_ms); }
+int cy_forced_kernel_ms(const cy_ctx* c, double* out_ms) { return step_kernel_ms(c, STEP_FORCED, out_ms); }
 
 int cy_expand_background(cy_ctx* c, const double* h_mesh, int ncy, int ncx, int cell, int MH, int MW, float* d_bkg, float* d_rms, void* stream) {
     if (!c) return fail(c, CY_ERR_ARG, "null argument");

@@ -32,6 +32,7 @@ class Analyzer(object):
         # NEW: --measure_sources and the steps after it (measure.plan, measure.Chain); beam_area / wcs / wcs_origin are set by the
         # caller that read the header (SFinder.run)
         self.beam_area, self.wcs, self.wcs_origin = 0, None, (0, 0)
+        self.freq, self.forced_maps = None, None                  # --forced_fit: the image's frequency and the other maps (inference.load_forced_maps)
         self.merge_overlap_iou_thr_soft = config['merge_overlap_iou_thr_soft']
         self.merge_overlap_iou_thr_hard = config['merge_overlap_iou_thr_hard']
         self.write_to_json = config.get('save_catalog', True)
@@ -155,7 +156,7 @@ class Analyzer(object):
         elif steps:
             try:
                 chain = measure.Chain(det, frame, self.results["objs"], self.config, self.beam_area, self.wcs, box_origin=(xmin, ymin),
-                                      wcs_origin=self.wcs_origin).run(steps)
+                                      wcs_origin=self.wcs_origin, freq=self.freq, forced_maps=self.forced_maps).run(steps)
                 if chain.ndef == 0:
                     logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
                 chain.save_maps(self.outfile_json or ('out_' + str(self.image_id) + '.json'))

@@ -170,6 +170,35 @@ class MosaicSource(object):
         return t, x0, y0
 
 
+def load_forced_maps(config, ny, nx, crop=None):
+    """The maps of --forced_images for measure.Chain (its forced_maps): per path utils.read_fits_image (the payload stays a memory
+    map), its whole shape checked against the whole image's ny x nx, then cropped like the image with crop = (xmin, xmax, ymin, ymax)
+    of the serial run, its beam area and frequency from its own header, and `upload`, which brings it to the device as the mosaic
+    is (MosaicSource.region).  -> the list, or None after an error message when a map cannot be read or its shape is not the image's."""
+    maps, tags = [], set()
+    for path in measure.forced_config(config)[2]:
+        res = utils.read_fits_image(path) if os.path.splitext(path)[1] == '.fits' else None
+        if res is None:
+            logger.error("Failed to read forced-photometry map %s!" % path)
+            return None
+        data, header = res
+        if tuple(data.shape) != (ny, nx):                         # the whole map against the whole image: a crop that fits inside both proves nothing
+            logger.error("Forced-photometry map %s has shape %s, the image %s!" % (path, tuple(data.shape), (ny, nx)))
+            return None
+        if crop is not None:
+            data = data[crop[2]:crop[3], crop[0]:crop[1]]
+        tag = os.path.splitext(os.path.basename(path))[0]
+        while tag in tags or tag == "self":
+            tag += "_"
+        tags.add(tag)
+
+        def upload(det, data=data):
+            return MosaicSource(data, big_endian=True).region(det, 0, data.shape[1], 0, data.shape[0])[0]
+        maps.append({"tag": tag, "path": path, "freq": measure.header_frequency(header), "beam_area": measure.header_beam_area(header),
+                     "upload": upload})
+    return maps
+
+
 class TileEngine(object):
     """Runs the per-tile path for this rank's share of a tile grid and merges all ranks' detections.
 
@@ -433,6 +462,8 @@ class SFinder(object):
         self.outfile_ds9 = ""
         self.runtime = 0.0
         self.stats = {}
+        self.header = None
+        self.forced_maps = None                                # --forced_fit: the maps of --forced_images (load_forced_maps)
 
     # ---- shared
     def _load_mosaic(self, resident=True):
@@ -501,6 +532,7 @@ class SFinder(object):
             logger.error("Failed to read image %s!" % path)
             return -1
         data, self.header = res
+        full_ny, full_nx = data.shape
         # sub-image of the serial run (caesar_yolo/inference.py:499-505 -> utils.read_fits_crop, utils.py:340-394): ranges all 0 / -1 =
         # the whole image; otherwise [ymin:ymax, xmin:xmax] with the max pixel EXCLUDED, the same argument errors, and catalog
         # coordinates relative to the crop (the reference hands the crop to Analyzer.predict without an origin)
@@ -527,6 +559,11 @@ class SFinder(object):
         # --measure_sources: what the Analyzer needs beside the pixels (the crop's origin places its pixels in the frame of the WCS)
         analyzer.beam_area, analyzer.wcs = self.beamArea, self.wcs
         analyzer.wcs_origin = (rng[0], rng[2]) if not all(v in (0, -1) for v in rng) else (0, 0)
+        if measure.wants_forced(c):                               # --forced_fit: the other maps, cropped like the image, checked before detection
+            analyzer.freq = measure.header_frequency(self.header)
+            analyzer.forced_maps = load_forced_maps(c, full_ny, full_nx, None if all(v in (0, -1) for v in rng) else rng)
+            if analyzer.forced_maps is None:
+                return -1
         if analyzer.predict(image=data, image_id=self.image_id, header=self.header) < 0:
             logger.error("Failed to run model prediction on image %s!" % path)
             return -1
@@ -577,7 +614,8 @@ class SFinder(object):
         times and counts to the stats."""
         t0 = time.time()
         img, ox, oy = mosaic.region(det, 0, self.nx, 0, self.ny)
-        chain = measure.Chain(det, img, src, self.config, self.beamArea, self.wcs, box_origin=(ox, oy)).run(steps, self.stats, t0)
+        chain = measure.Chain(det, img, src, self.config, self.beamArea, self.wcs, box_origin=(ox, oy), freq=measure.header_frequency(self.header),
+                              forced_maps=self.forced_maps).run(steps, self.stats, t0)
         if chain.ndef == 0:
             logger.warning("Background mesh: no cell holds %d valid pixels, bkg_map and rms_map are 0." % chain.min_pix)
         chain.save_maps(self.outfile_json or ('catalog_' + str(self.image_id) + '.json'))
@@ -594,6 +632,9 @@ class SFinder(object):
             return -1
         det, mosaic = m
         c = self.config
+        self.forced_maps = load_forced_maps(c, self.ny, self.nx) if measure.wants_forced(c) else None      # --forced_fit: checked before detection
+        if measure.wants_forced(c) and self.forced_maps is None:
+            return -1
         tsx, tsy = (c['tile_xsize'], c['tile_ysize']) if c['split_image_in_tiles'] else (self.nx, self.ny)
         stx, sty = (c['tile_xstep'], c['tile_ystep']) if c['split_image_in_tiles'] else (1, 1)
         grid = utils.generate_tiles(0, self.nx - 1, 0, self.ny - 1, tsx, tsy, stx, sty)

@@ -45,6 +45,10 @@ PGRP_NAMES = BLEND_NAMES + ("wx0", "wx1", "wy0", "wy1", "clipped", "nexcluded", 
 CY_DRES_FIELDS = 16
 DRES_NAMES = ("status", "npix", "nexcluded", "sum", "sumsq", "maxabs", "x_max", "y_max", "model_sum", "reserved", "wx0", "wx1", "wy0", "wy1",
               "clipped", "nneigh")
+CY_FORCED_JOB_FIELDS, CY_FORCED_FIELDS, CY_FORCED_NEIGH_MAX, CY_FORCED_JOBS_MAX = 6, 24, 7, 1 << 20
+FORCED_JOB_NAMES = ("x0", "y0", "a", "b", "c", "bkg")
+FORCED_NAMES = ("status", "npix", "nexcluded", "K", "nneigh", "crowded", "ndup", "amp", "amp_var", "bkg_off", "bkg_var", "cov_amp_bkg", "chi2",
+                "syy", "n00", "b0", "corr_max", "wx0", "wx1", "wy0", "wy1", "capped", "reserved0", "reserved1")
 CY_BKG_FIELDS = 8
 BKG_NAMES = ("n0", "n", "bkg", "rms", "L", "H", "rounds", "reserved")
 OP_BKG, OP_SHIFT, OP_CLIP, OP_ZSCALE, OP_HISTEQ, OP_MINMAX = 1, 2, 3, 4, 5, 6
@@ -65,7 +69,7 @@ EXPORTS = [
     "cy_render_gaussians", "cy_render_kernel_ms", "cy_render_signed_gaussians", "cy_measure_residuals", "cy_residual_kernel_ms", "cy_find_peaks", "cy_peaks_kernel_ms",
     "cy_atrous_step", "cy_atrous_kernel_ms", "cy_aperture_sums", "cy_aperture_kernel_ms",
     "cy_fit_peaks", "cy_peakfit_kernel_ms", "cy_fit_peak_groups", "cy_peakgroup_kernel_ms",
-    "cy_disc_residuals", "cy_disc_residual_kernel_ms",
+    "cy_disc_residuals", "cy_disc_residual_kernel_ms", "cy_forced_fit", "cy_forced_kernel_ms",
 ]
 
 
@@ -233,6 +237,8 @@ def load():
         "cy_peakgroup_kernel_ms": (C.c_int, [vp, dp]),
         "cy_disc_residuals": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, C.c_int, dp, vp]),
         "cy_disc_residual_kernel_ms": (C.c_int, [vp, dp]),
+        "cy_forced_fit": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, dp, vp]),
+        "cy_forced_kernel_ms": (C.c_int, [vp, dp]),
         "cy_measure_background": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, vp]),
         "cy_background_kernel_ms": (C.c_int, [vp, dp]),
         "cy_expand_background": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

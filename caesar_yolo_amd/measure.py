@@ -63,6 +63,13 @@ fitted entry the group fit where there is one, else the single fit, `cy_render_s
 lib.DRES_NAMES, keys GRES_KEYS on every entry (annotate_peak_residuals), and `cy_find_peaks` searches it in both signs: the lists
 "residual_peaks_left" / "residual_holes_left" and SOURCE_LEFT_KEYS on every source.  Chain.run() calls Chain.subtract() last.
 
+--forced_fit measures every rendered component again with its position and shape FIXED: forced_jobs() turns the selection of the
+residual step into jobs, `cy_forced_fit` (HipDetector.forced_fit) solves per job the amplitudes of the component and its
+overlapping neighbours and a local constant by weighted linear least squares, raw rows lib.FORCED_NAMES, on the detection image
+and on every co-registered map of --forced_images; annotate_forced() writes the key "forced" (one dict per map, FORCED_KEYS) and,
+when two maps carry a frequency, the spectral index keys FORCED_ALPHA_KEYS on every component.  Chain.run() calls Chain.forced()
+after the residual step's own followers.
+
 Everything below is float64 arithmetic on those rows: given the rows, the keys are deterministic.
 
 plan() names the steps a config asks for and Chain runs them on one image: the one place that knows their order, what each hands to
@@ -86,6 +93,7 @@ MEAS, ISL, DBL, COMP, FIT, BLEND = (_fields(t) for t in (L.MEAS_NAMES, L.ISL_NAM
 RND, RES, BKG, PEAK = _fields(L.RND_NAMES), _fields(L.RES_NAMES), _fields(L.BKG_NAMES), _fields(L.PEAK_NAMES)
 APER, APER_RING = _fields(L.APER_NAMES), _fields(L.APER_RING_NAMES)
 PFIT, PFIT_JOB, PGRP, DRES = _fields(L.PFIT_NAMES), _fields(L.PFIT_JOB_NAMES), _fields(L.PGRP_NAMES), _fields(L.DRES_NAMES)
+FORCED = _fields(L.FORCED_NAMES)
 _PFIT_JOB_PARAMS = [getattr(PFIT_JOB, k) for k in "A x0 y0 a b c".split()]
 _PFIT_PARAMS = [getattr(PFIT, k) for k in "A x0 y0 a b c".split()]
 _MEAS_USED = [getattr(MEAS, k) for k in "npix bkg rms peak x_peak y_peak sum sw swx swy".split()]
@@ -125,6 +133,9 @@ GBLEND_KEYS = ("gblend_group", "gblend_size", "gblend_slot", "gblend_status", "g
 GRES_KEYS = ("gres_subtracted", "gres_source", "gres_render_status", "gres_npix", "gres_mean", "gres_rms", "gres_max", "gres_x_max", "gres_y_max",
              "gres_ratio", "gres_chi2", "gres_model_flux")
 SOURCE_LEFT_KEYS = ("res_npeaks_left", "res_nholes_left")
+FORCED_KEYS = ("image", "status", "npix", "nneigh", "crowded", "peak", "peak_err", "bkg", "chi2", "corr_max", "flux", "flux_err")
+FORCED_ALPHA_KEYS = ("forced_alpha", "forced_alpha_err", "forced_alpha_n")
+FORCED_STATS = ("forced_ms", "forced_kernel_ms", "forced_maps", "forced_jobs", "forced_fitted", "forced_crowded", "forced_singular")
 PEAK_LIST_NAMES = ("residual_peaks", "residual_holes", "residual_scale_peaks")     # the order the fitted lists are walked in
 MAD_TO_SIGMA = 1.482602218505602   # 1 / Phi^-1(3/4): the standard deviation of a normal distribution in units of its MAD
 SCALES_MAX = 6                     # most scales of --residual_scales: step 2^5 = 32 on the last
@@ -615,6 +626,127 @@ def annotate_residuals(sources, raw, index, render_rows, beam_area, origin=(0, 0
         if ba > 0.0:
             s["res_flux"], s["res_model_flux"] = float(r[RES.sum_isl]) / ba, float(r[RES.model_isl]) / ba
         s["res_ratio"] = s["res_rms"] / rms if rms > 0.0 else None
+    return sources
+
+
+# ---- forced photometry (--forced_fit, --forced_images)
+def forced_config(config):
+    """(nsigma, fit_bkg, the list of map paths) of --forced_fit from a config dictionary; forced_images is a list or a
+    comma-separated string."""
+    images = config.get('forced_images') or []
+    if isinstance(images, str):
+        images = [p for p in (q.strip() for q in images.split(',')) if p]
+    return float(config.get('forced_nsigma', 3.0)), bool(int(config.get('forced_fit_bkg', 1))), list(images)
+
+
+def wants_forced(config):
+    """Whether Chain.forced() runs: forced_fit, or a map named in forced_images."""
+    return bool(config.get('forced_fit', False)) or bool(forced_config(config)[2])
+
+
+def header_beam_area(h):
+    """The beam area in pixels from a FITS header as SFinder._beam_info forms it: pi BMAJ BMIN / (4 ln 2) / |CDELT1 CDELT2|; 0 when
+    one of CDELT1, CDELT2, BMAJ, BMIN, BPA is missing or there is no header."""
+    if h is None or any(k not in h for k in ("CDELT1", "CDELT2", "BMAJ", "BMIN", "BPA")):
+        return 0
+    return float(np.pi * h["BMAJ"] * h["BMIN"] / (4 * np.log(2)) / np.abs(h["CDELT1"] * h["CDELT2"]))
+
+
+def header_frequency(h):
+    """The frequency of a map from its FITS header: the first of RESTFRQ, RESTFREQ, FREQ, or CRVAL3 / CRVAL4 whose CTYPE starts with
+    FREQ, that holds a positive finite number (a continuum map's RESTFRQ = 0 is passed over); None without one."""
+    if h is None:
+        return None
+    cand = [h[k] for k in ("RESTFRQ", "RESTFREQ", "FREQ") if k in h]
+    cand += [h["CRVAL%d" % ax] for ax in (3, 4) if str(h["CTYPE%d" % ax] if "CTYPE%d" % ax in h else "").strip().upper().startswith("FREQ") and "CRVAL%d" % ax in h]
+    for v in cand:
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            continue
+        if math.isfinite(v) and v > 0.0:
+            return v
+    return None
+
+
+def forced_jobs(comp, index, sources, use_map=False, mesh=None, cell=0):
+    """The jobs of cy_forced_fit ([m, CY_FORCED_JOB_FIELDS] {x0, y0, a, b, c, bkg}) for the components render_selection() chose: comp
+    [m, 6] {A, x0, y0, a, b, c} in the pixel frame of the map, index [m, 2] {source, component}.  bkg without a mesh: the background
+    of the job's source (bkg_map with use_map, else bkg), the detection image's own; with `mesh` ([ncy, ncx, 2] of another map, cell
+    wide): sample_mesh() of its bkg plane at the component's centre; mesh == 0 (a scalar): 0."""
+    comp = np.asarray(comp, np.float64).reshape(-1, 6)
+    index = np.asarray(index, np.int64).reshape(-1, 2)
+    jobs = np.zeros((comp.shape[0], L.CY_FORCED_JOB_FIELDS), np.float64)
+    jobs[:, :5] = comp[:, 1:]
+    if comp.shape[0] == 0:
+        return jobs
+    if mesh is None:
+        jobs[:, 5] = _bkg_of(sources, use_map)[index[:, 0]]
+    elif np.ndim(mesh) > 0:
+        jobs[:, 5] = sample_mesh(np.asarray(mesh, np.float64)[:, :, 0], cell, comp[:, 1], comp[:, 2])
+    return jobs
+
+
+def forced_alpha(points):
+    """The spectral index of one component.  points: (nu, S, sigma_S) per map; those with S > 0 and a finite sigma_S > 0 enter a
+    weighted least-squares line of ln S on ln nu with weights (S / sigma_S)^2 (the inverse variance of ln S to first order).
+    -> (alpha, alpha_err, n): with x = ln nu about its weighted mean, the slope sum w x y / sum w x^2, its error 1 / sqrt(sum w x^2),
+    and the number of points; (None, None, None) with fewer than two points or fewer than two different frequencies."""
+    pts = [(math.log(nu), math.log(S), (S / e) ** 2) for nu, S, e in points
+           if nu and S is not None and e is not None and S > 0.0 and e > 0.0 and math.isfinite(S) and math.isfinite(e)]
+    if len(pts) < 2 or len({x for x, _, _ in pts}) < 2:
+        return None, None, None
+    sw = sum(w for _, _, w in pts)
+    xm = sum(w * x for x, _, w in pts) / sw
+    sxx, sxy = sum(w * (x - xm) * (x - xm) for x, _, w in pts), sum(w * (x - xm) * y for x, y, w in pts)
+    if not sxx > 0.0:
+        return None, None, None
+    return sxy / sxx, 1.0 / math.sqrt(sxx), len(pts)
+
+
+def annotate_forced(sources, index, maps):
+    """Adds "forced" to every component dict of every source (in place; returns the list), and FORCED_ALPHA_KEYS when at least two
+    maps carry a frequency.  index: [m, 2] {source, component} of render_selection(); maps: one dict per measured map, in the order
+    they were measured: tag, rows ([m, CY_FORCED_FIELDS] of cy_forced_fit), jobs ([m, CY_FORCED_JOB_FIELDS]), beam_area (0: none),
+    freq (None: none) and err_scale ([m] what sqrt(amp_var) is multiplied with: 1 for a weighted fit, the source's rms for an
+    unweighted one; None, or an entry that is not > 0: the errors are None).  Per rendered component "forced" is a list with one dict of FORCED_KEYS per map:
+      image = tag; status, npix, nneigh, crowded as in the row
+      peak = amp, peak_err = sqrt(amp_var) * err_scale, bkg = the job's bkg + bkg_off, chi2, corr_max as in the row
+      flux = peak * 2 pi / sqrt(a c - b^2) / beam_area of that map, flux_err likewise from peak_err; None without a beam
+    The value keys (peak .. flux_err) are None for a status other than 0 and 2.  A component that was not rendered gets None.
+    forced_alpha, forced_alpha_err, forced_alpha_n: forced_alpha() over the maps with a frequency and status 0 or 2, S the flux when
+    every map with a frequency has a beam, else the peak."""
+    index = np.asarray(index, np.int64).reshape(-1, 2)
+    with_freq = [m for m in maps if m.get("freq")]
+    use_flux = bool(with_freq) and all(m.get("beam_area") for m in with_freq)
+    for s in sources:
+        for d in s.get("components") or []:
+            d["forced"] = None
+    for t, (i, k) in enumerate(index):
+        d = sources[int(i)]["components"][int(k)]
+        out, points = [], []
+        for m in maps:
+            r, j = np.asarray(m["rows"], np.float64)[t], np.asarray(m["jobs"], np.float64)[t]
+            e = {key: None for key in FORCED_KEYS}
+            st = int(r[FORCED.status])
+            e.update(image=m["tag"], status=st, npix=int(r[FORCED.npix]), nneigh=int(r[FORCED.nneigh]), crowded=int(r[FORCED.crowded]))
+            if st in (0, 2):
+                scale = None if m.get("err_scale") is None else float(np.asarray(m["err_scale"], np.float64)[t])
+                if scale is not None and not scale > 0.0:      # an unweighted fit of a source without a noise: no error
+                    scale = None
+                e["peak"], e["bkg"] = float(r[FORCED.amp]), float(j[5]) + float(r[FORCED.bkg_off])
+                e["chi2"], e["corr_max"] = float(r[FORCED.chi2]), float(r[FORCED.corr_max])
+                e["peak_err"] = None if scale is None else math.sqrt(max(float(r[FORCED.amp_var]), 0.0)) * scale
+                ba = float(m["beam_area"]) if m.get("beam_area") else 0.0
+                if ba > 0.0:
+                    f = 2.0 * math.pi / math.sqrt(j[2] * j[4] - j[3] * j[3]) / ba
+                    e["flux"], e["flux_err"] = e["peak"] * f, None if e["peak_err"] is None else e["peak_err"] * f
+                if m.get("freq"):
+                    points.append((float(m["freq"]), e["flux"] if use_flux else e["peak"], e["flux_err"] if use_flux else e["peak_err"]))
+            out.append(e)
+        d["forced"] = out
+        if len(with_freq) >= 2:
+            d["forced_alpha"], d["forced_alpha_err"], d["forced_alpha_n"] = forced_alpha(points)
     return sources
 
 
@@ -1140,7 +1272,8 @@ def wants_peaks(config):
 def peak_lists(chain):
     """What a catalog file carries beside its sources after Chain.run(): {"residual_peaks": [...]} and, when holes were searched,
     "residual_holes", and "residual_scale_peaks" when the scales were, and "residual_peaks_left" / "residual_holes_left" when the
-    fitted peaks were subtracted; empty when the chain (or None) did not search."""
+    fitted peaks were subtracted, and "forced_images" (tag, path, freq, beam_area, mesh_ndef per measured map) after the forced
+    fits; empty when the chain (or None) did none of these."""
     out = {}
     if chain is not None and chain.peak_list is not None:
         out["residual_peaks"] = chain.peak_list
@@ -1150,6 +1283,8 @@ def peak_lists(chain):
         out["residual_scale_peaks"] = chain.scale_list
     if chain is not None and chain.left_peak_list is not None:
         out["residual_peaks_left"], out["residual_holes_left"] = chain.left_peak_list, chain.left_hole_list
+    if chain is not None and chain.forced_images is not None:
+        out["forced_images"] = chain.forced_images
     return out
 
 
@@ -1277,11 +1412,12 @@ def plan(config):
     step of STEPS) imply the residual step, whose map they search, and the mesh, whose rms map is their noise; residual_scales > 0
     (Chain.scale_peaks, no step either) implies exactly the same, and so do peak_apertures (Chain.apertures), fit_peaks
     (Chain.peak_fits), fit_peak_groups (Chain.peak_groups, which implies fit_peaks) and subtract_peaks (Chain.subtract, which
-    implies fit_peaks too), which measure on the residual map with the rms map of the mesh but turn no search on."""
+    implies fit_peaks too), which measure on the residual map with the rms map of the mesh but turn no search on.  forced_fit or
+    forced_images (Chain.forced, no step either) imply the residual step like save_residual_maps, and nothing else."""
     on = {k for k in ("measure_sources", "bkg_map", "save_bkg_maps", "measure_islands", "deblend_islands", "fit_components", "fit_blends",
                       "residual_map", "save_residual_maps", "residual_peaks", "residual_holes") if config.get(k, False)}
     peaks = bool(on & {"residual_peaks", "residual_holes"}) or wants_scales(config) or wants_apertures(config) or wants_peak_fits(config) or wants_peak_groups(config) or wants_subtract(config)
-    residual = peaks or bool(on & {"residual_map", "save_residual_maps"})
+    residual = peaks or bool(on & {"residual_map", "save_residual_maps"}) or wants_forced(config)
     fit = residual or bool(on & {"fit_components", "fit_blends"})
     deblend = fit or "deblend_islands" in on
     islands = deblend or "measure_islands" in on
@@ -1300,8 +1436,15 @@ class Chain(object):
     those pixels + box_origin, the catalog coordinates of pixel [0, 0] of img_dev (fit_rows, blend_rows); sky positions are taken
     at catalog coordinates + wcs_origin, the position of catalog coordinate (0, 0) in the frame of the WCS."""
 
-    def __init__(self, det, img_dev, sources, config, beam_area=0, wcs=None, box_origin=(0, 0), wcs_origin=(0, 0)):
+    def __init__(self, det, img_dev, sources, config, beam_area=0, wcs=None, box_origin=(0, 0), wcs_origin=(0, 0), freq=None, forced_maps=None):
         c = config
+        # --forced_fit: freq is the detection image's frequency; forced_maps the other maps, one dict each: tag, path, freq, beam_area
+        # and upload, a callable (det) -> the map on the device, of img_dev's shape
+        self.want_forced = wants_forced(c)
+        self.forced_nsigma, self.forced_fit_bkg, _ = forced_config(c)
+        self.freq, self.forced_maps, self.image_path = freq, list(forced_maps or []), c.get('image_path')
+        self.render_comp = self.render_index = self.render_rows = None
+        self.forced_rows = self.forced_job_rows = self.forced_images = self.forced_stats = self.forced_comp = self.forced_index = None
         self.det, self.img, self.sources, self.beam_area, self.wcs = det, img_dev, sources, beam_area, wcs
         self.box_origin, self.wcs_origin = box_origin, wcs_origin
         self.ring = int(c.get('measure_ring', 8))
@@ -1432,6 +1575,7 @@ class Chain(object):
             comp, index, ndup = render_selection(src, self.fit_pixel_rows, self.blend_pixel_rows)
         bkg_dev = self.det.expand_background(self.mesh, self.cell, self.img.shape, want=("bkg",))[0] if self.use_map else None
         rows, self.model, self.resid = self.det.render_gaussians(self.img, comp, self.nsigma, bkg_dev)
+        self.render_comp, self.render_index, self.render_rows = comp, index, rows
         if src:
             raw = self.det.measure_residuals(self.img, self.model, self.boxes, _bkg_of(src, self.use_map), self.masks)
             annotate_residuals(src, raw, index, rows, self.beam_area, self.box_origin, self.use_map)
@@ -1648,8 +1792,67 @@ class Chain(object):
         st["subtract_ms"] = 1e3 * (time.time() - t1)
         self.subtract_stats = st
 
+    def forced(self):
+        """After residual(): forced_jobs() for the components it rendered (.render_comp / .render_index with a render status of 0 or 2;
+        kept in .forced_comp / .forced_index), then one cy_forced_fit
+        call per map, with the nsigma and fit_bkg of forced_config(), and annotate_forced().
+          self         the detection image; bkg of a job = its source's background, d_rms = the expanded rms map of the mesh when the
+                       background step ran (weighted: the errors are sqrt(C_00)), else none (the errors are sqrt(C_00) times
+                       the source's rms, as annotate_fits scales its own)
+          other maps   in the order of forced_maps: uploaded (upload(det)), its own mesh by cy_measure_background / fill_mesh with
+                       this chain's parameters, bkg of a job = sample_mesh at the component's centre, d_rms = its expanded rms
+                       map; with no defined cell it is measured unweighted with bkg 0 and its errors are None.  The device copy
+                       is dropped after its call
+        Leaves .forced_rows / .forced_job_rows ({tag: rows} as the library gave / took them), .forced_images (what the catalog
+        lists) and .forced_stats (FORCED_STATS; the kernel time summed over the calls that launched)."""
+        t1 = time.time()
+        det, src = self.det, self.sources
+        # what the model map holds: a selected component that the render call turned away (status 1 or 3) is not forced either
+        shown = np.isin(np.asarray(self.render_rows, np.float64).reshape(-1, L.CY_RND_FIELDS)[:, RND.status], _FITTED)
+        comp, index = self.render_comp[shown], np.asarray(self.render_index, np.int64).reshape(-1, 2)[shown]
+        maps, listed = [], []
+        self.forced_rows, self.forced_job_rows = {}, {}
+        self.forced_comp, self.forced_index = comp, index
+        st = dict.fromkeys(FORCED_STATS, 0)
+        st["forced_kernel_ms"] = 0.0
+
+        def call(tag, dev, rms_dev, jobs, beam_area, freq, err_scale):
+            rows = det.forced_fit(dev, rms_dev, jobs, self.forced_nsigma, self.forced_fit_bkg)
+            if np.isin(rows[:, FORCED.status], (0.0, 2.0, 4.0, 5.0)).any():      # a call without a runnable job launches nothing
+                st["forced_kernel_ms"] += max(det.forced_kernel_ms(), 0.0)
+            self.forced_rows[tag], self.forced_job_rows[tag] = rows, jobs
+            maps.append({"tag": tag, "rows": rows, "jobs": jobs, "beam_area": beam_area, "freq": freq, "err_scale": err_scale})
+            status = rows[:, FORCED.status]
+            st["forced_maps"] += 1
+            st["forced_jobs"] += int(rows.shape[0])
+            st["forced_fitted"] += int(np.isin(status, _FITTED).sum())
+            st["forced_crowded"] += int((rows[:, FORCED.crowded] > 0).sum())
+            st["forced_singular"] += int((status == 4.0).sum())
+
+        m = comp.shape[0]
+        rms_dev = det.expand_background(self.mesh, self.cell, self.img.shape, want=("rms",))[1] if self.use_map else None
+        scale = np.ones(m) if self.use_map else np.array([_rms_of(src[int(i)], False) for i in index[:, 0]], np.float64).reshape(m)
+        call("self", self.img, rms_dev, forced_jobs(comp, index, src, self.use_map), self.beam_area, self.freq, scale)
+        listed.append({"tag": "self", "path": self.image_path, "freq": self.freq, "beam_area": float(self.beam_area) if self.beam_area else 0.0,
+                       "mesh_ndef": self.ndef if self.use_map else None})
+        del rms_dev
+        for fm in self.forced_maps:
+            dev = fm["upload"](det)
+            if tuple(int(v) for v in dev.shape) != (self.MH, self.MW):
+                raise L.CyError("forced_fit: map %s has shape %s, the image %s" % (fm["path"], tuple(dev.shape), (self.MH, self.MW)))
+            mesh, ndef = fill_mesh(det.measure_background(dev, cell=self.cell, k=self.clip_sigma, niter=self.clip_iters), self.min_pix)
+            rms_dev = det.expand_background(mesh, self.cell, dev.shape, want=("rms",))[1] if ndef > 0 else None
+            jobs = forced_jobs(comp, index, src, mesh=mesh if ndef > 0 else 0.0, cell=self.cell)
+            call(fm["tag"], dev, rms_dev, jobs, fm.get("beam_area") or 0, fm.get("freq"), np.ones(m) if ndef > 0 else None)
+            listed.append({"tag": fm["tag"], "path": fm["path"], "freq": fm.get("freq"), "beam_area": float(fm.get("beam_area") or 0.0), "mesh_ndef": int(ndef)})
+            del dev, rms_dev
+        annotate_forced(src, index, maps)
+        self.forced_images = listed
+        st["forced_ms"] = 1e3 * (time.time() - t1)
+        self.forced_stats = st
+
     def run(self, steps, stats=None, t0=None):
-        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures(), peak_fits(), peak_groups() and subtract(), each when the
+        """The steps named in `steps` (plan()) in the order of STEPS, then peaks(), scale_peaks(), apertures(), peak_fits(), peak_groups(), subtract() and forced(), each when the
         config asks for it and the residual step ran.  stats: a dictionary that takes, per step that ran, <step>_ms
         (wall time), the kernel times and the counts; t0: when the first step's clock started, if before this call."""
         det, src = self.det, self.sources
@@ -1701,6 +1904,10 @@ class Chain(object):
             self.subtract()
             if stats is not None:
                 stats.update(self.subtract_stats)
+        if self.want_forced and "residual" in steps:
+            self.forced()
+            if stats is not None:
+                stats.update(self.forced_stats)
         return self
 
     def save_maps(self, catalog_path):

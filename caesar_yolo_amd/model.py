@@ -670,6 +670,27 @@ class HipDetector(object):
         """Kernel time of the last disc_residuals call that launched in ms (hipEvents around the launch); -1 before the first."""
         return self._kernel_ms(self.lib.cy_disc_residual_kernel_ms)
 
+    # ---- forced photometry (the amplitudes of fixed shapes on any map)
+    def forced_fit(self, map_dev, rms_dev, jobs, nsigma=3.0, fit_bkg=True):
+        """The amplitude of a Gaussian of fixed position and shape per job on map_dev, solved together with its overlapping
+        neighbours' and a local constant (cy_forced_fit).  map_dev: a contiguous 2-D float32 device map; rms_dev: a noise map of its
+        shape, or None (unit weights); jobs: [n, CY_FORCED_JOB_FIELDS] float64 (lib.FORCED_JOB_NAMES), positions in the pixels of
+        map_dev.  -> numpy float64 [n, CY_FORCED_FIELDS] (lib.FORCED_NAMES)."""
+        MH, MW = self._image_2d(map_dev, "forced_fit")
+        if rms_dev is not None and (rms_dev.shape != map_dev.shape or self._image_2d(rms_dev, "forced_fit (rms_dev)") != (MH, MW)):
+            raise L.CyError("forced_fit: rms_dev must have the shape of the map")
+        jobs = np.ascontiguousarray(np.asarray(jobs, np.float64).reshape(-1, L.CY_FORCED_JOB_FIELDS))
+        n = jobs.shape[0]
+        out = np.zeros((n, L.CY_FORCED_FIELDS), np.float64)
+        dp = C.POINTER(C.c_double)
+        self._chk(self.lib.cy_forced_fit(self.ctx, self._p(map_dev), self._p(rms_dev) if rms_dev is not None else None, MH, MW,
+                                         jobs.ctypes.data_as(dp), n, float(nsigma), int(bool(fit_bkg)), out.ctypes.data_as(dp), self._stream()))
+        return out
+
+    def forced_kernel_ms(self):
+        """Kernel time of the last forced_fit call that launched in ms (hipEvents around the launch); -1 before the first."""
+        return self._kernel_ms(self.lib.cy_forced_kernel_ms)
+
     # ---- background and noise mesh (the global noise map of the measurement steps)
     def measure_background(self, img_dev, cell=128, k=3.0, niter=3):
         """Clipped median / MAD of every cell of the mesh over img_dev (as measure_sources takes it), cy_measure_background.

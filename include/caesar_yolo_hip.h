@@ -797,6 +797,61 @@ int cy_disc_residuals(cy_ctx* ctx, const float* d_map, const float* d_model /* o
 /* milliseconds the kernel of the last cy_disc_residuals call that launched one took (hipEvents around the launch); -1 before it */
 int cy_disc_residual_kernel_ms(const cy_ctx* ctx, double* out_ms);
 
+/* ---- forced photometry (an addition: linear fits of fixed shapes on any map) -----------------------------------------------
+ * The amplitude of a Gaussian of FIXED position and shape on d_map (device fp32 [MH][MW]), with an error, for every job: a
+ * weighted linear least-squares problem per job whose unknowns are the job's amplitude, the amplitudes of its overlapping
+ * neighbours and (fit_bkg) a local constant.  d_rms: a noise map of the same shape, or NULL (unit weights).  The chain gives it
+ * the components it rendered, on the detection image and on any co-registered map.  h_jobs: [n][CY_FORCED_JOB_FIELDS] {x0, y0, a,
+ * b, c, bkg}, positions in image pixels.  Image, valid pixel and pixel-centre conventions are those of cy_measure_sources; a
+ * usable rms r is finite and > 0.  Everything in float64, every product and sum rounded on its own (no contraction).
+ *   q            q = (a*u)*u + ((2*b)*u)*v + (c*v)*v, u = ix - x0, v = iy - y0: the expression of cy_render_gaussians
+ *   admissible   the five shape and position fields and bkg finite, a > 0, c > 0, a*c - b*b > 0 (cy_fit_components' rule without
+ *                the amplitude); otherwise status 1
+ *   rectangle    the support rectangle of cy_render_gaussians for (x0, y0, a, b, c) and nsigma, by the same code: half-widths
+ *                capped at CY_RND_HALF_MAX (status 2), status 3 when it misses the image; at most 514 x 514 pixels
+ *   runnable     a job of status 0 or 2
+ *   neighbours   of job k: the runnable jobs f != k whose clipped rectangle intersects k's, ordered by (D2, f), D2 = dx*dx + dy*dy
+ *                of the centres.  Walking that order, a candidate whose x0 y0 a b c compare equal to k's or to those of a
+ *                neighbour kept before it is dropped and counted in ndup (an exact duplicate would make the system singular);
+ *                otherwise it is kept while fewer than CY_FORCED_NEIGH_MAX = 7 are kept, and sets crowded = 1 when they are
+ *   unknowns     K = 1 + nneigh + fit_bkg <= 9, in this order: the job's amplitude, the neighbours' in kept order, the constant
+ *   pixel set    window pixel (ix, iy) of k's rectangle with q_k <= nsigma * nsigma (the product rounded once), a valid v and,
+ *                with d_rms, a usable rms.  A pixel inside the ellipse that fails the second or third test counts in nexcluded.
+ *                Neighbours contribute their wings on k's pixels whether or not the pixel lies inside their own ellipse
+ *   per pixel    s = 1 / (double)rms (1 without d_rms); w = (((double)v - bkg) * s, e_0 * s, .., e_nneigh * s, [s]) with
+ *                e_i = exp(-0.5 * q_i); the sums are the upper triangle of w^T w (at most 55): syy = w_0 w_0, b_i = w_0 w_{1+i},
+ *                N_ij = w_{1+i} w_{1+j}
+ *   ORDER        window pixel i = wy * W + wx sits on thread i mod 256; every sum runs sequentially per thread over increasing i,
+ *                then the block reduction of the measurement kernels (six steps with offsets 32 .. 1 inside a wave, then the four
+ *                waves in order).  Two calls give the same bytes
+ *   solve        npix < K: status 5.  Cholesky N = L L^T row by row: t = N_jj - L_j0^2 - .. - L_j,j-1^2 subtracted term by term in
+ *                increasing k; the pivot fails, and the status is 4, when !(t > N_jj * 2^-40) or t is not finite; L_ij = (N_ji -
+ *                sum_k<j L_ik L_jk) / L_jj likewise.  z = L^-1 b by forward and x = L^-T z by back substitution, X = L^-1 column by
+ *                column, C_ij = sum_k>=max(i,j) X_ki X_kj added in increasing k
+ *   chi2         a second sweep over the same pixel set in the same order: the sum of (w_0 - m)^2 with m = x_0 w_1, then
+ *                + x_i w_{1+i} in increasing i, every product rounded; not the cancelling syy - x.b
+ * Row i of h_out, CY_FORCED_FIELDS float64: [0] status (0 fitted, 1 not admissible, 2 fitted with a capped half-width, 3 the
+ * rectangle misses the image, 4 no positive pivot, 5 npix < K, an empty set included), [1] npix, [2] nexcluded, [3] K, [4] nneigh,
+ * [5] crowded, [6] ndup, [7] amp = x_0, [8] amp_var = C_00, [9] bkg_off (the constant), [10] bkg_var, [11] cov_amp_bkg (all three 0
+ * with fit_bkg == 0), [12] chi2, [13] syy, [14] n00 = N_00, [15] b0, [16] corr_max = the largest |C_0i| / sqrt(C_00 * C_ii) over the
+ * neighbours (0 without any), [17..20] wx0 wx1 wy0 wy1, [21] capped, [22] [23] 0.  Rows of status 1 and 3: the status, the window as
+ * -1 and zeros.  Rows of status 4 and 5: the counts, the sums and the window, zeros for the solution (fields 7 .. 12 and 16).
+ * One launch: one workgroup of 256 threads per runnable job, two sweeps over its window, pixel addresses formed in 64 bits.
+ * Synchronous on `stream`; needs no loaded weights; the maps are only read.  CY_ERR_ARG with a message (cy_last_error), nothing
+ * launched and h_out untouched, checked in this order: a null ctx or d_map; MH or MW <= 0; an image of 2^31 pixels or more; nsigma
+ * outside [1, 8] or NaN; fit_bkg not 0 or 1; n outside [0, CY_FORCED_JOBS_MAX]; with n > 0 a null h_jobs or h_out.  n == 0, or no
+ * runnable job: CY_OK, nothing launched, and cy_forced_kernel_ms keeps its value. */
+#define CY_FORCED_JOB_FIELDS 6   /* x0 y0 a b c bkg */
+#define CY_FORCED_FIELDS 24      /* status npix nexcluded K nneigh crowded ndup amp amp_var bkg_off bkg_var cov_amp_bkg chi2 syy n00 b0
+                                    corr_max wx0 wx1 wy0 wy1 capped 0 0 */
+#define CY_FORCED_NEIGH_MAX 7
+#define CY_FORCED_JOBS_MAX (1 << 20)
+int cy_forced_fit(cy_ctx* ctx, const float* d_map, const float* d_rms /* or NULL */, int MH, int MW,
+                  const double* h_jobs /* [n][CY_FORCED_JOB_FIELDS] */, int n, double nsigma, int fit_bkg,
+                  double* h_out /* [n][CY_FORCED_FIELDS] */, void* stream);
+/* milliseconds the kernel of the last cy_forced_fit call that launched one took (hipEvents around the launch); -1 before it */
+int cy_forced_kernel_ms(const cy_ctx* ctx, double* out_ms);
+
 /* ---- background and noise mesh (an addition: a global noise map for the measurement steps) ---------------------------------
  * Iteratively clipped median and MAD of every cell of a mesh over the resident image d_img [MH][MW].  Image, validity of a pixel
  * and pixel-centre convention are those of cy_measure_sources.

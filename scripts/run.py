@@ -89,6 +89,17 @@ Differences that come with the MI355X engine:
              on the second residual in both signs, and every source res_npeaks_left and res_nholes_left.  With
              --save_residual_maps the peak model and the second residual are written as peakmodel_<catalog name>.fits and
              resid2_<catalog name>.fits (cy_render_gaussians, cy_disc_residuals; DESIGN.md "Second residual").
+  --forced_fit  (new; implies --residual_map) forced photometry: every component of the model map is measured again with its
+             fitted position and shape fixed; only its amplitude, those of its overlapping neighbours (at most seven) and a local
+             constant (--forced_fit_bkg 1, the default) are solved, a weighted linear least-squares problem per component on the
+             pixels within --forced_nsigma (default 3) sigma, with the rms map of --bkg_map as weights when there is one.  Every
+             rendered component gains "forced": one dict per measured map with image, status, npix, nneigh, crowded, peak,
+             peak_err, bkg, chi2, corr_max, flux, flux_err (cy_forced_fit; DESIGN.md "Forced photometry").
+  --forced_images a.fits,b.fits  (new; implies --forced_fit) co-registered maps of the image's shape (another frequency, epoch or
+             Stokes plane) measured the same way after the image itself ("self"), each with its own background mesh, beam and
+             frequency; a map of another shape ends the run before detection.  The catalog file gains "forced_images" (tag, path,
+             freq, beam_area, mesh_ndef per map) and, when two maps carry a frequency, every component forced_alpha,
+             forced_alpha_err and forced_alpha_n.
 """
 import argparse
 import logging
@@ -250,7 +261,19 @@ def parse_args(argv=None):
                    help='entries closer than this times the larger of their disc radii are fitted together, in (0, 2] (with --fit_peak_groups)')
     p.add_argument('--subtract_peaks', dest='subtract_peaks', action='store_true',
                    help='subtract the fitted peaks from the residual map, measure every fit on that second residual and search it again in both signs (implies --fit_peaks)')
+    p.add_argument('--forced_fit', dest='forced_fit', action='store_true',
+                   help='forced photometry: the amplitude of every rendered component with its fitted position and shape fixed, on the image itself (implies --residual_map)')
+    p.add_argument('--forced_images', dest='forced_images', type=str, default='',
+                   help='comma-separated FITS maps of the same field and shape that are measured the same way (implies --forced_fit)')
+    p.add_argument('--forced_nsigma', dest='forced_nsigma', type=float, default=3.0,
+                   help='the pixels of a forced fit lie within this many sigma of the component, in [1, 8] (with --forced_fit)')
+    p.add_argument('--forced_fit_bkg', dest='forced_fit_bkg', type=int, default=1, choices=(0, 1),
+                   help='1: a local constant is fitted beside the amplitudes; 0: the background is the one given (with --forced_fit)')
     args = p.parse_args(argv)
+    if args.forced_images:
+        args.forced_fit = True
+    if args.forced_fit and not 1.0 <= args.forced_nsigma <= 8.0:
+        p.error("--forced_nsigma must be in [1, 8]")
     if args.subtract_peaks:
         args.fit_peaks = True                                 # what is subtracted are the fits
     if args.fit_peak_groups:
@@ -365,7 +388,7 @@ MEASURE_KEYS = ('measure_sources', 'measure_ring', 'measure_islands', 'island_se
                 'residual_holes', 'residual_scales', 'residual_scale_first', 'residual_scales_sigma', 'save_scale_maps',
                 'peak_apertures', 'aperture_unit', 'aperture_radii', 'aperture_annulus',
                 'fit_peaks', 'fit_peaks_radius', 'fit_peaks_sigma', 'fit_peaks_max_iter', 'fit_peak_groups', 'fit_peaks_link',
-                'subtract_peaks')
+                'subtract_peaks', 'forced_fit', 'forced_images', 'forced_nsigma', 'forced_fit_bkg')
 
 
 def measure_config(args):

@@ -38,6 +38,9 @@ Unless --no-subtract (or --no-peakgroups, ..) is given there is a variant `subtr
 (subtract_ms, subtract_render_kernel_ms, disc_residual_kernel_ms summed over the calls, left_peaks_kernel_ms of the two searches beside
 peakgroup_kernel_ms of the same runs, the numbers of selected, rendered, wandered and duplicate components and of the entries of the
 two left lists); subtract_added_ms is its run time over that of the `peakgroups` variant of the same runs.
+Unless --no-forced (or --no-residual, ..) is given there is a variant `forced`, the flags of `residual` plus --forced_fit (forced_ms,
+forced_kernel_ms beside residual_ms and render_kernel_ms of the same runs, the numbers of maps, jobs, fitted, crowded and singular
+ones); forced_added_ms is its run time over that of the `residual` variant of the same runs.
 --only a,b keeps the named variants (and `off`) and drops the others.
 Unless --no-blend (or --no-fit) is given there is a variant --fit_blends (blend_ms, blend_kernel_ms, the number of joint jobs, their
 iterations and the groups above the member limit).  Unless --no-fit (or --no-deblend) is given there is a variant --fit_components (fit_ms, fit_kernel_ms, the number of fitted jobs and
@@ -146,6 +149,7 @@ def main():
     ap.add_argument("--no-peakfits", action="store_true")
     ap.add_argument("--no-peakgroups", action="store_true")
     ap.add_argument("--no-subtract", action="store_true")
+    ap.add_argument("--no-forced", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated variants to keep beside `off`")
     ap.add_argument("--host-ref", action="store_true")
     args = ap.parse_args()
@@ -217,6 +221,8 @@ def main():
                                    "left_peaks_kernel_ms"),
                                   ("peakfit_jobs", "subtract_selected", "subtract_rendered", "subtract_wandered", "subtract_duplicates", "left_peaks",
                                    "left_holes", "left_truncated")),
+                     "forced": (["--fit_blends", "--residual_map", "--forced_fit"], ("residual_ms", "render_kernel_ms", "forced_ms", "forced_kernel_ms"),
+                                ("residual_rendered", "forced_maps", "forced_jobs", "forced_fitted", "forced_crowded", "forced_singular")),
                      "islands": (["--measure_islands"], ("islands_ms", "islands_kernel_ms"), ())}
             skip = {"bkg": args.no_bkg, "deblend": args.no_deblend, "fit": args.no_deblend or args.no_fit,
                     "blend": args.no_deblend or args.no_fit or args.no_blend,
@@ -230,6 +236,7 @@ def main():
                                    args.no_peakfits or args.no_peakgroups),
                     "subtract": (args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_scales or args.no_apertures or
                                  args.no_peakfits or args.no_peakgroups or args.no_subtract),
+                    "forced": args.no_deblend or args.no_fit or args.no_blend or args.no_residual or args.no_forced,
                     "islands": args.no_islands}
             if args.only:
                 skip.update({name: True for name in table if name not in args.only.split(",")})
@@ -271,6 +278,8 @@ def main():
                 res["peakgroups_added_ms"] = res["peakgroups"]["run_ms_median"] - res["peakfits"]["run_ms_median"]
             if "subtract" in got and "peakgroups" in got:
                 res["subtract_added_ms"] = res["subtract"]["run_ms_median"] - res["peakgroups"]["run_ms_median"]
+            if "forced" in got and "residual" in got:
+                res["forced_added_ms"] = res["forced"]["run_ms_median"] - res["residual"]["run_ms_median"]
             if "scales" in got:
                 res["atrous_levels"] = atrous_levels(img, args.runs)
             if "bkg" in got:
